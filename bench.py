@@ -38,12 +38,14 @@ sys.path.insert(0, str(ROOT / "tests"))
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
 SEED = 0xA11CE5EED00
+DUMP_MAX_RECORDS = 1 << 20  # --dump-outputs: 28 B per sampled record (i, j, kind as f64, dist as f32) -> 28 MB at most
+DUMP_SEED = 0xD0A9
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps of the headline workload (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--atoms", type=int, default=1_000_000)
     ap.add_argument("--workload", choices=["s2", "s1", "batch5k"], default="s2")
@@ -60,7 +62,13 @@ def parse():
                          "auto = the engine's memo (a sample of the previous call's atoms), which is what a caller gets")
     ap.add_argument("--contacts-only", action="store_true",
                     help="informational: ARP_FLAG_CONTACTS_ONLY (what the table path runs); `value` then counts emitted contacts, not the headline metric")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the records the LAST timed headline step emitted as DIR/<name>.npy (rank 0): sorted by (i, j), "
+                         f"a fixed seeded sample of at most {DUMP_MAX_RECORDS} of them, for comparing two builds output for output")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    return a
 
 
 def to_device(soa, torch, dev):
@@ -137,14 +145,31 @@ def record_hash_device(torch, out, n) -> int:
     return total
 
 
+def dump_records(torch, np, out, n) -> dict:
+    """--dump-outputs: the records out[0:n] (int32 [n, 4] = i, j, distance bits, kind) the way a caller receives them from the pair path
+    (arpeggia_amd.api.PAIR_DTYPE), in a canonical order -- the single-pass emitter's slot order differs run to run -- and, beyond
+    DUMP_MAX_RECORDS, a sample at positions that depend only on n and DUMP_SEED.  i, j and kind are exact in f64; dist stays f32."""
+    r = out[:n].to(torch.int64) & 0xFFFFFFFF
+    order = torch.sort((r[:, 2] << 32) | r[:, 3], stable=True).indices  # (ties of (i, j) never occur; sorted fully anyway)
+    order = order[torch.sort((r[order, 0] << 32) | r[order, 1], stable=True).indices]
+    if n > DUMP_MAX_RECORDS:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_RECORDS, replace=False, shuffle=False))
+        order = order[torch.from_numpy(pos).to(order.device)]
+    rec = out[order].cpu().numpy()
+    u = rec.view(np.uint32)
+    return {"pairs_i": u[:, 0].astype(np.float64), "pairs_j": u[:, 1].astype(np.float64), "pairs_dist": np.ascontiguousarray(rec[:, 2]).view(np.float32),
+            "pairs_kind": u[:, 3].astype(np.float64), "pairs_count": np.asarray([n], dtype=np.float64)}
+
+
 LAST: dict = {}  # what the most recent measure_resident() saw besides its return values: first_call_ms, pair_hash
 WANT_HASH = False  # set by main() when the CPU-baseline leg will compare the records (the hash runs torch kernels: kept out of profiler runs)
 
 
-def measure_resident(aa, _lib, torch, dev, dev_index, soa, prm, steps, warmup, profile_steps, barrier, check=True):
+def measure_resident(aa, _lib, torch, dev, dev_index, soa, prm, steps, warmup, profile_steps, barrier, check=True, dump=False):
     """`steps` passes over one device-resident SoA: (wall seconds over the steps, device ms per step, pairs, per-kernel ms).
     LAST receives the device time of the FIRST pass on these arrays (no memo yet: the probe pass is launched, the kernels are the
-    default ones) and, after the timed steps, the order-independent hash of the emitted records."""
+    default ones) and, after the timed steps, the order-independent hash of the emitted records (and with dump=True the records
+    themselves, dump_records)."""
     dsoa = to_device(soa, torch, dev)
     keep = []
     atoms = aa.atoms_from_arrays(dsoa, location=_lib.ARP_MEM_DEVICE, keep=keep)
@@ -181,6 +206,10 @@ def measure_resident(aa, _lib, torch, dev, dev_index, soa, prm, steps, warmup, p
     dev_ms = ev0.elapsed_time(ev1) / steps
     if WANT_HASH:
         LAST["pair_hash"] = record_hash_device(torch, out, got)  # what the LAST timed step left in the buffer
+    if dump:  # (before the profile passes below overwrite the buffer)
+        import numpy as np
+
+        LAST["dump"] = dump_records(torch, np, out, got)
     # per-kernel durations (HIP events on the same stream, separate pass so they do not perturb the timed region)
     acc: dict = {}
     if profile_steps:
@@ -383,6 +412,7 @@ def main():
     prm = aa.default_params(0.1, 6.5, deterministic=args.deterministic, contacts_only=args.contacts_only,
                             residue_runs={"auto": None, "on": True, "off": False}[args.residue_runs])
     check = not args.no_check
+    dump = args.dump_outputs is not None and rank == 0
 
     recs = {}  # (workload, atoms) -> the generated records (the SAP leg reuses the S1 clouds)
 
@@ -416,7 +446,8 @@ def main():
         n_pairs = n_atoms = 0
         acc: dict = {}
         for p in packs:  # (one pack unless a rank holds more than 60000 structures)
-            w, d, npair, a, na = measure_resident(aa, _lib, torch, dev, dev_index, p, prm, args.steps, args.warmup, args.profile_steps, barrier, check)
+            w, d, npair, a, na = measure_resident(aa, _lib, torch, dev, dev_index, p, prm, args.steps, args.warmup, args.profile_steps, barrier, check,
+                                                  dump=dump)
             wall += w; dev_ms += d; n_pairs += npair; n_atoms += na
             head = dict(LAST)
             for k, v in a.items():
@@ -426,7 +457,7 @@ def main():
         scaling = "strong" if args.structures else "weak"
     else:
         wall, dev_ms, n_pairs, acc, n_atoms = measure_resident(aa, _lib, torch, dev, dev_index, cloud(args.workload), prm, args.steps, args.warmup,
-                                                                args.profile_steps, barrier, check)
+                                                                args.profile_steps, barrier, check, dump=dump)
         label = f"{args.workload.upper()} synthetic {n_atoms}-atom cloud per GPU (tests/synth.py gen_{args.workload})"
         head = dict(LAST)
         if rank == 0 and not args.no_extras and not args.deterministic:  # informational: two independent calls in flight on two streams
@@ -593,6 +624,12 @@ def main():
             line["cpu_baseline"] = cpu_baseline(args.cpu_sample_atoms, wl, SEED + (4 if wl == "s2" else 3) if same else 0xBA5E,
                                                 n_pairs if same and not args.contacts_only else None, head.get("pair_hash") if same and not args.contacts_only else None)
         print(json.dumps(line), flush=True)
+        if dump:  # (one pack per rank unless it holds more than 60000 structures: then the last pack's records)
+            out_dir = Path(args.dump_outputs)
+            out_dir.mkdir(parents=True, exist_ok=True)
+            for name, arr in head["dump"].items():
+                np.save(out_dir / f"{name}.npy", arr)
+            print(f"bench.py: {len(head['dump']['pairs_i'])} of {n_pairs} records of the last timed step -> {out_dir}/", file=sys.stderr, flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
