@@ -66,9 +66,9 @@ DEVFN unsigned long long compact_round(uint32_t &mask, uint32_t home_slot, uint3
     uint32_t t, lz, slot, bm;
     asm volatile(
         "v_cmp_ne_u32 vcc, 0, %[mask]\n\t"
+        "v_ffbh_u32 %[lz], %[mask]\n\t"  // (here: v_mbcnt_lo reads vcc as a constant, one wait state after the compare -- tests/test_isa_hazards.py)
         "v_mbcnt_lo_u32_b32 %[t], vcc_lo, 0\n\t"
         "v_mbcnt_hi_u32_b32 %[t], vcc_hi, %[t]\n\t"
-        "v_ffbh_u32 %[lz], %[mask]\n\t"
         "v_lshl_add_u32 %[t], %[t], 3, %[qaddr]\n\t"
         "v_add_u32 %[slot], %[nb], %[lz]\n\t"
         "v_lshrrev_b32 %[bm], %[lz], %[top]\n\t"

@@ -151,7 +151,8 @@ DEVFN void compact_rounds_res_e(uint32_t &mask, uint32_t tag, uint32_t &qbyte, u
         "v_cmp_lt_u32_e32 vcc, 2, %[d]\n\t"
         // (gfx9 hazard, "mixed use of VCC": a VALU instruction that reads vcc as a CONSTANT needs one wait state after the VALU compare that
         // wrote it, and nothing inserts it inside inline assembly -- v_mbcnt_lo right behind the compare ranked the lanes on the previous
-        // round's mask.  The plain rounds get their wait state from the branch between v_cmpx and v_mbcnt_lo.)
+        // round's mask.  The plain rounds get their wait state from the branch between v_cmpx and v_mbcnt_lo.  tests/test_isa_hazards.py checks
+        // every such pair at the edges of the kernels' inline assembly.)
         "ds_read_b32 %[kn], %[ka]\n\t"
         "s_bcnt1_i32_b64 %[c], vcc\n\t"
         "v_mbcnt_lo_u32_b32 %[t], vcc_lo, 0\n\t"
@@ -219,11 +220,17 @@ DEVFN uint32_t lm_count(lmask m) {  // (as asm: the builtin popcount of an asm-p
     asm("s_bcnt1_i32_b64 %0, %1" : "=s"(c) : "s"(m) : "scc");
     return c;
 }
-// one 16-byte non-temporal record store per lane of m: scalar base + 32-bit lane offset (store_record, pairs.inl)
-DEVFN void lm_store_records(lmask m, uint4 *base, uint32_t byte_off, const u32x4 &rec) {
+// one 16-byte record store per lane of m: scalar base + 32-bit lane offset.  NT: non-temporal, the final list (store_record, pairs.inl); plain
+// (cached): the staged records, which are read again.  The caller makes the base scalar well ahead of the call: a VALU write of an SGPR
+// (readfirstlane) needs 5 wait states before the store reads it, and nothing pads them inside the string (tests/test_isa_hazards.py).
+template <bool NT>
+DEVFN void lm_store_records(lmask m, const uint4 *base, uint32_t byte_off, const u32x4 &rec) {
     lmask save;
-    asm volatile("s_and_saveexec_b64 %0, %1\n\tglobal_store_dwordx4 %2, %3, %4 nt\n\ts_mov_b64 exec, %0"
-                 : "=&s"(save) : "s"(m), "v"(byte_off), "v"(rec), "s"(base) : "memory");
+#define ARP_STORE(HINT) asm volatile("s_and_saveexec_b64 %0, %1\n\tglobal_store_dwordx4 %2, %3, %4" HINT "\n\ts_mov_b64 exec, %0" \
+                                     : "=&s"(save) : "s"(m), "v"(byte_off), "v"(rec), "s"(base) : "memory")
+    if constexpr (NT) ARP_STORE(" nt");
+    else ARP_STORE("");
+#undef ARP_STORE
 }
 
 // The block allocator's common case without the compiler's help (round 3's form cost ~25 scalar instructions per batch: 64-bit
@@ -241,7 +248,7 @@ DEVFN unsigned long long u64_of(const u32x2 &v) { return ((unsigned long long)v.
 DEVFN void store_batch_general(const Slots &sl, lmask m_valid, uint32_t n_rec, uint32_t rank, const u32x4 &rec, const EmitTarget &tg, unsigned long long *result,
                                uint32_t lane) {
     if (sl.n0 == n_rec && sl.pos0 + n_rec <= tg.capacity) {
-        lm_store_records(m_valid, reinterpret_cast<uint4 *>(tg.out) + sl.pos0, rank << 4, rec);
+        lm_store_records<true>(m_valid, reinterpret_cast<uint4 *>(tg.out) + sl.pos0, rank << 4, rec);
     } else if (lm_lane(m_valid, lane)) {
         uint4 *d = emit_slot(tg, rank < sl.n0 ? sl.pos0 + rank : sl.pos1 + (rank - sl.n0), result);
         if (d) store_record(d, make_uint4(rec.x, rec.y, rec.z, rec.w));
@@ -298,16 +305,6 @@ DEVFN void stage_flush_g(StageRef &sg, const EmitTarget &tg, unsigned long long 
     const Slots sl = alloc_direct(&result[2], n, lane);
     stage_copy_g(sg.buf, n, sl.pos0, tg, lane);
     sg.n = 0u;
-}
-// one plain (cached) 16-byte record store per lane of m: scalar base + 32-bit lane offset -- the staged records are read again (lm_store_records: nt)
-DEVFN void lm_store_records_cached(lmask m, uint4 *base_v, uint32_t byte_off, const u32x4 &rec) {
-    lmask save;
-    // (the wave's region: wave-uniform by construction, but derived from threadIdx -- say so, the store wants its base in a scalar register pair)
-    const uintptr_t bv = (uintptr_t)base_v;
-    // (the builtin returns int: without the casts the low half is SIGN-extended into the high one -- a region above a 2 GB boundary then faults)
-    uint4 *base = (uint4 *)(((uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(bv >> 32)) << 32) | (uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)bv));
-    asm volatile("s_and_saveexec_b64 %0, %1\n\tglobal_store_dwordx4 %2, %3, %4\n\ts_mov_b64 exec, %0"
-                 : "=&s"(save) : "s"(m), "v"(byte_off), "v"(rec), "s"(base) : "memory");
 }
 DEVFN void stage_flush_e(StageRef &sg, const EmitTarget &tg, unsigned long long *result, uint32_t lane) {
     const uint32_t n = __builtin_amdgcn_readfirstlane(sg.n);
@@ -475,7 +472,7 @@ DEVFN void exact_finish_e(const ExactRegs &g, const ConstsE &K, const TablesE &t
         if (ONLY) { if (n_rec == 0u) return; }
         if constexpr (STAGE) {  // the wave's own region: the next n_rec places, no allocator at all
             if (__builtin_expect(sg.n + n_rec > kWaveStageRecords, 0)) stage_flush_g(sg, tg, result, lane);
-            lm_store_records_cached(m_valid, sg.buf, (sg.n + lm_rank(m_valid)) << 4, rec);
+            lm_store_records<false>(m_valid, sg.buf, (sg.n + lm_rank(m_valid)) << 4, rec);
             sg.n += n_rec;
             return;
         }
@@ -640,7 +637,10 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == kEWaves ? kEWavesPerSimd : 2) 
     WaveLdsE &w = wl[wave].e;
     uint32_t nkey_lds = 0;  // RES: LDS byte address of the staged chunk's residue words
     if constexpr (RES) nkey_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)wl[wave].nkey);
-    StageRef sg{STAGE ? reinterpret_cast<uint4 *>(tg.scratch) + (size_t)(blockIdx.x * (uint32_t)WAVES + wave) * kWaveStageRecords : stg.rec[DIRECT ? wave : 0u], 0u};
+    // STAGE: the wave's region, made scalar here once (the record stores take it as their base: lm_store_records); the readfirstlane is of the wave's
+    // index, zero-extended before the 64-bit arithmetic (the builtin returns int)
+    StageRef sg{STAGE ? reinterpret_cast<uint4 *>(tg.scratch) + (size_t)(blockIdx.x * (uint32_t)WAVES + (uint32_t)__builtin_amdgcn_readfirstlane(wave)) * kWaveStageRecords
+                      : stg.rec[DIRECT ? wave : 0u], 0u};
     const ProbeParamsE pe{dprm->s_clash, dprm->s_cov, tb.s_vdw, dprm->s_hacc, K.s_ion, K.s_polar, K.s_hphob};
     // task distribution as in k_pairs: block group (b mod 8) = one XCD = one contiguous eighth of the tasks, static first task per wave
     const uint32_t n_groups = min(8u, gridDim.x), group = blockIdx.x % n_groups;
