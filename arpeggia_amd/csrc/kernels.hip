@@ -96,15 +96,26 @@ DEVFN int orient_all_both(const Fat &a, const Fat &b) {
     return valid ? (kb < ka ? 2 : 1) : 0;
 }
 
-DEVFN double angle_deg(const double a[3], const double b[3], const double c[3]) {
-    // pdbtbx Atom::angle: angle at b between b->a and b->c, degrees
+// Angle rules decided on the cosine quotient q = dot / (|u| |v|), never on the device's acos: the reference compares
+// rn(rn(acos q) * 180/pi) with a threshold using the C library's acos (Rust std on Linux), and the device acos rounds differently
+// within an ulp or so of 90 degrees (measured: a hydrogen bond at q ~ 1e-16 lost).  rn(acos(.)) is monotone, so "angle >= T" is
+// "q <= Q(T)" with Q(T) the largest q of [-1, 1] the host's acos still maps to >= T, and "angle <= T" is "q >= the smallest such q".
+// The four constants were found by bisection over the doubles with the host's acos; tests/test_edge_rules.py re-derives them.
+// q outside [-1, 1] or NaN (a zero-length vector: 0/0) makes acos NaN and every comparison false, here as there.
+constexpr double kCosHbond = 0x1.8d313198a2e03p-53;       // largest q with angle >= 90   (hbond.rs:55)
+constexpr double kCosWeakHbond = -0x1.491b7523c161cp-1;   // largest q with angle >= 130  (hbond.rs:99)
+constexpr double kCosDisulfideLo = 0x1p-1;                 // largest q with |dihedral| >= 60   (vdw.rs:78)
+constexpr double kCosDisulfideHi = -0x1.fffffffffffffp-2;  // smallest q with |dihedral| <= 120 (vdw.rs:78)
+
+DEVFN double angle_cos(const double a[3], const double b[3], const double c[3]) {
+    // pdbtbx Atom::angle before the acos: angle at b between b->a and b->c
     double ba[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]}, bc[3] = {c[0] - b[0], c[1] - b[1], c[2] - b[2]};
     double nba = sqrt(0.0 + ba[0] * ba[0] + ba[1] * ba[1] + ba[2] * ba[2]);
     double nbc = sqrt(0.0 + bc[0] * bc[0] + bc[1] * bc[1] + bc[2] * bc[2]);
     double dot = 0.0 + ba[0] * bc[0] + ba[1] * bc[1] + ba[2] * bc[2];
-    return acos(dot / (nba * nbc)) * (180.0 / 3.14159265358979323846264338327950288);
+    return dot / (nba * nbc);
 }
-DEVFN double dihedral_deg(const double a[3], const double b[3], const double c[3], const double d[3]) {
+DEVFN double dihedral_cos(const double a[3], const double b[3], const double c[3], const double d[3]) {
     double ba[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]}, bc[3] = {c[0] - b[0], c[1] - b[1], c[2] - b[2]};
     double cb[3] = {b[0] - c[0], b[1] - c[1], b[2] - c[2]}, cd[3] = {d[0] - c[0], d[1] - c[1], d[2] - c[2]};
     double n1[3] = {ba[1] * bc[2] - ba[2] * bc[1], ba[2] * bc[0] - ba[0] * bc[2], ba[0] * bc[1] - ba[1] * bc[0]};
@@ -112,13 +123,13 @@ DEVFN double dihedral_deg(const double a[3], const double b[3], const double c[3
     double a1 = sqrt(0.0 + n1[0] * n1[0] + n1[1] * n1[1] + n1[2] * n1[2]);
     double a2 = sqrt(0.0 + n2[0] * n2[0] + n2[1] * n2[1] + n2[2] * n2[2]);
     double dot = 0.0 + n1[0] * n2[0] + n1[1] * n2[1] + n1[2] * n2[2];
-    return acos(dot / (a1 * a2)) * (180.0 / 3.14159265358979323846264338327950288);
+    return dot / (a1 * a2);
 }
 
 // hbond.rs:36-63 / 80-107: the hydrogen probe, out of line -- it runs only for donor residues that really carry hydrogens.
 __device__ __noinline__ int hydrogen_probe(const double *X, const double *Y, const double *Z, const uint32_t *res_h_idx, double lim,
                                            uint32_t p0, uint32_t p1, double dx, double dy, double dz, double ax, double ay, double az,
-                                           double min_angle) {
+                                           double max_cos) {
     const double pd[3] = {dx, dy, dz}, pa[3] = {ax, ay, az};
     // four hydrogens per trip: index loads, then twelve coordinate loads in flight together -- one by one the loop is a chain
     // of dependent round trips (index -> coordinates) per hydrogen.  "Some hydrogen qualifies" does not depend on the order.
@@ -133,7 +144,7 @@ __device__ __noinline__ int hydrogen_probe(const double *X, const double *Y, con
 #pragma unroll
         for (uint32_t u = 0; u < 4u; u++) {
             const double ph[3] = {hx[u], hy[u], hz[u]};
-            if (p + u < p1 && sq_dist(ph[0], ph[1], ph[2], pa[0], pa[1], pa[2]) < lim) hit = hit || (angle_deg(pd, ph, pa) >= min_angle);
+            if (p + u < p1 && sq_dist(ph[0], ph[1], ph[2], pa[0], pa[1], pa[2]) < lim) { const double q = angle_cos(pd, ph, pa); hit = hit || ((q >= -1.0) & (q <= max_cos)); }
         }
         if (hit) return 1;
     }
@@ -150,8 +161,8 @@ __device__ __noinline__ int disulfide_probe(const double *X, const double *Y, co
         return 0;
     }
     const double a[3] = {X[cb1], Y[cb1], Z[cb1]}, b[3] = {X[s1], Y[s1], Z[s1]}, c[3] = {X[s2], Y[s2], Z[s2]}, d[3] = {X[cb2], Y[cb2], Z[cb2]};
-    double dih = fabs(dihedral_deg(a, b, c, d));
-    return (dih >= 60.0) && (dih <= 120.0);
+    const double q = dihedral_cos(a, b, c, d);  // (|dihedral| = acos(q) * 180/pi: the fabs changes nothing)
+    return (q >= kCosDisulfideHi) && (q <= kCosDisulfideLo);
 }
 
 constexpr uint32_t kDeferKind = 0xFFFFFFFFu;  // classify<false>: the pair needs a hydrogen / disulfide probe, decide it in the deferred pass
@@ -160,13 +171,13 @@ constexpr uint32_t kDeferKind = 0xFFFFFFFFu;  // classify<false>: the pair needs
 // residue satisfies the distance and angle conditions.  Only called for donors whose residue carries hydrogens.
 // (P: LdsParams, or ProbeParamsE of the small-input emit kernels -- anything with the bounds as members)
 template <typename P>
-DEVFN bool hbond_probe(const DevAtoms &in, const P &prm, bool donor_is_a, const Fat &a, const Fat &b, double min_angle) {
+DEVFN bool hbond_probe(const DevAtoms &in, const P &prm, bool donor_is_a, const Fat &a, const Fat &b, double max_cos) {
     const uint32_t res = in.res_id[donor_is_a ? a.orig : b.orig];
     const uint2 hi = make_uint2(in.res_h_ptr[res], in.res_h_ptr[res + 1]);
     const uint32_t acc_attr = donor_is_a ? b.attr : a.attr;
     const double dx = donor_is_a ? a.x : b.x, dy = donor_is_a ? a.y : b.y, dz = donor_is_a ? a.z : b.z;
     const double ax = donor_is_a ? b.x : a.x, ay = donor_is_a ? b.y : a.y, az = donor_is_a ? b.z : a.z;
-    return hydrogen_probe(in.x, in.y, in.z, in.res_h_idx, prm.s_hacc[acc_attr & ARP_ATTR_ELEM_MASK], hi.x, hi.y, dx, dy, dz, ax, ay, az, min_angle) != 0;
+    return hydrogen_probe(in.x, in.y, in.z, in.res_h_idx, prm.s_hacc[acc_attr & ARP_ATTR_ELEM_MASK], hi.x, hi.y, dx, dy, dz, ax, ay, az, max_cos) != 0;
 }
 
 // All rows of one candidate pair as a bit set (complex.rs:217-296).  The rules are symmetric in the two atoms except for
@@ -192,8 +203,8 @@ DEVFN uint32_t classify(const DevAtoms &in, const P &prm, double s, const Fat &a
     if (!clash && (need_hs | need_hw | need_ss)) {                                     // rare
         if (!PROBES) return kDeferKind;
         if (need_ss) ss = disulfide_probe(in.x, in.y, in.z, in.res_id, in.res_cb, in.res_sg, swap ? b.orig : a.orig, swap ? a.orig : b.orig, result);
-        if (need_hs) hb2 = hbond_probe(in, prm, sd_a, a, b, 90.0);
-        if (need_hw) wk2 = hbond_probe(in, prm, wd_a, a, b, 130.0);
+        if (need_hs) hb2 = hbond_probe(in, prm, sd_a, a, b, kCosHbond);
+        if (need_hw) wk2 = hbond_probe(in, prm, wd_a, a, b, kCosWeakHbond);
     }
     const bool ionic = near4 & ((((aa >> 7) & (ab >> 8)) | ((ab >> 7) & (aa >> 8))) & 1u);     // ionic.rs:11-22,37-57
     const bool repel = near4 & (((both >> 7) | (both >> 8)) & 1u);                              // ionic.rs:25-35,59-81
