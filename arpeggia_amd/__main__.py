@@ -1,6 +1,6 @@
 """Command-line driver: `python -m arpeggia_amd contacts -i model.pdb -o out/` -- the flags and defaults of the reference's
-`arpeggia contacts` (src/cli/contacts.rs:9-52) over the MI355X engine.  Only the `contacts` subcommand exists here (the
-one hot path this repository replaces); it writes <output>/<filename>.<format> like cli/contacts.rs:108-137.
+`arpeggia contacts` (src/cli/contacts.rs:9-52) over the MI355X engine; it writes <output>/<filename>.<format> like cli/contacts.rs:108-137.
+`sasa`, `sap` and `dsasa` take the flags and defaults of src/cli/{sasa,sap,dsasa}.rs (sasa at level "atom" only: see arpeggia_amd/api.py).
 """
 from __future__ import annotations
 
@@ -28,7 +28,71 @@ def build_parser() -> argparse.ArgumentParser:
     c.add_argument("-d", "--dist-cutoff", default=6.5, type=float, help="Distance cutoff when searching for neighboring atoms")
     c.add_argument("-j", "--num-threads", default=1, type=int, help="Host threads of the table path (0 = all cores); the search runs on the GPU")
     c.add_argument("--ignore-zero-occupancy", action="store_true", help="Ignore atoms with zero occupancy")
+    common = dict(model=("-m", "--model", 0, int, "Model number to analyze (0: the first model)"),
+                  probe=("-r", "--probe-radius", 1.4, float, "Probe radius in Angstroms"),
+                  points=("-n", "--num-points", 100, int, "Number of points for surface calculation"),
+                  threads=("-j", "--num-threads", 1, int, "Number of threads (accepted; the computation runs on the GPU)"))
+
+    def add(p, *keys):
+        for k in keys:
+            short, long_, default, typ, hlp = common[k]
+            p.add_argument(short, long_, default=default, type=typ, help=hlp, dest={"model": "model_num", "points": "n_points"}.get(k))
+
+    a = sub.add_parser("sasa", help="solvent accessible surface area per atom (cli/sasa.rs)")
+    a.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file to be analyzed")
+    a.add_argument("-o", "--output", required=True, type=Path, help="Output directory")
+    a.add_argument("-f", "--filename", default="sasa", help="Name of the output file")
+    a.add_argument("-t", "--output-format", default="csv", type=str.lower, choices=FORMATS, help="Output file type")
+    add(a, "model", "probe", "points", "threads")
+    a.add_argument("-l", "--level", default="atom", type=str.lower, choices=("atom", "residue", "chain"), help="Aggregation level (only atom is available)")
+    a.add_argument("-c", "--chains", default="", help="Comma-separated chain IDs to include (empty: all)")
+    p = sub.add_parser("sap", help="spatial aggregation propensity per atom or residue (cli/sap.rs)")
+    p.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file to be analyzed")
+    p.add_argument("-o", "--output", required=True, type=Path, help="Output directory")
+    p.add_argument("-f", "--filename", default="sap", help="Name of the output file")
+    p.add_argument("-t", "--output-format", default="csv", type=str.lower, choices=FORMATS, help="Output file type")
+    add(p, "model", "probe", "points")
+    p.add_argument("-s", "--sap-radius", default=5.0, type=float, help="Radius in Angstroms for the neighbour search")
+    add(p, "threads")
+    p.add_argument("-l", "--level", default="residue", type=str.lower, choices=("atom", "residue"), help="Aggregation level")
+    p.add_argument("-c", "--chains", default="", help="Comma-separated chain IDs to include (empty: all)")
+    d = sub.add_parser("dsasa", help="buried surface area between two chain groups (cli/dsasa.rs)")
+    d.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file to be analyzed")
+    d.add_argument("-g", "--groups", required=True, help="Chain groups, e.g. A,B/C,D")
+    add(d, "model", "probe", "points", "threads")
     return ap
+
+
+def run_surface(args) -> int:
+    """sasa / sap / dsasa (cli/sasa.rs, cli/sap.rs, cli/dsasa.rs)."""
+    import arpeggia_amd as aa
+
+    if not args.input.exists():
+        log.error("Failed to retrieve input file: %s", args.input)
+        return 1
+    s = aa.Structure.load(str(args.input.resolve()))
+    if args.command == "dsasa":
+        v = aa.get_dsasa(s, args.groups, args.probe_radius, args.n_points, args.model_num)
+        log.info("Buried surface area (dSASA) at the interface between chains [%s]: %.2f A^2", args.groups, v)
+        return 0
+    if args.command == "sasa":
+        if args.level != "atom":
+            log.error("sasa level '%s' is not available (the reference's rust-sasa radius table is not part of its tree); use --level atom", args.level)
+            return 2
+        table = aa.get_atom_sasa(s, args.probe_radius, args.n_points, args.model_num, True, args.chains)
+        what = "atoms"
+    else:
+        f = aa.get_per_atom_sap_score if args.level == "atom" else aa.get_per_residue_sap_score
+        table = f(s, args.probe_radius, args.n_points, args.model_num, args.sap_radius, args.chains)
+        what = "atoms" if args.level == "atom" else "residues"
+    if len(table) == 0:
+        log.error("No data found in the input file. Please check the provided arguments, especially the model number.")
+        return 1
+    args.output.mkdir(parents=True, exist_ok=True)
+    out = (args.output / args.filename).with_suffix("." + args.output_format)
+    write_table(table, out, args.output_format)
+    log.info("Results for %d %s saved to %s", len(table), what, out)
+    return 0
 
 
 def write_table(table, path: Path, fmt: str) -> None:
@@ -81,7 +145,7 @@ def run_contacts(args) -> int:
 def main(argv=None) -> int:
     logging.basicConfig(level=logging.INFO, format="%(levelname)s %(message)s", stream=sys.stderr)
     args = build_parser().parse_args(argv)
-    return run_contacts(args)
+    return run_contacts(args) if args.command == "contacts" else run_surface(args)
 
 
 if __name__ == "__main__":

@@ -21,6 +21,7 @@ ARP_FLAG_CONTACTS_ONLY = 0x2
 ARP_FLAG_NO_SPECULATION = 0x4
 ARP_FLAG_RESIDUE_RUNS = 0x8
 ARP_FLAG_NO_RESIDUE_RUNS = 0x10
+ARP_SASA_MAX_POINTS = 4096
 
 ATTR = dict(
     ELEM_MASK=0xF, DONOR=0x10, ACCEPTOR=0x20, WEAK_DONOR=0x40, POS=0x80, NEG=0x100, HYDROPHOBIC=0x200, CYS_SG=0x400,
@@ -139,6 +140,15 @@ def _load():
         "arp_release_host_pool": (C.c_uint64, []),
         "arp_sap_weight": (C.c_float, [C.c_char_p, C.c_float]),
         "arp_sap_neighbor_sum": (C.c_int32, [vp, C.c_uint64, _dp, _dp, _dp, C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float)]),
+        "arp_sasa_sphere_points": (C.c_int32, [C.c_uint32, C.POINTER(C.c_float)]),
+        "arp_atom_sasa": (C.c_int32, [vp, C.c_uint64, _dp, _dp, _dp, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.c_float, C.c_int32, C.POINTER(C.c_float), _i32p]),
+        "arp_sasa_tests": (C.c_uint64, [vp]),
+        "arp_structure_sasa_select": (C.c_int32, [vp, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), _u32p]),
+        "arp_structure_atom_sasa": (C.c_int32, [vp, vp, C.c_char_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.POINTER(C.c_uint64), _u32p,
+                                                C.POINTER(C.c_float), _i32p]),
+        "arp_structure_sap_score": (C.c_int32, [vp, vp, C.c_char_p, C.c_int32, C.c_float, C.c_int32, C.c_float, C.POINTER(C.c_uint64), _u32p,
+                                                C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+        "arp_structure_dsasa": (C.c_int32, [vp, vp, C.c_char_p, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
         "arp_profile_enable": (C.c_int32, [vp, C.c_int32]),
         "arp_profile_read": (C.c_int32, [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int32]),
         "arp_structure_load": (C.c_int32, [C.c_char_p, C.c_int32, C.POINTER(vp)]),

@@ -462,3 +462,213 @@ def contacts_batch(input_files, groups: str = "/", vdw_comp: float = 0.1, dist_c
         return []
     with ThreadPoolExecutor(max_workers=max(1, min(int(num_workers), len(files)))) as pool:
         return list(pool.map(one, enumerate(files)))
+
+
+# ---------------------------------------------------------------------------------------------- atom SASA, SAP score, dSASA
+# Atom-level SASA (reference src/sasa.rs:174-249) and everything built on it: per-atom / per-residue SAP (src/sap.rs:137-340) and dSASA
+# (src/sasa.rs:400-451, python.rs:161-191).  The Shrake-Rupley kernel, the SAP weights and the neighbour sum run on the device
+# (include/arpeggia_amd.h "atom SASA").  Residue- and chain-level SASA and relative_sasa are not offered: the reference computes them through
+# rust-sasa's SASAOptions, whose own radius table (van der Waals only as a fallback) is not part of the reference's tree, so those numbers would
+# be a guess.  dSASA is built from atom-level SASA here, where the reference sums chain-level SASA; its tolerance test is the check.
+SASA_LEVELS = ("atom",)
+SAP_LEVELS = ("atom", "residue")
+# src/sap.rs:77-101 get_sc_max_asa (the table of arp_sap_weight; tests/test_sasa_host.py checks the two agree)
+SAP_MAX_SC_ASA = {
+    "ALA": 15.395, "ARG": 124.338, "ASN": 90.303, "ASP": 87.601, "CYS": 46.456, "GLU": 95.534, "GLN": 99.186, "GLY": 3.229, "HIS": 96.532,
+    "ILE": 31.448, "LEU": 30.271, "LYS": 61.962, "MET": 65.233, "PHE": 67.945, "PRO": 17.812, "SER": 39.355, "THR": 42.648, "TRP": 101.491,
+    "TYR": 94.478, "VAL": 26.702,
+}
+ATOM_SASA_COLUMNS = ["atomi", "sasa", "chain", "resn", "resi", "insertion", "altloc", "atomn"]
+ATOM_SAP_COLUMNS = ["chain", "resn", "resi", "insertion", "atomn", "atomi", "sasa", "sap_score"]
+RESIDUE_SAP_COLUMNS = ["chain", "resn", "resi", "insertion", "sc_sasa", "sap_score", "max_sc_asa", "relative_sc_sasa"]
+
+
+def sasa_sphere_points(n_points: int) -> np.ndarray:
+    """The n_points x 3 f32 unit vectors of the SASA contract (arp_sasa_sphere_points: golden spiral in f64, rounded to f32)."""
+    out = np.zeros((int(n_points), 3), dtype="<f4")
+    _check(lib.arp_sasa_sphere_points(int(n_points), out.ctypes.data_as(C.POINTER(C.c_float))))
+    return out
+
+
+def atom_sasa(ctx: "Context", x, y, z, radius, include=None, probe: float = 1.4, n_points: int = 100):
+    """arp_atom_sasa on host arrays: (sasa f32, count i32) per atom; atoms outside `include` get 0 and neither bury nor are buried."""
+    x, y, z = (np.ascontiguousarray(v, dtype="<f8") for v in (x, y, z))
+    r = np.ascontiguousarray(radius, dtype="<f4")
+    n = len(x)
+    inc = None if include is None else np.ascontiguousarray(include, dtype=np.uint8)
+    sasa = np.zeros(n, dtype="<f4")
+    count = np.zeros(n, dtype="<i4")
+    dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
+    _check(lib.arp_atom_sasa(ctx._h, n, x.ctypes.data_as(dp), y.ctypes.data_as(dp), z.ctypes.data_as(dp), r.ctypes.data_as(fp),
+                             None if inc is None else inc.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_float(probe), int(n_points),
+                             sasa.ctypes.data_as(fp), count.ctypes.data_as(C.POINTER(C.c_int32))))
+    return sasa, count
+
+
+def sasa_tests(ctx: "Context") -> int:
+    """f32 distance tests the kernel of the context's most recent SASA call made (diagnostics)."""
+    return int(lib.arp_sasa_tests(ctx._h))
+
+
+def sasa_select(structure: Structure, chains: str = "", model_num: int = 0, remove_hydrogens: bool = True) -> np.ndarray:
+    """Structure atom indices get_atom_sasa works on (prepare_pdb_for_sasa + filter_pdb_by_model, sasa.rs:27-135,183-195; the steps and
+    the model quirk are in include/arpeggia_amd.h arp_structure_sasa_select)."""
+    out = np.zeros(max(structure.n_atoms, 1), dtype="<u4")
+    n = C.c_uint64()
+    _check(lib.arp_structure_sasa_select(structure._h, chains.encode(), int(model_num), int(bool(remove_hydrogens)), C.byref(n),
+                                         out.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return out[: n.value].copy()
+
+
+def _frame(cols: dict):
+    """A table of the contact table's type: polars.DataFrame when polars is importable, else pyarrow.Table."""
+    import pyarrow as pa
+
+    table = pa.table(cols)
+    try:
+        import polars as pl
+
+        return pl.from_arrow(table)
+    except ImportError:
+        return table
+
+
+def _strings(structure: Structure, column: str, idx: np.ndarray) -> list:
+    return [b.decode() for b in structure.strings(column)[idx]]
+
+
+def _identity(structure: Structure, idx: np.ndarray) -> dict:
+    """Entity columns of the given atoms with the contact table's conventions (utf8, "" for a blank insertion code / altloc)."""
+    import pyarrow as pa
+
+    return {
+        "chain": pa.array(_strings(structure, "chain", idx), pa.string()), "resn": pa.array(_strings(structure, "resn", idx), pa.string()),
+        "resi": pa.array(structure.ints("resi")[idx].astype("<i4"), pa.int32()),
+        "insertion": pa.array(_strings(structure, "insertion", idx), pa.string()),
+        "altloc": pa.array(_strings(structure, "altloc", idx), pa.string()), "atomn": pa.array(_strings(structure, "atomn", idx), pa.string()),
+        "atomi": pa.array(structure.ints("atomi")[idx].astype("<i4"), pa.int32()),
+    }
+
+
+def atom_sasa_rows(structure: Structure, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, remove_hydrogens: bool = True,
+                   chains: str = "", device: int = 0):
+    """arp_structure_atom_sasa as numpy arrays: (structure atom index u32, sasa f32, count i32), rows sorted by serial number."""
+    n = max(structure.n_atoms, 1)
+    atoms, sasa, count = np.zeros(n, "<u4"), np.zeros(n, "<f4"), np.zeros(n, "<i4")
+    rows = C.c_uint64()
+    _check(lib.arp_structure_atom_sasa(_context(device)._h, structure._h, chains.encode(), int(model_num), int(bool(remove_hydrogens)),
+                                       C.c_float(probe_radius), int(n_points), C.byref(rows), atoms.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                       sasa.ctypes.data_as(C.POINTER(C.c_float)), count.ctypes.data_as(C.POINTER(C.c_int32))))
+    k = rows.value
+    return atoms[:k].copy(), sasa[:k].copy(), count[:k].copy()
+
+
+def get_atom_sasa(structure: Structure, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, remove_hydrogens: bool = True,
+                  chains: str = "", device: int = 0):
+    """`arpeggia::get_atom_sasa` (sasa.rs:174): columns atomi i32, sasa f32, chain, resn, resi i32, insertion, altloc, atomn; sorted by atomi."""
+    import pyarrow as pa
+
+    idx, sasa, _ = atom_sasa_rows(structure, probe_radius, n_points, model_num, remove_hydrogens, chains, device)
+    ident = _identity(structure, idx)
+    cols = {"atomi": ident["atomi"], "sasa": pa.array(sasa, pa.float32())}
+    cols.update({k: ident[k] for k in ATOM_SASA_COLUMNS[2:]})
+    return _frame(cols)
+
+
+def sasa(input_file: str, level: str = "atom", probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, chains: str = "",
+         num_threads: int = 1):
+    """Drop-in for `arpeggia.sasa` (python.rs:93) at level "atom" (the only level offered: see the section comment above)."""
+    lv = str(level).lower()
+    if lv not in ("atom", "residue", "chain"):
+        raise ValueError(f"Invalid level '{level}'. Must be one of: 'atom', 'residue', 'chain'")
+    if lv != "atom":
+        raise NotImplementedError(f"sasa level '{lv}' is not available: the reference computes it with rust-sasa's own radius table, which is "
+                                  "not part of its source tree; only level='atom' (get_atom_sasa) is reproduced")
+    del num_threads  # (the computation runs on the GPU; accepted for signature compatibility)
+    return get_atom_sasa(Structure.load(input_file), probe_radius, n_points, model_num, True, chains)
+
+
+def atom_sap_rows(structure: Structure, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, sap_radius: float = 5.0,
+                  chains: str = "", device: int = 0):
+    """arp_structure_sap_score as numpy arrays: (structure atom index, sasa f32, sap_score f32), rows sorted by serial number."""
+    n = max(structure.n_atoms, 1)
+    atoms, sasa_, sap = np.zeros(n, "<u4"), np.zeros(n, "<f4"), np.zeros(n, "<f4")
+    rows = C.c_uint64()
+    fp = C.POINTER(C.c_float)
+    _check(lib.arp_structure_sap_score(_context(device)._h, structure._h, chains.encode(), int(model_num), C.c_float(probe_radius), int(n_points),
+                                       C.c_float(sap_radius), C.byref(rows), atoms.ctypes.data_as(C.POINTER(C.c_uint32)), sasa_.ctypes.data_as(fp),
+                                       sap.ctypes.data_as(fp)))
+    k = rows.value
+    return atoms[:k].copy(), sasa_[:k].copy(), sap[:k].copy()
+
+
+def get_per_atom_sap_score(structure: Structure, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, sap_radius: float = 5.0,
+                           chains: str = "", device: int = 0):
+    """`arpeggia::get_per_atom_sap_score` (sap.rs:137-259): chain, resn, resi, insertion, atomn, atomi, sasa, sap_score; sorted by atomi."""
+    import pyarrow as pa
+
+    idx, sasa_, sap = atom_sap_rows(structure, probe_radius, n_points, model_num, sap_radius, chains, device)
+    ident = _identity(structure, idx)
+    cols = {k: ident[k] for k in ATOM_SAP_COLUMNS[:6]}
+    cols["sasa"] = pa.array(sasa_, pa.float32())
+    cols["sap_score"] = pa.array(sap, pa.float32())
+    return _frame(cols)
+
+
+def residue_sap_from_atoms(chain, resn, resi, insertion, sasa_, sap) -> dict:
+    """sap.rs:295-340 on per-atom columns: rows with sap_score > 0, grouped by (chain, resn, resi, insertion), sc_sasa and sap_score summed
+    (in f64, rounded to f32 once), sorted by chain, resi, insertion (stable), then max_sc_asa and relative_sc_sasa = clip(sc_sasa / max_sc_asa,
+    0, 1) in f32.  Returns numpy / list columns in RESIDUE_SAP_COLUMNS order."""
+    groups: dict = {}
+    for c, rn, ri, ic, a, s in zip(chain, resn, resi, insertion, sasa_, sap):
+        if not s > 0.0:
+            continue
+        g = groups.setdefault((c, rn, int(ri), ic), [0.0, 0.0])
+        g[0] += float(a)
+        g[1] += float(s)
+    keys = sorted(groups, key=lambda k: (k[0], k[2], k[3]))
+    sc = np.array([groups[k][0] for k in keys], dtype=np.float64).astype(np.float32)
+    sp = np.array([groups[k][1] for k in keys], dtype=np.float64).astype(np.float32)
+    mx = np.array([SAP_MAX_SC_ASA[k[1]] for k in keys], dtype=np.float32)  # (sap.rs:326 unwraps: every residue with a score has a value)
+    rel = np.clip(sc / mx, np.float32(0.0), np.float32(1.0)).astype(np.float32) if keys else np.zeros(0, np.float32)
+    return {"chain": [k[0] for k in keys], "resn": [k[1] for k in keys], "resi": np.array([k[2] for k in keys], dtype="<i4"),
+            "insertion": [k[3] for k in keys], "sc_sasa": sc, "sap_score": sp, "max_sc_asa": mx, "relative_sc_sasa": rel}
+
+
+def get_per_residue_sap_score(structure: Structure, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, sap_radius: float = 5.0,
+                              chains: str = "", device: int = 0):
+    """`arpeggia::get_per_residue_sap_score` (sap.rs:295-340): chain, resn, resi, insertion, sc_sasa, sap_score, max_sc_asa, relative_sc_sasa."""
+    import pyarrow as pa
+
+    idx, sasa_, sap = atom_sap_rows(structure, probe_radius, n_points, model_num, sap_radius, chains, device)
+    cols = residue_sap_from_atoms(_strings(structure, "chain", idx), _strings(structure, "resn", idx), structure.ints("resi")[idx],
+                                  _strings(structure, "insertion", idx), sasa_, sap)
+    types = {"chain": pa.string(), "resn": pa.string(), "resi": pa.int32(), "insertion": pa.string()}
+    return _frame({k: pa.array(v, types.get(k, pa.float32())) for k, v in cols.items()})
+
+
+def sap_score(input_file: str, level: str = "residue", probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0,
+              sap_radius: float = 5.0, chains: str = "", num_threads: int = 1):
+    """Drop-in for `arpeggia.sap_score` (python.rs:286-325)."""
+    lv = str(level).lower()
+    if lv not in SAP_LEVELS:
+        raise ValueError(f"Invalid level '{level}'. Must be one of: 'atom', 'residue'")
+    del num_threads
+    s = Structure.load(input_file)
+    f = get_per_atom_sap_score if lv == "atom" else get_per_residue_sap_score
+    return f(s, probe_radius, n_points, model_num, sap_radius, chains)
+
+
+def get_dsasa(structure: Structure, groups: str, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, device: int = 0) -> float:
+    """`arpeggia::get_dsasa` (sasa.rs:400-451) from atom-level SASA: SASA(group 1) + SASA(group 2) - SASA(complex), not halved.
+    A negative value raises (python.rs:177-188); group errors are those of the contact path's parse_groups."""
+    out = C.c_float()
+    _check(lib.arp_structure_dsasa(_context(device)._h, structure._h, groups.encode(), C.c_float(probe_radius), int(n_points), int(model_num),
+                                   C.byref(out)))
+    return float(out.value)
+
+
+def dsasa(input_file: str, groups: str, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, num_threads: int = 1) -> float:
+    """Drop-in for `arpeggia.dsasa` (python.rs:161-191)."""
+    del num_threads
+    return get_dsasa(Structure.load(input_file), groups, probe_radius, n_points, model_num)

@@ -8,6 +8,17 @@
 
 namespace arp {
 
+// SAP residue table (src/sap.rs:41-101): name, hydrophobicity (Black & Mould, shifted so that glycine is 0), largest side-chain SASA.
+// One list for arp_sap_weight (engine.cpp) and the device weight kernel (sasa.inl): the code of a residue is its position here.
+#define ARP_SAP_RESIDUES(X)                                                                                                          \
+    X("ALA", 0.616f - 0.501f, 15.395f) X("ARG", 0.000f - 0.501f, 124.338f) X("ASN", 0.236f - 0.501f, 90.303f)                       \
+    X("ASP", 0.028f - 0.501f, 87.601f) X("CYS", 0.680f - 0.501f, 46.456f) X("GLU", 0.043f - 0.501f, 95.534f)                        \
+    X("GLN", 0.251f - 0.501f, 99.186f) X("GLY", 0.000f, 3.229f) X("HIS", 0.165f - 0.501f, 96.532f) X("ILE", 0.943f - 0.501f, 31.448f) \
+    X("LEU", 0.943f - 0.501f, 30.271f) X("LYS", 0.283f - 0.501f, 61.962f) X("MET", 0.738f - 0.501f, 65.233f)                        \
+    X("PHE", 1.000f - 0.501f, 67.945f) X("PRO", 0.711f - 0.501f, 17.812f) X("SER", 0.359f - 0.501f, 39.355f)                        \
+    X("THR", 0.450f - 0.501f, 42.648f) X("TRP", 0.878f - 0.501f, 101.491f) X("TYR", 0.880f - 0.501f, 94.478f)                       \
+    X("VAL", 0.825f - 0.501f, 26.702f)
+
 // Decision constants in SQUARED-distance space.  The reference compares d = sqrt(s) (correctly rounded f64)
 // against thresholds T with `<` (vdw.rs:33-41) or `<=` (everything else).  Because rn(sqrt(.)) is monotone,
 // {s : sqrt(s) < T} = {s : s < lt(T)} with lt(T) = min{s : sqrt(s) >= T}; likewise d <= T  <=>  s < le(T).
@@ -176,6 +187,13 @@ bool launch_emit(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsigne
 bool emit_takes_res_filter(const DevAtoms &in);  // the single-pass emitter has residue-rule kernels for an input of this size (the grid build then writes Sorted::rkey)
 unsigned long long emit_scratch_records();
 void launch_neighbor_sum(const DevAtoms &in, const Workspace &ws, double radius, double r2, const float *weight, float *out, hipStream_t st, Profiler *prof);
+// Atom SASA (sasa.inl): grid over the atoms without ARP_ATTR_H, then one wave per grid atom.  sasa / count are indexed like the input arrays
+// (atoms outside the grid are not written).  The kernel adds its number of f32 distance tests to Workspace::result[kSasaTestsWord].
+constexpr uint32_t kSasaTestsWord = 8;
+void launch_sasa(const DevAtoms &in, const Workspace &ws, double cutoff, const float *R, const float *sphere, uint32_t n_points, float r_max,
+                 float *sasa, int32_t *count, hipStream_t st, Profiler *prof);
+// w[j] = arp_sap_weight(ARP_SAP_RESIDUES name code[j], sasa[src[j]]), 0 where src[j] < 0 or code[j] >= 20
+void launch_sap_weight(uint32_t n, const uint32_t *code, const int32_t *src, const float *sasa, float *w, hipStream_t st);
 void launch_pack_fix(const PackArrays &pa, hipStream_t st);
 void launch_pack_split(const PackArrays &pa, const unsigned long long *result, const arp_pair *pairs, unsigned long long capacity, arp_pair *grouped, bool ordered, hipStream_t st);
 

@@ -150,6 +150,7 @@ struct arp_context {
     const double *grid_x = nullptr; uint64_t grid_n = 0;  // the arrays the workspace's cell list was last built from (context_grid)
     arp_atoms last_atoms{};                // the enqueued call, kept so that arp_contacts_atomic_result can re-run it after growing a list
     arp_pair *last_out = nullptr;
+    uint64_t sasa_tests = 0;               // f32 distance tests of the last SASA call (arp_sasa_tests)
     Profiler prof;
 };
 
@@ -1125,21 +1126,28 @@ extern "C" arp_status arp_contacts_atomic_batch(arp_context *const *ctxs, int32_
 } ARP_ABI_CATCH
 
 // ---- SAP neighbour sum (reference src/sap.rs:155-204) ---------------------------------------------------
-extern "C" float arp_sap_weight(const char *resn, float sasa) {
-    // hydrophobicity (Black & Mould minus glycine, sap.rs:41-64) x clamp(sasa / max side-chain SASA (sap.rs:77-101), 0, 1); 0 for residues
-    // without a hydrophobicity value (sap.rs:198-209)
-    static const struct { const char *n; float h, a; } T[] = {
-        {"ALA", 0.616f - 0.501f, 15.395f}, {"ARG", 0.000f - 0.501f, 124.338f}, {"ASN", 0.236f - 0.501f, 90.303f}, {"ASP", 0.028f - 0.501f, 87.601f},
-        {"CYS", 0.680f - 0.501f, 46.456f}, {"GLU", 0.043f - 0.501f, 95.534f}, {"GLN", 0.251f - 0.501f, 99.186f}, {"GLY", 0.000f, 3.229f},
-        {"HIS", 0.165f - 0.501f, 96.532f}, {"ILE", 0.943f - 0.501f, 31.448f}, {"LEU", 0.943f - 0.501f, 30.271f}, {"LYS", 0.283f - 0.501f, 61.962f},
-        {"MET", 0.738f - 0.501f, 65.233f}, {"PHE", 1.000f - 0.501f, 67.945f}, {"PRO", 0.711f - 0.501f, 17.812f}, {"SER", 0.359f - 0.501f, 39.355f},
-        {"THR", 0.450f - 0.501f, 42.648f}, {"TRP", 0.878f - 0.501f, 101.491f}, {"TYR", 0.880f - 0.501f, 94.478f}, {"VAL", 0.825f - 0.501f, 26.702f}};
-    if (!resn) return 0.0f;
+namespace arp {
+struct SapResidue { const char *n; float h, a; };
+#define ARP_SAP_ROW(n, h, a) {n, h, a},
+static const SapResidue kSapResidues[20] = {ARP_SAP_RESIDUES(ARP_SAP_ROW)};
+#undef ARP_SAP_ROW
+uint32_t sap_residue_code(const char *resn) {
+    if (!resn) return 20u;
     char up[8] = {0};
     for (int k = 0; k < 7 && resn[k]; k++) up[k] = (char)toupper((unsigned char)resn[k]);
-    for (const auto &t : T)
-        if (strcmp(t.n, up) == 0) return t.h * std::min(1.0f, std::max(0.0f, sasa / t.a));
-    return 0.0f;
+    for (uint32_t r = 0; r < 20u; r++)
+        if (strcmp(kSapResidues[r].n, up) == 0) return r;
+    return 20u;
+}
+}  // namespace arp
+
+extern "C" float arp_sap_weight(const char *resn, float sasa) {
+    // hydrophobicity (Black & Mould minus glycine, sap.rs:41-64) x clamp(sasa / max side-chain SASA (sap.rs:77-101), 0, 1); 0 for residues
+    // without a hydrophobicity value (sap.rs:198-209).  The table is ARP_SAP_RESIDUES (arp_internal.h), shared with the device weight kernel.
+    const uint32_t r = sap_residue_code(resn);
+    if (r >= 20u) return 0.0f;
+    const SapResidue &t = kSapResidues[r];
+    return t.h * std::min(1.0f, std::max(0.0f, sasa / t.a));
 }
 
 extern "C" arp_status arp_sap_neighbor_sum(arp_context *ctx, uint64_t n, const double *x, const double *y, const double *z, const uint8_t *sidechain,
@@ -1184,6 +1192,143 @@ extern "C" arp_status arp_sap_neighbor_sum(arp_context *ctx, uint64_t n, const d
     memcpy(out, h_out, n * 4);
     return ARP_OK;
 } ARP_ABI_CATCH
+
+// ---- atom SASA (sasa.inl; reference src/sasa.rs:174-247) and the SAP chain (src/sap.rs:137-250) --------------------------------------
+namespace arp {
+void sasa_sphere_points(uint32_t n, float *xyz) {
+    // golden spiral: t = k / n, theta = acos(1 - 2 t), phi = (2 pi golden) k; (sin theta cos phi, sin theta sin phi, cos theta) in f64, rounded to f32
+    const double golden = (1.0 + std::sqrt(5.0)) / 2.0, step = 2.0 * 3.141592653589793 * golden;
+    for (uint32_t k = 0; k < n; k++) {
+        const double t = (double)k / (double)n, theta = std::acos(1.0 - 2.0 * t), phi = step * (double)k;
+        xyz[3 * k] = (float)(std::sin(theta) * std::cos(phi));
+        xyz[3 * k + 1] = (float)(std::sin(theta) * std::sin(phi));
+        xyz[3 * k + 2] = (float)std::cos(theta);
+    }
+}
+
+arp_status sasa_run(arp_context *ctx, const SasaJob &j, float *sasa, int32_t *count, float *sap) {
+    arp_status s = check_device(ctx);
+    if (s != ARP_OK) return s;
+    if (ctx->pending) { set_error("a call enqueued on this context has not been collected (arp_contacts_atomic_result)"); return ARP_ERR_BAD_INPUT; }
+    const uint64_t n = j.n;
+    if (n >= 0x5000000ull) { set_error("too many atoms for one SASA call (< 83886080)"); return ARP_ERR_BAD_INPUT; }
+    if (n == 0) return ARP_OK;
+    const bool with_sap = j.sidechain != nullptr;
+    float r_max = 0.0f;
+    for (uint64_t i = 0; i < n; i++) {
+        const bool use = j.include[i] != 0, side = with_sap && j.sidechain[i];
+        if ((use || side) && !(std::isfinite(j.x[i]) && std::isfinite(j.y[i]) && std::isfinite(j.z[i]))) { set_error("non-finite atom coordinate"); return ARP_ERR_BAD_INPUT; }
+        if (use) r_max = std::max(r_max, j.R[i]);
+    }
+    // one pinned block out, one back: inputs {f32-rounded x y z (f64), SASA attr, zeros, model, R, sphere, [x y z, SAP attr, code, src]}, outputs {sasa, count, [sap]}
+    uint64_t off = 0;
+    auto seg = [&](uint64_t bytes) { const uint64_t o = off; off += (bytes + 255u) & ~255ull; return o; };
+    const uint64_t o_x = seg(8 * n), o_y = seg(8 * n), o_z = seg(8 * n), o_attr = seg(4 * n), o_zero = seg(4 * n), o_model = seg(4 * n), o_R = seg(4 * n),
+                   o_sph = seg(12ull * j.n_points);
+    uint64_t o_px = 0, o_py = 0, o_pz = 0, o_pattr = 0, o_code = 0, o_src = 0;
+    if (with_sap) { o_px = seg(8 * n); o_py = seg(8 * n); o_pz = seg(8 * n); o_pattr = seg(4 * n); o_code = seg(4 * n); o_src = seg(4 * n); }
+    const uint64_t in_bytes = off;
+    const uint64_t o_sasa = seg(4 * n), o_count = seg(4 * n), o_w = with_sap ? seg(4 * n) : 0, o_sap = with_sap ? seg(4 * n) : 0;
+    const uint64_t out_bytes = off - in_bytes;
+    char *dev = nullptr, *pin = nullptr;
+    if ((s = context_scratch(ctx, 0, off, off, &dev, &pin)) != ARP_OK) return s;
+    double *hx = (double *)(pin + o_x), *hy = (double *)(pin + o_y), *hz = (double *)(pin + o_z);
+    uint32_t *hattr = (uint32_t *)(pin + o_attr), *hmodel = (uint32_t *)(pin + o_model);
+    float *hR = (float *)(pin + o_R);
+    for (uint64_t i = 0; i < n; i++) {
+        const bool use = j.include[i] != 0;
+        hx[i] = (double)(float)j.x[i]; hy[i] = (double)(float)j.y[i]; hz[i] = (double)(float)j.z[i];  // sasa.rs:196-198
+        hattr[i] = use ? 0u : ARP_ATTR_H;  // (the attribute bit that keeps an atom out of the grid)
+        hmodel[i] = j.model ? j.model[i] : 0u;
+        hR[i] = use ? j.R[i] : 0.0f;
+    }
+    memset(pin + o_zero, 0, 4 * n);
+    memcpy(pin + o_sph, j.sphere, 12ull * j.n_points);
+    if (with_sap) {
+        memcpy(pin + o_px, j.x, 8 * n); memcpy(pin + o_py, j.y, 8 * n); memcpy(pin + o_pz, j.z, 8 * n);
+        uint32_t *pa = (uint32_t *)(pin + o_pattr);
+        for (uint64_t i = 0; i < n; i++) pa[i] = j.sidechain[i] ? (ARP_ATTR_LIGAND | ARP_ATTR_RECEPTOR) : ARP_ATTR_H;
+        memcpy(pin + o_code, j.res_code, 4 * n); memcpy(pin + o_src, j.src, 4 * n);
+    }
+    if ((s = ensure_workspace(ctx, n)) != ARP_OK) return s;
+    ctx->grid_x = nullptr; ctx->grid_n = 0;  // the workspace's cell list is about to hold another input (context_grid must not hand it out)
+    ctx->nodefer_x = nullptr; ctx->nodefer_n = 0;
+    HIP_TRY(hipMemcpyAsync(dev, pin, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(dev + in_bytes, 0, out_bytes, ctx->stream));  // atoms outside the grid keep sasa 0, count 0
+    Profiler *prof = ctx->prof.enabled ? &ctx->prof : nullptr;
+    // search radius: a burier j of a point of i is closer than R_i |s_k| + R_j <= 2 R_max (1 + 2^-23); 1e-5 covers that and the f32 gather test
+    const double cutoff = 2.0 * (double)r_max * (1.0 + 1e-5) + 1e-6;
+    arp_params prm;
+    arp_default_params(&prm);
+    prm.dist_cutoff = cutoff;
+    if ((s = upload_params(ctx, &prm)) != ARP_OK) return s;
+    DevAtoms d{};
+    d.n = (uint32_t)n;
+    d.x = (const double *)(dev + o_x); d.y = (const double *)(dev + o_y); d.z = (const double *)(dev + o_z);
+    d.attr = (const uint32_t *)(dev + o_attr); d.res_ord = d.chain_rank = (const uint32_t *)(dev + o_zero); d.model = (const uint32_t *)(dev + o_model);
+    float *d_sasa = (float *)(dev + o_sasa);
+    launch_sasa(d, ctx->ws, cutoff, (const float *)(dev + o_R), (const float *)(dev + o_sph), j.n_points, r_max, d_sasa, (int32_t *)(dev + o_count),
+                ctx->stream, prof);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ctx->h_result + 6, ctx->ws.result + kSasaTestsWord, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    if (with_sap) {
+        prm.dist_cutoff = (double)j.sap_radius;
+        if ((s = upload_params(ctx, &prm)) != ARP_OK) return s;
+        launch_sap_weight((uint32_t)n, (const uint32_t *)(dev + o_code), (const int32_t *)(dev + o_src), d_sasa, (float *)(dev + o_w), ctx->stream);
+        DevAtoms e = d;
+        e.x = (const double *)(dev + o_px); e.y = (const double *)(dev + o_py); e.z = (const double *)(dev + o_pz);
+        e.attr = (const uint32_t *)(dev + o_pattr); e.model = (const uint32_t *)(dev + o_zero);
+        const double r2 = (double)(j.sap_radius * j.sap_radius);  // sap.rs:184: the product is formed in f32
+        launch_neighbor_sum(e, ctx->ws, (double)j.sap_radius, r2, (const float *)(dev + o_w), (float *)(dev + o_sap), ctx->stream, prof);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(pin + in_bytes, dev + in_bytes, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->sasa_tests = ctx->h_result[6];
+    if (sasa) memcpy(sasa, pin + o_sasa, 4 * n);
+    if (count) memcpy(count, pin + o_count, 4 * n);
+    if (sap && with_sap) memcpy(sap, pin + o_sap, 4 * n);
+    return ARP_OK;
+}
+}  // namespace arp
+
+extern "C" arp_status arp_sasa_sphere_points(uint32_t n, float *xyz) try {
+    if (n < 1 || n > ARP_SASA_MAX_POINTS || !xyz) { set_error("arp_sasa_sphere_points: n must be 1..%d and xyz non-null", ARP_SASA_MAX_POINTS); return ARP_ERR_BAD_INPUT; }
+    sasa_sphere_points(n, xyz);
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+namespace arp {
+arp_status sasa_check_params(float probe, int32_t n_points) {
+    if (n_points < 1 || n_points > ARP_SASA_MAX_POINTS) { set_error("n_points must be 1..%d (got %d)", ARP_SASA_MAX_POINTS, (int)n_points); return ARP_ERR_BAD_INPUT; }
+    if (!(std::isfinite(probe) && probe >= 0.0f)) { set_error("probe radius must be finite and >= 0"); return ARP_ERR_BAD_INPUT; }
+    return ARP_OK;
+}
+}  // namespace arp
+
+extern "C" arp_status arp_atom_sasa(arp_context *ctx, uint64_t n, const double *x, const double *y, const double *z, const float *radius,
+                                    const uint8_t *include, float probe, int32_t n_points, float *out_sasa, int32_t *out_count) try {
+    arp_status s = check_device(ctx);
+    if (s != ARP_OK) return s;
+    if ((s = sasa_check_params(probe, n_points)) != ARP_OK) return s;
+    if (n && (!x || !y || !z || !radius || !out_sasa)) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    std::vector<uint8_t> all;
+    if (!include) { all.assign(n, 1); include = all.data(); }
+    std::vector<float> R(n, 0.0f);
+    for (uint64_t i = 0; i < n; i++) {
+        if (!include[i]) continue;
+        if (!(std::isfinite(radius[i]) && radius[i] >= 0.0f)) { set_error("atom %llu: radius must be finite and >= 0", (unsigned long long)i); return ARP_ERR_BAD_INPUT; }
+        R[i] = radius[i] + probe;  // sasa.rs:200-206 + rust-sasa: r + probe in f32
+    }
+    std::vector<float> sphere(3ull * (uint32_t)n_points);
+    sasa_sphere_points((uint32_t)n_points, sphere.data());
+    SasaJob j;
+    j.n = n; j.x = x; j.y = y; j.z = z; j.R = R.data(); j.include = include; j.n_points = (uint32_t)n_points; j.sphere = sphere.data();
+    std::vector<int32_t> cnt(out_count ? 0 : n);
+    return sasa_run(ctx, j, out_sasa, out_count ? out_count : cnt.data(), nullptr);
+} ARP_ABI_CATCH
+
+extern "C" uint64_t arp_sasa_tests(const arp_context *ctx) { return ctx ? ctx->sasa_tests : 0u; }
 
 // ---- accessors for the table path (table_dev.hip) ---------------------------------------------------------------------------
 namespace arp {

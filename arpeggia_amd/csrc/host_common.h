@@ -88,6 +88,29 @@ struct arp_structure {
 };
 
 namespace arp {
+// Atom SASA (+ the SAP chain) on the device: engine.cpp runs it, arp_atom_sasa and the structure-level entry points (sasa.cpp) fill the job.
+struct SasaJob {
+    uint64_t n = 0;                        // atoms of the job, host arrays of n entries
+    const double *x = nullptr, *y = nullptr, *z = nullptr;  // f64 coordinates: SASA rounds them to f32, the SAP neighbour sum takes them as they are
+    const float *R = nullptr;              // radius + probe in f32 (read for the SASA atoms only)
+    const uint8_t *include = nullptr;      // the SASA atoms; the others get sasa 0, count 0
+    const uint32_t *model = nullptr;       // slab of every atom (dSASA runs three selections as three models of one grid); nullptr = all 0
+    uint32_t n_points = 0;
+    const float *sphere = nullptr;         // n_points x 3 unit vectors (sasa_sphere_points)
+    // SAP (src/sap.rs:137-250), when sidechain != nullptr: weight[j] = arp_sap_weight(residue code[j], sasa[src[j]]) (0 for src[j] < 0),
+    // sap[i] = the f32 sum of the weights of the side-chain atoms within sap_radius of side-chain atom i (arp_sap_neighbor_sum)
+    const uint8_t *sidechain = nullptr;
+    const uint32_t *res_code = nullptr;    // position in ARP_SAP_RESIDUES, >= 20: none
+    const int32_t *src = nullptr;
+    float sap_radius = 0.0f;
+};
+// sasa / count / sap (nullable) receive n entries; one synchronisation at the end.  Inputs are checked by the callers.
+arp_status sasa_run(arp_context *ctx, const SasaJob &job, float *sasa, int32_t *count, float *sap);
+// golden-spiral unit vectors in f64, rounded to f32 (DESIGN.md "Atom SASA")
+void sasa_sphere_points(uint32_t n, float *xyz);
+uint32_t sap_residue_code(const char *resn);
+arp_status sasa_check_params(float probe, int32_t n_points);  // ARP_ERR_BAD_INPUT + message unless 1 <= n_points <= ARP_SASA_MAX_POINTS, probe finite >= 0  // position in ARP_SAP_RESIDUES (case-insensitive, as arp_sap_weight), 20 if none
+
 arp_status parse_groups(const std::vector<std::string> &all_chains, const char *groups, std::vector<std::string> *ligand,
                         std::vector<std::string> *receptor);
 arp_status apply_groups(arp_structure *s, const char *groups);

@@ -280,5 +280,6 @@ DEVFN float dist_f32(double s) {
 #include "pairs_emit.inl"
 #include "batch.inl"
 #include "sap.inl"
+#include "sasa.inl"
 
 }  // namespace arp

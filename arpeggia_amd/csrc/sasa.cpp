@@ -1,0 +1,234 @@
+// Structure-level atom SASA, SAP score and dSASA (reference src/sasa.rs:27-451, src/sap.rs:137-259): the atom selection of
+// prepare_pdb_for_sasa + filter_pdb_by_model on the parsed structure, then one device run (engine.cpp sasa_run, kernels in sasa.inl).
+// Residue- and chain-level SASA (get_residue_sasa / get_chain_sasa, relative_sasa) are NOT here: the reference computes them through
+// rust-sasa's SASAOptions, whose own radius table (with a van-der-Waals fallback) is not part of the reference's tree -- those levels would
+// be a guess.  dSASA, chain-level in the reference, is built from atom-level SASA instead (arpeggia_amd.h arp_structure_dsasa).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <numeric>
+#include <string>
+#include <unordered_map>
+#include <unordered_set>
+#include <vector>
+
+#include "arp_internal.h"
+#include "host_common.h"
+
+namespace arp {
+
+// sasa.rs:44-51 SOLVENT_RESIDUES + ION_RESIDUES (exact, case-sensitive names, as `contains` compares them)
+static bool solvent_or_ion(const char *resn) {
+    static const char *k[] = {"HOH", "H2O", "D2O", "WAT", "TIP", "TIP3", "TIP4", "SPC", "NA", "CL", "K", "CA", "MG", "ZN", "FE", "MN",
+                              "CU", "CO", "NI", "CD", "SO4", "PO4", "NO3", "ACE", "NH2"};
+    for (const char *r : k) if (strcmp(r, resn) == 0) return true;
+    return false;
+}
+
+// sasa.rs:71-81 parse_chain_string: split on ',', trim, drop empty entries
+static std::unordered_set<std::string> chain_set(const char *chains) {
+    std::unordered_set<std::string> out;
+    std::string cur;
+    auto push = [&]() {
+        size_t b = 0, e = cur.size();
+        while (b < e && isspace((unsigned char)cur[b])) b++;
+        while (e > b && isspace((unsigned char)cur[e - 1])) e--;
+        if (e > b) out.insert(cur.substr(b, e - b));
+        cur.clear();
+    };
+    if (chains) {
+        for (const char *p = chains; *p; p++) { if (*p == ',') push(); else cur.push_back(*p); }
+        push();
+    }
+    return out;
+}
+
+// Steps 1-5 of arpeggia_amd.h arp_structure_sasa_select.  keep: chain ids to keep (empty = all); model_filter: step 4; serial_filter: step 5.
+static std::vector<uint32_t> select_atoms(const arp_structure *s, const std::unordered_set<std::string> &keep, bool remove_h, bool model_filter,
+                                          bool serial_filter, int32_t model_num) {
+    const uint64_t n = s->n;
+    uint32_t n_models = 0;
+    for (uint64_t i = 0; i < n; i++) n_models = std::max(n_models, s->model[i] + 1u);
+    uint32_t model_idx = ARP_NONE;  // step 4 (filter_pdb_by_model): only when there is more than one model
+    if (model_filter && n_models > 1) {
+        model_idx = 0;
+        if (model_num != 0) {
+            std::vector<int32_t> serial_of(n_models, 0);
+            std::vector<uint8_t> seen(n_models, 0);
+            for (uint64_t i = 0; i < n; i++) if (!seen[s->model[i]]) { seen[s->model[i]] = 1; serial_of[s->model[i]] = s->model_serial[i]; }
+            for (uint32_t m = 0; m < n_models; m++) if (seen[m] && serial_of[m] == model_num) { model_idx = m; break; }
+        }
+    }
+    std::vector<uint32_t> out;
+    out.reserve(n);
+    for (uint64_t i = 0; i < n; i++) {
+        if (!keep.empty() && !keep.count(std::string(s->chain.at(i)))) continue;  // step 1
+        if (remove_h && (s->base_attr[i] & ARP_ATTR_H)) continue;               // step 2 (element H)
+        if (solvent_or_ion(s->res_resn.at(i))) continue;                           // step 3 (Residue::name)
+        if (model_idx != ARP_NONE && s->model[i] != model_idx) continue;           // step 4
+        if (serial_filter && s->model_serial[i] != model_num) continue;            // step 5 (sasa.rs:193)
+        out.push_back((uint32_t)i);
+    }
+    return out;
+}
+
+static bool is_backbone(const char *name) {  // pdbtbx Atom::is_backbone (not in the reference's tree): the set the SAP test uses
+    return !strcmp(name, "N") || !strcmp(name, "CA") || !strcmp(name, "C") || !strcmp(name, "O") || !strcmp(name, "OXT");
+}
+
+// Radius + probe of every structure atom (f32: sasa.rs:200-206 casts van_der_waals to f32, rust-sasa adds the probe in f32)
+static arp_status radii(const arp_structure *s, const std::vector<uint32_t> &atoms, float probe, std::vector<float> *R) {
+    arp_params p;
+    arp_default_params(&p);
+    R->assign(s->n, 0.0f);
+    for (uint32_t i : atoms) {
+        const double vdw = p.vdw_radius[s->base_attr[i] & ARP_ATTR_ELEM_MASK];
+        if (!(vdw > 0.0)) { set_error("atom %d: element '%s' has no van der Waals radius (the reference unwraps None, sasa.rs:201-206)", s->serial[i], s->elem.at(i)); return ARP_ERR_BAD_INPUT; }
+        (*R)[i] = (float)vdw + probe;
+    }
+    return ARP_OK;
+}
+
+static void sort_rows(const arp_structure *s, std::vector<uint32_t> &rows) {  // sasa.rs:247: by atomi (stable: structure order among equal serials)
+    std::stable_sort(rows.begin(), rows.end(), [&](uint32_t a, uint32_t b) { return s->serial[a] < s->serial[b]; });
+}
+
+}  // namespace arp
+
+using namespace arp;
+
+extern "C" arp_status arp_structure_sasa_select(const arp_structure *s, const char *chains, int32_t model_num, int32_t remove_hydrogens,
+                                                uint64_t *n_out, uint32_t *out_atoms) try {
+    if (!s || !n_out) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    const std::vector<uint32_t> sel = select_atoms(s, chain_set(chains), remove_hydrogens != 0, true, true, model_num);
+    *n_out = sel.size();
+    if (out_atoms) std::copy(sel.begin(), sel.end(), out_atoms);
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+extern "C" arp_status arp_structure_atom_sasa(arp_context *ctx, const arp_structure *s, const char *chains, int32_t model_num, int32_t remove_hydrogens,
+                                              float probe, int32_t n_points, uint64_t *n_rows, uint32_t *out_atoms, float *out_sasa, int32_t *out_count) try {
+    if (!ctx || !s || !n_rows || !out_atoms || !out_sasa) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    arp_status st = sasa_check_params(probe, n_points);
+    if (st != ARP_OK) return st;
+    *n_rows = 0;
+    std::vector<uint32_t> sel = select_atoms(s, chain_set(chains), remove_hydrogens != 0, true, true, model_num);
+    std::vector<float> R;
+    if ((st = radii(s, sel, probe, &R)) != ARP_OK) return st;
+    // the job runs over the selected atoms only (compact arrays)
+    const uint64_t m = sel.size();
+    std::vector<double> x(m), y(m), z(m);
+    std::vector<float> Rm(m), sasa(m), sphere(3ull * (uint32_t)n_points);
+    std::vector<int32_t> count(m);
+    std::vector<uint8_t> inc(m, 1);
+    for (uint64_t k = 0; k < m; k++) { const uint32_t i = sel[k]; x[k] = s->x[i]; y[k] = s->y[i]; z[k] = s->z[i]; Rm[k] = R[i]; }
+    sasa_sphere_points((uint32_t)n_points, sphere.data());
+    SasaJob j;
+    j.n = m; j.x = x.data(); j.y = y.data(); j.z = z.data(); j.R = Rm.data(); j.include = inc.data(); j.n_points = (uint32_t)n_points; j.sphere = sphere.data();
+    if ((st = sasa_run(ctx, j, sasa.data(), count.data(), nullptr)) != ARP_OK) return st;
+    std::vector<uint32_t> order(m);
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return s->serial[sel[a]] < s->serial[sel[b]]; });
+    for (uint64_t r = 0; r < m; r++) {
+        out_atoms[r] = sel[order[r]]; out_sasa[r] = sasa[order[r]];
+        if (out_count) out_count[r] = count[order[r]];
+    }
+    *n_rows = m;
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+extern "C" arp_status arp_structure_sap_score(arp_context *ctx, const arp_structure *s, const char *chains, int32_t model_num, float probe,
+                                              int32_t n_points, float sap_radius, uint64_t *n_rows, uint32_t *out_atoms, float *out_sasa, float *out_sap) try {
+    if (!ctx || !s || !n_rows || !out_atoms || !out_sasa || !out_sap) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    arp_status st = sasa_check_params(probe, n_points);
+    if (st != ARP_OK) return st;
+    if (!(sap_radius >= 0.0f)) { set_error("bad sap_radius"); return ARP_ERR_BAD_INPUT; }
+    *n_rows = 0;
+    const std::unordered_set<std::string> keep = chain_set(chains);
+    // the neighbour set: steps 1-3 without the model filter (sap.rs:182); the SASA rows: steps 1-5 (sap.rs:147) -- a subset of it
+    const std::vector<uint32_t> nb = select_atoms(s, keep, true, false, false, model_num);
+    const std::vector<uint32_t> sel = select_atoms(s, keep, true, true, true, model_num);
+    std::vector<float> R;
+    if ((st = radii(s, sel, probe, &R)) != ARP_OK) return st;
+    const uint64_t m = nb.size();
+    std::vector<uint32_t> pos(s->n, ARP_NONE);
+    for (uint64_t k = 0; k < m; k++) pos[nb[k]] = (uint32_t)k;
+    std::vector<uint8_t> inc(m, 0), side(m, 0);
+    for (uint32_t i : sel) inc[pos[i]] = 1;
+    // the SASA map of sap.rs:164-168 (serial -> row; rows in atomi order, a later row of the same serial wins) and the residue names that
+    // have a row (sap.rs:172-179)
+    std::vector<uint32_t> rows = sel;
+    sort_rows(s, rows);
+    std::unordered_map<int32_t, int32_t> row_of_serial;
+    std::unordered_set<std::string> resn_with_row;
+    for (uint32_t i : rows) { row_of_serial[s->serial[i]] = (int32_t)pos[i]; resn_with_row.insert(s->res_resn.at(i)); }
+    std::vector<double> x(m), y(m), z(m);
+    std::vector<float> Rm(m), sasa(m), sap(m), sphere(3ull * (uint32_t)n_points);
+    std::vector<uint32_t> code(m);
+    std::vector<int32_t> src(m), count(m);
+    for (uint64_t k = 0; k < m; k++) {
+        const uint32_t i = nb[k];
+        x[k] = s->x[i]; y[k] = s->y[i]; z[k] = s->z[i]; Rm[k] = R[i];
+        side[k] = !is_backbone(s->name.at(i));  // AtomConformerResidueChainModel::is_sidechain
+        code[k] = resn_with_row.count(s->res_resn.at(i)) ? sap_residue_code(s->res_resn.at(i)) : 20u;
+        auto it = row_of_serial.find(s->serial[i]);
+        src[k] = it == row_of_serial.end() ? -1 : it->second;
+    }
+    sasa_sphere_points((uint32_t)n_points, sphere.data());
+    SasaJob j;
+    j.n = m; j.x = x.data(); j.y = y.data(); j.z = z.data(); j.R = Rm.data(); j.include = inc.data(); j.n_points = (uint32_t)n_points; j.sphere = sphere.data();
+    j.sidechain = side.data(); j.res_code = code.data(); j.src = src.data(); j.sap_radius = sap_radius;
+    if ((st = sasa_run(ctx, j, sasa.data(), count.data(), sap.data())) != ARP_OK) return st;
+    // sap.rs:187-215: score by serial over the side-chain atoms of the neighbour set (a later atom of the same serial wins);
+    // sap.rs:218-238: the rows whose serial is a non-backbone serial of the WHOLE structure, with the score of that serial (0 if none)
+    std::unordered_map<int32_t, float> score_of_serial;
+    for (uint64_t k = 0; k < m; k++) if (side[k]) score_of_serial[s->serial[nb[k]]] = sap[k];
+    std::unordered_set<int32_t> non_backbone;
+    for (uint64_t i = 0; i < s->n; i++) if (!is_backbone(s->name.at(i))) non_backbone.insert(s->serial[i]);
+    uint64_t r = 0;
+    for (uint32_t i : rows) {
+        if (!non_backbone.count(s->serial[i])) continue;
+        auto it = score_of_serial.find(s->serial[i]);
+        out_atoms[r] = i; out_sasa[r] = sasa[pos[i]]; out_sap[r] = it == score_of_serial.end() ? 0.0f : it->second;
+        r++;
+    }
+    *n_rows = r;
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+extern "C" arp_status arp_structure_dsasa(arp_context *ctx, const arp_structure *s, const char *groups, float probe, int32_t n_points, int32_t model_num,
+                                          float *out) try {
+    if (!ctx || !s || !groups || !out) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    arp_status st = sasa_check_params(probe, n_points);
+    if (st != ARP_OK) return st;
+    std::vector<std::string> g1, g2;
+    if ((st = parse_groups(s->chain_ids, groups, &g1, &g2)) != ARP_OK) return st;  // utils.rs:71-115 (sasa.rs:411)
+    std::unordered_set<std::string> k1(g1.begin(), g1.end()), k2(g2.begin(), g2.end()), kc = k1;
+    kc.insert(g2.begin(), g2.end());
+    // complex, group 1, group 2 = models 0, 1, 2 of one grid: remove_chains_by (exact ids) then get_chain_sasa's selection (steps 2-4)
+    const std::vector<uint32_t> sets[3] = {select_atoms(s, kc, true, true, false, model_num), select_atoms(s, k1, true, true, false, model_num),
+                                           select_atoms(s, k2, true, true, false, model_num)};
+    std::vector<double> x, y, z;
+    std::vector<float> R;
+    std::vector<uint32_t> model;
+    for (int g = 0; g < 3; g++) {
+        std::vector<float> Rg;
+        if ((st = radii(s, sets[g], probe, &Rg)) != ARP_OK) return st;
+        for (uint32_t i : sets[g]) { x.push_back(s->x[i]); y.push_back(s->y[i]); z.push_back(s->z[i]); R.push_back(Rg[i]); model.push_back((uint32_t)g); }
+    }
+    const uint64_t m = x.size();
+    std::vector<uint8_t> inc(m, 1);
+    std::vector<float> sasa(m), sphere(3ull * (uint32_t)n_points);
+    std::vector<int32_t> count(m);
+    sasa_sphere_points((uint32_t)n_points, sphere.data());
+    SasaJob j;
+    j.n = m; j.x = x.data(); j.y = y.data(); j.z = z.data(); j.R = R.data(); j.include = inc.data(); j.model = model.data();
+    j.n_points = (uint32_t)n_points; j.sphere = sphere.data();
+    if ((st = sasa_run(ctx, j, sasa.data(), count.data(), nullptr)) != ARP_OK) return st;
+    double tot[3] = {0.0, 0.0, 0.0};
+    for (uint64_t k = 0; k < m; k++) tot[model[k]] += (double)sasa[k];
+    const float complex_total = (float)tot[0], g1_total = (float)tot[1], g2_total = (float)tot[2];
+    *out = g1_total + g2_total - complex_total;  // sasa.rs:450 (f32)
+    if (*out < 0.0f) { set_error("Negative dSASA calculated. Please check the input file and chain groups."); return ARP_ERR_BAD_INPUT; }
+    return ARP_OK;
+} ARP_ABI_CATCH

@@ -214,6 +214,55 @@ float arp_sap_weight(const char *resn, float sasa);
 arp_status arp_sap_neighbor_sum(arp_context *ctx, uint64_t n, const double *x, const double *y, const double *z,
                                 const uint8_t *sidechain, const float *weight, float sap_radius, float *out);
 
+/* ---- atom SASA: Shrake-Rupley on the same cell list (reference src/sasa.rs:174-247, get_atom_sasa through rust-sasa) ----
+ * Numerical contract (DESIGN.md "Atom SASA"; tests/sasa_restatement.py restates it in numpy bit for bit):
+ *   inputs as the reference casts them (sasa.rs:193-210): c_i = f32 coordinates, R_i = f32(radius_i + probe) with radius_i the f32
+ *   pdbtbx van_der_waals radius (arp_params.vdw_radius of the element class at the structure level);
+ *   sphere points s_k, k < n_points: arp_sasa_sphere_points (golden spiral, computed in f64 and rounded to f32 -- believed to be rust-sasa's
+ *   formula; that crate is not part of the reference's tree, so this is an assumption);
+ *   point k of atom i is BURIED iff some other selected atom j (self excluded by index) has d^2 < R_j^2 (strict), where
+ *   d^2 = tx^2 + ty^2 + tz^2 evaluated left to right in f64 without contraction, t = (c_i - c_j) + s_k R_i per axis from the f32 values;
+ *   count_i = number of points not buried (exact integer); sasa_i = f32(((4 pi R_i) R_i count_i) / n_points) evaluated in f64.
+ * n_points must be 1..ARP_SASA_MAX_POINTS and probe finite and >= 0, else ARP_ERR_BAD_INPUT (so is a radius that is not finite and >= 0). */
+#define ARP_SASA_MAX_POINTS 4096
+/* xyz: 3 n floats, the unit vectors of the contract. */
+arp_status arp_sasa_sphere_points(uint32_t n, float *xyz);
+/* Raw arrays (host), like arp_sap_neighbor_sum.  include[i] != 0 selects atom i (NULL: all); the others neither bury nor get a value
+ * (sasa 0, count 0).  out_count may be NULL.  Synchronous. */
+arp_status arp_atom_sasa(arp_context *ctx, uint64_t n, const double *x, const double *y, const double *z, const float *radius,
+                         const uint8_t *include, float probe, int32_t n_points, float *out_sasa, int32_t *out_count);
+/* Diagnostics: f32 distance tests (point x list entry) the kernel of the most recent SASA call on ctx made. */
+uint64_t arp_sasa_tests(const arp_context *ctx);
+
+/* Structure level.  The atom selection is the reference's prepare_pdb_for_sasa + filter_pdb_by_model (sasa.rs:27-135, 183-195), in order:
+ *   1. chains: a comma-separated list, entries trimmed, empty entries dropped; empty = all chains;
+ *   2. remove_hydrogens: drop element H;
+ *   3. drop whole residues named HOH H2O D2O WAT TIP TIP3 TIP4 SPC NA CL K CA MG ZN FE MN CU CO NI CD SO4 PO4 NO3 ACE NH2;
+ *   4. only when the structure has more than one model: keep the model whose serial is model_num (the first one for 0 or no match);
+ *   5. keep the atoms whose MODEL serial equals model_num.
+ * Step 5 is the reference's quirk, kept on purpose: a file with MODEL 1..N records and the default model_num 0 selects NO atom, and
+ * model_num 1 on a file without MODEL records (serial 0) selects none either.
+ * out_atoms (n_atoms entries, arp_structure_n_atoms) receives the selected structure atom indices in structure order. */
+arp_status arp_structure_sasa_select(const arp_structure *s, const char *chains, int32_t model_num, int32_t remove_hydrogens,
+                                     uint64_t *n_out, uint32_t *out_atoms);
+/* get_atom_sasa (sasa.rs:174): one row per selected atom, sorted by serial number (atomi; structure order among equal serials).
+ * Every out_* array holds arp_structure_n_atoms(s) entries (an upper bound); *n_rows says how many were written.  out_count may be NULL. */
+arp_status arp_structure_atom_sasa(arp_context *ctx, const arp_structure *s, const char *chains, int32_t model_num, int32_t remove_hydrogens,
+                                   float probe, int32_t n_points, uint64_t *n_rows, uint32_t *out_atoms, float *out_sasa, int32_t *out_count);
+/* get_per_atom_sap_score (sap.rs:137-259): SASA, weights and the neighbour sum on one stream with one synchronisation.  The rows are the
+ * atom-SASA rows (above, hydrogens removed) whose serial is that of a non-backbone atom of the whole structure; sap = the f32 sum, over the
+ * side-chain atoms of the structure after steps 1-3 (NO model filter, all models) within sap_radius (inclusive) of the row's atom with that
+ * serial, of arp_sap_weight(resn, atom SASA of the neighbour's serial), 0 for a neighbour whose serial has no SASA row.  Backbone = atom
+ * names N CA C O OXT (pdbtbx's is_backbone; an assumption).  Arrays and *n_rows as arp_structure_atom_sasa. */
+arp_status arp_structure_sap_score(arp_context *ctx, const arp_structure *s, const char *chains, int32_t model_num, float probe,
+                                   int32_t n_points, float sap_radius, uint64_t *n_rows, uint32_t *out_atoms, float *out_sasa, float *out_sap);
+/* get_dsasa (sasa.rs:400-451) from ATOM-level SASA: groups are parsed as arp_get_contacts does (its errors); each of complex (both groups),
+ * group 1 and group 2 is selected by steps 2-4 above (no step 5: the reference sums chain-level SASA here) and the three run as three
+ * models of one grid in one launch.  *out = f32(g1 + g2 - complex) of the three f32 totals (each summed in f64, rounded once); no halving.
+ * A negative result is written and ARP_ERR_BAD_INPUT returned (python.rs:177-188 raises). */
+arp_status arp_structure_dsasa(arp_context *ctx, const arp_structure *s, const char *groups, float probe, int32_t n_points, int32_t model_num,
+                               float *out);
+
 /* Per-kernel device timing of the most recent call (HIP events on the context's stream).  Enable, run, then read.
  * names[k] points to a static string.  Returns the number of kernels recorded (<= cap). */
 arp_status arp_profile_enable(arp_context *ctx, int32_t on);
