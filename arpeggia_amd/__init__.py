@@ -1,7 +1,7 @@
 """arpeggia_amd: MI355X-native drop-in for the `contacts` path of y1zhou/arpeggia.
 
 Public surface mirrors the reference (src/lib.rs:20-34, src/python.rs:31-56) for this one path:
-contacts(), get_contacts(), load_model(), parse_groups(); and atom-level sasa(), sap_score(), dsasa().  Importing this package loads libarpeggia_amd.so and
+contacts(), get_contacts(), load_model(), parse_groups(); and atom-level sasa(), sap_score(), dsasa(); and sc().  Importing this package loads libarpeggia_amd.so and
 fails loudly if the HIP extension has not been built -- there is no CPU fallback.
 """
 from .api import (  # noqa: F401
@@ -12,6 +12,7 @@ from .api import (  # noqa: F401  atom SASA, SAP score, dSASA (reference src/sas
     atom_sasa, dsasa, get_atom_sasa, get_dsasa, get_per_atom_sap_score, get_per_residue_sap_score, sap_score, sasa, sasa_select,
     sasa_sphere_points, sasa_tests,
 )
+from .api import get_sc, get_sc_results, sc, sc_arrays, sc_dots, sc_radius, sc_select  # noqa: F401  shape complementarity (src/sc/)
 from ._lib import ATTR, INTERACTIONS  # noqa: F401
 
 __version__ = "0.1.0"

@@ -1,6 +1,6 @@
 """Command-line driver: `python -m arpeggia_amd contacts -i model.pdb -o out/` -- the flags and defaults of the reference's
 `arpeggia contacts` (src/cli/contacts.rs:9-52) over the MI355X engine; it writes <output>/<filename>.<format> like cli/contacts.rs:108-137.
-`sasa`, `sap` and `dsasa` take the flags and defaults of src/cli/{sasa,sap,dsasa}.rs (sasa at level "atom" only: see arpeggia_amd/api.py).
+`sasa`, `sap`, `dsasa` and `sc` take the flags and defaults of src/cli/{sasa,sap,dsasa,sc}.rs (sasa at level "atom" only: see arpeggia_amd/api.py).
 """
 from __future__ import annotations
 
@@ -60,7 +60,31 @@ def build_parser() -> argparse.ArgumentParser:
     d.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file to be analyzed")
     d.add_argument("-g", "--groups", required=True, help="Chain groups, e.g. A,B/C,D")
     add(d, "model", "probe", "points", "threads")
+    g = sub.add_parser("sc", help="shape complementarity of two chain groups (cli/sc.rs)")
+    g.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file to be analyzed")
+    g.add_argument("-g", "--groups", required=True, help="Chain groups, e.g. A,B/C,D: both surfaces must be given")
+    g.add_argument("-m", "--model", default=0, type=int, dest="model_num", help="Model number to analyze (0: the first model)")
+    g.add_argument("-j", "--num-threads", default=0, type=int, help="Number of threads (accepted; the computation runs on the GPU)")
     return ap
+
+
+def run_sc(args) -> int:
+    """cli/sc.rs: the groups must contain '/'; logs `SC: {:.4}`; a failure is logged and exits nonzero."""
+    import arpeggia_amd as aa
+
+    if not args.input.exists():
+        log.error("Failed to retrieve input file: %s", args.input)
+        return 1
+    if "/" not in args.groups:
+        log.error("Groups must be specified as 'A,B/C,D' with both surfaces defined")
+        return 2
+    try:
+        v = aa.get_sc(aa.Structure.load(str(args.input.resolve())), args.groups, args.model_num)
+    except aa.ArpeggiaError as e:
+        log.error("SC calculation failed: %s", e)
+        return 1
+    log.info("SC: %.4f", v)
+    return 0
 
 
 def run_surface(args) -> int:
@@ -145,6 +169,8 @@ def run_contacts(args) -> int:
 def main(argv=None) -> int:
     logging.basicConfig(level=logging.INFO, format="%(levelname)s %(message)s", stream=sys.stderr)
     args = build_parser().parse_args(argv)
+    if args.command == "sc":
+        return run_sc(args)
     return run_contacts(args) if args.command == "contacts" else run_surface(args)
 
 

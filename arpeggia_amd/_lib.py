@@ -99,6 +99,20 @@ class ArrowSchema(C.Structure):  # Arrow C Data Interface (ABI-stable), include/
                 ("children", C.c_void_p), ("dictionary", C.c_void_p), ("release", C.c_void_p), ("private_data", C.c_void_p)]
 
 
+class arp_sc_settings(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("probe_radius", "dot_density", "peripheral_band", "separation_cutoff", "gaussian_w")]
+
+
+class arp_sc_surface(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_atoms", "n_buried_atoms", "n_far_atoms", "n_all_dots", "n_trimmed_dots")] + \
+               [(k, C.c_double) for k in ("trimmed_area", "d_mean", "d_median", "s_mean", "s_median")]
+
+
+class arp_sc_results(C.Structure):
+    _fields_ = [("surface", arp_sc_surface * 2), ("combined", arp_sc_surface)] + \
+               [(k, C.c_uint64) for k in ("n_convex", "n_toroidal", "n_concave", "n_probes")] + [(k, C.c_double) for k in ("sc", "distance", "area")]
+
+
 class ArrowArray(C.Structure):
     _fields_ = [("length", C.c_int64), ("null_count", C.c_int64), ("offset", C.c_int64), ("n_buffers", C.c_int64), ("n_children", C.c_int64),
                 ("buffers", C.c_void_p), ("children", C.c_void_p), ("dictionary", C.c_void_p), ("release", C.c_void_p), ("private_data", C.c_void_p)]
@@ -149,6 +163,13 @@ def _load():
         "arp_structure_sap_score": (C.c_int32, [vp, vp, C.c_char_p, C.c_int32, C.c_float, C.c_int32, C.c_float, C.POINTER(C.c_uint64), _u32p,
                                                 C.POINTER(C.c_float), C.POINTER(C.c_float)]),
         "arp_structure_dsasa": (C.c_int32, [vp, vp, C.c_char_p, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
+        "arp_sc_default_settings": (None, [C.POINTER(arp_sc_settings)]),
+        "arp_sc_radius": (C.c_double, [C.c_char_p, C.c_char_p, C.c_char_p]),
+        "arp_sc": (C.c_int32, [vp, C.c_uint64, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(arp_sc_settings),
+                               C.POINTER(arp_sc_results)]),
+        "arp_structure_sc": (C.c_int32, [vp, vp, C.c_char_p, C.c_int32, C.POINTER(arp_sc_results)]),
+        "arp_structure_sc_select": (C.c_int32, [vp, C.c_char_p, C.c_int32, C.POINTER(C.c_uint64), _u32p, C.POINTER(C.c_uint8)]),
+        "arp_sc_dots": (C.c_int32, [vp, C.c_int32, C.c_uint64, C.POINTER(C.c_uint64), _dp, _dp, _dp, _u32p, _dp, _dp]),
         "arp_profile_enable": (C.c_int32, [vp, C.c_int32]),
         "arp_profile_read": (C.c_int32, [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int32]),
         "arp_structure_load": (C.c_int32, [C.c_char_p, C.c_int32, C.POINTER(vp)]),

@@ -672,3 +672,76 @@ def dsasa(input_file: str, groups: str, probe_radius: float = 1.4, n_points: int
     """Drop-in for `arpeggia.dsasa` (python.rs:161-191)."""
     del num_threads
     return get_dsasa(Structure.load(input_file), groups, probe_radius, n_points, model_num)
+
+
+# ---- shape complementarity (reference src/sc/, python.rs:369-381; include/arpeggia_amd.h "shape complementarity")
+def _sc_dict(r: _lib.arp_sc_results) -> dict:
+    surf = lambda s: {k: (int(getattr(s, k)) if k.startswith("n_") else float(getattr(s, k))) for k, _ in _lib.arp_sc_surface._fields_}
+    out = {"surfaces": [surf(r.surface[0]), surf(r.surface[1])], "combined": surf(r.combined)}
+    out.update({k: int(getattr(r, k)) for k in ("n_convex", "n_toroidal", "n_concave", "n_probes")})
+    out.update({k: float(getattr(r, k)) for k in ("sc", "distance", "area")})
+    return out
+
+
+def sc_radius(resn: str, atomn: str, element: str = "") -> float:
+    """Lawrence & Colman radius of (residue, atom) from the reference's table, else the element's van der Waals radius; 0 if none."""
+    return float(lib.arp_sc_radius(resn.encode(), atomn.encode(), element.encode()))
+
+
+def sc_select(structure: Structure, groups: str, model_num: int = 0):
+    """(structure atom indices, molecule 0/1) that get_sc works on (mod.rs:51-80; arp_structure_sc_select)."""
+    m = max(structure.n_atoms, 1)
+    atoms, mol, n = np.zeros(m, dtype="<u4"), np.zeros(m, dtype=np.uint8), C.c_uint64()
+    _check(lib.arp_structure_sc_select(structure._h, groups.encode(), int(model_num), C.byref(n), atoms.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                       mol.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return atoms[: n.value].copy(), mol[: n.value].copy()
+
+
+def sc_arrays(ctx: Context, x, y, z, radius, molecule, serial=None, settings: dict | None = None) -> dict:
+    """arp_sc on raw arrays: molecule 0/1 per atom, serial None = the index.  Returns the results dict of get_sc_results."""
+    x, y, z, r = (np.ascontiguousarray(a, dtype=np.float64) for a in (x, y, z, radius))
+    mol = np.ascontiguousarray(molecule, dtype=np.uint8)
+    ser = None if serial is None else np.ascontiguousarray(serial, dtype=np.int64)
+    st = _lib.arp_sc_settings()
+    lib.arp_sc_default_settings(C.byref(st))
+    for k, v in (settings or {}).items():
+        setattr(st, k, float(v))
+    res = _lib.arp_sc_results()
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    _check(lib.arp_sc(ctx._h, len(x), dp(x), dp(y), dp(z), dp(r), mol.ctypes.data_as(C.POINTER(C.c_uint8)),
+                      None if ser is None else ser.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(st), C.byref(res)))
+    return _sc_dict(res)
+
+
+def sc_dots(ctx: Context, surface: int) -> dict:
+    """The dots of one surface of ctx's last SC call (arp_sc_dots): xyz, normal, area, flags, nn_dist, score."""
+    n = C.c_uint64()
+    _check(lib.arp_sc_dots(ctx._h, int(surface), 0, C.byref(n), None, None, None, None, None, None))
+    m = n.value
+    d = {"xyz": np.zeros((m, 3)), "normal": np.zeros((m, 3)), "area": np.zeros(m), "flags": np.zeros(m, dtype="<u4"), "nn_dist": np.zeros(m),
+         "score": np.zeros(m)}
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    _check(lib.arp_sc_dots(ctx._h, int(surface), m, C.byref(n), dp(d["xyz"]), dp(d["normal"]), dp(d["area"]),
+                           d["flags"].ctypes.data_as(C.POINTER(C.c_uint32)), dp(d["nn_dist"]), dp(d["score"])))
+    return d
+
+
+def get_sc_results(structure: Structure, groups: str, model_num: int = 0, device: int = 0) -> dict:
+    """Every result of `get_sc` (mod.rs:51-80): per surface, combined, dot and probe counts, sc, distance, area."""
+    res = _lib.arp_sc_results()
+    _check(lib.arp_structure_sc(_context(device)._h, structure._h, groups.encode(), int(model_num), C.byref(res)))
+    return _sc_dict(res)
+
+
+def get_sc(structure: Structure, groups: str, model_num: int = 0, device: int = 0) -> float:
+    """`arpeggia::get_sc`: the shape complementarity of the two chain groups."""
+    return get_sc_results(structure, groups, model_num, device)["sc"]
+
+
+def sc(input_file: str, groups: str, model_num: int = 0, num_threads: int = 0) -> float:
+    """Drop-in for `arpeggia.sc` (python.rs:369-381): raises RuntimeError("SC calculation failed: ...") on failure."""
+    del num_threads
+    try:
+        return get_sc(Structure.load(input_file), groups, model_num)
+    except ArpeggiaError as e:
+        raise RuntimeError(f"SC calculation failed: {e}") from e

@@ -1,6 +1,7 @@
 // Internal declarations shared by the HIP kernels (kernels.hip) and the host engine (engine.cpp).
 #pragma once
 #include <cstdint>
+#include <vector>
 #include <hip/hip_runtime.h>
 
 #include "../../include/arpeggia_amd.h"
@@ -195,6 +196,31 @@ void launch_sasa(const DevAtoms &in, const Workspace &ws, double cutoff, const f
 // w[j] = arp_sap_weight(ARP_SAP_RESIDUES name code[j], sasa[src[j]]), 0 where src[j] < 0 or code[j] >= 20
 void launch_sap_weight(uint32_t n, const uint32_t *code, const int32_t *src, const float *sasa, float *w, hipStream_t st);
 void launch_pack_fix(const PackArrays &pa, hipStream_t st);
+// Shape complementarity (sc.inl).  Dot and probe records as the kernels write them; arp_sc_dots copies from the dots.
+struct ScDot {        // 80 B
+    double p[3], n[3], area, nn_dist, score;
+    uint32_t atom, flags;  // flags: kind (ARP_SC_DOT_*) | ARP_SC_DOT_BURIED | ARP_SC_DOT_TRIMMED
+};
+struct ScProbe {      // 72 B
+    double p[3], alt[3], height;
+    uint32_t a[3], i;  // a: the reference's atom_indices; i: the first atom of the pair the probe came from (its burial candidate list)
+};
+constexpr uint32_t kScErrCoincident = 1, kScErrSubdiv = 2;
+struct ScJob {
+    uint32_t n;
+    const double *x, *y, *z, *r;   // host arrays
+    const uint32_t *mol;           // 0 / 1
+    const long long *serial;
+    double rp, density, band, sep, w;
+};
+struct ScRunOut {
+    std::vector<ScDot> dots[2];    // toroidal, contact, concave: the reference's order
+    uint64_t n_toroidal = 0, n_convex = 0, n_concave = 0, n_probes = 0;
+    std::vector<uint32_t> att;     // 1: Buried, 0: Far
+    uint32_t err = 0, err_i = 0, err_j = 0;  // kScErr*: Coincident (atoms err_i, err_j) or TooManySubdivisions
+};
+// Runs every device stage on `st` (synchronising for the sizes of the outputs).  ARP_ERR_HIP on a runtime failure; the SC errors in out->err.
+arp_status launch_sc(const ScJob &job, hipStream_t st, Profiler *prof, ScRunOut *out);
 void launch_pack_split(const PackArrays &pa, const unsigned long long *result, const arp_pair *pairs, unsigned long long capacity, arp_pair *grouped, bool ordered, hipStream_t st);
 
 }  // namespace arp

@@ -126,6 +126,7 @@ struct arp_context {
     // Residue-rule memo: the last input's residues were runs of atoms (k_place's sample, result[4]) -- the next call's launcher then picks the
     // kernels that apply the reference's residue rule before the gathers (k_emit<.., RES>).  Same result either way; ARP_FLAG_RESIDUE_RUNS /
     // ARP_FLAG_NO_RESIDUE_RUNS overrule the memo.
+    std::vector<ScDot> sc_dots[2];          // the dots of the last successful SC call (arp_sc_dots)
     bool res_hint = false;
     bool rkey_valid = false;               // the workspace's residue words (Sorted::rkey) belong to the cell list that was built last
     // Deferred-pass memo: the arrays (address + length) of the last single-pass call that deferred NOTHING to the probe pass (no hydrogens,
@@ -1338,6 +1339,16 @@ bool context_grid(arp_context *ctx, const double *x, uint64_t n, const GridParam
     if (!ctx || ctx->pending || !ctx->ws.grid || !x || ctx->grid_x != x || ctx->grid_n != n) return false;
     *grid = ctx->ws.grid; *cell_start = ctx->ws.cell_start; *fat = ctx->ws.sorted.fat;
     return true;
+}
+arp_status context_sc(arp_context *ctx, bool call, hipStream_t *st, Profiler **prof, std::vector<ScDot> **dots) {
+    arp_status s = check_device(ctx);
+    if (s != ARP_OK) return s;
+    if (ctx->pending) { set_error("a call enqueued on this context has not been collected (arp_contacts_atomic_result)"); return ARP_ERR_BAD_INPUT; }
+    *st = ctx->stream;
+    *prof = ctx->prof.enabled ? &ctx->prof : nullptr;
+    if (*prof && call) ctx->prof.n = 0;  // the timings of this call only
+    *dots = ctx->sc_dots;
+    return ARP_OK;
 }
 arp_status context_scratch(arp_context *ctx, int slot, uint64_t dev_bytes, uint64_t pinned_bytes, char **dev, char **pinned) {
     arp_status s = check_device(ctx);

@@ -9,6 +9,7 @@
 #include <string>
 #include <system_error>
 #include <thread>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/arpeggia_amd.h"
@@ -111,6 +112,9 @@ void sasa_sphere_points(uint32_t n, float *xyz);
 uint32_t sap_residue_code(const char *resn);
 arp_status sasa_check_params(float probe, int32_t n_points);  // ARP_ERR_BAD_INPUT + message unless 1 <= n_points <= ARP_SASA_MAX_POINTS, probe finite >= 0  // position in ARP_SAP_RESIDUES (case-insensitive, as arp_sap_weight), 20 if none
 
+// sasa.cpp: steps 1-5 of arp_structure_sasa_select (keep: chain ids, empty = all; model_filter: step 4; serial_filter: step 5)
+std::vector<uint32_t> select_atoms(const arp_structure *s, const std::unordered_set<std::string> &keep, bool remove_h, bool model_filter,
+                                   bool serial_filter, int32_t model_num);
 arp_status parse_groups(const std::vector<std::string> &all_chains, const char *groups, std::vector<std::string> *ligand,
                         std::vector<std::string> *receptor);
 arp_status apply_groups(arp_structure *s, const char *groups);

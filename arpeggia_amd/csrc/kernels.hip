@@ -281,5 +281,6 @@ DEVFN float dist_f32(double s) {
 #include "batch.inl"
 #include "sap.inl"
 #include "sasa.inl"
+#include "sc.inl"
 
 }  // namespace arp

@@ -44,7 +44,8 @@ static std::unordered_set<std::string> chain_set(const char *chains) {
 }
 
 // Steps 1-5 of arpeggia_amd.h arp_structure_sasa_select.  keep: chain ids to keep (empty = all); model_filter: step 4; serial_filter: step 5.
-static std::vector<uint32_t> select_atoms(const arp_structure *s, const std::unordered_set<std::string> &keep, bool remove_h, bool model_filter,
+// (Also the selection of shape complementarity, sc.cpp: steps 1-4.)
+std::vector<uint32_t> select_atoms(const arp_structure *s, const std::unordered_set<std::string> &keep, bool remove_h, bool model_filter,
                                           bool serial_filter, int32_t model_num) {
     const uint64_t n = s->n;
     uint32_t n_models = 0;

@@ -263,6 +263,55 @@ arp_status arp_structure_sap_score(arp_context *ctx, const arp_structure *s, con
 arp_status arp_structure_dsasa(arp_context *ctx, const arp_structure *s, const char *groups, float probe, int32_t n_points, int32_t model_num,
                                float *out);
 
+/* ---- shape complementarity (Lawrence & Colman 1993; reference src/sc/, get_sc) -- DESIGN.md section 3.6 ----
+ * Every quantity is f64 and follows the reference's rules and order; sums run in dot order; of two nearest dots at equal distance the
+ * lower index wins; same-molecule neighbours at equal distance are ordered by atom index. */
+typedef struct arp_sc_settings {
+    double probe_radius;       /* rp, 1.7 (must be > 0) */
+    double dot_density;        /* dots per A^2, 15 */
+    double peripheral_band;    /* A, 1.5 */
+    double separation_cutoff;  /* A, 8 */
+    double gaussian_w;         /* A^-2, 0.5 */
+} arp_sc_settings;
+void arp_sc_default_settings(arp_sc_settings *out);
+typedef struct arp_sc_surface {
+    uint64_t n_atoms, n_buried_atoms, n_far_atoms, n_all_dots, n_trimmed_dots;
+    double trimmed_area, d_mean, d_median, s_mean, s_median;
+} arp_sc_surface;
+typedef struct arp_sc_results {
+    arp_sc_surface surface[2];
+    arp_sc_surface combined;   /* counts and area: sums; means and medians: midpoints of the two surfaces */
+    uint64_t n_convex, n_toroidal, n_concave, n_probes;
+    double sc, distance, area; /* combined s_median, d_median, trimmed_area */
+} arp_sc_results;
+/* The Lawrence & Colman radius of (residue, atom name) from the reference's table (first match, '*' wildcards), else the element's
+ * van der Waals radius (arp_params.vdw_radius); 0 when neither exists.  Host only. */
+double arp_sc_radius(const char *resn, const char *atomn, const char *element);
+/* Raw arrays (host): molecule[i] is 0 or 1; serial NULL = the index (serials must be distinct: the reference keys its maps by them);
+ * radius > 0.  settings NULL = the defaults.  Errors (ARP_ERR_BAD_INPUT, arp_last_error holds the reference's text): "No atoms defined",
+ * "Failed to read radii: No atoms for chain group 1", "Overlapping atoms detected: ...", "Sampling limit exceeded",
+ * "Failed to read radii: No molecular dots generated".  Synchronous. */
+arp_status arp_sc(arp_context *ctx, uint64_t n, const double *x, const double *y, const double *z, const double *radius, const uint8_t *molecule,
+                  const int64_t *serial, const arp_sc_settings *settings, arp_sc_results *out);
+/* get_sc (src/sc/mod.rs:51-80): groups parsed as arp_get_contacts does (its errors); the atoms are steps 1-4 of arp_structure_sasa_select
+ * (hydrogens removed, chains = both groups, NO step 5) with molecule 0 for a chain of group 1, else 1; radii from arp_sc_radius (an atom
+ * without one is refused).  Duplicate serial numbers among the selected atoms are refused. */
+arp_status arp_structure_sc(arp_context *ctx, const arp_structure *s, const char *groups, int32_t model_num, arp_sc_results *out);
+/* The selection of arp_structure_sc without running it: out_atoms / out_molecule hold arp_structure_n_atoms(s) entries; *n_out are written. */
+arp_status arp_structure_sc_select(const arp_structure *s, const char *groups, int32_t model_num, uint64_t *n_out, uint32_t *out_atoms,
+                                   uint8_t *out_molecule);
+/* The dots of surface 0 / 1 of the context's last successful SC call, in the reference's order (toroidal by pair (i, j), ring point,
+ * side i then j, arc point; then contact by atom, latitude, point; then concave by probe).  *n = the count; the arrays are written when
+ * cap >= *n (any may be NULL): xyz and normal 3 per dot; flags = kind | ARP_SC_DOT_BURIED | ARP_SC_DOT_TRIMMED; nn_dist and score are
+ * set on trimmed dots (0 elsewhere). */
+#define ARP_SC_DOT_CONVEX 0
+#define ARP_SC_DOT_TOROIDAL 1
+#define ARP_SC_DOT_CONCAVE 2
+#define ARP_SC_DOT_BURIED 4
+#define ARP_SC_DOT_TRIMMED 8
+arp_status arp_sc_dots(arp_context *ctx, int32_t surface, uint64_t cap, uint64_t *n, double *xyz, double *normal, double *area, uint32_t *flags,
+                       double *nn_dist, double *score);
+
 /* Per-kernel device timing of the most recent call (HIP events on the context's stream).  Enable, run, then read.
  * names[k] points to a static string.  Returns the number of kernels recorded (<= cap). */
 arp_status arp_profile_enable(arp_context *ctx, int32_t on);
