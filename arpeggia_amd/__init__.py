@@ -1,7 +1,8 @@
 """arpeggia_amd: MI355X-native drop-in for the `contacts` path of y1zhou/arpeggia.
 
 Public surface mirrors the reference (src/lib.rs:20-34, src/python.rs:31-56) for this one path:
-contacts(), get_contacts(), load_model(), parse_groups(); and atom-level sasa(), sap_score(), dsasa(); and sc().  Importing this package loads libarpeggia_amd.so and
+contacts(), get_contacts(), load_model(), parse_groups(); and atom-level sasa(), sap_score(), dsasa(); and sc(); and
+contact_frequencies() across the frames of an ensemble (no counterpart in the reference).  Importing this package loads libarpeggia_amd.so and
 fails loudly if the HIP extension has not been built -- there is no CPU fallback.
 """
 from .api import (  # noqa: F401
@@ -13,6 +14,7 @@ from .api import (  # noqa: F401  atom SASA, SAP score, dSASA (reference src/sas
     sasa_sphere_points, sasa_tests,
 )
 from .api import get_sc, get_sc_results, sc, sc_arrays, sc_dots, sc_radius, sc_select  # noqa: F401  shape complementarity (src/sc/)
+from .api import FREQ_COLUMNS, contact_frequencies, get_contact_frequencies  # noqa: F401  contact frequencies across the frames of an ensemble
 from ._lib import ATTR, INTERACTIONS  # noqa: F401
 
 __version__ = "0.1.0"

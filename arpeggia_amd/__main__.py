@@ -1,6 +1,7 @@
 """Command-line driver: `python -m arpeggia_amd contacts -i model.pdb -o out/` -- the flags and defaults of the reference's
 `arpeggia contacts` (src/cli/contacts.rs:9-52) over the MI355X engine; it writes <output>/<filename>.<format> like cli/contacts.rs:108-137.
 `sasa`, `sap`, `dsasa` and `sc` take the flags and defaults of src/cli/{sasa,sap,dsasa,sc}.rs (sasa at level "atom" only: see arpeggia_amd/api.py).
+`contact-frequency` (no counterpart in the reference) takes the flags and defaults of `contacts`; the models of the input file are the frames.
 """
 from __future__ import annotations
 
@@ -28,6 +29,16 @@ def build_parser() -> argparse.ArgumentParser:
     c.add_argument("-d", "--dist-cutoff", default=6.5, type=float, help="Distance cutoff when searching for neighboring atoms")
     c.add_argument("-j", "--num-threads", default=1, type=int, help="Host threads of the table path (0 = all cores); the search runs on the GPU")
     c.add_argument("--ignore-zero-occupancy", action="store_true", help="Ignore atoms with zero occupancy")
+    q = sub.add_parser("contact-frequency", help="how often each atom-atom contact occurs across the models of a multi-model file")
+    q.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file whose models are the frames")
+    q.add_argument("-o", "--output", required=True, type=Path, help="Output directory")
+    q.add_argument("-g", "--groups", default="/", help="Chain groups, e.g. A,B/C,D ('/' = all against all)")
+    q.add_argument("-f", "--filename", default="contact_frequency", help="Name of the output file")
+    q.add_argument("-t", "--output-format", default="csv", type=str.lower, choices=FORMATS, help="Output file type")
+    q.add_argument("-c", "--vdw-comp", default=0.1, type=float, help="Compensation factor for VdW radii dependent interaction types")
+    q.add_argument("-d", "--dist-cutoff", default=6.5, type=float, help="Distance cutoff when searching for neighboring atoms")
+    q.add_argument("-j", "--num-threads", default=1, type=int, help="Number of threads (accepted; the computation runs on the GPU)")
+    q.add_argument("--ignore-zero-occupancy", action="store_true", help="Ignore atoms with zero occupancy")
     common = dict(model=("-m", "--model", 0, int, "Model number to analyze (0: the first model)"),
                   probe=("-r", "--probe-radius", 1.4, float, "Probe radius in Angstroms"),
                   points=("-n", "--num-points", 100, int, "Number of points for surface calculation"),
@@ -166,11 +177,31 @@ def run_contacts(args) -> int:
     return 0
 
 
+def run_contact_frequency(args) -> int:
+    import arpeggia_amd as aa
+
+    if not args.input.exists():
+        log.error("Failed to retrieve input file: %s", args.input)
+        return 1
+    try:
+        table = aa.contact_frequencies(str(args.input.resolve()), args.groups, args.vdw_comp, args.dist_cutoff, args.ignore_zero_occupancy)
+    except aa.ArpeggiaError as e:
+        log.error("Contact frequencies failed: %s", e)
+        return 1
+    args.output.mkdir(parents=True, exist_ok=True)
+    out = (args.output / args.filename).with_suffix("." + args.output_format)
+    write_table(table, out, args.output_format)
+    log.info("Results for %d contacts saved to %s", len(table), out)
+    return 0
+
+
 def main(argv=None) -> int:
     logging.basicConfig(level=logging.INFO, format="%(levelname)s %(message)s", stream=sys.stderr)
     args = build_parser().parse_args(argv)
     if args.command == "sc":
         return run_sc(args)
+    if args.command == "contact-frequency":
+        return run_contact_frequency(args)
     return run_contacts(args) if args.command == "contacts" else run_surface(args)
 
 

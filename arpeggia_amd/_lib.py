@@ -189,6 +189,7 @@ def _load():
         "arp_table_rows": (C.c_uint64, [vp]),
         "arp_table_column": (vp, [vp, C.c_char_p, C.POINTER(C.c_int32)]),
         "arp_table_export_arrow": (C.c_int32, [vp, C.POINTER(ArrowArray), C.POINTER(ArrowSchema)]),
+        "arp_contact_frequencies": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_double, C.c_double, C.POINTER(vp)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here == the library does not export what the header declares

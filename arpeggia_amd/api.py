@@ -28,6 +28,15 @@ TABLE_COLUMNS = [  # mod.rs:140-181 + 209-211, in the reference's order with its
     ("sc_centroid_dist", "f4"), ("sc_dihedral", "f4"), ("sc_centroid_angle", "f4"),
 ]
 
+FREQ_COLUMNS = [  # arp_contact_frequencies (include/arpeggia_amd.h): one row per distinct (from atom, to atom, interaction) over the frames
+    ("interaction", "str"),
+    ("from_chain", "str"), ("from_resn", "str"), ("from_resi", "i4"), ("from_insertion", "str"), ("from_altloc", "str"),
+    ("from_atomn", "str"), ("from_atomi", "i4"),
+    ("to_chain", "str"), ("to_resn", "str"), ("to_resi", "i4"), ("to_insertion", "str"), ("to_altloc", "str"),
+    ("to_atomn", "str"), ("to_atomi", "i4"),
+    ("n_frames", "u4"), ("frequency", "f4"), ("min_distance", "f4"), ("max_distance", "f4"),
+]
+
 
 class ArpeggiaError(RuntimeError):
     """Raised where the reference panics (pyo3_runtime.PanicException) or a HIP call fails."""
@@ -338,6 +347,62 @@ class Context:
         finally:
             lib.arp_table_free(t)
 
+    def contact_frequencies(self, structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5) -> dict:
+        """arp_contact_frequencies as a dict of numpy columns (FREQ_COLUMNS + from_atom / to_atom).  frames: [F, N, 3] f64 coordinates of the
+        topology's N atoms (model 0 of `structure`); None: the structure's models are the frames."""
+        t = _freq_table(self, structure, frames, groups, vdw_comp, dist_cutoff)
+        try:
+            n = int(lib.arp_table_rows(t))
+            cols = {}
+
+            def col(name, dtype=None):
+                w = C.c_int32()
+                p = lib.arp_table_column(t, name.encode(), C.byref(w))
+                if not p and n:
+                    raise KeyError(name)
+                return _np_from(p, n, dtype or f"S{max(w.value, 1)}")
+
+            for name, kind in FREQ_COLUMNS:
+                if name == "interaction":
+                    cols[name] = col(name, "<i4")
+                elif kind == "str":
+                    cols[name] = col(name)
+                else:
+                    cols[name] = col(name, "<" + kind)
+            cols["from_atom"] = col("from_atom", "<i4")
+            cols["to_atom"] = col("to_atom", "<i4")
+            return cols
+        finally:
+            lib.arp_table_free(t)
+
+
+def _topology_atoms(structure: Structure) -> int:
+    """Atoms of model 0 (the topology of arp_contact_frequencies): the leading run of the first MODEL serial."""
+    m = structure.ints("model")
+    if len(m) == 0:
+        return 0
+    other = np.flatnonzero(m != m[0])
+    return int(other[0]) if len(other) else len(m)
+
+
+def _freq_table(ctx: "Context | None", structure: Structure, frames, groups: str, vdw_comp: float, dist_cutoff: float):
+    """arp_contact_frequencies -> table handle (the caller frees it).  ctx None: the inputs are only checked (raises their error, else returns None)."""
+    if frames is None:
+        n_frames, ptr, keep = 0, None, None
+    else:
+        keep = np.ascontiguousarray(frames, dtype="<f8")
+        n = _topology_atoms(structure)
+        if keep.ndim != 3 or keep.shape[1:] != (n, 3):
+            raise ArpeggiaError(_lib.ARP_ERR_BAD_INPUT, f"contact frequencies: frames must have shape [F, {n}, 3] (the topology's atoms), got {list(keep.shape)}")
+        n_frames = keep.shape[0]
+        if keep.size == 0:
+            keep = np.zeros(1, dtype="<f8")  # (a valid pointer; n_frames == 0 is refused by the library)
+        ptr = keep.ctypes.data_as(C.POINTER(C.c_double))
+    t = C.c_void_p()
+    _check(lib.arp_contact_frequencies(ctx._h if ctx is not None else None, structure._h, int(n_frames), ptr, groups.encode(), float(vdw_comp),
+                                       float(dist_cutoff), C.byref(t)))
+    return t if ctx is not None else None
+
 
 def sap_weight(resn: str, sasa: float) -> float:
     """hydrophobicity(resn) * clamp(sasa / max side-chain SASA(resn), 0, 1) as src/sap.rs:41-101,198-209 forms it (f32)."""
@@ -432,6 +497,38 @@ def contacts(input_file: str, groups: str = "/", vdw_comp: float = 0.1, dist_cut
     """
     s = Structure.load(input_file, ignore_zero_occupancy)
     return get_contacts(s, groups, vdw_comp, dist_cutoff, num_threads=int(num_threads))
+
+
+def get_contact_frequencies(structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, device: int = 0):
+    """How often every atom-atom contact occurs across the frames of an ensemble (arp_contact_frequencies): one row per distinct
+    (from atom, to atom, interaction) with n_frames, frequency, min_distance and max_distance (FREQ_COLUMNS).  frames: [F, N, 3] f64
+    coordinates of the N atoms of the topology (model 0 of `structure`); None: the structure's models are the frames.  Returns a
+    polars.DataFrame when polars is importable, else a pyarrow.Table, like get_contacts."""
+    import pyarrow as pa
+
+    try:
+        ctx = _context(device)
+    except ArpeggiaError:
+        _freq_table(None, structure, frames, groups, vdw_comp, dist_cutoff)  # an input error takes precedence over the missing device
+        raise
+    t = _freq_table(ctx, structure, frames, groups, vdw_comp, dist_cutoff)
+    try:
+        arr, sch = _lib.ArrowArray(), _lib.ArrowSchema()
+        _check(lib.arp_table_export_arrow(t, C.byref(arr), C.byref(sch)))
+    finally:
+        lib.arp_table_free(t)
+    table = pa.Table.from_batches([pa.RecordBatch._import_from_c(C.addressof(arr), C.addressof(sch))])
+    try:
+        import polars as pl
+
+        return pl.from_arrow(table)
+    except ImportError:
+        return table
+
+
+def contact_frequencies(input_file: str, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, ignore_zero_occupancy: bool = False):
+    """Contact frequencies across the models of a multi-model file (NMR models, MODEL-record snapshots): see get_contact_frequencies."""
+    return get_contact_frequencies(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff)
 
 
 def contacts_batch(input_files, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, ignore_zero_occupancy: bool = False,

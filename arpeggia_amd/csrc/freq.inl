@@ -1,0 +1,286 @@
+// Contact frequencies over the frames of an ensemble (arp_contact_frequencies).  Included by table_dev.hip inside
+// namespace arp, after the table kernels (k_iota is shared).
+//
+// F frames of one topology run as F models of one packed input: every model owns its own z slab of the grid, so no pair crosses frames
+// (batch.inl makes the same argument for packed structures).  Only the coordinates cross PCIe per frame; k_freq_tile writes the per-frame
+// copies of the topology's arrays on the device with the index offsets of frame f and model ordinal f.  The pair list of a chunk of frames
+// becomes (key, value) items -- key = i_top << 34 | j_top << 5 | code, value = {1 frame, distance, distance} -- which are appended to the
+// running aggregate (one item per distinct key so far), sorted by key and reduced run by run.  Memory stays bounded by the distinct rows and
+// one chunk's items, whatever F is, and only the aggregate comes back.
+
+constexpr uint32_t kFreqKeyShiftI = 34, kFreqKeyShiftJ = 5;
+constexpr uint64_t kFreqAutoAtoms = 1u << 21;  // atoms per pass when the knob freq_chunk_atoms is 0: 1ubq x 3000 frames, 6bft x 230
+
+// {frames, min, max} of one key; min / max are order-preserving codes of the f32 distances, so that unsigned atomics order them like floats
+struct FreqVal { uint32_t count, mn, mx; };
+__device__ inline uint32_t freq_code(float f) {
+    const uint32_t b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// topology arrays (device, frame 0) and the packed arrays of a chunk of `frames` frames
+struct FreqTopo {
+    uint32_t n, n_res, n_h;
+    const uint32_t *attr, *res_ord, *chain_rank, *res_id, *res_h_ptr, *res_h_idx, *res_cb, *res_sg;
+};
+struct FreqPack {
+    double *x, *y, *z;
+    uint32_t *attr, *res_ord, *chain_rank, *model, *res_id, *res_h_ptr, *res_h_idx, *res_cb, *res_sg;
+};
+
+// item t = (frame f, entry k) of W = max(n, n_res + 1, n_h) entries per frame: atom k, residue k, hydrogen-list entry k of frame f.
+// xyz: the chunk's coordinates as they came from the host, frames x n x 3.
+__global__ __launch_bounds__(256) void k_freq_tile(uint32_t frames, uint32_t W, const double *xyz, FreqTopo t, FreqPack p) {
+    const unsigned long long total = (unsigned long long)frames * W;
+    for (unsigned long long q = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (unsigned long long)gridDim.x * blockDim.x) {
+        const uint32_t f = (uint32_t)(q / W), k = (uint32_t)(q % W);
+        const uint32_t atom0 = f * t.n, res0 = f * t.n_res, h0 = f * t.n_h;  // (frames x n < 2^32: checked by the host)
+        if (k < t.n) {
+            const uint32_t a = atom0 + k;
+            const double *c = xyz + 3ull * a;
+            p.x[a] = c[0]; p.y[a] = c[1]; p.z[a] = c[2];
+            p.attr[a] = t.attr[k]; p.res_ord[a] = t.res_ord[k]; p.chain_rank[a] = t.chain_rank[k];
+            p.model[a] = f;
+            if (t.n_res) p.res_id[a] = t.res_id[k] + res0;
+        }
+        if (k < t.n_res) {
+            const uint32_t r = res0 + k;
+            p.res_h_ptr[r] = t.res_h_ptr[k] + h0;
+            const uint32_t cb = t.res_cb[k], sg = t.res_sg[k];
+            p.res_cb[r] = cb == ARP_NONE ? ARP_NONE : cb + atom0;
+            p.res_sg[r] = sg == ARP_NONE ? ARP_NONE : sg + atom0;
+        }
+        if (t.n_res && k == t.n_res && f + 1u == frames) p.res_h_ptr[frames * t.n_res] = frames * t.n_h;
+        if (k < t.n_h) p.res_h_idx[h0 + k] = t.res_h_idx[k] + atom0;
+    }
+}
+
+// one item per set bit of a pair's kind word, appended at base + (a place reserved with one atomic per wave); nothing is written at or past
+// cap, but *counter still counts every item (the host then grows the buffers and runs this again on the same pair list)
+__global__ __launch_bounds__(256) void k_freq_expand(const arp_pair *pairs, uint32_t n_pairs, uint32_t n, unsigned long long *keys, FreqVal *vals, uint32_t base,
+                                                     uint32_t cap, uint32_t *counter) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63u;
+    arp_pair q = {0u, 0u, 0.0f, 0u};
+    if (p < n_pairs) q = pairs[p];
+    const uint32_t kind = q.kind & ((1u << ARP_N_INTERACTIONS) - 1u);
+    const uint32_t cnt = (uint32_t)__popc(kind);
+    uint32_t incl = cnt;  // inclusive prefix over the wave
+    for (uint32_t off = 1; off < 64u; off <<= 1) {
+        const uint32_t v = (uint32_t)__shfl_up((int)incl, off);
+        if (lane >= off) incl += v;
+    }
+    const uint32_t wave_total = (uint32_t)__shfl((int)incl, 63);
+    uint32_t at = 0;
+    if (lane == 63u && wave_total) at = atomicAdd(counter, wave_total);
+    at = (uint32_t)__shfl((int)at, 63);
+    if (!cnt) return;
+    // i and j are atoms of the same frame: their topology indices are the packed indices modulo n
+    const unsigned long long ij = ((unsigned long long)(q.i % n) << kFreqKeyShiftI) | ((unsigned long long)(q.j % n) << kFreqKeyShiftJ);
+    const uint32_t d = freq_code(q.dist);
+    unsigned long long o = (unsigned long long)base + at + (incl - cnt);
+    for (uint32_t b = kind; b; b &= b - 1u, ++o) {
+        if (o >= cap) break;
+        keys[o] = ij | (unsigned long long)(__ffs((int)b) - 1);
+        vals[o] = FreqVal{1u, d, d};
+    }
+}
+
+// sorted items: flag the first item of every key
+__global__ __launch_bounds__(256) void k_freq_heads(uint32_t m, const unsigned long long *keys, uint32_t *head) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < m) head[t] = (t == 0u || keys[t] != keys[t - 1u]) ? 1u : 0u;
+}
+__global__ __launch_bounds__(256) void k_freq_init(uint32_t m, FreqVal *out) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < m) out[t] = FreqVal{0u, 0xFFFFFFFFu, 0u};
+}
+// run r (run = inclusive scan of the heads - 1): the wave first combines its items per run (runs are contiguous), then the first lane of each
+// run in the wave adds the run's share with one atomic per field -- integer sums, minima and maxima, so the result is the same in any order
+__global__ __launch_bounds__(256) void k_freq_reduce(uint32_t m, const unsigned long long *keys, const uint32_t *idx, const FreqVal *vals, const uint32_t *run_incl,
+                                                     unsigned long long *out_keys, FreqVal *out) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63u;
+    const bool have = t < m;
+    uint32_t r = 0xFFFFFFFFu;
+    FreqVal v{0u, 0xFFFFFFFFu, 0u};
+    if (have) { r = run_incl[t] - 1u; v = vals[idx[t]]; }
+    for (uint32_t off = 1; off < 64u; off <<= 1) {
+        const uint32_t r2 = (uint32_t)__shfl_down((int)r, off);
+        const uint32_t c2 = (uint32_t)__shfl_down((int)v.count, off), mn2 = (uint32_t)__shfl_down((int)v.mn, off), mx2 = (uint32_t)__shfl_down((int)v.mx, off);
+        if (lane + off < 64u && r2 == r) { v.count += c2; v.mn = min(v.mn, mn2); v.mx = max(v.mx, mx2); }
+    }
+    const uint32_t r_prev = (uint32_t)__shfl_up((int)r, 1);
+    if (!have || (lane != 0u && r_prev == r)) return;
+    atomicAdd(&out[r].count, v.count);
+    atomicMin(&out[r].mn, v.mn);
+    atomicMax(&out[r].mx, v.mx);
+    if (t == 0u || keys[t - 1u] != keys[t]) out_keys[r] = keys[t];
+}
+
+namespace {
+uint32_t freq_blocks(unsigned long long items) { return (uint32_t)std::max<unsigned long long>(1ull, (items + 255u) / 256u); }  // (items < 2^32: one thread each)
+
+// the aggregate and one chunk's items: kin / vin hold the aggregate (first n_agg) + the new items; the sort and the reduction write the other set
+struct FreqBufs {
+    char *block = nullptr;
+    uint64_t cap = 0;  // items
+    unsigned long long *kin = nullptr, *ks = nullptr, *kout = nullptr;
+    FreqVal *vin = nullptr, *vout = nullptr;
+    uint32_t *iota = nullptr, *is = nullptr, *head = nullptr, *scan = nullptr, *counter = nullptr;
+    void *tmp = nullptr; size_t tmp_bytes = 0;
+};
+arp_status freq_alloc(FreqBufs *b, uint64_t cap, uint64_t keep, hipStream_t st) {
+    if (cap > 0x7FFFFFF0ull) { set_error("contact frequencies: more than 2^31 items in one pass (lower freq_chunk_atoms)"); return ARP_ERR_CAPACITY; }
+    size_t sort_bytes = 0, scan_bytes = 0;
+    TRY_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (const uint32_t *)nullptr,
+                                               (uint32_t *)nullptr, (int)cap, 0, 64, st));
+    TRY_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)cap, st));
+    const size_t tmp = std::max(sort_bytes, scan_bytes);
+    const uint64_t bytes = 3 * al(cap * 8) + 2 * al(cap * sizeof(FreqVal)) + 4 * al(cap * 4) + al(256) + al(tmp);
+    char *block = nullptr;
+    TRY_HIP(hipMalloc((void **)&block, bytes));
+    Bump bp{block, 0, bytes};
+    FreqBufs nb;
+    nb.block = block; nb.cap = cap;
+    nb.kin = bp.take<unsigned long long>(cap); nb.ks = bp.take<unsigned long long>(cap); nb.kout = bp.take<unsigned long long>(cap);
+    nb.vin = bp.take<FreqVal>(cap); nb.vout = bp.take<FreqVal>(cap);
+    nb.iota = bp.take<uint32_t>(cap); nb.is = bp.take<uint32_t>(cap); nb.head = bp.take<uint32_t>(cap); nb.scan = bp.take<uint32_t>(cap);
+    nb.counter = bp.take<uint32_t>(64); nb.tmp = bp.take<char>(tmp); nb.tmp_bytes = tmp;
+    if (keep && b->block) {  // the aggregate moves into the new block
+        TRY_HIP(hipMemcpyAsync(nb.kin, b->kin, keep * 8, hipMemcpyDeviceToDevice, st));
+        TRY_HIP(hipMemcpyAsync(nb.vin, b->vin, keep * sizeof(FreqVal), hipMemcpyDeviceToDevice, st));
+    }
+    TRY_HIP(hipStreamSynchronize(st));
+    if (b->block) (void)hipFree(b->block);
+    *b = nb;
+    return ARP_OK;
+}
+}  // namespace
+
+arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost *out) {
+    hipStream_t st = (hipStream_t)context_stream(ctx);
+    TRY_HIP(hipSetDevice(context_device(ctx)));
+    const bool timing = g_debug.timing != 0;
+    auto t_prev = std::chrono::steady_clock::now();
+    auto lap = [&](const char *what) {
+        if (!timing) return;
+        (void)hipStreamSynchronize(st);
+        auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "    frequencies %-24s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
+        t_prev = now;
+    };
+    *out = FreqRowsHost{};
+    const uint64_t n = job.n, nr = job.n_res, nh = job.n_h, F = job.n_frames;
+    if (n == 0 || F == 0) return ARP_OK;
+    // frames per pass: the knob's atom budget, else kFreqAutoAtoms; never more frames than fit 32-bit packed indices
+    const uint64_t budget = job.chunk_atoms ? job.chunk_atoms : kFreqAutoAtoms;
+    uint64_t per = std::max<uint64_t>(1, budget / n);
+    per = std::min<uint64_t>({per, F, 0x7FFFFFF0ull / std::max<uint64_t>({n, nr + 1, nh, 1}), 65535});
+    if (per == 0) { set_error("contact frequencies: one frame exceeds 32-bit indices"); return ARP_ERR_BAD_INPUT; }
+    // topology (once) and the packed arrays of one pass
+    struct Seg { const void *src; uint64_t bytes; };
+    const Seg topo_seg[8] = {{job.attr, n * 4}, {job.res_ord, n * 4}, {job.chain_rank, n * 4}, {nr ? job.res_id : nullptr, nr ? n * 4 : 0},
+                             {nr ? job.res_h_ptr : nullptr, nr ? (nr + 1) * 4 : 0}, {nh ? job.res_h_idx : nullptr, nh * 4}, {nr ? job.res_cb : nullptr, nr * 4},
+                             {nr ? job.res_sg : nullptr, nr * 4}};
+    uint64_t topo_bytes = 0;
+    for (const Seg &g : topo_seg) topo_bytes += al(g.bytes);
+    const uint64_t pn = per * n, pr = per * nr, ph = per * nh;
+    const uint64_t pack_bytes = al(pn * 24) + 3 * al(pn * 8) + 5 * al(pn * 4) + al((pr + 1) * 4) + 2 * al(pr * 4) + al(ph * 4);
+    char *block = nullptr;
+    TRY_HIP(hipMalloc((void **)&block, topo_bytes + pack_bytes + 256));
+    std::unique_ptr<char, void (*)(char *)> block_owner(block, [](char *p) { (void)hipFree(p); });
+    Bump bp{block, 0, topo_bytes + pack_bytes + 256};
+    const void *topo_dev[8];
+    for (int k = 0; k < 8; k++) {
+        char *d = bp.take<char>(topo_seg[k].bytes);
+        topo_dev[k] = d;
+        if (topo_seg[k].bytes) TRY_HIP(hipMemcpyAsync(d, topo_seg[k].src, topo_seg[k].bytes, hipMemcpyHostToDevice, st));
+    }
+    FreqTopo tp{(uint32_t)n, (uint32_t)nr, (uint32_t)nh, (const uint32_t *)topo_dev[0], (const uint32_t *)topo_dev[1], (const uint32_t *)topo_dev[2],
+                (const uint32_t *)topo_dev[3], (const uint32_t *)topo_dev[4], (const uint32_t *)topo_dev[5], (const uint32_t *)topo_dev[6], (const uint32_t *)topo_dev[7]};
+    double *xyz = bp.take<double>(pn * 3);
+    FreqPack pk;
+    pk.x = bp.take<double>(pn); pk.y = bp.take<double>(pn); pk.z = bp.take<double>(pn);
+    pk.attr = bp.take<uint32_t>(pn); pk.res_ord = bp.take<uint32_t>(pn); pk.chain_rank = bp.take<uint32_t>(pn); pk.model = bp.take<uint32_t>(pn);
+    pk.res_id = bp.take<uint32_t>(pn); pk.res_h_ptr = bp.take<uint32_t>(pr + 1); pk.res_cb = bp.take<uint32_t>(pr); pk.res_sg = bp.take<uint32_t>(pr);
+    pk.res_h_idx = bp.take<uint32_t>(ph);
+    lap("topology upload");
+    arp_params prm;
+    arp_default_params(&prm);
+    prm.vdw_comp = job.vdw_comp; prm.dist_cutoff = job.dist_cutoff;
+    prm.flags |= ARP_FLAG_CONTACTS_ONLY;
+    // key bits: j in bits 5.., i in bits 34..; only the bits an index of n atoms can set are sorted
+    int ibits = 1;
+    while (ibits < 29 && (1ull << ibits) < n) ibits++;
+    const int end_bit = (int)kFreqKeyShiftI + ibits;
+    FreqBufs fb;
+    struct FreeBufs { FreqBufs *b; ~FreeBufs() { if (b->block) (void)hipFree(b->block); } } fb_owner{&fb};
+    uint64_t n_agg = 0;
+    for (uint64_t f0 = 0; f0 < F; f0 += per) {
+        const uint64_t fc = std::min<uint64_t>(per, F - f0);
+        // 1. upload: the chunk's coordinates only; the tiling kernel writes the per-frame arrays
+        TRY_HIP(hipMemcpyAsync(xyz, job.xyz + f0 * n * 3, fc * n * 24, hipMemcpyHostToDevice, st));
+        const uint64_t W = std::max<uint64_t>({n, nr ? nr + 1 : 0, nh});
+        hipLaunchKernelGGL(k_freq_tile, dim3(std::min<uint32_t>(freq_blocks(fc * W), 1u << 16)), dim3(256), 0, st, (uint32_t)fc, (uint32_t)W, (const double *)xyz, tp, pk);
+        TRY_HIP(hipGetLastError());
+        // 2. the pair pass over the packed frames (contacts only: what arp_get_contacts turns into rows)
+        arp_atoms av{};
+        av.n = fc * n; av.x = pk.x; av.y = pk.y; av.z = pk.z; av.attr = pk.attr; av.res_ord = pk.res_ord; av.chain_rank = pk.chain_rank; av.model = pk.model;
+        av.res_id = nr ? pk.res_id : nullptr; av.n_res = fc * nr; av.res_h_ptr = nr ? pk.res_h_ptr : nullptr; av.res_h_idx = pk.res_h_idx;
+        av.res_cb = nr ? pk.res_cb : nullptr; av.res_sg = nr ? pk.res_sg : nullptr;
+        av.location = ARP_MEM_DEVICE;
+        const arp_pair *pairs = nullptr;
+        uint64_t n_pairs = 0;
+        arp_status s = contacts_atomic_view(ctx, &av, &prm, &pairs, &n_pairs);
+        if (s != ARP_OK) return s;
+        lap("pair pass");
+        if (n_pairs > 0xFFFFFFF0ull) { set_error("contact frequencies: more than 2^32 pairs in one pass (lower freq_chunk_atoms)"); return ARP_ERR_CAPACITY; }
+        if (n_pairs == 0) continue;
+        // 3. expand into (key, value) items behind the aggregate; grown and repeated when they do not fit
+        if (!fb.block && (s = freq_alloc(&fb, std::max<uint64_t>(1u << 16, 2 * n_pairs), 0, st)) != ARP_OK) return s;
+        uint32_t n_items = 0;
+        for (int attempt = 0;; attempt++) {
+            TRY_HIP(hipMemsetAsync(fb.counter, 0, 4, st));
+            hipLaunchKernelGGL(k_freq_expand, dim3(freq_blocks(n_pairs)), dim3(256), 0, st, pairs, (uint32_t)n_pairs, (uint32_t)n, fb.kin, fb.vin, (uint32_t)n_agg,
+                               (uint32_t)fb.cap, fb.counter);
+            TRY_HIP(hipGetLastError());
+            TRY_HIP(hipMemcpyAsync(&n_items, fb.counter, 4, hipMemcpyDeviceToHost, st));
+            TRY_HIP(hipStreamSynchronize(st));
+            if (n_agg + n_items <= fb.cap) break;
+            if (attempt) { set_error("internal error: the item count changed between passes"); return ARP_ERR_HIP; }
+            const uint64_t want = n_agg + n_items;
+            if ((s = freq_alloc(&fb, want + want / 4, n_agg, st)) != ARP_OK) return s;
+        }
+        lap("expand");
+        if (n_items == 0) continue;
+        // 4. + 5. sort the aggregate and the new items together, reduce every run of equal keys to one
+        const uint32_t m = (uint32_t)(n_agg + n_items);
+        size_t tb = fb.tmp_bytes;
+        hipLaunchKernelGGL(k_iota, dim3(freq_blocks(m)), dim3(256), 0, st, m, fb.iota);
+        TRY_HIP(hipcub::DeviceRadixSort::SortPairs(fb.tmp, tb, (const unsigned long long *)fb.kin, fb.ks, (const uint32_t *)fb.iota, fb.is, (int)m, 0, end_bit, st));
+        hipLaunchKernelGGL(k_freq_heads, dim3(freq_blocks(m)), dim3(256), 0, st, m, (const unsigned long long *)fb.ks, fb.head);
+        tb = fb.tmp_bytes;
+        TRY_HIP(hipcub::DeviceScan::InclusiveSum(fb.tmp, tb, (const uint32_t *)fb.head, fb.scan, (int)m, st));
+        hipLaunchKernelGGL(k_freq_init, dim3(freq_blocks(m)), dim3(256), 0, st, m, fb.vout);
+        hipLaunchKernelGGL(k_freq_reduce, dim3(freq_blocks(m)), dim3(256), 0, st, m, (const unsigned long long *)fb.ks, (const uint32_t *)fb.is, (const FreqVal *)fb.vin,
+                           (const uint32_t *)fb.scan, fb.kout, fb.vout);
+        TRY_HIP(hipGetLastError());
+        uint32_t runs = 0;
+        TRY_HIP(hipMemcpyAsync(&runs, fb.scan + (m - 1u), 4, hipMemcpyDeviceToHost, st));
+        TRY_HIP(hipStreamSynchronize(st));
+        std::swap(fb.kin, fb.kout); std::swap(fb.vin, fb.vout);
+        n_agg = runs;
+        lap("sort + reduce");
+    }
+    // 6. only the aggregate comes back
+    out->key.resize(n_agg); out->count.resize(n_agg); out->mn.resize(n_agg); out->mx.resize(n_agg);
+    if (n_agg) {
+        std::vector<FreqVal> v(n_agg);
+        TRY_HIP(hipMemcpyAsync(out->key.data(), fb.kin, n_agg * 8, hipMemcpyDeviceToHost, st));
+        TRY_HIP(hipMemcpyAsync(v.data(), fb.vin, n_agg * sizeof(FreqVal), hipMemcpyDeviceToHost, st));
+        TRY_HIP(hipStreamSynchronize(st));
+        auto decode = [](uint32_t c) { const uint32_t b = (c & 0x80000000u) ? (c & 0x7FFFFFFFu) : ~c; float f; memcpy(&f, &b, 4); return f; };
+        for (uint64_t r = 0; r < n_agg; r++) { out->count[r] = v[r].count; out->mn[r] = decode(v[r].mn); out->mx[r] = decode(v[r].mx); }
+    }
+    lap("download");
+    return ARP_OK;
+}

@@ -285,6 +285,10 @@ struct arp_table {
     std::vector<uint8_t> sc_valid;
     StrCol<8> from_chain, from_resn, from_atomn, to_chain, to_resn, to_atomn;
     StrCol<4> from_insertion, from_altloc, to_insertion, to_altloc;
+    // contact-frequency table (arp_contact_frequencies): no model / distance / sc_* columns; these four instead, materialised when built
+    bool freq = false;
+    std::vector<uint32_t> n_frames;
+    std::vector<float> frequency, min_distance, max_distance;
 };
 
 namespace {
@@ -682,6 +686,13 @@ extern "C" const void *arp_table_column(const arp_table *t_const, const char *na
     if (t->book) std::call_once(t->columns_once, [t]() { materialize_columns(t); });
     std::string c(name);
     auto num = [&](const void *p, int w) -> const void * { if (width) *width = w; return p; };
+    if (t->freq) {  // the frequency table's own columns; it has no model, distance or sc_* column
+        if (c == "n_frames") return num(t->n_frames.data(), 4);
+        if (c == "frequency") return num(t->frequency.data(), 4);
+        if (c == "min_distance") return num(t->min_distance.data(), 4);
+        if (c == "max_distance") return num(t->max_distance.data(), 4);
+        if (c == "model" || c == "distance" || c.compare(0, 3, "sc_") == 0) return nullptr;
+    }
     if (c == "model") return num(t->model.data(), 4);
     if (c == "interaction") return num(t->interaction.data(), 4);
     if (c == "distance") return num(t->distance.data(), 4);
@@ -905,9 +916,70 @@ arp_status export_arrow_fast(const arp_table *t, ArrowArray *out_array, ArrowSch
 }
 }  // namespace
 
+namespace {
+// Arrow export of a contact-frequency table: the 21 columns of FREQ_COLUMNS (api.py), from the fixed-width columns it was built with
+arp_status export_arrow_freq(const arp_table *t, ArrowArray *out_array, ArrowSchema *out_schema) {
+    const int64_t n = (int64_t)t->n;
+    struct Field { const char *name, *format; ArrowCol *col; };
+    ArrowCol *names = new ArrowCol();
+    names->offsets.resize(n + 1);
+    int32_t o = 0;
+    for (int64_t i = 0; i < n; i++) {
+        names->offsets[i] = o;
+        const char *v = arp_interaction_name(t->interaction[i]);
+        const size_t len = strlen(v);
+        names->bytes.insert(names->bytes.end(), v, v + len);
+        o += (int32_t)len;
+    }
+    names->offsets[n] = o;
+    names->bytes.resize(names->bytes.size() + 8);
+    names->bufs[1] = names->offsets.data(); names->bufs[2] = names->bytes.data();
+    std::vector<Field> fields = {
+        {"interaction", "u", names},
+        {"from_chain", "u", utf8_col(t->from_chain)}, {"from_resn", "u", utf8_col(t->from_resn)}, {"from_resi", "i", numeric_col(t->from_resi)},
+        {"from_insertion", "u", utf8_col(t->from_insertion)}, {"from_altloc", "u", utf8_col(t->from_altloc)}, {"from_atomn", "u", utf8_col(t->from_atomn)},
+        {"from_atomi", "i", numeric_col(t->from_atomi)},
+        {"to_chain", "u", utf8_col(t->to_chain)}, {"to_resn", "u", utf8_col(t->to_resn)}, {"to_resi", "i", numeric_col(t->to_resi)},
+        {"to_insertion", "u", utf8_col(t->to_insertion)}, {"to_altloc", "u", utf8_col(t->to_altloc)}, {"to_atomn", "u", utf8_col(t->to_atomn)},
+        {"to_atomi", "i", numeric_col(t->to_atomi)},
+        {"n_frames", "I", numeric_col(t->n_frames)}, {"frequency", "f", numeric_col(t->frequency)},
+        {"min_distance", "f", numeric_col(t->min_distance)}, {"max_distance", "f", numeric_col(t->max_distance)},
+    };
+    ArrowBatch *b = new ArrowBatch();
+    ArrowFields *f = new ArrowFields();
+    b->kids.resize(fields.size()); f->kids.resize(fields.size());
+    for (size_t k = 0; k < fields.size(); k++) {
+        ArrowArray &a = b->kids[k];
+        a = ArrowArray{};
+        a.length = n; a.null_count = 0; a.offset = 0;
+        a.n_buffers = fields[k].format[0] == 'u' ? 3 : 2; a.n_children = 0;
+        a.buffers = fields[k].col->bufs; a.children = nullptr; a.dictionary = nullptr;
+        a.release = release_col; a.private_data = fields[k].col;
+        b->kid_ptrs.push_back(&a);
+        ArrowSchema &sch = f->kids[k];
+        sch = ArrowSchema{};
+        sch.format = fields[k].format; sch.name = fields[k].name; sch.metadata = nullptr; sch.flags = 0;
+        sch.n_children = 0; sch.children = nullptr; sch.dictionary = nullptr;
+        sch.release = release_leaf_schema; sch.private_data = nullptr;
+        f->kid_ptrs.push_back(&sch);
+    }
+    *out_array = ArrowArray{};
+    out_array->length = n; out_array->null_count = 0; out_array->offset = 0;
+    out_array->n_buffers = 1; out_array->buffers = b->bufs;
+    out_array->n_children = (int64_t)fields.size(); out_array->children = b->kid_ptrs.data(); out_array->dictionary = nullptr;
+    out_array->release = release_batch; out_array->private_data = b;
+    *out_schema = ArrowSchema{};
+    out_schema->format = "+s"; out_schema->name = ""; out_schema->metadata = nullptr; out_schema->flags = 0;
+    out_schema->n_children = (int64_t)fields.size(); out_schema->children = f->kid_ptrs.data(); out_schema->dictionary = nullptr;
+    out_schema->release = release_fields; out_schema->private_data = f;
+    return ARP_OK;
+}
+}  // namespace
+
 extern "C" arp_status arp_table_export_arrow(const arp_table *t, ArrowArray *out_array, ArrowSchema *out_schema) try {
     if (!t || !out_array || !out_schema) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
     if (t->n > 0x7FFFFFF0ull) { set_error("table too large for 32-bit utf8 offsets"); return ARP_ERR_BAD_INPUT; }
+    if (t->freq) return export_arrow_freq(t, out_array, out_schema);
     if (t->book) return export_arrow_fast(t, out_array, out_schema);
     const int64_t n = (int64_t)t->n;
     struct Field { const char *name, *format; ArrowCol *col; int64_t n_buffers; bool nullable; };
@@ -980,5 +1052,128 @@ extern "C" arp_status arp_table_export_arrow(const arp_table *t, ArrowArray *out
     out_schema->format = "+s"; out_schema->name = ""; out_schema->metadata = nullptr; out_schema->flags = 0;
     out_schema->n_children = (int64_t)fields.size(); out_schema->children = f->kid_ptrs.data(); out_schema->dictionary = nullptr;
     out_schema->release = release_fields; out_schema->private_data = f;
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+// ---- contact frequencies over frames (device pipeline: freq.inl) -------------------------------------------------
+namespace {
+// Model 0 of the structure is the topology: its atoms are the prefix [0, n0) of the structure's atoms and its residues the prefix [0, r0) of the
+// residue tables (the hierarchy is built in file order, model by model).  With frames_from_models, every further model must repeat model 0's
+// atoms one for one; the frames are then the models' coordinates.
+arp_status freq_topology(const arp_structure *s, bool frames_from_models, uint64_t *n0, uint64_t *r0, uint64_t *n_models) {
+    uint64_t n = 0;
+    while (n < s->n && s->model[n] == 0u) n++;
+    uint64_t r = 0;
+    while (r < s->residues.size() && s->chains[s->residues[r].chain].model_idx == 0u) r++;
+    const uint64_t nm = s->chains.empty() ? 1u : (uint64_t)s->chains.back().model_idx + 1u;
+    *n0 = n; *r0 = r; *n_models = nm;
+    if (!frames_from_models || nm == 1) return ARP_OK;
+    auto serial_of = [&](uint64_t m) { for (const ChainInfo &c : s->chains) if (c.model_idx == m) return c.model_serial; return 0; };
+    for (uint64_t m = 1; m < nm; m++) {
+        const uint64_t base = m * n;
+        uint64_t have = 0;
+        while (base + have < s->n && s->model[base + have] == m) have++;
+        const uint64_t shared = std::min(have, n);
+        for (uint64_t k = 0; k < shared; k++) {
+            const uint64_t a = base + k;
+            const char *what = nullptr;
+            if (memcmp(s->chain.at(a), s->chain.at(k), 8) != 0) what = "chain";
+            else if (memcmp(s->resn.at(a), s->resn.at(k), 8) != 0 || memcmp(s->res_resn.at(a), s->res_resn.at(k), 8) != 0) what = "residue name";
+            else if (s->resi[a] != s->resi[k]) what = "residue number";
+            else if (memcmp(s->icode.at(a), s->icode.at(k), 4) != 0) what = "insertion code";
+            else if (memcmp(s->altloc.at(a), s->altloc.at(k), 4) != 0) what = "altloc";
+            else if (memcmp(s->name.at(a), s->name.at(k), 8) != 0) what = "atom name";
+            else if (s->serial[a] != s->serial[k]) what = "serial number";
+            else if (memcmp(s->elem.at(a), s->elem.at(k), 4) != 0) what = "element";
+            if (what) {
+                set_error("contact frequencies: model %llu (MODEL %d) differs from model 0 at atom %llu: %s (%s %s %d %s serial %d, model 0 has %s %s %d %s serial %d)",
+                          (unsigned long long)m, serial_of(m), (unsigned long long)k, what, s->chain.at(a), s->resn.at(a), s->resi[a], s->name.at(a), s->serial[a],
+                          s->chain.at(k), s->resn.at(k), s->resi[k], s->name.at(k), s->serial[k]);
+                return ARP_ERR_BAD_INPUT;
+            }
+        }
+        if (have != n) {
+            set_error("contact frequencies: model %llu (MODEL %d) differs from model 0 at atom %llu: it has %llu atoms, model 0 has %llu",
+                      (unsigned long long)m, serial_of(m), (unsigned long long)shared, (unsigned long long)have, (unsigned long long)n);
+            return ARP_ERR_BAD_INPUT;
+        }
+    }
+    return ARP_OK;
+}
+}  // namespace
+
+extern "C" arp_status arp_contact_frequencies(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
+                                              double dist_cutoff, arp_table **out) try {
+    if (!s || !out || !groups) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    *out = nullptr;
+    // validation: nothing here touches the device
+    uint64_t n0 = 0, r0 = 0, nm = 1;
+    arp_status st = freq_topology(s, xyz == nullptr, &n0, &r0, &nm);
+    if (st != ARP_OK) return st;
+    const uint64_t F = xyz ? n_frames : nm;
+    if (F == 0) { set_error("contact frequencies: at least one frame is needed"); return ARP_ERR_BAD_INPUT; }
+    if (n0 >= (1ull << 29)) { set_error("contact frequencies: the topology has %llu atoms, at most 2^29 - 1 are supported", (unsigned long long)n0); return ARP_ERR_BAD_INPUT; }
+    if (F > (1ull << 40) / std::max<uint64_t>(n0, 1)) { set_error("contact frequencies: too many frames"); return ARP_ERR_BAD_INPUT; }
+    std::vector<double> model_xyz;
+    if (!xyz) {  // the models' coordinates as F x n0 x 3
+        model_xyz.resize(F * n0 * 3);
+        for (uint64_t a = 0; a < F * n0; a++) { model_xyz[3 * a] = s->x[a]; model_xyz[3 * a + 1] = s->y[a]; model_xyz[3 * a + 2] = s->z[a]; }
+    }
+    const double *frames = xyz ? xyz : model_xyz.data();
+    {
+        const uint64_t nv = F * n0 * 3;
+        uint64_t bad = nv;
+        for (uint64_t v = 0; v < nv; v++) if (!std::isfinite(frames[v])) { bad = v; break; }
+        if (bad != nv) {
+            set_error("contact frequencies: non-finite coordinate in frame %llu, atom %llu", (unsigned long long)(bad / (3 * n0)), (unsigned long long)(bad / 3 % n0));
+            return ARP_ERR_BAD_INPUT;
+        }
+    }
+    if (std::isnan(vdw_comp) || std::isnan(dist_cutoff)) { set_error("NaN parameter"); return ARP_ERR_BAD_INPUT; }
+    // the ligand / receptor bits of this chain-group spec, with the errors of arp_get_contacts (utils.rs:71-115); the structure's own attribute
+    // words are left alone (a table call on it may be using them)
+    std::vector<uint32_t> attr(n0);
+    {
+        std::vector<std::string> L, R;
+        if ((st = parse_groups(s->chain_ids, groups, &L, &R)) != ARP_OK) return st;
+        std::vector<uint32_t> bits(s->chain_ids.size(), 0);
+        for (size_t k = 0; k < s->chain_ids.size(); k++) {
+            if (std::binary_search(L.begin(), L.end(), s->chain_ids[k])) bits[k] |= ARP_ATTR_LIGAND;
+            if (std::binary_search(R.begin(), R.end(), s->chain_ids[k])) bits[k] |= ARP_ATTR_RECEPTOR;
+        }
+        for (uint64_t a = 0; a < n0; a++) attr[a] = s->base_attr[a] | bits[s->chain_rank[a]];
+    }
+    if (!ctx) return ARP_OK;  // validation only
+    FreqJob job;
+    job.n = n0; job.n_res = r0; job.n_h = r0 ? s->res_h_ptr[r0] : 0; job.n_frames = F;
+    job.attr = attr.data(); job.res_ord = s->res_ord.data(); job.chain_rank = s->chain_rank.data(); job.res_id = s->res_id.data();
+    job.res_h_ptr = s->res_h_ptr.data(); job.res_h_idx = s->res_h_idx.data(); job.res_cb = s->res_cb.data(); job.res_sg = s->res_sg.data();
+    job.xyz = frames; job.vdw_comp = vdw_comp; job.dist_cutoff = dist_cutoff;
+    job.chunk_atoms = g_debug.freq_chunk_atoms > 0 ? (uint64_t)g_debug.freq_chunk_atoms : 0u;
+    FreqRowsHost rows;
+    if ((st = device_frequencies(ctx, job, &rows)) != ARP_OK) return st;
+    // the table: identity strings of the rows' atoms from the topology
+    std::unique_ptr<arp_table> t(new arp_table());
+    const size_t nrow = rows.key.size();
+    t->freq = true; t->n = nrow;
+    t->interaction.resize(nrow); t->from_resi.resize(nrow); t->from_atomi.resize(nrow); t->to_resi.resize(nrow); t->to_atomi.resize(nrow);
+    t->from_atom.resize(nrow); t->to_atom.resize(nrow);
+    t->from_chain.resize(nrow); t->from_resn.resize(nrow); t->from_atomn.resize(nrow); t->to_chain.resize(nrow); t->to_resn.resize(nrow); t->to_atomn.resize(nrow);
+    t->from_insertion.resize(nrow); t->from_altloc.resize(nrow); t->to_insertion.resize(nrow); t->to_altloc.resize(nrow);
+    t->n_frames = std::move(rows.count); t->min_distance = std::move(rows.mn); t->max_distance = std::move(rows.mx);
+    t->frequency.resize(nrow);
+    for (size_t k = 0; k < nrow; k++) {
+        const unsigned long long key = rows.key[k];
+        const uint32_t i = (uint32_t)(key >> 34), j = (uint32_t)((key >> 5) & ((1ull << 29) - 1u)), code = (uint32_t)(key & 31u);
+        t->interaction[k] = (int32_t)code;
+        t->frequency[k] = (float)((double)t->n_frames[k] / (double)F);
+        memcpy(t->from_chain.at(k), s->chain.at(i), 8); memcpy(t->from_resn.at(k), s->res_resn.at(i), 8); memcpy(t->from_atomn.at(k), s->name.at(i), 8);
+        memcpy(t->from_insertion.at(k), s->icode.at(i), 4); memcpy(t->from_altloc.at(k), s->altloc.at(i), 4);
+        t->from_resi[k] = s->resi[i]; t->from_atomi[k] = s->serial[i]; t->from_atom[k] = (int32_t)i;
+        memcpy(t->to_chain.at(k), s->chain.at(j), 8); memcpy(t->to_resn.at(k), s->res_resn.at(j), 8); memcpy(t->to_atomn.at(k), s->name.at(j), 8);
+        memcpy(t->to_insertion.at(k), s->icode.at(j), 4); memcpy(t->to_altloc.at(k), s->altloc.at(j), 4);
+        t->to_resi[k] = s->resi[j]; t->to_atomi[k] = s->serial[j]; t->to_atom[k] = (int32_t)j;
+    }
+    *out = t.release();
     return ARP_OK;
 } ARP_ABI_CATCH

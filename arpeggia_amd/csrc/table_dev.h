@@ -69,6 +69,23 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
 // the planes the device fitted, for tests (PHE4 of 1ubq: residues.rs:355-372): 12 doubles per residue {ring c, ring n, sc c, sc n} + validity bits
 arp_status device_planes(arp_context *ctx, const DevStructure &ds, std::vector<double> *planes, std::vector<uint8_t> *valid);
 
+// Contact frequencies over frames (freq.inl, arp_contact_frequencies): the topology's arrays (host, the chain groups applied to attr) and
+// n_frames x n x 3 f64 coordinates.  Rows come back sorted by key = i << 34 | j << 5 | interaction code.
+struct FreqJob {
+    uint64_t n = 0, n_res = 0, n_h = 0, n_frames = 0;
+    const uint32_t *attr = nullptr, *res_ord = nullptr, *chain_rank = nullptr, *res_id = nullptr, *res_h_ptr = nullptr, *res_h_idx = nullptr,
+                   *res_cb = nullptr, *res_sg = nullptr;
+    const double *xyz = nullptr;
+    double vdw_comp = 0.1, dist_cutoff = 6.5;
+    uint64_t chunk_atoms = 0;  // atoms per pass, 0 = automatic (arp_debug_set "freq_chunk_atoms")
+};
+struct FreqRowsHost {
+    std::vector<unsigned long long> key;
+    std::vector<uint32_t> count;
+    std::vector<float> mn, mx;
+};
+arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost *out);
+
 // engine.cpp: the context's stream / device and grow-only scratch (device and pinned host)
 void *context_stream(arp_context *ctx);
 int context_device(arp_context *ctx);

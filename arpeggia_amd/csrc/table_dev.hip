@@ -945,4 +945,6 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
     return ARP_OK;
 }
 
+#include "freq.inl"
+
 }  // namespace arp

@@ -151,6 +151,8 @@ typedef struct arp_table arp_table;         /* the 20-column contact table (mod.
  *   "strip_rows"    N = a power of two: the cell rows of single-model inputs are ordered in y strips of N rows (chosen by input size when 0, the default:
  *                      strips only from ~2.5 x 10^6 atoms of a compact structure on), for parameter blocks built from now on -- lets the parity suite run the strip order on small inputs
  *   "table_host"    1: only in the test library built with -DARP_WITH_HOST_TABLE (tests/hosttable): arp_get_contacts assembles the table on the host
+ *   "freq_chunk_atoms" N > 0: arp_contact_frequencies runs its frames in passes of N atoms (whole frames, at least one per pass), so that tests can
+ *                      force several passes; 0 (default): about 2 x 10^6 atoms per pass
  * Unknown keys return ARP_ERR_BAD_INPUT. */
 arp_status arp_debug_set(const char *key, int64_t value);
 int32_t arp_api_version(void);
@@ -373,6 +375,24 @@ uint64_t arp_table_rows(const arp_table *t);
  * (+ "sc_valid" u8: 0 => null); string columns are rows x width fixed-width NUL-padded chars.  Also
  * "from_atom"/"to_atom" i32 atom indices (-1 for a "Ring" entity). */
 const void *arp_table_column(const arp_table *t, const char *name, int32_t *width);
+
+/* ---- contact frequencies over the frames of an ensemble (NMR models, MD snapshots, conformers of one topology) -- DESIGN.md section 3.7 ----
+ * The topology is model 0 of `topology` (after load_model's filtering), N atoms.  Frame f is the topology with its coordinates replaced by
+ * xyz[f] (n_frames x N x 3 f64, host, C order); xyz == NULL: the structure's models are the frames (n_frames is ignored), and every model must list
+ * model 0's atoms in the same order -- equal chain, residue name, resi, insertion code, altloc, atom name, serial and element -- else
+ * ARP_ERR_BAD_INPUT naming the first model and atom that differ.  The atom-atom pairs of a frame are those of arp_contacts_atomic (groups,
+ * vdw_comp, dist_cutoff as for arp_get_contacts, with its group errors); every set bit of a pair's kind is one (i, j, interaction) item.
+ * The table has one row per distinct (i, j, interaction) of at least one frame, i / j topology atom indices, ordered by (i, j, interaction):
+ *   "interaction" i32 code; "from_chain" "from_resn" "from_insertion" "from_altloc" "from_atomn" fixed-width strings, "from_resi" "from_atomi" i32,
+ *   the same seven "to_*" columns, "from_atom" / "to_atom" i32 (i, j); "n_frames" u32 (frames with the row); "frequency" f32 = f32(n_frames / F)
+ *   divided in f64; "min_distance" / "max_distance" f32 over those frames.  No ring rows (CationPi, Pi*) and no sc_* columns; no ring is required.
+ * The result does not depend on the order the device produces pairs in: two calls give identical bytes.  arp_table_rows / arp_table_column /
+ * arp_table_export_arrow serve this column set (the Arrow batch has the columns above in that order, without from_atom / to_atom).
+ * Errors before the device is touched (ARP_ERR_BAD_INPUT unless noted): n_frames == 0 with xyz, a non-finite coordinate, N >= 2^29, the
+ * model check, the chain groups (ARP_ERR_BAD_GROUPS / ARP_ERR_EMPTY_GROUPS).  ctx == NULL runs only these checks (ARP_OK, *out = NULL).
+ * Frames run through the device in passes of about 2 x 10^6 atoms (arp_debug_set "freq_chunk_atoms"); memory grows with the distinct rows, not F. */
+arp_status arp_contact_frequencies(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
+                                   double dist_cutoff, arp_table **out);
 
 /* The same 20 columns through the Arrow C Data Interface (a struct array = one record batch; utf8 strings, nullable
  * f32 sc_* columns): what pyo3-polars hands to Python in the reference (python.rs:55, mod.rs:140-214), importable with
