@@ -2,7 +2,7 @@
 
 Public surface mirrors the reference (src/lib.rs:20-34, src/python.rs:31-56) for this one path:
 contacts(), get_contacts(), load_model(), parse_groups(); and atom-level sasa(), sap_score(), dsasa(); and sc(); and
-contact_frequencies() across the frames of an ensemble (no counterpart in the reference).  Importing this package loads libarpeggia_amd.so and
+contact_frequencies(), sasa_ensemble() and sap_ensemble() across the frames of an ensemble (no counterpart in the reference).  Importing this package loads libarpeggia_amd.so and
 fails loudly if the HIP extension has not been built -- there is no CPU fallback.
 """
 from .api import (  # noqa: F401
@@ -15,6 +15,10 @@ from .api import (  # noqa: F401  atom SASA, SAP score, dSASA (reference src/sas
 )
 from .api import get_sc, get_sc_results, sc, sc_arrays, sc_dots, sc_radius, sc_select  # noqa: F401  shape complementarity (src/sc/)
 from .api import FREQ_COLUMNS, contact_frequencies, get_contact_frequencies  # noqa: F401  contact frequencies across the frames of an ensemble
+from .api import (  # noqa: F401  SASA / SAP statistics across the frames of an ensemble
+    ENSEMBLE_SAP_COLUMNS, ENSEMBLE_SASA_COLUMNS, RESIDUE_ENSEMBLE_SAP_COLUMNS, get_residue_sap_ensemble, get_sap_ensemble, get_sasa_ensemble,
+    sap_ensemble, sasa_ensemble, sasa_ensemble_stats,
+)
 from ._lib import ATTR, INTERACTIONS  # noqa: F401
 
 __version__ = "0.1.0"

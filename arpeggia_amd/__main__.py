@@ -2,6 +2,7 @@
 `arpeggia contacts` (src/cli/contacts.rs:9-52) over the MI355X engine; it writes <output>/<filename>.<format> like cli/contacts.rs:108-137.
 `sasa`, `sap`, `dsasa` and `sc` take the flags and defaults of src/cli/{sasa,sap,dsasa,sc}.rs (sasa at level "atom" only: see arpeggia_amd/api.py).
 `contact-frequency` (no counterpart in the reference) takes the flags and defaults of `contacts`; the models of the input file are the frames.
+`sasa-ensemble` and `sap-ensemble` (no counterpart either) take the flags and defaults of `sasa` / `sap` without --model: statistics over the models.
 """
 from __future__ import annotations
 
@@ -67,6 +68,24 @@ def build_parser() -> argparse.ArgumentParser:
     add(p, "threads")
     p.add_argument("-l", "--level", default="residue", type=str.lower, choices=("atom", "residue"), help="Aggregation level")
     p.add_argument("-c", "--chains", default="", help="Comma-separated chain IDs to include (empty: all)")
+    ea = sub.add_parser("sasa-ensemble", help="per-atom SASA mean / spread / extremes across the models of a multi-model file")
+    ea.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file whose models are the frames")
+    ea.add_argument("-o", "--output", required=True, type=Path, help="Output directory")
+    ea.add_argument("-f", "--filename", default="sasa_ensemble", help="Name of the output file")
+    ea.add_argument("-t", "--output-format", default="csv", type=str.lower, choices=FORMATS, help="Output file type")
+    add(ea, "probe", "points", "threads")
+    ea.add_argument("-l", "--level", default="atom", type=str.lower, choices=("atom", "residue", "chain"), help="Aggregation level (only atom is available)")
+    ea.add_argument("-c", "--chains", default="", help="Comma-separated chain IDs to include (empty: all)")
+    ep = sub.add_parser("sap-ensemble", help="spatial aggregation propensity averaged across the models of a multi-model file, per atom or residue")
+    ep.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file whose models are the frames")
+    ep.add_argument("-o", "--output", required=True, type=Path, help="Output directory")
+    ep.add_argument("-f", "--filename", default="sap_ensemble", help="Name of the output file")
+    ep.add_argument("-t", "--output-format", default="csv", type=str.lower, choices=FORMATS, help="Output file type")
+    add(ep, "probe", "points")
+    ep.add_argument("-s", "--sap-radius", default=5.0, type=float, help="Radius in Angstroms for the neighbour search")
+    add(ep, "threads")
+    ep.add_argument("-l", "--level", default="residue", type=str.lower, choices=("atom", "residue"), help="Aggregation level")
+    ep.add_argument("-c", "--chains", default="", help="Comma-separated chain IDs to include (empty: all)")
     d = sub.add_parser("dsasa", help="buried surface area between two chain groups (cli/dsasa.rs)")
     d.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file to be analyzed")
     d.add_argument("-g", "--groups", required=True, help="Chain groups, e.g. A,B/C,D")
@@ -127,6 +146,36 @@ def run_surface(args) -> int:
     out = (args.output / args.filename).with_suffix("." + args.output_format)
     write_table(table, out, args.output_format)
     log.info("Results for %d %s saved to %s", len(table), what, out)
+    return 0
+
+
+def run_ensemble(args) -> int:
+    """sasa-ensemble / sap-ensemble: the models of the input file are the frames."""
+    import arpeggia_amd as aa
+
+    if not args.input.exists():
+        log.error("Failed to retrieve input file: %s", args.input)
+        return 1
+    if args.command == "sasa-ensemble" and args.level != "atom":
+        log.error("sasa level '%s' is not available (the reference's rust-sasa radius table is not part of its tree); use --level atom", args.level)
+        return 2
+    try:
+        s = aa.Structure.load(str(args.input.resolve()))
+        if args.command == "sasa-ensemble":
+            table = aa.get_sasa_ensemble(s, None, args.chains, args.probe_radius, args.n_points)
+        else:
+            f = aa.get_sap_ensemble if args.level == "atom" else aa.get_residue_sap_ensemble
+            table = f(s, None, args.chains, args.probe_radius, args.n_points, args.sap_radius)
+    except aa.ArpeggiaError as e:
+        log.error("Ensemble statistics failed: %s", e)
+        return 1
+    if len(table) == 0:
+        log.error("No data found in the input file. Please check the provided arguments.")
+        return 1
+    args.output.mkdir(parents=True, exist_ok=True)
+    out = (args.output / args.filename).with_suffix("." + args.output_format)
+    write_table(table, out, args.output_format)
+    log.info("Results for %d %s saved to %s", len(table), "residues" if getattr(args, "level", "atom") == "residue" else "atoms", out)
     return 0
 
 
@@ -200,6 +249,8 @@ def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     if args.command == "sc":
         return run_sc(args)
+    if args.command in ("sasa-ensemble", "sap-ensemble"):
+        return run_ensemble(args)
     if args.command == "contact-frequency":
         return run_contact_frequency(args)
     return run_contacts(args) if args.command == "contacts" else run_surface(args)

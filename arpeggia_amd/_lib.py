@@ -189,6 +189,10 @@ def _load():
         "arp_table_rows": (C.c_uint64, [vp]),
         "arp_table_column": (vp, [vp, C.c_char_p, C.POINTER(C.c_int32)]),
         "arp_table_export_arrow": (C.c_int32, [vp, C.POINTER(ArrowArray), C.POINTER(ArrowSchema)]),
+        "arp_sasa_ensemble": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_float, C.c_int32, C.c_int32, C.c_float, C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_uint64), _u32p] + [C.POINTER(C.c_float)] * 9 + [_i32p, C.POINTER(C.c_float)]),
+        "arp_sasa_ensemble_stats": (C.c_int32, [C.c_uint64, C.c_uint64, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _i32p, _i32p,
+                                                _dp, _dp] + [C.POINTER(C.c_float)] * 6),
         "arp_contact_frequencies": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_double, C.c_double, C.POINTER(vp)]),
     }
     for name, (res, args) in sig.items():

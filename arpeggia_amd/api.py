@@ -375,6 +375,14 @@ class Context:
         finally:
             lib.arp_table_free(t)
 
+    def sasa_ensemble(self, structure: Structure, frames=None, chains: str = "", probe_radius: float = 1.4, n_points: int = 100, sap_radius: float | None = None,
+                      per_frame: bool = False) -> dict:
+        """arp_sasa_ensemble as a dict of numpy arrays: per-atom SASA statistics over the frames of an ensemble, and SAP statistics when
+        sap_radius is given.  frames: [F, N, 3] f64 coordinates of the topology's N atoms (model 0 of `structure`); None: the structure's models
+        are the frames.  Keys: atoms (u32 structure indices of the m selected atoms), n_frames, mean_sasa / std_sasa / min_sasa / max_sasa [m],
+        total_sasa [F], with SAP mean_sap / std_sap / min_sap / max_sap [m]; per_frame adds count [F, m] i32 and, with SAP, sap [F, m] f32."""
+        return _sasa_ensemble(self, structure, frames, chains, probe_radius, n_points, sap_radius, per_frame)
+
 
 def _topology_atoms(structure: Structure) -> int:
     """Atoms of model 0 (the topology of arp_contact_frequencies): the leading run of the first MODEL serial."""
@@ -387,21 +395,81 @@ def _topology_atoms(structure: Structure) -> int:
 
 def _freq_table(ctx: "Context | None", structure: Structure, frames, groups: str, vdw_comp: float, dist_cutoff: float):
     """arp_contact_frequencies -> table handle (the caller frees it).  ctx None: the inputs are only checked (raises their error, else returns None)."""
-    if frames is None:
-        n_frames, ptr, keep = 0, None, None
-    else:
-        keep = np.ascontiguousarray(frames, dtype="<f8")
-        n = _topology_atoms(structure)
-        if keep.ndim != 3 or keep.shape[1:] != (n, 3):
-            raise ArpeggiaError(_lib.ARP_ERR_BAD_INPUT, f"contact frequencies: frames must have shape [F, {n}, 3] (the topology's atoms), got {list(keep.shape)}")
-        n_frames = keep.shape[0]
-        if keep.size == 0:
-            keep = np.zeros(1, dtype="<f8")  # (a valid pointer; n_frames == 0 is refused by the library)
-        ptr = keep.ctypes.data_as(C.POINTER(C.c_double))
+    n_frames, ptr, keep = _frames_arg(structure, frames, "contact frequencies")
     t = C.c_void_p()
     _check(lib.arp_contact_frequencies(ctx._h if ctx is not None else None, structure._h, int(n_frames), ptr, groups.encode(), float(vdw_comp),
                                        float(dist_cutoff), C.byref(t)))
     return t if ctx is not None else None
+
+
+def _frames_arg(structure: Structure, frames, what: str):
+    """(n_frames, pointer, keep-alive array) of an optional [F, N, 3] coordinate array; N = the atoms of model 0."""
+    if frames is None:
+        return 0, None, None
+    keep = np.ascontiguousarray(frames, dtype="<f8")
+    n = _topology_atoms(structure)
+    if keep.ndim != 3 or keep.shape[1:] != (n, 3):
+        raise ArpeggiaError(_lib.ARP_ERR_BAD_INPUT, f"{what}: frames must have shape [F, {n}, 3] (the topology's atoms), got {list(keep.shape)}")
+    n_frames = keep.shape[0]
+    if keep.size == 0:
+        keep = np.zeros(1, dtype="<f8")  # (a valid pointer; n_frames == 0 is refused by the library)
+    return n_frames, keep.ctypes.data_as(C.POINTER(C.c_double)), keep
+
+
+def _sasa_ensemble(ctx: "Context | None", structure: Structure, frames, chains: str, probe_radius: float, n_points: int, sap_radius, per_frame: bool) -> dict:
+    """arp_sasa_ensemble.  ctx None: the inputs are only checked (raises their error); the result then holds atoms and n_frames only."""
+    n_frames, ptr, keep = _frames_arg(structure, frames, "sasa ensemble")
+    with_sap = sap_radius is not None
+    fp = C.POINTER(C.c_float)
+    rows, used = C.c_uint64(), C.c_uint64()
+    atoms = np.zeros(max(structure.n_atoms, 1), "<u4")
+    args = (structure._h, int(n_frames), ptr, chains.encode(), C.c_float(probe_radius), int(n_points), int(with_sap), C.c_float(sap_radius if with_sap else 0.0),
+            C.byref(rows), C.byref(used), atoms.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if ctx is None:
+        _check(lib.arp_sasa_ensemble(None, *args, *([None] * 11)))
+        return {"atoms": atoms[: rows.value].copy(), "n_frames": int(used.value)}
+    # outputs sized by their bounds: m <= the topology's atoms, F = the frames given or the structure's models
+    n_top = _topology_atoms(structure)
+    f_cap = n_frames if frames is not None else (structure.n_atoms // n_top if n_top else 1)
+    names = ["mean_sasa", "std_sasa", "min_sasa", "max_sasa"] + (["mean_sap", "std_sap", "min_sap", "max_sap"] if with_sap else [])
+    cols = {k: np.zeros(max(n_top, 1), "<f4") for k in names}
+    total = np.zeros(max(f_cap, 1), "<f4")
+    count = np.zeros(max(f_cap * n_top, 1), "<i4") if per_frame else None
+    sap = np.zeros(max(f_cap * n_top, 1), "<f4") if per_frame and with_sap else None
+    p = lambda k: cols[k].ctypes.data_as(fp) if k in cols else None  # noqa: E731
+    _check(lib.arp_sasa_ensemble(ctx._h, *args, p("mean_sasa"), p("std_sasa"), p("min_sasa"), p("max_sasa"), p("mean_sap"), p("std_sap"), p("min_sap"),
+                                 p("max_sap"), total.ctypes.data_as(fp), None if count is None else count.ctypes.data_as(C.POINTER(C.c_int32)),
+                                 None if sap is None else sap.ctypes.data_as(fp)))
+    del keep
+    m, F = int(rows.value), int(used.value)
+    out = {"atoms": atoms[:m].copy(), "n_frames": F}
+    out.update({k: v[:m].copy() for k, v in cols.items()})
+    out["total_sasa"] = total[:F].copy()
+    if count is not None:
+        out["count"] = count[: F * m].reshape(F, m)
+    if sap is not None:
+        out["sap"] = sap[: F * m].reshape(F, m)
+    return out
+
+
+def sasa_ensemble_stats(n_frames: int, radius_plus_probe, n_points: int, s1, s2, cmin, cmax, t1=None, t2=None) -> dict:
+    """arp_sasa_ensemble_stats: the host-side finishing of arp_sasa_ensemble from its per-atom accumulators (no device)."""
+    R = np.ascontiguousarray(radius_plus_probe, dtype="<f4")
+    m = len(R)
+    s1, s2 = (np.ascontiguousarray(v, dtype="<u8") for v in (s1, s2))
+    cmin, cmax = (np.ascontiguousarray(v, dtype="<i4") for v in (cmin, cmax))
+    with_sap = t1 is not None
+    if with_sap:
+        t1, t2 = (np.ascontiguousarray(v, dtype="<f8") for v in (t1, t2))
+    names = ["mean_sasa", "std_sasa", "min_sasa", "max_sasa"] + (["mean_sap", "std_sap"] if with_sap else [])
+    out = {k: np.zeros(m, "<f4") for k in names}
+    fp, dp, u64, i32 = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+    p = lambda k: out[k].ctypes.data_as(fp) if k in out else None  # noqa: E731
+    _check(lib.arp_sasa_ensemble_stats(int(n_frames), m, R.ctypes.data_as(fp), int(n_points), s1.ctypes.data_as(u64), s2.ctypes.data_as(u64),
+                                       cmin.ctypes.data_as(i32), cmax.ctypes.data_as(i32), t1.ctypes.data_as(dp) if with_sap else None,
+                                       t2.ctypes.data_as(dp) if with_sap else None, p("mean_sasa"), p("std_sasa"), p("min_sasa"), p("max_sasa"),
+                                       p("mean_sap"), p("std_sap")))
+    return out
 
 
 def sap_weight(resn: str, sasa: float) -> float:
@@ -772,6 +840,81 @@ def dsasa(input_file: str, groups: str, probe_radius: float = 1.4, n_points: int
 
 
 # ---- shape complementarity (reference src/sc/, python.rs:369-381; include/arpeggia_amd.h "shape complementarity")
+# ---- SASA / SAP statistics over the frames of an ensemble (include/arpeggia_amd.h arp_sasa_ensemble; no counterpart in the reference) ----
+ENSEMBLE_SASA_COLUMNS = ["chain", "resn", "resi", "insertion", "altloc", "atomn", "atomi", "n_frames", "mean_sasa", "std_sasa", "min_sasa", "max_sasa"]
+ENSEMBLE_SAP_COLUMNS = ENSEMBLE_SASA_COLUMNS + ["mean_sap", "std_sap", "min_sap", "max_sap"]
+RESIDUE_ENSEMBLE_SAP_COLUMNS = RESIDUE_SAP_COLUMNS + ["n_frames"]
+
+
+def _ensemble_table(structure: Structure, r: dict, names: list):
+    import pyarrow as pa
+
+    ident = _identity(structure, r["atoms"])
+    cols = {k: ident[k] for k in ENSEMBLE_SASA_COLUMNS[:7]}
+    cols["n_frames"] = pa.array(np.full(len(r["atoms"]), r["n_frames"], "<u4"), pa.uint32())
+    for k in names[8:]:
+        cols[k] = pa.array(r[k], pa.float32())
+    return _frame(cols)
+
+
+def _ensemble_run(structure: Structure, frames, chains: str, probe_radius: float, n_points: int, sap_radius, per_frame: bool, device: int) -> dict:
+    try:
+        ctx = _context(device)
+    except ArpeggiaError:
+        _sasa_ensemble(None, structure, frames, chains, probe_radius, n_points, sap_radius, False)  # an input error takes precedence over the missing device
+        raise
+    return ctx.sasa_ensemble(structure, frames, chains, probe_radius, n_points, sap_radius, per_frame)
+
+
+def get_sasa_ensemble(structure: Structure, frames=None, chains: str = "", probe_radius: float = 1.4, n_points: int = 100, per_frame: bool = False,
+                      device: int = 0):
+    """Per-atom SASA statistics over the frames of an ensemble, frames packed on the device in one call: one row per selected heavy atom with
+    the identity columns of get_atom_sasa, n_frames, mean_sasa, std_sasa (population), min_sasa, max_sasa (ENSEMBLE_SASA_COLUMNS).  frames:
+    [F, N, 3] f64 coordinates of the N atoms of model 0; None: the structure's models are the frames.  per_frame=True returns (table, extras)
+    with extras = {"total_sasa": [F] f32, "count": [F, m] i32 unburied points}."""
+    r = _ensemble_run(structure, frames, chains, probe_radius, n_points, None, per_frame, device)
+    t = _ensemble_table(structure, r, ENSEMBLE_SASA_COLUMNS)
+    return (t, {k: r[k] for k in ("total_sasa", "count")}) if per_frame else t
+
+
+def get_sap_ensemble(structure: Structure, frames=None, chains: str = "", probe_radius: float = 1.4, n_points: int = 100, sap_radius: float = 5.0,
+                     per_frame: bool = False, device: int = 0):
+    """get_sasa_ensemble plus the SAP score of every frame averaged over the frames -- SAP as Chennamsetty et al. define it: mean_sap, std_sap,
+    min_sap, max_sap (ENSEMBLE_SAP_COLUMNS; 0 for backbone atoms).  per_frame=True also returns "sap": [F, m] f32 among the extras."""
+    r = _ensemble_run(structure, frames, chains, probe_radius, n_points, float(sap_radius), per_frame, device)
+    t = _ensemble_table(structure, r, ENSEMBLE_SAP_COLUMNS)
+    return (t, {k: r[k] for k in ("total_sasa", "count", "sap")}) if per_frame else t
+
+
+def get_residue_sap_ensemble(structure: Structure, frames=None, chains: str = "", probe_radius: float = 1.4, n_points: int = 100,
+                             sap_radius: float = 5.0, device: int = 0):
+    """Residue-level time-averaged SAP: residue_sap_from_atoms on the per-atom means (mean_sasa, mean_sap) of get_sap_ensemble, plus n_frames."""
+    import pyarrow as pa
+
+    r = _ensemble_run(structure, frames, chains, probe_radius, n_points, float(sap_radius), False, device)
+    idx = r["atoms"]
+    cols = residue_sap_from_atoms(_strings(structure, "chain", idx), _strings(structure, "resn", idx), structure.ints("resi")[idx],
+                                  _strings(structure, "insertion", idx), r["mean_sasa"], r["mean_sap"])
+    types = {"chain": pa.string(), "resn": pa.string(), "resi": pa.int32(), "insertion": pa.string()}
+    out = {k: pa.array(v, types.get(k, pa.float32())) for k, v in cols.items()}
+    out["n_frames"] = pa.array(np.full(len(cols["resi"]), r["n_frames"], "<u4"), pa.uint32())
+    return _frame(out)
+
+
+def sasa_ensemble(input_file: str, probe_radius: float = 1.4, n_points: int = 100, chains: str = ""):
+    """SASA statistics across the models of a multi-model file (NMR models, MODEL-record snapshots): see get_sasa_ensemble."""
+    return get_sasa_ensemble(Structure.load(input_file), None, chains, probe_radius, n_points)
+
+
+def sap_ensemble(input_file: str, level: str = "residue", probe_radius: float = 1.4, n_points: int = 100, sap_radius: float = 5.0, chains: str = ""):
+    """SAP averaged across the models of a multi-model file, per atom or per residue: see get_sap_ensemble / get_residue_sap_ensemble."""
+    lv = str(level).lower()
+    if lv not in SAP_LEVELS:
+        raise ValueError(f"Invalid level '{level}'. Must be one of: 'atom', 'residue'")
+    f = get_sap_ensemble if lv == "atom" else get_residue_sap_ensemble
+    return f(Structure.load(input_file), None, chains, probe_radius, n_points, sap_radius)
+
+
 def _sc_dict(r: _lib.arp_sc_results) -> dict:
     surf = lambda s: {k: (int(getattr(s, k)) if k.startswith("n_") else float(getattr(s, k))) for k, _ in _lib.arp_sc_surface._fields_}
     out = {"surfaces": [surf(r.surface[0]), surf(r.surface[1])], "combined": surf(r.combined)}

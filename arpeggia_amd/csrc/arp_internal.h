@@ -196,6 +196,32 @@ void launch_sasa(const DevAtoms &in, const Workspace &ws, double cutoff, const f
 // w[j] = arp_sap_weight(ARP_SAP_RESIDUES name code[j], sasa[src[j]]), 0 where src[j] < 0 or code[j] >= 20
 void launch_sap_weight(uint32_t n, const uint32_t *code, const int32_t *src, const float *sasa, float *w, hipStream_t st);
 void launch_pack_fix(const PackArrays &pa, hipStream_t st);
+// SASA / SAP statistics over the frames of an ensemble (ens.inl).  All device pointers.
+struct EnsTopo {          // the topology, uploaded once per call: m selected atoms of the n_top atoms a frame's coordinates cover
+    uint32_t n_top, m;
+    const uint32_t *sel;    // m: topology index of selected atom k
+    const float *R;         // m: radius + probe
+    const uint32_t *code;   // m: position in ARP_SAP_RESIDUES (>= 20: none); SAP only
+    const uint32_t *pattr;  // m: attribute word of the SAP grid (side chain: in the grid; else ARP_ATTR_H: kept out); SAP only
+};
+struct EnsPack {          // the packed arrays of one pass, frames x m entries each; px == nullptr: no SAP
+    double *x, *y, *z, *px, *py, *pz;
+    uint32_t *model, *pattr, *code;
+    int32_t *src;
+    float *R;
+};
+struct EnsAcc {           // per selected atom, over all frames so far
+    unsigned long long *s1, *s2;  // sum of count, sum of count^2
+    int32_t *cmin, *cmax;
+    double *t1, *t2;              // SAP: sum and sum of squares of the per-frame f32 values, added in frame order
+    float *pmin, *pmax;
+};
+// item f * m + k of the packed arrays = selected atom k of frame f of the pass; xyz: frames x n_top x 3 as uploaded
+void launch_ens_tile(uint32_t frames, const double *xyz, const EnsTopo &t, const EnsPack &p, hipStream_t st);
+// folds the pass's count / sap ([frame][atom]; sap nullable) into the accumulators (first: they start with this pass) and writes total[f] = the
+// f32 of the f64 sum of sasa[f][:] in atom order for every frame of the pass
+void launch_ens_reduce(uint32_t frames, uint32_t m, const int32_t *count, const float *sasa, const float *sap, const EnsAcc &a, bool first, float *total,
+                       hipStream_t st);
 // Shape complementarity (sc.inl).  Dot and probe records as the kernels write them; arp_sc_dots copies from the dots.
 struct ScDot {        // 80 B
     double p[3], n[3], area, nn_dist, score;

@@ -1291,6 +1291,122 @@ arp_status sasa_run(arp_context *ctx, const SasaJob &j, float *sasa, int32_t *co
     if (sap && with_sap) memcpy(sap, pin + o_sap, 4 * n);
     return ARP_OK;
 }
+
+// SASA / SAP statistics over the frames of an ensemble (arp_sasa_ensemble).  Frames go through the device in passes of
+// whole frames; a pass is one packed input of frames x m atoms, model = frame, every model with its own origin (DevAtoms::per_model), on which
+// the SASA and SAP kernels of sasa_run run as they are.  Per pass only the coordinates are uploaded (pinned staging, refilled while the device
+// works on the previous pass); the per-atom accumulators stay on the device until the last pass.
+constexpr uint64_t kEnsAutoAtoms = 1u << 21;  // packed atoms per pass when the knob ens_chunk_atoms is 0 (1ubq x 3400 frames, 6bft x 230)
+arp_status ens_run(arp_context *ctx, const EnsJob &j, const EnsOut &o) {
+    arp_status s = check_device(ctx);
+    if (s != ARP_OK) return s;
+    if (ctx->pending) { set_error("a call enqueued on this context has not been collected (arp_contacts_atomic_result)"); return ARP_ERR_BAD_INPUT; }
+    const uint64_t m = j.m, N = j.n_top, F = j.n_frames;
+    if (m == 0 || F == 0) return ARP_OK;
+    // frames per pass: the atom budget; a model ordinal per frame (grid.inl kPackModels); one pass below the SASA / SAP kernels' atom limit
+    constexpr uint64_t kMaxPassAtoms = 0x5000000ull - 1u;
+    if (m > kMaxPassAtoms) { set_error("sasa ensemble: too many selected atoms for one frame (< 83886080)"); return ARP_ERR_BAD_INPUT; }
+    const uint64_t budget = j.chunk_atoms ? j.chunk_atoms : kEnsAutoAtoms;
+    const uint64_t per = std::min<uint64_t>({std::max<uint64_t>(1, budget / m), F, 65535u, kMaxPassAtoms / m});
+    const uint64_t pn = per * m;
+    float r_max = 0.0f;
+    for (uint64_t k = 0; k < m; k++) r_max = std::max(r_max, j.R[k]);
+    // device block: {topology | accumulators + totals | one pass}; the pinned block repeats the first two at the same offsets (one copy each
+    // way) and adds the coordinate staging and, when asked for, the per-frame outputs of a pass
+    uint64_t off = 0;
+    auto seg = [&](uint64_t bytes) { const uint64_t at = off; off += (bytes + 255u) & ~255ull; return at; };
+    const uint64_t o_sel = seg(4 * m), o_R = seg(4 * m), o_code = seg(4 * m), o_pattr = seg(4 * m), o_sph = seg(12ull * j.n_points);
+    const uint64_t topo_bytes = off;
+    const uint64_t o_s1 = seg(8 * m), o_s2 = seg(8 * m), o_t1 = seg(8 * m), o_t2 = seg(8 * m), o_cmin = seg(4 * m), o_cmax = seg(4 * m), o_pmin = seg(4 * m),
+                   o_pmax = seg(4 * m), o_total = seg(4 * F);
+    const uint64_t acc_bytes = off - topo_bytes, shared_bytes = off;
+    const uint64_t o_xyz = seg(24 * per * N), o_x = seg(8 * pn), o_y = seg(8 * pn), o_z = seg(8 * pn), o_zero = seg(4 * pn), o_model = seg(4 * pn), o_Rp = seg(4 * pn),
+                   o_sasa = seg(4 * pn), o_count = seg(4 * pn);
+    uint64_t o_px = 0, o_py = 0, o_pz = 0, o_pa = 0, o_pc = 0, o_src = 0, o_w = 0, o_sap = 0;
+    if (j.with_sap) { o_px = seg(8 * pn); o_py = seg(8 * pn); o_pz = seg(8 * pn); o_pa = seg(4 * pn); o_pc = seg(4 * pn); o_src = seg(4 * pn); o_w = seg(4 * pn); o_sap = seg(4 * pn); }
+    const uint64_t dev_bytes = off;
+    off = shared_bytes;
+    const uint64_t h_xyz = seg(24 * per * N), h_count = o.count ? seg(4 * pn) : 0, h_sap = o.sap ? seg(4 * pn) : 0;
+    const uint64_t pin_bytes = off;
+    if ((s = ensure_workspace(ctx, pn)) != ARP_OK) return s;
+    char *dev = nullptr, *pin = nullptr;
+    if ((s = context_scratch(ctx, 0, dev_bytes, pin_bytes, &dev, &pin)) != ARP_OK) return s;
+    ctx->grid_x = nullptr; ctx->grid_n = 0;  // the workspace's cell list is about to hold another input (context_grid must not hand it out)
+    ctx->nodefer_x = nullptr; ctx->nodefer_n = 0;
+    memcpy(pin + o_sel, j.sel, 4 * m); memcpy(pin + o_R, j.R, 4 * m); memcpy(pin + o_sph, j.sphere, 12ull * j.n_points);
+    if (j.with_sap) {
+        memcpy(pin + o_code, j.res_code, 4 * m);
+        uint32_t *pa = (uint32_t *)(pin + o_pattr);
+        for (uint64_t k = 0; k < m; k++) pa[k] = j.sidechain[k] ? (ARP_ATTR_LIGAND | ARP_ATTR_RECEPTOR) : ARP_ATTR_H;  // (the bit that keeps an atom out of the grid)
+    }
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(dev, pin, topo_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(dev + o_zero, 0, 4 * pn, st));  // attribute word of the SASA grid (every packed atom is in it), residue ordinal, chain rank
+    if (j.with_sap) HIP_TRY(hipMemsetAsync(dev + o_sap, 0, 4 * pn, st));  // backbone atoms are outside the SAP grid in every frame: they keep 0
+    struct Event {
+        hipEvent_t e = nullptr;
+        ~Event() { if (e) (void)hipEventDestroy(e); }
+    } staged;  // behind the upload of the staging buffer: the host refills it only after that copy has run
+    HIP_TRY(hipEventCreateWithFlags(&staged.e, hipEventDisableTiming));
+    EnsTopo tp{(uint32_t)N, (uint32_t)m, (const uint32_t *)(dev + o_sel), (const float *)(dev + o_R), (const uint32_t *)(dev + o_code), (const uint32_t *)(dev + o_pattr)};
+    EnsPack pk{};
+    pk.x = (double *)(dev + o_x); pk.y = (double *)(dev + o_y); pk.z = (double *)(dev + o_z);
+    pk.model = (uint32_t *)(dev + o_model); pk.R = (float *)(dev + o_Rp);
+    if (j.with_sap) {
+        pk.px = (double *)(dev + o_px); pk.py = (double *)(dev + o_py); pk.pz = (double *)(dev + o_pz);
+        pk.pattr = (uint32_t *)(dev + o_pa); pk.code = (uint32_t *)(dev + o_pc); pk.src = (int32_t *)(dev + o_src);
+    }
+    EnsAcc acc{(unsigned long long *)(dev + o_s1), (unsigned long long *)(dev + o_s2), (int32_t *)(dev + o_cmin), (int32_t *)(dev + o_cmax),
+               (double *)(dev + o_t1), (double *)(dev + o_t2), (float *)(dev + o_pmin), (float *)(dev + o_pmax)};
+    Profiler *prof = ctx->prof.enabled ? &ctx->prof : nullptr;
+    // search radius of the SASA grid: as sasa_run
+    const double cutoff = 2.0 * (double)r_max * (1.0 + 1e-5) + 1e-6;
+    const double sap_r2 = (double)(j.sap_radius * j.sap_radius);  // sap.rs:184: the product is formed in f32
+    arp_params prm;
+    arp_default_params(&prm);
+    float *d_sasa = (float *)(dev + o_sasa), *d_sap = j.with_sap ? (float *)(dev + o_sap) : nullptr;
+    int32_t *d_count = (int32_t *)(dev + o_count);
+    for (uint64_t f0 = 0; f0 < F; f0 += per) {
+        const uint64_t fc = std::min<uint64_t>(per, F - f0), cn = fc * m;
+        if (f0) HIP_TRY(hipEventSynchronize(staged.e));
+        memcpy(pin + h_xyz, j.xyz + f0 * N * 3, 24 * fc * N);
+        HIP_TRY(hipMemcpyAsync(dev + o_xyz, pin + h_xyz, 24 * fc * N, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(staged.e, st));
+        launch_ens_tile((uint32_t)fc, (const double *)(dev + o_xyz), tp, pk, st);
+        prm.dist_cutoff = cutoff;
+        if ((s = upload_params(ctx, &prm)) != ARP_OK) return s;
+        DevAtoms d{};
+        d.n = (uint32_t)cn; d.per_model = 1u;
+        d.x = pk.x; d.y = pk.y; d.z = pk.z;
+        d.attr = d.res_ord = d.chain_rank = (const uint32_t *)(dev + o_zero); d.model = pk.model;
+        launch_sasa(d, ctx->ws, cutoff, pk.R, (const float *)(dev + o_sph), j.n_points, r_max, d_sasa, d_count, st, prof);
+        HIP_TRY(hipGetLastError());
+        if (j.with_sap) {
+            prm.dist_cutoff = (double)j.sap_radius;
+            if ((s = upload_params(ctx, &prm)) != ARP_OK) return s;
+            launch_sap_weight((uint32_t)cn, pk.code, pk.src, d_sasa, (float *)(dev + o_w), st);
+            DevAtoms e = d;
+            e.x = pk.px; e.y = pk.py; e.z = pk.pz; e.attr = pk.pattr;
+            launch_neighbor_sum(e, ctx->ws, (double)j.sap_radius, sap_r2, (const float *)(dev + o_w), d_sap, st, prof);
+            HIP_TRY(hipGetLastError());
+        }
+        launch_ens_reduce((uint32_t)fc, (uint32_t)m, d_count, d_sasa, d_sap, acc, f0 == 0, (float *)(dev + o_total) + f0, st);
+        HIP_TRY(hipGetLastError());
+        if (o.count || o.sap) {  // the pass's own values, only when the caller wants them
+            if (o.count) HIP_TRY(hipMemcpyAsync(pin + h_count, d_count, 4 * cn, hipMemcpyDeviceToHost, st));
+            if (o.sap) HIP_TRY(hipMemcpyAsync(pin + h_sap, d_sap, 4 * cn, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (o.count) memcpy(o.count + f0 * m, pin + h_count, 4 * cn);
+            if (o.sap) memcpy(o.sap + f0 * m, pin + h_sap, 4 * cn);
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(pin + topo_bytes, dev + topo_bytes, acc_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memcpy(o.s1, pin + o_s1, 8 * m); memcpy(o.s2, pin + o_s2, 8 * m); memcpy(o.cmin, pin + o_cmin, 4 * m); memcpy(o.cmax, pin + o_cmax, 4 * m);
+    memcpy(o.total, pin + o_total, 4 * F);
+    if (j.with_sap) { memcpy(o.t1, pin + o_t1, 8 * m); memcpy(o.t2, pin + o_t2, 8 * m); memcpy(o.pmin, pin + o_pmin, 4 * m); memcpy(o.pmax, pin + o_pmax, 4 * m); }
+    return ARP_OK;
+}
 }  // namespace arp
 
 extern "C" arp_status arp_sasa_sphere_points(uint32_t n, float *xyz) try {
@@ -1397,7 +1513,7 @@ extern "C" int32_t arp_profile_read(arp_context *ctx, const char **names, float 
 }
 
 // ---- library-level -----------------------------------------------------------------------------------------------
-namespace arp { DebugKnobs g_debug{0, 0, 0, 0, 0, 0}; }
+namespace arp { DebugKnobs g_debug{0, 0, 0, 0, 0, 0, 0}; }
 extern "C" arp_status arp_debug_set(const char *key, int64_t value) {
     if (!key) { set_error("null key"); return ARP_ERR_BAD_INPUT; }
     const std::string k(key);
@@ -1409,11 +1525,15 @@ extern "C" arp_status arp_debug_set(const char *key, int64_t value) {
         if (value < 0) { set_error("arp_debug_set: freq_chunk_atoms takes 0 (automatic) or a positive atom count"); return ARP_ERR_BAD_INPUT; }
         g_debug.freq_chunk_atoms = (long)value;
     }
+    else if (k == "ens_chunk_atoms") {
+        if (value < 0) { set_error("arp_debug_set: ens_chunk_atoms takes 0 (automatic) or a positive atom count"); return ARP_ERR_BAD_INPUT; }
+        g_debug.ens_chunk_atoms = (long)value;
+    }
     else if (k == "strip_rows") {
         if (value < 0 || value > 1024 || (value & (value - 1)) != 0) { set_error("arp_debug_set: strip_rows takes 0 or a power of two up to 1024"); return ARP_ERR_BAD_INPUT; }
         g_debug.strip_rows = (int)value;
     }
-    else { set_error("arp_debug_set: unknown key '%s' (timing, emit_kernel, defer_entries, strip_rows, table_host, freq_chunk_atoms)", key); return ARP_ERR_BAD_INPUT; }
+    else { set_error("arp_debug_set: unknown key '%s' (timing, emit_kernel, defer_entries, strip_rows, table_host, freq_chunk_atoms, ens_chunk_atoms)", key); return ARP_ERR_BAD_INPUT; }
     return ARP_OK;
 }
 extern "C" int32_t arp_api_version(void) { return ARP_API_VERSION; }

@@ -107,6 +107,34 @@ struct SasaJob {
 };
 // sasa / count / sap (nullable) receive n entries; one synchronisation at the end.  Inputs are checked by the callers.
 arp_status sasa_run(arp_context *ctx, const SasaJob &job, float *sasa, int32_t *count, float *sap);
+// SASA / SAP statistics over the frames of an ensemble (arp_sasa_ensemble): engine.cpp ens_run packs the frames into
+// passes and runs them (kernels in ens.inl + the unchanged SASA / SAP kernels); sasa.cpp selects, checks and finishes.  Host arrays.
+struct EnsJob {
+    uint64_t n_top = 0, m = 0, n_frames = 0;  // atoms a frame's coordinates cover, selected atoms, frames
+    const double *xyz = nullptr;           // n_frames x n_top x 3
+    const uint32_t *sel = nullptr;         // m topology indices, ascending
+    const float *R = nullptr;              // m: radius + probe in f32
+    uint32_t n_points = 0;
+    const float *sphere = nullptr;
+    bool with_sap = false;
+    const uint8_t *sidechain = nullptr;    // m (SAP)
+    const uint32_t *res_code = nullptr;    // m (SAP): position in ARP_SAP_RESIDUES, >= 20: none
+    float sap_radius = 0.0f;
+    uint64_t chunk_atoms = 0;              // packed atoms per pass, 0: automatic
+};
+struct EnsOut {                            // m entries each unless noted; the SAP members are written only with EnsJob::with_sap
+    unsigned long long *s1 = nullptr, *s2 = nullptr;
+    int32_t *cmin = nullptr, *cmax = nullptr;
+    double *t1 = nullptr, *t2 = nullptr;
+    float *pmin = nullptr, *pmax = nullptr;
+    float *total = nullptr;                // n_frames
+    int32_t *count = nullptr;              // n_frames x m, nullable
+    float *sap = nullptr;                  // n_frames x m, nullable
+};
+arp_status ens_run(arp_context *ctx, const EnsJob &job, const EnsOut &out);
+// table.cpp: model 0 of a structure as the topology of an ensemble (n0 atoms, r0 residues); with frames_from_models every further model must
+// repeat model 0's atoms one for one (ARP_ERR_BAD_INPUT naming the first model and atom that differ)
+arp_status freq_topology(const arp_structure *s, bool frames_from_models, uint64_t *n0, uint64_t *r0, uint64_t *n_models);
 // golden-spiral unit vectors in f64, rounded to f32 (DESIGN.md "Atom SASA")
 void sasa_sphere_points(uint32_t n, float *xyz);
 uint32_t sap_residue_code(const char *resn);

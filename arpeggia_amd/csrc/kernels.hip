@@ -281,6 +281,7 @@ DEVFN float dist_f32(double s) {
 #include "batch.inl"
 #include "sap.inl"
 #include "sasa.inl"
+#include "ens.inl"
 #include "sc.inl"
 
 }  // namespace arp

@@ -233,3 +233,102 @@ extern "C" arp_status arp_structure_dsasa(arp_context *ctx, const arp_structure 
     if (*out < 0.0f) { set_error("Negative dSASA calculated. Please check the input file and chain groups."); return ARP_ERR_BAD_INPUT; }
     return ARP_OK;
 } ARP_ABI_CATCH
+
+// ---- SASA / SAP statistics over the frames of an ensemble (device path: engine.cpp ens_run, ens.inl) ----------------
+extern "C" arp_status arp_sasa_ensemble_stats(uint64_t n_frames, uint64_t m, const float *R, int32_t n_points, const uint64_t *s1, const uint64_t *s2,
+                                              const int32_t *cmin, const int32_t *cmax, const double *t1, const double *t2, float *mean_sasa,
+                                              float *std_sasa, float *min_sasa, float *max_sasa, float *mean_sap, float *std_sap) try {
+    if (n_frames == 0 || n_points < 1) { set_error("sasa ensemble statistics: n_frames and n_points must be positive"); return ARP_ERR_BAD_INPUT; }
+    if (m && (!R || !s1 || !s2 || !cmin || !cmax || !mean_sasa || !std_sasa || !min_sasa || !max_sasa)) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    if (m && (t1 || t2 || mean_sap || std_sap) && !(t1 && t2 && mean_sap && std_sap)) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    const double F = (double)n_frames, n = (double)n_points;
+    for (uint64_t k = 0; k < m; k++) {
+        // b = (4 pi R) R as k_sasa forms it (sasa.inl); every value below is one f64 chain, left to right, rounded to f32 once
+        const double ri = (double)R[k], b = (4.0 * 3.141592653589793 * ri) * ri;
+        const unsigned __int128 d = (unsigned __int128)n_frames * s2[k] - (unsigned __int128)s1[k] * s1[k];  // F S2 - S1^2 >= 0 (Cauchy-Schwarz), exact
+        mean_sasa[k] = (float)(b * (double)s1[k] / n / F);
+        std_sasa[k] = (float)(b * std::sqrt((double)d) / n / F);
+        min_sasa[k] = (float)(b * (double)cmin[k] / n);  // (the value k_sasa gives the frame with that count)
+        max_sasa[k] = (float)(b * (double)cmax[k] / n);
+        if (t1) {
+            const double mu = t1[k] / F, var = t2[k] / F - mu * mu;
+            mean_sap[k] = (float)mu;
+            std_sap[k] = (float)std::sqrt(var > 0.0 ? var : 0.0);
+        }
+    }
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+extern "C" arp_status arp_sasa_ensemble(arp_context *ctx, const arp_structure *s, uint64_t n_frames, const double *xyz, const char *chains, float probe,
+                                        int32_t n_points, int32_t with_sap, float sap_radius, uint64_t *n_rows, uint64_t *frames_used, uint32_t *out_atoms,
+                                        float *mean_sasa, float *std_sasa, float *min_sasa, float *max_sasa, float *mean_sap, float *std_sap, float *min_sap,
+                                        float *max_sap, float *total_sasa, int32_t *out_count, float *out_sap) try {
+    if (!s || !n_rows || !frames_used) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    *n_rows = 0; *frames_used = 0;
+    // validation: nothing here touches the device
+    uint64_t n0 = 0, r0 = 0, nm = 1;
+    arp_status st = freq_topology(s, xyz == nullptr, &n0, &r0, &nm);
+    if (st != ARP_OK) return st;
+    const uint64_t F = xyz ? n_frames : nm;
+    if (F == 0) { set_error("sasa ensemble: at least one frame is needed"); return ARP_ERR_BAD_INPUT; }
+    if (n0 >= (1ull << 29)) { set_error("sasa ensemble: the topology has %llu atoms, at most 2^29 - 1 are supported", (unsigned long long)n0); return ARP_ERR_BAD_INPUT; }
+    if (F > (1ull << 40) / std::max<uint64_t>(n0, 1)) { set_error("sasa ensemble: too many frames"); return ARP_ERR_BAD_INPUT; }
+    if ((st = sasa_check_params(probe, n_points)) != ARP_OK) return st;
+    if (with_sap && !(sap_radius >= 0.0f)) { set_error("bad sap_radius"); return ARP_ERR_BAD_INPUT; }
+    if (!with_sap && out_sap) { set_error("sasa ensemble: out_sap needs with_sap"); return ARP_ERR_BAD_INPUT; }
+    // steps 1-3 of arp_structure_sasa_select on model 0's atoms (the prefix [0, n0) of the structure)
+    std::vector<uint32_t> sel = select_atoms(s, chain_set(chains), true, false, false, 0);
+    while (!sel.empty() && sel.back() >= n0) sel.pop_back();  // (ascending)
+    const uint64_t m = sel.size();
+    std::vector<float> R;
+    if ((st = radii(s, sel, probe, &R)) != ARP_OK) return st;
+    std::vector<double> model_xyz;
+    if (!xyz) {  // the models' coordinates as F x n0 x 3
+        model_xyz.resize(F * n0 * 3);
+        for (uint64_t a = 0; a < F * n0; a++) { model_xyz[3 * a] = s->x[a]; model_xyz[3 * a + 1] = s->y[a]; model_xyz[3 * a + 2] = s->z[a]; }
+    }
+    const double *frames = xyz ? xyz : model_xyz.data();
+    for (uint64_t f = 0; f < F; f++)
+        for (uint64_t k = 0; k < m; k++) {
+            const double *c = frames + 3 * (f * n0 + sel[k]);
+            if (!(std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]))) {
+                set_error("sasa ensemble: non-finite coordinate in frame %llu, atom %llu", (unsigned long long)f, (unsigned long long)sel[k]);
+                return ARP_ERR_BAD_INPUT;
+            }
+        }
+    if (out_atoms) std::copy(sel.begin(), sel.end(), out_atoms);
+    *frames_used = F;
+    if (!ctx) { *n_rows = m; return ARP_OK; }  // validation only: the selection and the frame count
+    if (!out_atoms || !mean_sasa || !std_sasa || !min_sasa || !max_sasa || !total_sasa || (with_sap && (!mean_sap || !std_sap || !min_sap || !max_sap))) {
+        set_error("null argument");
+        return ARP_ERR_BAD_INPUT;
+    }
+    if (m == 0) { std::fill(total_sasa, total_sasa + F, 0.0f); return ARP_OK; }  // an empty selection: no rows, every frame's total is 0
+    std::vector<float> Rm(m), sphere(3ull * (uint32_t)n_points);
+    std::vector<uint8_t> side(m, 0);
+    std::vector<uint32_t> code(m, 20u);
+    for (uint64_t k = 0; k < m; k++) {
+        const uint32_t i = sel[k];
+        Rm[k] = R[i];
+        side[k] = !is_backbone(s->name.at(i));
+        code[k] = sap_residue_code(s->res_resn.at(i));
+    }
+    sasa_sphere_points((uint32_t)n_points, sphere.data());
+    EnsJob j;
+    j.n_top = n0; j.m = m; j.n_frames = F; j.xyz = frames; j.sel = sel.data(); j.R = Rm.data(); j.n_points = (uint32_t)n_points; j.sphere = sphere.data();
+    j.with_sap = with_sap != 0; j.sidechain = side.data(); j.res_code = code.data(); j.sap_radius = sap_radius;
+    j.chunk_atoms = g_debug.ens_chunk_atoms > 0 ? (uint64_t)g_debug.ens_chunk_atoms : 0u;
+    std::vector<unsigned long long> s1(m), s2(m);
+    std::vector<int32_t> cmin(m), cmax(m);
+    std::vector<double> t1(with_sap ? m : 0), t2(with_sap ? m : 0);
+    EnsOut o;
+    o.s1 = s1.data(); o.s2 = s2.data(); o.cmin = cmin.data(); o.cmax = cmax.data(); o.total = total_sasa; o.count = out_count;
+    if (with_sap) { o.t1 = t1.data(); o.t2 = t2.data(); o.pmin = min_sap; o.pmax = max_sap; o.sap = out_sap; }
+    if ((st = ens_run(ctx, j, o)) != ARP_OK) return st;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "accumulator width");
+    if ((st = arp_sasa_ensemble_stats(F, m, Rm.data(), n_points, (const uint64_t *)s1.data(), (const uint64_t *)s2.data(), cmin.data(), cmax.data(),
+                                      with_sap ? t1.data() : nullptr, with_sap ? t2.data() : nullptr, mean_sasa, std_sasa, min_sasa, max_sasa,
+                                      with_sap ? mean_sap : nullptr, with_sap ? std_sap : nullptr)) != ARP_OK) return st;
+    *n_rows = m;
+    return ARP_OK;
+} ARP_ABI_CATCH

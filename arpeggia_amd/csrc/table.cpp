@@ -1056,7 +1056,7 @@ extern "C" arp_status arp_table_export_arrow(const arp_table *t, ArrowArray *out
 } ARP_ABI_CATCH
 
 // ---- contact frequencies over frames (device pipeline: freq.inl) -------------------------------------------------
-namespace {
+namespace arp {
 // Model 0 of the structure is the topology: its atoms are the prefix [0, n0) of the structure's atoms and its residues the prefix [0, r0) of the
 // residue tables (the hierarchy is built in file order, model by model).  With frames_from_models, every further model must repeat model 0's
 // atoms one for one; the frames are then the models' coordinates.
@@ -1100,7 +1100,7 @@ arp_status freq_topology(const arp_structure *s, bool frames_from_models, uint64
     }
     return ARP_OK;
 }
-}  // namespace
+}  // namespace arp
 
 extern "C" arp_status arp_contact_frequencies(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
                                               double dist_cutoff, arp_table **out) try {

@@ -153,6 +153,8 @@ typedef struct arp_table arp_table;         /* the 20-column contact table (mod.
  *   "table_host"    1: only in the test library built with -DARP_WITH_HOST_TABLE (tests/hosttable): arp_get_contacts assembles the table on the host
  *   "freq_chunk_atoms" N > 0: arp_contact_frequencies runs its frames in passes of N atoms (whole frames, at least one per pass), so that tests can
  *                      force several passes; 0 (default): about 2 x 10^6 atoms per pass
+ *   "ens_chunk_atoms" N > 0: arp_sasa_ensemble runs its frames in passes of N packed atoms (frames x selected atoms; whole frames, at least one per
+ *                      pass), so that tests can force several passes; 0 (default): about 2 x 10^6 atoms per pass
  * Unknown keys return ARP_ERR_BAD_INPUT. */
 arp_status arp_debug_set(const char *key, int64_t value);
 int32_t arp_api_version(void);
@@ -393,6 +395,47 @@ const void *arp_table_column(const arp_table *t, const char *name, int32_t *widt
  * Frames run through the device in passes of about 2 x 10^6 atoms (arp_debug_set "freq_chunk_atoms"); memory grows with the distinct rows, not F. */
 arp_status arp_contact_frequencies(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
                                    double dist_cutoff, arp_table **out);
+
+/* ---- SASA and SAP statistics over the frames of an ensemble (MD snapshots, NMR models, conformers of one topology) -- DESIGN.md section 3.8 ----
+ * Topology, N, frames and xyz exactly as arp_contact_frequencies defines them: model 0 of `topology` is the topology, frame f is xyz[f]
+ * (n_frames x N x 3 f64, host, C order); xyz == NULL: the structure's models are the frames, with the same one-for-one model check and its error.
+ * Selection: steps 1-3 of arp_structure_sasa_select (chain filter, hydrogens out, solvent / ion residues out) on model 0's atoms -- no step 4 / 5:
+ * the models are the frames here.  m selected atoms, in structure order; R_k = f32(van der Waals radius) + probe as arp_structure_atom_sasa
+ * (an element without a radius is its error).
+ * Per frame f, by definition:
+ *   count[f][k], sasa[f][k] = what arp_atom_sasa returns for the m selected atoms with frame f's coordinates, their van der Waals radii (f32), `probe`, include all ones
+ *     (counts are integers: exact, whatever the pass size).
+ *   with_sap: w[f][k] = arp_sap_weight(residue name of k, sasa[f][k]) (bit for bit); sap[f][k] = arp_sap_neighbor_sum over the side-chain atoms
+ *     of the selection (atom name not N CA C O OXT) with frame f's f64 coordinates, the weights w[f][:] and sap_radius; 0 for backbone atoms.
+ *     The f32 additions of a neighbour sum run in the order of the cell list the frame sits in, and that list depends on what the pass holds
+ *     (every frame of a pass is a model of one packed grid, sized by the largest frame; one z layer or one cell row per wave by task count):
+ *     sap[f][k] may differ in its last bits from the per-frame call and between pass sizes.  Two calls with the same inputs and the same
+ *     pass size give identical bytes in every output; SASA outputs are identical for every pass size.
+ * Per selected atom k, over the F frames (independent of pass boundaries given the per-frame values):
+ *   S1 = sum count, S2 = sum count^2 (u64), cmin, cmax; b = (4 pi R_k) R_k in f64, left to right (4 pi = 4.0 * the double nearest pi);
+ *   mean_sasa = f32(b * S1 / n_points / F), min_sasa = f32(b * cmin / n_points), max_sasa = f32(b * cmax / n_points) -- the last two are the
+ *   per-frame sasa values of those counts --, std_sasa = f32(b * sqrt(D) / n_points / F) with D = F S2 - S1^2 formed exactly in 128-bit integers
+ *   and converted to f64 once (population standard deviation); every expression is one f64 chain evaluated left to right, rounded to f32 once.
+ *   with_sap: T1 = sum of (f64) sap[f][k], T2 = sum of (f64) sap[f][k]^2, both added in f64 in frame order 0 .. F - 1; mu = T1 / F;
+ *   mean_sap = f32(mu), std_sap = f32(sqrt(max(T2 / F - mu * mu, 0))), min_sap / max_sap over the frames.
+ * Per frame: total_sasa[f] = f32 of the f64 sum of sasa[f][k] over k in atom order.
+ * Outputs: *n_rows = m, *frames_used = F, out_atoms[m] structure atom indices; the per-atom arrays hold m entries (arp_structure_n_atoms entries
+ * always suffice); total_sasa holds F; the *_sap arrays are written only with with_sap (else they may be NULL); out_count (i32) / out_sap (f32),
+ * both F x m in C order and both nullable, are only copied back when given (out_sap needs with_sap).
+ * Errors before the device is touched (ARP_ERR_BAD_INPUT): the model check, n_frames == 0 with xyz, N >= 2^29, n_points / probe as
+ * arp_atom_sasa, sap_radius < 0 or NaN, an element without a radius, a non-finite coordinate of a selected atom.  ctx == NULL runs only these
+ * checks and writes *n_rows, *frames_used and (when given) out_atoms.  An empty selection is ARP_OK with 0 rows and zero totals.
+ * Frames run through the device in passes of about 2 x 10^6 packed atoms (arp_debug_set "ens_chunk_atoms"), at most 65535 frames each; device
+ * memory is one pass plus the per-atom accumulators, whatever F is.  Synchronous. */
+arp_status arp_sasa_ensemble(arp_context *ctx, const arp_structure *topology, uint64_t n_frames, const double *xyz, const char *chains, float probe,
+                             int32_t n_points, int32_t with_sap, float sap_radius, uint64_t *n_rows, uint64_t *frames_used, uint32_t *out_atoms,
+                             float *mean_sasa, float *std_sasa, float *min_sasa, float *max_sasa, float *mean_sap, float *std_sap, float *min_sap,
+                             float *max_sap, float *total_sasa, int32_t *out_count, float *out_sap);
+/* The host-side finishing of arp_sasa_ensemble on its own (no device): the formulas above from the accumulators of m atoms; R = radius + probe.
+ * t1 / t2 / mean_sap / std_sap are given together or all NULL. */
+arp_status arp_sasa_ensemble_stats(uint64_t n_frames, uint64_t m, const float *R, int32_t n_points, const uint64_t *s1, const uint64_t *s2,
+                                   const int32_t *cmin, const int32_t *cmax, const double *t1, const double *t2, float *mean_sasa, float *std_sasa,
+                                   float *min_sasa, float *max_sasa, float *mean_sap, float *std_sap);
 
 /* The same 20 columns through the Arrow C Data Interface (a struct array = one record batch; utf8 strings, nullable
  * f32 sc_* columns): what pyo3-polars hands to Python in the reference (python.rs:55, mod.rs:140-214), importable with
