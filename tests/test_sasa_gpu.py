@@ -108,11 +108,24 @@ def test_analytic_cases(ctx):
     sasa, count = aa.atom_sasa(ctx, [1.0], [2.0], [3.0], one, probe=1.4, n_points=100)
     R = np.float32(np.float32(1.7) + np.float32(1.4))
     assert count.tolist() == [100] and sasa[0] == np.float32(4.0 * np.pi * float(R) * float(R))
-    # two atoms exactly R_i + R_j apart (representable: R = 2 + 1 = 3, centres 6 apart): nothing is buried (strict <)
+    # two atoms exactly R_i + R_j apart along x (representable: R = 2 + 1 = 3, centres 6 apart): nothing is buried -- but not because the test is
+    # strict: no golden-spiral point lies on the x axis (point 0 is the pole (0, 0, 1) for every n_points), so no point touches the other sphere
     sasa, count = aa.atom_sasa(ctx, [0.0, 6.0], [0.0, 0.0], [0.0, 0.0], np.array([2.0, 2.0], np.float32), probe=1.0, n_points=1)
     assert count.tolist() == [1, 1]
     sasa, count = aa.atom_sasa(ctx, [0.0, 6.0], [0.0, 0.0], [0.0, 0.0], np.array([2.0, 2.0], np.float32), probe=1.0, n_points=64)
     assert count.tolist() == [64, 64]
+    # the strict edge: along z point 0 of the lower atom sits at d^2 == R_j^2 exactly -- open; one f32 step closer it is buried
+    closer = float(np.nextafter(np.float32(6.0), np.float32(0.0)))
+    for n_points, full in ((1, 1), (64, 64)):
+        sasa, count = aa.atom_sasa(ctx, [0.0, 0.0], [0.0, 0.0], [0.0, 6.0], np.array([2.0, 2.0], np.float32), probe=1.0, n_points=n_points)
+        assert count.tolist() == [full, full]
+        sasa, count = aa.atom_sasa(ctx, [0.0, 0.0], [0.0, 0.0], [0.0, closer], np.array([2.0, 2.0], np.float32), probe=1.0, n_points=n_points)
+        assert count.tolist() == [full - 1, full]
+    sasa, count = aa.atom_sasa(ctx, [0.0, 0.0], [0.0, 0.0], [100.0, 110.5], np.array([0.5, 10.0], np.float32), probe=0.0, n_points=1)
+    assert count.tolist() == [1, 1]
+    sasa, count = aa.atom_sasa(ctx, [0.0, 0.0], [0.0, 0.0], [100.0, float(np.nextafter(np.float32(110.5), np.float32(0.0)))], np.array([0.5, 10.0], np.float32),
+                               probe=0.0, n_points=1)
+    assert count.tolist() == [0, 1]
     # an atom inside a much larger one
     sasa, count = aa.atom_sasa(ctx, [0.0, 0.5], [0.0, 0.0], [0.0, 0.0], np.array([10.0, 1.0], np.float32), probe=1.4, n_points=100)
     assert count[1] == 0 and sasa[1] == 0.0 and count[0] == 100
