@@ -1,4 +1,4 @@
-// Internal declarations shared by the HIP kernels (kernels.hip) and the host engine (engine.cpp).
+// Internal declarations shared by the HIP kernels (kernels.hip) and the host engine (engine.cpp, batch.cpp, sasa_dev.cpp; their own internals: engine.h).
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -10,7 +10,7 @@
 namespace arp {
 
 // SAP residue table (src/sap.rs:41-101): name, hydrophobicity (Black & Mould, shifted so that glycine is 0), largest side-chain SASA.
-// One list for arp_sap_weight (engine.cpp) and the device weight kernel (sasa.inl): the code of a residue is its position here.
+// One list for arp_sap_weight (sasa_dev.cpp) and the device weight kernel (sasa.inl): the code of a residue is its position here.
 #define ARP_SAP_RESIDUES(X)                                                                                                          \
     X("ALA", 0.616f - 0.501f, 15.395f) X("ARG", 0.000f - 0.501f, 124.338f) X("ASN", 0.236f - 0.501f, 90.303f)                       \
     X("ASP", 0.028f - 0.501f, 87.601f) X("CYS", 0.680f - 0.501f, 46.456f) X("GLU", 0.043f - 0.501f, 95.534f)                        \
@@ -123,8 +123,20 @@ constexpr uint32_t kRkOrdBits = 20, kRkOrdMax = (1u << kRkOrdBits) - 3u, kRkChai
 constexpr uint32_t kTaskCtrStride = 32;                       // words
 constexpr uint32_t kTaskCtrWords = 4 * 8 * kTaskCtrStride;    // [mode][group]
 
+// The device/host result contract.  Words of Workspace::result that a pair pass publishes (the host reads the first kResultWords of them into
+// arp_context::h_result after every pass; the kernels write them, engine.cpp pass_collect reads them): total pairs; status bits (kStat*); emit
+// allocator head (64-record units; records in the hole-free sequence); chunks of the deferred-probe list; how many of the first 255 atoms
+// carry their predecessor's residue word (k_place: the launcher's hint for the next call).  kSasaTestsWord: the SASA kernel's f32 distance tests.
+enum : uint32_t { kResPairs = 0, kResFlags = 1, kResEmitHead = 2, kResDeferred = 3, kResResRuns = 4, kResultWords = 5, kSasaTestsWord = 8 };
+// Status bits: the list did not fit the capacity / CYS SG..SG covalent pair whose residue has no CB / non-finite coordinate / the deferred-probe
+// list overflowed / k_fixup's hole plan is inconsistent / model ids too sparse for the workspace / the probe pass was skipped on a stale memo
+constexpr unsigned long long kStatCapacity = 1, kStatCysNoCb = 2, kStatNonFinite = 4, kStatDeferOverflow = 8, kStatHolePlan = 16,
+                             kStatSparseModels = 64, kStatStaleSkip = 128;
+// the pinned host block of a context (arp_context::h_result): the kResultWords of the last pair pass, then slots of other calls
+constexpr uint32_t kHostSasaTestsSlot = 6, kHostResultWords = 8;
+
 struct Workspace {
-    double *partials;         // k_bounds: [256][8] per-block partial results
+    double *partials;        // k_bounds: [256][8] per-block partial results
     uint32_t *tickets;        // self-resetting arrival counters: [0] bounds, [1] cell scan, [2] pair scan
     GridParams *grid;
     DevParams *params;
@@ -139,8 +151,7 @@ struct Workspace {
     unsigned long long *task_base;  // n/64 + 2
     uint32_t *scan_tmp;       // block sums (1024 + 1)
     unsigned long long *scan_tmp64;
-    unsigned long long *result;  // [0] = total pairs, [1] = flags, [2] = emit allocator head (64-record units), [3] = deferred candidates,
-                                 // [4] = how many of the first 255 atoms carry their predecessor's residue word (k_place: the launcher's hint for the next call)
+    unsigned long long *result;  // the words kRes* above (+ kSasaTestsWord; from word 32 on the chunk totals of k_scan_single)
     ulonglong2 *hole_list;    // emit mode: one (start, length) per block
     arp_pair *scratch;        // emit mode: home of positions >= the caller's capacity until k_fixup has closed the holes
     unsigned long long scratch_cap;
@@ -184,13 +195,12 @@ void launch_count(const DevAtoms &in, const Workspace &ws, hipStream_t st, Profi
 void launch_fill_ordered(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsigned long long capacity, hipStream_t st, Profiler *prof,
                          bool contacts_only);
 bool launch_emit(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsigned long long capacity, hipStream_t st, Profiler *prof, bool contacts_only,
-                 bool skip_deferred, bool res_filter = false);  // true: the hole-free sequence of small inputs ran (the host derives result[0] and the flags: engine.cpp finish_result)
+                 bool skip_deferred, bool res_filter = false);  // true: the hole-free sequence of small inputs ran (the host derives kResPairs and the flags: engine.cpp finish_result)
 bool emit_takes_res_filter(const DevAtoms &in);  // the single-pass emitter has residue-rule kernels for an input of this size (the grid build then writes Sorted::rkey)
 unsigned long long emit_scratch_records();
 void launch_neighbor_sum(const DevAtoms &in, const Workspace &ws, double radius, double r2, const float *weight, float *out, hipStream_t st, Profiler *prof);
 // Atom SASA (sasa.inl): grid over the atoms without ARP_ATTR_H, then one wave per grid atom.  sasa / count are indexed like the input arrays
 // (atoms outside the grid are not written).  The kernel adds its number of f32 distance tests to Workspace::result[kSasaTestsWord].
-constexpr uint32_t kSasaTestsWord = 8;
 void launch_sasa(const DevAtoms &in, const Workspace &ws, double cutoff, const float *R, const float *sphere, uint32_t n_points, float r_max,
                  float *sasa, int32_t *count, hipStream_t st, Profiler *prof);
 // w[j] = arp_sap_weight(ARP_SAP_RESIDUES name code[j], sasa[src[j]]), 0 where src[j] < 0 or code[j] >= 20

@@ -107,7 +107,7 @@ DEVFN void split_range(unsigned long long P, unsigned long long *lo, unsigned lo
 // (capacity: the records `pairs` holds.  A pack whose list did not fit -- result[0] > capacity: the fix-up then only reports the size, and the host grows
 // the buffer and runs the pack again -- is not split at all: round 5 found the split kernels reading result[0] records out of a buffer that held
 // fewer, a fault as soon as the excess left the allocation's padding.)
-DEVFN unsigned long long split_records(const unsigned long long *result, unsigned long long capacity) { return result[0] <= capacity ? result[0] : 0ull; }
+DEVFN unsigned long long split_records(const unsigned long long *result, unsigned long long capacity) { return result[kResPairs] <= capacity ? result[kResPairs] : 0ull; }
 __global__ __launch_bounds__(kSplitThreads) void k_split_count(const unsigned long long *result, unsigned long long capacity, const arp_pair *pairs, uint32_t K, const PackDesc *desc,
                                                                unsigned long long *count) {
     const unsigned long long P = split_records(result, capacity);

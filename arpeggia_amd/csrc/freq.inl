@@ -131,14 +131,14 @@ struct FreqBufs {
 arp_status freq_alloc(FreqBufs *b, uint64_t cap, uint64_t keep, hipStream_t st) {
     if (cap > 0x7FFFFFF0ull) { set_error("contact frequencies: more than 2^31 items in one pass (lower freq_chunk_atoms)"); return ARP_ERR_CAPACITY; }
     size_t sort_bytes = 0, scan_bytes = 0;
-    TRY_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (const uint32_t *)nullptr,
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (const uint32_t *)nullptr,
                                                (uint32_t *)nullptr, (int)cap, 0, 64, st));
-    TRY_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)cap, st));
+    HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)cap, st));
     const size_t tmp = std::max(sort_bytes, scan_bytes);
-    const uint64_t bytes = 3 * al(cap * 8) + 2 * al(cap * sizeof(FreqVal)) + 4 * al(cap * 4) + al(256) + al(tmp);
+    const uint64_t bytes = 3 * seg_align(cap * 8) + 2 * seg_align(cap * sizeof(FreqVal)) + 4 * seg_align(cap * 4) + seg_align(256) + seg_align(tmp);
     char *block = nullptr;
-    TRY_HIP(hipMalloc((void **)&block, bytes));
-    Bump bp{block, 0, bytes};
+    HIP_TRY(hipMalloc((void **)&block, bytes));
+    Bump bp{block};
     FreqBufs nb;
     nb.block = block; nb.cap = cap;
     nb.kin = bp.take<unsigned long long>(cap); nb.ks = bp.take<unsigned long long>(cap); nb.kout = bp.take<unsigned long long>(cap);
@@ -146,10 +146,10 @@ arp_status freq_alloc(FreqBufs *b, uint64_t cap, uint64_t keep, hipStream_t st) 
     nb.iota = bp.take<uint32_t>(cap); nb.is = bp.take<uint32_t>(cap); nb.head = bp.take<uint32_t>(cap); nb.scan = bp.take<uint32_t>(cap);
     nb.counter = bp.take<uint32_t>(64); nb.tmp = bp.take<char>(tmp); nb.tmp_bytes = tmp;
     if (keep && b->block) {  // the aggregate moves into the new block
-        TRY_HIP(hipMemcpyAsync(nb.kin, b->kin, keep * 8, hipMemcpyDeviceToDevice, st));
-        TRY_HIP(hipMemcpyAsync(nb.vin, b->vin, keep * sizeof(FreqVal), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(nb.kin, b->kin, keep * 8, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(nb.vin, b->vin, keep * sizeof(FreqVal), hipMemcpyDeviceToDevice, st));
     }
-    TRY_HIP(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(st));
     if (b->block) (void)hipFree(b->block);
     *b = nb;
     return ARP_OK;
@@ -158,7 +158,7 @@ arp_status freq_alloc(FreqBufs *b, uint64_t cap, uint64_t keep, hipStream_t st) 
 
 arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost *out) {
     hipStream_t st = (hipStream_t)context_stream(ctx);
-    TRY_HIP(hipSetDevice(context_device(ctx)));
+    HIP_TRY(hipSetDevice(context_device(ctx)));
     const bool timing = g_debug.timing != 0;
     auto t_prev = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
@@ -182,18 +182,18 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
                              {nr ? job.res_h_ptr : nullptr, nr ? (nr + 1) * 4 : 0}, {nh ? job.res_h_idx : nullptr, nh * 4}, {nr ? job.res_cb : nullptr, nr * 4},
                              {nr ? job.res_sg : nullptr, nr * 4}};
     uint64_t topo_bytes = 0;
-    for (const Seg &g : topo_seg) topo_bytes += al(g.bytes);
+    for (const Seg &g : topo_seg) topo_bytes += seg_align(g.bytes);
     const uint64_t pn = per * n, pr = per * nr, ph = per * nh;
-    const uint64_t pack_bytes = al(pn * 24) + 3 * al(pn * 8) + 5 * al(pn * 4) + al((pr + 1) * 4) + 2 * al(pr * 4) + al(ph * 4);
+    const uint64_t pack_bytes = seg_align(pn * 24) + 3 * seg_align(pn * 8) + 5 * seg_align(pn * 4) + seg_align((pr + 1) * 4) + 2 * seg_align(pr * 4) + seg_align(ph * 4);
     char *block = nullptr;
-    TRY_HIP(hipMalloc((void **)&block, topo_bytes + pack_bytes + 256));
+    HIP_TRY(hipMalloc((void **)&block, topo_bytes + pack_bytes + 256));
     std::unique_ptr<char, void (*)(char *)> block_owner(block, [](char *p) { (void)hipFree(p); });
-    Bump bp{block, 0, topo_bytes + pack_bytes + 256};
+    Bump bp{block};
     const void *topo_dev[8];
     for (int k = 0; k < 8; k++) {
         char *d = bp.take<char>(topo_seg[k].bytes);
         topo_dev[k] = d;
-        if (topo_seg[k].bytes) TRY_HIP(hipMemcpyAsync(d, topo_seg[k].src, topo_seg[k].bytes, hipMemcpyHostToDevice, st));
+        if (topo_seg[k].bytes) HIP_TRY(hipMemcpyAsync(d, topo_seg[k].src, topo_seg[k].bytes, hipMemcpyHostToDevice, st));
     }
     FreqTopo tp{(uint32_t)n, (uint32_t)nr, (uint32_t)nh, (const uint32_t *)topo_dev[0], (const uint32_t *)topo_dev[1], (const uint32_t *)topo_dev[2],
                 (const uint32_t *)topo_dev[3], (const uint32_t *)topo_dev[4], (const uint32_t *)topo_dev[5], (const uint32_t *)topo_dev[6], (const uint32_t *)topo_dev[7]};
@@ -218,10 +218,10 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
     for (uint64_t f0 = 0; f0 < F; f0 += per) {
         const uint64_t fc = std::min<uint64_t>(per, F - f0);
         // 1. upload: the chunk's coordinates only; the tiling kernel writes the per-frame arrays
-        TRY_HIP(hipMemcpyAsync(xyz, job.xyz + f0 * n * 3, fc * n * 24, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(xyz, job.xyz + f0 * n * 3, fc * n * 24, hipMemcpyHostToDevice, st));
         const uint64_t W = std::max<uint64_t>({n, nr ? nr + 1 : 0, nh});
         hipLaunchKernelGGL(k_freq_tile, dim3(std::min<uint32_t>(freq_blocks(fc * W), 1u << 16)), dim3(256), 0, st, (uint32_t)fc, (uint32_t)W, (const double *)xyz, tp, pk);
-        TRY_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         // 2. the pair pass over the packed frames (contacts only: what arp_get_contacts turns into rows)
         arp_atoms av{};
         av.n = fc * n; av.x = pk.x; av.y = pk.y; av.z = pk.z; av.attr = pk.attr; av.res_ord = pk.res_ord; av.chain_rank = pk.chain_rank; av.model = pk.model;
@@ -239,12 +239,12 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
         if (!fb.block && (s = freq_alloc(&fb, std::max<uint64_t>(1u << 16, 2 * n_pairs), 0, st)) != ARP_OK) return s;
         uint32_t n_items = 0;
         for (int attempt = 0;; attempt++) {
-            TRY_HIP(hipMemsetAsync(fb.counter, 0, 4, st));
+            HIP_TRY(hipMemsetAsync(fb.counter, 0, 4, st));
             hipLaunchKernelGGL(k_freq_expand, dim3(freq_blocks(n_pairs)), dim3(256), 0, st, pairs, (uint32_t)n_pairs, (uint32_t)n, fb.kin, fb.vin, (uint32_t)n_agg,
                                (uint32_t)fb.cap, fb.counter);
-            TRY_HIP(hipGetLastError());
-            TRY_HIP(hipMemcpyAsync(&n_items, fb.counter, 4, hipMemcpyDeviceToHost, st));
-            TRY_HIP(hipStreamSynchronize(st));
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&n_items, fb.counter, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
             if (n_agg + n_items <= fb.cap) break;
             if (attempt) { set_error("internal error: the item count changed between passes"); return ARP_ERR_HIP; }
             const uint64_t want = n_agg + n_items;
@@ -256,17 +256,17 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
         const uint32_t m = (uint32_t)(n_agg + n_items);
         size_t tb = fb.tmp_bytes;
         hipLaunchKernelGGL(k_iota, dim3(freq_blocks(m)), dim3(256), 0, st, m, fb.iota);
-        TRY_HIP(hipcub::DeviceRadixSort::SortPairs(fb.tmp, tb, (const unsigned long long *)fb.kin, fb.ks, (const uint32_t *)fb.iota, fb.is, (int)m, 0, end_bit, st));
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(fb.tmp, tb, (const unsigned long long *)fb.kin, fb.ks, (const uint32_t *)fb.iota, fb.is, (int)m, 0, end_bit, st));
         hipLaunchKernelGGL(k_freq_heads, dim3(freq_blocks(m)), dim3(256), 0, st, m, (const unsigned long long *)fb.ks, fb.head);
         tb = fb.tmp_bytes;
-        TRY_HIP(hipcub::DeviceScan::InclusiveSum(fb.tmp, tb, (const uint32_t *)fb.head, fb.scan, (int)m, st));
+        HIP_TRY(hipcub::DeviceScan::InclusiveSum(fb.tmp, tb, (const uint32_t *)fb.head, fb.scan, (int)m, st));
         hipLaunchKernelGGL(k_freq_init, dim3(freq_blocks(m)), dim3(256), 0, st, m, fb.vout);
         hipLaunchKernelGGL(k_freq_reduce, dim3(freq_blocks(m)), dim3(256), 0, st, m, (const unsigned long long *)fb.ks, (const uint32_t *)fb.is, (const FreqVal *)fb.vin,
                            (const uint32_t *)fb.scan, fb.kout, fb.vout);
-        TRY_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         uint32_t runs = 0;
-        TRY_HIP(hipMemcpyAsync(&runs, fb.scan + (m - 1u), 4, hipMemcpyDeviceToHost, st));
-        TRY_HIP(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(&runs, fb.scan + (m - 1u), 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         std::swap(fb.kin, fb.kout); std::swap(fb.vin, fb.vout);
         n_agg = runs;
         lap("sort + reduce");
@@ -275,9 +275,9 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
     out->key.resize(n_agg); out->count.resize(n_agg); out->mn.resize(n_agg); out->mx.resize(n_agg);
     if (n_agg) {
         std::vector<FreqVal> v(n_agg);
-        TRY_HIP(hipMemcpyAsync(out->key.data(), fb.kin, n_agg * 8, hipMemcpyDeviceToHost, st));
-        TRY_HIP(hipMemcpyAsync(v.data(), fb.vin, n_agg * sizeof(FreqVal), hipMemcpyDeviceToHost, st));
-        TRY_HIP(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(out->key.data(), fb.kin, n_agg * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(v.data(), fb.vin, n_agg * sizeof(FreqVal), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         auto decode = [](uint32_t c) { const uint32_t b = (c & 0x80000000u) ? (c & 0x7FFFFFFFu) : ~c; float f; memcpy(&f, &b, 4); return f; };
         for (uint64_t r = 0; r < n_agg; r++) { out->count[r] = v[r].count; out->mn[r] = decode(v[r].mn); out->mx[r] = decode(v[r].mx); }
     }

@@ -278,8 +278,8 @@ DEVFN void setup_block(BoxAcc &acc, SetupLds &l, bool publish, GridParams *g, De
         if (publish) {
             *g = gl; prm->r2 = r2; prm->r2f = r2f; prm->s_cov_max = cov_max;
             // the input errors as status flags right away (k_fixup and the count scan set them again; the hole-free sequence of small inputs has neither)
-            const unsigned long long fl = ((gl.bad & 1u) ? 4ull : 0ull) | ((gl.bad & 2u) ? 64ull : 0ull);
-            if (fl) atomicOr(&result[1], fl);
+            const unsigned long long fl = ((gl.bad & 1u) ? kStatNonFinite : 0ull) | ((gl.bad & 2u) ? kStatSparseModels : 0ull);
+            if (fl) atomicOr(&result[kResFlags], fl);
         }
     }
     __syncthreads();
@@ -464,10 +464,10 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_apply(uint32_t *in, const
         const TOut total = grand;
         out[n] = total;
         if (FINISH) {  // the pair-count scan also publishes the result word and the status flags
-            result[0] = (unsigned long long)total;
-            if (have_out && (unsigned long long)total > capacity) result[1] |= 1ull;
-            if (g->bad & 1u) result[1] |= 4ull;
-            if (g->bad & 2u) result[1] |= 64ull;
+            result[kResPairs] = (unsigned long long)total;
+            if (have_out && (unsigned long long)total > capacity) result[kResFlags] |= kStatCapacity;
+            if (g->bad & 1u) result[kResFlags] |= kStatNonFinite;
+            if (g->bad & 2u) result[kResFlags] |= kStatSparseModels;
         }
     }
 }
@@ -656,7 +656,7 @@ DEVFN uint32_t residue_word(uint32_t res_ord, uint32_t chain_rank, bool *bad) {
 // RKEY: also write the residue words of the slots (the launcher is about to run the residue-rule kernels, k_emit<.., RES>).
 // Block 0 always leaves result[4] = how many of atoms 1..255 carry their predecessor's residue word: inputs whose residues are runs of atoms
 // (every protein; not a cloud of one-atom residues) are the ones the residue-rule kernels pay for, and the engine picks the kernels of the
-// NEXT call by it (engine.cpp res_filter_for) -- a choice between two kernels with identical results, never a correctness assumption.
+// NEXT call by it (engine.cpp grid_for_call) -- a choice between two kernels with identical results, never a correctness assumption.
 template <bool RKEY>
 __global__ __launch_bounds__(256) void k_place(DevAtoms in, GridParams *gp, const uint32_t *cell_start, const uint32_t *cell_of_atom,
                                                const uint32_t *rank_of_atom, Sorted so, unsigned long long *result) {
@@ -669,7 +669,7 @@ __global__ __launch_bounds__(256) void k_place(DevAtoms in, GridParams *gp, cons
         const uint32_t ip = threadIdx.x ? threadIdx.x - 1u : 0u, iq = min(threadIdx.x, last);
         const uint32_t wp = residue_word(in.res_ord[min(ip, last)], in.chain_rank[min(ip, last)], &b0), wq = residue_word(in.res_ord[iq], in.chain_rank[iq], &b1);
         const int runs = __syncthreads_count(threadIdx.x != 0u && threadIdx.x <= last && wp == wq && !b0 && !b1);
-        if (threadIdx.x == 0u) result[4] = (unsigned long long)runs;
+        if (threadIdx.x == 0u) result[kResResRuns] = (unsigned long long)runs;
     }
     const bool any_h = in.n_res != 0u && in.res_h_ptr[in.n_res] != 0u;  // (wave-uniform)
     const double *morg = gp->model_org;

@@ -1,4 +1,4 @@
-// Host-side declarations shared by engine.cpp, structure.cpp and table.cpp.
+// Host-side declarations shared by the host sources (engine.cpp, batch.cpp, sasa_dev.cpp, structure.cpp, table.cpp, table_dev.hip).
 #pragma once
 #include <array>
 #include <cstdarg>
@@ -19,12 +19,29 @@ namespace arp {
 
 void set_error(const char *fmt, ...);
 
+// A block that holds several arrays is carved into 256-byte aligned segments.  The rule lives here and nowhere else.
+constexpr uint64_t seg_align(uint64_t bytes) { return (bytes + 255u) & ~255ull; }
+struct Carver {  // the offset of the next segment; offsets only: one layout serves a device block and its pinned twin
+    uint64_t off = 0;
+    uint64_t take(uint64_t bytes) { const uint64_t at = off; off += seg_align(bytes); return at; }
+};
+
 // No exception may cross the C ABI (SURVEY.md 8b "Errors": the reference panics, a C boundary returns a status).  Every status-returning entry
 // point that allocates or starts threads is a function-try-block that ends in this: `extern "C" arp_status f(...) try { ... } ARP_ABI_CATCH`.
 #define ARP_ABI_CATCH                                                                                                               \
     catch (const std::bad_alloc &) { arp::set_error("out of host memory"); return ARP_ERR_OOM; }                                   \
     catch (const std::exception &e_) { arp::set_error("internal error: %s", e_.what()); return ARP_ERR_HIP; }                       \
     catch (...) { arp::set_error("internal error: unknown exception"); return ARP_ERR_HIP; }
+
+// A failing HIP runtime call ends the calling function with a status (OOM told apart) and a message naming the call.
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) {                                                                    \
+            arp::set_error("HIP error %d (%s) at %s:%d: %s", (int)e_, hipGetErrorString(e_), __FILE__, __LINE__, #expr); \
+            return (e_ == hipErrorOutOfMemory) ? ARP_ERR_OOM : ARP_ERR_HIP;                        \
+        }                                                                                          \
+    } while (0)
 
 // Fixed-width, NUL-padded string column (n x W chars), the layout the C ABI hands to numpy / Rust.
 template <int W>
@@ -89,7 +106,7 @@ struct arp_structure {
 };
 
 namespace arp {
-// Atom SASA (+ the SAP chain) on the device: engine.cpp runs it, arp_atom_sasa and the structure-level entry points (sasa.cpp) fill the job.
+// Atom SASA (+ the SAP chain) on the device: sasa_dev.cpp runs it, arp_atom_sasa and the structure-level entry points (sasa.cpp) fill the job.
 struct SasaJob {
     uint64_t n = 0;                        // atoms of the job, host arrays of n entries
     const double *x = nullptr, *y = nullptr, *z = nullptr;  // f64 coordinates: SASA rounds them to f32, the SAP neighbour sum takes them as they are
@@ -107,7 +124,7 @@ struct SasaJob {
 };
 // sasa / count / sap (nullable) receive n entries; one synchronisation at the end.  Inputs are checked by the callers.
 arp_status sasa_run(arp_context *ctx, const SasaJob &job, float *sasa, int32_t *count, float *sap);
-// SASA / SAP statistics over the frames of an ensemble (arp_sasa_ensemble): engine.cpp ens_run packs the frames into
+// SASA / SAP statistics over the frames of an ensemble (arp_sasa_ensemble): sasa_dev.cpp ens_run packs the frames into
 // passes and runs them (kernels in ens.inl + the unchanged SASA / SAP kernels); sasa.cpp selects, checks and finishes.  Host arrays.
 struct EnsJob {
     uint64_t n_top = 0, m = 0, n_frames = 0;  // atoms a frame's coordinates cover, selected atoms, frames

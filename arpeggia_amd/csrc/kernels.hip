@@ -157,7 +157,7 @@ __device__ __noinline__ int disulfide_probe(const double *X, const double *Y, co
     uint32_t r1 = res_id[ix], r2 = res_id[iy];
     uint32_t cb1 = res_cb[r1], s1 = res_sg[r1], s2 = res_sg[r2], cb2 = res_cb[r2];
     if (cb1 == ARP_NONE || cb2 == ARP_NONE || s1 == ARP_NONE || s2 == ARP_NONE) {
-        atomicOr(&result[1], 2ull);  // the reference unwrap()s and panics here
+        atomicOr(&result[kResFlags], kStatCysNoCb);  // the reference unwrap()s and panics here
         return 0;
     }
     const double a[3] = {X[cb1], Y[cb1], Z[cb1]}, b[3] = {X[s1], Y[s1], Z[s1]}, c[3] = {X[s2], Y[s2], Z[s2]}, d[3] = {X[cb2], Y[cb2], Z[cb2]};

@@ -100,7 +100,7 @@ DEVFN uint4 *emit_slot(const EmitTarget &tg, unsigned long long pos, unsigned lo
     if (pos < tg.capacity) return reinterpret_cast<uint4 *>(tg.out) + pos;
     const unsigned long long q = pos - tg.capacity;
     if (q < tg.scratch_cap) return reinterpret_cast<uint4 *>(tg.scratch) + q;
-    atomicOr(&result[1], 1ull);
+    atomicOr(&result[kResFlags], kStatCapacity);
     return nullptr;
 }
 
@@ -234,12 +234,12 @@ DEVFN uint32_t process_batch(const DevAtoms &in, const LdsParams &prm, const Sor
                 const bool defer = valid && r.w == kDeferKind && pos < tg.capacity;
                 const unsigned long long dm = __ballot(defer);
                 if (dm) {
-                    const Slots ds = alloc_chunked<kDeferChunk>(bl.defer_state, &result[3], 2u * (uint32_t)__popcll(dm), lane);
+                    const Slots ds = alloc_chunked<kDeferChunk>(bl.defer_state, &result[kResDeferred], 2u * (uint32_t)__popcll(dm), lane);
                     if (defer) {
                         const uint32_t dr = 2u * mbcnt(dm);
                         const unsigned long long p = dr < ds.n0 ? ds.pos0 + dr : ds.pos1 + (dr - ds.n0);
                         if (p + 1ull < tg.defer_cap) { tg.defer_list[p] = ent; tg.defer_list[p + 1ull] = make_uint2((uint32_t)pos, (uint32_t)(pos >> 32)); }
-                        else atomicOr(&result[1], 8ull);
+                        else atomicOr(&result[kResFlags], kStatDeferOverflow);
                     }
                 }
             }
@@ -250,11 +250,11 @@ DEVFN uint32_t process_batch(const DevAtoms &in, const LdsParams &prm, const Sor
                 if (dm) {  // hand the candidates to the deferred pass.  The list is carved in kDeferChunk-entry chunks by the
                            // same block-level allocator as the records: one device atomic per wave and batch on result[3]
                            // serialised hydrogen-rich inputs at ~90 ns each (measured: 2.0 ms on a 150k-atom structure).
-                    const Slots ds = alloc_chunked<kDeferChunk>(bl.defer_state, &result[3], (uint32_t)__popcll(dm), lane);
+                    const Slots ds = alloc_chunked<kDeferChunk>(bl.defer_state, &result[kResDeferred], (uint32_t)__popcll(dm), lane);
                     if (defer) {
                         const uint32_t dr = mbcnt(dm);
                         const unsigned long long p = dr < ds.n0 ? ds.pos0 + dr : ds.pos1 + (dr - ds.n0);
-                        if (p < tg.defer_cap) tg.defer_list[p] = ent; else atomicOr(&result[1], 8ull);
+                        if (p < tg.defer_cap) tg.defer_list[p] = ent; else atomicOr(&result[kResFlags], kStatDeferOverflow);
                     }
                     valid = valid && !defer;
                     vm = __ballot(valid);
@@ -262,7 +262,7 @@ DEVFN uint32_t process_batch(const DevAtoms &in, const LdsParams &prm, const Sor
             }
             const uint32_t n = (uint32_t)__popcll(vm);
             if (n) {  // compacted, coalesced store of the batch's records straight from registers
-                const Slots sl = alloc_chunked_rt(bl.alloc_state, &result[2], n, lane, bl.chunk_shift);
+                const Slots sl = alloc_chunked_rt(bl.alloc_state, &result[kResEmitHead], n, lane, bl.chunk_shift);
                 const uint32_t rank = mbcnt(vm);
                 if (sl.n0 == n && sl.pos0 + n <= tg.capacity) {
                     // the common case, decided on the scalar unit: one run inside the caller's buffer -> scalar base + 32-bit lane offset
@@ -479,7 +479,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void k_pairs_deferred(DevAtoms
     __shared__ LdsParams prm;
     __shared__ WaveLds<kEmit> wl[kWavesPerBlock];
     __shared__ BlockLds bl;
-    const unsigned long long n = min(result[3] * kDeferChunk, tg.defer_cap);  // result[3] counts list chunks
+    const unsigned long long n = min(result[kResDeferred] * kDeferChunk, tg.defer_cap);  // result[3] counts list chunks
     if (n == 0ull) {  // nothing was deferred (no hydrogens, no close CYS SG pair): no parameter tables, no hole
         if (threadIdx.x == 0) hole_list[blockIdx.x] = make_ulonglong2(0ull, 0ull);
         return;
@@ -507,7 +507,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void k_pairs_deferred(DevAtoms
 __global__ __launch_bounds__(kWavesPerBlock * 64) void k_patch_deferred(DevAtoms in, const DevParams *dprm, Sorted so, EmitTarget tg,
                                                                          unsigned long long *result) {
     __shared__ LdsParams prm;
-    const unsigned long long n = min(result[3] * kDeferChunk, tg.defer_cap) / 2ull;  // {entry, position} pairs
+    const unsigned long long n = min(result[kResDeferred] * kDeferChunk, tg.defer_cap) / 2ull;  // {entry, position} pairs
     if (n == 0ull) return;  // nothing was deferred (no hydrogens, no close CYS SG pair)
     load_lds_params(prm, dprm, nullptr);
     const uint4 *list = reinterpret_cast<const uint4 *>(tg.defer_list);
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(kFixThreads) void k_fixup(const ulonglong2 *hole_li
     const ulonglong2 h0 = (e0 < n_holes) ? hole_list[e0] : make_ulonglong2(0ull, 0ull);
     const ulonglong2 h1 = (e1 < n_holes) ? hole_list[e1] : make_ulonglong2(0ull, 0ull);
     const uint32_t sh = chunk_shift;  // records per chunk = 1 << sh (what the emit kernels of this launch sequence allocated in)
-    const unsigned long long R = result[2] << sh;
+    const unsigned long long R = result[kResEmitHead] << sh;
     unsigned long long holes_total;
     scan1024_u64(h0.y + h1.y, red, &holes_total);
     const unsigned long long P = R - holes_total;
@@ -587,12 +587,12 @@ __global__ __launch_bounds__(kFixThreads) void k_fixup(const ulonglong2 *hole_li
     if (i == 0) { fpre[kMaxHoles] = F; tpre[kMaxHoles] = T; }
     __syncthreads();
     if (blockIdx.x == 0 && i == 0) {
-        result[0] = P;
-        if (P > tg.capacity) result[1] |= 1ull;
-        if (F != T) result[1] |= 16ull;  // internal consistency check of the plan
-        if (g->bad & 1u) result[1] |= 4ull;
-        if (g->bad & 2u) result[1] |= 64ull;
-        if (no_deferred_pass && result[3] != 0ull) result[1] |= 128ull;
+        result[kResPairs] = P;
+        if (P > tg.capacity) result[kResFlags] |= kStatCapacity;
+        if (F != T) result[kResFlags] |= kStatHolePlan;  // internal consistency check of the plan
+        if (g->bad & 1u) result[kResFlags] |= kStatNonFinite;
+        if (g->bad & 2u) result[kResFlags] |= kStatSparseModels;
+        if (no_deferred_pass && result[kResDeferred] != 0ull) result[kResFlags] |= kStatStaleSkip;
     }
     if (P > tg.capacity || F != T) return;  // the caller's buffer cannot hold the table: report the size only
     // The copy.  List entry e with a part of f = fpre[e + 1] - fpre[e] slots below P takes the records fpre[e] .. fpre[e] + f of the tail's
@@ -775,7 +775,7 @@ bool emit_takes_res_filter(const DevAtoms &in) {
 }
 // single-pass emit + hole fix-up: leaves result[0] = number of pairs, out[0..P) contiguous
 // Returns true when the hole-free sequence of small inputs ran: result[0] and the flags k_fixup sets are then the host's to derive from
-// result[2] (the records) and result[3] (the deferred list's chunks) -- engine.cpp finish_result.
+// kResEmitHead (the records) and kResDeferred (the deferred list's chunks) -- engine.cpp finish_result.
 bool launch_emit(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsigned long long capacity, hipStream_t st, Profiler *prof, bool contacts_only,
                  bool skip_deferred, bool res_filter) {
     if (in.n >= kBigSlots) {  // beyond the 32-bit record offsets of the single-pass kernels: count + ordered fill with inline probes

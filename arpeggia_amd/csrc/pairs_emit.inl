@@ -302,14 +302,14 @@ DEVFN void stage_copy_g(const uint4 *buf, uint32_t n, unsigned long long pos, co
 DEVFN void stage_flush_g(StageRef &sg, const EmitTarget &tg, unsigned long long *result, uint32_t lane) {
     const uint32_t n = __builtin_amdgcn_readfirstlane(sg.n);
     if (n == 0u) return;
-    const Slots sl = alloc_direct(&result[2], n, lane);
+    const Slots sl = alloc_direct(&result[kResEmitHead], n, lane);
     stage_copy_g(sg.buf, n, sl.pos0, tg, lane);
     sg.n = 0u;
 }
 DEVFN void stage_flush_e(StageRef &sg, const EmitTarget &tg, unsigned long long *result, uint32_t lane) {
     const uint32_t n = __builtin_amdgcn_readfirstlane(sg.n);
     if (n == 0u) return;
-    const Slots sl = alloc_direct(&result[2], n, lane);
+    const Slots sl = alloc_direct(&result[kResEmitHead], n, lane);
     stage_copy_e(sg.buf, n, sl.pos0, tg, result, lane);
     sg.n = 0u;
 }
@@ -525,11 +525,11 @@ DEVFN void exact_finish_e(const ExactRegs &g, const ConstsE &K, const TablesE &t
         }
         if (ONLY) {
             if (m_defer) {  // candidates whose rules need a probe go to the deferred pass (k_pairs_deferred), as global slot pairs
-                const Slots ds = alloc_chunked<kDeferChunk>(bl.defer_state, &result[3], (uint32_t)__popcll(m_defer), lane);
+                const Slots ds = alloc_chunked<kDeferChunk>(bl.defer_state, &result[kResDeferred], (uint32_t)__popcll(m_defer), lane);
                 if (lm_lane(m_defer, lane)) {
                     const uint32_t dr = lm_rank(m_defer);
                     const unsigned long long p = dr < ds.n0 ? ds.pos0 + dr : ds.pos1 + (dr - ds.n0);
-                    if (p < tg.defer_cap) tg.defer_list[p] = make_uint2(slot0 + hl, nb); else atomicOr(&result[1], 8ull);
+                    if (p < tg.defer_cap) tg.defer_list[p] = make_uint2(slot0 + hl, nb); else atomicOr(&result[kResFlags], kStatDeferOverflow);
                 }
                 m_valid &= ~m_defer;
             }
@@ -537,7 +537,7 @@ DEVFN void exact_finish_e(const ExactRegs &g, const ConstsE &K, const TablesE &t
         }
         if (STAGE && m_defer) {  // launched on the engine's memo that this input defers nothing, and it does after all: the host repeats the call with the
                                  // chunked sequence and its probe pass (status bit 128, as k_fixup raises it for a skipped pass); these records do not matter
-            if (lane == 0u) atomicOr(&result[1], 128ull);
+            if (lane == 0u) atomicOr(&result[kResFlags], kStatStaleSkip);
             if (ONLY) n_rec = lm_count(m_valid);
             m_defer = 0ull;
         }
@@ -556,16 +556,16 @@ DEVFN void exact_finish_e(const ExactRegs &g, const ConstsE &K, const TablesE &t
             sg.n += n_rec;
             return;
         }
-        const Slots sl = alloc_finish<CHUNK>(bl.alloc_state, &result[2], n_rec, lane, u64_of(a_old));
+        const Slots sl = alloc_finish<CHUNK>(bl.alloc_state, &result[kResEmitHead], n_rec, lane, u64_of(a_old));
         const uint32_t rank = lm_rank(m_valid);
         if (!ONLY && m_defer) {  // the probe pass patches these kinds in place: it is told the records' final positions
-            const Slots ds = alloc_chunked<kDeferChunk>(bl.defer_state, &result[3], 2u * (uint32_t)__popcll(m_defer), lane);  // (even counts: a pair never straddles a chunk)
+            const Slots ds = alloc_chunked<kDeferChunk>(bl.defer_state, &result[kResDeferred], 2u * (uint32_t)__popcll(m_defer), lane);  // (even counts: a pair never straddles a chunk)
             if (lm_lane(m_defer, lane)) {
                 const unsigned long long pos = rank < sl.n0 ? sl.pos0 + rank : sl.pos1 + (rank - sl.n0);
                 const uint32_t dr = 2u * lm_rank(m_defer);
                 const unsigned long long p = dr < ds.n0 ? ds.pos0 + dr : ds.pos1 + (dr - ds.n0);
                 if (p + 1ull < tg.defer_cap) { tg.defer_list[p] = make_uint2(slot0 + hl, nb); tg.defer_list[p + 1ull] = make_uint2((uint32_t)pos, (uint32_t)(pos >> 32)); }
-                else atomicOr(&result[1], 8ull);
+                else atomicOr(&result[kResFlags], kStatDeferOverflow);
                 kind = 0u;
             }
         }
@@ -820,7 +820,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == kEWaves ? kEWavesPerSimd : 2) 
         if (threadIdx.x == 0u) {
             uint32_t total = 0;
             for (int k = 0; k < WAVES; k++) total += stg.wave_n[k];
-            stg.base = total ? atomicAdd(&result[2], (unsigned long long)total) : 0ull;
+            stg.base = total ? atomicAdd(&result[kResEmitHead], (unsigned long long)total) : 0ull;
         }
         __syncthreads();
         unsigned long long pos = stg.base;
@@ -874,6 +874,6 @@ bool launch_emit_e(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsig
     }
 #undef ARP_LAUNCH_E
     launch_emit_tail(in, ws, tg, nb, st, prof, skip_deferred, !contacts_only, (direct || stage) ? 1u : (shared ? kSmallChunkRecords : kChunkRecords));
-    return direct || stage;  // (the host derives the count and the capacity flag from result[2]: engine.cpp finish_result)
+    return direct || stage;  // (the host derives the count and the capacity flag from kResEmitHead: engine.cpp finish_result)
 }
 static_assert(kEBlocks + 384u <= kMaxHoles && 1536u + 384u <= kMaxHoles, "hole list: one entry per block of either kernel");

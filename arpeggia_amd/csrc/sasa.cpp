@@ -1,5 +1,5 @@
 // Structure-level atom SASA, SAP score and dSASA (reference src/sasa.rs:27-451, src/sap.rs:137-259): the atom selection of
-// prepare_pdb_for_sasa + filter_pdb_by_model on the parsed structure, then one device run (engine.cpp sasa_run, kernels in sasa.inl).
+// prepare_pdb_for_sasa + filter_pdb_by_model on the parsed structure, then one device run (sasa_dev.cpp sasa_run, kernels in sasa.inl).
 // Residue- and chain-level SASA (get_residue_sasa / get_chain_sasa, relative_sasa) are NOT here: the reference computes them through
 // rust-sasa's SASAOptions, whose own radius table (with a van-der-Waals fallback) is not part of the reference's tree -- those levels would
 // be a guess.  dSASA, chain-level in the reference, is built from atom-level SASA instead (arpeggia_amd.h arp_structure_dsasa).
@@ -234,7 +234,7 @@ extern "C" arp_status arp_structure_dsasa(arp_context *ctx, const arp_structure 
     return ARP_OK;
 } ARP_ABI_CATCH
 
-// ---- SASA / SAP statistics over the frames of an ensemble (device path: engine.cpp ens_run, ens.inl) ----------------
+// ---- SASA / SAP statistics over the frames of an ensemble (device path: sasa_dev.cpp ens_run, ens.inl) ----------------
 extern "C" arp_status arp_sasa_ensemble_stats(uint64_t n_frames, uint64_t m, const float *R, int32_t n_points, const uint64_t *s1, const uint64_t *s2,
                                               const int32_t *cmin, const int32_t *cmax, const double *t1, const double *t2, float *mean_sasa,
                                               float *std_sasa, float *min_sasa, float *max_sasa, float *mean_sap, float *std_sap) try {

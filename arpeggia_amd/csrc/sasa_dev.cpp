@@ -1,0 +1,323 @@
+// Atom SASA and the SAP chain on the device (sasa.inl, sap.inl, ens.inl run them; reference src/sasa.rs:174-247, src/sap.rs:137-250): the
+// launch chain SASA -> SAP weight -> neighbour sum, and its three callers -- arp_sap_neighbor_sum, sasa_run (arp_atom_sasa and the
+// structure-level entry points of sasa.cpp) and ens_run (arp_sasa_ensemble).
+#include <cctype>
+#include <cmath>
+#include <cstring>
+#include <algorithm>
+
+#include "engine.h"
+#include "table_dev.h"
+
+using namespace arp;
+
+// ---- SAP residue table (reference src/sap.rs:41-101) --------------------------------------------------------------------------
+namespace arp {
+struct SapResidue { const char *n; float h, a; };
+#define ARP_SAP_ROW(n, h, a) {n, h, a},
+static const SapResidue kSapResidues[20] = {ARP_SAP_RESIDUES(ARP_SAP_ROW)};
+#undef ARP_SAP_ROW
+uint32_t sap_residue_code(const char *resn) {
+    if (!resn) return 20u;
+    char up[8] = {0};
+    for (int k = 0; k < 7 && resn[k]; k++) up[k] = (char)toupper((unsigned char)resn[k]);
+    for (uint32_t r = 0; r < 20u; r++)
+        if (strcmp(kSapResidues[r].n, up) == 0) return r;
+    return 20u;
+}
+}  // namespace arp
+
+extern "C" float arp_sap_weight(const char *resn, float sasa) {
+    // hydrophobicity (Black & Mould minus glycine, sap.rs:41-64) x clamp(sasa / max side-chain SASA (sap.rs:77-101), 0, 1); 0 for residues
+    // without a hydrophobicity value (sap.rs:198-209).  The table is ARP_SAP_RESIDUES (arp_internal.h), shared with the device weight kernel.
+    const uint32_t r = sap_residue_code(resn);
+    if (r >= 20u) return 0.0f;
+    const SapResidue &t = kSapResidues[r];
+    return t.h * std::min(1.0f, std::max(0.0f, sasa / t.a));
+}
+
+// ---- the launch chain ------------------------------------------------------------------------------------------------------------
+namespace {
+// search radius of the SASA grid: a burier j of a point of i is closer than R_i |s_k| + R_j <= 2 R_max (1 + 2^-23); 1e-5 covers that and the f32 gather test
+double sasa_cutoff(float r_max) { return 2.0 * (double)r_max * (1.0 + 1e-5) + 1e-6; }
+// attribute word of the SAP grid (the contact search's, over the side-chain atoms only): the rest is kept out by the bit that keeps hydrogens out of the contact grid
+uint32_t sap_attr(uint8_t sidechain) { return sidechain ? (ARP_ATTR_LIGAND | ARP_ATTR_RECEPTOR) : ARP_ATTR_H; }
+
+// Each stage uploads the parameters of its search radius and builds its grid in the context's workspace, whose cell list is then no pair pass's any more.
+arp_status sasa_stage(arp_context *ctx, const DevAtoms &d, float r_max, const float *R, const float *sphere, uint32_t n_points, float *sasa, int32_t *count) {
+    arp_params prm;
+    arp_default_params(&prm);
+    prm.dist_cutoff = sasa_cutoff(r_max);
+    const arp_status s = upload_params(ctx, &prm);
+    if (s != ARP_OK) return s;
+    mark_grid_foreign(ctx);
+    launch_sasa(d, ctx->ws, prm.dist_cutoff, R, sphere, n_points, r_max, sasa, count, ctx->stream, context_profiler(ctx));
+    HIP_TRY(hipGetLastError());
+    return ARP_OK;
+}
+// out[i] = the f32 sum of w[j] over the grid atoms j within sap_radius of grid atom i; code != nullptr: w is first derived from the SASA values
+arp_status sap_stage(arp_context *ctx, const DevAtoms &e, float sap_radius, const uint32_t *code, const int32_t *src, const float *sasa, float *w, float *out) {
+    arp_params prm;
+    arp_default_params(&prm);
+    prm.dist_cutoff = (double)sap_radius;
+    const arp_status s = upload_params(ctx, &prm);
+    if (s != ARP_OK) return s;
+    mark_grid_foreign(ctx);
+    if (code) launch_sap_weight(e.n, code, src, sasa, w, ctx->stream);
+    const double r2 = (double)(sap_radius * sap_radius);  // sap.rs:183-184: the product is formed in f32
+    launch_neighbor_sum(e, ctx->ws, (double)sap_radius, r2, w, out, ctx->stream, context_profiler(ctx));
+    HIP_TRY(hipGetLastError());
+    return ARP_OK;
+}
+}  // namespace
+
+// ---- SAP neighbour sum (reference src/sap.rs:155-204) ---------------------------------------------------
+extern "C" arp_status arp_sap_neighbor_sum(arp_context *ctx, uint64_t n, const double *x, const double *y, const double *z, const uint8_t *sidechain,
+                                           const float *weight, float sap_radius, float *out) try {
+    arp_status s = check_device(ctx);
+    if (s != ARP_OK) return s;
+    if (n && (!x || !y || !z || !sidechain || !weight || !out)) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    if (n >= 0x5000000ull) { set_error("too many atoms for one SAP neighbour sum (the kernel addresses the sorted records with 32-bit byte offsets: < 83886080 atoms)"); return ARP_ERR_BAD_INPUT; }
+    if (!(sap_radius >= 0.0f)) { set_error("bad sap_radius"); return ARP_ERR_BAD_INPUT; }
+    if (n == 0) return ARP_OK;
+    std::vector<uint32_t> attr(n), zero32(n, 0);
+    for (uint64_t i = 0; i < n; i++) attr[i] = sap_attr(sidechain[i]);
+    arp_atoms a{};
+    a.n = n; a.x = x; a.y = y; a.z = z; a.attr = attr.data(); a.res_ord = zero32.data(); a.chain_rank = zero32.data(); a.model = zero32.data();
+    a.n_res = 0; a.location = ARP_MEM_HOST;
+    if ((s = ensure_workspace(ctx, n)) != ARP_OK) return s;
+    DevAtoms d{};
+    if ((s = stage_inputs(ctx, &a, &d)) != ARP_OK) return s;
+    const uint64_t seg = seg_align(n * 4);  // {weights, sums} on the device; {weights, sums} pinned
+    char *dev = nullptr, *pin = nullptr;
+    if ((s = context_scratch(ctx, 0, 2 * seg, 2 * seg, &dev, &pin)) != ARP_OK) return s;
+    float *d_w = (float *)dev, *d_out = (float *)(dev + seg), *h_out = (float *)(pin + seg);
+    memcpy(pin, weight, n * 4);
+    HIP_TRY(hipMemcpyAsync(d_w, pin, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(d_out, 0, n * 4, ctx->stream));  // atoms outside the side-chain set keep 0
+    if ((s = sap_stage(ctx, d, sap_radius, nullptr, nullptr, nullptr, d_w, d_out)) != ARP_OK) return s;
+    HIP_TRY(hipMemcpyAsync(h_out, d_out, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    // non-finite coordinates are reported by the grid build through the pair pass's status word only; check here
+    for (uint64_t i = 0; i < n; i++)
+        if (sidechain[i] && !(std::isfinite(x[i]) && std::isfinite(y[i]) && std::isfinite(z[i]))) { set_error("non-finite atom coordinate"); return ARP_ERR_BAD_INPUT; }
+    memcpy(out, h_out, n * 4);
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+// ---- atom SASA (sasa.inl; reference src/sasa.rs:174-247) and the SAP chain (src/sap.rs:137-250) --------------------------------------
+namespace arp {
+void sasa_sphere_points(uint32_t n, float *xyz) {
+    // golden spiral: t = k / n, theta = acos(1 - 2 t), phi = (2 pi golden) k; (sin theta cos phi, sin theta sin phi, cos theta) in f64, rounded to f32
+    const double golden = (1.0 + std::sqrt(5.0)) / 2.0, step = 2.0 * 3.141592653589793 * golden;
+    for (uint32_t k = 0; k < n; k++) {
+        const double t = (double)k / (double)n, theta = std::acos(1.0 - 2.0 * t), phi = step * (double)k;
+        xyz[3 * k] = (float)(std::sin(theta) * std::cos(phi));
+        xyz[3 * k + 1] = (float)(std::sin(theta) * std::sin(phi));
+        xyz[3 * k + 2] = (float)std::cos(theta);
+    }
+}
+
+arp_status sasa_run(arp_context *ctx, const SasaJob &j, float *sasa, int32_t *count, float *sap) {
+    arp_status s = check_device(ctx);
+    if (s != ARP_OK) return s;
+    if (ctx->pending) { set_error("a call enqueued on this context has not been collected (arp_contacts_atomic_result)"); return ARP_ERR_BAD_INPUT; }
+    const uint64_t n = j.n;
+    if (n >= 0x5000000ull) { set_error("too many atoms for one SASA call (< 83886080)"); return ARP_ERR_BAD_INPUT; }
+    if (n == 0) return ARP_OK;
+    const bool with_sap = j.sidechain != nullptr;
+    float r_max = 0.0f;
+    for (uint64_t i = 0; i < n; i++) {
+        const bool use = j.include[i] != 0, side = with_sap && j.sidechain[i];
+        if ((use || side) && !(std::isfinite(j.x[i]) && std::isfinite(j.y[i]) && std::isfinite(j.z[i]))) { set_error("non-finite atom coordinate"); return ARP_ERR_BAD_INPUT; }
+        if (use) r_max = std::max(r_max, j.R[i]);
+    }
+    // one pinned block out, one back: inputs {f32-rounded x y z (f64), SASA attr, zeros, model, R, sphere, [x y z, SAP attr, code, src]}, outputs {sasa, count, [sap]}
+    Carver lay;
+    const uint64_t o_x = lay.take(8 * n), o_y = lay.take(8 * n), o_z = lay.take(8 * n), o_attr = lay.take(4 * n), o_zero = lay.take(4 * n), o_model = lay.take(4 * n), o_R = lay.take(4 * n),
+                   o_sph = lay.take(12ull * j.n_points);
+    uint64_t o_px = 0, o_py = 0, o_pz = 0, o_pattr = 0, o_code = 0, o_src = 0;
+    if (with_sap) { o_px = lay.take(8 * n); o_py = lay.take(8 * n); o_pz = lay.take(8 * n); o_pattr = lay.take(4 * n); o_code = lay.take(4 * n); o_src = lay.take(4 * n); }
+    const uint64_t in_bytes = lay.off;
+    const uint64_t o_sasa = lay.take(4 * n), o_count = lay.take(4 * n), o_w = with_sap ? lay.take(4 * n) : 0, o_sap = with_sap ? lay.take(4 * n) : 0;
+    const uint64_t out_bytes = lay.off - in_bytes;
+    char *dev = nullptr, *pin = nullptr;
+    if ((s = context_scratch(ctx, 0, lay.off, lay.off, &dev, &pin)) != ARP_OK) return s;
+    double *hx = (double *)(pin + o_x), *hy = (double *)(pin + o_y), *hz = (double *)(pin + o_z);
+    uint32_t *hattr = (uint32_t *)(pin + o_attr), *hmodel = (uint32_t *)(pin + o_model);
+    float *hR = (float *)(pin + o_R);
+    for (uint64_t i = 0; i < n; i++) {
+        const bool use = j.include[i] != 0;
+        hx[i] = (double)(float)j.x[i]; hy[i] = (double)(float)j.y[i]; hz[i] = (double)(float)j.z[i];  // sasa.rs:196-198
+        hattr[i] = use ? 0u : ARP_ATTR_H;  // (the attribute bit that keeps an atom out of the grid)
+        hmodel[i] = j.model ? j.model[i] : 0u;
+        hR[i] = use ? j.R[i] : 0.0f;
+    }
+    memset(pin + o_zero, 0, 4 * n);
+    memcpy(pin + o_sph, j.sphere, 12ull * j.n_points);
+    if (with_sap) {
+        memcpy(pin + o_px, j.x, 8 * n); memcpy(pin + o_py, j.y, 8 * n); memcpy(pin + o_pz, j.z, 8 * n);
+        uint32_t *pa = (uint32_t *)(pin + o_pattr);
+        for (uint64_t i = 0; i < n; i++) pa[i] = sap_attr(j.sidechain[i]);
+        memcpy(pin + o_code, j.res_code, 4 * n); memcpy(pin + o_src, j.src, 4 * n);
+    }
+    if ((s = ensure_workspace(ctx, n)) != ARP_OK) return s;
+    HIP_TRY(hipMemcpyAsync(dev, pin, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(dev + in_bytes, 0, out_bytes, ctx->stream));  // atoms outside the grid keep sasa 0, count 0
+    DevAtoms d{};
+    d.n = (uint32_t)n;
+    d.x = (const double *)(dev + o_x); d.y = (const double *)(dev + o_y); d.z = (const double *)(dev + o_z);
+    d.attr = (const uint32_t *)(dev + o_attr); d.res_ord = d.chain_rank = (const uint32_t *)(dev + o_zero); d.model = (const uint32_t *)(dev + o_model);
+    float *d_sasa = (float *)(dev + o_sasa);
+    if ((s = sasa_stage(ctx, d, r_max, (const float *)(dev + o_R), (const float *)(dev + o_sph), j.n_points, d_sasa, (int32_t *)(dev + o_count))) != ARP_OK) return s;
+    HIP_TRY(hipMemcpyAsync(ctx->h_result + kHostSasaTestsSlot, ctx->ws.result + kSasaTestsWord, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    if (with_sap) {
+        DevAtoms e = d;
+        e.x = (const double *)(dev + o_px); e.y = (const double *)(dev + o_py); e.z = (const double *)(dev + o_pz);
+        e.attr = (const uint32_t *)(dev + o_pattr); e.model = (const uint32_t *)(dev + o_zero);
+        if ((s = sap_stage(ctx, e, j.sap_radius, (const uint32_t *)(dev + o_code), (const int32_t *)(dev + o_src), d_sasa, (float *)(dev + o_w), (float *)(dev + o_sap))) != ARP_OK) return s;
+    }
+    HIP_TRY(hipMemcpyAsync(pin + in_bytes, dev + in_bytes, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->sasa_tests = ctx->h_result[kHostSasaTestsSlot];
+    if (sasa) memcpy(sasa, pin + o_sasa, 4 * n);
+    if (count) memcpy(count, pin + o_count, 4 * n);
+    if (sap && with_sap) memcpy(sap, pin + o_sap, 4 * n);
+    return ARP_OK;
+}
+
+// SASA / SAP statistics over the frames of an ensemble (arp_sasa_ensemble).  Frames go through the device in passes of
+// whole frames; a pass is one packed input of frames x m atoms, model = frame, every model with its own origin (DevAtoms::per_model), on which
+// the SASA and SAP kernels of sasa_run run as they are.  Per pass only the coordinates are uploaded (pinned staging, refilled while the device
+// works on the previous pass); the per-atom accumulators stay on the device until the last pass.
+constexpr uint64_t kEnsAutoAtoms = 1u << 21;  // packed atoms per pass when the knob ens_chunk_atoms is 0 (1ubq x 3400 frames, 6bft x 230)
+arp_status ens_run(arp_context *ctx, const EnsJob &j, const EnsOut &o) {
+    arp_status s = check_device(ctx);
+    if (s != ARP_OK) return s;
+    if (ctx->pending) { set_error("a call enqueued on this context has not been collected (arp_contacts_atomic_result)"); return ARP_ERR_BAD_INPUT; }
+    const uint64_t m = j.m, N = j.n_top, F = j.n_frames;
+    if (m == 0 || F == 0) return ARP_OK;
+    // frames per pass: the atom budget; a model ordinal per frame (grid.inl kPackModels); one pass below the SASA / SAP kernels' atom limit
+    constexpr uint64_t kMaxPassAtoms = 0x5000000ull - 1u;
+    if (m > kMaxPassAtoms) { set_error("sasa ensemble: too many selected atoms for one frame (< 83886080)"); return ARP_ERR_BAD_INPUT; }
+    const uint64_t budget = j.chunk_atoms ? j.chunk_atoms : kEnsAutoAtoms;
+    const uint64_t per = std::min<uint64_t>({std::max<uint64_t>(1, budget / m), F, 65535u, kMaxPassAtoms / m});
+    const uint64_t pn = per * m;
+    float r_max = 0.0f;
+    for (uint64_t k = 0; k < m; k++) r_max = std::max(r_max, j.R[k]);
+    // device block: {topology | accumulators + totals | one pass}; the pinned block repeats the first two at the same offsets (one copy each
+    // way) and adds the coordinate staging and, when asked for, the per-frame outputs of a pass
+    Carver lay;
+    const uint64_t o_sel = lay.take(4 * m), o_R = lay.take(4 * m), o_code = lay.take(4 * m), o_pattr = lay.take(4 * m), o_sph = lay.take(12ull * j.n_points);
+    const uint64_t topo_bytes = lay.off;
+    const uint64_t o_s1 = lay.take(8 * m), o_s2 = lay.take(8 * m), o_t1 = lay.take(8 * m), o_t2 = lay.take(8 * m), o_cmin = lay.take(4 * m), o_cmax = lay.take(4 * m), o_pmin = lay.take(4 * m),
+                   o_pmax = lay.take(4 * m), o_total = lay.take(4 * F);
+    const uint64_t acc_bytes = lay.off - topo_bytes, shared_bytes = lay.off;
+    const uint64_t o_xyz = lay.take(24 * per * N), o_x = lay.take(8 * pn), o_y = lay.take(8 * pn), o_z = lay.take(8 * pn), o_zero = lay.take(4 * pn), o_model = lay.take(4 * pn), o_Rp = lay.take(4 * pn),
+                   o_sasa = lay.take(4 * pn), o_count = lay.take(4 * pn);
+    uint64_t o_px = 0, o_py = 0, o_pz = 0, o_pa = 0, o_pc = 0, o_src = 0, o_w = 0, o_sap = 0;
+    if (j.with_sap) { o_px = lay.take(8 * pn); o_py = lay.take(8 * pn); o_pz = lay.take(8 * pn); o_pa = lay.take(4 * pn); o_pc = lay.take(4 * pn); o_src = lay.take(4 * pn); o_w = lay.take(4 * pn); o_sap = lay.take(4 * pn); }
+    const uint64_t dev_bytes = lay.off;
+    lay.off = shared_bytes;
+    const uint64_t h_xyz = lay.take(24 * per * N), h_count = o.count ? lay.take(4 * pn) : 0, h_sap = o.sap ? lay.take(4 * pn) : 0;
+    const uint64_t pin_bytes = lay.off;
+    if ((s = ensure_workspace(ctx, pn)) != ARP_OK) return s;
+    char *dev = nullptr, *pin = nullptr;
+    if ((s = context_scratch(ctx, 0, dev_bytes, pin_bytes, &dev, &pin)) != ARP_OK) return s;
+    memcpy(pin + o_sel, j.sel, 4 * m); memcpy(pin + o_R, j.R, 4 * m); memcpy(pin + o_sph, j.sphere, 12ull * j.n_points);
+    if (j.with_sap) {
+        memcpy(pin + o_code, j.res_code, 4 * m);
+        uint32_t *pa = (uint32_t *)(pin + o_pattr);
+        for (uint64_t k = 0; k < m; k++) pa[k] = sap_attr(j.sidechain[k]);
+    }
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(dev, pin, topo_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(dev + o_zero, 0, 4 * pn, st));  // attribute word of the SASA grid (every packed atom is in it), residue ordinal, chain rank
+    if (j.with_sap) HIP_TRY(hipMemsetAsync(dev + o_sap, 0, 4 * pn, st));  // backbone atoms are outside the SAP grid in every frame: they keep 0
+    struct Event { hipEvent_t e = nullptr; ~Event() { if (e) (void)hipEventDestroy(e); } } staged;  // behind the upload of the staging buffer: the host refills it only after that copy has run
+    HIP_TRY(hipEventCreateWithFlags(&staged.e, hipEventDisableTiming));
+    EnsTopo tp{(uint32_t)N, (uint32_t)m, (const uint32_t *)(dev + o_sel), (const float *)(dev + o_R), (const uint32_t *)(dev + o_code), (const uint32_t *)(dev + o_pattr)};
+    EnsPack pk{};
+    pk.x = (double *)(dev + o_x); pk.y = (double *)(dev + o_y); pk.z = (double *)(dev + o_z);
+    pk.model = (uint32_t *)(dev + o_model); pk.R = (float *)(dev + o_Rp);
+    if (j.with_sap) {
+        pk.px = (double *)(dev + o_px); pk.py = (double *)(dev + o_py); pk.pz = (double *)(dev + o_pz);
+        pk.pattr = (uint32_t *)(dev + o_pa); pk.code = (uint32_t *)(dev + o_pc); pk.src = (int32_t *)(dev + o_src);
+    }
+    EnsAcc acc{(unsigned long long *)(dev + o_s1), (unsigned long long *)(dev + o_s2), (int32_t *)(dev + o_cmin), (int32_t *)(dev + o_cmax),
+               (double *)(dev + o_t1), (double *)(dev + o_t2), (float *)(dev + o_pmin), (float *)(dev + o_pmax)};
+    float *d_sasa = (float *)(dev + o_sasa), *d_sap = j.with_sap ? (float *)(dev + o_sap) : nullptr;
+    int32_t *d_count = (int32_t *)(dev + o_count);
+    for (uint64_t f0 = 0; f0 < F; f0 += per) {
+        const uint64_t fc = std::min<uint64_t>(per, F - f0), cn = fc * m;
+        if (f0) HIP_TRY(hipEventSynchronize(staged.e));
+        memcpy(pin + h_xyz, j.xyz + f0 * N * 3, 24 * fc * N);
+        HIP_TRY(hipMemcpyAsync(dev + o_xyz, pin + h_xyz, 24 * fc * N, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(staged.e, st));
+        launch_ens_tile((uint32_t)fc, (const double *)(dev + o_xyz), tp, pk, st);
+        DevAtoms d{};
+        d.n = (uint32_t)cn; d.per_model = 1u;
+        d.x = pk.x; d.y = pk.y; d.z = pk.z;
+        d.attr = d.res_ord = d.chain_rank = (const uint32_t *)(dev + o_zero); d.model = pk.model;
+        if ((s = sasa_stage(ctx, d, r_max, pk.R, (const float *)(dev + o_sph), j.n_points, d_sasa, d_count)) != ARP_OK) return s;
+        if (j.with_sap) {
+            DevAtoms e = d;
+            e.x = pk.px; e.y = pk.py; e.z = pk.pz; e.attr = pk.pattr;
+            if ((s = sap_stage(ctx, e, j.sap_radius, pk.code, pk.src, d_sasa, (float *)(dev + o_w), d_sap)) != ARP_OK) return s;
+        }
+        launch_ens_reduce((uint32_t)fc, (uint32_t)m, d_count, d_sasa, d_sap, acc, f0 == 0, (float *)(dev + o_total) + f0, st);
+        HIP_TRY(hipGetLastError());
+        if (o.count || o.sap) {  // the pass's own values, only when the caller wants them
+            if (o.count) HIP_TRY(hipMemcpyAsync(pin + h_count, d_count, 4 * cn, hipMemcpyDeviceToHost, st));
+            if (o.sap) HIP_TRY(hipMemcpyAsync(pin + h_sap, d_sap, 4 * cn, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (o.count) memcpy(o.count + f0 * m, pin + h_count, 4 * cn);
+            if (o.sap) memcpy(o.sap + f0 * m, pin + h_sap, 4 * cn);
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(pin + topo_bytes, dev + topo_bytes, acc_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memcpy(o.s1, pin + o_s1, 8 * m); memcpy(o.s2, pin + o_s2, 8 * m); memcpy(o.cmin, pin + o_cmin, 4 * m); memcpy(o.cmax, pin + o_cmax, 4 * m);
+    memcpy(o.total, pin + o_total, 4 * F);
+    if (j.with_sap) { memcpy(o.t1, pin + o_t1, 8 * m); memcpy(o.t2, pin + o_t2, 8 * m); memcpy(o.pmin, pin + o_pmin, 4 * m); memcpy(o.pmax, pin + o_pmax, 4 * m); }
+    return ARP_OK;
+}
+}  // namespace arp
+
+extern "C" arp_status arp_sasa_sphere_points(uint32_t n, float *xyz) try {
+    if (n < 1 || n > ARP_SASA_MAX_POINTS || !xyz) { set_error("arp_sasa_sphere_points: n must be 1..%d and xyz non-null", ARP_SASA_MAX_POINTS); return ARP_ERR_BAD_INPUT; }
+    sasa_sphere_points(n, xyz);
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+namespace arp {
+arp_status sasa_check_params(float probe, int32_t n_points) {
+    if (n_points < 1 || n_points > ARP_SASA_MAX_POINTS) { set_error("n_points must be 1..%d (got %d)", ARP_SASA_MAX_POINTS, (int)n_points); return ARP_ERR_BAD_INPUT; }
+    if (!(std::isfinite(probe) && probe >= 0.0f)) { set_error("probe radius must be finite and >= 0"); return ARP_ERR_BAD_INPUT; }
+    return ARP_OK;
+}
+}  // namespace arp
+
+extern "C" arp_status arp_atom_sasa(arp_context *ctx, uint64_t n, const double *x, const double *y, const double *z, const float *radius,
+                                    const uint8_t *include, float probe, int32_t n_points, float *out_sasa, int32_t *out_count) try {
+    arp_status s = check_device(ctx);
+    if (s != ARP_OK) return s;
+    if ((s = sasa_check_params(probe, n_points)) != ARP_OK) return s;
+    if (n && (!x || !y || !z || !radius || !out_sasa)) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    std::vector<uint8_t> all;
+    if (!include) { all.assign(n, 1); include = all.data(); }
+    std::vector<float> R(n, 0.0f);
+    for (uint64_t i = 0; i < n; i++) {
+        if (!include[i]) continue;
+        if (!(std::isfinite(radius[i]) && radius[i] >= 0.0f)) { set_error("atom %llu: radius must be finite and >= 0", (unsigned long long)i); return ARP_ERR_BAD_INPUT; }
+        R[i] = radius[i] + probe;  // sasa.rs:200-206 + rust-sasa: r + probe in f32
+    }
+    std::vector<float> sphere(3ull * (uint32_t)n_points);
+    sasa_sphere_points((uint32_t)n_points, sphere.data());
+    SasaJob j;
+    j.n = n; j.x = x; j.y = y; j.z = z; j.R = R.data(); j.include = include; j.n_points = (uint32_t)n_points; j.sphere = sphere.data();
+    std::vector<int32_t> cnt(out_count ? 0 : n);
+    return sasa_run(ctx, j, out_sasa, out_count ? out_count : cnt.data(), nullptr);
+} ARP_ABI_CATCH
+
+extern "C" uint64_t arp_sasa_tests(const arp_context *ctx) { return ctx ? ctx->sasa_tests : 0u; }

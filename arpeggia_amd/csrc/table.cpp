@@ -493,21 +493,12 @@ void materialize_columns(arp_table *t) {
     });
 }
 
-#define TBL_HIP(expr)                                                                                                       \
-    do {                                                                                                                    \
-        hipError_t e_ = (expr);                                                                                             \
-        if (e_ != hipSuccess) {                                                                                             \
-            set_error("HIP error %d (%s) at %s:%d: %s", (int)e_, hipGetErrorString(e_), __FILE__, __LINE__, #expr);         \
-            return (e_ == hipErrorOutOfMemory) ? ARP_ERR_OOM : ARP_ERR_HIP;                                                 \
-        }                                                                                                                   \
-    } while (0)
-
 // the structure's arrays on the context's device: uploaded once; only the attribute words depend on the chain groups
 arp_status ensure_resident(arp_context *ctx, arp_structure *s, TableCache *c, const char *groups) {
     DevStructure &d = c->dev;
     const int device = context_device(ctx);
     hipStream_t st = (hipStream_t)context_stream(ctx);
-    TBL_HIP(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     const uint64_t n = s->n, nr = s->residues.size(), nh = s->res_h_idx.size(), nm = c->model_rank.size();
     if (!d.block || d.device != device) {
         if (d.block) { (void)hipSetDevice(d.device); (void)hipFree(d.block); if (d.derived) (void)hipFree(d.derived); if (d.rings_block) (void)hipFree(d.rings_block); (void)hipSetDevice(device); d.block = nullptr; d.derived = nullptr; d.rings_block = nullptr; d.rings_cap = 0; d.rings_host.clear(); }
@@ -521,9 +512,10 @@ arp_status ensure_resident(arp_context *ctx, arp_structure *s, TableCache *c, co
                      {c->res_atom_idx.data(), c->res_atom_idx.size() * 4, (void **)&d.res_atom_idx}, {c->atom_sc_src.data(), n * 4, (void **)&d.atom_sc_src},
                      {c->atom_keys.data(), n * sizeof(EntKey), (void **)&d.ent_key}, {c->model_rank.data(), nm * 4, (void **)&d.model_rank},
                      {c->model_serial_of.data(), nm * 4, (void **)&d.model_serial_of}};
-        uint64_t total = 0;
-        for (const Seg &g : seg) total += (g.bytes + 255u) & ~255ull;
-        total = std::max<uint64_t>(total, 256);
+        Carver lay;
+        std::vector<uint64_t> offs;
+        for (const Seg &g : seg) offs.push_back(lay.take(g.bytes));
+        const uint64_t total = std::max<uint64_t>(lay.off, 256);
         const bool timing = g_debug.timing != 0;
         auto t_prev = std::chrono::steady_clock::now();
         auto lap = [&](const char *what) {
@@ -532,7 +524,7 @@ arp_status ensure_resident(arp_context *ctx, arp_structure *s, TableCache *c, co
             fprintf(stderr, "    resident %-25s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
             t_prev = now;
         };
-        TBL_HIP(hipMalloc((void **)&d.block, total));
+        HIP_TRY(hipMalloc((void **)&d.block, total));
         lap("device block");
         d.device = device;
         // one pinned staging block, filled by the host workers, one copy across PCIe (pageable arrays cross at ~3 GB/s)
@@ -540,10 +532,8 @@ arp_status ensure_resident(arp_context *ctx, arp_structure *s, TableCache *c, co
         arp_status stt = context_scratch(ctx, 1, 0, total, &dev_scr, &pin);
         if (stt != ARP_OK) return stt;
         lap("pinned staging block");
-        uint64_t off = 0;
-        std::vector<uint64_t> offs;
-        for (const Seg &g : seg) { offs.push_back(off); *g.dst = d.block + off; off += (g.bytes + 255u) & ~255ull; }
         const size_t n_seg = sizeof seg / sizeof seg[0];
+        for (size_t k = 0; k < n_seg; k++) *seg[k].dst = d.block + offs[k];
         parallel_for(n_seg * 8, 1, [&](size_t k0, size_t k1, size_t) {  // every segment in 8 slices
             for (size_t k = k0; k < k1; k++) {
                 const Seg &g = seg[k / 8];
@@ -552,8 +542,8 @@ arp_status ensure_resident(arp_context *ctx, arp_structure *s, TableCache *c, co
             }
         });
         lap("gather into it");
-        TBL_HIP(hipMemcpyAsync(d.block, pin, total, hipMemcpyHostToDevice, st));
-        TBL_HIP(hipStreamSynchronize(st));  // (the pinned block is scratch: reused by the table pass below)
+        HIP_TRY(hipMemcpyAsync(d.block, pin, total, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));  // (the pinned block is scratch: reused by the table pass below)
         lap("H2D");
         d.n = n; d.n_res = nr; d.n_h = nh;
         d.n_chains = (uint32_t)s->chain_ids.size(); d.n_models = (uint32_t)nm;
@@ -562,8 +552,8 @@ arp_status ensure_resident(arp_context *ctx, arp_structure *s, TableCache *c, co
         d.attr_groups = groups;
         lap("insertion-code scan");
     } else if (d.attr_groups != groups) {
-        TBL_HIP(hipMemcpyAsync(d.attr, s->attr.data(), n * 4, hipMemcpyHostToDevice, st));
-        TBL_HIP(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(d.attr, s->attr.data(), n * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
         d.attr_groups = groups;
     }
     return ARP_OK;

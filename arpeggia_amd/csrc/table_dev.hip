@@ -18,15 +18,6 @@
 
 namespace arp {
 
-#define TRY_HIP(expr)                                                                                                     \
-    do {                                                                                                                  \
-        hipError_t e_ = (expr);                                                                                           \
-        if (e_ != hipSuccess) {                                                                                           \
-            set_error("HIP error %d (%s) at %s:%d: %s", (int)e_, hipGetErrorString(e_), __FILE__, __LINE__, #expr);       \
-            return (e_ == hipErrorOutOfMemory) ? ARP_ERR_OOM : ARP_ERR_HIP;                                               \
-        }                                                                                                                 \
-    } while (0)
-
 struct PlaneD { double c[3], n[3]; };
 
 // ---- plane fits (residues.rs:270-298): centroid + direction of least variance --------------------------------------
@@ -613,35 +604,30 @@ __global__ __launch_bounds__(kSmallThreads) void k_table_small(const arp_pair *p
 
 // ---- host orchestration ----------------------------------------------------------------------------------------------
 namespace {
-struct Bump {  // carve a scratch block (256-byte aligned pieces)
-    char *base; uint64_t off = 0, cap;
-    template <class T> T *take(uint64_t count) {
-        T *p = reinterpret_cast<T *>(base + off);
-        off += (count * sizeof(T) + 255u) & ~255ull;
-        return p;
-    }
+struct Bump {  // typed pieces of one block
+    char *base; Carver c{};
+    template <class T> T *take(uint64_t count) { return reinterpret_cast<T *>(base + c.take(count * sizeof(T))); }
 };
-uint64_t al(uint64_t bytes) { return (bytes + 255u) & ~255ull; }
 }  // namespace
 
 arp_status device_planes(arp_context *ctx, const DevStructure &ds, std::vector<double> *planes, std::vector<uint8_t> *valid) {
     hipStream_t st = (hipStream_t)context_stream(ctx);
     const uint64_t nr = ds.n_res;
     char *dev = nullptr, *pin = nullptr;
-    arp_status s = context_scratch(ctx, 0, 2 * al(nr * sizeof(PlaneD)) + al(nr) + 4096, 0, &dev, &pin);
+    arp_status s = context_scratch(ctx, 0, 2 * seg_align(nr * sizeof(PlaneD)) + seg_align(nr) + 4096, 0, &dev, &pin);
     if (s != ARP_OK) return s;
-    Bump b{dev, 0, 0};
+    Bump b{dev};
     PlaneD *ring = b.take<PlaneD>(nr), *sc = b.take<PlaneD>(nr);
     uint8_t *v = b.take<uint8_t>(nr);
     if (nr) hipLaunchKernelGGL(k_fit_planes, dim3((uint32_t)((nr + 127) / 128)), dim3(128), 0, st, (uint32_t)nr, (const uint32_t *)ds.res_atom_ptr, (const uint32_t *)ds.res_atom_idx,
                                (const uint8_t *)ds.plane_bits, (const double *)ds.x, (const double *)ds.y, (const double *)ds.z, ring, sc, v);
-    TRY_HIP(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     std::vector<PlaneD> hr(nr), hs(nr);
     valid->assign(nr, 0);
-    TRY_HIP(hipMemcpyAsync(hr.data(), ring, nr * sizeof(PlaneD), hipMemcpyDeviceToHost, st));
-    TRY_HIP(hipMemcpyAsync(hs.data(), sc, nr * sizeof(PlaneD), hipMemcpyDeviceToHost, st));
-    TRY_HIP(hipMemcpyAsync(valid->data(), v, nr, hipMemcpyDeviceToHost, st));
-    TRY_HIP(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(hr.data(), ring, nr * sizeof(PlaneD), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(hs.data(), sc, nr * sizeof(PlaneD), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(valid->data(), v, nr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     planes->assign(12 * nr, 0.0);
     for (uint64_t r = 0; r < nr; r++) {
         if ((*valid)[r] & 1u) memcpy(&(*planes)[12 * r], &hr[r], sizeof(PlaneD));
@@ -671,20 +657,20 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
     (void)hipcub::DeviceRadixSort::SortPairs(nullptr, cub_sort_ent, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (const uint32_t *)nullptr,
                                              (uint32_t *)nullptr, (int)n_ent, 0, 64);
     const uint64_t ring_rows_cap = 64 * n_rings + 1024;  // each ring meets a handful of cations / rings; checked below
-    uint64_t need = 2 * al(nr * sizeof(PlaneD)) + al(nr) + al(n_rings * sizeof(RingEnt)) + al(n_rings * sizeof(EntKey)) + al(n_rings * 32) + 4096 + al((n_pairs + 1) * 4) * 2 +
-                    al(std::max(cub_scan, cub_sort_ent)) + al(n_ent * 8) * 2 + al(n_ent * 4) * 4 + al(ring_rows_cap * 16);
+    uint64_t need = 2 * seg_align(nr * sizeof(PlaneD)) + seg_align(nr) + seg_align(n_rings * sizeof(RingEnt)) + seg_align(n_rings * sizeof(EntKey)) + seg_align(n_rings * 32) + 4096 + seg_align((n_pairs + 1) * 4) * 2 +
+                    seg_align(std::max(cub_scan, cub_sort_ent)) + seg_align(n_ent * 8) * 2 + seg_align(n_ent * 4) * 4 + seg_align(ring_rows_cap * 16);
     char *dev = nullptr, *pin = nullptr;
-    const uint64_t pin_bytes = al(n_rings * sizeof(RingEnt)) + al(n_rings * sizeof(EntKey)) + 4096;
+    const uint64_t pin_bytes = seg_align(n_rings * sizeof(RingEnt)) + seg_align(n_rings * sizeof(EntKey)) + 4096;
     arp_status s = context_scratch(ctx, 0, need, pin_bytes, &dev, &pin);
     if (s != ARP_OK) return s;
-    Bump b{dev, 0, need};
+    Bump b{dev};
     // planes and entity ranks depend on the structure alone: computed by the first call, kept with the resident copy
     const bool derive = !ds.derived || ds.derived_n_ent != n_ent;
     if (derive) {
         if (ds.derived) { (void)hipFree(ds.derived); ds.derived = nullptr; }
-        const uint64_t bytes = 2 * al(nr * sizeof(PlaneD)) + al(nr) + al(n_ent * 4) + 1024;
-        TRY_HIP(hipMalloc((void **)&ds.derived, bytes));
-        Bump db{ds.derived, 0, bytes};
+        const uint64_t bytes = 2 * seg_align(nr * sizeof(PlaneD)) + seg_align(nr) + seg_align(n_ent * 4) + 1024;
+        HIP_TRY(hipMalloc((void **)&ds.derived, bytes));
+        Bump db{ds.derived};
         ds.ring_pl = db.take<PlaneD>(nr); ds.sc_pl = db.take<PlaneD>(nr); ds.pl_valid = db.take<uint8_t>(nr); ds.ent_rank = db.take<uint32_t>(n_ent);
         ds.derived_n_ent = n_ent;
     }
@@ -694,19 +680,19 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
     RingEnt *d_rings = nullptr;
     EntKey *d_ring_keys = nullptr;
     if (n_rings) {
-        const uint64_t rb = n_rings * sizeof(RingEnt), kb = n_rings * sizeof(EntKey), tot = al(rb) + kb;
-        bool send = ds.rings_host.size() != tot || memcmp(ds.rings_host.data(), rings.data(), rb) != 0 || memcmp(ds.rings_host.data() + al(rb), ring_keys.data(), kb) != 0;
+        const uint64_t rb = n_rings * sizeof(RingEnt), kb = n_rings * sizeof(EntKey), tot = seg_align(rb) + kb;
+        bool send = ds.rings_host.size() != tot || memcmp(ds.rings_host.data(), rings.data(), rb) != 0 || memcmp(ds.rings_host.data() + seg_align(rb), ring_keys.data(), kb) != 0;
         if (!ds.rings_block || ds.rings_cap < tot) {
             if (ds.rings_block) { (void)hipStreamSynchronize(st); (void)hipFree(ds.rings_block); ds.rings_block = nullptr; }
-            TRY_HIP(hipMalloc((void **)&ds.rings_block, tot + tot / 4));
+            HIP_TRY(hipMalloc((void **)&ds.rings_block, tot + tot / 4));
             ds.rings_cap = tot + tot / 4; send = true;
         }
-        d_rings = reinterpret_cast<RingEnt *>(ds.rings_block); d_ring_keys = reinterpret_cast<EntKey *>(ds.rings_block + al(rb));
+        d_rings = reinterpret_cast<RingEnt *>(ds.rings_block); d_ring_keys = reinterpret_cast<EntKey *>(ds.rings_block + seg_align(rb));
         if (send) {
             ds.rings_host.assign(tot, 0);
-            memcpy(ds.rings_host.data(), rings.data(), rb); memcpy(ds.rings_host.data() + al(rb), ring_keys.data(), kb);
+            memcpy(ds.rings_host.data(), rings.data(), rb); memcpy(ds.rings_host.data() + seg_align(rb), ring_keys.data(), kb);
             memcpy(pin, ds.rings_host.data(), tot);
-            TRY_HIP(hipMemcpyAsync(ds.rings_block, pin, tot, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ds.rings_block, pin, tot, hipMemcpyHostToDevice, st));
         }
     }
     RingPoint *ring_pts = b.take<RingPoint>(n_rings);
@@ -733,12 +719,12 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
         hipLaunchKernelGGL(k_count_bits, grid(n_pairs + 1, 256), dim3(256), 0, st, pairs_dev, (uint32_t)n_pairs, bits, counters);  // (also clears the counters)
         if (n_pairs) {
             size_t tmp = cub_scan;
-            TRY_HIP(hipcub::DeviceScan::ExclusiveSum(cub_tmp, tmp, (const uint32_t *)bits, first, (int)n_pairs + 1, st));
+            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(cub_tmp, tmp, (const uint32_t *)bits, first, (int)n_pairs + 1, st));
         }
         return ARP_OK;
     };
     if (!small_try) { if ((s = launch_bits()) != ARP_OK) return s; }
-    else if (n_rings || derive) TRY_HIP(hipMemsetAsync(counters, 0, 64 * sizeof(uint32_t), st));
+    else if (n_rings || derive) HIP_TRY(hipMemsetAsync(counters, 0, 64 * sizeof(uint32_t), st));
     // entity ranks: sort the entities by (chain, resi, altloc, atomi), least significant key first; rank = number of key changes since the
     // chain's first entity
     if (derive) {
@@ -747,32 +733,32 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
         hipLaunchKernelGGL(k_ent_key, grid(n_ent, 256), dim3(256), 0, st, (uint32_t)n_ent, (const EntKey *)ds.ent_key, (uint32_t)n, (const EntKey *)d_ring_keys, chain,
                            (const RingEnt *)d_rings, 0, (const uint32_t *)nullptr, ek0);
         size_t tmp = cub_sort_ent;
-        TRY_HIP(hipcub::DeviceRadixSort::SortPairs(cub_tmp, tmp, (const unsigned long long *)ek0, ek1, (const uint32_t *)eid0, eid1, (int)n_ent, 0, 32, st));
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub_tmp, tmp, (const unsigned long long *)ek0, ek1, (const uint32_t *)eid0, eid1, (int)n_ent, 0, 32, st));
         hipLaunchKernelGGL(k_ent_key, grid(n_ent, 256), dim3(256), 0, st, (uint32_t)n_ent, (const EntKey *)ds.ent_key, (uint32_t)n, (const EntKey *)d_ring_keys, chain,
                            (const RingEnt *)d_rings, 1, (const uint32_t *)eid1, ek0);
         tmp = cub_sort_ent;
-        TRY_HIP(hipcub::DeviceRadixSort::SortPairs(cub_tmp, tmp, (const unsigned long long *)ek0, ek1, (const uint32_t *)eid1, eid0, (int)n_ent, 0, 64, st));
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub_tmp, tmp, (const unsigned long long *)ek0, ek1, (const uint32_t *)eid1, eid0, (int)n_ent, 0, 64, st));
         hipLaunchKernelGGL(k_ent_key, grid(n_ent, 256), dim3(256), 0, st, (uint32_t)n_ent, (const EntKey *)ds.ent_key, (uint32_t)n, (const EntKey *)d_ring_keys, chain,
                            (const RingEnt *)d_rings, 2, (const uint32_t *)eid0, ek0);
         tmp = cub_sort_ent;
         {   // (the chain pass: as many key bits as the structure's chain count needs -- 32-bit chain ranks since API v2)
             int chain_key_bits = 1;
             while (chain_key_bits < 32 && (1ull << chain_key_bits) < std::max<uint64_t>(ds.n_chains, 1)) chain_key_bits++;
-            TRY_HIP(hipcub::DeviceRadixSort::SortPairs(cub_tmp, tmp, (const unsigned long long *)ek0, ek1, (const uint32_t *)eid0, eid1, (int)n_ent, 0, chain_key_bits, st));
+            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub_tmp, tmp, (const unsigned long long *)ek0, ek1, (const uint32_t *)eid0, eid1, (int)n_ent, 0, chain_key_bits, st));
         }
         hipLaunchKernelGGL(k_ent_flags, grid(n_ent, 256), dim3(256), 0, st, (uint32_t)n_ent, (const EntKey *)ds.ent_key, (uint32_t)n, (const EntKey *)d_ring_keys, chain,
                            (const RingEnt *)d_rings, (const uint32_t *)eid1, eflag);
         tmp = cub_scan;
-        TRY_HIP(hipcub::DeviceScan::InclusiveSum(cub_tmp, tmp, (const uint32_t *)eflag, eid0, (int)n_ent, st));
+        HIP_TRY(hipcub::DeviceScan::InclusiveSum(cub_tmp, tmp, (const uint32_t *)eflag, eid0, (int)n_ent, st));
         uint32_t *chain_base = reinterpret_cast<uint32_t *>(ek0);  // (the sort keys are done with: their first n_chains words hold the per-chain bases; n_chains <= n_ent)
         hipLaunchKernelGGL(k_ent_base, grid(n_ent, 256), dim3(256), 0, st, (uint32_t)n_ent, (uint32_t)n, chain, (const RingEnt *)d_rings, (const uint32_t *)eid1, (const uint32_t *)eid0,
                            chain_base);
         hipLaunchKernelGGL(k_ent_rank, grid(n_ent, 256), dim3(256), 0, st, (uint32_t)n_ent, (uint32_t)n, chain, (const RingEnt *)d_rings, (const uint32_t *)eid1, (const uint32_t *)eid0,
                            (const uint32_t *)chain_base, ent_rank, counters + 2);
-        TRY_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         uint32_t max_rank = 0;  // (once per structure: the width of a rank in the rows' sort key)
-        TRY_HIP(hipMemcpyAsync(&max_rank, counters + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        TRY_HIP(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(&max_rank, counters + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         ds.max_ent_rank = max_rank;
     }
     lap("planes+bits+ranks");
@@ -804,14 +790,14 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
         // ONE launch behind the ring kernels, the table written straight into the pinned landing block, one wait for the stream
         const uint64_t land = 16 + (uint64_t)kSmallRows * 32 + 256;
         char *dev2 = nullptr, *pin2 = nullptr;
-        if ((s = context_scratch(ctx, 1, al((uint64_t)kSmallRows * 16) + 4096, land, &dev2, &pin2)) != ARP_OK) return s;
+        if ((s = context_scratch(ctx, 1, seg_align((uint64_t)kSmallRows * 16) + 4096, land, &dev2, &pin2)) != ARP_OK) return s;
         if (n_rings && (s = launch_rings()) != ARP_OK) return s;
         hipLaunchKernelGGL(k_table_small, dim3(1), dim3(kSmallThreads), 0, st, pairs_dev, (uint32_t)n_pairs, (const uint4 *)ring_rows, n_rings ? (const uint32_t *)counters : (const uint32_t *)nullptr,
                            (uint32_t)ring_rows_cap, reinterpret_cast<uint4 *>(dev2), (uint32_t)n, (const EntKey *)ds.ent_key, (const EntKey *)d_ring_keys, (const uint32_t *)ent_rank,
                            (const uint32_t *)ds.chain_rank, (const uint32_t *)ds.model, (const uint32_t *)ds.model_rank, (const RingEnt *)d_rings, tb, (const uint32_t *)ds.atom_sc_src,
                            (const PlaneD *)sc_pl, (const uint8_t *)valid, pin2, timing ? reinterpret_cast<unsigned long long *>(pin2 + land - 128) : (unsigned long long *)nullptr);
-        TRY_HIP(hipGetLastError());
-        TRY_HIP(hipStreamSynchronize(st));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
         SmallHeader head;
         memcpy(&head, pin2, sizeof head);
         lap("one-launch table");
@@ -844,9 +830,9 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
     }
     // how many rows?  (one small read-back: the row buffers are sized by it)
     counts_host[0] = counts_host[3] = 0u;
-    if (n_rings) TRY_HIP(hipMemcpyAsync((void *)counts_host, counters, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    else if (n_pairs) TRY_HIP(hipMemcpyAsync((void *)(counts_host + 3), first + n_pairs, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    TRY_HIP(hipStreamSynchronize(st));
+    if (n_rings) HIP_TRY(hipMemcpyAsync((void *)counts_host, counters, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    else if (n_pairs) HIP_TRY(hipMemcpyAsync((void *)(counts_host + 3), first + n_pairs, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     const uint32_t n_ring_rows = counts_host[0], n_atom_rows = counts_host[3];
     if (n_ring_rows > ring_rows_cap) { set_error("internal error: more ring rows than reserved (%u > %llu)", n_ring_rows, (unsigned long long)ring_rows_cap); return ARP_ERR_HIP; }
     const uint32_t n_rows = n_atom_rows + n_ring_rows;
@@ -854,10 +840,10 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
     size_t cub_sort_rows = 0;
     (void)hipcub::DeviceRadixSort::SortPairs(nullptr, cub_sort_rows, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (const uint32_t *)nullptr,
                                              (uint32_t *)nullptr, (int)rows_cap, 0, 64);
-    const uint64_t need2 = al(rows_cap * 16) + al(rows_cap * 32 + 256) + al(rows_cap * 8) * 2 + al(rows_cap * 4) * 2 + al(cub_sort_rows) + 4096;
+    const uint64_t need2 = seg_align(rows_cap * 16) + seg_align(rows_cap * 32 + 256) + seg_align(rows_cap * 8) * 2 + seg_align(rows_cap * 4) * 2 + seg_align(cub_sort_rows) + 4096;
     char *dev2 = nullptr, *pin2 = nullptr;  // the row-sized buffers live in a scratch slot of their own: the first one must not move
-    if ((s = context_scratch(ctx, 1, need2, 2 * al(rows_cap * 16) + 4096, &dev2, &pin2)) != ARP_OK) return s;
-    b = Bump{dev2, 0, need2};
+    if ((s = context_scratch(ctx, 1, need2, 2 * seg_align(rows_cap * 16) + 4096, &dev2, &pin2)) != ARP_OK) return s;
+    b = Bump{dev2};
     pin = pin2;
     lap("ring rows + scratch");
     // the finished table in ONE device block {rows, sc values, the tie-overflow word}: one copy fetches it
@@ -894,7 +880,7 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
                                (const EntKey *)ds.ent_key, (const EntKey *)d_ring_keys, (const uint32_t *)ent_rank, (const uint32_t *)ds.chain_rank, (const uint32_t *)ds.model,
                                (const uint32_t *)ds.model_rank, (const RingEnt *)d_rings, tb, rk0, q ? (uint32_t *)nullptr : pin_);
             size_t tmp = cub_sort_rows;
-            TRY_HIP(hipcub::DeviceRadixSort::SortPairs(cub_tmp2, tmp, (const unsigned long long *)rk0, rk1, (const uint32_t *)pin_, pout, (int)n_rows, 0, end_bit[q], st));
+            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub_tmp2, tmp, (const unsigned long long *)rk0, rk1, (const uint32_t *)pin_, pout, (int)n_rows, 0, end_bit[q], st));
             std::swap(pin_, pout);
         }
         if (!long_way) {
@@ -906,7 +892,7 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
         }
         hipLaunchKernelGGL(k_finish_rows, grid(n_rows, 256), dim3(256), 0, st, n_rows, (const uint4 *)rows, (const uint32_t *)pin_, (uint32_t)n, (const uint32_t *)ds.atom_sc_src,
                            (const RingEnt *)d_rings, (const PlaneD *)sc_pl, (const uint8_t *)valid, out_rows, out_sc, (const uint32_t *)(counters + 1), out_flag);
-        TRY_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         return ARP_OK;
     };
     if (n_rows && (s = sort_and_finish(false)) != ARP_OK) return s;
@@ -931,8 +917,8 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
     uint32_t tie_overflow = 0u;
     auto fetch = [&]() -> arp_status {
         if (!n_rows) return ARP_OK;
-        TRY_HIP(hipMemcpyAsync(landing, out_all, all_bytes, hipMemcpyDeviceToHost, st));
-        TRY_HIP(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(landing, out_all, all_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         memcpy(&tie_overflow, landing + 2 * row_bytes, sizeof tie_overflow);
         if (heap) memcpy(heap, landing, 2 * row_bytes);
         return ARP_OK;

@@ -13,7 +13,7 @@ from typing import Sequence
 def lpt_assign(sizes: Sequence[int], n_shards: int) -> list[list[int]]:
     """Indices of `sizes` per shard: largest first, each to the currently lightest shard (ties: lowest shard id).
 
-    Mirrors arp_contacts_atomic_batch (engine.cpp): load += size + 1, stable descending order."""
+    Mirrors arp_contacts_atomic_batch (batch.cpp): load += size + 1, stable descending order."""
     order = sorted(range(len(sizes)), key=lambda k: -sizes[k])  # Python's sort is stable, like std::stable_sort
     shards: list[list[int]] = [[] for _ in range(n_shards)]
     load = [0] * n_shards
