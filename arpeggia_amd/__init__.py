@@ -1,7 +1,7 @@
 """arpeggia_amd: MI355X-native drop-in for the `contacts` path of y1zhou/arpeggia.
 
 Public surface mirrors the reference (src/lib.rs:20-34, src/python.rs:31-56) for this one path:
-contacts(), get_contacts(), load_model(), parse_groups(); and atom-level sasa(), sap_score(), dsasa(); and sc(); and
+contacts(), get_contacts(), load_model(), parse_groups(); and sasa(), relative_sasa(), sap_score(), dsasa(); and sc(); and
 contact_frequencies(), sasa_ensemble() and sap_ensemble() across the frames of an ensemble (no counterpart in the reference).  Importing this package loads libarpeggia_amd.so and
 fails loudly if the HIP extension has not been built -- there is no CPU fallback.
 """
@@ -12,6 +12,10 @@ from .api import (  # noqa: F401
 from .api import (  # noqa: F401  atom SASA, SAP score, dSASA (reference src/sasa.rs, src/sap.rs)
     atom_sasa, dsasa, get_atom_sasa, get_dsasa, get_per_atom_sap_score, get_per_residue_sap_score, sap_score, sasa, sasa_select,
     sasa_sphere_points, sasa_tests,
+)
+from .api import (  # noqa: F401  residue- and chain-level SASA, relative SASA (src/sasa.rs:284-382, 520-561), segment sums on the device
+    CHAIN_SASA_COLUMNS, RELATIVE_SASA_COLUMNS, RESIDUE_ENSEMBLE_SASA_COLUMNS, RESIDUE_SASA_COLUMNS, get_chain_sasa, get_relative_sasa, get_residue_sasa,
+    get_residue_sasa_ensemble, max_asa, relative_sasa, sasa_radius, segment_sum,
 )
 from .api import get_sc, get_sc_results, sc, sc_arrays, sc_dots, sc_radius, sc_select  # noqa: F401  shape complementarity (src/sc/)
 from .api import FREQ_COLUMNS, contact_frequencies, get_contact_frequencies  # noqa: F401  contact frequencies across the frames of an ensemble

@@ -1,6 +1,7 @@
 """Command-line driver: `python -m arpeggia_amd contacts -i model.pdb -o out/` -- the flags and defaults of the reference's
 `arpeggia contacts` (src/cli/contacts.rs:9-52) over the MI355X engine; it writes <output>/<filename>.<format> like cli/contacts.rs:108-137.
-`sasa`, `sap`, `dsasa` and `sc` take the flags and defaults of src/cli/{sasa,sap,dsasa,sc}.rs (sasa at level "atom" only: see arpeggia_amd/api.py).
+`sasa`, `relative-sasa`, `sap`, `dsasa` and `sc` take the flags and defaults of src/cli/{sasa,relative_sasa,sap,dsasa,sc}.rs; `sasa`, `dsasa` and
+`sasa-ensemble` also take --radii {vdw,protor}: the radius table, which the residue and chain levels of `sasa` need (see arpeggia_amd/api.py).
 `contact-frequency` (no counterpart in the reference) takes the flags and defaults of `contacts`; the models of the input file are the frames.
 `sasa-ensemble` and `sap-ensemble` (no counterpart either) take the flags and defaults of `sasa` / `sap` without --model: statistics over the models.
 """
@@ -13,6 +14,8 @@ import sys
 from pathlib import Path
 
 FORMATS = ("csv", "parquet", "json", "ndjson")  # utils.rs:148-167 DataFrameFileType
+
+RADII_HELP = "Radius table: vdw (element radii) or protor (ProtOr, Tsai et al. 1999); the residue and chain levels of sasa need one"
 
 log = logging.getLogger("arpeggia_amd")
 
@@ -56,8 +59,16 @@ def build_parser() -> argparse.ArgumentParser:
     a.add_argument("-f", "--filename", default="sasa", help="Name of the output file")
     a.add_argument("-t", "--output-format", default="csv", type=str.lower, choices=FORMATS, help="Output file type")
     add(a, "model", "probe", "points", "threads")
-    a.add_argument("-l", "--level", default="atom", type=str.lower, choices=("atom", "residue", "chain"), help="Aggregation level (only atom is available)")
+    a.add_argument("-l", "--level", default="atom", type=str.lower, choices=("atom", "residue", "chain"), help="Aggregation level (residue and chain need --radii)")
     a.add_argument("-c", "--chains", default="", help="Comma-separated chain IDs to include (empty: all)")
+    a.add_argument("--radii", default=None, type=str.lower, choices=("vdw", "protor"), help=RADII_HELP)
+    rs = sub.add_parser("relative-sasa", help="relative solvent accessible surface area per residue (cli/relative_sasa.rs)")
+    rs.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file to be analyzed")
+    rs.add_argument("-o", "--output", required=True, type=Path, help="Output directory")
+    rs.add_argument("-f", "--filename", default="relative_sasa", help="Name of the output file")
+    rs.add_argument("-t", "--output-format", default="csv", type=str.lower, choices=FORMATS, help="Output file type")
+    add(rs, "model", "probe", "points", "threads")
+    rs.add_argument("-c", "--chains", default="", help="Comma-separated chain IDs to include (empty: all)")
     p = sub.add_parser("sap", help="spatial aggregation propensity per atom or residue (cli/sap.rs)")
     p.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file to be analyzed")
     p.add_argument("-o", "--output", required=True, type=Path, help="Output directory")
@@ -74,8 +85,9 @@ def build_parser() -> argparse.ArgumentParser:
     ea.add_argument("-f", "--filename", default="sasa_ensemble", help="Name of the output file")
     ea.add_argument("-t", "--output-format", default="csv", type=str.lower, choices=FORMATS, help="Output file type")
     add(ea, "probe", "points", "threads")
-    ea.add_argument("-l", "--level", default="atom", type=str.lower, choices=("atom", "residue", "chain"), help="Aggregation level (only atom is available)")
+    ea.add_argument("-l", "--level", default="atom", type=str.lower, choices=("atom", "residue", "chain"), help="Aggregation level (residue and chain need --radii)")
     ea.add_argument("-c", "--chains", default="", help="Comma-separated chain IDs to include (empty: all)")
+    ea.add_argument("--radii", default=None, type=str.lower, choices=("vdw", "protor"), help=RADII_HELP)
     ep = sub.add_parser("sap-ensemble", help="spatial aggregation propensity averaged across the models of a multi-model file, per atom or residue")
     ep.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file whose models are the frames")
     ep.add_argument("-o", "--output", required=True, type=Path, help="Output directory")
@@ -90,6 +102,7 @@ def build_parser() -> argparse.ArgumentParser:
     d.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file to be analyzed")
     d.add_argument("-g", "--groups", required=True, help="Chain groups, e.g. A,B/C,D")
     add(d, "model", "probe", "points", "threads")
+    d.add_argument("--radii", default=None, type=str.lower, choices=("vdw", "protor"), help=RADII_HELP)
     g = sub.add_parser("sc", help="shape complementarity of two chain groups (cli/sc.rs)")
     g.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file to be analyzed")
     g.add_argument("-g", "--groups", required=True, help="Chain groups, e.g. A,B/C,D: both surfaces must be given")
@@ -118,7 +131,7 @@ def run_sc(args) -> int:
 
 
 def run_surface(args) -> int:
-    """sasa / sap / dsasa (cli/sasa.rs, cli/sap.rs, cli/dsasa.rs)."""
+    """sasa / relative-sasa / sap / dsasa (cli/sasa.rs, cli/relative_sasa.rs, cli/sap.rs, cli/dsasa.rs)."""
     import arpeggia_amd as aa
 
     if not args.input.exists():
@@ -126,15 +139,22 @@ def run_surface(args) -> int:
         return 1
     s = aa.Structure.load(str(args.input.resolve()))
     if args.command == "dsasa":
-        v = aa.get_dsasa(s, args.groups, args.probe_radius, args.n_points, args.model_num)
+        v = aa.get_dsasa(s, args.groups, args.probe_radius, args.n_points, args.model_num, radii=args.radii)
         log.info("Buried surface area (dSASA) at the interface between chains [%s]: %.2f A^2", args.groups, v)
         return 0
     if args.command == "sasa":
-        if args.level != "atom":
-            log.error("sasa level '%s' is not available (the reference's rust-sasa radius table is not part of its tree); use --level atom", args.level)
+        if args.level != "atom" and args.radii is None:
+            log.error("sasa level '%s' needs a named radius table (the reference's rust-sasa table is not part of its tree): add --radii protor, or use --level atom", args.level)
             return 2
-        table = aa.get_atom_sasa(s, args.probe_radius, args.n_points, args.model_num, True, args.chains)
-        what = "atoms"
+        if args.level == "atom":
+            table = aa.get_atom_sasa(s, args.probe_radius, args.n_points, args.model_num, True, args.chains, radii=args.radii)
+        else:
+            f = aa.get_residue_sasa if args.level == "residue" else aa.get_chain_sasa
+            table = f(s, args.probe_radius, args.n_points, args.model_num, args.chains, args.radii)
+        what = {"atom": "atoms", "residue": "residues", "chain": "chains"}[args.level]
+    elif args.command == "relative-sasa":
+        table = aa.get_relative_sasa(s, args.probe_radius, args.n_points, args.model_num, args.chains)
+        what = "residues"
     else:
         f = aa.get_per_atom_sap_score if args.level == "atom" else aa.get_per_residue_sap_score
         table = f(s, args.probe_radius, args.n_points, args.model_num, args.sap_radius, args.chains)
@@ -156,14 +176,14 @@ def run_ensemble(args) -> int:
     if not args.input.exists():
         log.error("Failed to retrieve input file: %s", args.input)
         return 1
-    if args.command == "sasa-ensemble" and args.level != "atom":
-        log.error("sasa level '%s' is not available (the reference's rust-sasa radius table is not part of its tree); use --level atom", args.level)
+    if args.command == "sasa-ensemble" and args.level != "atom" and args.radii is None:
+        log.error("sasa level '%s' needs a named radius table (the reference's rust-sasa table is not part of its tree): add --radii protor, or use --level atom", args.level)
         return 2
     try:
-        s = aa.Structure.load(str(args.input.resolve()))
         if args.command == "sasa-ensemble":
-            table = aa.get_sasa_ensemble(s, None, args.chains, args.probe_radius, args.n_points)
+            table = aa.sasa_ensemble(str(args.input.resolve()), args.probe_radius, args.n_points, args.chains, args.level, args.radii)
         else:
+            s = aa.Structure.load(str(args.input.resolve()))
             f = aa.get_sap_ensemble if args.level == "atom" else aa.get_residue_sap_ensemble
             table = f(s, None, args.chains, args.probe_radius, args.n_points, args.sap_radius)
     except aa.ArpeggiaError as e:
@@ -175,7 +195,7 @@ def run_ensemble(args) -> int:
     args.output.mkdir(parents=True, exist_ok=True)
     out = (args.output / args.filename).with_suffix("." + args.output_format)
     write_table(table, out, args.output_format)
-    log.info("Results for %d %s saved to %s", len(table), "residues" if getattr(args, "level", "atom") == "residue" else "atoms", out)
+    log.info("Results for %d %s saved to %s", len(table), {"atom": "atoms", "residue": "residues", "chain": "chains"}[getattr(args, "level", "atom")], out)
     return 0
 
 

@@ -22,6 +22,7 @@ ARP_FLAG_NO_SPECULATION = 0x4
 ARP_FLAG_RESIDUE_RUNS = 0x8
 ARP_FLAG_NO_RESIDUE_RUNS = 0x10
 ARP_SASA_MAX_POINTS = 4096
+ARP_RADII_VDW, ARP_RADII_PROTOR = 0, 1
 
 ATTR = dict(
     ELEM_MASK=0xF, DONOR=0x10, ACCEPTOR=0x20, WEAK_DONOR=0x40, POS=0x80, NEG=0x100, HYDROPHOBIC=0x200, CYS_SG=0x400,
@@ -38,6 +39,8 @@ _dp = C.POINTER(C.c_double)
 _u32p = C.POINTER(C.c_uint32)
 _u16p = C.POINTER(C.c_uint16)
 _i32p = C.POINTER(C.c_int32)
+_fp = C.POINTER(C.c_float)
+_u8p = C.POINTER(C.c_uint8)
 
 
 class arp_atoms(C.Structure):
@@ -194,6 +197,19 @@ def _load():
         "arp_sasa_ensemble_stats": (C.c_int32, [C.c_uint64, C.c_uint64, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _i32p, _i32p,
                                                 _dp, _dp] + [C.POINTER(C.c_float)] * 6),
         "arp_contact_frequencies": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_double, C.c_double, C.POINTER(vp)]),
+        "arp_sasa_radius": (C.c_int32, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, _fp]),
+        "arp_max_asa": (C.c_float, [C.c_char_p]),
+        "arp_residue_is_polar": (C.c_int32, [C.c_char_p]),
+        "arp_segment_sum": (C.c_int32, [vp, C.c_uint64, C.c_uint64, _fp, C.c_uint64, _u32p, _u32p, _fp]),
+        "arp_structure_atom_sasa_radii": (C.c_int32, [vp, vp, C.c_char_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), _u32p, _fp, _i32p]),
+        "arp_structure_dsasa_radii": (C.c_int32, [vp, vp, C.c_char_p, C.c_float, C.c_int32, C.c_int32, C.c_int32, _fp]),
+        "arp_structure_residue_sasa": (C.c_int32, [vp, vp, C.c_char_p, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), _u32p, _fp, _u8p]),
+        "arp_structure_chain_sasa": (C.c_int32, [vp, vp, C.c_char_p, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), _u32p, _fp]),
+        "arp_structure_relative_sasa": (C.c_int32, [vp, vp, C.c_char_p, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), _u32p, _fp, _u8p, _fp, _u8p]),
+        "arp_sasa_ensemble_radii": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                                _u32p] + [_fp] * 5 + [_i32p]),
+        "arp_sasa_ensemble_residues": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_float, C.c_int32, C.c_int32] + [C.POINTER(C.c_uint64)] * 3 +
+                                       [_u32p, _u8p] + [_fp] * 5 + [_u8p, _u32p, _fp, _fp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here == the library does not export what the header declares

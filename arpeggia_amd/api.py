@@ -376,12 +376,20 @@ class Context:
             lib.arp_table_free(t)
 
     def sasa_ensemble(self, structure: Structure, frames=None, chains: str = "", probe_radius: float = 1.4, n_points: int = 100, sap_radius: float | None = None,
-                      per_frame: bool = False) -> dict:
+                      per_frame: bool = False, radii=None) -> dict:
         """arp_sasa_ensemble as a dict of numpy arrays: per-atom SASA statistics over the frames of an ensemble, and SAP statistics when
         sap_radius is given.  frames: [F, N, 3] f64 coordinates of the topology's N atoms (model 0 of `structure`); None: the structure's models
         are the frames.  Keys: atoms (u32 structure indices of the m selected atoms), n_frames, mean_sasa / std_sasa / min_sasa / max_sasa [m],
         total_sasa [F], with SAP mean_sap / std_sap / min_sap / max_sap [m]; per_frame adds count [F, m] i32 and, with SAP, sap [F, m] f32."""
-        return _sasa_ensemble(self, structure, frames, chains, probe_radius, n_points, sap_radius, per_frame)
+        return _sasa_ensemble(self, structure, frames, chains, probe_radius, n_points, sap_radius, per_frame, radii)
+
+    def residue_sasa_ensemble(self, structure: Structure, frames=None, chains: str = "", probe_radius: float = 1.4, n_points: int = 100,
+                              radii: str = "protor", per_frame: bool = False) -> dict:
+        """arp_sasa_ensemble_residues as a dict of numpy arrays: residue-level SASA statistics over the frames of an ensemble, summed on the
+        device.  Keys: res_atoms / chain_atoms (u32: the first selected atom of every residue / chain), n_frames, is_polar [n_res] bool,
+        mean_sasa / std_sasa / min_sasa / max_sasa [n_res], mean_relative_sasa [n_res] (NaN where relative_valid is False), chain_sasa
+        [F, n_chains]; per_frame adds residue_sasa [F, n_res]."""
+        return _residue_sasa_ensemble(self, structure, frames, chains, probe_radius, n_points, radii, per_frame)
 
 
 def _topology_atoms(structure: Structure) -> int:
@@ -416,8 +424,12 @@ def _frames_arg(structure: Structure, frames, what: str):
     return n_frames, keep.ctypes.data_as(C.POINTER(C.c_double)), keep
 
 
-def _sasa_ensemble(ctx: "Context | None", structure: Structure, frames, chains: str, probe_radius: float, n_points: int, sap_radius, per_frame: bool) -> dict:
-    """arp_sasa_ensemble.  ctx None: the inputs are only checked (raises their error); the result then holds atoms and n_frames only."""
+def _sasa_ensemble(ctx: "Context | None", structure: Structure, frames, chains: str, probe_radius: float, n_points: int, sap_radius, per_frame: bool,
+                   radii=None) -> dict:
+    """arp_sasa_ensemble.  ctx None: the inputs are only checked (raises their error); the result then holds atoms and n_frames only.
+    radii: a table name runs arp_sasa_ensemble_radii (SASA only: the SAP score is defined on the van der Waals radii)."""
+    if radii is not None:
+        return _sasa_ensemble_radii(ctx, structure, frames, chains, probe_radius, n_points, sap_radius, per_frame, radii)
     n_frames, ptr, keep = _frames_arg(structure, frames, "sasa ensemble")
     with_sap = sap_radius is not None
     fp = C.POINTER(C.c_float)
@@ -449,6 +461,69 @@ def _sasa_ensemble(ctx: "Context | None", structure: Structure, frames, chains: 
         out["count"] = count[: F * m].reshape(F, m)
     if sap is not None:
         out["sap"] = sap[: F * m].reshape(F, m)
+    return out
+
+
+def _sasa_ensemble_radii(ctx: "Context | None", structure: Structure, frames, chains: str, probe_radius: float, n_points: int, sap_radius, per_frame: bool,
+                         radii) -> dict:
+    table = _radii_table(radii)
+    if sap_radius is not None:
+        raise ValueError("the SAP statistics use the van der Waals radii: radii must be None with sap_radius")
+    n_frames, ptr, keep = _frames_arg(structure, frames, "sasa ensemble")
+    fp = C.POINTER(C.c_float)
+    rows, used = C.c_uint64(), C.c_uint64()
+    atoms = np.zeros(max(structure.n_atoms, 1), "<u4")
+    args = (structure._h, int(n_frames), ptr, chains.encode(), C.c_float(probe_radius), int(n_points), table, C.byref(rows), C.byref(used),
+            atoms.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if ctx is None:
+        _check(lib.arp_sasa_ensemble_radii(None, *args, *([None] * 6)))
+        return {"atoms": atoms[: rows.value].copy(), "n_frames": int(used.value)}
+    n_top = _topology_atoms(structure)
+    f_cap = n_frames if frames is not None else (structure.n_atoms // n_top if n_top else 1)
+    cols = {k: np.zeros(max(n_top, 1), "<f4") for k in ("mean_sasa", "std_sasa", "min_sasa", "max_sasa")}
+    total = np.zeros(max(f_cap, 1), "<f4")
+    count = np.zeros(max(f_cap * n_top, 1), "<i4") if per_frame else None
+    _check(lib.arp_sasa_ensemble_radii(ctx._h, *args, *(cols[k].ctypes.data_as(fp) for k in cols), total.ctypes.data_as(fp),
+                                       None if count is None else count.ctypes.data_as(C.POINTER(C.c_int32))))
+    del keep
+    m, F = int(rows.value), int(used.value)
+    out = {"atoms": atoms[:m].copy(), "n_frames": F}
+    out.update({k: v[:m].copy() for k, v in cols.items()})
+    out["total_sasa"] = total[:F].copy()
+    if count is not None:
+        out["count"] = count[: F * m].reshape(F, m)
+    return out
+
+
+def _residue_sasa_ensemble(ctx: "Context | None", structure: Structure, frames, chains: str, probe_radius: float, n_points: int, radii, per_frame: bool) -> dict:
+    """arp_sasa_ensemble_residues.  ctx None: the inputs are only checked (raises their error); the result then holds res_atoms, chain_atoms
+    and n_frames only."""
+    table = _radii_table(radii)
+    n_frames, ptr, keep = _frames_arg(structure, frames, "sasa ensemble")
+    fp, bp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    rows, n_chains, used = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    n = max(structure.n_atoms, 1)
+    res_atoms, chain_atoms = np.zeros(n, "<u4"), np.zeros(n, "<u4")
+    head = (structure._h, int(n_frames), ptr, chains.encode(), C.c_float(probe_radius), int(n_points), table, C.byref(rows), C.byref(n_chains), C.byref(used),
+            res_atoms.ctypes.data_as(up))
+    # the checks alone: they size the outputs (residues, chains, frames)
+    _check(lib.arp_sasa_ensemble_residues(None, *head, *([None] * 7), chain_atoms.ctypes.data_as(up), None, None))
+    nr, nc, F = int(rows.value), int(n_chains.value), int(used.value)
+    if ctx is None:
+        return {"res_atoms": res_atoms[:nr].copy(), "chain_atoms": chain_atoms[:nc].copy(), "n_frames": F}
+    cols = {k: np.zeros(max(nr, 1), "<f4") for k in ("mean_sasa", "std_sasa", "min_sasa", "max_sasa", "mean_relative_sasa")}
+    polar, valid = np.zeros(max(nr, 1), np.uint8), np.zeros(max(nr, 1), np.uint8)
+    chain_sasa = np.zeros(max(F * nc, 1), "<f4")
+    per = np.zeros(max(F * nr, 1), "<f4") if per_frame else None
+    _check(lib.arp_sasa_ensemble_residues(ctx._h, *head, polar.ctypes.data_as(bp), *(cols[k].ctypes.data_as(fp) for k in cols), valid.ctypes.data_as(bp),
+                                          chain_atoms.ctypes.data_as(up), chain_sasa.ctypes.data_as(fp), None if per is None else per.ctypes.data_as(fp)))
+    del keep
+    nr, nc, F = int(rows.value), int(n_chains.value), int(used.value)
+    out = {"res_atoms": res_atoms[:nr].copy(), "chain_atoms": chain_atoms[:nc].copy(), "n_frames": F, "is_polar": polar[:nr].astype(bool),
+           "relative_valid": valid[:nr].astype(bool), "chain_sasa": chain_sasa[: F * nc].reshape(F, nc)}
+    out.update({k: v[:nr].copy() for k, v in cols.items()})
+    if per is not None:
+        out["residue_sasa"] = per[: F * nr].reshape(F, nr)
     return out
 
 
@@ -632,10 +707,16 @@ def contacts_batch(input_files, groups: str = "/", vdw_comp: float = 0.1, dist_c
 # ---------------------------------------------------------------------------------------------- atom SASA, SAP score, dSASA
 # Atom-level SASA (reference src/sasa.rs:174-249) and everything built on it: per-atom / per-residue SAP (src/sap.rs:137-340) and dSASA
 # (src/sasa.rs:400-451, python.rs:161-191).  The Shrake-Rupley kernel, the SAP weights and the neighbour sum run on the device
-# (include/arpeggia_amd.h "atom SASA").  Residue- and chain-level SASA and relative_sasa are not offered: the reference computes them through
-# rust-sasa's SASAOptions, whose own radius table (van der Waals only as a fallback) is not part of the reference's tree, so those numbers would
-# be a guess.  dSASA is built from atom-level SASA here, where the reference sums chain-level SASA; its tolerance test is the check.
-SASA_LEVELS = ("atom",)
+# (include/arpeggia_amd.h "atom SASA").  Residue- and chain-level SASA and relative_sasa (src/sasa.rs:284-382, 520-561) sum the per-atom values
+# on the device (arp_segment_sum) with the radii of a NAMED table: the reference computes them through rust-sasa, whose table is not part of its
+# tree; "protor" is the table that reproduces the reference's chain-level pin, "vdw" the element radii of the atom level.
+# On the older entry points (sasa, get_atom_sasa, get_dsasa, get_sasa_ensemble) radii=None keeps their behaviour: van der Waals radii at the
+# atom level, the other levels refused.  dSASA is built from atom-level SASA here, where the reference sums chain-level SASA.
+SASA_LEVELS = ("atom", "residue", "chain")
+RADII_TABLES = {"vdw": _lib.ARP_RADII_VDW, "protor": _lib.ARP_RADII_PROTOR}
+RESIDUE_SASA_COLUMNS = ["chain", "resn", "resi", "insertion", "sasa", "is_polar"]
+CHAIN_SASA_COLUMNS = ["chain", "sasa"]
+RELATIVE_SASA_COLUMNS = RESIDUE_SASA_COLUMNS + ["relative_sasa"]
 SAP_LEVELS = ("atom", "residue")
 # src/sap.rs:77-101 get_sc_max_asa (the table of arp_sap_weight; tests/test_sasa_host.py checks the two agree)
 SAP_MAX_SC_ASA = {
@@ -715,42 +796,172 @@ def _identity(structure: Structure, idx: np.ndarray) -> dict:
     }
 
 
+def _radii_table(radii) -> int:
+    """The table code of a radii name ("vdw" / "protor", case-insensitive); an unknown name is a ValueError."""
+    key = str(radii).lower()
+    if key not in RADII_TABLES:
+        raise ValueError(f"Invalid radii '{radii}'. Must be one of: 'vdw', 'protor'")
+    return RADII_TABLES[key]
+
+
+def sasa_radius(resn: str, atomn: str, element: str = "", radii: str = "protor") -> float:
+    """arp_sasa_radius: the f32 radius of (residue, atom name) in the named table, with its van der Waals fallback by element."""
+    out = C.c_float()
+    _check(lib.arp_sasa_radius(resn.encode(), atomn.encode(), element.encode(), _radii_table(radii), C.byref(out)))
+    return float(out.value)
+
+
+def max_asa(resn: str):
+    """arp_max_asa: MaxASA of Tien et al. 2013 (the reference's get_max_asa), None for a residue without one."""
+    v = float(lib.arp_max_asa(resn.encode()))
+    return v if v > 0.0 else None
+
+
+def segment_sum(ctx: "Context | None", values, seg_start, seg_item) -> np.ndarray:
+    """arp_segment_sum: values [rows, m] f32, a CSR of segments over the m items -> [rows, n_seg] f32, every sum the sequential f64 chain in
+    list order rounded to f32 once.  ctx None: the inputs are only checked."""
+    v = np.ascontiguousarray(values, dtype="<f4")
+    if v.ndim == 1:
+        v = v[None]
+    start = np.ascontiguousarray(seg_start, dtype="<u4")
+    item = np.ascontiguousarray(seg_item, dtype="<u4")
+    rows, m = v.shape
+    n_seg = len(start) - 1
+    out = np.zeros((rows, max(n_seg, 0)), dtype="<f4")
+    fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+    pad = lambda a, ty: (a if a.size else np.zeros(1, a.dtype)).ctypes.data_as(ty)  # noqa: E731  (a valid pointer for an empty array)
+    _check(lib.arp_segment_sum(ctx._h if ctx is not None else None, rows, m, pad(v, fp), max(n_seg, 0), pad(start, up), pad(item, up), pad(out, fp)))
+    return out
+
+
 def atom_sasa_rows(structure: Structure, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, remove_hydrogens: bool = True,
-                   chains: str = "", device: int = 0):
-    """arp_structure_atom_sasa as numpy arrays: (structure atom index u32, sasa f32, count i32), rows sorted by serial number."""
+                   chains: str = "", device: int = 0, radii=None):
+    """arp_structure_atom_sasa as numpy arrays: (structure atom index u32, sasa f32, count i32), rows sorted by serial number.  radii: None (van
+    der Waals, as ever) or a table name."""
+    table = None if radii is None else _radii_table(radii)
     n = max(structure.n_atoms, 1)
     atoms, sasa, count = np.zeros(n, "<u4"), np.zeros(n, "<f4"), np.zeros(n, "<i4")
     rows = C.c_uint64()
-    _check(lib.arp_structure_atom_sasa(_context(device)._h, structure._h, chains.encode(), int(model_num), int(bool(remove_hydrogens)),
-                                       C.c_float(probe_radius), int(n_points), C.byref(rows), atoms.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                       sasa.ctypes.data_as(C.POINTER(C.c_float)), count.ctypes.data_as(C.POINTER(C.c_int32))))
+    tail = (C.byref(rows), atoms.ctypes.data_as(C.POINTER(C.c_uint32)), sasa.ctypes.data_as(C.POINTER(C.c_float)), count.ctypes.data_as(C.POINTER(C.c_int32)))
+    head = (structure._h, chains.encode(), int(model_num), int(bool(remove_hydrogens)), C.c_float(probe_radius), int(n_points))
+    if table is None:
+        _check(lib.arp_structure_atom_sasa(_context(device)._h, *head, *tail))
+    else:
+        _check(lib.arp_structure_atom_sasa_radii(_context(device)._h, *head, table, *tail))
     k = rows.value
     return atoms[:k].copy(), sasa[:k].copy(), count[:k].copy()
 
 
 def get_atom_sasa(structure: Structure, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, remove_hydrogens: bool = True,
-                  chains: str = "", device: int = 0):
+                  chains: str = "", device: int = 0, radii=None):
     """`arpeggia::get_atom_sasa` (sasa.rs:174): columns atomi i32, sasa f32, chain, resn, resi i32, insertion, altloc, atomn; sorted by atomi."""
     import pyarrow as pa
 
-    idx, sasa, _ = atom_sasa_rows(structure, probe_radius, n_points, model_num, remove_hydrogens, chains, device)
+    idx, sasa, _ = atom_sasa_rows(structure, probe_radius, n_points, model_num, remove_hydrogens, chains, device, radii)
     ident = _identity(structure, idx)
     cols = {"atomi": ident["atomi"], "sasa": pa.array(sasa, pa.float32())}
     cols.update({k: ident[k] for k in ATOM_SASA_COLUMNS[2:]})
     return _frame(cols)
 
 
+def level_sasa_rows(structure: Structure, level: str, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, chains: str = "",
+                    radii: str = "protor", device: int = 0) -> dict:
+    """arp_structure_residue_sasa / _chain_sasa / _relative_sasa as numpy arrays: atoms (the first selected atom of every row: its identity),
+    sasa f32, and for the residue levels is_polar (bool); level "relative" adds relative_sasa f32 (NaN where null) and valid (bool)."""
+    table = _radii_table(radii)
+    n = max(structure.n_atoms, 1)
+    atoms, sasa_ = np.zeros(n, "<u4"), np.zeros(n, "<f4")
+    polar, valid, rel = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, "<f4")
+    rows = C.c_uint64()
+    fp, bp = C.POINTER(C.c_float), C.POINTER(C.c_uint8)
+    args = (_context(device)._h, structure._h, chains.encode(), int(model_num), C.c_float(probe_radius), int(n_points), table, C.byref(rows),
+            atoms.ctypes.data_as(C.POINTER(C.c_uint32)), sasa_.ctypes.data_as(fp))
+    if level == "chain":
+        _check(lib.arp_structure_chain_sasa(*args))
+    elif level == "residue":
+        _check(lib.arp_structure_residue_sasa(*args, polar.ctypes.data_as(bp)))
+    elif level == "relative":
+        _check(lib.arp_structure_relative_sasa(*args, polar.ctypes.data_as(bp), rel.ctypes.data_as(fp), valid.ctypes.data_as(bp)))
+    else:
+        raise ValueError(f"Invalid level '{level}'")
+    k = rows.value
+    out = {"atoms": atoms[:k].copy(), "sasa": sasa_[:k].copy()}
+    if level != "chain":
+        out["is_polar"] = polar[:k].astype(bool)
+    if level == "relative":
+        out["relative_sasa"], out["valid"] = rel[:k].copy(), valid[:k].astype(bool)
+    return out
+
+
+def _residue_identity(structure: Structure, idx: np.ndarray) -> dict:
+    ident = _identity(structure, idx)
+    return {k: ident[k] for k in RESIDUE_SASA_COLUMNS[:4]}
+
+
+def _nullable_f32(values: np.ndarray, valid: np.ndarray):
+    import pyarrow as pa
+
+    return pa.array(values, pa.float32(), mask=~np.asarray(valid, bool))
+
+
+def get_residue_sasa(structure: Structure, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, chains: str = "",
+                     radii: str = "protor", device: int = 0):
+    """`arpeggia::get_residue_sasa` (sasa.rs:284): chain, resn, resi i32, insertion, sasa f32, is_polar; sorted by chain, resi, insertion."""
+    import pyarrow as pa
+
+    r = level_sasa_rows(structure, "residue", probe_radius, n_points, model_num, chains, radii, device)
+    cols = _residue_identity(structure, r["atoms"])
+    cols["sasa"] = pa.array(r["sasa"], pa.float32())
+    cols["is_polar"] = pa.array(r["is_polar"], pa.bool_())
+    return _frame(cols)
+
+
+def get_chain_sasa(structure: Structure, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, chains: str = "",
+                   radii: str = "protor", device: int = 0):
+    """`arpeggia::get_chain_sasa` (sasa.rs:352): chain, sasa f32; sorted by chain."""
+    import pyarrow as pa
+
+    r = level_sasa_rows(structure, "chain", probe_radius, n_points, model_num, chains, radii, device)
+    return _frame({"chain": pa.array(_strings(structure, "chain", r["atoms"]), pa.string()), "sasa": pa.array(r["sasa"], pa.float32())})
+
+
+def get_relative_sasa(structure: Structure, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, chains: str = "",
+                      radii: str = "protor", device: int = 0):
+    """`arpeggia::get_relative_sasa` (sasa.rs:520, its code): the residue rows plus relative_sasa = sasa / MaxASA (Tien et al. 2013), null for
+    a residue without a MaxASA."""
+    import pyarrow as pa
+
+    r = level_sasa_rows(structure, "relative", probe_radius, n_points, model_num, chains, radii, device)
+    cols = _residue_identity(structure, r["atoms"])
+    cols["sasa"] = pa.array(r["sasa"], pa.float32())
+    cols["is_polar"] = pa.array(r["is_polar"], pa.bool_())
+    cols["relative_sasa"] = _nullable_f32(r["relative_sasa"], r["valid"])
+    return _frame(cols)
+
+
+def relative_sasa(input_file: str, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, chains: str = "", num_threads: int = 1):
+    """Drop-in for `arpeggia.relative_sasa` (python.rs:242), with the "protor" radii."""
+    del num_threads  # (the computation runs on the GPU; accepted for signature compatibility)
+    return get_relative_sasa(Structure.load(input_file), probe_radius, n_points, model_num, chains)
+
+
 def sasa(input_file: str, level: str = "atom", probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, chains: str = "",
-         num_threads: int = 1):
-    """Drop-in for `arpeggia.sasa` (python.rs:93) at level "atom" (the only level offered: see the section comment above)."""
+         num_threads: int = 1, radii=None):
+    """Drop-in for `arpeggia.sasa` (python.rs:93).  radii None: level "atom" with van der Waals radii, the other levels refused (they need a
+    named radius table: see the section comment above); radii "protor" / "vdw": every level, with that table."""
     lv = str(level).lower()
     if lv not in ("atom", "residue", "chain"):
         raise ValueError(f"Invalid level '{level}'. Must be one of: 'atom', 'residue', 'chain'")
-    if lv != "atom":
-        raise NotImplementedError(f"sasa level '{lv}' is not available: the reference computes it with rust-sasa's own radius table, which is "
-                                  "not part of its source tree; only level='atom' (get_atom_sasa) is reproduced")
+    if radii is not None:
+        _radii_table(radii)
+    elif lv != "atom":
+        raise NotImplementedError(f"sasa level '{lv}' needs a named radius table: the reference computes it with rust-sasa's own table, which is "
+                                  "not part of its source tree; pass radii='protor' (the table that reproduces its chain-level pin) or radii='vdw'")
     del num_threads  # (the computation runs on the GPU; accepted for signature compatibility)
-    return get_atom_sasa(Structure.load(input_file), probe_radius, n_points, model_num, True, chains)
+    s = Structure.load(input_file)
+    if lv == "atom":
+        return get_atom_sasa(s, probe_radius, n_points, model_num, True, chains, radii=radii)
+    return (get_residue_sasa if lv == "residue" else get_chain_sasa)(s, probe_radius, n_points, model_num, chains, radii)
 
 
 def atom_sap_rows(structure: Structure, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, sap_radius: float = 5.0,
@@ -824,19 +1035,24 @@ def sap_score(input_file: str, level: str = "residue", probe_radius: float = 1.4
     return f(s, probe_radius, n_points, model_num, sap_radius, chains)
 
 
-def get_dsasa(structure: Structure, groups: str, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, device: int = 0) -> float:
+def get_dsasa(structure: Structure, groups: str, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, device: int = 0, radii=None) -> float:
     """`arpeggia::get_dsasa` (sasa.rs:400-451) from atom-level SASA: SASA(group 1) + SASA(group 2) - SASA(complex), not halved.
-    A negative value raises (python.rs:177-188); group errors are those of the contact path's parse_groups."""
+    A negative value raises (python.rs:177-188); group errors are those of the contact path's parse_groups.  radii: None (van der Waals) or a table name."""
     out = C.c_float()
-    _check(lib.arp_structure_dsasa(_context(device)._h, structure._h, groups.encode(), C.c_float(probe_radius), int(n_points), int(model_num),
-                                   C.byref(out)))
+    if radii is None:
+        _check(lib.arp_structure_dsasa(_context(device)._h, structure._h, groups.encode(), C.c_float(probe_radius), int(n_points), int(model_num),
+                                       C.byref(out)))
+    else:
+        table = _radii_table(radii)
+        _check(lib.arp_structure_dsasa_radii(_context(device)._h, structure._h, groups.encode(), C.c_float(probe_radius), int(n_points), int(model_num),
+                                             table, C.byref(out)))
     return float(out.value)
 
 
-def dsasa(input_file: str, groups: str, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, num_threads: int = 1) -> float:
+def dsasa(input_file: str, groups: str, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, num_threads: int = 1, radii=None) -> float:
     """Drop-in for `arpeggia.dsasa` (python.rs:161-191)."""
     del num_threads
-    return get_dsasa(Structure.load(input_file), groups, probe_radius, n_points, model_num)
+    return get_dsasa(Structure.load(input_file), groups, probe_radius, n_points, model_num, radii=radii)
 
 
 # ---- shape complementarity (reference src/sc/, python.rs:369-381; include/arpeggia_amd.h "shape complementarity")
@@ -857,22 +1073,51 @@ def _ensemble_table(structure: Structure, r: dict, names: list):
     return _frame(cols)
 
 
-def _ensemble_run(structure: Structure, frames, chains: str, probe_radius: float, n_points: int, sap_radius, per_frame: bool, device: int) -> dict:
+def _ensemble_run(structure: Structure, frames, chains: str, probe_radius: float, n_points: int, sap_radius, per_frame: bool, device: int, radii=None) -> dict:
     try:
         ctx = _context(device)
     except ArpeggiaError:
-        _sasa_ensemble(None, structure, frames, chains, probe_radius, n_points, sap_radius, False)  # an input error takes precedence over the missing device
+        _sasa_ensemble(None, structure, frames, chains, probe_radius, n_points, sap_radius, False, radii)  # an input error takes precedence over the missing device
         raise
-    return ctx.sasa_ensemble(structure, frames, chains, probe_radius, n_points, sap_radius, per_frame)
+    return ctx.sasa_ensemble(structure, frames, chains, probe_radius, n_points, sap_radius, per_frame, radii)
+
+
+RESIDUE_ENSEMBLE_SASA_COLUMNS = ["chain", "resn", "resi", "insertion", "is_polar", "mean_sasa", "std_sasa", "min_sasa", "max_sasa", "mean_relative_sasa", "n_frames"]
+
+
+def get_residue_sasa_ensemble(structure: Structure, frames=None, chains: str = "", probe_radius: float = 1.4, n_points: int = 100, radii: str = "protor",
+                              per_frame: bool = False, device: int = 0):
+    """Residue-level SASA statistics over the frames of an ensemble, the per-atom values summed per residue and per chain on the device: one row
+    per residue of the selection (the rows and order of get_residue_sasa) with is_polar, mean_sasa, std_sasa (population), min_sasa, max_sasa,
+    mean_relative_sasa (mean_sasa / MaxASA, null without one) and n_frames (RESIDUE_ENSEMBLE_SASA_COLUMNS).  Returns (table, extras) with
+    extras = {"chains": the chain ids in get_chain_sasa's order, "chain_sasa": [F, n_chains] f32}; per_frame=True adds "residue_sasa": [F, n_res] f32."""
+    import pyarrow as pa
+
+    try:
+        ctx = _context(device)
+    except ArpeggiaError:
+        _residue_sasa_ensemble(None, structure, frames, chains, probe_radius, n_points, radii, False)  # an input error takes precedence over the missing device
+        raise
+    r = ctx.residue_sasa_ensemble(structure, frames, chains, probe_radius, n_points, radii, per_frame)
+    cols = _residue_identity(structure, r["res_atoms"])
+    cols["is_polar"] = pa.array(r["is_polar"], pa.bool_())
+    for k in ("mean_sasa", "std_sasa", "min_sasa", "max_sasa"):
+        cols[k] = pa.array(r[k], pa.float32())
+    cols["mean_relative_sasa"] = _nullable_f32(r["mean_relative_sasa"], r["relative_valid"])
+    cols["n_frames"] = pa.array(np.full(len(r["res_atoms"]), r["n_frames"], "<u4"), pa.uint32())
+    extras = {"chains": _strings(structure, "chain", r["chain_atoms"]), "chain_sasa": r["chain_sasa"]}
+    if per_frame:
+        extras["residue_sasa"] = r["residue_sasa"]
+    return _frame(cols), extras
 
 
 def get_sasa_ensemble(structure: Structure, frames=None, chains: str = "", probe_radius: float = 1.4, n_points: int = 100, per_frame: bool = False,
-                      device: int = 0):
+                      device: int = 0, radii=None):
     """Per-atom SASA statistics over the frames of an ensemble, frames packed on the device in one call: one row per selected heavy atom with
     the identity columns of get_atom_sasa, n_frames, mean_sasa, std_sasa (population), min_sasa, max_sasa (ENSEMBLE_SASA_COLUMNS).  frames:
     [F, N, 3] f64 coordinates of the N atoms of model 0; None: the structure's models are the frames.  per_frame=True returns (table, extras)
     with extras = {"total_sasa": [F] f32, "count": [F, m] i32 unburied points}."""
-    r = _ensemble_run(structure, frames, chains, probe_radius, n_points, None, per_frame, device)
+    r = _ensemble_run(structure, frames, chains, probe_radius, n_points, None, per_frame, device, radii)
     t = _ensemble_table(structure, r, ENSEMBLE_SASA_COLUMNS)
     return (t, {k: r[k] for k in ("total_sasa", "count")}) if per_frame else t
 
@@ -901,9 +1146,32 @@ def get_residue_sap_ensemble(structure: Structure, frames=None, chains: str = ""
     return _frame(out)
 
 
-def sasa_ensemble(input_file: str, probe_radius: float = 1.4, n_points: int = 100, chains: str = ""):
-    """SASA statistics across the models of a multi-model file (NMR models, MODEL-record snapshots): see get_sasa_ensemble."""
-    return get_sasa_ensemble(Structure.load(input_file), None, chains, probe_radius, n_points)
+def sasa_ensemble(input_file: str, probe_radius: float = 1.4, n_points: int = 100, chains: str = "", level: str = "atom", radii=None):
+    """SASA statistics across the models of a multi-model file (NMR models, MODEL-record snapshots): see get_sasa_ensemble.  With a named radius
+    table (radii "protor" / "vdw") level "residue" gives get_residue_sasa_ensemble's table and level "chain" one row per chain with the mean,
+    spread and extremes of its per-frame sums; without one only level "atom" is offered, as in sasa()."""
+    lv = str(level).lower()
+    if lv not in SASA_LEVELS:
+        raise ValueError(f"Invalid level '{level}'. Must be one of: 'atom', 'residue', 'chain'")
+    if radii is not None:
+        _radii_table(radii)
+    elif lv != "atom":
+        raise NotImplementedError(f"sasa level '{lv}' needs a named radius table: pass radii='protor' or radii='vdw'")
+    s = Structure.load(input_file)
+    if lv == "atom":
+        return get_sasa_ensemble(s, None, chains, probe_radius, n_points, radii=radii)
+    table, extras = get_residue_sasa_ensemble(s, None, chains, probe_radius, n_points, radii)
+    return table if lv == "residue" else _chain_ensemble_table(extras, len(extras["chain_sasa"]))
+
+
+def _chain_ensemble_table(extras: dict, n_frames: int):
+    """One row per chain from the per-frame chain sums: f64 statistics over the frames, rounded to f32 once."""
+    import pyarrow as pa
+
+    v = np.asarray(extras["chain_sasa"], np.float64).reshape(n_frames, len(extras["chains"]))
+    f32 = lambda a: pa.array(np.asarray(a, np.float64).astype(np.float32), pa.float32())  # noqa: E731
+    return _frame({"chain": pa.array(extras["chains"], pa.string()), "mean_sasa": f32(v.mean(0)), "std_sasa": f32(v.std(0)), "min_sasa": f32(v.min(0)),
+                   "max_sasa": f32(v.max(0)), "n_frames": pa.array(np.full(v.shape[1], n_frames, "<u4"), pa.uint32())})
 
 
 def sap_ensemble(input_file: str, level: str = "residue", probe_radius: float = 1.4, n_points: int = 100, sap_radius: float = 5.0, chains: str = ""):

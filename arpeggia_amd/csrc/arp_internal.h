@@ -232,6 +232,20 @@ void launch_ens_tile(uint32_t frames, const double *xyz, const EnsTopo &t, const
 // f32 of the f64 sum of sasa[f][:] in atom order for every frame of the pass
 void launch_ens_reduce(uint32_t frames, uint32_t m, const int32_t *count, const float *sasa, const float *sap, const EnsAcc &a, bool first, float *total,
                        hipStream_t st);
+// Segment sums (seg.inl).  All device pointers.
+struct SegCsr {           // n_seg segments over the items of a row: segment s lists item[start[s] .. start[s + 1]) in the order they are added
+    uint32_t n_seg, n_long;
+    const uint32_t *start, *item;
+    const uint32_t *long_ids;  // n_long: the segments with more than 64 items (the wave kernel's), ascending
+};
+// out[row][s] = f32 of the f64 sum of values[row][item] over segment s in list order (one __dadd_rn per item), rows x n_seg; values: rows x m
+void launch_segment_sum(uint64_t rows, uint32_t m, const float *values, const SegCsr &c, float *out, hipStream_t st);
+struct SegAcc {           // per residue, over all frames so far: sum and sum of squares of the per-frame f32 values (f64, frame order), extremes
+    double *t1, *t2;
+    float *vmin, *vmax;
+};
+// folds the pass's rs ([frame][n_res]) into the accumulators (first: they start with this pass)
+void launch_ens_res_reduce(uint32_t frames, uint32_t n_res, const float *rs, const SegAcc &a, bool first, hipStream_t st);
 // Shape complementarity (sc.inl).  Dot and probe records as the kernels write them; arp_sc_dots copies from the dots.
 struct ScDot {        // 80 B
     double p[3], n[3], area, nn_dist, score;

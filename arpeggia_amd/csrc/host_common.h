@@ -121,8 +121,20 @@ struct SasaJob {
     const uint32_t *res_code = nullptr;    // position in ARP_SAP_RESIDUES, >= 20: none
     const int32_t *src = nullptr;
     float sap_radius = 0.0f;
+    // segment sums of the SASA values on the device (seg.inl), in the same stream: residue and chain level
+    const struct SegJob *segs = nullptr;
+    uint32_t n_segs = 0;
 };
-// sasa / count / sap (nullable) receive n entries; one synchronisation at the end.  Inputs are checked by the callers.
+// One CSR over the atoms of a job / the selected atoms of an ensemble (arp_segment_sum's contract; checked by seg_check) and where its sums go.
+struct SegJob {
+    uint32_t n_seg = 0;
+    const uint32_t *start = nullptr, *item = nullptr;  // n_seg + 1, start[n_seg]
+    float *out = nullptr;                  // n_seg (sasa_run); unused by ens_run
+};
+// ARP_ERR_BAD_INPUT + message unless start is monotone from 0, below 2^31 - 64, and every item is below m
+arp_status seg_check(uint64_t m, uint64_t n_seg, const uint32_t *start, const uint32_t *item);
+// sasa / count / sap (nullable) receive n entries; one synchronisation at the end.  Inputs are checked by the callers.  With all three null
+// only the segment sums come back.
 arp_status sasa_run(arp_context *ctx, const SasaJob &job, float *sasa, int32_t *count, float *sap);
 // SASA / SAP statistics over the frames of an ensemble (arp_sasa_ensemble): sasa_dev.cpp ens_run packs the frames into
 // passes and runs them (kernels in ens.inl + the unchanged SASA / SAP kernels); sasa.cpp selects, checks and finishes.  Host arrays.
@@ -138,6 +150,7 @@ struct EnsJob {
     const uint32_t *res_code = nullptr;    // m (SAP): position in ARP_SAP_RESIDUES, >= 20: none
     float sap_radius = 0.0f;
     uint64_t chunk_atoms = 0;              // packed atoms per pass, 0: automatic
+    const SegJob *res = nullptr, *chain = nullptr;  // residue level (arp_sasa_ensemble_residues): the CSRs over the m selected atoms, both or none
 };
 struct EnsOut {                            // m entries each unless noted; the SAP members are written only with EnsJob::with_sap
     unsigned long long *s1 = nullptr, *s2 = nullptr;
@@ -147,6 +160,12 @@ struct EnsOut {                            // m entries each unless noted; the S
     float *total = nullptr;                // n_frames
     int32_t *count = nullptr;              // n_frames x m, nullable
     float *sap = nullptr;                  // n_frames x m, nullable
+    // with EnsJob::res: per residue the f64 sums of the per-frame residue SASA and of its square (frame order) and the extremes; per frame the
+    // chain sums; the per-frame residue values only when asked for
+    double *rt1 = nullptr, *rt2 = nullptr;
+    float *rmin = nullptr, *rmax = nullptr;
+    float *chain_sasa = nullptr;           // n_frames x chain->n_seg
+    float *residue_sasa = nullptr;         // n_frames x res->n_seg, nullable
 };
 arp_status ens_run(arp_context *ctx, const EnsJob &job, const EnsOut &out);
 // table.cpp: model 0 of a structure as the topology of an ensemble (n0 atoms, r0 residues); with frames_from_models every further model must

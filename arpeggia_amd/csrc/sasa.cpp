@@ -1,8 +1,8 @@
-// Structure-level atom SASA, SAP score and dSASA (reference src/sasa.rs:27-451, src/sap.rs:137-259): the atom selection of
-// prepare_pdb_for_sasa + filter_pdb_by_model on the parsed structure, then one device run (sasa_dev.cpp sasa_run, kernels in sasa.inl).
-// Residue- and chain-level SASA (get_residue_sasa / get_chain_sasa, relative_sasa) are NOT here: the reference computes them through
-// rust-sasa's SASAOptions, whose own radius table (with a van-der-Waals fallback) is not part of the reference's tree -- those levels would
-// be a guess.  dSASA, chain-level in the reference, is built from atom-level SASA instead (arpeggia_amd.h arp_structure_dsasa).
+// Structure-level SASA (atom, residue, chain, relative), SAP score and dSASA (reference src/sasa.rs:27-561, src/sap.rs:137-259): the atom
+// selection of prepare_pdb_for_sasa + filter_pdb_by_model on the parsed structure, then one device run (sasa_dev.cpp sasa_run, kernels in
+// sasa.inl and seg.inl).  The reference computes the residue and chain levels through rust-sasa's SASAOptions with a radius table of its own;
+// here the table is named by the caller (ARP_RADII_PROTOR: the table that reproduces the reference's chain-level pin).
+// dSASA, chain-level in the reference, is built from atom-level SASA (arpeggia_amd.h arp_structure_dsasa).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -77,15 +77,88 @@ static bool is_backbone(const char *name) {  // pdbtbx Atom::is_backbone (not in
     return !strcmp(name, "N") || !strcmp(name, "CA") || !strcmp(name, "C") || !strcmp(name, "O") || !strcmp(name, "OXT");
 }
 
-// Radius + probe of every structure atom (f32: sasa.rs:200-206 casts van_der_waals to f32, rust-sasa adds the probe in f32)
-static arp_status radii(const arp_structure *s, const std::vector<uint32_t> &atoms, float probe, std::vector<float> *R) {
+// ---- radius tables -------------------------------------------------------------------------------------------
+// ARP_RADII_PROTOR: the ProtOr radii of Tsai, Taylor, Chothia & Gerstein 1999 by (residue, atom name), as FreeSASA lists them -- the table
+// rust-sasa is believed to embed: with it the chain-level total of 1ubq is the reference's own pin (sasa.rs test_sasa_regression_ubiquitin).
+namespace {
+constexpr float C3H0 = 1.61f, C3H1 = 1.76f, C4H1 = 1.88f, C4H2 = 1.88f, C4H3 = 1.88f, N3H0 = 1.64f, N3H1 = 1.64f, N3H2 = 1.64f, N4H3 = 1.64f,
+                O1H0 = 1.42f, O2H1 = 1.46f, S2H0 = 1.77f, S2H1 = 1.77f;
+struct ProtorRow { const char *resn, *atom; float r; };
+const ProtorRow ARP_PROTOR[] = {
+    {"ANY", "N", N3H1}, {"ANY", "CA", C4H1}, {"ANY", "C", C3H0}, {"ANY", "O", O1H0}, {"ANY", "CB", C4H2}, {"ANY", "OXT", O2H1},
+    {"ALA", "CB", C4H3},
+    {"ARG", "CG", C4H2}, {"ARG", "CD", C4H2}, {"ARG", "NE", N3H1}, {"ARG", "CZ", C3H0}, {"ARG", "NH1", N3H2}, {"ARG", "NH2", N3H2},
+    {"ASN", "CG", C3H0}, {"ASN", "OD1", O1H0}, {"ASN", "ND2", N3H2},
+    {"ASP", "CG", C3H0}, {"ASP", "OD1", O1H0}, {"ASP", "OD2", O1H0},
+    {"CYS", "SG", S2H1},
+    {"GLN", "CG", C4H2}, {"GLN", "CD", C3H0}, {"GLN", "OE1", O1H0}, {"GLN", "NE2", N3H2},
+    {"GLU", "CG", C4H2}, {"GLU", "CD", C3H0}, {"GLU", "OE1", O1H0}, {"GLU", "OE2", O1H0},
+    {"GLY", "CA", C4H2},
+    {"HIS", "CG", C3H0}, {"HIS", "ND1", N3H1}, {"HIS", "CD2", C3H1}, {"HIS", "NE2", N3H1}, {"HIS", "CE1", C3H1},
+    {"ILE", "CB", C4H1}, {"ILE", "CG1", C4H2}, {"ILE", "CG2", C4H3}, {"ILE", "CD1", C4H3},
+    {"LEU", "CG", C4H1}, {"LEU", "CD1", C4H3}, {"LEU", "CD2", C4H3},
+    {"LYS", "CG", C4H2}, {"LYS", "CD", C4H2}, {"LYS", "CE", C4H2}, {"LYS", "NZ", N4H3},
+    {"MET", "CG", C4H2}, {"MET", "SD", S2H0}, {"MET", "CE", C4H3},
+    {"PHE", "CG", C3H0}, {"PHE", "CD1", C3H1}, {"PHE", "CD2", C3H1}, {"PHE", "CE1", C3H1}, {"PHE", "CE2", C3H1}, {"PHE", "CZ", C3H1},
+    {"PRO", "N", N3H0}, {"PRO", "CG", C4H2}, {"PRO", "CD", C4H2},
+    {"SER", "OG", O2H1},
+    {"THR", "CB", C4H1}, {"THR", "OG1", O2H1}, {"THR", "CG2", C4H3},
+    {"TRP", "CG", C3H0}, {"TRP", "CD2", C3H0}, {"TRP", "CE2", C3H0}, {"TRP", "CD1", C3H1}, {"TRP", "CE3", C3H1}, {"TRP", "CZ2", C3H1},
+    {"TRP", "CZ3", C3H1}, {"TRP", "CH2", C3H1}, {"TRP", "NE1", N3H1},
+    {"TYR", "CG", C3H0}, {"TYR", "CZ", C3H0}, {"TYR", "CD1", C3H1}, {"TYR", "CD2", C3H1}, {"TYR", "CE1", C3H1}, {"TYR", "CE2", C3H1}, {"TYR", "OH", O2H1},
+    {"VAL", "CB", C4H1}, {"VAL", "CG1", C4H3}, {"VAL", "CG2", C4H3},
+};
+// Tien et al. 2013 (theoretical MaxASA of Gly-X-Gly), the values of the reference's get_max_asa (sasa.rs:460-483)
+struct MaxAsaRow { const char *resn; float v; };
+const MaxAsaRow kMaxAsa[] = {{"ALA", 129.0f}, {"ARG", 274.0f}, {"ASN", 195.0f}, {"ASP", 193.0f}, {"CYS", 167.0f}, {"GLU", 223.0f}, {"GLN", 225.0f},
+                             {"GLY", 104.0f}, {"HIS", 224.0f}, {"MET", 224.0f}, {"ILE", 197.0f}, {"LEU", 201.0f}, {"LYS", 236.0f}, {"PHE", 240.0f},
+                             {"PRO", 159.0f}, {"SER", 155.0f}, {"THR", 172.0f}, {"TRP", 285.0f}, {"TYR", 263.0f}, {"VAL", 174.0f}};
+// ASSUMPTION: rust-sasa's own list of polar residues is not part of the reference's tree, and the reference only tests that the column
+// exists.  These are the residues with a charged or hydrogen-bonding side chain.
+const char *const kPolar[] = {"ARG", "ASN", "ASP", "GLN", "GLU", "HIS", "LYS", "SER", "THR", "TYR"};
+
+void upper(const char *in, char (&up)[8]) {
+    memset(up, 0, sizeof up);
+    for (int k = 0; k < 7 && in && in[k]; k++) up[k] = (char)toupper((unsigned char)in[k]);
+}
+const ProtorRow *protor_find(const char *resn, const char *atomn) {
+    for (const ProtorRow &r : ARP_PROTOR) if (!strcmp(r.resn, resn) && !strcmp(r.atom, atomn)) return &r;
+    return nullptr;
+}
+}  // namespace
+
+// The radius of one atom in f32.  vdw: the element's van der Waals radius (arp_params.vdw_radius), what every SASA entry point used before the
+// tables had names.  protor: (residue, atom name), then (ANY, atom name), then -- ASSUMPTION: with_allow_vdw_fallback(true) falls back to an
+// element table of rust-sasa's that is not on disk -- the same van der Waals radius.  fell_back (nullable) says that the fallback was taken.
+static arp_status sasa_radius(const char *resn, const char *atomn, int32_t elem_class, int32_t table, float *out, bool *fell_back = nullptr) {
+    if (table != ARP_RADII_VDW && table != ARP_RADII_PROTOR) { set_error("unknown radius table %d (ARP_RADII_VDW = 0, ARP_RADII_PROTOR = 1)", (int)table); return ARP_ERR_BAD_INPUT; }
+    if (fell_back) *fell_back = false;
+    if (table == ARP_RADII_PROTOR) {
+        char up[8];
+        upper(resn, up);
+        const ProtorRow *r = protor_find(up, atomn ? atomn : "");
+        if (!r) r = protor_find("ANY", atomn ? atomn : "");
+        if (r) { *out = r->r; return ARP_OK; }
+        if (fell_back) *fell_back = true;
+    }
     arp_params p;
     arp_default_params(&p);
+    const double vdw = elem_class >= 0 && elem_class < 16 ? p.vdw_radius[elem_class] : 0.0;
+    if (!(vdw > 0.0)) { set_error("the element has no van der Waals radius"); return ARP_ERR_BAD_INPUT; }
+    *out = (float)vdw;
+    return ARP_OK;
+}
+
+// Radius + probe of every structure atom (f32: sasa.rs:200-206 casts van_der_waals to f32, rust-sasa adds the probe in f32)
+static arp_status radii(const arp_structure *s, const std::vector<uint32_t> &atoms, float probe, std::vector<float> *R, int32_t table = ARP_RADII_VDW) {
     R->assign(s->n, 0.0f);
     for (uint32_t i : atoms) {
-        const double vdw = p.vdw_radius[s->base_attr[i] & ARP_ATTR_ELEM_MASK];
-        if (!(vdw > 0.0)) { set_error("atom %d: element '%s' has no van der Waals radius (the reference unwraps None, sasa.rs:201-206)", s->serial[i], s->elem.at(i)); return ARP_ERR_BAD_INPUT; }
-        (*R)[i] = (float)vdw + probe;
+        float r = 0.0f;
+        if (sasa_radius(s->res_resn.at(i), s->name.at(i), (int32_t)(s->base_attr[i] & ARP_ATTR_ELEM_MASK), table, &r) != ARP_OK) {
+            if (table != ARP_RADII_VDW && table != ARP_RADII_PROTOR) return ARP_ERR_BAD_INPUT;
+            set_error("atom %d: element '%s' has no van der Waals radius (the reference unwraps None, sasa.rs:201-206)", s->serial[i], s->elem.at(i)); return ARP_ERR_BAD_INPUT;
+        }
+        (*R)[i] = r + probe;
     }
     return ARP_OK;
 }
@@ -107,15 +180,22 @@ extern "C" arp_status arp_structure_sasa_select(const arp_structure *s, const ch
     return ARP_OK;
 } ARP_ABI_CATCH
 
-extern "C" arp_status arp_structure_atom_sasa(arp_context *ctx, const arp_structure *s, const char *chains, int32_t model_num, int32_t remove_hydrogens,
-                                              float probe, int32_t n_points, uint64_t *n_rows, uint32_t *out_atoms, float *out_sasa, int32_t *out_count) try {
+static arp_status check_table(int32_t table) {
+    if (table == ARP_RADII_VDW || table == ARP_RADII_PROTOR) return ARP_OK;
+    set_error("unknown radius table %d (ARP_RADII_VDW = 0, ARP_RADII_PROTOR = 1)", (int)table);
+    return ARP_ERR_BAD_INPUT;
+}
+
+static arp_status atom_sasa_impl(arp_context *ctx, const arp_structure *s, const char *chains, int32_t model_num, int32_t remove_hydrogens, float probe,
+                                 int32_t n_points, int32_t table, uint64_t *n_rows, uint32_t *out_atoms, float *out_sasa, int32_t *out_count) {
     if (!ctx || !s || !n_rows || !out_atoms || !out_sasa) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
     arp_status st = sasa_check_params(probe, n_points);
     if (st != ARP_OK) return st;
+    if ((st = check_table(table)) != ARP_OK) return st;
     *n_rows = 0;
     std::vector<uint32_t> sel = select_atoms(s, chain_set(chains), remove_hydrogens != 0, true, true, model_num);
     std::vector<float> R;
-    if ((st = radii(s, sel, probe, &R)) != ARP_OK) return st;
+    if ((st = radii(s, sel, probe, &R, table)) != ARP_OK) return st;
     // the job runs over the selected atoms only (compact arrays)
     const uint64_t m = sel.size();
     std::vector<double> x(m), y(m), z(m);
@@ -136,6 +216,17 @@ extern "C" arp_status arp_structure_atom_sasa(arp_context *ctx, const arp_struct
     }
     *n_rows = m;
     return ARP_OK;
+}
+
+extern "C" arp_status arp_structure_atom_sasa(arp_context *ctx, const arp_structure *s, const char *chains, int32_t model_num, int32_t remove_hydrogens,
+                                              float probe, int32_t n_points, uint64_t *n_rows, uint32_t *out_atoms, float *out_sasa, int32_t *out_count) try {
+    return atom_sasa_impl(ctx, s, chains, model_num, remove_hydrogens, probe, n_points, ARP_RADII_VDW, n_rows, out_atoms, out_sasa, out_count);
+} ARP_ABI_CATCH
+
+extern "C" arp_status arp_structure_atom_sasa_radii(arp_context *ctx, const arp_structure *s, const char *chains, int32_t model_num, int32_t remove_hydrogens,
+                                                    float probe, int32_t n_points, int32_t table, uint64_t *n_rows, uint32_t *out_atoms, float *out_sasa,
+                                                    int32_t *out_count) try {
+    return atom_sasa_impl(ctx, s, chains, model_num, remove_hydrogens, probe, n_points, table, n_rows, out_atoms, out_sasa, out_count);
 } ARP_ABI_CATCH
 
 extern "C" arp_status arp_structure_sap_score(arp_context *ctx, const arp_structure *s, const char *chains, int32_t model_num, float probe,
@@ -197,11 +288,12 @@ extern "C" arp_status arp_structure_sap_score(arp_context *ctx, const arp_struct
     return ARP_OK;
 } ARP_ABI_CATCH
 
-extern "C" arp_status arp_structure_dsasa(arp_context *ctx, const arp_structure *s, const char *groups, float probe, int32_t n_points, int32_t model_num,
-                                          float *out) try {
+static arp_status dsasa_impl(arp_context *ctx, const arp_structure *s, const char *groups, float probe, int32_t n_points, int32_t model_num, int32_t table,
+                             float *out) {
     if (!ctx || !s || !groups || !out) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
     arp_status st = sasa_check_params(probe, n_points);
     if (st != ARP_OK) return st;
+    if ((st = check_table(table)) != ARP_OK) return st;
     std::vector<std::string> g1, g2;
     if ((st = parse_groups(s->chain_ids, groups, &g1, &g2)) != ARP_OK) return st;  // utils.rs:71-115 (sasa.rs:411)
     std::unordered_set<std::string> k1(g1.begin(), g1.end()), k2(g2.begin(), g2.end()), kc = k1;
@@ -214,7 +306,7 @@ extern "C" arp_status arp_structure_dsasa(arp_context *ctx, const arp_structure 
     std::vector<uint32_t> model;
     for (int g = 0; g < 3; g++) {
         std::vector<float> Rg;
-        if ((st = radii(s, sets[g], probe, &Rg)) != ARP_OK) return st;
+        if ((st = radii(s, sets[g], probe, &Rg, table)) != ARP_OK) return st;
         for (uint32_t i : sets[g]) { x.push_back(s->x[i]); y.push_back(s->y[i]); z.push_back(s->z[i]); R.push_back(Rg[i]); model.push_back((uint32_t)g); }
     }
     const uint64_t m = x.size();
@@ -232,6 +324,142 @@ extern "C" arp_status arp_structure_dsasa(arp_context *ctx, const arp_structure 
     *out = g1_total + g2_total - complex_total;  // sasa.rs:450 (f32)
     if (*out < 0.0f) { set_error("Negative dSASA calculated. Please check the input file and chain groups."); return ARP_ERR_BAD_INPUT; }
     return ARP_OK;
+}
+
+extern "C" arp_status arp_structure_dsasa(arp_context *ctx, const arp_structure *s, const char *groups, float probe, int32_t n_points, int32_t model_num,
+                                          float *out) try {
+    return dsasa_impl(ctx, s, groups, probe, n_points, model_num, ARP_RADII_VDW, out);
+} ARP_ABI_CATCH
+
+extern "C" arp_status arp_structure_dsasa_radii(arp_context *ctx, const arp_structure *s, const char *groups, float probe, int32_t n_points, int32_t model_num,
+                                                int32_t table, float *out) try {
+    return dsasa_impl(ctx, s, groups, probe, n_points, model_num, table, out);
+} ARP_ABI_CATCH
+
+// ---- radius and residue tables over the C ABI ---------------------------------------------------------------------------------------------
+extern "C" arp_status arp_sasa_radius(const char *resn, const char *atomn, const char *element, int32_t table, float *out) try {
+    if (!out) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    return sasa_radius(resn ? resn : "", atomn ? atomn : "", element ? arp_element_class(element) : -1, table, out);
+} ARP_ABI_CATCH
+
+extern "C" float arp_max_asa(const char *resn) {
+    char up[8];
+    upper(resn, up);
+    for (const MaxAsaRow &r : kMaxAsa) if (!strcmp(r.resn, up)) return r.v;
+    return 0.0f;
+}
+
+extern "C" int32_t arp_residue_is_polar(const char *resn) {
+    char up[8];
+    upper(resn, up);
+    for (const char *r : kPolar) if (!strcmp(r, up)) return 1;
+    return 0;
+}
+
+// ---- residue- and chain-level SASA (sasa.rs:284-382, 520-561) ----------------------------------------------------------
+namespace {
+// The segments of a selection, in row order: per residue (the ingest's residue id: chain, resi, insertion), rows sorted stably by (chain as a
+// byte string, resi, insertion); or per chain id, sorted.  Items are positions in `sel`, in selection order.  first[r]: the structure atom the
+// row takes its identity from (the first selected atom of the segment).
+struct Segments { std::vector<uint32_t> start, item, first; };
+Segments build_segments(const arp_structure *s, const std::vector<uint32_t> &sel, bool by_chain) {
+    std::vector<std::vector<uint32_t>> groups;
+    if (by_chain) {
+        std::unordered_map<std::string, uint32_t> at;
+        for (uint32_t k = 0; k < sel.size(); k++) {
+            auto it = at.emplace(s->chain.str(sel[k]), (uint32_t)groups.size());
+            if (it.second) groups.emplace_back();
+            groups[it.first->second].push_back(k);
+        }
+    } else {
+        std::unordered_map<uint32_t, uint32_t> at;
+        for (uint32_t k = 0; k < sel.size(); k++) {
+            auto it = at.emplace(s->res_id[sel[k]], (uint32_t)groups.size());
+            if (it.second) groups.emplace_back();
+            groups[it.first->second].push_back(k);
+        }
+    }
+    std::vector<uint32_t> order(groups.size());
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        const uint32_t i = sel[groups[a][0]], j = sel[groups[b][0]];
+        const int c = s->chain.str(i).compare(s->chain.str(j));
+        if (c || by_chain) return c < 0;
+        if (s->resi[i] != s->resi[j]) return s->resi[i] < s->resi[j];
+        return s->icode.str(i).compare(s->icode.str(j)) < 0;
+    });
+    Segments g;
+    g.start.push_back(0u);
+    for (uint32_t r : order) {
+        g.first.push_back(sel[groups[r][0]]);
+        g.item.insert(g.item.end(), groups[r].begin(), groups[r].end());
+        g.start.push_back((uint32_t)g.item.size());
+    }
+    return g;
+}
+
+// One device run over the selection (steps 1-4, hydrogens out) with the table's radii; the per-atom values are summed on the device and only
+// the sums come back.  Writes the rows of one level.
+arp_status level_sasa(arp_context *ctx, const arp_structure *s, const char *chains, int32_t model_num, float probe, int32_t n_points, int32_t table,
+                      bool by_chain, uint64_t *n_rows, uint32_t *out_atoms, float *out_sasa) {
+    if (!ctx || !s || !n_rows || !out_atoms || !out_sasa) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    arp_status st = sasa_check_params(probe, n_points);
+    if (st != ARP_OK) return st;
+    if ((st = check_table(table)) != ARP_OK) return st;
+    *n_rows = 0;
+    const std::vector<uint32_t> sel = select_atoms(s, chain_set(chains), true, true, false, model_num);  // no serial filter: sasa.rs:294-295
+    std::vector<float> R;
+    if ((st = radii(s, sel, probe, &R, table)) != ARP_OK) return st;
+    const uint64_t m = sel.size();
+    if (m == 0) return ARP_OK;
+    const Segments g = build_segments(s, sel, by_chain);
+    std::vector<double> x(m), y(m), z(m);
+    std::vector<float> Rm(m), sphere(3ull * (uint32_t)n_points);
+    std::vector<uint8_t> inc(m, 1);
+    for (uint64_t k = 0; k < m; k++) { const uint32_t i = sel[k]; x[k] = s->x[i]; y[k] = s->y[i]; z[k] = s->z[i]; Rm[k] = R[i]; }
+    sasa_sphere_points((uint32_t)n_points, sphere.data());
+    SegJob sj;
+    sj.n_seg = (uint32_t)g.first.size(); sj.start = g.start.data(); sj.item = g.item.data(); sj.out = out_sasa;
+    SasaJob j;
+    j.n = m; j.x = x.data(); j.y = y.data(); j.z = z.data(); j.R = Rm.data(); j.include = inc.data(); j.n_points = (uint32_t)n_points; j.sphere = sphere.data();
+    j.segs = &sj; j.n_segs = 1;
+    if ((st = sasa_run(ctx, j, nullptr, nullptr, nullptr)) != ARP_OK) return st;
+    std::copy(g.first.begin(), g.first.end(), out_atoms);
+    *n_rows = g.first.size();
+    return ARP_OK;
+}
+void residue_columns(const arp_structure *s, uint64_t n, const uint32_t *atoms, const float *sasa, uint8_t *is_polar, float *relative, uint8_t *valid) {
+    for (uint64_t r = 0; r < n; r++) {
+        const char *resn = s->res_resn.at(atoms[r]);
+        if (is_polar) is_polar[r] = (uint8_t)arp_residue_is_polar(resn);
+        if (relative) {
+            const float mx = arp_max_asa(resn);
+            valid[r] = mx > 0.0f;
+            relative[r] = mx > 0.0f ? sasa[r] / mx : NAN;  // sasa.rs:547
+        }
+    }
+}
+}  // namespace
+
+extern "C" arp_status arp_structure_residue_sasa(arp_context *ctx, const arp_structure *s, const char *chains, int32_t model_num, float probe, int32_t n_points,
+                                                 int32_t table, uint64_t *n_rows, uint32_t *out_atoms, float *out_sasa, uint8_t *out_is_polar) try {
+    const arp_status st = level_sasa(ctx, s, chains, model_num, probe, n_points, table, false, n_rows, out_atoms, out_sasa);
+    if (st == ARP_OK) residue_columns(s, *n_rows, out_atoms, out_sasa, out_is_polar, nullptr, nullptr);
+    return st;
+} ARP_ABI_CATCH
+
+extern "C" arp_status arp_structure_chain_sasa(arp_context *ctx, const arp_structure *s, const char *chains, int32_t model_num, float probe, int32_t n_points,
+                                               int32_t table, uint64_t *n_rows, uint32_t *out_atoms, float *out_sasa) try {
+    return level_sasa(ctx, s, chains, model_num, probe, n_points, table, true, n_rows, out_atoms, out_sasa);
+} ARP_ABI_CATCH
+
+extern "C" arp_status arp_structure_relative_sasa(arp_context *ctx, const arp_structure *s, const char *chains, int32_t model_num, float probe, int32_t n_points,
+                                                  int32_t table, uint64_t *n_rows, uint32_t *out_atoms, float *out_sasa, uint8_t *out_is_polar,
+                                                  float *out_relative, uint8_t *out_valid) try {
+    if (!out_relative || !out_valid) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    const arp_status st = level_sasa(ctx, s, chains, model_num, probe, n_points, table, false, n_rows, out_atoms, out_sasa);
+    if (st == ARP_OK) residue_columns(s, *n_rows, out_atoms, out_sasa, out_is_polar, out_relative, out_valid);
+    return st;
 } ARP_ABI_CATCH
 
 // ---- SASA / SAP statistics over the frames of an ensemble (device path: sasa_dev.cpp ens_run, ens.inl) ----------------
@@ -259,12 +487,67 @@ extern "C" arp_status arp_sasa_ensemble_stats(uint64_t n_frames, uint64_t m, con
     return ARP_OK;
 } ARP_ABI_CATCH
 
-extern "C" arp_status arp_sasa_ensemble(arp_context *ctx, const arp_structure *s, uint64_t n_frames, const double *xyz, const char *chains, float probe,
-                                        int32_t n_points, int32_t with_sap, float sap_radius, uint64_t *n_rows, uint64_t *frames_used, uint32_t *out_atoms,
-                                        float *mean_sasa, float *std_sasa, float *min_sasa, float *max_sasa, float *mean_sap, float *std_sap, float *min_sap,
-                                        float *max_sap, float *total_sasa, int32_t *out_count, float *out_sap) try {
-    if (!s || !n_rows || !frames_used) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+namespace {
+struct ResidueEnsOut {  // arp_sasa_ensemble_residues: its outputs, filled instead of the per-atom ones
+    uint64_t *n_chains;
+    uint32_t *res_atoms, *chain_atoms;
+    uint8_t *is_polar, *relative_valid;
+    float *mean, *sd, *vmin, *vmax, *mean_relative, *chain_sasa, *residue_sasa;
+};
+}  // namespace
+
+// The residue level of the ensemble path once the inputs have been checked: sel (m atoms of the topology, ascending), their R, F frames.
+static arp_status residue_ensemble(arp_context *ctx, const arp_structure *s, const std::vector<uint32_t> &sel, const std::vector<float> &R, uint64_t F, uint64_t n0,
+                                   const double *frames, float probe, int32_t n_points, const ResidueEnsOut &ro, uint64_t *n_rows) {
+    (void)probe;
+    const uint64_t m = sel.size();
+    const Segments res = build_segments(s, sel, false), chn = build_segments(s, sel, true);
+    const uint64_t nr = res.first.size(), nc = chn.first.size();
+    if (ro.res_atoms) std::copy(res.first.begin(), res.first.end(), ro.res_atoms);
+    if (ro.chain_atoms) std::copy(chn.first.begin(), chn.first.end(), ro.chain_atoms);
+    *ro.n_chains = nc;
+    if (!ctx) { *n_rows = nr; return ARP_OK; }  // validation only: the rows, the chains and the frame count
+    if (!ro.res_atoms || !ro.chain_atoms || !ro.is_polar || !ro.relative_valid || !ro.mean || !ro.sd || !ro.vmin || !ro.vmax || !ro.mean_relative || !ro.chain_sasa) {
+        set_error("null argument");
+        return ARP_ERR_BAD_INPUT;
+    }
+    if (m == 0) return ARP_OK;  // an empty selection: no rows, no chains
+    std::vector<float> Rm(m), sphere(3ull * (uint32_t)n_points), total(F);
+    for (uint64_t k = 0; k < m; k++) Rm[k] = R[sel[k]];
+    sasa_sphere_points((uint32_t)n_points, sphere.data());
+    SegJob rj, cj;
+    rj.n_seg = (uint32_t)nr; rj.start = res.start.data(); rj.item = res.item.data();
+    cj.n_seg = (uint32_t)nc; cj.start = chn.start.data(); cj.item = chn.item.data();
+    EnsJob j;
+    j.n_top = n0; j.m = m; j.n_frames = F; j.xyz = frames; j.sel = sel.data(); j.R = Rm.data(); j.n_points = (uint32_t)n_points; j.sphere = sphere.data();
+    j.chunk_atoms = g_debug.ens_chunk_atoms > 0 ? (uint64_t)g_debug.ens_chunk_atoms : 0u;
+    j.res = &rj; j.chain = &cj;
+    std::vector<unsigned long long> s1(m), s2(m);
+    std::vector<int32_t> cmin(m), cmax(m);
+    std::vector<double> t1(nr), t2(nr);
+    EnsOut o;
+    o.s1 = s1.data(); o.s2 = s2.data(); o.cmin = cmin.data(); o.cmax = cmax.data(); o.total = total.data();
+    o.rt1 = t1.data(); o.rt2 = t2.data(); o.rmin = ro.vmin; o.rmax = ro.vmax; o.chain_sasa = ro.chain_sasa; o.residue_sasa = ro.residue_sasa;
+    const arp_status st = ens_run(ctx, j, o);
+    if (st != ARP_OK) return st;
+    const double Fd = (double)F;
+    for (uint64_t r = 0; r < nr; r++) {  // as arp_sasa_ensemble_stats finishes SAP
+        const double mu = t1[r] / Fd, var = t2[r] / Fd - mu * mu;
+        ro.mean[r] = (float)mu;
+        ro.sd[r] = (float)std::sqrt(var > 0.0 ? var : 0.0);
+    }
+    residue_columns(s, nr, ro.res_atoms, ro.mean, ro.is_polar, ro.mean_relative, ro.relative_valid);
+    *n_rows = nr;
+    return ARP_OK;
+}
+
+static arp_status sasa_ensemble_impl(arp_context *ctx, const arp_structure *s, uint64_t n_frames, const double *xyz, const char *chains, float probe,
+                                     int32_t n_points, int32_t with_sap, float sap_radius, int32_t table, const ResidueEnsOut *ro, uint64_t *n_rows,
+                                     uint64_t *frames_used, uint32_t *out_atoms, float *mean_sasa, float *std_sasa, float *min_sasa, float *max_sasa,
+                                     float *mean_sap, float *std_sap, float *min_sap, float *max_sap, float *total_sasa, int32_t *out_count, float *out_sap) {
+    if (!s || !n_rows || !frames_used || (ro && !ro->n_chains)) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
     *n_rows = 0; *frames_used = 0;
+    if (ro) *ro->n_chains = 0;
     // validation: nothing here touches the device
     uint64_t n0 = 0, r0 = 0, nm = 1;
     arp_status st = freq_topology(s, xyz == nullptr, &n0, &r0, &nm);
@@ -276,12 +559,13 @@ extern "C" arp_status arp_sasa_ensemble(arp_context *ctx, const arp_structure *s
     if ((st = sasa_check_params(probe, n_points)) != ARP_OK) return st;
     if (with_sap && !(sap_radius >= 0.0f)) { set_error("bad sap_radius"); return ARP_ERR_BAD_INPUT; }
     if (!with_sap && out_sap) { set_error("sasa ensemble: out_sap needs with_sap"); return ARP_ERR_BAD_INPUT; }
+    if ((st = check_table(table)) != ARP_OK) return st;
     // steps 1-3 of arp_structure_sasa_select on model 0's atoms (the prefix [0, n0) of the structure)
     std::vector<uint32_t> sel = select_atoms(s, chain_set(chains), true, false, false, 0);
     while (!sel.empty() && sel.back() >= n0) sel.pop_back();  // (ascending)
     const uint64_t m = sel.size();
     std::vector<float> R;
-    if ((st = radii(s, sel, probe, &R)) != ARP_OK) return st;
+    if ((st = radii(s, sel, probe, &R, table)) != ARP_OK) return st;
     std::vector<double> model_xyz;
     if (!xyz) {  // the models' coordinates as F x n0 x 3
         model_xyz.resize(F * n0 * 3);
@@ -296,8 +580,9 @@ extern "C" arp_status arp_sasa_ensemble(arp_context *ctx, const arp_structure *s
                 return ARP_ERR_BAD_INPUT;
             }
         }
-    if (out_atoms) std::copy(sel.begin(), sel.end(), out_atoms);
     *frames_used = F;
+    if (ro) return residue_ensemble(ctx, s, sel, R, F, n0, frames, probe, n_points, *ro, n_rows);
+    if (out_atoms) std::copy(sel.begin(), sel.end(), out_atoms);
     if (!ctx) { *n_rows = m; return ARP_OK; }  // validation only: the selection and the frame count
     if (!out_atoms || !mean_sasa || !std_sasa || !min_sasa || !max_sasa || !total_sasa || (with_sap && (!mean_sap || !std_sap || !min_sap || !max_sap))) {
         set_error("null argument");
@@ -331,4 +616,30 @@ extern "C" arp_status arp_sasa_ensemble(arp_context *ctx, const arp_structure *s
                                       with_sap ? mean_sap : nullptr, with_sap ? std_sap : nullptr)) != ARP_OK) return st;
     *n_rows = m;
     return ARP_OK;
+}
+
+extern "C" arp_status arp_sasa_ensemble(arp_context *ctx, const arp_structure *s, uint64_t n_frames, const double *xyz, const char *chains, float probe,
+                                        int32_t n_points, int32_t with_sap, float sap_radius, uint64_t *n_rows, uint64_t *frames_used, uint32_t *out_atoms,
+                                        float *mean_sasa, float *std_sasa, float *min_sasa, float *max_sasa, float *mean_sap, float *std_sap, float *min_sap,
+                                        float *max_sap, float *total_sasa, int32_t *out_count, float *out_sap) try {
+    return sasa_ensemble_impl(ctx, s, n_frames, xyz, chains, probe, n_points, with_sap, sap_radius, ARP_RADII_VDW, nullptr, n_rows, frames_used, out_atoms,
+                              mean_sasa, std_sasa, min_sasa, max_sasa, mean_sap, std_sap, min_sap, max_sap, total_sasa, out_count, out_sap);
+} ARP_ABI_CATCH
+
+extern "C" arp_status arp_sasa_ensemble_radii(arp_context *ctx, const arp_structure *s, uint64_t n_frames, const double *xyz, const char *chains, float probe,
+                                              int32_t n_points, int32_t table, uint64_t *n_rows, uint64_t *frames_used, uint32_t *out_atoms, float *mean_sasa,
+                                              float *std_sasa, float *min_sasa, float *max_sasa, float *total_sasa, int32_t *out_count) try {
+    return sasa_ensemble_impl(ctx, s, n_frames, xyz, chains, probe, n_points, 0, 0.0f, table, nullptr, n_rows, frames_used, out_atoms, mean_sasa, std_sasa,
+                              min_sasa, max_sasa, nullptr, nullptr, nullptr, nullptr, total_sasa, out_count, nullptr);
+} ARP_ABI_CATCH
+
+extern "C" arp_status arp_sasa_ensemble_residues(arp_context *ctx, const arp_structure *s, uint64_t n_frames, const double *xyz, const char *chains, float probe,
+                                                 int32_t n_points, int32_t table, uint64_t *n_rows, uint64_t *n_chains, uint64_t *frames_used,
+                                                 uint32_t *out_res_atoms, uint8_t *out_is_polar, float *mean_sasa, float *std_sasa, float *min_sasa,
+                                                 float *max_sasa, float *mean_relative, uint8_t *relative_valid, uint32_t *out_chain_atoms, float *chain_sasa,
+                                                 float *residue_sasa) try {
+    const ResidueEnsOut ro{n_chains, out_res_atoms, out_chain_atoms, out_is_polar, relative_valid, mean_sasa, std_sasa, min_sasa, max_sasa, mean_relative,
+                           chain_sasa, residue_sasa};
+    return sasa_ensemble_impl(ctx, s, n_frames, xyz, chains, probe, n_points, 0, 0.0f, table, &ro, n_rows, frames_used, nullptr, nullptr, nullptr, nullptr,
+                              nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
 } ARP_ABI_CATCH

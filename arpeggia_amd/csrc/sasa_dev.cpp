@@ -105,6 +105,68 @@ extern "C" arp_status arp_sap_neighbor_sum(arp_context *ctx, uint64_t n, const d
     return ARP_OK;
 } ARP_ABI_CATCH
 
+// ---- segment sums (seg.inl) --------------------------------------------------------------------------------------
+namespace arp {
+arp_status seg_check(uint64_t m, uint64_t n_seg, const uint32_t *start, const uint32_t *item) {
+    if (n_seg >= (1ull << 31) || m >= (1ull << 32)) { set_error("segment sum: too many segments or items per row (< 2^31 segments, < 2^32 items per row)"); return ARP_ERR_BAD_INPUT; }
+    if (start[0] != 0u) { set_error("segment sum: seg_start[0] must be 0"); return ARP_ERR_BAD_INPUT; }
+    for (uint64_t s = 0; s < n_seg; s++)
+        if (start[s + 1] < start[s]) { set_error("segment sum: seg_start is not monotone at segment %llu", (unsigned long long)s); return ARP_ERR_BAD_INPUT; }
+    if (start[n_seg] > 0x7FFFFFFFu - 64u) { set_error("segment sum: too many listed items (< 2^31 - 64)"); return ARP_ERR_BAD_INPUT; }
+    for (uint32_t q = 0; q < start[n_seg]; q++)
+        if (item[q] >= m) { set_error("segment sum: seg_item[%u] = %u is not below m = %llu", q, item[q], (unsigned long long)m); return ARP_ERR_BAD_INPUT; }
+    return ARP_OK;
+}
+}  // namespace arp
+namespace {
+// Where one CSR sits in a block (offsets: device and pinned alike) and the segments the wave kernel takes (seg.inl kSegLaneItems)
+struct SegLayout {
+    uint64_t o_start = 0, o_item = 0, o_long = 0, o_out = 0;
+    std::vector<uint32_t> long_ids;
+    void take_csr(Carver &lay, const SegJob &g) {
+        for (uint32_t s = 0; s < g.n_seg; s++) if (g.start[s + 1] - g.start[s] > 64u) long_ids.push_back(s);
+        o_start = lay.take(4ull * (g.n_seg + 1)); o_item = lay.take(4ull * g.start[g.n_seg]); o_long = lay.take(4ull * long_ids.size());
+    }
+    void fill(char *pin, const SegJob &g) const {
+        memcpy(pin + o_start, g.start, 4ull * (g.n_seg + 1)); memcpy(pin + o_item, g.item, 4ull * g.start[g.n_seg]);
+        memcpy(pin + o_long, long_ids.data(), 4ull * long_ids.size());
+    }
+    SegCsr csr(const char *dev, const SegJob &g) const {
+        return SegCsr{g.n_seg, (uint32_t)long_ids.size(), (const uint32_t *)(dev + o_start), (const uint32_t *)(dev + o_item), (const uint32_t *)(dev + o_long)};
+    }
+};
+}  // namespace
+
+extern "C" arp_status arp_segment_sum(arp_context *ctx, uint64_t rows, uint64_t m, const float *values, uint64_t n_seg, const uint32_t *seg_start,
+                                      const uint32_t *seg_item, float *out) try {
+    if (rows == 0 || n_seg == 0 || m == 0) return ARP_OK;
+    if (!values || !seg_start || !out || (seg_start[n_seg] && !seg_item)) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    arp_status s = seg_check(m, n_seg, seg_start, seg_item);
+    if (s != ARP_OK) return s;
+    if (rows > (1ull << 40) / m || rows > (1ull << 40) / n_seg) { set_error("segment sum: rows x m and rows x n_seg must stay below 2^40"); return ARP_ERR_BAD_INPUT; }
+    if (!ctx) return ARP_OK;  // the checks alone
+    if ((s = check_device(ctx)) != ARP_OK) return s;
+    if (ctx->pending) { set_error("a call enqueued on this context has not been collected (arp_contacts_atomic_result)"); return ARP_ERR_BAD_INPUT; }
+    SegJob g;
+    g.n_seg = (uint32_t)n_seg; g.start = seg_start; g.item = seg_item;
+    Carver lay;
+    SegLayout sl;
+    sl.take_csr(lay, g);
+    const uint64_t o_val = lay.take(4 * rows * m), in_bytes = lay.off;
+    sl.o_out = lay.take(4 * rows * n_seg);
+    char *dev = nullptr, *pin = nullptr;
+    if ((s = context_scratch(ctx, 0, lay.off, lay.off, &dev, &pin)) != ARP_OK) return s;
+    sl.fill(pin, g);
+    memcpy(pin + o_val, values, 4 * rows * m);
+    HIP_TRY(hipMemcpyAsync(dev, pin, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    launch_segment_sum(rows, (uint32_t)m, (const float *)(dev + o_val), sl.csr(dev, g), (float *)(dev + sl.o_out), ctx->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(pin + sl.o_out, dev + sl.o_out, 4 * rows * n_seg, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    memcpy(out, pin + sl.o_out, 4 * rows * n_seg);
+    return ARP_OK;
+} ARP_ABI_CATCH
+
 // ---- atom SASA (sasa.inl; reference src/sasa.rs:174-247) and the SAP chain (src/sap.rs:137-250) --------------------------------------
 namespace arp {
 void sasa_sphere_points(uint32_t n, float *xyz) {
@@ -138,8 +200,12 @@ arp_status sasa_run(arp_context *ctx, const SasaJob &j, float *sasa, int32_t *co
                    o_sph = lay.take(12ull * j.n_points);
     uint64_t o_px = 0, o_py = 0, o_pz = 0, o_pattr = 0, o_code = 0, o_src = 0;
     if (with_sap) { o_px = lay.take(8 * n); o_py = lay.take(8 * n); o_pz = lay.take(8 * n); o_pattr = lay.take(4 * n); o_code = lay.take(4 * n); o_src = lay.take(4 * n); }
+    std::vector<SegLayout> seg(j.n_segs);
+    for (uint32_t g = 0; g < j.n_segs; g++) seg[g].take_csr(lay, j.segs[g]);
     const uint64_t in_bytes = lay.off;
     const uint64_t o_sasa = lay.take(4 * n), o_count = lay.take(4 * n), o_w = with_sap ? lay.take(4 * n) : 0, o_sap = with_sap ? lay.take(4 * n) : 0;
+    const uint64_t seg_out0 = lay.off;
+    for (uint32_t g = 0; g < j.n_segs; g++) seg[g].o_out = lay.take(4ull * j.segs[g].n_seg);
     const uint64_t out_bytes = lay.off - in_bytes;
     char *dev = nullptr, *pin = nullptr;
     if ((s = context_scratch(ctx, 0, lay.off, lay.off, &dev, &pin)) != ARP_OK) return s;
@@ -161,6 +227,7 @@ arp_status sasa_run(arp_context *ctx, const SasaJob &j, float *sasa, int32_t *co
         for (uint64_t i = 0; i < n; i++) pa[i] = sap_attr(j.sidechain[i]);
         memcpy(pin + o_code, j.res_code, 4 * n); memcpy(pin + o_src, j.src, 4 * n);
     }
+    for (uint32_t g = 0; g < j.n_segs; g++) seg[g].fill(pin, j.segs[g]);
     if ((s = ensure_workspace(ctx, n)) != ARP_OK) return s;
     HIP_TRY(hipMemcpyAsync(dev, pin, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemsetAsync(dev + in_bytes, 0, out_bytes, ctx->stream));  // atoms outside the grid keep sasa 0, count 0
@@ -177,8 +244,12 @@ arp_status sasa_run(arp_context *ctx, const SasaJob &j, float *sasa, int32_t *co
         e.attr = (const uint32_t *)(dev + o_pattr); e.model = (const uint32_t *)(dev + o_zero);
         if ((s = sap_stage(ctx, e, j.sap_radius, (const uint32_t *)(dev + o_code), (const int32_t *)(dev + o_src), d_sasa, (float *)(dev + o_w), (float *)(dev + o_sap))) != ARP_OK) return s;
     }
-    HIP_TRY(hipMemcpyAsync(pin + in_bytes, dev + in_bytes, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    for (uint32_t g = 0; g < j.n_segs; g++) launch_segment_sum(1, (uint32_t)n, d_sasa, seg[g].csr(dev, j.segs[g]), (float *)(dev + seg[g].o_out), ctx->stream);
+    if (j.n_segs) HIP_TRY(hipGetLastError());
+    const uint64_t back0 = (sasa || count || sap) ? in_bytes : seg_out0;  // the per-atom values stay on the device when nobody asked for them
+    HIP_TRY(hipMemcpyAsync(pin + back0, dev + back0, lay.off - back0, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (uint32_t g = 0; g < j.n_segs; g++) memcpy(j.segs[g].out, pin + seg[g].o_out, 4ull * j.segs[g].n_seg);
     ctx->sasa_tests = ctx->h_result[kHostSasaTestsSlot];
     if (sasa) memcpy(sasa, pin + o_sasa, 4 * n);
     if (count) memcpy(count, pin + o_count, 4 * n);
@@ -209,7 +280,12 @@ arp_status ens_run(arp_context *ctx, const EnsJob &j, const EnsOut &o) {
     // way) and adds the coordinate staging and, when asked for, the per-frame outputs of a pass
     Carver lay;
     const uint64_t o_sel = lay.take(4 * m), o_R = lay.take(4 * m), o_code = lay.take(4 * m), o_pattr = lay.take(4 * m), o_sph = lay.take(12ull * j.n_points);
+    const bool with_res = j.res != nullptr;  // (then j.chain is given as well)
+    const uint64_t n_res = with_res ? j.res->n_seg : 0, n_chain = with_res ? j.chain->n_seg : 0;
+    SegLayout seg_res, seg_chain;
+    if (with_res) { seg_res.take_csr(lay, *j.res); seg_chain.take_csr(lay, *j.chain); }
     const uint64_t topo_bytes = lay.off;
+    const uint64_t o_rt1 = lay.take(8 * n_res), o_rt2 = lay.take(8 * n_res), o_rmin = lay.take(4 * n_res), o_rmax = lay.take(4 * n_res), o_chain = lay.take(4 * F * n_chain);
     const uint64_t o_s1 = lay.take(8 * m), o_s2 = lay.take(8 * m), o_t1 = lay.take(8 * m), o_t2 = lay.take(8 * m), o_cmin = lay.take(4 * m), o_cmax = lay.take(4 * m), o_pmin = lay.take(4 * m),
                    o_pmax = lay.take(4 * m), o_total = lay.take(4 * F);
     const uint64_t acc_bytes = lay.off - topo_bytes, shared_bytes = lay.off;
@@ -217,9 +293,11 @@ arp_status ens_run(arp_context *ctx, const EnsJob &j, const EnsOut &o) {
                    o_sasa = lay.take(4 * pn), o_count = lay.take(4 * pn);
     uint64_t o_px = 0, o_py = 0, o_pz = 0, o_pa = 0, o_pc = 0, o_src = 0, o_w = 0, o_sap = 0;
     if (j.with_sap) { o_px = lay.take(8 * pn); o_py = lay.take(8 * pn); o_pz = lay.take(8 * pn); o_pa = lay.take(4 * pn); o_pc = lay.take(4 * pn); o_src = lay.take(4 * pn); o_w = lay.take(4 * pn); o_sap = lay.take(4 * pn); }
+    const uint64_t o_rs = lay.take(4 * per * n_res);
     const uint64_t dev_bytes = lay.off;
     lay.off = shared_bytes;
-    const uint64_t h_xyz = lay.take(24 * per * N), h_count = o.count ? lay.take(4 * pn) : 0, h_sap = o.sap ? lay.take(4 * pn) : 0;
+    const uint64_t h_xyz = lay.take(24 * per * N), h_count = o.count ? lay.take(4 * pn) : 0, h_sap = o.sap ? lay.take(4 * pn) : 0,
+                   h_rs = o.residue_sasa ? lay.take(4 * per * n_res) : 0;
     const uint64_t pin_bytes = lay.off;
     if ((s = ensure_workspace(ctx, pn)) != ARP_OK) return s;
     char *dev = nullptr, *pin = nullptr;
@@ -230,6 +308,9 @@ arp_status ens_run(arp_context *ctx, const EnsJob &j, const EnsOut &o) {
         uint32_t *pa = (uint32_t *)(pin + o_pattr);
         for (uint64_t k = 0; k < m; k++) pa[k] = sap_attr(j.sidechain[k]);
     }
+    if (with_res) { seg_res.fill(pin, *j.res); seg_chain.fill(pin, *j.chain); }
+    const SegCsr csr_res = with_res ? seg_res.csr(dev, *j.res) : SegCsr{}, csr_chain = with_res ? seg_chain.csr(dev, *j.chain) : SegCsr{};
+    const SegAcc racc{(double *)(dev + o_rt1), (double *)(dev + o_rt2), (float *)(dev + o_rmin), (float *)(dev + o_rmax)};
     hipStream_t st = ctx->stream;
     HIP_TRY(hipMemcpyAsync(dev, pin, topo_bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(dev + o_zero, 0, 4 * pn, st));  // attribute word of the SASA grid (every packed atom is in it), residue ordinal, chain rank
@@ -266,13 +347,20 @@ arp_status ens_run(arp_context *ctx, const EnsJob &j, const EnsOut &o) {
             if ((s = sap_stage(ctx, e, j.sap_radius, pk.code, pk.src, d_sasa, (float *)(dev + o_w), d_sap)) != ARP_OK) return s;
         }
         launch_ens_reduce((uint32_t)fc, (uint32_t)m, d_count, d_sasa, d_sap, acc, f0 == 0, (float *)(dev + o_total) + f0, st);
+        if (with_res) {  // the pass's [frame][residue] and [frame][chain] sums of the SASA values, then the residues' fold over its frames
+            launch_segment_sum(fc, (uint32_t)m, d_sasa, csr_res, (float *)(dev + o_rs), st);
+            launch_segment_sum(fc, (uint32_t)m, d_sasa, csr_chain, (float *)(dev + o_chain) + f0 * n_chain, st);
+            launch_ens_res_reduce((uint32_t)fc, (uint32_t)n_res, (const float *)(dev + o_rs), racc, f0 == 0, st);
+        }
         HIP_TRY(hipGetLastError());
-        if (o.count || o.sap) {  // the pass's own values, only when the caller wants them
+        if (o.count || o.sap || o.residue_sasa) {  // the pass's own values, only when the caller wants them
             if (o.count) HIP_TRY(hipMemcpyAsync(pin + h_count, d_count, 4 * cn, hipMemcpyDeviceToHost, st));
             if (o.sap) HIP_TRY(hipMemcpyAsync(pin + h_sap, d_sap, 4 * cn, hipMemcpyDeviceToHost, st));
+            if (o.residue_sasa) HIP_TRY(hipMemcpyAsync(pin + h_rs, dev + o_rs, 4 * fc * n_res, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             if (o.count) memcpy(o.count + f0 * m, pin + h_count, 4 * cn);
             if (o.sap) memcpy(o.sap + f0 * m, pin + h_sap, 4 * cn);
+            if (o.residue_sasa) memcpy(o.residue_sasa + f0 * n_res, pin + h_rs, 4 * fc * n_res);
         }
     }
     HIP_TRY(hipMemcpyAsync(pin + topo_bytes, dev + topo_bytes, acc_bytes, hipMemcpyDeviceToHost, st));
@@ -280,6 +368,10 @@ arp_status ens_run(arp_context *ctx, const EnsJob &j, const EnsOut &o) {
     memcpy(o.s1, pin + o_s1, 8 * m); memcpy(o.s2, pin + o_s2, 8 * m); memcpy(o.cmin, pin + o_cmin, 4 * m); memcpy(o.cmax, pin + o_cmax, 4 * m);
     memcpy(o.total, pin + o_total, 4 * F);
     if (j.with_sap) { memcpy(o.t1, pin + o_t1, 8 * m); memcpy(o.t2, pin + o_t2, 8 * m); memcpy(o.pmin, pin + o_pmin, 4 * m); memcpy(o.pmax, pin + o_pmax, 4 * m); }
+    if (with_res) {
+        memcpy(o.rt1, pin + o_rt1, 8 * n_res); memcpy(o.rt2, pin + o_rt2, 8 * n_res); memcpy(o.rmin, pin + o_rmin, 4 * n_res); memcpy(o.rmax, pin + o_rmax, 4 * n_res);
+        memcpy(o.chain_sasa, pin + o_chain, 4 * F * n_chain);
+    }
     return ARP_OK;
 }
 }  // namespace arp

@@ -267,6 +267,55 @@ arp_status arp_structure_sap_score(arp_context *ctx, const arp_structure *s, con
 arp_status arp_structure_dsasa(arp_context *ctx, const arp_structure *s, const char *groups, float probe, int32_t n_points, int32_t model_num,
                                float *out);
 
+/* ---- residue- and chain-level SASA, relative SASA, segment sums -- DESIGN.md section 3.9 ----
+ * Radius tables.  ARP_RADII_VDW: the element's van der Waals radius (arp_params.vdw_radius), what arp_structure_atom_sasa, arp_structure_dsasa
+ * and arp_sasa_ensemble use.  ARP_RADII_PROTOR: the ProtOr radii of Tsai et al. 1999 by (residue name, atom name), then (ANY, atom name) for the
+ * backbone and CB, then the element's van der Waals radius.  The reference computes its residue and chain levels through rust-sasa with
+ * with_allow_vdw_fallback(true); ProtOr is the table that reproduces the reference's own chain-level pin on 1ubq (4813 A^2).  ASSUMPTIONS, since
+ * rust-sasa is not part of the reference's tree: which element table its fallback uses (here: arp_params.vdw_radius); its list of polar residues
+ * (here: ARG ASN ASP GLN GLU HIS LYS SER THR TYR); its rule that "only the first altloc is considered" at the residue level (not restated: all
+ * selected atoms take part, as at the atom level and in arp_structure_dsasa). */
+#define ARP_RADII_VDW 0
+#define ARP_RADII_PROTOR 1
+/* *out = the radius in f32 (the probe is added in f32 by the callers).  The residue name is matched case-insensitively, the atom name exactly.
+ * ARP_ERR_BAD_INPUT: an unknown table, or no table entry and an element without a van der Waals radius.  Host only. */
+arp_status arp_sasa_radius(const char *resn, const char *atomn, const char *element, int32_t table, float *out);
+/* MaxASA of Tien et al. 2013 (the reference's get_max_asa, sasa.rs:460-483), residue name matched case-insensitively; 0 = none.  Host only. */
+float arp_max_asa(const char *resn);
+/* 1 for ARG ASN ASP GLN GLU HIS LYS SER THR TYR (case-insensitive; an assumption, see above), else 0.  Host only. */
+int32_t arp_residue_is_polar(const char *resn);
+/* Segment sums on the device.  values: rows x m finite, non-negative f32 (host, C order).  n_seg segments as a CSR: seg_start[n_seg + 1]
+ * (seg_start[0] = 0, monotone, at most 2^31 - 65 items in all) and seg_item[seg_start[n_seg]], every entry an index below m; a segment lists
+ * its items in the order they are added -- they need not be contiguous, ascending or disjoint.
+ * out[row][s] (rows x n_seg, host) = f32(acc), acc = 0.0; acc = acc + (double)values[row][seg_item[q]] for q = seg_start[s] .. seg_start[s + 1) - 1
+ * in that order, every addition one IEEE f64 round-to-nearest add: the bytes of that sequential chain for every input; an empty segment gives
+ * 0.0f.  No atomics: two calls give the same bytes.  rows == 0, n_seg == 0 or m == 0: ARP_OK, nothing written.  ARP_ERR_BAD_INPUT before the
+ * device is touched: an item >= m, a seg_start that is not monotone from 0, sizes out of range.  ctx == NULL runs only these checks.  Synchronous. */
+arp_status arp_segment_sum(arp_context *ctx, uint64_t rows, uint64_t m, const float *values, uint64_t n_seg, const uint32_t *seg_start,
+                           const uint32_t *seg_item, float *out);
+/* arp_structure_atom_sasa / arp_structure_dsasa with the radii of `table` (ARP_RADII_VDW: the same bytes as those). */
+arp_status arp_structure_atom_sasa_radii(arp_context *ctx, const arp_structure *s, const char *chains, int32_t model_num, int32_t remove_hydrogens,
+                                         float probe, int32_t n_points, int32_t table, uint64_t *n_rows, uint32_t *out_atoms, float *out_sasa,
+                                         int32_t *out_count);
+arp_status arp_structure_dsasa_radii(arp_context *ctx, const arp_structure *s, const char *groups, float probe, int32_t n_points, int32_t model_num,
+                                     int32_t table, float *out);
+/* get_residue_sasa (sasa.rs:284-318).  Selection: steps 1-4 of arp_structure_sasa_select with hydrogens removed (NO step 5: the reference has no
+ * serial filter here).  Per-atom SASA: what arp_atom_sasa gives the selected atoms with the radii of `table`.  One row per residue of the selection
+ * -- the atoms sharing the ingest's residue (chain, resi, insertion) --, sasa = the segment sum (above) of its atoms' values in selection order,
+ * summed on the device behind the SASA kernel; only the sums come back.  Rows sorted stably by (chain as a byte string, resi, insertion).
+ * out_atoms[r]: the first selected atom of the row's residue (its chain, resn, resi and insertion are the row's identity); out_is_polar[r]:
+ * arp_residue_is_polar of its residue name (nullable).  Every out_* array holds arp_structure_n_atoms(s) entries (an upper bound). */
+arp_status arp_structure_residue_sasa(arp_context *ctx, const arp_structure *s, const char *chains, int32_t model_num, float probe, int32_t n_points,
+                                      int32_t table, uint64_t *n_rows, uint32_t *out_atoms, float *out_sasa, uint8_t *out_is_polar);
+/* get_chain_sasa (sasa.rs:352-382): the same selection, one row per chain id (a chain need not be one run of the selection), sorted by chain id. */
+arp_status arp_structure_chain_sasa(arp_context *ctx, const arp_structure *s, const char *chains, int32_t model_num, float probe, int32_t n_points,
+                                    int32_t table, uint64_t *n_rows, uint32_t *out_atoms, float *out_sasa);
+/* get_relative_sasa (sasa.rs:520-561, its code: no altloc and no max_sasa column): the residue rows plus out_relative[r] = sasa / arp_max_asa
+ * (one f32 division) with out_valid[r] = 1, or NaN with out_valid[r] = 0 (null) where the residue has no MaxASA. */
+arp_status arp_structure_relative_sasa(arp_context *ctx, const arp_structure *s, const char *chains, int32_t model_num, float probe, int32_t n_points,
+                                       int32_t table, uint64_t *n_rows, uint32_t *out_atoms, float *out_sasa, uint8_t *out_is_polar, float *out_relative,
+                                       uint8_t *out_valid);
+
 /* ---- shape complementarity (Lawrence & Colman 1993; reference src/sc/, get_sc) -- DESIGN.md section 3.6 ----
  * Every quantity is f64 and follows the reference's rules and order; sums run in dot order; of two nearest dots at equal distance the
  * lower index wins; same-molecule neighbours at equal distance are ordered by atom index. */
@@ -436,6 +485,26 @@ arp_status arp_sasa_ensemble(arp_context *ctx, const arp_structure *topology, ui
 arp_status arp_sasa_ensemble_stats(uint64_t n_frames, uint64_t m, const float *R, int32_t n_points, const uint64_t *s1, const uint64_t *s2,
                                    const int32_t *cmin, const int32_t *cmax, const double *t1, const double *t2, float *mean_sasa, float *std_sasa,
                                    float *min_sasa, float *max_sasa, float *mean_sap, float *std_sap);
+
+/* arp_sasa_ensemble without SAP, with the radii of `table` (ARP_RADII_VDW: the same bytes). */
+arp_status arp_sasa_ensemble_radii(arp_context *ctx, const arp_structure *topology, uint64_t n_frames, const double *xyz, const char *chains, float probe,
+                                   int32_t n_points, int32_t table, uint64_t *n_rows, uint64_t *frames_used, uint32_t *out_atoms, float *mean_sasa,
+                                   float *std_sasa, float *min_sasa, float *max_sasa, float *total_sasa, int32_t *out_count);
+/* Residue level across the frames of an ensemble.  Topology, frames, selection (m atoms), checks, NULL-context mode, pass
+ * sizing and the memory bound are arp_sasa_ensemble's; radii from `table`.  The residues and chains of the selection and their order are those
+ * of arp_structure_residue_sasa / arp_structure_chain_sasa.  Per frame f: rs[f][r] and chain_sasa[f][c] are the segment sums (arp_segment_sum)
+ * of frame f's per-atom SASA values -- what the single-structure calls give for that frame, for every pass size.  Per residue over the frames:
+ * T1 = sum rs, T2 = sum rs^2 (f64, frame order 0 .. F - 1 whatever the pass size), mu = T1 / F, mean_sasa = f32(mu),
+ * std_sasa = f32(sqrt(max(T2 / F - mu * mu, 0))), min_sasa / max_sasa over the frames; mean_relative = mean_sasa / arp_max_asa (f32) with
+ * relative_valid = 1, or NaN / 0 without a MaxASA.
+ * Outputs: *n_rows residues, *n_chains chains, *frames_used = F; out_res_atoms / out_chain_atoms: the first selected atom of every residue /
+ * chain; the per-residue arrays and out_*_atoms hold arp_structure_n_atoms entries at most; chain_sasa holds F x n_chains (C order);
+ * residue_sasa (F x n_rows, nullable) is copied back only when given.  ctx == NULL runs only the checks and writes the three counts and (when
+ * given) out_res_atoms / out_chain_atoms: the way to size chain_sasa.  An empty selection is ARP_OK with 0 rows and 0 chains.  Synchronous. */
+arp_status arp_sasa_ensemble_residues(arp_context *ctx, const arp_structure *topology, uint64_t n_frames, const double *xyz, const char *chains, float probe,
+                                      int32_t n_points, int32_t table, uint64_t *n_rows, uint64_t *n_chains, uint64_t *frames_used, uint32_t *out_res_atoms,
+                                      uint8_t *out_is_polar, float *mean_sasa, float *std_sasa, float *min_sasa, float *max_sasa, float *mean_relative,
+                                      uint8_t *relative_valid, uint32_t *out_chain_atoms, float *chain_sasa, float *residue_sasa);
 
 /* The same 20 columns through the Arrow C Data Interface (a struct array = one record batch; utf8 strings, nullable
  * f32 sc_* columns): what pyo3-polars hands to Python in the reference (python.rs:55, mod.rs:140-214), importable with
