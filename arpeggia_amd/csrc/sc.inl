@@ -654,7 +654,8 @@ uint32_t sc_read(ScArena &A, const uint32_t *p) {
     return v;
 }
 struct ScBox { double lo[3], hi[3]; };
-// cell list over the points of `base` (stride in doubles) that `mode` includes; edge >= edge_req, at most 128 cells per axis
+// cell list over the points of `base` (stride in doubles) that `mode` includes; edge >= edge_req and >= the longest axis / 128, so at most
+// 129 cells per axis ((int)(ext / edge) + 1 with ext / edge up to 128; cell_of clamps to n - 1)
 ScCells sc_cells(ScArena &A, const ScBox &box, const double *base, uint32_t stride, uint32_t n, uint32_t mode, double rp, double edge_req,
                  Profiler *prof, const char *name) {
     double ext = 0.0;

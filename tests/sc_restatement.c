@@ -52,6 +52,7 @@ typedef struct {
     int64_t n_convex, n_toroidal, n_concave;
     int err, err_i, err_j;
     int64_t branch[5];  /* times each quirk branch ran: see scr_branches */
+    int64_t reach[6];   /* how far the run went into the paths the edge tests are about: see scr_reach */
 } Run;
 
 static int in_map(Run *R, int a, int b) { return dist2(R->c[a], R->c[b]) <= R->sep * R->sep; }
@@ -126,7 +127,11 @@ static int categorize(Run *R) {
         int m = 0;
         for (int j = 0; j < n; j++) {
             double d2 = dist2(R->c[i], R->c[j]);
-            if (!(d2 <= s2)) continue;
+            if (!(d2 <= s2)) {
+                double br = R->r[i] + R->r[j] + 2.0 * R->rp;
+                if (R->mol[j] == R->mol[i] && R->serial[j] != R->serial[i] && d2 < br * br) R->reach[4]++;
+                continue;
+            }
             if (R->mol[j] != R->mol[i] && d2 < best) best = d2;
             if (R->serial[j] == R->serial[i]) continue;
             if (R->mol[j] == R->mol[i]) {
@@ -139,6 +144,7 @@ static int categorize(Run *R) {
                 }
             }
         }
+        for (int q = 1; q < m; q++) if (d2tmp[q] == d2tmp[q - 1]) R->reach[2]++;
         R->att[i] = best < s2 ? BURIED : FAR;
         R->nnb[i] = m;
         R->nb[i] = malloc(sizeof(int) * (m ? m : 1));
@@ -167,7 +173,10 @@ static void triplets(Run *R, int i, int j, V ua, V mid, double ring_r) {  /* :44
         int k = R->nb[i][q];
         if (R->serial[k] <= R->serial[j]) continue;
         double ek = R->r[k] + R->rp;
-        if (!in_map(R, j, k)) continue;
+        if (!in_map(R, j, k)) {
+            if (sqrt(dist2(R->c[j], R->c[k])) < ej + ek) R->reach[3]++;
+            continue;
+        }
         if (sqrt(dist2(R->c[j], R->c[k])) >= ej + ek) continue;
         double dik = sqrt(dist2(ci, R->c[k]));
         if (dik >= ei + ek) continue;
@@ -332,6 +341,7 @@ static void contact_atom(Run *R, int i, Pts *lats, Pts *pts, Dots *tmp) {  /* :2
     }
     double cs, ps;
     if (sample_arc(v3(0.0, 0.0, 0.0), ri, eq, R->density, north, south, lats, &cs)) return;
+    int64_t nlat = (int64_t)lats->n;
     int other = R->mol[i] == 0 ? 1 : 0;
     for (size_t l = 0; l < lats->n; l++) {
         double dt = dot(lats->d[l], north);
@@ -365,6 +375,7 @@ static void contact_atom(Run *R, int i, Pts *lats, Pts *pts, Dots *tmp) {  /* :2
             PUSH(*tmp, d);
         }
     }
+    if (tmp->n && nlat > R->reach[0]) R->reach[0] = nlat;
 }
 
 static void concave_probe(Run *R, size_t pi, const int *low, size_t nlow, Pts *lats, Pts *pts, Dots *tmp0, Dots *tmp1) {  /* :713-880 */
@@ -392,6 +403,7 @@ static void concave_probe(Run *R, size_t pi, const int *low, size_t nlow, Pts *l
     V axis = normalized(cross(vp[mm], south));
     double cs, ps;
     if (sample_arc(v3(0.0, 0.0, 0.0), rp, axis, density, vp[mm], south, lats, &cs)) { free(nears); return; }
+    int64_t nlat = (int64_t)lats->n;
     for (size_t l = 0; l < lats->n; l++) {
         double dt = dot(lats->d[l], south);
         V cen = mul(south, dt);
@@ -424,8 +436,10 @@ static void concave_probe(Run *R, size_t pi, const int *low, size_t nlow, Pts *l
             d.p[0] = p.x; d.p[1] = p.y; d.p[2] = p.z; d.n[0] = nml.x; d.n[1] = nml.y; d.n[2] = nml.z;
             d.area = area; d.flags = 2 | (buried ? 4 : 0); d.atom = atom;
             if (molecule == 0) PUSH(*tmp0, d); else PUSH(*tmp1, d);
+            if (l >= 64) R->reach[5]++;
         }
     }
+    if (tmp0->n + tmp1->n && nlat > R->reach[1]) R->reach[1] = nlat;
     free(nears);
 }
 
@@ -572,6 +586,11 @@ void scr_probes(void *h, int32_t *atoms, double *height, double *point) {
 /* branch counts: [0] the sin_wedge <= 0 `return`, [1] its `continue`, [2] the ring-point |dot| >= 1 `return`, [3] the num_neighbors <= 1
  * `break`, [4] ring points whose Far atom j emitted an arc */
 void scr_branches(void *h, int64_t *out) { memcpy(out, ((Run *)h)->branch, sizeof ((Run *)h)->branch); }
+/* reach counters: [0] the largest latitude count of a contact atom that emitted a dot, [1] the same of a concave probe, [2] neighbour-list
+ * entries whose d^2 equals that of the entry before them, [3] triplet candidates k outside j's map (d_jk^2 > sep^2) although
+ * d_jk < e_j + e_k, [4] ordered same-molecule pairs with d^2 < bridge^2 that d^2 <= sep^2 rejected, [5] concave dots of latitudes 64 and up
+ * (kept only if their probe is: a probe whose circle fails is dropped whole, which no case here reaches) */
+void scr_reach(void *h, int64_t *out) { memcpy(out, ((Run *)h)->reach, sizeof ((Run *)h)->reach); }
 void scr_free(void *h) {
     Run *R = h;
     for (int i = 0; i < R->n; i++) free(R->nb[i]);

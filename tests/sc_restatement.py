@@ -21,6 +21,11 @@ ERRORS = {1: "No atoms defined", 2: "No atoms for chain group 1", 3: "No molecul
 
 # the quirk branches the restatement counts (scr_branches): surface_generator.rs :494-496 return / :497 continue, :620-627, :418-422, :654-685
 BRANCHES = ("wedge_return", "wedge_continue", "ring_return", "lonely_break", "far_j_arc")
+# how far a run went into the paths of tests/sc_edge_cases.py (scr_reach): the largest latitude count of a contact atom / a concave probe
+# that emitted a dot, neighbour-list entries with the d^2 of the entry before them, triplet candidates k that only "k is not in j's map"
+# rejected (d_jk < e_j + e_k), ordered same-molecule pairs inside the bridge distance that only d^2 <= sep^2 rejected, concave dots of a
+# probe's latitudes 64 and up
+REACH = ("max_lat_contact", "max_lat_probe", "d2_ties", "kmap_rejects", "sep_rejects", "probe_dots_past_64")
 
 
 class ScrResults(C.Structure):
@@ -44,6 +49,7 @@ def compile(out_dir) -> C.CDLL:
     L.scr_n_probes.argtypes = [vp]
     L.scr_probes.argtypes = [vp, C.POINTER(C.c_int32), dp, dp]
     L.scr_branches.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.scr_reach.argtypes = [vp, C.POINTER(C.c_int64)]
     L.scr_free.argtypes = [vp]
     return L
 
@@ -53,7 +59,8 @@ def _p(a, t):
 
 
 def run(L, x, y, z, r, mol, serial=None, **settings) -> dict:
-    """Results as a dict (err: 0 or an ERRORS key), the per-surface dots (xyz, normal, area, flags, nn_dist, score) and the probes."""
+    """Results as a dict (err: 0 or an ERRORS key), the per-surface dots (xyz, normal, area, flags, nn_dist, score), the probes, the
+    branch counts (BRANCHES) and the reach counters (REACH)."""
     st = dict(SETTINGS, **settings)
     n = len(x)
     x, y, z, r = (np.ascontiguousarray(a, dtype=np.float64) for a in (x, y, z, r))
@@ -81,6 +88,9 @@ def run(L, x, y, z, r, mol, serial=None, **settings) -> dict:
         br = np.zeros(len(BRANCHES), dtype=np.int64)
         L.scr_branches(h, _p(br, C.c_int64))
         out["branches"] = dict(zip(BRANCHES, br.tolist()))
+        rc = np.zeros(len(REACH), dtype=np.int64)
+        L.scr_reach(h, _p(rc, C.c_int64))
+        out["reach"] = dict(zip(REACH, rc.tolist()))
     finally:
         L.scr_free(h)
     return out
