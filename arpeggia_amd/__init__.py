@@ -1,8 +1,8 @@
 """arpeggia_amd: MI355X-native drop-in for the `contacts` path of y1zhou/arpeggia.
 
 Public surface mirrors the reference (src/lib.rs:20-34, src/python.rs:31-56) for this one path:
-contacts(), get_contacts(), load_model(), parse_groups(); and sasa(), relative_sasa(), sap_score(), dsasa(); and sc(); and
-contact_frequencies(), sasa_ensemble() and sap_ensemble() across the frames of an ensemble (no counterpart in the reference).  Importing this package loads libarpeggia_amd.so and
+contacts(), get_contacts(), load_model(), parse_groups(); and sasa(), relative_sasa(), sap_score(), dsasa(), buried_sasa(); and sc(); and
+contact_frequencies(), sasa_ensemble(), sap_ensemble() and dsasa_ensemble() across the frames of an ensemble (no counterpart in the reference).  Importing this package loads libarpeggia_amd.so and
 fails loudly if the HIP extension has not been built -- there is no CPU fallback.
 """
 from .api import (  # noqa: F401
@@ -22,6 +22,10 @@ from .api import FREQ_COLUMNS, contact_frequencies, get_contact_frequencies  # n
 from .api import (  # noqa: F401  SASA / SAP statistics across the frames of an ensemble
     ENSEMBLE_SAP_COLUMNS, ENSEMBLE_SASA_COLUMNS, RESIDUE_ENSEMBLE_SAP_COLUMNS, get_residue_sap_ensemble, get_sap_ensemble, get_sasa_ensemble,
     sap_ensemble, sasa_ensemble, sasa_ensemble_stats,
+)
+from .api import (  # noqa: F401  buried surface per atom and residue, dSASA across the frames of an ensemble
+    BURIED_ATOM_COLUMNS, BURIED_RESIDUE_COLUMNS, DSASA_ENSEMBLE_COLUMNS, DSASA_FRAME_COLUMNS, atom_sasa_groups, buried_sasa, dsasa_ensemble,
+    dsasa_ensemble_stats, dsasa_total, get_buried_sasa, get_dsasa_ensemble,
 )
 from ._lib import ATTR, INTERACTIONS  # noqa: F401
 

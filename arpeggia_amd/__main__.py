@@ -4,6 +4,8 @@
 `sasa-ensemble` also take --radii {vdw,protor}: the radius table, which the residue and chain levels of `sasa` need (see arpeggia_amd/api.py).
 `contact-frequency` (no counterpart in the reference) takes the flags and defaults of `contacts`; the models of the input file are the frames.
 `sasa-ensemble` and `sap-ensemble` (no counterpart either) take the flags and defaults of `sasa` / `sap` without --model: statistics over the models.
+`dsasa --level atom|residue` writes the interface row by row (default `total`: the reference's scalar); `dsasa-ensemble` takes the flags of
+`sasa-ensemble` and -g: dSASA per model and the per-atom statistics of the buried surface.
 """
 from __future__ import annotations
 
@@ -103,6 +105,19 @@ def build_parser() -> argparse.ArgumentParser:
     d.add_argument("-g", "--groups", required=True, help="Chain groups, e.g. A,B/C,D")
     add(d, "model", "probe", "points", "threads")
     d.add_argument("--radii", default=None, type=str.lower, choices=("vdw", "protor"), help=RADII_HELP)
+    d.add_argument("-l", "--level", default="total", type=str.lower, choices=("total", "atom", "residue"),
+                   help="total: the scalar (cli/dsasa.rs); atom / residue: the interface row by row, written to --output")
+    d.add_argument("-o", "--output", default=None, type=Path, help="Output directory (levels atom and residue)")
+    d.add_argument("-f", "--filename", default="dsasa", help="Name of the output file (levels atom and residue)")
+    d.add_argument("-t", "--output-format", default="csv", type=str.lower, choices=FORMATS, help="Output file type (levels atom and residue)")
+    de = sub.add_parser("dsasa-ensemble", help="dSASA of every model of a multi-model file and how often each atom sits in the interface")
+    de.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file whose models are the frames")
+    de.add_argument("-o", "--output", required=True, type=Path, help="Output directory")
+    de.add_argument("-g", "--groups", required=True, help="Chain groups, e.g. A,B/C,D")
+    de.add_argument("-f", "--filename", default="dsasa_ensemble", help="Name of the per-atom output file; the per-frame table goes to <filename>_frames")
+    de.add_argument("-t", "--output-format", default="csv", type=str.lower, choices=FORMATS, help="Output file type")
+    add(de, "probe", "points", "threads")
+    de.add_argument("--radii", default=None, type=str.lower, choices=("vdw", "protor"), help=RADII_HELP)
     g = sub.add_parser("sc", help="shape complementarity of two chain groups (cli/sc.rs)")
     g.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file to be analyzed")
     g.add_argument("-g", "--groups", required=True, help="Chain groups, e.g. A,B/C,D: both surfaces must be given")
@@ -138,11 +153,18 @@ def run_surface(args) -> int:
         log.error("Failed to retrieve input file: %s", args.input)
         return 1
     s = aa.Structure.load(str(args.input.resolve()))
-    if args.command == "dsasa":
+    if args.command == "dsasa" and args.level != "total":
+        if args.output is None:
+            log.error("dsasa level '%s' writes a table: add --output", args.level)
+            return 2
+        table, v = aa.get_buried_sasa(s, args.groups, args.level, args.probe_radius, args.n_points, args.model_num, args.radii)
+        log.info("Buried surface area (dSASA) at the interface between chains [%s]: %.2f A^2", args.groups, v)
+        what = "atoms" if args.level == "atom" else "residues"
+    elif args.command == "dsasa":
         v = aa.get_dsasa(s, args.groups, args.probe_radius, args.n_points, args.model_num, radii=args.radii)
         log.info("Buried surface area (dSASA) at the interface between chains [%s]: %.2f A^2", args.groups, v)
         return 0
-    if args.command == "sasa":
+    elif args.command == "sasa":
         if args.level != "atom" and args.radii is None:
             log.error("sasa level '%s' needs a named radius table (the reference's rust-sasa table is not part of its tree): add --radii protor, or use --level atom", args.level)
             return 2
@@ -170,12 +192,24 @@ def run_surface(args) -> int:
 
 
 def run_ensemble(args) -> int:
-    """sasa-ensemble / sap-ensemble: the models of the input file are the frames."""
+    """sasa-ensemble / sap-ensemble / dsasa-ensemble: the models of the input file are the frames."""
     import arpeggia_amd as aa
 
     if not args.input.exists():
         log.error("Failed to retrieve input file: %s", args.input)
         return 1
+    if args.command == "dsasa-ensemble":
+        try:
+            frames, table = aa.dsasa_ensemble(str(args.input.resolve()), args.groups, args.probe_radius, args.n_points, args.radii)
+        except aa.ArpeggiaError as e:
+            log.error("Ensemble statistics failed: %s", e)
+            return 1
+        args.output.mkdir(parents=True, exist_ok=True)
+        out = (args.output / args.filename).with_suffix("." + args.output_format)
+        write_table(table, out, args.output_format)
+        write_table(frames, (args.output / (args.filename + "_frames")).with_suffix("." + args.output_format), args.output_format)
+        log.info("Results for %d atoms over %d frames saved to %s", len(table), len(frames), out)
+        return 0
     if args.command == "sasa-ensemble" and args.level != "atom" and args.radii is None:
         log.error("sasa level '%s' needs a named radius table (the reference's rust-sasa table is not part of its tree): add --radii protor, or use --level atom", args.level)
         return 2
@@ -269,7 +303,7 @@ def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     if args.command == "sc":
         return run_sc(args)
-    if args.command in ("sasa-ensemble", "sap-ensemble"):
+    if args.command in ("sasa-ensemble", "sap-ensemble", "dsasa-ensemble"):
         return run_ensemble(args)
     if args.command == "contact-frequency":
         return run_contact_frequency(args)

@@ -210,6 +210,12 @@ def _load():
                                                 _u32p] + [_fp] * 5 + [_i32p]),
         "arp_sasa_ensemble_residues": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_float, C.c_int32, C.c_int32] + [C.POINTER(C.c_uint64)] * 3 +
                                        [_u32p, _u8p] + [_fp] * 5 + [_u8p, _u32p, _fp, _fp]),
+        "arp_atom_sasa_groups": (C.c_int32, [vp, C.c_uint64, _dp, _dp, _dp, _fp, _u8p, C.c_float, C.c_int32, _i32p, _fp, _i32p]),
+        "arp_structure_buried_sasa": (C.c_int32, [vp, vp, C.c_char_p, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), _u32p, _u8p, _fp, _i32p,
+                                                  _i32p, C.POINTER(C.c_uint64), _u32p, _fp, _u32p, _fp]),
+        "arp_dsasa_total": (C.c_int32, [C.c_float, C.c_float, C.c_float, _fp]),
+        "arp_dsasa_ensemble": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                           _u32p, _u8p, _fp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _i32p, _i32p, _u32p, _fp, _fp, _fp, _fp, _i32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here == the library does not export what the header declares

@@ -391,6 +391,20 @@ class Context:
         [F, n_chains]; per_frame adds residue_sasa [F, n_res]."""
         return _residue_sasa_ensemble(self, structure, frames, chains, probe_radius, n_points, radii, per_frame)
 
+    def buried_sasa(self, structure: Structure, groups: str, probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, radii=None) -> dict:
+        """arp_structure_buried_sasa as a dict of numpy arrays: the interface of two chain groups atom by atom and residue by residue, from one
+        walk of the split kernel.  Keys: atoms (u32 structure indices, by serial), group (u8: 1, 2, 3), sasa [3, m] f32 and count [3, m] i32
+        (complex, group 1, group 2; 0 where the atom is not in the group), buried [m] i32 (points), res_atoms, res_sasa [3, n_res] f32,
+        res_buried_atoms [n_res] u32, totals [4] f32 (complex, group 1, group 2, dSASA), dsasa (float)."""
+        return _buried_sasa(self, structure, groups, probe_radius, n_points, model_num, radii)
+
+    def dsasa_ensemble(self, structure: Structure, frames=None, groups: str = "/", probe_radius: float = 1.4, n_points: int = 100, radii=None,
+                       per_frame: bool = False) -> dict:
+        """arp_dsasa_ensemble as a dict of numpy arrays: dSASA of every frame and the per-atom statistics of the buried points over the frames.
+        Keys: atoms, group, R (radius + probe) [m], n_frames, sum_buried / sum_buried_sq (u64), min_buried / max_buried (i32), frames_buried (u32)
+        [m], total_complex / total_g1 / total_g2 / dsasa [F] f32; per_frame adds buried [F, m] i32."""
+        return _dsasa_ensemble(self, structure, frames, groups, probe_radius, n_points, radii, per_frame)
+
 
 def _topology_atoms(structure: Structure) -> int:
     """Atoms of model 0 (the topology of arp_contact_frequencies): the leading run of the first MODEL serial."""
@@ -751,6 +765,22 @@ def atom_sasa(ctx: "Context", x, y, z, radius, include=None, probe: float = 1.4,
     return sasa, count
 
 
+def atom_sasa_groups(ctx: "Context | None", x, y, z, radius, group, probe: float = 1.4, n_points: int = 100):
+    """arp_atom_sasa_groups on host arrays: group is a u8 mask per atom (0: out, 1: group 1, 2: group 2, 3: both).  Returns (count [3, n] i32,
+    sasa [3, n] f32, buried [n] i32): the planes are complex, group 1, group 2 (0 where the atom is not in the group); buried = own group
+    counts - complex count, in points.  ctx None: the arguments are only checked (raises their error, else the missing context's)."""
+    x, y, z = (np.ascontiguousarray(v, dtype="<f8") for v in (x, y, z))
+    r = np.ascontiguousarray(radius, dtype="<f4")
+    g = np.ascontiguousarray(group, dtype=np.uint8)
+    n = len(x)
+    count, sasa_, buried = np.zeros((3, n), "<i4"), np.zeros((3, n), "<f4"), np.zeros(n, "<i4")
+    dp, fp, ip = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    _check(lib.arp_atom_sasa_groups(ctx._h if ctx is not None else None, n, x.ctypes.data_as(dp), y.ctypes.data_as(dp), z.ctypes.data_as(dp),
+                                    r.ctypes.data_as(fp), g.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_float(probe), int(n_points),
+                                    count.ctypes.data_as(ip), sasa_.ctypes.data_as(fp), buried.ctypes.data_as(ip)))
+    return count, sasa_, buried
+
+
 def sasa_tests(ctx: "Context") -> int:
     """f32 distance tests the kernel of the context's most recent SASA call made (diagnostics)."""
     return int(lib.arp_sasa_tests(ctx._h))
@@ -1053,6 +1083,167 @@ def dsasa(input_file: str, groups: str, probe_radius: float = 1.4, n_points: int
     """Drop-in for `arpeggia.dsasa` (python.rs:161-191)."""
     del num_threads
     return get_dsasa(Structure.load(input_file), groups, probe_radius, n_points, model_num, radii=radii)
+
+
+# ---- buried surface per atom and residue; dSASA across frames (include/arpeggia_amd.h arp_structure_buried_sasa; no counterpart in the reference) ----
+BURIED_SASA_VALUE_COLUMNS = ["sasa_complex", "sasa_group1", "sasa_group2", "buried"]
+BURIED_ATOM_COLUMNS = ATOM_SASA_COLUMNS[:1] + ATOM_SASA_COLUMNS[2:] + ["group"] + BURIED_SASA_VALUE_COLUMNS
+BURIED_RESIDUE_COLUMNS = ["chain", "resn", "resi", "insertion", "group"] + BURIED_SASA_VALUE_COLUMNS + ["n_buried_atoms"]
+DSASA_FRAME_COLUMNS = ["frame", "total_complex", "total_group1", "total_group2", "dsasa"]
+DSASA_ENSEMBLE_COLUMNS = ["chain", "resn", "resi", "insertion", "altloc", "atomn", "atomi", "group", "n_frames", "buried_mean", "buried_std", "buried_min",
+                          "buried_max", "occupancy"]
+
+
+def _buried_sasa(ctx: "Context | None", structure: Structure, groups: str, probe_radius: float, n_points: int, model_num: int, radii) -> dict:
+    """arp_structure_buried_sasa.  ctx None: the checks that need no device run (raises their error, else the missing context's)."""
+    table = RADII_TABLES["vdw"] if radii is None else _radii_table(radii)
+    n = max(structure.n_atoms, 1)
+    atoms, grp, sasa_, count, buried = np.zeros(n, "<u4"), np.zeros(n, np.uint8), np.zeros(3 * n, "<f4"), np.zeros(3 * n, "<i4"), np.zeros(n, "<i4")
+    res_atoms, res_sasa, res_nb, totals = np.zeros(n, "<u4"), np.zeros(3 * n, "<f4"), np.zeros(n, "<u4"), np.zeros(4, "<f4")
+    rows, res_rows = C.c_uint64(), C.c_uint64()
+    fp, ip, up = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
+    _check(lib.arp_structure_buried_sasa(ctx._h if ctx is not None else None, structure._h, groups.encode(), C.c_float(probe_radius), int(n_points),
+                                         int(model_num), table, C.byref(rows), atoms.ctypes.data_as(up), grp.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                         sasa_.ctypes.data_as(fp), count.ctypes.data_as(ip), buried.ctypes.data_as(ip), C.byref(res_rows),
+                                         res_atoms.ctypes.data_as(up), res_sasa.ctypes.data_as(fp), res_nb.ctypes.data_as(up), totals.ctypes.data_as(fp)))
+    m, nr = int(rows.value), int(res_rows.value)
+    return {"atoms": atoms[:m].copy(), "group": grp[:m].copy(), "sasa": sasa_[: 3 * m].reshape(3, m).copy(), "count": count[: 3 * m].reshape(3, m).copy(),
+            "buried": buried[:m].copy(), "res_atoms": res_atoms[:nr].copy(), "res_sasa": res_sasa[: 3 * nr].reshape(3, nr).copy(),
+            "res_buried_atoms": res_nb[:nr].copy(), "totals": totals.copy(), "dsasa": float(totals[3])}
+
+
+def dsasa_total(total_complex: float, total_group1: float, total_group2: float) -> float:
+    """arp_dsasa_total: group 1 + group 2 - complex in f32, as get_dsasa forms its scalar; a negative value raises as there."""
+    out = C.c_float()
+    _check(lib.arp_dsasa_total(C.c_float(total_complex), C.c_float(total_group1), C.c_float(total_group2), C.byref(out)))
+    return float(out.value)
+
+
+def _buried_value_columns(group: np.ndarray, planes: np.ndarray) -> dict:
+    """group, sasa_complex, sasa_group1 / sasa_group2 (null where the row is not in the group) and buried = the non-null group values - complex, in f32."""
+    import pyarrow as pa
+
+    in1, in2 = (group & 1) != 0, (group & 2) != 0
+    own = np.where(in1, planes[1], np.float32(0.0)).astype(np.float32) + np.where(in2, planes[2], np.float32(0.0)).astype(np.float32)
+    return {"group": pa.array(group, pa.uint8()), "sasa_complex": pa.array(planes[0], pa.float32()), "sasa_group1": _nullable_f32(planes[1], in1),
+            "sasa_group2": _nullable_f32(planes[2], in2), "buried": pa.array((own - planes[0]).astype(np.float32), pa.float32())}
+
+
+def get_buried_sasa(structure: Structure, groups: str, level: str = "atom", probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0,
+                    radii=None, device: int = 0):
+    """The interface between two chain groups, row by row: returns (table, dsasa).  level "atom": one row per atom of the two groups (the rows
+    and order of get_atom_sasa on their chains) with the identity columns of get_atom_sasa, group (1, 2, 3 = in both), sasa_complex, sasa_group1,
+    sasa_group2 (null where the atom is not in the group) and buried (A^2, f32: the non-null group values - sasa_complex) -- BURIED_ATOM_COLUMNS.
+    level "residue": one row per residue (the rows and order of get_residue_sasa) with the same value columns from segment sums on the device and
+    n_buried_atoms (atoms with buried points) -- BURIED_RESIDUE_COLUMNS.  dsasa: the scalar of get_dsasa on the same arguments, bit for bit (a
+    negative value raises, as there).  radii: None (van der Waals) or a table name."""
+    import pyarrow as pa
+
+    lv = str(level).lower()
+    if lv not in ("atom", "residue"):
+        raise ValueError(f"Invalid level '{level}'. Must be one of: 'atom', 'residue'")
+    if radii is not None:
+        _radii_table(radii)
+    try:
+        ctx = _context(device)
+    except ArpeggiaError:
+        _buried_sasa(None, structure, groups, probe_radius, n_points, model_num, radii)  # an input error takes precedence over the missing device
+        raise
+    r = ctx.buried_sasa(structure, groups, probe_radius, n_points, model_num, radii)
+    if lv == "atom":
+        ident = _identity(structure, r["atoms"])
+        cols = {"atomi": ident["atomi"]}
+        cols.update({k: ident[k] for k in ATOM_SASA_COLUMNS[2:]})
+        cols.update(_buried_value_columns(r["group"], r["sasa"]))
+        return _frame(cols), r["dsasa"]
+    cols = _residue_identity(structure, r["res_atoms"])
+    by_atom = dict(zip(r["atoms"].tolist(), r["group"].tolist()))
+    cols.update(_buried_value_columns(np.array([by_atom[a] for a in r["res_atoms"].tolist()], np.uint8), r["res_sasa"]))
+    cols["n_buried_atoms"] = pa.array(r["res_buried_atoms"], pa.uint32())
+    return _frame(cols), r["dsasa"]
+
+
+def buried_sasa(input_file: str, groups: str, level: str = "atom", probe_radius: float = 1.4, n_points: int = 100, model_num: int = 0, radii=None):
+    """get_buried_sasa on a file: (table, dsasa)."""
+    return get_buried_sasa(Structure.load(input_file), groups, level, probe_radius, n_points, model_num, radii)
+
+
+def _dsasa_ensemble(ctx: "Context | None", structure: Structure, frames, groups: str, probe_radius: float, n_points: int, radii, per_frame: bool) -> dict:
+    """arp_dsasa_ensemble.  ctx None: the inputs are only checked (raises their error); the result then holds atoms, group, R and n_frames only."""
+    table = RADII_TABLES["vdw"] if radii is None else _radii_table(radii)
+    n_frames, ptr, keep = _frames_arg(structure, frames, "dsasa ensemble")
+    fp, ip, up, qp = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    rows, used = C.c_uint64(), C.c_uint64()
+    n = max(structure.n_atoms, 1)
+    atoms, grp, R = np.zeros(n, "<u4"), np.zeros(n, np.uint8), np.zeros(n, "<f4")
+    head = (structure._h, int(n_frames), ptr, groups.encode(), C.c_float(probe_radius), int(n_points), table, C.byref(rows), C.byref(used),
+            atoms.ctypes.data_as(up), grp.ctypes.data_as(C.POINTER(C.c_uint8)), R.ctypes.data_as(fp))
+    if ctx is None:
+        _check(lib.arp_dsasa_ensemble(None, *head, *([None] * 10)))
+        m = int(rows.value)
+        return {"atoms": atoms[:m].copy(), "group": grp[:m].copy(), "R": R[:m].copy(), "n_frames": int(used.value)}
+    n_top = _topology_atoms(structure)
+    f_cap = n_frames if frames is not None else (structure.n_atoms // n_top if n_top else 1)
+    s1, s2 = np.zeros(max(n_top, 1), "<u8"), np.zeros(max(n_top, 1), "<u8")
+    bmin, bmax, fb = np.zeros(max(n_top, 1), "<i4"), np.zeros(max(n_top, 1), "<i4"), np.zeros(max(n_top, 1), "<u4")
+    tot = {k: np.zeros(max(f_cap, 1), "<f4") for k in ("total_complex", "total_g1", "total_g2", "dsasa")}
+    per = np.zeros(max(f_cap * n_top, 1), "<i4") if per_frame else None
+    _check(lib.arp_dsasa_ensemble(ctx._h, *head, s1.ctypes.data_as(qp), s2.ctypes.data_as(qp), bmin.ctypes.data_as(ip), bmax.ctypes.data_as(ip),
+                                  fb.ctypes.data_as(up), *(tot[k].ctypes.data_as(fp) for k in tot), None if per is None else per.ctypes.data_as(ip)))
+    del keep
+    m, F = int(rows.value), int(used.value)
+    out = {"atoms": atoms[:m].copy(), "group": grp[:m].copy(), "R": R[:m].copy(), "n_frames": F, "sum_buried": s1[:m].copy(), "sum_buried_sq": s2[:m].copy(),
+           "min_buried": bmin[:m].copy(), "max_buried": bmax[:m].copy(), "frames_buried": fb[:m].copy()}
+    out.update({k: v[:F].copy() for k, v in tot.items()})
+    if per is not None:
+        out["buried"] = per[: F * m].reshape(F, m)
+    return out
+
+
+def dsasa_ensemble_stats(n_frames: int, radius_plus_probe, n_points: int, sum_buried, sum_buried_sq, min_buried, max_buried, frames_buried) -> dict:
+    """The per-atom columns of get_dsasa_ensemble from the integer accumulators of arp_dsasa_ensemble, on the host: buried_mean, buried_std
+    (population), buried_min, buried_max in A^2 -- sasa_ensemble_stats on the buried points, a point being 4 pi R^2 / n_points -- and
+    occupancy = frames_buried / n_frames (f64)."""
+    r = sasa_ensemble_stats(n_frames, radius_plus_probe, n_points, sum_buried, sum_buried_sq, min_buried, max_buried)
+    out = {"buried_mean": r["mean_sasa"], "buried_std": r["std_sasa"], "buried_min": r["min_sasa"], "buried_max": r["max_sasa"]}
+    out["occupancy"] = np.asarray(frames_buried, np.float64) / float(n_frames)
+    return out
+
+
+def get_dsasa_ensemble(structure: Structure, frames=None, groups: str = "/", probe_radius: float = 1.4, n_points: int = 100, radii=None,
+                       per_frame: bool = False, device: int = 0):
+    """dSASA across the frames of an ensemble, frames packed on the device in one call: returns (frame_table, atom_table).  frame_table: frame,
+    total_complex, total_group1, total_group2, dsasa (DSASA_FRAME_COLUMNS; a negative frame value is returned as it is).  atom_table: one row per
+    atom of the two groups with the identity columns, group, n_frames, buried_mean, buried_std, buried_min, buried_max (A^2) and occupancy = the
+    share of frames in which the atom has buried points (DSASA_ENSEMBLE_COLUMNS).  frames: [F, N, 3] f64 coordinates of the N atoms of model 0;
+    None: the structure's models are the frames.  per_frame=True adds a third value {"buried": [F, m] i32 points}."""
+    import pyarrow as pa
+
+    try:
+        ctx = _context(device)
+    except ArpeggiaError:
+        _dsasa_ensemble(None, structure, frames, groups, probe_radius, n_points, radii, False)  # an input error takes precedence over the missing device
+        raise
+    r = ctx.dsasa_ensemble(structure, frames, groups, probe_radius, n_points, radii, per_frame)
+    F = r["n_frames"]
+    ft = _frame({"frame": pa.array(np.arange(F, dtype="<u4"), pa.uint32()), "total_complex": pa.array(r["total_complex"], pa.float32()),
+                 "total_group1": pa.array(r["total_g1"], pa.float32()), "total_group2": pa.array(r["total_g2"], pa.float32()),
+                 "dsasa": pa.array(r["dsasa"], pa.float32())})
+    st = dsasa_ensemble_stats(F, r["R"], n_points, r["sum_buried"], r["sum_buried_sq"], r["min_buried"], r["max_buried"], r["frames_buried"])
+    ident = _identity(structure, r["atoms"])
+    cols = {k: ident[k] for k in DSASA_ENSEMBLE_COLUMNS[:7]}
+    cols["group"] = pa.array(r["group"], pa.uint8())
+    cols["n_frames"] = pa.array(np.full(len(r["atoms"]), F, "<u4"), pa.uint32())
+    for k in ("buried_mean", "buried_std", "buried_min", "buried_max"):
+        cols[k] = pa.array(st[k], pa.float32())
+    cols["occupancy"] = pa.array(st["occupancy"], pa.float64())
+    at = _frame(cols)
+    return (ft, at, {"buried": r["buried"]}) if per_frame else (ft, at)
+
+
+def dsasa_ensemble(input_file: str, groups: str, probe_radius: float = 1.4, n_points: int = 100, radii=None):
+    """dSASA across the models of a multi-model file: see get_dsasa_ensemble."""
+    return get_dsasa_ensemble(Structure.load(input_file), None, groups, probe_radius, n_points, radii)
 
 
 # ---- shape complementarity (reference src/sc/, python.rs:369-381; include/arpeggia_amd.h "shape complementarity")

@@ -232,6 +232,18 @@ void launch_ens_tile(uint32_t frames, const double *xyz, const EnsTopo &t, const
 // f32 of the f64 sum of sasa[f][:] in atom order for every frame of the pass
 void launch_ens_reduce(uint32_t frames, uint32_t m, const int32_t *count, const float *sasa, const float *sap, const EnsAcc &a, bool first, float *total,
                        hipStream_t st);
+// Buried surface (bsa.inl): the grid over the atoms without ARP_ATTR_H, whose group mask is ARP_ATTR_LIGAND (group 1) |
+// ARP_ATTR_RECEPTOR (group 2) of their attribute word, then one wave per grid atom.  sasa3 / count3: three planes of in.n entries (complex,
+// group 1, group 2), buried: in.n entries, all indexed like the input arrays (atoms outside the grid are not written).  Adds its f32 distance
+// tests to Workspace::result[kSasaTestsWord].
+void launch_sasa_split(const DevAtoms &in, const Workspace &ws, double cutoff, const float *R, const float *sphere, uint32_t n_points, float r_max,
+                       float *sasa3, int32_t *count3, int32_t *buried, hipStream_t st, Profiler *prof);
+// out[f * m + k] = attr[k]: the attribute words of a pass of packed frames
+void launch_bsa_tile_attr(uint32_t frames, uint32_t m, const uint32_t *attr, uint32_t *out, hipStream_t st);
+// folds the pass's buried ([frame][atom]) into a.s1 / s2 / cmin / cmax (k_ens_reduce as it is) and into frames_buried (frames with buried > 0),
+// and writes total[g][f] = the f32 of the f64 sum of plane g of sasa3 ([3][frame][atom]) over frame f in atom order (k_ens_totals as it is)
+void launch_bsa_ens_reduce(uint32_t frames, uint32_t m, const int32_t *buried, const float *sasa3, const EnsAcc &a, uint32_t *frames_buried, bool first,
+                           float *const total[3], hipStream_t st);
 // Segment sums (seg.inl).  All device pointers.
 struct SegCsr {           // n_seg segments over the items of a row: segment s lists item[start[s] .. start[s + 1]) in the order they are added
     uint32_t n_seg, n_long;

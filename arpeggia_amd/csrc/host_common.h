@@ -168,6 +168,39 @@ struct EnsOut {                            // m entries each unless noted; the S
     float *residue_sasa = nullptr;         // n_frames x res->n_seg, nullable
 };
 arp_status ens_run(arp_context *ctx, const EnsJob &job, const EnsOut &out);
+// Buried surface per atom (bsa.inl k_sasa_split): sasa_dev.cpp bsa_run, beside sasa_run and with its staging.
+struct BsaJob {
+    uint64_t n = 0;                        // atoms of the job, host arrays of n entries
+    const double *x = nullptr, *y = nullptr, *z = nullptr;  // f64 coordinates, rounded to f32 as sasa_run does
+    const float *R = nullptr;              // radius + probe in f32 (read where group != 0)
+    const uint8_t *group = nullptr;        // 0: not in the grid; bit 0: in group 1, bit 1: in group 2
+    const uint32_t *model = nullptr;       // slab of every atom; nullptr = all 0
+    bool per_model = false;                // every model gets its own origin (DevAtoms::per_model)
+    uint32_t n_points = 0;
+    const float *sphere = nullptr;
+    const SegJob *seg = nullptr;           // nullable: one CSR over the n atoms; SegJob::out receives 3 x n_seg sums (complex, group 1, group 2)
+};
+// sasa3 / count3 (nullable): 3 x n (complex, group 1, group 2; 0 where the atom is not in the group); buried (nullable): n.  One synchronisation.
+arp_status bsa_run(arp_context *ctx, const BsaJob &job, float *sasa3, int32_t *count3, int32_t *buried);
+// dSASA over the frames of an ensemble (arp_dsasa_ensemble): ens_run's scheme of passes with k_sasa_split on the pack
+struct BsaEnsJob {
+    uint64_t n_top = 0, m = 0, n_frames = 0;
+    const double *xyz = nullptr;           // n_frames x n_top x 3
+    const uint32_t *sel = nullptr;         // m topology indices, ascending
+    const float *R = nullptr;              // m: radius + probe
+    const uint8_t *group = nullptr;        // m: 1, 2 or 3
+    uint32_t n_points = 0;
+    const float *sphere = nullptr;
+    uint64_t chunk_atoms = 0;              // packed atoms per pass, 0: automatic
+};
+struct BsaEnsOut {
+    unsigned long long *s1 = nullptr, *s2 = nullptr;  // m: sum of buried, sum of buried^2 over the frames
+    int32_t *bmin = nullptr, *bmax = nullptr;         // m
+    uint32_t *frames_buried = nullptr;                // m: frames with buried > 0
+    float *total[3] = {nullptr, nullptr, nullptr};    // n_frames each: complex, group 1, group 2
+    int32_t *buried = nullptr;                        // n_frames x m, nullable
+};
+arp_status bsa_ens_run(arp_context *ctx, const BsaEnsJob &job, const BsaEnsOut &out);
 // table.cpp: model 0 of a structure as the topology of an ensemble (n0 atoms, r0 residues); with frames_from_models every further model must
 // repeat model 0's atoms one for one (ARP_ERR_BAD_INPUT naming the first model and atom that differ)
 arp_status freq_topology(const arp_structure *s, bool frames_from_models, uint64_t *n0, uint64_t *r0, uint64_t *n_models);

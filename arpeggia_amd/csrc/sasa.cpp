@@ -643,3 +643,150 @@ extern "C" arp_status arp_sasa_ensemble_residues(arp_context *ctx, const arp_str
     return sasa_ensemble_impl(ctx, s, n_frames, xyz, chains, probe, n_points, 0, 0.0f, table, &ro, n_rows, frames_used, nullptr, nullptr, nullptr, nullptr,
                               nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
 } ARP_ABI_CATCH
+
+// ---- buried surface per atom and residue, dSASA over the frames of an ensemble (kernel: bsa.inl k_sasa_split) -------------
+namespace {
+// groups -> the two chain sets of dsasa_impl (utils.rs:71-115, sasa.rs:411) and their union
+struct GroupSets { std::unordered_set<std::string> k1, k2, kc; };
+arp_status group_sets(const arp_structure *s, const char *groups, GroupSets *g) {
+    std::vector<std::string> g1, g2;
+    const arp_status st = parse_groups(s->chain_ids, groups, &g1, &g2);
+    if (st != ARP_OK) return st;
+    g->k1.insert(g1.begin(), g1.end()); g->k2.insert(g2.begin(), g2.end());
+    g->kc = g->k1; g->kc.insert(g2.begin(), g2.end());
+    return ARP_OK;
+}
+// the mask of a selected atom: membership of its chain (an empty set keeps every chain, as select_atoms reads it)
+uint8_t group_mask(const arp_structure *s, const GroupSets &g, uint32_t i) {
+    const std::string c(s->chain.at(i));
+    return (uint8_t)(((g.k1.empty() || g.k1.count(c)) ? 1u : 0u) | ((g.k2.empty() || g.k2.count(c)) ? 2u : 0u));
+}
+}  // namespace
+
+extern "C" arp_status arp_dsasa_total(float total_complex, float total_g1, float total_g2, float *out) {
+    if (!out) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    *out = total_g1 + total_g2 - total_complex;  // sasa.rs:450 (f32)
+    if (*out < 0.0f) { set_error("Negative dSASA calculated. Please check the input file and chain groups."); return ARP_ERR_BAD_INPUT; }
+    return ARP_OK;
+}
+
+extern "C" arp_status arp_structure_buried_sasa(arp_context *ctx, const arp_structure *s, const char *groups, float probe, int32_t n_points, int32_t model_num,
+                                                int32_t table, uint64_t *n_rows, uint32_t *out_atoms, uint8_t *out_group, float *out_sasa, int32_t *out_count,
+                                                int32_t *out_buried, uint64_t *n_res_rows, uint32_t *out_res_atoms, float *out_res_sasa,
+                                                uint32_t *out_res_buried_atoms, float *out_totals) try {
+    if (!s || !groups || !n_rows || !n_res_rows || !out_atoms || !out_group || !out_sasa || !out_count || !out_buried || !out_res_atoms || !out_res_sasa ||
+        !out_res_buried_atoms || !out_totals) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    *n_rows = 0; *n_res_rows = 0;
+    arp_status st = sasa_check_params(probe, n_points);
+    if (st != ARP_OK) return st;
+    if ((st = check_table(table)) != ARP_OK) return st;
+    GroupSets gs;
+    if ((st = group_sets(s, groups, &gs)) != ARP_OK) return st;
+    if (!ctx) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    // the rows: the union selection of dsasa_impl (remove_chains_by + get_chain_sasa's steps 2-4)
+    const std::vector<uint32_t> sel = select_atoms(s, gs.kc, true, true, false, model_num);
+    std::vector<float> R;
+    if ((st = radii(s, sel, probe, &R, table)) != ARP_OK) return st;
+    const uint64_t m = sel.size();
+    for (int g = 0; g < 4; g++) out_totals[g] = 0.0f;
+    if (m == 0) return ARP_OK;
+    const Segments res = build_segments(s, sel, false);
+    const uint64_t nr = res.first.size();
+    std::vector<double> x(m), y(m), z(m);
+    std::vector<float> Rm(m), sasa(3 * m), sphere(3ull * (uint32_t)n_points), rsum(3 * nr);
+    std::vector<int32_t> count(3 * m), buried(m);
+    std::vector<uint8_t> grp(m);
+    for (uint64_t k = 0; k < m; k++) { const uint32_t i = sel[k]; x[k] = s->x[i]; y[k] = s->y[i]; z[k] = s->z[i]; Rm[k] = R[i]; grp[k] = group_mask(s, gs, i); }
+    sasa_sphere_points((uint32_t)n_points, sphere.data());
+    SegJob sj;
+    sj.n_seg = (uint32_t)nr; sj.start = res.start.data(); sj.item = res.item.data(); sj.out = rsum.data();
+    BsaJob j;
+    j.n = m; j.x = x.data(); j.y = y.data(); j.z = z.data(); j.R = Rm.data(); j.group = grp.data(); j.n_points = (uint32_t)n_points; j.sphere = sphere.data();
+    j.seg = &sj;
+    if ((st = bsa_run(ctx, j, sasa.data(), count.data(), buried.data())) != ARP_OK) return st;
+    // the totals as dsasa_impl forms them: every sum in f64 in selection order (a non-member adds +0.0), one rounding to f32, then f32 arithmetic
+    double tot[3] = {0.0, 0.0, 0.0};
+    for (int g = 0; g < 3; g++) for (uint64_t k = 0; k < m; k++) tot[g] += (double)sasa[g * m + k];
+    out_totals[0] = (float)tot[0]; out_totals[1] = (float)tot[1]; out_totals[2] = (float)tot[2];
+    if ((st = arp_dsasa_total(out_totals[0], out_totals[1], out_totals[2], &out_totals[3])) != ARP_OK) return st;
+    std::vector<uint32_t> order(m);
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return s->serial[sel[a]] < s->serial[sel[b]]; });  // arp_structure_atom_sasa's order
+    for (uint64_t r = 0; r < m; r++) {
+        const uint32_t k = order[r];
+        out_atoms[r] = sel[k]; out_group[r] = grp[k]; out_buried[r] = buried[k];
+        for (int g = 0; g < 3; g++) { out_sasa[g * m + r] = sasa[g * m + k]; out_count[g * m + r] = count[g * m + k]; }
+    }
+    for (uint64_t r = 0; r < nr; r++) {
+        out_res_atoms[r] = res.first[r];
+        uint32_t nb = 0;
+        for (uint32_t q = res.start[r]; q < res.start[r + 1]; q++) nb += buried[res.item[q]] > 0;
+        out_res_buried_atoms[r] = nb;
+    }
+    std::copy(rsum.begin(), rsum.end(), out_res_sasa);
+    *n_rows = m; *n_res_rows = nr;
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+extern "C" arp_status arp_dsasa_ensemble(arp_context *ctx, const arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, float probe,
+                                         int32_t n_points, int32_t table, uint64_t *n_rows, uint64_t *frames_used, uint32_t *out_atoms, uint8_t *out_group,
+                                         float *out_R, uint64_t *sum_buried, uint64_t *sum_buried_sq, int32_t *min_buried, int32_t *max_buried,
+                                         uint32_t *frames_buried, float *total_complex, float *total_g1, float *total_g2, float *dsasa, int32_t *out_buried) try {
+    if (!s || !groups || !n_rows || !frames_used) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    *n_rows = 0; *frames_used = 0;
+    // validation: nothing here touches the device (sasa_ensemble_impl's checks)
+    uint64_t n0 = 0, r0 = 0, nm = 1;
+    arp_status st = freq_topology(s, xyz == nullptr, &n0, &r0, &nm);
+    if (st != ARP_OK) return st;
+    const uint64_t F = xyz ? n_frames : nm;
+    if (F == 0) { set_error("dsasa ensemble: at least one frame is needed"); return ARP_ERR_BAD_INPUT; }
+    if (n0 >= (1ull << 29)) { set_error("dsasa ensemble: the topology has %llu atoms, at most 2^29 - 1 are supported", (unsigned long long)n0); return ARP_ERR_BAD_INPUT; }
+    if (F > (1ull << 40) / std::max<uint64_t>(n0, 1)) { set_error("dsasa ensemble: too many frames"); return ARP_ERR_BAD_INPUT; }
+    if ((st = sasa_check_params(probe, n_points)) != ARP_OK) return st;
+    if ((st = check_table(table)) != ARP_OK) return st;
+    GroupSets gs;
+    if ((st = group_sets(s, groups, &gs)) != ARP_OK) return st;
+    std::vector<uint32_t> sel = select_atoms(s, gs.kc, true, false, false, 0);  // steps 1-3 on model 0's atoms (the prefix [0, n0))
+    while (!sel.empty() && sel.back() >= n0) sel.pop_back();
+    const uint64_t m = sel.size();
+    std::vector<float> R;
+    if ((st = radii(s, sel, probe, &R, table)) != ARP_OK) return st;
+    std::vector<double> model_xyz;
+    if (!xyz) {
+        model_xyz.resize(F * n0 * 3);
+        for (uint64_t a = 0; a < F * n0; a++) { model_xyz[3 * a] = s->x[a]; model_xyz[3 * a + 1] = s->y[a]; model_xyz[3 * a + 2] = s->z[a]; }
+    }
+    const double *frames = xyz ? xyz : model_xyz.data();
+    for (uint64_t f = 0; f < F; f++)
+        for (uint64_t k = 0; k < m; k++) {
+            const double *c = frames + 3 * (f * n0 + sel[k]);
+            if (!(std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]))) {
+                set_error("dsasa ensemble: non-finite coordinate in frame %llu, atom %llu", (unsigned long long)f, (unsigned long long)sel[k]);
+                return ARP_ERR_BAD_INPUT;
+            }
+        }
+    std::vector<float> Rm(m);
+    std::vector<uint8_t> grp(m);
+    for (uint64_t k = 0; k < m; k++) { Rm[k] = R[sel[k]]; grp[k] = group_mask(s, gs, sel[k]); }
+    *frames_used = F;
+    if (out_atoms) std::copy(sel.begin(), sel.end(), out_atoms);
+    if (out_group) std::copy(grp.begin(), grp.end(), out_group);
+    if (out_R) std::copy(Rm.begin(), Rm.end(), out_R);
+    if (!ctx) { *n_rows = m; return ARP_OK; }  // validation only: the selection and the frame count
+    if (!out_atoms || !out_group || !out_R || !sum_buried || !sum_buried_sq || !min_buried || !max_buried || !frames_buried || !total_complex || !total_g1 ||
+        !total_g2 || !dsasa) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    if (m == 0) { for (float *t : {total_complex, total_g1, total_g2, dsasa}) std::fill(t, t + F, 0.0f); return ARP_OK; }
+    std::vector<float> sphere(3ull * (uint32_t)n_points);
+    sasa_sphere_points((uint32_t)n_points, sphere.data());
+    BsaEnsJob j;
+    j.n_top = n0; j.m = m; j.n_frames = F; j.xyz = frames; j.sel = sel.data(); j.R = Rm.data(); j.group = grp.data(); j.n_points = (uint32_t)n_points;
+    j.sphere = sphere.data(); j.chunk_atoms = g_debug.ens_chunk_atoms > 0 ? (uint64_t)g_debug.ens_chunk_atoms : 0u;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "accumulator width");
+    BsaEnsOut o;
+    o.s1 = (unsigned long long *)sum_buried; o.s2 = (unsigned long long *)sum_buried_sq; o.bmin = min_buried; o.bmax = max_buried; o.frames_buried = frames_buried;
+    o.total[0] = total_complex; o.total[1] = total_g1; o.total[2] = total_g2; o.buried = out_buried;
+    if ((st = bsa_ens_run(ctx, j, o)) != ARP_OK) return st;
+    for (uint64_t f = 0; f < F; f++) dsasa[f] = total_g1[f] + total_g2[f] - total_complex[f];  // (f32; a negative frame value is returned as it is)
+    *n_rows = m;
+    return ARP_OK;
+} ARP_ABI_CATCH

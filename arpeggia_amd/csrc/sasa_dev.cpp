@@ -55,6 +55,21 @@ arp_status sasa_stage(arp_context *ctx, const DevAtoms &d, float r_max, const fl
     HIP_TRY(hipGetLastError());
     return ARP_OK;
 }
+// the same for the split kernel (bsa.inl): three planes of d.n areas and counts, and the buried points
+arp_status bsa_stage(arp_context *ctx, const DevAtoms &d, float r_max, const float *R, const float *sphere, uint32_t n_points, float *sasa3, int32_t *count3,
+                     int32_t *buried) {
+    arp_params prm;
+    arp_default_params(&prm);
+    prm.dist_cutoff = sasa_cutoff(r_max);
+    const arp_status s = upload_params(ctx, &prm);
+    if (s != ARP_OK) return s;
+    mark_grid_foreign(ctx);
+    launch_sasa_split(d, ctx->ws, prm.dist_cutoff, R, sphere, n_points, r_max, sasa3, count3, buried, ctx->stream, context_profiler(ctx));
+    HIP_TRY(hipGetLastError());
+    return ARP_OK;
+}
+// attribute word of the split kernel's grid: the group mask as the two set bits of the contact search (the grid build copies them into Fat::pw)
+uint32_t bsa_attr(uint8_t group) { return group ? ((group & 1u) ? ARP_ATTR_LIGAND : 0u) | ((group & 2u) ? ARP_ATTR_RECEPTOR : 0u) : ARP_ATTR_H; }
 // out[i] = the f32 sum of w[j] over the grid atoms j within sap_radius of grid atom i; code != nullptr: w is first derived from the SASA values
 arp_status sap_stage(arp_context *ctx, const DevAtoms &e, float sap_radius, const uint32_t *code, const int32_t *src, const float *sasa, float *w, float *out) {
     arp_params prm;
@@ -374,6 +389,145 @@ arp_status ens_run(arp_context *ctx, const EnsJob &j, const EnsOut &o) {
     }
     return ARP_OK;
 }
+
+// ---- buried surface per atom (bsa.inl) ----------------------------------------------------------------------------------
+arp_status bsa_run(arp_context *ctx, const BsaJob &j, float *sasa3, int32_t *count3, int32_t *buried) {
+    arp_status s = check_device(ctx);
+    if (s != ARP_OK) return s;
+    if (ctx->pending) { set_error("a call enqueued on this context has not been collected (arp_contacts_atomic_result)"); return ARP_ERR_BAD_INPUT; }
+    const uint64_t n = j.n;
+    if (n >= 0x5000000ull) { set_error("too many atoms for one SASA call (< 83886080)"); return ARP_ERR_BAD_INPUT; }
+    if (n == 0) return ARP_OK;
+    float r_max = 0.0f;
+    for (uint64_t i = 0; i < n; i++) {
+        if (!j.group[i]) continue;
+        if (!(std::isfinite(j.x[i]) && std::isfinite(j.y[i]) && std::isfinite(j.z[i]))) { set_error("non-finite atom coordinate"); return ARP_ERR_BAD_INPUT; }
+        r_max = std::max(r_max, j.R[i]);
+    }
+    // one pinned block out, one back (sasa_run's): inputs {f32-rounded x y z (f64), attr, zeros, model, R, sphere, [CSR]}, outputs {sasa x 3, count x 3, buried, [sums x 3]}
+    Carver lay;
+    const uint64_t o_x = lay.take(8 * n), o_y = lay.take(8 * n), o_z = lay.take(8 * n), o_attr = lay.take(4 * n), o_zero = lay.take(4 * n), o_model = lay.take(4 * n), o_R = lay.take(4 * n),
+                   o_sph = lay.take(12ull * j.n_points);
+    SegLayout seg;
+    if (j.seg) seg.take_csr(lay, *j.seg);
+    const uint64_t in_bytes = lay.off;
+    const uint64_t o_sasa = lay.take(12 * n), o_count = lay.take(12 * n), o_buried = lay.take(4 * n);
+    const uint64_t seg_out0 = lay.off;
+    if (j.seg) seg.o_out = lay.take(12ull * j.seg->n_seg);
+    const uint64_t out_bytes = lay.off - in_bytes;
+    char *dev = nullptr, *pin = nullptr;
+    if ((s = context_scratch(ctx, 0, lay.off, lay.off, &dev, &pin)) != ARP_OK) return s;
+    double *hx = (double *)(pin + o_x), *hy = (double *)(pin + o_y), *hz = (double *)(pin + o_z);
+    uint32_t *hattr = (uint32_t *)(pin + o_attr), *hmodel = (uint32_t *)(pin + o_model);
+    float *hR = (float *)(pin + o_R);
+    for (uint64_t i = 0; i < n; i++) {
+        hx[i] = (double)(float)j.x[i]; hy[i] = (double)(float)j.y[i]; hz[i] = (double)(float)j.z[i];  // sasa.rs:196-198
+        hattr[i] = bsa_attr(j.group[i]);
+        hmodel[i] = j.model ? j.model[i] : 0u;
+        hR[i] = j.group[i] ? j.R[i] : 0.0f;
+    }
+    memset(pin + o_zero, 0, 4 * n);
+    memcpy(pin + o_sph, j.sphere, 12ull * j.n_points);
+    if (j.seg) seg.fill(pin, *j.seg);
+    if ((s = ensure_workspace(ctx, n)) != ARP_OK) return s;
+    HIP_TRY(hipMemcpyAsync(dev, pin, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(dev + in_bytes, 0, out_bytes, ctx->stream));  // atoms outside the grid keep 0 everywhere
+    DevAtoms d{};
+    d.n = (uint32_t)n; d.per_model = j.per_model ? 1u : 0u;
+    d.x = (const double *)(dev + o_x); d.y = (const double *)(dev + o_y); d.z = (const double *)(dev + o_z);
+    d.attr = (const uint32_t *)(dev + o_attr); d.res_ord = d.chain_rank = (const uint32_t *)(dev + o_zero); d.model = (const uint32_t *)(dev + o_model);
+    float *d_sasa = (float *)(dev + o_sasa);
+    if ((s = bsa_stage(ctx, d, r_max, (const float *)(dev + o_R), (const float *)(dev + o_sph), j.n_points, d_sasa, (int32_t *)(dev + o_count), (int32_t *)(dev + o_buried))) != ARP_OK) return s;
+    HIP_TRY(hipMemcpyAsync(ctx->h_result + kHostSasaTestsSlot, ctx->ws.result + kSasaTestsWord, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    if (j.seg) {  // the three planes are three rows of n values
+        launch_segment_sum(3, (uint32_t)n, d_sasa, seg.csr(dev, *j.seg), (float *)(dev + seg.o_out), ctx->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    const uint64_t back0 = (sasa3 || count3 || buried) ? in_bytes : seg_out0;
+    if (lay.off > back0) HIP_TRY(hipMemcpyAsync(pin + back0, dev + back0, lay.off - back0, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (j.seg) memcpy(j.seg->out, pin + seg.o_out, 12ull * j.seg->n_seg);
+    ctx->sasa_tests = ctx->h_result[kHostSasaTestsSlot];
+    if (sasa3) memcpy(sasa3, pin + o_sasa, 12 * n);
+    if (count3) memcpy(count3, pin + o_count, 12 * n);
+    if (buried) memcpy(buried, pin + o_buried, 4 * n);
+    return ARP_OK;
+}
+
+// ens_run's scheme (passes of whole frames, model = frame, per_model, only coordinates cross PCIe per pass) with the split kernel on the pack:
+// k_ens_tile packs the frames, k_bsa_tile_attr repeats the masks, k_ens_reduce and k_ens_totals run as they are on what k_sasa_split writes.
+arp_status bsa_ens_run(arp_context *ctx, const BsaEnsJob &j, const BsaEnsOut &o) {
+    arp_status s = check_device(ctx);
+    if (s != ARP_OK) return s;
+    if (ctx->pending) { set_error("a call enqueued on this context has not been collected (arp_contacts_atomic_result)"); return ARP_ERR_BAD_INPUT; }
+    const uint64_t m = j.m, N = j.n_top, F = j.n_frames;
+    if (m == 0 || F == 0) return ARP_OK;
+    constexpr uint64_t kMaxPassAtoms = 0x5000000ull - 1u;
+    if (m > kMaxPassAtoms) { set_error("dsasa ensemble: too many selected atoms for one frame (< 83886080)"); return ARP_ERR_BAD_INPUT; }
+    const uint64_t budget = j.chunk_atoms ? j.chunk_atoms : kEnsAutoAtoms;
+    const uint64_t per = std::min<uint64_t>({std::max<uint64_t>(1, budget / m), F, 65535u, kMaxPassAtoms / m});
+    const uint64_t pn = per * m;
+    float r_max = 0.0f;
+    for (uint64_t k = 0; k < m; k++) r_max = std::max(r_max, j.R[k]);
+    // device block: {topology | accumulators + totals | one pass}; the pinned block repeats the first two at the same offsets and adds the staging
+    Carver lay;
+    const uint64_t o_sel = lay.take(4 * m), o_R = lay.take(4 * m), o_gattr = lay.take(4 * m), o_sph = lay.take(12ull * j.n_points);
+    const uint64_t topo_bytes = lay.off;
+    const uint64_t o_s1 = lay.take(8 * m), o_s2 = lay.take(8 * m), o_bmin = lay.take(4 * m), o_bmax = lay.take(4 * m), o_fb = lay.take(4 * m), o_total = lay.take(12 * F);
+    const uint64_t acc_bytes = lay.off - topo_bytes, shared_bytes = lay.off;
+    const uint64_t o_xyz = lay.take(24 * per * N), o_x = lay.take(8 * pn), o_y = lay.take(8 * pn), o_z = lay.take(8 * pn), o_attr = lay.take(4 * pn), o_zero = lay.take(4 * pn),
+                   o_model = lay.take(4 * pn), o_Rp = lay.take(4 * pn), o_sasa = lay.take(12 * pn), o_count = lay.take(12 * pn), o_buried = lay.take(4 * pn);
+    const uint64_t dev_bytes = lay.off;
+    lay.off = shared_bytes;
+    const uint64_t h_xyz = lay.take(24 * per * N), h_buried = o.buried ? lay.take(4 * pn) : 0;
+    const uint64_t pin_bytes = lay.off;
+    if ((s = ensure_workspace(ctx, pn)) != ARP_OK) return s;
+    char *dev = nullptr, *pin = nullptr;
+    if ((s = context_scratch(ctx, 0, dev_bytes, pin_bytes, &dev, &pin)) != ARP_OK) return s;
+    memcpy(pin + o_sel, j.sel, 4 * m); memcpy(pin + o_R, j.R, 4 * m); memcpy(pin + o_sph, j.sphere, 12ull * j.n_points);
+    uint32_t *ga = (uint32_t *)(pin + o_gattr);
+    for (uint64_t k = 0; k < m; k++) ga[k] = bsa_attr(j.group[k]);
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(dev, pin, topo_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(dev + o_zero, 0, 4 * pn, st));  // residue ordinal, chain rank
+    struct Event { hipEvent_t e = nullptr; ~Event() { if (e) (void)hipEventDestroy(e); } } staged;  // behind the upload of the staging buffer
+    HIP_TRY(hipEventCreateWithFlags(&staged.e, hipEventDisableTiming));
+    EnsTopo tp{(uint32_t)N, (uint32_t)m, (const uint32_t *)(dev + o_sel), (const float *)(dev + o_R), nullptr, nullptr};
+    EnsPack pk{};
+    pk.x = (double *)(dev + o_x); pk.y = (double *)(dev + o_y); pk.z = (double *)(dev + o_z);
+    pk.model = (uint32_t *)(dev + o_model); pk.R = (float *)(dev + o_Rp);
+    EnsAcc acc{(unsigned long long *)(dev + o_s1), (unsigned long long *)(dev + o_s2), (int32_t *)(dev + o_bmin), (int32_t *)(dev + o_bmax), nullptr, nullptr, nullptr, nullptr};
+    float *d_sasa = (float *)(dev + o_sasa);
+    int32_t *d_buried = (int32_t *)(dev + o_buried);
+    for (uint64_t f0 = 0; f0 < F; f0 += per) {
+        const uint64_t fc = std::min<uint64_t>(per, F - f0), cn = fc * m;
+        if (f0) HIP_TRY(hipEventSynchronize(staged.e));
+        memcpy(pin + h_xyz, j.xyz + f0 * N * 3, 24 * fc * N);
+        HIP_TRY(hipMemcpyAsync(dev + o_xyz, pin + h_xyz, 24 * fc * N, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(staged.e, st));
+        launch_ens_tile((uint32_t)fc, (const double *)(dev + o_xyz), tp, pk, st);
+        launch_bsa_tile_attr((uint32_t)fc, (uint32_t)m, (const uint32_t *)(dev + o_gattr), (uint32_t *)(dev + o_attr), st);
+        DevAtoms d{};
+        d.n = (uint32_t)cn; d.per_model = 1u;
+        d.x = pk.x; d.y = pk.y; d.z = pk.z;
+        d.attr = (const uint32_t *)(dev + o_attr); d.res_ord = d.chain_rank = (const uint32_t *)(dev + o_zero); d.model = pk.model;
+        if ((s = bsa_stage(ctx, d, r_max, pk.R, (const float *)(dev + o_sph), j.n_points, d_sasa, (int32_t *)(dev + o_count), d_buried)) != ARP_OK) return s;
+        float *const tot[3] = {(float *)(dev + o_total) + f0, (float *)(dev + o_total) + F + f0, (float *)(dev + o_total) + 2 * F + f0};
+        launch_bsa_ens_reduce((uint32_t)fc, (uint32_t)m, d_buried, d_sasa, acc, (uint32_t *)(dev + o_fb), f0 == 0, tot, st);
+        HIP_TRY(hipGetLastError());
+        if (o.buried) {  // the pass's own values, only when the caller wants them
+            HIP_TRY(hipMemcpyAsync(pin + h_buried, d_buried, 4 * cn, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            memcpy(o.buried + f0 * m, pin + h_buried, 4 * cn);
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(pin + topo_bytes, dev + topo_bytes, acc_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memcpy(o.s1, pin + o_s1, 8 * m); memcpy(o.s2, pin + o_s2, 8 * m); memcpy(o.bmin, pin + o_bmin, 4 * m); memcpy(o.bmax, pin + o_bmax, 4 * m);
+    memcpy(o.frames_buried, pin + o_fb, 4 * m);
+    for (int g = 0; g < 3; g++) memcpy(o.total[g], pin + o_total + 4 * F * g, 4 * F);
+    return ARP_OK;
+}
 }  // namespace arp
 
 extern "C" arp_status arp_sasa_sphere_points(uint32_t n, float *xyz) try {
@@ -410,6 +564,27 @@ extern "C" arp_status arp_atom_sasa(arp_context *ctx, uint64_t n, const double *
     j.n = n; j.x = x; j.y = y; j.z = z; j.R = R.data(); j.include = include; j.n_points = (uint32_t)n_points; j.sphere = sphere.data();
     std::vector<int32_t> cnt(out_count ? 0 : n);
     return sasa_run(ctx, j, out_sasa, out_count ? out_count : cnt.data(), nullptr);
+} ARP_ABI_CATCH
+
+extern "C" arp_status arp_atom_sasa_groups(arp_context *ctx, uint64_t n, const double *x, const double *y, const double *z, const float *radius,
+                                           const uint8_t *group, float probe, int32_t n_points, int32_t *out_count, float *out_sasa, int32_t *out_buried) try {
+    // (the argument checks come first: they need no device)
+    arp_status s = sasa_check_params(probe, n_points);
+    if (s != ARP_OK) return s;
+    if (n && (!x || !y || !z || !radius || !group || !out_count || !out_sasa || !out_buried)) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    std::vector<float> R(n, 0.0f);
+    for (uint64_t i = 0; i < n; i++) {
+        if (group[i] > 3u) { set_error("atom %llu: group mask %u is not one of 0 (out), 1, 2, 3 (both)", (unsigned long long)i, (unsigned)group[i]); return ARP_ERR_BAD_INPUT; }
+        if (!group[i]) continue;
+        if (!(std::isfinite(radius[i]) && radius[i] >= 0.0f)) { set_error("atom %llu: radius must be finite and >= 0", (unsigned long long)i); return ARP_ERR_BAD_INPUT; }
+        R[i] = radius[i] + probe;  // as arp_atom_sasa
+    }
+    if ((s = check_device(ctx)) != ARP_OK) return s;
+    std::vector<float> sphere(3ull * (uint32_t)n_points);
+    sasa_sphere_points((uint32_t)n_points, sphere.data());
+    BsaJob j;
+    j.n = n; j.x = x; j.y = y; j.z = z; j.R = R.data(); j.group = group; j.n_points = (uint32_t)n_points; j.sphere = sphere.data();
+    return bsa_run(ctx, j, out_sasa, out_count, out_buried);
 } ARP_ABI_CATCH
 
 extern "C" uint64_t arp_sasa_tests(const arp_context *ctx) { return ctx ? ctx->sasa_tests : 0u; }

@@ -506,6 +506,44 @@ arp_status arp_sasa_ensemble_residues(arp_context *ctx, const arp_structure *top
                                       uint8_t *out_is_polar, float *mean_sasa, float *std_sasa, float *min_sasa, float *max_sasa, float *mean_relative,
                                       uint8_t *relative_valid, uint32_t *out_chain_atoms, float *chain_sasa, float *residue_sasa);
 
+/* ---- buried surface per atom and residue, dSASA over the frames of an ensemble (no counterpart in the reference) ----
+ * Every atom carries a group mask: 0 = not in the calculation, bit 0 = in group 1, bit 1 = in group 2 (3 = in both).  With the burial test of
+ * arp_atom_sasa unchanged, one kernel walk gives atom i three counts of open points: against every other atom with a non-zero mask (the
+ * complex), against the other atoms of group 1, and against the other atoms of group 2; a group count is 0 where the atom is not in that
+ * group.  Areas are f32(4 pi R_i^2 count / n_points) as in arp_atom_sasa, and buried = the atom's own group counts minus its complex count,
+ * in points, >= 0.  The complex count equals arp_atom_sasa's on the union, a group count equals arp_atom_sasa's on that group alone, exactly.
+ * out_count / out_sasa: three planes of n entries (complex, group 1, group 2); out_buried: n.  Masks above 3 and a negative or non-finite radius
+ * of an atom with a non-zero mask are ARP_ERR_BAD_INPUT (checked before the device is touched), as is a call on a context with an uncollected
+ * enqueued call.  The atom limit is arp_atom_sasa's.  Synchronous. */
+arp_status arp_atom_sasa_groups(arp_context *ctx, uint64_t n, const double *x, const double *y, const double *z, const float *radius,
+                                const uint8_t *group, float probe, int32_t n_points, int32_t *out_count, float *out_sasa, int32_t *out_buried);
+/* The same on a structure, for the `groups` of arp_structure_dsasa (same selection, same group errors, the named radius table).  Rows: the atoms
+ * of the two groups' union in arp_structure_atom_sasa's order (by serial, stable); out_atoms (structure index), out_group (1, 2, 3), out_buried hold
+ * *n_rows entries, out_sasa / out_count three planes of *n_rows entries (complex, group 1, group 2).  Residue rows (arp_structure_residue_sasa's
+ * rows and order, over the union): out_res_atoms (first selected atom), out_res_sasa three planes of *n_res_rows sums (every sum the f64 chain
+ * of arp_segment_sum), out_res_buried_atoms (atoms of the residue with buried > 0).  out_totals[4]: complex, group 1, group 2 (each the f64
+ * sum in selection order rounded to f32 once) and group 1 + group 2 - complex in f32, which equals arp_structure_dsasa_radii on the same
+ * arguments bit for bit; a negative value is the same error.  Every array holds arp_structure_n_atoms entries (x 3 for the planes) at most.
+ * The checks that need no device (null arguments, n_points, probe, table, groups) run first, with ctx == NULL as well. */
+arp_status arp_structure_buried_sasa(arp_context *ctx, const arp_structure *s, const char *groups, float probe, int32_t n_points, int32_t model_num,
+                                     int32_t table, uint64_t *n_rows, uint32_t *out_atoms, uint8_t *out_group, float *out_sasa, int32_t *out_count,
+                                     int32_t *out_buried, uint64_t *n_res_rows, uint32_t *out_res_atoms, float *out_res_sasa,
+                                     uint32_t *out_res_buried_atoms, float *out_totals);
+/* The scalar of arp_structure_dsasa from its three totals: *out = total_g1 + total_g2 - total_complex in f32 (sasa.rs:450); a negative value
+ * is ARP_ERR_BAD_INPUT with the reference's message (*out is written all the same).  No device. */
+arp_status arp_dsasa_total(float total_complex, float total_g1, float total_g2, float *out);
+/* dSASA over the frames of an ensemble, frames packed on the device as in arp_sasa_ensemble (topology, n_frames, xyz, the pass size knob
+ * ens_chunk_atoms: as there; the selection is steps 1-3 of arp_structure_sasa_select on the union of the two groups).  Per selected atom:
+ * out_atoms, out_group, out_R (radius + probe), and over the frames in frame order the integer accumulators of buried (in points):
+ * sum_buried, sum_buried_sq, min_buried, max_buried, frames_buried (frames with buried > 0) -- arp_sasa_ensemble_stats turns the first four
+ * into areas.  Per frame: total_complex, total_g1, total_g2 (the f64 sum over the selection rounded to f32 once) and dsasa = g1 + g2 - complex
+ * in f32; a negative frame value is returned as it is.  out_buried (n_frames x *n_rows, nullable) is copied back per pass when given.
+ * ctx == NULL runs only the checks and writes *n_rows, *frames_used and (when given) out_atoms, out_group, out_R.  Synchronous. */
+arp_status arp_dsasa_ensemble(arp_context *ctx, const arp_structure *topology, uint64_t n_frames, const double *xyz, const char *groups, float probe,
+                              int32_t n_points, int32_t table, uint64_t *n_rows, uint64_t *frames_used, uint32_t *out_atoms, uint8_t *out_group,
+                              float *out_R, uint64_t *sum_buried, uint64_t *sum_buried_sq, int32_t *min_buried, int32_t *max_buried,
+                              uint32_t *frames_buried, float *total_complex, float *total_g1, float *total_g2, float *dsasa, int32_t *out_buried);
+
 /* The same 20 columns through the Arrow C Data Interface (a struct array = one record batch; utf8 strings, nullable
  * f32 sc_* columns): what pyo3-polars hands to Python in the reference (python.rs:55, mod.rs:140-214), importable with
  * zero per-row work by pyarrow / polars / arrow-rs (`FFI_ArrowArray`).  The exported arrays own copies of the columns:
