@@ -236,7 +236,7 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
         if (n_pairs > 0xFFFFFFF0ull) { set_error("contact frequencies: more than 2^32 pairs in one pass (lower freq_chunk_atoms)"); return ARP_ERR_CAPACITY; }
         if (n_pairs == 0) continue;
         // 3. expand into (key, value) items behind the aggregate; grown and repeated when they do not fit
-        if (!fb.block && (s = freq_alloc(&fb, std::max<uint64_t>(1u << 16, 2 * n_pairs), 0, st)) != ARP_OK) return s;
+        if (!fb.block && (s = freq_alloc(&fb, g_debug.freq_cap_items > 0 ? (uint64_t)g_debug.freq_cap_items : std::max<uint64_t>(1u << 16, 2 * n_pairs), 0, st)) != ARP_OK) return s;
         uint32_t n_items = 0;
         for (int attempt = 0;; attempt++) {
             HIP_TRY(hipMemsetAsync(fb.counter, 0, 4, st));

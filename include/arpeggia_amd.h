@@ -153,6 +153,8 @@ typedef struct arp_table arp_table;         /* the 20-column contact table (mod.
  *   "table_host"    1: only in the test library built with -DARP_WITH_HOST_TABLE (tests/hosttable): arp_get_contacts assembles the table on the host
  *   "freq_chunk_atoms" N > 0: arp_contact_frequencies runs its frames in passes of N atoms (whole frames, at least one per pass), so that tests can
  *                      force several passes; 0 (default): about 2 x 10^6 atoms per pass
+ *   "freq_cap_items" N > 0: the first buffers of arp_contact_frequencies hold N items (aggregate + one pass's items) instead of max(65536, 2 x pairs),
+ *                      so that tests can make the grow-and-repeat path run; 0 (default): automatic
  *   "ens_chunk_atoms" N > 0: arp_sasa_ensemble runs its frames in passes of N packed atoms (frames x selected atoms; whole frames, at least one per
  *                      pass), so that tests can force several passes; 0 (default): about 2 x 10^6 atoms per pass
  * Unknown keys return ARP_ERR_BAD_INPUT. */

@@ -52,6 +52,13 @@ def test_chunk_knob():
     refused(_lib.ARP_ERR_BAD_INPUT, aa.debug_set, "freq_chunk_atoms", -1)
 
 
+def test_cap_knob():
+    aa.debug_set("freq_cap_items", 1)
+    aa.debug_set("freq_cap_items", 0)
+    refused(_lib.ARP_ERR_BAD_INPUT, aa.debug_set, "freq_cap_items", -1)
+    assert "freq_cap_items" in refused(_lib.ARP_ERR_BAD_INPUT, aa.debug_set, "no_such_knob", 1)
+
+
 def test_exported():
     assert "arp_contact_frequencies" in _lib.EXPORTS
     assert [c for c, _ in aa.FREQ_COLUMNS][-4:] == ["n_frames", "frequency", "min_distance", "max_distance"]
