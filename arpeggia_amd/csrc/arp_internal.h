@@ -199,10 +199,13 @@ bool launch_emit(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsigne
 bool emit_takes_res_filter(const DevAtoms &in);  // the single-pass emitter has residue-rule kernels for an input of this size (the grid build then writes Sorted::rkey)
 unsigned long long emit_scratch_records();
 void launch_neighbor_sum(const DevAtoms &in, const Workspace &ws, double radius, double r2, const float *weight, float *out, hipStream_t st, Profiler *prof);
-// Atom SASA (sasa.inl): grid over the atoms without ARP_ATTR_H, then one wave per grid atom.  sasa / count are indexed like the input arrays
-// (atoms outside the grid are not written).  The kernel adds its number of f32 distance tests to Workspace::result[kSasaTestsWord].
+// Atom SASA (sasa.inl): the grid over the atoms without ARP_ATTR_H, then one wave per grid atom.  buried == nullptr: k_sasa; sasa / count hold
+// in.n entries.  buried != nullptr: k_sasa_split; the group mask of an atom is ARP_ATTR_LIGAND (group 1) |
+// ARP_ATTR_RECEPTOR (group 2) of its attribute word, sasa / count are three planes of in.n entries (complex, group 1, group 2), buried in.n
+// entries.  All indexed like the input arrays (atoms outside the grid are not written).  The kernel adds its number of f32 distance tests to
+// Workspace::result[kSasaTestsWord].
 void launch_sasa(const DevAtoms &in, const Workspace &ws, double cutoff, const float *R, const float *sphere, uint32_t n_points, float r_max,
-                 float *sasa, int32_t *count, hipStream_t st, Profiler *prof);
+                 float *sasa, int32_t *count, int32_t *buried, hipStream_t st, Profiler *prof);
 // w[j] = arp_sap_weight(ARP_SAP_RESIDUES name code[j], sasa[src[j]]), 0 where src[j] < 0 or code[j] >= 20
 void launch_sap_weight(uint32_t n, const uint32_t *code, const int32_t *src, const float *sasa, float *w, hipStream_t st);
 void launch_pack_fix(const PackArrays &pa, hipStream_t st);
@@ -232,13 +235,7 @@ void launch_ens_tile(uint32_t frames, const double *xyz, const EnsTopo &t, const
 // f32 of the f64 sum of sasa[f][:] in atom order for every frame of the pass
 void launch_ens_reduce(uint32_t frames, uint32_t m, const int32_t *count, const float *sasa, const float *sap, const EnsAcc &a, bool first, float *total,
                        hipStream_t st);
-// Buried surface (bsa.inl): the grid over the atoms without ARP_ATTR_H, whose group mask is ARP_ATTR_LIGAND (group 1) |
-// ARP_ATTR_RECEPTOR (group 2) of their attribute word, then one wave per grid atom.  sasa3 / count3: three planes of in.n entries (complex,
-// group 1, group 2), buried: in.n entries, all indexed like the input arrays (atoms outside the grid are not written).  Adds its f32 distance
-// tests to Workspace::result[kSasaTestsWord].
-void launch_sasa_split(const DevAtoms &in, const Workspace &ws, double cutoff, const float *R, const float *sphere, uint32_t n_points, float r_max,
-                       float *sasa3, int32_t *count3, int32_t *buried, hipStream_t st, Profiler *prof);
-// out[f * m + k] = attr[k]: the attribute words of a pass of packed frames
+// dSASA over frames (ens.inl).  out[f * m + k] = attr[k]: the attribute words of a pass of packed frames
 void launch_bsa_tile_attr(uint32_t frames, uint32_t m, const uint32_t *attr, uint32_t *out, hipStream_t st);
 // folds the pass's buried ([frame][atom]) into a.s1 / s2 / cmin / cmax (k_ens_reduce as it is) and into frames_buried (frames with buried > 0),
 // and writes total[g][f] = the f32 of the f64 sum of plane g of sasa3 ([3][frame][atom]) over frame f in atom order (k_ens_totals as it is)

@@ -1,5 +1,6 @@
 // SASA and SAP statistics over the frames of an ensemble (arp_sasa_ensemble).  Included by kernels.hip inside
-// namespace arp, after sasa.inl and sap.inl: k_sasa, k_sap_weight and k_neighbor_sum run unchanged on what k_ens_tile writes.
+// namespace arp, after sasa.inl and sap.inl: k_sasa, k_sap_weight and k_neighbor_sum run unchanged on what k_ens_tile writes.  The dSASA form
+// (arp_dsasa_ensemble) runs k_sasa_split on the same pack and adds k_bsa_tile_attr and k_bsa_frames_buried.
 //
 // The frames of a pass are the models of one packed input (model = frame ordinal inside the pass, DevAtoms::per_model: every frame gets its own
 // z slab of the grid and its own origin, so frames never see each other and a drifting trajectory does not inflate the cell count).  Only the
@@ -26,6 +27,13 @@ __global__ __launch_bounds__(256) void k_ens_tile(uint32_t frames, const double 
             p.src[q] = (int32_t)q;  // the weight of an atom comes from its own SASA of its own frame
         }
     }
+}
+
+// (dSASA form) attribute word of the packed atoms: item f * m + k gets the word of selected atom k (k_ens_tile writes everything else of the pack)
+__global__ __launch_bounds__(256) void k_bsa_tile_attr(uint32_t frames, uint32_t m, const uint32_t *attr, uint32_t *out) {
+    const unsigned long long total = (unsigned long long)frames * m;
+    for (unsigned long long q = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (unsigned long long)gridDim.x * blockDim.x)
+        out[q] = attr[(uint32_t)(q % m)];
 }
 
 // One thread per selected atom walks the frames of the pass in order (loads coalesced across atoms).  first: the call's first pass -- the
@@ -62,6 +70,17 @@ __global__ __launch_bounds__(256) void k_ens_reduce(uint32_t frames, uint32_t m,
     }
 }
 
+// (dSASA form) per selected atom the frames with buried > 0, over all frames so far; one thread owns one accumulator (k_ens_reduce's scheme)
+__global__ __launch_bounds__(256) void k_bsa_frames_buried(uint32_t frames, uint32_t m, const int32_t *buried, uint32_t *acc, uint32_t first) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= m) return;
+    uint32_t n = first ? 0u : acc[k];
+    const int32_t *bp = buried + k;
+#pragma unroll 4
+    for (uint32_t f = 0; f < frames; f++) n += bp[(unsigned long long)f * m] > 0 ? 1u : 0u;
+    acc[k] = n;
+}
+
 // total[f] = f32 of the f64 sum of sasa[f][0 .. m) in atom order (as arp_structure_dsasa sums its totals).  One wave per frame: the lanes load
 // 64 consecutive values at once, then every lane adds them up in lane order (the same uniform chain in all lanes); a lane past the end adds 0.0,
 // which leaves the non-negative sum unchanged.
@@ -92,4 +111,20 @@ void launch_ens_reduce(uint32_t frames, uint32_t m, const int32_t *count, const 
     if (!frames || !m) return;
     hipLaunchKernelGGL(k_ens_reduce, dim3((m + 255u) / 256u), dim3(256), 0, st, frames, m, count, sap, a, first ? 1u : 0u);
     hipLaunchKernelGGL(k_ens_totals, dim3((frames + 3u) / 4u), dim3(256), 0, st, frames, m, sasa, total);
+}
+
+void launch_bsa_tile_attr(uint32_t frames, uint32_t m, const uint32_t *attr, uint32_t *out, hipStream_t st) {
+    const unsigned long long items = (unsigned long long)frames * m;
+    if (!items) return;
+    hipLaunchKernelGGL(k_bsa_tile_attr, dim3((uint32_t)std::min<unsigned long long>((items + 255u) / 256u, 1u << 16)), dim3(256), 0, st, frames, m, attr, out);
+}
+
+void launch_bsa_ens_reduce(uint32_t frames, uint32_t m, const int32_t *buried, const float *sasa3, const EnsAcc &a, uint32_t *frames_buried, bool first,
+                           float *const total[3], hipStream_t st) {
+    if (!frames || !m) return;
+    const unsigned long long plane = (unsigned long long)frames * m;
+    hipLaunchKernelGGL(k_ens_reduce, dim3((m + 255u) / 256u), dim3(256), 0, st, frames, m, buried, (const float *)nullptr, a, first ? 1u : 0u);
+    hipLaunchKernelGGL(k_bsa_frames_buried, dim3((m + 255u) / 256u), dim3(256), 0, st, frames, m, buried, frames_buried, first ? 1u : 0u);
+    for (int g = 0; g < 3; g++)
+        hipLaunchKernelGGL(k_ens_totals, dim3((frames + 3u) / 4u), dim3(256), 0, st, frames, m, sasa3 + g * plane, total[g]);
 }

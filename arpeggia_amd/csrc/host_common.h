@@ -106,15 +106,18 @@ struct arp_structure {
 };
 
 namespace arp {
-// Atom SASA (+ the SAP chain) on the device: sasa_dev.cpp runs it, arp_atom_sasa and the structure-level entry points (sasa.cpp) fill the job.
-struct SasaJob {
-    uint64_t n = 0;                        // atoms of the job, host arrays of n entries
+// The atoms of one SASA run on the device (sasa_dev.cpp), host arrays of n entries: what sasa_run and bsa_run share.
+struct SasaAtoms {
+    uint64_t n = 0;
     const double *x = nullptr, *y = nullptr, *z = nullptr;  // f64 coordinates: SASA rounds them to f32, the SAP neighbour sum takes them as they are
-    const float *R = nullptr;              // radius + probe in f32 (read for the SASA atoms only)
-    const uint8_t *include = nullptr;      // the SASA atoms; the others get sasa 0, count 0
+    const float *R = nullptr;              // radius + probe in f32 (read for the atoms in the grid only)
     const uint32_t *model = nullptr;       // slab of every atom (dSASA runs three selections as three models of one grid); nullptr = all 0
     uint32_t n_points = 0;
     const float *sphere = nullptr;         // n_points x 3 unit vectors (sasa_sphere_points)
+};
+// Atom SASA (+ the SAP chain): sasa_dev.cpp runs it, arp_atom_sasa and the structure-level entry points (sasa.cpp) fill the job.
+struct SasaJob : SasaAtoms {
+    const uint8_t *include = nullptr;      // the SASA atoms; the others get sasa 0, count 0
     // SAP (src/sap.rs:137-250), when sidechain != nullptr: weight[j] = arp_sap_weight(residue code[j], sasa[src[j]]) (0 for src[j] < 0),
     // sap[i] = the f32 sum of the weights of the side-chain atoms within sap_radius of side-chain atom i (arp_sap_neighbor_sum)
     const uint8_t *sidechain = nullptr;
@@ -136,20 +139,23 @@ arp_status seg_check(uint64_t m, uint64_t n_seg, const uint32_t *start, const ui
 // sasa / count / sap (nullable) receive n entries; one synchronisation at the end.  Inputs are checked by the callers.  With all three null
 // only the segment sums come back.
 arp_status sasa_run(arp_context *ctx, const SasaJob &job, float *sasa, int32_t *count, float *sap);
-// SASA / SAP statistics over the frames of an ensemble (arp_sasa_ensemble, DESIGN.md section 3.8): sasa_dev.cpp ens_run packs the frames into
-// passes and runs them (kernels in ens.inl + the unchanged SASA / SAP kernels); sasa.cpp selects, checks and finishes.  Host arrays.
-struct EnsJob {
+// The frames of an ensemble run (sasa_dev.cpp EnsPasses), host arrays: what ens_run and bsa_ens_run share.
+struct EnsAtoms {
     uint64_t n_top = 0, m = 0, n_frames = 0;  // atoms a frame's coordinates cover, selected atoms, frames
     const double *xyz = nullptr;           // n_frames x n_top x 3
     const uint32_t *sel = nullptr;         // m topology indices, ascending
     const float *R = nullptr;              // m: radius + probe in f32
     uint32_t n_points = 0;
     const float *sphere = nullptr;
+    uint64_t chunk_atoms = 0;              // packed atoms per pass, 0: automatic
+};
+// SASA / SAP statistics over the frames of an ensemble (arp_sasa_ensemble, DESIGN.md section 3.8): sasa_dev.cpp ens_run packs the frames into
+// passes and runs them (kernels in ens.inl + the unchanged SASA / SAP kernels); sasa.cpp selects, checks and finishes.
+struct EnsJob : EnsAtoms {
     bool with_sap = false;
     const uint8_t *sidechain = nullptr;    // m (SAP)
     const uint32_t *res_code = nullptr;    // m (SAP): position in ARP_SAP_RESIDUES, >= 20: none
     float sap_radius = 0.0f;
-    uint64_t chunk_atoms = 0;              // packed atoms per pass, 0: automatic
     const SegJob *res = nullptr, *chain = nullptr;  // residue level (arp_sasa_ensemble_residues): the CSRs over the m selected atoms, both or none
 };
 struct EnsOut {                            // m entries each unless noted; the SAP members are written only with EnsJob::with_sap
@@ -168,30 +174,17 @@ struct EnsOut {                            // m entries each unless noted; the S
     float *residue_sasa = nullptr;         // n_frames x res->n_seg, nullable
 };
 arp_status ens_run(arp_context *ctx, const EnsJob &job, const EnsOut &out);
-// Buried surface per atom (bsa.inl k_sasa_split): sasa_dev.cpp bsa_run, beside sasa_run and with its staging.
-struct BsaJob {
-    uint64_t n = 0;                        // atoms of the job, host arrays of n entries
-    const double *x = nullptr, *y = nullptr, *z = nullptr;  // f64 coordinates, rounded to f32 as sasa_run does
-    const float *R = nullptr;              // radius + probe in f32 (read where group != 0)
+// Buried surface per atom (sasa.inl k_sasa_split): sasa_dev.cpp bsa_run, sasa_run's staging with the split walk.
+struct BsaJob : SasaAtoms {
     const uint8_t *group = nullptr;        // 0: not in the grid; bit 0: in group 1, bit 1: in group 2
-    const uint32_t *model = nullptr;       // slab of every atom; nullptr = all 0
     bool per_model = false;                // every model gets its own origin (DevAtoms::per_model)
-    uint32_t n_points = 0;
-    const float *sphere = nullptr;
     const SegJob *seg = nullptr;           // nullable: one CSR over the n atoms; SegJob::out receives 3 x n_seg sums (complex, group 1, group 2)
 };
 // sasa3 / count3 (nullable): 3 x n (complex, group 1, group 2; 0 where the atom is not in the group); buried (nullable): n.  One synchronisation.
 arp_status bsa_run(arp_context *ctx, const BsaJob &job, float *sasa3, int32_t *count3, int32_t *buried);
-// dSASA over the frames of an ensemble (arp_dsasa_ensemble): ens_run's scheme of passes with k_sasa_split on the pack
-struct BsaEnsJob {
-    uint64_t n_top = 0, m = 0, n_frames = 0;
-    const double *xyz = nullptr;           // n_frames x n_top x 3
-    const uint32_t *sel = nullptr;         // m topology indices, ascending
-    const float *R = nullptr;              // m: radius + probe
+// dSASA over the frames of an ensemble (arp_dsasa_ensemble): ens_run's passes with k_sasa_split on the pack
+struct BsaEnsJob : EnsAtoms {
     const uint8_t *group = nullptr;        // m: 1, 2 or 3
-    uint32_t n_points = 0;
-    const float *sphere = nullptr;
-    uint64_t chunk_atoms = 0;              // packed atoms per pass, 0: automatic
 };
 struct BsaEnsOut {
     unsigned long long *s1 = nullptr, *s2 = nullptr;  // m: sum of buried, sum of buried^2 over the frames

@@ -282,7 +282,6 @@ DEVFN float dist_f32(double s) {
 #include "sap.inl"
 #include "sasa.inl"
 #include "ens.inl"
-#include "bsa.inl"
 #include "seg.inl"
 #include "sc.inl"
 

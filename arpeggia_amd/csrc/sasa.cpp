@@ -541,6 +541,51 @@ static arp_status residue_ensemble(arp_context *ctx, const arp_structure *s, con
     return ARP_OK;
 }
 
+namespace {
+// What every ensemble entry point checks and selects before anything touches the device: model 0 as the topology, the frame count, the
+// parameters and the table, then keep(&chains) -- the entry point's own checks and its chain set (empty = all) --, steps 1-3 of
+// arp_structure_sasa_select on model 0's atoms (the prefix [0, n0) of the structure), their radii, the models as frames, finite coordinates.
+struct EnsInput {
+    uint64_t n0 = 0, F = 0;
+    std::vector<uint32_t> sel;       // ascending
+    std::vector<float> R;            // per structure atom: radius + probe of the selected ones
+    std::vector<double> model_xyz;   // the models' coordinates as F x n0 x 3 when no frames were given
+    const double *frames = nullptr;
+};
+template <class Keep>
+arp_status ensemble_input(const arp_structure *s, uint64_t n_frames, const double *xyz, float probe, int32_t n_points, int32_t table, const char *what, Keep keep,
+                          EnsInput *in) {
+    uint64_t r0 = 0, nm = 1;
+    arp_status st = freq_topology(s, xyz == nullptr, &in->n0, &r0, &nm);
+    if (st != ARP_OK) return st;
+    const uint64_t n0 = in->n0, F = in->F = xyz ? n_frames : nm;
+    if (F == 0) { set_error("%s: at least one frame is needed", what); return ARP_ERR_BAD_INPUT; }
+    if (n0 >= (1ull << 29)) { set_error("%s: the topology has %llu atoms, at most 2^29 - 1 are supported", what, (unsigned long long)n0); return ARP_ERR_BAD_INPUT; }
+    if (F > (1ull << 40) / std::max<uint64_t>(n0, 1)) { set_error("%s: too many frames", what); return ARP_ERR_BAD_INPUT; }
+    if ((st = sasa_check_params(probe, n_points)) != ARP_OK) return st;
+    if ((st = check_table(table)) != ARP_OK) return st;
+    std::unordered_set<std::string> chains;
+    if ((st = keep(&chains)) != ARP_OK) return st;
+    in->sel = select_atoms(s, chains, true, false, false, 0);
+    while (!in->sel.empty() && in->sel.back() >= n0) in->sel.pop_back();
+    if ((st = radii(s, in->sel, probe, &in->R, table)) != ARP_OK) return st;
+    if (!xyz) {
+        in->model_xyz.resize(F * n0 * 3);
+        for (uint64_t a = 0; a < F * n0; a++) { in->model_xyz[3 * a] = s->x[a]; in->model_xyz[3 * a + 1] = s->y[a]; in->model_xyz[3 * a + 2] = s->z[a]; }
+    }
+    in->frames = xyz ? xyz : in->model_xyz.data();
+    for (uint64_t f = 0; f < F; f++)
+        for (uint32_t i : in->sel) {
+            const double *c = in->frames + 3 * (f * n0 + i);
+            if (!(std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]))) {
+                set_error("%s: non-finite coordinate in frame %llu, atom %llu", what, (unsigned long long)f, (unsigned long long)i);
+                return ARP_ERR_BAD_INPUT;
+            }
+        }
+    return ARP_OK;
+}
+}  // namespace
+
 static arp_status sasa_ensemble_impl(arp_context *ctx, const arp_structure *s, uint64_t n_frames, const double *xyz, const char *chains, float probe,
                                      int32_t n_points, int32_t with_sap, float sap_radius, int32_t table, const ResidueEnsOut *ro, uint64_t *n_rows,
                                      uint64_t *frames_used, uint32_t *out_atoms, float *mean_sasa, float *std_sasa, float *min_sasa, float *max_sasa,
@@ -548,38 +593,17 @@ static arp_status sasa_ensemble_impl(arp_context *ctx, const arp_structure *s, u
     if (!s || !n_rows || !frames_used || (ro && !ro->n_chains)) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
     *n_rows = 0; *frames_used = 0;
     if (ro) *ro->n_chains = 0;
-    // validation: nothing here touches the device
-    uint64_t n0 = 0, r0 = 0, nm = 1;
-    arp_status st = freq_topology(s, xyz == nullptr, &n0, &r0, &nm);
+    // validation: nothing here touches the device.  (The table is checked before the SAP arguments: no entry point passes both.)
+    EnsInput in;
+    arp_status st = ensemble_input(s, n_frames, xyz, probe, n_points, table, "sasa ensemble", [&](std::unordered_set<std::string> *keep) {
+        if (with_sap && !(sap_radius >= 0.0f)) { set_error("bad sap_radius"); return ARP_ERR_BAD_INPUT; }
+        if (!with_sap && out_sap) { set_error("sasa ensemble: out_sap needs with_sap"); return ARP_ERR_BAD_INPUT; }
+        *keep = chain_set(chains);
+        return ARP_OK;
+    }, &in);
     if (st != ARP_OK) return st;
-    const uint64_t F = xyz ? n_frames : nm;
-    if (F == 0) { set_error("sasa ensemble: at least one frame is needed"); return ARP_ERR_BAD_INPUT; }
-    if (n0 >= (1ull << 29)) { set_error("sasa ensemble: the topology has %llu atoms, at most 2^29 - 1 are supported", (unsigned long long)n0); return ARP_ERR_BAD_INPUT; }
-    if (F > (1ull << 40) / std::max<uint64_t>(n0, 1)) { set_error("sasa ensemble: too many frames"); return ARP_ERR_BAD_INPUT; }
-    if ((st = sasa_check_params(probe, n_points)) != ARP_OK) return st;
-    if (with_sap && !(sap_radius >= 0.0f)) { set_error("bad sap_radius"); return ARP_ERR_BAD_INPUT; }
-    if (!with_sap && out_sap) { set_error("sasa ensemble: out_sap needs with_sap"); return ARP_ERR_BAD_INPUT; }
-    if ((st = check_table(table)) != ARP_OK) return st;
-    // steps 1-3 of arp_structure_sasa_select on model 0's atoms (the prefix [0, n0) of the structure)
-    std::vector<uint32_t> sel = select_atoms(s, chain_set(chains), true, false, false, 0);
-    while (!sel.empty() && sel.back() >= n0) sel.pop_back();  // (ascending)
+    const auto &[n0, F, sel, R, model_xyz, frames] = in;
     const uint64_t m = sel.size();
-    std::vector<float> R;
-    if ((st = radii(s, sel, probe, &R, table)) != ARP_OK) return st;
-    std::vector<double> model_xyz;
-    if (!xyz) {  // the models' coordinates as F x n0 x 3
-        model_xyz.resize(F * n0 * 3);
-        for (uint64_t a = 0; a < F * n0; a++) { model_xyz[3 * a] = s->x[a]; model_xyz[3 * a + 1] = s->y[a]; model_xyz[3 * a + 2] = s->z[a]; }
-    }
-    const double *frames = xyz ? xyz : model_xyz.data();
-    for (uint64_t f = 0; f < F; f++)
-        for (uint64_t k = 0; k < m; k++) {
-            const double *c = frames + 3 * (f * n0 + sel[k]);
-            if (!(std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]))) {
-                set_error("sasa ensemble: non-finite coordinate in frame %llu, atom %llu", (unsigned long long)f, (unsigned long long)sel[k]);
-                return ARP_ERR_BAD_INPUT;
-            }
-        }
     *frames_used = F;
     if (ro) return residue_ensemble(ctx, s, sel, R, F, n0, frames, probe, n_points, *ro, n_rows);
     if (out_atoms) std::copy(sel.begin(), sel.end(), out_atoms);
@@ -644,7 +668,7 @@ extern "C" arp_status arp_sasa_ensemble_residues(arp_context *ctx, const arp_str
                               nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
 } ARP_ABI_CATCH
 
-// ---- buried surface per atom and residue, dSASA over the frames of an ensemble (kernel: bsa.inl k_sasa_split) -------------
+// ---- buried surface per atom and residue, dSASA over the frames of an ensemble (kernel: sasa.inl k_sasa_split) -------------
 namespace {
 // groups -> the two chain sets of dsasa_impl (utils.rs:71-115, sasa.rs:411) and their union
 struct GroupSets { std::unordered_set<std::string> k1, k2, kc; };
@@ -734,37 +758,17 @@ extern "C" arp_status arp_dsasa_ensemble(arp_context *ctx, const arp_structure *
                                          uint32_t *frames_buried, float *total_complex, float *total_g1, float *total_g2, float *dsasa, int32_t *out_buried) try {
     if (!s || !groups || !n_rows || !frames_used) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
     *n_rows = 0; *frames_used = 0;
-    // validation: nothing here touches the device (sasa_ensemble_impl's checks)
-    uint64_t n0 = 0, r0 = 0, nm = 1;
-    arp_status st = freq_topology(s, xyz == nullptr, &n0, &r0, &nm);
-    if (st != ARP_OK) return st;
-    const uint64_t F = xyz ? n_frames : nm;
-    if (F == 0) { set_error("dsasa ensemble: at least one frame is needed"); return ARP_ERR_BAD_INPUT; }
-    if (n0 >= (1ull << 29)) { set_error("dsasa ensemble: the topology has %llu atoms, at most 2^29 - 1 are supported", (unsigned long long)n0); return ARP_ERR_BAD_INPUT; }
-    if (F > (1ull << 40) / std::max<uint64_t>(n0, 1)) { set_error("dsasa ensemble: too many frames"); return ARP_ERR_BAD_INPUT; }
-    if ((st = sasa_check_params(probe, n_points)) != ARP_OK) return st;
-    if ((st = check_table(table)) != ARP_OK) return st;
+    // validation: nothing here touches the device
     GroupSets gs;
-    if ((st = group_sets(s, groups, &gs)) != ARP_OK) return st;
-    std::vector<uint32_t> sel = select_atoms(s, gs.kc, true, false, false, 0);  // steps 1-3 on model 0's atoms (the prefix [0, n0))
-    while (!sel.empty() && sel.back() >= n0) sel.pop_back();
+    EnsInput in;
+    arp_status st = ensemble_input(s, n_frames, xyz, probe, n_points, table, "dsasa ensemble", [&](std::unordered_set<std::string> *keep) {
+        const arp_status g = group_sets(s, groups, &gs);
+        *keep = gs.kc;
+        return g;
+    }, &in);
+    if (st != ARP_OK) return st;
+    const auto &[n0, F, sel, R, model_xyz, frames] = in;
     const uint64_t m = sel.size();
-    std::vector<float> R;
-    if ((st = radii(s, sel, probe, &R, table)) != ARP_OK) return st;
-    std::vector<double> model_xyz;
-    if (!xyz) {
-        model_xyz.resize(F * n0 * 3);
-        for (uint64_t a = 0; a < F * n0; a++) { model_xyz[3 * a] = s->x[a]; model_xyz[3 * a + 1] = s->y[a]; model_xyz[3 * a + 2] = s->z[a]; }
-    }
-    const double *frames = xyz ? xyz : model_xyz.data();
-    for (uint64_t f = 0; f < F; f++)
-        for (uint64_t k = 0; k < m; k++) {
-            const double *c = frames + 3 * (f * n0 + sel[k]);
-            if (!(std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]))) {
-                set_error("dsasa ensemble: non-finite coordinate in frame %llu, atom %llu", (unsigned long long)f, (unsigned long long)sel[k]);
-                return ARP_ERR_BAD_INPUT;
-            }
-        }
     std::vector<float> Rm(m);
     std::vector<uint8_t> grp(m);
     for (uint64_t k = 0; k < m; k++) { Rm[k] = R[sel[k]]; grp[k] = group_mask(s, gs, sel[k]); }

@@ -12,7 +12,7 @@ import sasa_edge_cases as edge
 import sasa_restatement as sr
 
 FOUR_PI = 4.0 * 3.141592653589793
-PAIR_POINTS = (1, 63, 64, 65, 128, 257)  # one pass, the pass edge, more than four passes
+PAIR_POINTS = (1, 63, 64, 65, 128, 257, 4095, 4096)  # one pass, the pass edge, more than four passes, 64 passes (bit 63 of every buried word)
 PAIR_MASKS = ((1, 2), (2, 1), (3, 3), (1, 1))
 COINCIDENT_N = (300, 600, 1100)
 FILE_GROUPS = ("C/H,L", "H/L", "A,B/G", "/", "A,B/A,G", "C/")

@@ -1,4 +1,4 @@
-"""k_sasa_split (arpeggia_amd/csrc/bsa.inl) and what is built on it -- arp_atom_sasa_groups, arp_structure_buried_sasa, arp_dsasa_ensemble -- on
+"""k_sasa_split (arpeggia_amd/csrc/sasa.inl: the split instantiation of sasa_walk) and what is built on it -- arp_atom_sasa_groups, arp_structure_buried_sasa, arp_dsasa_ensemble -- on
 the MI355X.  The yardsticks are never the new kernel: counts come from the numpy restatement of the contract (tests/sasa_restatement.py through
 tests/bsa_common.py split_counts), for the decided edge cases from exact rational arithmetic (tests/sasa_edge_cases.py), and on the device from
 the existing atom_sasa / atom_sasa_rows / get_residue_sasa / get_dsasa run three times (union, group 1, group 2).  Every comparison is exact:

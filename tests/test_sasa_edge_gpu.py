@@ -1,4 +1,4 @@
-"""k_sasa (arpeggia_amd/csrc/sasa.inl) where the rest of the suite does not reach: the flush of the 256-entry neighbour list, the strict edge
+"""k_sasa (arpeggia_amd/csrc/sasa.inl: the plain instantiation of sasa_walk) where the rest of the suite does not reach: the flush of the 256-entry neighbour list, the strict edge
 d^2 < R_j^2 at point 0, placements within a few f32 steps of a neighbour's sphere, 64 passes of points, heterogeneous and zero radii, include
 masks, large extents, and the same kernel under the ensemble path and dSASA.  Everything is compared as integers and f32 bit patterns with the
 restatement of the contract (tests/sasa_restatement.py), which tests/test_sasa_edge_host.py holds to exact rational arithmetic on these very
