@@ -347,10 +347,12 @@ class Context:
         finally:
             lib.arp_table_free(t)
 
-    def contact_frequencies(self, structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5) -> dict:
-        """arp_contact_frequencies as a dict of numpy columns (FREQ_COLUMNS + from_atom / to_atom).  frames: [F, N, 3] f64 coordinates of the
-        topology's N atoms (model 0 of `structure`); None: the structure's models are the frames."""
-        t = _freq_table(self, structure, frames, groups, vdw_comp, dist_cutoff)
+    def contact_frequencies(self, structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, rings: bool = False) -> dict:
+        """arp_contact_frequencies_ex as a dict of numpy columns (FREQ_COLUMNS + from_atom / to_atom).  frames: [F, N, 3] f64 coordinates of the
+        topology's N atoms (model 0 of `structure`); None: the structure's models are the frames.  rings=True (ARP_FREQ_RINGS) adds the ring rows
+        (CationPi, Pi* stackings) behind the atom rows, and the columns from_ring / to_ring (ring entity index, -1 for an atom; from_atom /
+        to_atom are -1 for a ring)."""
+        t = _freq_table(self, structure, frames, groups, vdw_comp, dist_cutoff, rings)
         try:
             n = int(lib.arp_table_rows(t))
             cols = {}
@@ -371,6 +373,9 @@ class Context:
                     cols[name] = col(name, "<" + kind)
             cols["from_atom"] = col("from_atom", "<i4")
             cols["to_atom"] = col("to_atom", "<i4")
+            if rings:
+                cols["from_ring"] = col("from_ring", "<i4")
+                cols["to_ring"] = col("to_ring", "<i4")
             return cols
         finally:
             lib.arp_table_free(t)
@@ -415,12 +420,12 @@ def _topology_atoms(structure: Structure) -> int:
     return int(other[0]) if len(other) else len(m)
 
 
-def _freq_table(ctx: "Context | None", structure: Structure, frames, groups: str, vdw_comp: float, dist_cutoff: float):
-    """arp_contact_frequencies -> table handle (the caller frees it).  ctx None: the inputs are only checked (raises their error, else returns None)."""
+def _freq_table(ctx: "Context | None", structure: Structure, frames, groups: str, vdw_comp: float, dist_cutoff: float, rings: bool = False):
+    """arp_contact_frequencies_ex -> table handle (the caller frees it).  ctx None: the inputs are only checked (raises their error, else returns None)."""
     n_frames, ptr, keep = _frames_arg(structure, frames, "contact frequencies")
     t = C.c_void_p()
-    _check(lib.arp_contact_frequencies(ctx._h if ctx is not None else None, structure._h, int(n_frames), ptr, groups.encode(), float(vdw_comp),
-                                       float(dist_cutoff), C.byref(t)))
+    _check(lib.arp_contact_frequencies_ex(ctx._h if ctx is not None else None, structure._h, int(n_frames), ptr, groups.encode(), float(vdw_comp),
+                                          float(dist_cutoff), _lib.ARP_FREQ_RINGS if rings else 0, C.byref(t)))
     return t if ctx is not None else None
 
 
@@ -656,19 +661,21 @@ def contacts(input_file: str, groups: str = "/", vdw_comp: float = 0.1, dist_cut
     return get_contacts(s, groups, vdw_comp, dist_cutoff, num_threads=int(num_threads))
 
 
-def get_contact_frequencies(structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, device: int = 0):
-    """How often every atom-atom contact occurs across the frames of an ensemble (arp_contact_frequencies): one row per distinct
+def get_contact_frequencies(structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, device: int = 0,
+                            rings: bool = False):
+    """How often every atom-atom contact occurs across the frames of an ensemble (arp_contact_frequencies_ex): one row per distinct
     (from atom, to atom, interaction) with n_frames, frequency, min_distance and max_distance (FREQ_COLUMNS).  frames: [F, N, 3] f64
-    coordinates of the N atoms of the topology (model 0 of `structure`); None: the structure's models are the frames.  Returns a
-    polars.DataFrame when polars is importable, else a pyarrow.Table, like get_contacts."""
+    coordinates of the N atoms of the topology (model 0 of `structure`); None: the structure's models are the frames.  rings=True adds the
+    ring rows (CationPi, Pi* stackings; atomn "Ring", atomi 0) of every frame regarded as a single-model structure, behind the atom rows;
+    ring-ring rows do not depend on dist_cutoff.  Returns a polars.DataFrame when polars is importable, else a pyarrow.Table, like get_contacts."""
     import pyarrow as pa
 
     try:
         ctx = _context(device)
     except ArpeggiaError:
-        _freq_table(None, structure, frames, groups, vdw_comp, dist_cutoff)  # an input error takes precedence over the missing device
+        _freq_table(None, structure, frames, groups, vdw_comp, dist_cutoff, rings)  # an input error takes precedence over the missing device
         raise
-    t = _freq_table(ctx, structure, frames, groups, vdw_comp, dist_cutoff)
+    t = _freq_table(ctx, structure, frames, groups, vdw_comp, dist_cutoff, rings)
     try:
         arr, sch = _lib.ArrowArray(), _lib.ArrowSchema()
         _check(lib.arp_table_export_arrow(t, C.byref(arr), C.byref(sch)))
@@ -683,9 +690,11 @@ def get_contact_frequencies(structure: Structure, frames=None, groups: str = "/"
         return table
 
 
-def contact_frequencies(input_file: str, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, ignore_zero_occupancy: bool = False):
-    """Contact frequencies across the models of a multi-model file (NMR models, MODEL-record snapshots): see get_contact_frequencies."""
-    return get_contact_frequencies(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff)
+def contact_frequencies(input_file: str, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, ignore_zero_occupancy: bool = False,
+                        rings: bool = False):
+    """Contact frequencies across the models of a multi-model file (NMR models, MODEL-record snapshots): see get_contact_frequencies.  With
+    rings=True the rings are those of model 0 regarded as a single-model structure, not what get_contacts files for the multi-model file."""
+    return get_contact_frequencies(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings)
 
 
 def contacts_batch(input_files, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, ignore_zero_occupancy: bool = False,

@@ -116,6 +116,21 @@ __global__ __launch_bounds__(256) void k_freq_reduce(uint32_t m, const unsigned 
     if (t == 0u || keys[t - 1u] != keys[t]) out_keys[r] = keys[t];
 }
 
+// the ring items of a pass (ARP_FREQ_RINGS): the kernels are in freq_rings.inl, behind this file.  The topology's rings on the device: one plane
+// per ring residue (slot), one RingEnt per entity (src_res = slot; every altloc of a residue is an entity of its own that shares the residue's
+// plane), and the atoms a CationPi row can name.
+struct FreqRings {
+    uint32_t n_rings, n_slots, n_cand;
+    const uint32_t *res_atom_ptr, *res_atom_idx, *slot_res, *cand;
+    const uint8_t *plane_bits;
+    const RingEnt *rings;
+};
+constexpr uint32_t kFreqRingTile = 64;  // ring entities per workgroup of k_freq_ring_rows
+__global__ __launch_bounds__(128) void k_freq_ring_fit(uint32_t frames, uint32_t n, FreqRings r, const double *x, const double *y, const double *z, PlaneD *planes);
+__global__ __launch_bounds__(256) void k_freq_ring_rows(uint32_t n_tiles, uint32_t n, FreqRings r, const uint32_t *attr, const uint32_t *res_ord, const uint32_t *chain_rank, const double *x,
+                                 const double *y, const double *z, const PlaneD *planes, double cutoff, unsigned long long *keys, FreqVal *vals, uint32_t base, uint32_t cap,
+                                 uint32_t *counter);
+
 namespace {
 uint32_t freq_blocks(unsigned long long items) { return (uint32_t)std::max<unsigned long long>(1ull, (items + 255u) / 256u); }  // (items < 2^32: one thread each)
 
@@ -170,27 +185,32 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
     };
     *out = FreqRowsHost{};
     const uint64_t n = job.n, nr = job.n_res, nh = job.n_h, F = job.n_frames;
+    const uint64_t n_rings = job.n_rings, n_slots = job.n_slots, n_cand = job.n_cand, n_ra = n_rings ? job.res_atom_ptr[nr] : 0;
     if (n == 0 || F == 0) return ARP_OK;
     // frames per pass: the knob's atom budget, else kFreqAutoAtoms; never more frames than fit 32-bit packed indices
     const uint64_t budget = job.chunk_atoms ? job.chunk_atoms : kFreqAutoAtoms;
     uint64_t per = std::max<uint64_t>(1, budget / n);
     per = std::min<uint64_t>({per, F, 0x7FFFFFF0ull / std::max<uint64_t>({n, nr + 1, nh, 1}), 65535});
+    if (n_rings) per = std::min<uint64_t>(per, std::max<uint64_t>(1, 0x7FFFFFF0ull / std::max<uint64_t>({n_slots, (n_rings + kFreqRingTile - 1) / kFreqRingTile, 1})));  // (one thread per (frame, slot), one workgroup per (frame, tile))
     if (per == 0) { set_error("contact frequencies: one frame exceeds 32-bit indices"); return ARP_ERR_BAD_INPUT; }
     // topology (once) and the packed arrays of one pass
     struct Seg { const void *src; uint64_t bytes; };
-    const Seg topo_seg[8] = {{job.attr, n * 4}, {job.res_ord, n * 4}, {job.chain_rank, n * 4}, {nr ? job.res_id : nullptr, nr ? n * 4 : 0},
+    const Seg topo_seg[14] = {{job.attr, n * 4}, {job.res_ord, n * 4}, {job.chain_rank, n * 4}, {nr ? job.res_id : nullptr, nr ? n * 4 : 0},
                              {nr ? job.res_h_ptr : nullptr, nr ? (nr + 1) * 4 : 0}, {nh ? job.res_h_idx : nullptr, nh * 4}, {nr ? job.res_cb : nullptr, nr * 4},
-                             {nr ? job.res_sg : nullptr, nr * 4}};
+                             {nr ? job.res_sg : nullptr, nr * 4},
+                             // the rings of the topology (ARP_FREQ_RINGS; nothing otherwise)
+                             {job.rings, n_rings * sizeof(RingEnt)}, {job.slot_res, n_slots * 4}, {job.res_atom_ptr, n_rings ? (nr + 1) * 4 : 0}, {job.res_atom_idx, n_ra * 4},
+                             {job.cand, n_cand * 4}, {job.plane_bits, n_rings ? n : 0}};
     uint64_t topo_bytes = 0;
     for (const Seg &g : topo_seg) topo_bytes += seg_align(g.bytes);
     const uint64_t pn = per * n, pr = per * nr, ph = per * nh;
     const uint64_t pack_bytes = seg_align(pn * 24) + 3 * seg_align(pn * 8) + 5 * seg_align(pn * 4) + seg_align((pr + 1) * 4) + 2 * seg_align(pr * 4) + seg_align(ph * 4);
     char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, topo_bytes + pack_bytes + 256));
+    HIP_TRY(hipMalloc((void **)&block, topo_bytes + pack_bytes + seg_align(per * n_slots * sizeof(PlaneD)) + 256));
     std::unique_ptr<char, void (*)(char *)> block_owner(block, [](char *p) { (void)hipFree(p); });
     Bump bp{block};
-    const void *topo_dev[8];
-    for (int k = 0; k < 8; k++) {
+    const void *topo_dev[14];
+    for (int k = 0; k < 14; k++) {
         char *d = bp.take<char>(topo_seg[k].bytes);
         topo_dev[k] = d;
         if (topo_seg[k].bytes) HIP_TRY(hipMemcpyAsync(d, topo_seg[k].src, topo_seg[k].bytes, hipMemcpyHostToDevice, st));
@@ -203,14 +223,18 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
     pk.attr = bp.take<uint32_t>(pn); pk.res_ord = bp.take<uint32_t>(pn); pk.chain_rank = bp.take<uint32_t>(pn); pk.model = bp.take<uint32_t>(pn);
     pk.res_id = bp.take<uint32_t>(pn); pk.res_h_ptr = bp.take<uint32_t>(pr + 1); pk.res_cb = bp.take<uint32_t>(pr); pk.res_sg = bp.take<uint32_t>(pr);
     pk.res_h_idx = bp.take<uint32_t>(ph);
+    const FreqRings fr{(uint32_t)n_rings, (uint32_t)n_slots, (uint32_t)n_cand, (const uint32_t *)topo_dev[10], (const uint32_t *)topo_dev[11], (const uint32_t *)topo_dev[9],
+                       (const uint32_t *)topo_dev[12], (const uint8_t *)topo_dev[13], (const RingEnt *)topo_dev[8]};
+    PlaneD *planes = bp.take<PlaneD>(per * n_slots);  // one pass's ring planes, frames x slots
+    const uint32_t ring_tiles = (uint32_t)((n_rings + kFreqRingTile - 1) / kFreqRingTile);
     lap("topology upload");
     arp_params prm;
     arp_default_params(&prm);
     prm.vdw_comp = job.vdw_comp; prm.dist_cutoff = job.dist_cutoff;
     prm.flags |= ARP_FLAG_CONTACTS_ONLY;
-    // key bits: j in bits 5.., i in bits 34..; only the bits an index of n atoms can set are sorted
+    // key bits: j in bits 5.., i in bits 34..; only the bits an index of n atoms + n_rings rings can set are sorted
     int ibits = 1;
-    while (ibits < 29 && (1ull << ibits) < n) ibits++;
+    while (ibits < 29 && (1ull << ibits) < n + n_rings) ibits++;
     const int end_bit = (int)kFreqKeyShiftI + ibits;
     FreqBufs fb;
     struct FreeBufs { FreqBufs *b; ~FreeBufs() { if (b->block) (void)hipFree(b->block); } } fb_owner{&fb};
@@ -234,15 +258,28 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
         if (s != ARP_OK) return s;
         lap("pair pass");
         if (n_pairs > 0xFFFFFFF0ull) { set_error("contact frequencies: more than 2^32 pairs in one pass (lower freq_chunk_atoms)"); return ARP_ERR_CAPACITY; }
-        if (n_pairs == 0) continue;
-        // 3. expand into (key, value) items behind the aggregate; grown and repeated when they do not fit
+        if (n_pairs == 0 && !n_rings) continue;  // (ring - ring items need no atom pair: with rings no pass is skipped here)
+        if (n_rings) {  // the frames' ring planes
+            hipLaunchKernelGGL(k_freq_ring_fit, dim3((uint32_t)((fc * n_slots + 127u) / 128u)), dim3(128), 0, st, (uint32_t)fc, (uint32_t)n, fr, (const double *)pk.x, (const double *)pk.y,
+                               (const double *)pk.z, planes);
+            HIP_TRY(hipGetLastError());
+            lap("ring fit");
+        }
+        // 3. expand into (key, value) items behind the aggregate, the ring items behind the atom items; grown and repeated when they do not fit
         if (!fb.block && (s = freq_alloc(&fb, g_debug.freq_cap_items > 0 ? (uint64_t)g_debug.freq_cap_items : std::max<uint64_t>(1u << 16, 2 * n_pairs), 0, st)) != ARP_OK) return s;
         uint32_t n_items = 0;
         for (int attempt = 0;; attempt++) {
             HIP_TRY(hipMemsetAsync(fb.counter, 0, 4, st));
-            hipLaunchKernelGGL(k_freq_expand, dim3(freq_blocks(n_pairs)), dim3(256), 0, st, pairs, (uint32_t)n_pairs, (uint32_t)n, fb.kin, fb.vin, (uint32_t)n_agg,
-                               (uint32_t)fb.cap, fb.counter);
+            if (n_pairs) hipLaunchKernelGGL(k_freq_expand, dim3(freq_blocks(n_pairs)), dim3(256), 0, st, pairs, (uint32_t)n_pairs, (uint32_t)n, fb.kin, fb.vin, (uint32_t)n_agg,
+                                            (uint32_t)fb.cap, fb.counter);
             HIP_TRY(hipGetLastError());
+            if (n_rings) {
+                lap("expand");
+                hipLaunchKernelGGL(k_freq_ring_rows, dim3((uint32_t)fc * ring_tiles), dim3(256), 0, st, ring_tiles, (uint32_t)n, fr, tp.attr, tp.res_ord, tp.chain_rank,
+                                   (const double *)pk.x, (const double *)pk.y, (const double *)pk.z, (const PlaneD *)planes, job.dist_cutoff, fb.kin, fb.vin, (uint32_t)n_agg,
+                                   (uint32_t)fb.cap, fb.counter);
+                HIP_TRY(hipGetLastError());
+            }
             HIP_TRY(hipMemcpyAsync(&n_items, fb.counter, 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             if (n_agg + n_items <= fb.cap) break;
@@ -250,7 +287,7 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
             const uint64_t want = n_agg + n_items;
             if ((s = freq_alloc(&fb, want + want / 4, n_agg, st)) != ARP_OK) return s;
         }
-        lap("expand");
+        lap(n_rings ? "ring rows" : "expand");
         if (n_items == 0) continue;
         // 4. + 5. sort the aggregate and the new items together, reduce every run of equal keys to one
         const uint32_t m = (uint32_t)(n_agg + n_items);

@@ -149,15 +149,22 @@ static PlaneKey plane_key(int32_t model, const char *chain, int32_t resi, const 
 // no plane -- one model holds one residue per (chain, resi, icode), so no key can be written twice and no keyed lookup is needed.
 // has_plane[r]: the residue has >= 3 plane atoms (residues.rs:273: the only way a fit fails).  fitted == nullptr: the planes
 // themselves are fitted on the device (table_dev.hip); the entries then only say WHICH residue's plane an entity uses (e.res).
+// n_res_use < the structure's residues: only model 0 (its residues are that prefix), regarded as a single-model structure -- the topology of
+// arp_contact_frequencies_ex when the frames are the models of a file.
 static void build_planes(const arp_structure &s, bool rings, const std::vector<char> &has_plane, const std::vector<Plane> *fitted_in, std::vector<PlaneEntry> *out,
-                         PlaneIndex *index, std::vector<int64_t> *first_of_res) {
+                         PlaneIndex *index, std::vector<int64_t> *first_of_res, size_t n_res_use = SIZE_MAX) {
+    const bool model0_only = n_res_use < s.residues.size();
+    const size_t n_res = std::min(n_res_use, s.residues.size());
     std::vector<int32_t> serials;
-    for (const ChainInfo &c : s.chains) if (std::find(serials.begin(), serials.end(), c.model_serial) == serials.end()) serials.push_back(c.model_serial);
+    for (const ChainInfo &c : s.chains) {
+        if (model0_only && c.model_idx != 0u) continue;
+        if (std::find(serials.begin(), serials.end(), c.model_serial) == serials.end()) serials.push_back(c.model_serial);
+    }
     // res2idx: (model serial, chain, resi, icode) -> residue
     // With ONE model serial a plane entry can only resolve to the residue it was fitted from (the hierarchy holds one residue
     // per (chain, resi, icode)); the keyed lookup below is needed for multi-model files only.
     const bool one_model = serials.size() <= 1;
-    const bool direct = s.chains.empty() || s.chains.back().model_idx == 0;  // a single model in the file
+    const bool direct = model0_only || s.chains.empty() || s.chains.back().model_idx == 0;  // a single model in the file
     if (direct) first_of_res->assign(s.residues.size(), -1);
     std::unordered_map<PlaneKey, uint32_t, PlaneKeyHash> res_of;
     if (!one_model) {
@@ -173,7 +180,7 @@ static void build_planes(const arp_structure &s, bool rings, const std::vector<c
     static const std::vector<Plane> no_planes;
     const std::vector<Plane> &fitted = fitted_in ? *fitted_in : no_planes;
     for (int32_t m : serials)
-        for (uint32_t r = 0; r < s.residues.size(); r++) {
+        for (uint32_t r = 0; r < n_res; r++) {
             const ResidueInfo &ri = s.residues[r];
             if (!has_plane[r]) continue;
             const Plane pl = fitted_in ? fitted[r] : Plane{};
@@ -287,6 +294,7 @@ struct arp_table {
     StrCol<4> from_insertion, from_altloc, to_insertion, to_altloc;
     // contact-frequency table (arp_contact_frequencies): no model / distance / sc_* columns; these four instead, materialised when built
     bool freq = false;
+    std::vector<int32_t> from_ring, to_ring;   // ring entity index of the topology, -1 for an atom (arp_contact_frequencies_ex)
     std::vector<uint32_t> n_frames;
     std::vector<float> frequency, min_distance, max_distance;
 };
@@ -681,6 +689,8 @@ extern "C" const void *arp_table_column(const arp_table *t_const, const char *na
         if (c == "frequency") return num(t->frequency.data(), 4);
         if (c == "min_distance") return num(t->min_distance.data(), 4);
         if (c == "max_distance") return num(t->max_distance.data(), 4);
+        if (c == "from_ring") return num(t->from_ring.data(), 4);
+        if (c == "to_ring") return num(t->to_ring.data(), 4);
         if (c == "model" || c == "distance" || c.compare(0, 3, "sc_") == 0) return nullptr;
     }
     if (c == "model") return num(t->model.data(), 4);
@@ -1092,10 +1102,35 @@ arp_status freq_topology(const arp_structure *s, bool frames_from_models, uint64
 }
 }  // namespace arp
 
+namespace {
+// The ring entities of the topology (arp_contact_frequencies_ex): those arp_get_contacts builds for model 0 as a single-model structure, from the
+// table path's own builder.  A single-model structure's are the cached ones; model 0 of a multi-model file gets its own list (the cached one files
+// planes under every model serial: DESIGN.md section 3.7).
+struct FreqRingTopo {
+    std::vector<PlaneEntry> own;
+    const std::vector<PlaneEntry> *ents = nullptr;
+    std::vector<RingEnt> rings;        // src_res = slot
+    std::vector<uint32_t> slot_res, cand;
+};
+void freq_ring_entities(arp_structure *s, TableCache *c, uint64_t r0, FreqRingTopo *out) {
+    if (c->direct) { out->ents = &c->rings; return; }
+    PlaneIndex idx;
+    std::vector<int64_t> first;
+    build_planes(*s, true, c->has_ring, nullptr, &out->own, &idx, &first, (size_t)r0);
+    out->ents = &out->own;
+}
+}  // namespace
+
 extern "C" arp_status arp_contact_frequencies(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
-                                              double dist_cutoff, arp_table **out) try {
+                                              double dist_cutoff, arp_table **out) {
+    return arp_contact_frequencies_ex(ctx, s, n_frames, xyz, groups, vdw_comp, dist_cutoff, 0u, out);
+}
+
+extern "C" arp_status arp_contact_frequencies_ex(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
+                                                 double dist_cutoff, uint32_t flags, arp_table **out) try {
     if (!s || !out || !groups) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
     *out = nullptr;
+    if (flags & ~(uint32_t)ARP_FREQ_RINGS) { set_error("contact frequencies: unknown flag bits 0x%x", flags & ~(uint32_t)ARP_FREQ_RINGS); return ARP_ERR_BAD_INPUT; }
     // validation: nothing here touches the device
     uint64_t n0 = 0, r0 = 0, nm = 1;
     arp_status st = freq_topology(s, xyz == nullptr, &n0, &r0, &nm);
@@ -1123,15 +1158,28 @@ extern "C" arp_status arp_contact_frequencies(arp_context *ctx, arp_structure *s
     // the ligand / receptor bits of this chain-group spec, with the errors of arp_get_contacts (utils.rs:71-115); the structure's own attribute
     // words are left alone (a table call on it may be using them)
     std::vector<uint32_t> attr(n0);
+    std::vector<uint32_t> bits(s->chain_ids.size(), 0);
     {
         std::vector<std::string> L, R;
         if ((st = parse_groups(s->chain_ids, groups, &L, &R)) != ARP_OK) return st;
-        std::vector<uint32_t> bits(s->chain_ids.size(), 0);
         for (size_t k = 0; k < s->chain_ids.size(); k++) {
             if (std::binary_search(L.begin(), L.end(), s->chain_ids[k])) bits[k] |= ARP_ATTR_LIGAND;
             if (std::binary_search(R.begin(), R.end(), s->chain_ids[k])) bits[k] |= ARP_ATTR_RECEPTOR;
         }
         for (uint64_t a = 0; a < n0; a++) attr[a] = s->base_attr[a] | bits[s->chain_rank[a]];
+    }
+    // ARP_FREQ_RINGS: the topology's ring entities, as entities n0 .. n0 + n_rings - 1 (a topology without rings is the table without rings)
+    FreqRingTopo rt;
+    TableCache *cache = nullptr;
+    uint64_t n_rings = 0;
+    if (flags & ARP_FREQ_RINGS) {
+        cache = table_cache_of(s);
+        freq_ring_entities(s, cache, r0, &rt);
+        n_rings = rt.ents->size();
+        if (n0 + n_rings >= (1ull << 29)) {
+            set_error("contact frequencies: the topology has %llu atoms and %llu rings, at most 2^29 - 1 entities are supported", (unsigned long long)n0, (unsigned long long)n_rings);
+            return ARP_ERR_BAD_INPUT;
+        }
     }
     if (!ctx) return ARP_OK;  // validation only
     FreqJob job;
@@ -1140,6 +1188,21 @@ extern "C" arp_status arp_contact_frequencies(arp_context *ctx, arp_structure *s
     job.res_h_ptr = s->res_h_ptr.data(); job.res_h_idx = s->res_h_idx.data(); job.res_cb = s->res_cb.data(); job.res_sg = s->res_sg.data();
     job.xyz = frames; job.vdw_comp = vdw_comp; job.dist_cutoff = dist_cutoff;
     job.chunk_atoms = g_debug.freq_chunk_atoms > 0 ? (uint64_t)g_debug.freq_chunk_atoms : 0u;
+    if (n_rings) {
+        std::unordered_map<std::string, uint32_t> rank;
+        for (size_t k = 0; k < s->chain_ids.size(); k++) rank[s->chain_ids[k]] = (uint32_t)k;
+        rt.rings.resize(n_rings);
+        for (uint64_t k = 0; k < n_rings; k++) {  // (the entities of a residue follow each other: one slot per residue)
+            const PlaneEntry &e = (*rt.ents)[k];
+            if (rt.slot_res.empty() || rt.slot_res.back() != e.res) rt.slot_res.push_back(e.res);
+            const uint32_t cr = rank[e.chain], cb = bits[cr];
+            rt.rings[k] = RingEnt{(uint32_t)rt.slot_res.size() - 1u, 0, 0u, cr, ((cb & ARP_ATTR_LIGAND) ? 1u : 0u) | ((cb & ARP_ATTR_RECEPTOR) ? 2u : 0u) | (e.has_ord ? 4u : 0u), e.ord, ARP_NONE, 0u};
+        }
+        for (uint64_t a = 0; a < n0; a++) if ((attr[a] & ARP_ATTR_POS_RESN) && !(attr[a] & ARP_ATTR_H)) rt.cand.push_back((uint32_t)a);  // what the pair pass's cell list holds of them
+        job.n_rings = n_rings; job.n_slots = rt.slot_res.size(); job.n_cand = rt.cand.size();
+        job.rings = rt.rings.data(); job.slot_res = rt.slot_res.data(); job.cand = rt.cand.data();
+        job.res_atom_ptr = cache->res_atom_ptr.data(); job.res_atom_idx = cache->res_atom_idx.data(); job.plane_bits = cache->plane_bits.data();
+    }
     FreqRowsHost rows;
     if ((st = device_frequencies(ctx, job, &rows)) != ARP_OK) return st;
     // the table: identity strings of the rows' atoms from the topology
@@ -1152,17 +1215,33 @@ extern "C" arp_status arp_contact_frequencies(arp_context *ctx, arp_structure *s
     t->from_insertion.resize(nrow); t->from_altloc.resize(nrow); t->to_insertion.resize(nrow); t->to_altloc.resize(nrow);
     t->n_frames = std::move(rows.count); t->min_distance = std::move(rows.mn); t->max_distance = std::move(rows.mx);
     t->frequency.resize(nrow);
+    t->from_ring.assign(nrow, -1); t->to_ring.assign(nrow, -1);
+    // a ring entity's identity: what get_contacts writes (the entity book, complex.rs:334-342) -- atomn "Ring", atomi 0, no atom index
+    auto ring_identity = [&](uint32_t e, char *chain, char *resn, char *atomn, char *ins, char *alt, int32_t *resi, int32_t *atomi, int32_t *atom, int32_t *ring) {
+        const PlaneEntry &r = (*rt.ents)[e];
+        auto put = [](char *dst, size_t cap, const std::string &v) { memset(dst, 0, cap); memcpy(dst, v.data(), std::min(cap - 1, v.size())); };
+        put(chain, 8, r.chain); put(resn, 8, r.resn); put(atomn, 8, "Ring"); put(ins, 4, r.icode); put(alt, 4, r.altloc);
+        *resi = r.resi; *atomi = 0; *atom = -1; *ring = (int32_t)e;
+    };
     for (size_t k = 0; k < nrow; k++) {
         const unsigned long long key = rows.key[k];
         const uint32_t i = (uint32_t)(key >> 34), j = (uint32_t)((key >> 5) & ((1ull << 29) - 1u)), code = (uint32_t)(key & 31u);
         t->interaction[k] = (int32_t)code;
         t->frequency[k] = (float)((double)t->n_frames[k] / (double)F);
-        memcpy(t->from_chain.at(k), s->chain.at(i), 8); memcpy(t->from_resn.at(k), s->res_resn.at(i), 8); memcpy(t->from_atomn.at(k), s->name.at(i), 8);
-        memcpy(t->from_insertion.at(k), s->icode.at(i), 4); memcpy(t->from_altloc.at(k), s->altloc.at(i), 4);
-        t->from_resi[k] = s->resi[i]; t->from_atomi[k] = s->serial[i]; t->from_atom[k] = (int32_t)i;
-        memcpy(t->to_chain.at(k), s->chain.at(j), 8); memcpy(t->to_resn.at(k), s->res_resn.at(j), 8); memcpy(t->to_atomn.at(k), s->name.at(j), 8);
-        memcpy(t->to_insertion.at(k), s->icode.at(j), 4); memcpy(t->to_altloc.at(k), s->altloc.at(j), 4);
-        t->to_resi[k] = s->resi[j]; t->to_atomi[k] = s->serial[j]; t->to_atom[k] = (int32_t)j;
+        if (i >= n0) ring_identity(i - (uint32_t)n0, t->from_chain.at(k), t->from_resn.at(k), t->from_atomn.at(k), t->from_insertion.at(k), t->from_altloc.at(k), &t->from_resi[k],
+                                   &t->from_atomi[k], &t->from_atom[k], &t->from_ring[k]);
+        else {
+            memcpy(t->from_chain.at(k), s->chain.at(i), 8); memcpy(t->from_resn.at(k), s->res_resn.at(i), 8); memcpy(t->from_atomn.at(k), s->name.at(i), 8);
+            memcpy(t->from_insertion.at(k), s->icode.at(i), 4); memcpy(t->from_altloc.at(k), s->altloc.at(i), 4);
+            t->from_resi[k] = s->resi[i]; t->from_atomi[k] = s->serial[i]; t->from_atom[k] = (int32_t)i;
+        }
+        if (j >= n0) ring_identity(j - (uint32_t)n0, t->to_chain.at(k), t->to_resn.at(k), t->to_atomn.at(k), t->to_insertion.at(k), t->to_altloc.at(k), &t->to_resi[k], &t->to_atomi[k],
+                                   &t->to_atom[k], &t->to_ring[k]);
+        else {
+            memcpy(t->to_chain.at(k), s->chain.at(j), 8); memcpy(t->to_resn.at(k), s->res_resn.at(j), 8); memcpy(t->to_atomn.at(k), s->name.at(j), 8);
+            memcpy(t->to_insertion.at(k), s->icode.at(j), 4); memcpy(t->to_altloc.at(k), s->altloc.at(j), 4);
+            t->to_resi[k] = s->resi[j]; t->to_atomi[k] = s->serial[j]; t->to_atom[k] = (int32_t)j;
+        }
     }
     *out = t.release();
     return ARP_OK;

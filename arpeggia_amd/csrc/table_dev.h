@@ -70,7 +70,7 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
 arp_status device_planes(arp_context *ctx, const DevStructure &ds, std::vector<double> *planes, std::vector<uint8_t> *valid);
 
 // Contact frequencies over frames (freq.inl, arp_contact_frequencies): the topology's arrays (host, the chain groups applied to attr) and
-// n_frames x n x 3 f64 coordinates.  Rows come back sorted by key = i << 34 | j << 5 | interaction code.
+// n_frames x n x 3 f64 coordinates.  Rows come back sorted by key = i << 34 | j << 5 | interaction code (i, j: entities -- atoms, or n + ring).
 struct FreqJob {
     uint64_t n = 0, n_res = 0, n_h = 0, n_frames = 0;
     const uint32_t *attr = nullptr, *res_ord = nullptr, *chain_rank = nullptr, *res_id = nullptr, *res_h_ptr = nullptr, *res_h_idx = nullptr,
@@ -78,6 +78,13 @@ struct FreqJob {
     const double *xyz = nullptr;
     double vdw_comp = 0.1, dist_cutoff = 6.5;
     uint64_t chunk_atoms = 0;  // atoms per pass, 0 = automatic (arp_debug_set "freq_chunk_atoms")
+    // ARP_FREQ_RINGS (freq_rings.inl), n_rings > 0: the topology's ring entities as entities n .. n + n_rings - 1.  rings[e].src_res is a SLOT:
+    // the ring residues in order, slot_res[k] the residue of slot k; res_atom_ptr / res_atom_idx / plane_bits as DevStructure holds them, cut
+    // to model 0; cand: the atoms a CationPi row can name (ARP_ATTR_POS_RESN, not ARP_ATTR_H), ascending
+    uint64_t n_rings = 0, n_slots = 0, n_cand = 0;
+    const RingEnt *rings = nullptr;
+    const uint32_t *slot_res = nullptr, *res_atom_ptr = nullptr, *res_atom_idx = nullptr, *cand = nullptr;
+    const uint8_t *plane_bits = nullptr;
 };
 struct FreqRowsHost {
     std::vector<unsigned long long> key;

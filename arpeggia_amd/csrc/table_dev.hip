@@ -113,6 +113,24 @@ __device__ inline bool compare_residues_d(const ResKeyD &a, const ResKeyD &b, bo
     return !(symmetric && a.in_r && b.in_r && a.in_l && b.in_l && a.chain_rank > b.chain_rank);
 }
 
+// The two ring classifications, shared by the table kernels below and the per-frame kernels of freq_rings.inl: one body each, so that a
+// frame's ring items are the table's ring rows by construction.
+// find_cation_pi (aromatic.rs:14-29): q = a positively ionizable atom near the ring; *dist = its distance from the ring centre
+__device__ inline bool cation_pi_d(const PlaneD &pl, const double q[3], double *dist) {
+    const double d = point_dist_d(pl, q), theta = point_angle_d(pl, q);
+    *dist = d;
+    return theta <= 30.0 && d <= 4.5;
+}
+// find_pi_pi (aromatic.rs:33-64): the stacking ladder of two rings whose centres are `dist` apart; -1 = none
+__device__ inline int pi_stacking_d(const PlaneD &p1, const PlaneD &p2, double dist) {
+    const double theta = point_angle_d(p1, p2.c), dih = plane_dihedral_d(p1, p2);
+    int code = -1;
+    if (dih <= 30.0) { if (theta <= 30.0) code = ARP_PiSandwichStacking; else if (theta <= 60.0) code = ARP_PiDisplacedStacking; else if (theta <= 90.0) code = ARP_PiParallelInPlaneStacking; }
+    else if (dih <= 60.0) code = ARP_PiTiltedStacking;
+    else if (dih <= 90.0) { if (theta >= 30.0 && theta < 60.0) code = ARP_PiLStacking; else if (dist <= 5.0) code = ARP_PiTStacking; }
+    return code;
+}
+
 // ---- rows ------------------------------------------------------------------------------------------------------------
 // A row = {from entity, to entity, (f32) distance, interaction code}: the layout of arp_pair.  Entity = atom index, or n + ring index.
 __device__ inline void append_row(uint4 *rows, uint32_t *n_rows, uint32_t cap, uint32_t from, uint32_t to, double dist, uint32_t code) {
@@ -171,8 +189,8 @@ __global__ __launch_bounds__(64) void k_ring_atom(uint32_t n_rings, const RingEn
                     if (!(dx * dx + dy * dy + dz * dz <= r2)) continue;  // rstar: inclusive (complex.rs:310)
                     const ResKeyD yk{ring.model_serial, f.crm, f.res_ord, (f.attr & ARP_ATTR_LIGAND) != 0u, (f.attr & ARP_ATTR_RECEPTOR) != 0u};
                     if (!compare_residues_d(rk, yk, false)) continue;
-                    const double dist = point_dist_d(pl, q), theta = point_angle_d(pl, q);
-                    if (theta <= 30.0 && dist <= 4.5) append_row(rows, n_rows, cap, n_atoms + e, f.orig, dist, ARP_CationPi);
+                    double dist;
+                    if (cation_pi_d(pl, q, &dist)) append_row(rows, n_rows, cap, n_atoms + e, f.orig, dist, ARP_CationPi);
                 }
             }
     }
@@ -199,11 +217,7 @@ __global__ __launch_bounds__(256) void k_ring_ring(uint32_t n_rings, const RingE
         const PlaneD p2 = ring_planes[k2.src_res];
         const ResKeyD r2k{k2.model_serial, k2.chain_rank, k2.ord, (k2.flags & 1u) != 0u, (k2.flags & 2u) != 0u};
         if (!compare_residues_d(r1, r2k, true)) continue;
-        const double theta = point_angle_d(p1, p2.c), dih = plane_dihedral_d(p1, p2);
-        int code = -1;
-        if (dih <= 30.0) { if (theta <= 30.0) code = ARP_PiSandwichStacking; else if (theta <= 60.0) code = ARP_PiDisplacedStacking; else if (theta <= 90.0) code = ARP_PiParallelInPlaneStacking; }
-        else if (dih <= 60.0) code = ARP_PiTiltedStacking;
-        else if (dih <= 90.0) { if (theta >= 30.0 && theta < 60.0) code = ARP_PiLStacking; else if (dist <= 5.0) code = ARP_PiTStacking; }
+        const int code = pi_stacking_d(p1, p2, dist);
         if (code >= 0) append_row(rows, n_rows, cap, n_atoms + e1, n_atoms + e2, dist, (uint32_t)code);
     }
 }
@@ -932,5 +946,6 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
 }
 
 #include "freq.inl"
+#include "freq_rings.inl"
 
 }  // namespace arp

@@ -438,7 +438,7 @@ const void *arp_table_column(const arp_table *t, const char *name, int32_t *widt
  * The table has one row per distinct (i, j, interaction) of at least one frame, i / j topology atom indices, ordered by (i, j, interaction):
  *   "interaction" i32 code; "from_chain" "from_resn" "from_insertion" "from_altloc" "from_atomn" fixed-width strings, "from_resi" "from_atomi" i32,
  *   the same seven "to_*" columns, "from_atom" / "to_atom" i32 (i, j); "n_frames" u32 (frames with the row); "frequency" f32 = f32(n_frames / F)
- *   divided in f64; "min_distance" / "max_distance" f32 over those frames.  No ring rows (CationPi, Pi*) and no sc_* columns; no ring is required.
+ *   divided in f64; "min_distance" / "max_distance" f32 over those frames.  No ring rows (CationPi, Pi*: arp_contact_frequencies_ex adds them) and no sc_* columns; no ring is required.
  * The result does not depend on the order the device produces pairs in: two calls give identical bytes.  arp_table_rows / arp_table_column /
  * arp_table_export_arrow serve this column set (the Arrow batch has the columns above in that order, without from_atom / to_atom).
  * Errors before the device is touched (ARP_ERR_BAD_INPUT unless noted): n_frames == 0 with xyz, a non-finite coordinate, N >= 2^29, the
@@ -446,6 +446,29 @@ const void *arp_table_column(const arp_table *t, const char *name, int32_t *widt
  * Frames run through the device in passes of about 2 x 10^6 atoms (arp_debug_set "freq_chunk_atoms"); memory grows with the distinct rows, not F. */
 arp_status arp_contact_frequencies(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
                                    double dist_cutoff, arp_table **out);
+
+/* arp_contact_frequencies with flags.  flags == 0 is arp_contact_frequencies: the same checks, the same bytes.  An unknown
+ * flag bit is ARP_ERR_BAD_INPUT.
+ * ARP_FREQ_RINGS adds the ring rows -- CationPi and the six Pi* stackings.  Definition: let S_f be the SINGLE-MODEL structure that holds model 0's
+ * atoms, in order, with frame f's coordinates (the same f64 values; nothing is parsed again).  The ring entities of the topology are the ring
+ * entities arp_get_contacts builds for S_0, in its order: one per altloc of every residue with at least 3 ring-plane atoms, in residue order; all
+ * entities of a residue share that residue's plane.  There are n_rings of them; entity numbers are 0 .. N - 1 for atoms and N + e for ring e.
+ * Frame f contributes, besides its atom-atom items, one item (from entity, to entity, code, f32 distance) for every row with a ring entity that
+ * arp_get_contacts(S_f, groups, vdw_comp, dist_cutoff) returns: CationPi rows ring -> atom, the six Pi* rows ring -> ring.  Ring-ring rows do NOT
+ * depend on dist_cutoff; ring-atom rows do (candidates: d^2 <= dist_cutoff^2 from the ring centre, inclusive, in f64).  Items are aggregated like
+ * atom items: one row per distinct (from, to, code) with n_frames, frequency, min_distance / max_distance; the same ring pair under different
+ * codes in different frames gives different rows.  Row order stays (from entity, to entity, code): every ring row has a ring as `from`, so all
+ * ring rows follow all atom-atom rows, and the atom-atom rows are byte for byte the table without rings.
+ * A ring entity's columns: chain, resn, resi, insertion, altloc of the entity, atomn "Ring", atomi 0 (what arp_get_contacts writes);
+ * "from_atom" / "to_atom" are -1.  arp_table_column also serves "from_ring" / "to_ring" i32 on frequency tables: the ring entity index, -1 for
+ * an atom.  The Arrow batch keeps its column set.
+ * A topology without any ring is not an error: ARP_OK and the table without rings (arp_get_contacts' ARP_ERR_NO_RINGS does not apply).
+ * With the frames taken from a multi-model FILE (xyz == NULL) the rings are still those of model 0 regarded as a single-model structure -- NOT what
+ * arp_get_contacts files for the multi-model file, which keeps ring planes under every model serial.
+ * One more check before the device is touched: N + n_rings < 2^29 (ARP_ERR_BAD_INPUT).  The sc_* statistics stay out of scope. */
+#define ARP_FREQ_RINGS 0x1u
+arp_status arp_contact_frequencies_ex(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
+                                      double dist_cutoff, uint32_t flags, arp_table **out);
 
 /* ---- SASA and SAP statistics over the frames of an ensemble (MD snapshots, NMR models, conformers of one topology) -- DESIGN.md section 3.8 ----
  * Topology, N, frames and xyz exactly as arp_contact_frequencies defines them: model 0 of `topology` is the topology, frame f is xyz[f]
