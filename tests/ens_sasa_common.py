@@ -7,6 +7,7 @@ import math
 import numpy as np
 
 import arpeggia_amd as aa
+import bsa_common
 from arpeggia_amd import _lib
 
 FOUR_PI = 4.0 * 3.141592653589793
@@ -102,3 +103,67 @@ def frame_loop(ctx, s: aa.Structure, sel, frames, probe: float, n_points: int, s
 
 def result_bytes(r: dict) -> bytes:
     return b"".join(np.ascontiguousarray(r[k]).tobytes() for k in sorted(r) if k != "n_frames")
+
+
+# ---- what tests/test_ens_sasa_gpu.py and tests/test_ens_shapes_gpu.py assert of a sasa_ensemble result -------------------------------------------
+SASA_KEYS = ("mean_sasa", "std_sasa", "min_sasa", "max_sasa")
+SAP_KEYS = ("mean_sap", "std_sap", "min_sap", "max_sap")
+
+
+def assert_sasa_equal(got: dict, want: dict, R, n_points: int):
+    """got: the new path with per_frame=True; want: frame_loop over all frames."""
+    F = got["n_frames"]
+    assert got["count"].dtype == np.int32 and got["count"].shape == want["count"].shape
+    assert np.array_equal(got["count"], want["count"])
+    stats = sasa_stats(F, R, n_points, want["count"])
+    for k in SASA_KEYS:
+        assert got[k].dtype == np.float32 and np.array_equal(got[k], stats[k]), k
+    # min / max are also the extremes of the loop's own f32 values
+    assert np.array_equal(got["min_sasa"], want["sasa"].min(0)) and np.array_equal(got["max_sasa"], want["sasa"].max(0))
+    assert np.array_equal(got["total_sasa"], total_sasa(want["sasa"]))
+
+
+def assert_sap_close(got_sap, want_sap, side):
+    assert got_sap.shape == want_sap.shape and got_sap.dtype == np.float32
+    assert (got_sap[:, ~side] == 0).all()  # backbone atoms
+    tol = SAP_TOL * max(1.0, float(np.abs(want_sap).max(initial=0.0)))
+    assert float(np.abs(got_sap - want_sap).max(initial=0.0)) <= tol
+
+
+def assert_sap_aggregates(got: dict):
+    """The aggregation separated from the order tolerance: from the new path's own per-frame values, exactly."""
+    w = sap_stats(got["sap"])
+    for k in SAP_KEYS:
+        assert got[k].dtype == np.float32 and np.array_equal(got[k], w[k]), k
+
+
+# ---- the per-frame loop of the dSASA form (tests/test_bsa_gpu.py, tests/test_ens_shapes_gpu.py) -------------------------------------------------------
+def bits(a) -> np.ndarray:
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def three_runs(ctx, x, y, z, r, group, probe, n_points=100):
+    """The existing kernel three times -- the union, group 1 alone, group 2 alone -- laid out as the split kernel's planes."""
+    group = np.asarray(group, np.uint8)
+    count, sasa = np.zeros((3, len(group)), np.int32), np.zeros((3, len(group)), np.float32)
+    for plane, members in enumerate((group != 0, (group & 1) != 0, (group & 2) != 0)):
+        s, c = aa.atom_sasa(ctx, x, y, z, r, include=members.astype(np.uint8), probe=probe, n_points=n_points)
+        count[plane], sasa[plane] = c, s
+    return count, sasa
+
+
+def bsa_frame_loop(ctx, s, r, frames, probe, n_points):
+    """The per-frame loop the ensemble call replaces: three atom_sasa calls per frame and an f64 cumsum per total."""
+    sel, group = r["atoms"].astype(np.int64), r["group"]
+    radius = (r["R"] - np.float32(probe)).astype(np.float32)
+    assert np.array_equal((radius + np.float32(probe)).astype(np.float32), r["R"])
+    out = {k: [] for k in ("buried", "total_complex", "total_g1", "total_g2", "dsasa")}
+    for f in range(len(frames)):
+        x, y, z = (np.ascontiguousarray(frames[f][sel, k]) for k in range(3))
+        count, sasa = three_runs(ctx, x, y, z, radius, group, probe, n_points)
+        totals = [bsa_common.f64_total(sasa[0]), bsa_common.f64_total(sasa[1][(group & 1) != 0]), bsa_common.f64_total(sasa[2][(group & 2) != 0])]
+        out["buried"].append(count[1] + count[2] - count[0])
+        for k, v in zip(("total_complex", "total_g1", "total_g2"), totals):
+            out[k].append(v)
+        out["dsasa"].append(bsa_common.dsasa_f32(*totals))
+    return {k: np.array(v) for k, v in out.items()}

@@ -140,3 +140,16 @@ def columns(table) -> dict:
     """{column: list} of a polars.DataFrame or pyarrow.Table"""
     arrow = table if hasattr(table, "column") and not hasattr(table, "to_arrow") else table.to_arrow()
     return {name: arrow.column(name).to_pylist() for name in arrow.column_names}
+
+
+def atom_values(ctx, s, sel, radii, n_points, xyz=None):
+    """Per-atom SASA of the selected atoms from the array call, with the helper's radii."""
+    soa = s.soa("/")
+    x, y, z = (soa[k][sel] for k in "xyz") if xyz is None else (np.ascontiguousarray(xyz[sel, k]) for k in range(3))
+    r, _ = table_radii(s, sel, radii)
+    return aa.atom_sasa(ctx, x, y, z, r, None, 1.4, n_points)[0]
+
+
+def expected_levels(s, sel, values):
+    res, chn = residue_groups(s, sel), chain_groups(s, sel)
+    return (res, np.array([seq_sum(values[g]) for _, g in res], np.float32), chn, np.array([seq_sum(values[g]) for _, g in chn], np.float32))

@@ -14,6 +14,8 @@ import sasa_restatement as sr
 import synth
 from arpeggia_amd import _lib
 from conftest import DATA
+from ens_sasa_common import bits, three_runs
+from ens_sasa_common import bsa_frame_loop as frame_loop
 
 pytestmark = pytest.mark.gpu
 
@@ -46,10 +48,6 @@ def structure_inputs(name: str):
     return soa["x"][sel], soa["y"][sel], soa["z"][sel], _vdw(s.strings("element")[sel])
 
 
-def bits(a) -> np.ndarray:
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def run(ctx, x, y, z, r, group, probe, n_points=100):
     """One device call with the invariants every result has: the shapes and types, buried = own counts - complex count >= 0, zeros outside the
     groups, areas = the formula on the counts."""
@@ -77,16 +75,6 @@ def check(ctx, x, y, z, r, group, probe, n_points=100, homes=None):
     assert np.array_equal(count[:, homes], want), (count[:, homes] != want).sum(1)
     assert np.array_equal(buried[homes], want_buried)
     return count, sasa, buried
-
-
-def three_runs(ctx, x, y, z, r, group, probe, n_points=100):
-    """The existing kernel three times -- the union, group 1 alone, group 2 alone -- laid out as the split kernel's planes."""
-    group = np.asarray(group, np.uint8)
-    count, sasa = np.zeros((3, len(group)), np.int32), np.zeros((3, len(group)), np.float32)
-    for plane, members in enumerate((group != 0, (group & 1) != 0, (group & 2) != 0)):
-        s, c = aa.atom_sasa(ctx, x, y, z, r, include=members.astype(np.uint8), probe=probe, n_points=n_points)
-        count[plane], sasa[plane] = c, s
-    return count, sasa
 
 
 # ---- 1. two atoms ---------------------------------------------------------------------------------------------------------------------------------
@@ -297,21 +285,6 @@ def test_three_run_identity_on_the_models_of_hand7(ctx, model_num):
 
 
 # ---- 6. packed frames ------------------------------------------------------------------------------------------------------------------------------------
-def frame_loop(ctx, s, r, frames, probe, n_points):
-    """The per-frame loop the ensemble call replaces: three atom_sasa calls per frame and an f64 cumsum per total."""
-    sel, group = r["atoms"].astype(np.int64), r["group"]
-    radius = (r["R"] - np.float32(probe)).astype(np.float32)
-    assert np.array_equal((radius + np.float32(probe)).astype(np.float32), r["R"])
-    out = {k: [] for k in ("buried", "total_complex", "total_g1", "total_g2", "dsasa")}
-    for f in range(len(frames)):
-        x, y, z = (np.ascontiguousarray(frames[f][sel, k]) for k in range(3))
-        count, sasa = three_runs(ctx, x, y, z, radius, group, probe, n_points)
-        totals = [bc.f64_total(sasa[0]), bc.f64_total(sasa[1][(group & 1) != 0]), bc.f64_total(sasa[2][(group & 2) != 0])]
-        out["buried"].append(count[1] + count[2] - count[0])
-        for k, v in zip(("total_complex", "total_g1", "total_g2"), totals):
-            out[k].append(v)
-        out["dsasa"].append(bc.dsasa_f32(*totals))
-    return {k: np.array(v) for k, v in out.items()}
 
 
 @pytest.mark.parametrize("name,groups,probe", [("6bft", "C/H,L", 1.4), ("6bft", "C/H,L", 6.0), ("6bft", "A,B/A,G", 1.4), ("hand7", "/", 1.4), ("1ubq", "/", 6.0)])

@@ -14,12 +14,9 @@ import pytest
 import arpeggia_amd as aa
 import ens_sasa_common as ec
 import synth
+from ens_sasa_common import SAP_KEYS, SASA_KEYS, assert_sap_aggregates, assert_sap_close, assert_sasa_equal
 
 pytestmark = pytest.mark.gpu
-
-SASA_KEYS = ("mean_sasa", "std_sasa", "min_sasa", "max_sasa")
-SAP_KEYS = ("mean_sap", "std_sap", "min_sap", "max_sap")
-
 
 @pytest.fixture(scope="module")
 def ctx():
@@ -46,33 +43,6 @@ def bft(bft_path):
 @pytest.fixture(scope="module")
 def stress():
     return aa.Structure.from_records(synth.gen_stress(n_res=120, seed=11, hydrogens=True, altlocs=True))
-
-
-def assert_sasa_equal(got: dict, want: dict, R, n_points: int):
-    """got: the new path with per_frame=True; want: frame_loop over all frames."""
-    F = got["n_frames"]
-    assert got["count"].dtype == np.int32 and got["count"].shape == want["count"].shape
-    assert np.array_equal(got["count"], want["count"])
-    stats = ec.sasa_stats(F, R, n_points, want["count"])
-    for k in SASA_KEYS:
-        assert got[k].dtype == np.float32 and np.array_equal(got[k], stats[k]), k
-    # min / max are also the extremes of the loop's own f32 values
-    assert np.array_equal(got["min_sasa"], want["sasa"].min(0)) and np.array_equal(got["max_sasa"], want["sasa"].max(0))
-    assert np.array_equal(got["total_sasa"], ec.total_sasa(want["sasa"]))
-
-
-def assert_sap_close(got_sap, want_sap, side):
-    assert got_sap.shape == want_sap.shape and got_sap.dtype == np.float32
-    assert (got_sap[:, ~side] == 0).all()  # backbone atoms
-    tol = ec.SAP_TOL * max(1.0, float(np.abs(want_sap).max(initial=0.0)))
-    assert float(np.abs(got_sap - want_sap).max(initial=0.0)) <= tol
-
-
-def assert_sap_aggregates(got: dict):
-    """The aggregation separated from the order tolerance: from the new path's own per-frame values, exactly."""
-    w = ec.sap_stats(got["sap"])
-    for k in SAP_KEYS:
-        assert got[k].dtype == np.float32 and np.array_equal(got[k], w[k]), k
 
 
 # ---- one frame -----------------------------------------------------------------------------------------------------------------------------

@@ -11,11 +11,9 @@ import pytest
 import arpeggia_amd as aa
 import synth
 from arpeggia_amd import _lib
+from freq_common import RING_CODES, assert_table_equal, expected, to_bytes  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-RING_CODES = set(range(11, 18))  # Pi* stackings and CationPi: ring rows, not part of the frequency table
-
 
 @pytest.fixture(scope="module")
 def ctx():
@@ -38,68 +36,6 @@ def jittered(s: aa.Structure, n_frames: int, seed: int, sigma: float = 0.3) -> n
     base = topology_xyz(s, n)
     rng = np.random.default_rng(seed)
     return base[None] + rng.normal(scale=sigma, size=(n_frames, n, 3))
-
-
-def expected(ctx, s: aa.Structure, frames: np.ndarray, groups: str) -> dict:
-    """One atomic_contacts call per frame on the topology (model 0) with the frame's coordinates; rows aggregated by (i, j, code)."""
-    soa = s.soa(groups)
-    F, n = frames.shape[0], frames.shape[1]
-    # model 0's residues are the residues of its atoms: ids 0 .. max + 1 (the hierarchy is built model by model)
-    nr = int(soa["res_id"][:n].max()) + 1 if n and len(soa["res_cb"]) else 0
-    top = {k: soa[k][:n] for k in ("attr", "res_ord", "chain_rank", "model", "res_id")}
-    top.update(res_h_ptr=soa["res_h_ptr"][: nr + 1] if nr else soa["res_h_ptr"][:0], res_cb=soa["res_cb"][:nr], res_sg=soa["res_sg"][:nr])
-    nh = int(top["res_h_ptr"][-1]) if nr else 0
-    top["res_h_idx"] = soa["res_h_idx"][:nh]
-    keys, dists = [], []
-    for f in range(F):
-        d = dict(top, x=frames[f, :, 0].copy(), y=frames[f, :, 1].copy(), z=frames[f, :, 2].copy())
-        p = ctx.atomic_contacts(d)
-        p = p[p["kind"] != 0]
-        for code in range(len(_lib.INTERACTIONS)):
-            sel = (p["kind"] >> np.uint32(code)) & np.uint32(1) == 1
-            if sel.any():
-                q = p[sel]
-                keys.append((q["i"].astype(np.uint64) << np.uint64(34)) | (q["j"].astype(np.uint64) << np.uint64(5)) | np.uint64(code))
-                dists.append(q["dist"])
-    keys = np.concatenate(keys) if keys else np.zeros(0, np.uint64)
-    dists = np.concatenate(dists) if dists else np.zeros(0, np.float32)
-    uk, inv, cnt = np.unique(keys, return_inverse=True, return_counts=True)
-    mn = np.full(len(uk), np.inf, np.float32)
-    mx = np.full(len(uk), -np.inf, np.float32)
-    np.minimum.at(mn, inv, dists)
-    np.maximum.at(mx, inv, dists)
-    i = (uk >> np.uint64(34)).astype(np.int64)
-    j = ((uk >> np.uint64(5)) & np.uint64((1 << 29) - 1)).astype(np.int64)
-    code = (uk & np.uint64(31)).astype(np.int32)
-    assert not (set(np.unique(code).tolist()) & RING_CODES)
-    out = {"interaction": code, "from_atom": i.astype(np.int32), "to_atom": j.astype(np.int32), "n_frames": cnt.astype(np.uint32),
-           "frequency": (cnt.astype(np.float64) / F).astype(np.float32), "min_distance": mn, "max_distance": mx}
-    for side, idx in (("from", i), ("to", j)):
-        out[f"{side}_chain"] = s.strings("chain")[idx]
-        out[f"{side}_resn"] = s.strings("resn")[idx]
-        out[f"{side}_resi"] = s.ints("resi")[idx]
-        out[f"{side}_insertion"] = s.strings("insertion")[idx]
-        out[f"{side}_altloc"] = s.strings("altloc")[idx]
-        out[f"{side}_atomn"] = s.strings("atomn")[idx]
-        out[f"{side}_atomi"] = s.ints("atomi")[idx]
-    return out
-
-
-def assert_table_equal(got: dict, want: dict):
-    names = [c for c, _ in aa.FREQ_COLUMNS] + ["from_atom", "to_atom"]
-    assert set(got) == set(names)
-    for c in names:
-        assert len(got[c]) == len(want[c]), c
-        if got[c].dtype.kind == "S":
-            assert np.array_equal(got[c].astype(want[c].dtype), want[c]), c
-        else:
-            kind = dict(aa.FREQ_COLUMNS + [("from_atom", "i4"), ("to_atom", "i4")])[c]
-            assert got[c].dtype == np.dtype("<" + (kind if kind != "str" else "i4")), c
-            assert np.array_equal(got[c], want[c].astype(got[c].dtype)), c
-
-
-def to_bytes(t: dict) -> bytes:
-    return b"".join(np.ascontiguousarray(t[c]).tobytes() for c in sorted(t))
 
 
 @pytest.fixture(scope="module")

@@ -17,12 +17,10 @@ import freq_ring_cases as rc
 import synth
 from arpeggia_amd import _lib
 from arpeggia_amd.api import _frames_arg, _np_from
+from freq_common import BASE, RING_ATOMS, assert_same_rows, atom_part, device_reference, ring_entities, ring_part  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-BASE = [c for c, _ in aa.FREQ_COLUMNS] + ["from_atom", "to_atom"]
-RING_ATOMS = {b"HIS": {b"CG", b"ND1", b"CE1", b"NE2", b"CD2"}, b"PHE": {b"CG", b"CD1", b"CD2", b"CE1", b"CE2", b"CZ"},
-              b"TYR": {b"CG", b"CD1", b"CD2", b"CE1", b"CE2", b"CZ"}, b"TRP": {b"CG", b"CD1", b"CD2", b"NE1", b"CE2", b"CE3", b"CZ2", b"CZ3", b"CH2"}}
 PI_CODES = set(range(11, 17))
 CATION_PI = 17
 
@@ -37,84 +35,6 @@ def _reset_knobs():
     yield
     aa.debug_set("freq_chunk_atoms", 0)
     aa.debug_set("freq_cap_items", 0)
-
-
-def ring_entities(rec: dict) -> dict:
-    """(chain, resi, insertion, altloc) -> ring entity index: one entity per altloc of every residue with at least 3 ring-plane atoms, in residue
-    order (records whose chains are contiguous: file order is hierarchy order)."""
-    residues, atoms_of = [], {}
-    for k in range(len(rec["x"])):
-        key = (bytes(rec["chain"][k]), int(rec["resi"][k]), bytes(rec["icode"][k]))
-        if key not in atoms_of:
-            residues.append(key)
-            atoms_of[key] = []
-        atoms_of[key].append(k)
-    out = {}
-    for key in residues:
-        ks = atoms_of[key]
-        names = RING_ATOMS.get(bytes(rec["resn"][ks[0]]))
-        if not names or sum(bytes(rec["name"][k]) in names for k in ks) < 3:
-            continue
-        for alt in dict.fromkeys(bytes(rec["altloc"][k]) for k in ks):
-            out[(key[0], key[1], key[2], alt)] = len(out)
-    return out
-
-
-def device_reference(ctx, rec: dict, frames: np.ndarray, groups: str, dist_cutoff: float = 6.5) -> dict:
-    """The ring rows of the frequency table by definition: Context.get_contacts on S_f for every frame, aggregated."""
-    ents = ring_entities(rec)
-    F, n = frames.shape[0], frames.shape[1]
-    first, dists = {}, {}
-    for f in range(F):
-        s = aa.Structure.from_records(dict(rec, x=frames[f, :, 0].copy(), y=frames[f, :, 1].copy(), z=frames[f, :, 2].copy()))
-        assert s.n_atoms == n
-        t = ctx.get_contacts(s, groups, 0.1, dist_cutoff)
-        for k in np.flatnonzero((t["from_atom"] < 0) | (t["to_atom"] < 0)):
-            assert t["from_atom"][k] < 0 and t["from_atomn"][k] == b"Ring"
-            e1 = ents[(bytes(t["from_chain"][k]), int(t["from_resi"][k]), bytes(t["from_insertion"][k]), bytes(t["from_altloc"][k]))]
-            if t["to_atom"][k] >= 0:
-                to_ent, e2 = int(t["to_atom"][k]), -1
-            else:
-                e2 = ents[(bytes(t["to_chain"][k]), int(t["to_resi"][k]), bytes(t["to_insertion"][k]), bytes(t["to_altloc"][k]))]
-                to_ent = n + e2
-            key = (n + e1, to_ent, int(t["interaction"][k]))
-            if key not in first:
-                row = {c: t[c][k] for c in BASE if c in t and c != "interaction"}
-                row.update(interaction=key[2], from_ring=e1, to_ring=e2)
-                first[key] = row
-            dists.setdefault(key, []).append(t["distance"][k])
-    keys = sorted(first)
-    out = {}
-    for c in BASE + ["from_ring", "to_ring"]:
-        if c == "n_frames":
-            out[c] = np.array([len(dists[k]) for k in keys], np.uint32)
-        elif c == "frequency":
-            out[c] = np.array([np.float32(len(dists[k]) / F) for k in keys], np.float32)
-        elif c == "min_distance":
-            out[c] = np.array([min(dists[k]) for k in keys], np.float32)
-        elif c == "max_distance":
-            out[c] = np.array([max(dists[k]) for k in keys], np.float32)
-        else:
-            out[c] = np.array([first[k][c] for k in keys]) if keys else np.zeros(0, "S8" if c.endswith(("chain", "resn", "atomn", "insertion", "altloc")) else np.int32)
-    return out
-
-
-def ring_part(t: dict) -> dict:
-    sel = t["from_ring"] >= 0
-    assert not sel.any() or sel[int(np.argmax(sel)):].all()  # every ring row follows every atom row
-    assert (t["to_ring"][~sel] == -1).all()
-    return {c: v[sel] for c, v in t.items()}
-
-
-def atom_part(t: dict) -> dict:
-    sel = t["from_ring"] < 0
-    return {c: t[c][sel] for c in BASE}
-
-
-def assert_same_rows(got: dict, want: dict):
-    for c in BASE + ["from_ring", "to_ring"]:
-        assert len(got[c]) == len(want[c]), c
-        assert np.array_equal(got[c], want[c].astype(got[c].dtype)), c
 
 
 def to_bytes(t: dict, cols=None) -> bytes:

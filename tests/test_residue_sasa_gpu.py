@@ -12,6 +12,7 @@ import pytest
 import arpeggia_amd as aa
 import ens_sasa_common as ec
 import residue_sasa_common as rc
+from residue_sasa_common import atom_values, expected_levels
 
 pytestmark = pytest.mark.gpu
 
@@ -174,17 +175,6 @@ def test_segment_sum_of_nothing(ctx):
 
 
 # ---- 8. the single-structure levels ----------------------------------------------------------------------------------------------------------
-def atom_values(ctx, s, sel, radii, n_points, xyz=None):
-    """Per-atom SASA of the selected atoms from the array call, with the helper's radii."""
-    soa = s.soa("/")
-    x, y, z = (soa[k][sel] for k in "xyz") if xyz is None else (np.ascontiguousarray(xyz[sel, k]) for k in range(3))
-    r, _ = rc.table_radii(s, sel, radii)
-    return aa.atom_sasa(ctx, x, y, z, r, None, 1.4, n_points)[0]
-
-
-def expected_levels(s, sel, values):
-    res, chn = rc.residue_groups(s, sel), rc.chain_groups(s, sel)
-    return (res, np.array([rc.seq_sum(values[g]) for _, g in res], np.float32), chn, np.array([rc.seq_sum(values[g]) for _, g in chn], np.float32))
 
 
 @pytest.mark.parametrize("n_points", [1, 64, 100])
