@@ -18,7 +18,7 @@ from .api import (  # noqa: F401  residue- and chain-level SASA, relative SASA (
     get_residue_sasa_ensemble, max_asa, relative_sasa, sasa_radius, segment_sum,
 )
 from .api import get_sc, get_sc_results, sc, sc_arrays, sc_dots, sc_radius, sc_select  # noqa: F401  shape complementarity (src/sc/)
-from .api import FREQ_COLUMNS, contact_frequencies, get_contact_frequencies  # noqa: F401  contact frequencies across the frames of an ensemble
+from .api import FREQ_COLUMNS, RESIDUE_FREQ_COLUMNS, contact_frequencies, get_contact_frequencies  # noqa: F401  contact frequencies across the frames of an ensemble
 from .api import (  # noqa: F401  SASA / SAP statistics across the frames of an ensemble
     ENSEMBLE_SAP_COLUMNS, ENSEMBLE_SASA_COLUMNS, RESIDUE_ENSEMBLE_SAP_COLUMNS, get_residue_sap_ensemble, get_sap_ensemble, get_sasa_ensemble,
     sap_ensemble, sasa_ensemble, sasa_ensemble_stats,

@@ -3,7 +3,8 @@
 `sasa`, `relative-sasa`, `sap`, `dsasa` and `sc` take the flags and defaults of src/cli/{sasa,relative_sasa,sap,dsasa,sc}.rs; `sasa`, `dsasa` and
 `sasa-ensemble` also take --radii {vdw,protor}: the radius table, which the residue and chain levels of `sasa` need (see arpeggia_amd/api.py).
 `contact-frequency` (no counterpart in the reference) takes the flags and defaults of `contacts`; the models of the input file are the frames, and
---rings adds the ring rows (CationPi, Pi* stackings) of every model regarded as a single-model structure.
+--rings adds the ring rows (CationPi, Pi* stackings) of every model regarded as a single-model structure; --level residue writes one row per
+residue pair and interaction (a model counts once however many of the residues' atoms are in contact).
 `sasa-ensemble` and `sap-ensemble` (no counterpart either) take the flags and defaults of `sasa` / `sap` without --model: statistics over the models.
 `dsasa --level atom|residue` writes the interface row by row (default `total`: the reference's scalar); `dsasa-ensemble` takes the flags of
 `sasa-ensemble` and -g: dSASA per model and the per-atom statistics of the buried surface.
@@ -47,6 +48,8 @@ def build_parser() -> argparse.ArgumentParser:
     q.add_argument("-j", "--num-threads", default=1, type=int, help="Number of threads (accepted; the computation runs on the GPU)")
     q.add_argument("--ignore-zero-occupancy", action="store_true", help="Ignore atoms with zero occupancy")
     q.add_argument("--rings", action="store_true", help="Add the ring rows (CationPi, Pi stackings) of every model; ring-ring rows do not depend on --dist-cutoff")
+    q.add_argument("-l", "--level", default="atom", choices=("atom", "residue"),
+                   help="Rows per atom pair, or per residue pair (a model counts once however many of the residues' atoms are in contact)")
     common = dict(model=("-m", "--model", 0, int, "Model number to analyze (0: the first model)"),
                   probe=("-r", "--probe-radius", 1.4, float, "Probe radius in Angstroms"),
                   points=("-n", "--num-points", 100, int, "Number of points for surface calculation"),
@@ -289,7 +292,7 @@ def run_contact_frequency(args) -> int:
         log.error("Failed to retrieve input file: %s", args.input)
         return 1
     try:
-        table = aa.contact_frequencies(str(args.input.resolve()), args.groups, args.vdw_comp, args.dist_cutoff, args.ignore_zero_occupancy, rings=args.rings)
+        table = aa.contact_frequencies(str(args.input.resolve()), args.groups, args.vdw_comp, args.dist_cutoff, args.ignore_zero_occupancy, rings=args.rings, level=args.level)
     except aa.ArpeggiaError as e:
         log.error("Contact frequencies failed: %s", e)
         return 1

@@ -199,6 +199,7 @@ def _load():
                                                 _dp, _dp] + [C.POINTER(C.c_float)] * 6),
         "arp_contact_frequencies": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_double, C.c_double, C.POINTER(vp)]),
         "arp_contact_frequencies_ex": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_double, C.c_double, C.c_uint32, C.POINTER(vp)]),
+        "arp_residue_contact_frequencies": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_double, C.c_double, C.c_uint32, C.POINTER(vp)]),
         "arp_sasa_radius": (C.c_int32, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, _fp]),
         "arp_max_asa": (C.c_float, [C.c_char_p]),
         "arp_residue_is_polar": (C.c_int32, [C.c_char_p]),

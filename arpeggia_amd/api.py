@@ -37,6 +37,13 @@ FREQ_COLUMNS = [  # arp_contact_frequencies (include/arpeggia_amd.h): one row pe
     ("n_frames", "u4"), ("frequency", "f4"), ("min_distance", "f4"), ("max_distance", "f4"),
 ]
 
+RESIDUE_FREQ_COLUMNS = [  # arp_residue_contact_frequencies: one row per distinct (residue of from, residue of to, interaction) over the frames
+    ("interaction", "str"),
+    ("from_chain", "str"), ("from_resn", "str"), ("from_resi", "i4"), ("from_insertion", "str"),
+    ("to_chain", "str"), ("to_resn", "str"), ("to_resi", "i4"), ("to_insertion", "str"),
+    ("n_frames", "u4"), ("frequency", "f4"), ("min_distance", "f4"), ("max_distance", "f4"),
+]
+
 
 class ArpeggiaError(RuntimeError):
     """Raised where the reference panics (pyo3_runtime.PanicException) or a HIP call fails."""
@@ -76,7 +83,7 @@ def default_params(vdw_comp: float = 0.1, dist_cutoff: float = 6.5, deterministi
 
 
 def debug_set(key: str, value: int):
-    """arp_debug_set: the library's diagnostic switches ("timing", "emit_kernel", "defer_entries", "table_host", "freq_chunk_atoms", "freq_cap_items", ...; include/arpeggia_amd.h)."""
+    """arp_debug_set: the library's diagnostic switches ("timing", "emit_kernel", "defer_entries", "table_host", "freq_chunk_atoms", "freq_cap_items", "freq_frame_bits", ...; include/arpeggia_amd.h)."""
     _check(lib.arp_debug_set(key.encode(), int(value)))
 
 
@@ -347,12 +354,15 @@ class Context:
         finally:
             lib.arp_table_free(t)
 
-    def contact_frequencies(self, structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, rings: bool = False) -> dict:
+    def contact_frequencies(self, structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, rings: bool = False,
+                            level: str = "atom") -> dict:
         """arp_contact_frequencies_ex as a dict of numpy columns (FREQ_COLUMNS + from_atom / to_atom).  frames: [F, N, 3] f64 coordinates of the
         topology's N atoms (model 0 of `structure`); None: the structure's models are the frames.  rings=True (ARP_FREQ_RINGS) adds the ring rows
         (CationPi, Pi* stackings) behind the atom rows, and the columns from_ring / to_ring (ring entity index, -1 for an atom; from_atom /
-        to_atom are -1 for a ring)."""
-        t = _freq_table(self, structure, frames, groups, vdw_comp, dist_cutoff, rings)
+        to_atom are -1 for a ring).  level="residue": arp_residue_contact_frequencies -- one row per (residue, residue, interaction), a frame
+        counted once per row however many of the residues' atom pairs (and, with rings, ring entities) are in contact; the columns are
+        RESIDUE_FREQ_COLUMNS + from_residue / to_residue (residue ordinals of the topology)."""
+        t = _freq_table(self, structure, frames, groups, vdw_comp, dist_cutoff, rings, level)
         try:
             n = int(lib.arp_table_rows(t))
             cols = {}
@@ -364,6 +374,12 @@ class Context:
                     raise KeyError(name)
                 return _np_from(p, n, dtype or f"S{max(w.value, 1)}")
 
+            if level == "residue":
+                for name, kind in RESIDUE_FREQ_COLUMNS:
+                    cols[name] = col(name, "<i4") if name == "interaction" else col(name) if kind == "str" else col(name, "<" + kind)
+                cols["from_residue"] = col("from_residue", "<i4")
+                cols["to_residue"] = col("to_residue", "<i4")
+                return cols
             for name, kind in FREQ_COLUMNS:
                 if name == "interaction":
                     cols[name] = col(name, "<i4")
@@ -420,12 +436,16 @@ def _topology_atoms(structure: Structure) -> int:
     return int(other[0]) if len(other) else len(m)
 
 
-def _freq_table(ctx: "Context | None", structure: Structure, frames, groups: str, vdw_comp: float, dist_cutoff: float, rings: bool = False):
-    """arp_contact_frequencies_ex -> table handle (the caller frees it).  ctx None: the inputs are only checked (raises their error, else returns None)."""
+def _freq_table(ctx: "Context | None", structure: Structure, frames, groups: str, vdw_comp: float, dist_cutoff: float, rings: bool = False, level: str = "atom"):
+    """arp_contact_frequencies_ex (level "atom") or arp_residue_contact_frequencies ("residue") -> table handle (the caller frees it).  ctx None:
+    the inputs are only checked (raises their error, else returns None)."""
+    if level not in ("atom", "residue"):
+        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
     n_frames, ptr, keep = _frames_arg(structure, frames, "contact frequencies")
     t = C.c_void_p()
-    _check(lib.arp_contact_frequencies_ex(ctx._h if ctx is not None else None, structure._h, int(n_frames), ptr, groups.encode(), float(vdw_comp),
-                                          float(dist_cutoff), _lib.ARP_FREQ_RINGS if rings else 0, C.byref(t)))
+    call = lib.arp_residue_contact_frequencies if level == "residue" else lib.arp_contact_frequencies_ex
+    _check(call(ctx._h if ctx is not None else None, structure._h, int(n_frames), ptr, groups.encode(), float(vdw_comp),
+                float(dist_cutoff), _lib.ARP_FREQ_RINGS if rings else 0, C.byref(t)))
     return t if ctx is not None else None
 
 
@@ -662,20 +682,25 @@ def contacts(input_file: str, groups: str = "/", vdw_comp: float = 0.1, dist_cut
 
 
 def get_contact_frequencies(structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, device: int = 0,
-                            rings: bool = False):
+                            rings: bool = False, level: str = "atom"):
     """How often every atom-atom contact occurs across the frames of an ensemble (arp_contact_frequencies_ex): one row per distinct
     (from atom, to atom, interaction) with n_frames, frequency, min_distance and max_distance (FREQ_COLUMNS).  frames: [F, N, 3] f64
     coordinates of the N atoms of the topology (model 0 of `structure`); None: the structure's models are the frames.  rings=True adds the
     ring rows (CationPi, Pi* stackings; atomn "Ring", atomi 0) of every frame regarded as a single-model structure, behind the atom rows;
-    ring-ring rows do not depend on dist_cutoff.  Returns a polars.DataFrame when polars is importable, else a pyarrow.Table, like get_contacts."""
+    ring-ring rows do not depend on dist_cutoff.  level="residue" (arp_residue_contact_frequencies): one row per distinct (residue of from,
+    residue of to, interaction) instead -- n_frames counts the distinct frames in which ANY item of the residue pair has the interaction (what
+    the atom-level table cannot give), min_distance / max_distance are the extremes over those frames of the frame's closest approach
+    (RESIDUE_FREQ_COLUMNS).  Returns a polars.DataFrame when polars is importable, else a pyarrow.Table, like get_contacts."""
     import pyarrow as pa
 
+    if level not in ("atom", "residue"):
+        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
     try:
         ctx = _context(device)
     except ArpeggiaError:
-        _freq_table(None, structure, frames, groups, vdw_comp, dist_cutoff, rings)  # an input error takes precedence over the missing device
+        _freq_table(None, structure, frames, groups, vdw_comp, dist_cutoff, rings, level)  # an input error takes precedence over the missing device
         raise
-    t = _freq_table(ctx, structure, frames, groups, vdw_comp, dist_cutoff, rings)
+    t = _freq_table(ctx, structure, frames, groups, vdw_comp, dist_cutoff, rings, level)
     try:
         arr, sch = _lib.ArrowArray(), _lib.ArrowSchema()
         _check(lib.arp_table_export_arrow(t, C.byref(arr), C.byref(sch)))
@@ -691,10 +716,13 @@ def get_contact_frequencies(structure: Structure, frames=None, groups: str = "/"
 
 
 def contact_frequencies(input_file: str, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, ignore_zero_occupancy: bool = False,
-                        rings: bool = False):
+                        rings: bool = False, level: str = "atom"):
     """Contact frequencies across the models of a multi-model file (NMR models, MODEL-record snapshots): see get_contact_frequencies.  With
-    rings=True the rings are those of model 0 regarded as a single-model structure, not what get_contacts files for the multi-model file."""
-    return get_contact_frequencies(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings)
+    rings=True the rings are those of model 0 regarded as a single-model structure, not what get_contacts files for the multi-model file.
+    level="residue": the residue-level table."""
+    if level not in ("atom", "residue"):
+        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
+    return get_contact_frequencies(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings, level=level)
 
 
 def contacts_batch(input_files, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, ignore_zero_occupancy: bool = False,

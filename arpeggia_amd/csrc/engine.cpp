@@ -638,7 +638,7 @@ extern "C" int32_t arp_profile_read(arp_context *ctx, const char **names, float 
 }
 
 // ---- library-level -----------------------------------------------------------------------------------------------
-namespace arp { DebugKnobs g_debug{0, 0, 0, 0, 0, 0, 0, 0}; }
+namespace arp { DebugKnobs g_debug{0, 0, 0, 0, 0, 0, 0, 0, 0}; }
 extern "C" arp_status arp_debug_set(const char *key, int64_t value) {
     if (!key) { set_error("null key"); return ARP_ERR_BAD_INPUT; }
     const std::string k(key);
@@ -654,6 +654,10 @@ extern "C" arp_status arp_debug_set(const char *key, int64_t value) {
         if (value < 0) { set_error("arp_debug_set: freq_cap_items takes 0 (automatic) or a positive item count"); return ARP_ERR_BAD_INPUT; }
         g_debug.freq_cap_items = (long)value;
     }
+    else if (k == "freq_frame_bits") {
+        if (value < 0 || value > 17) { set_error("arp_debug_set: freq_frame_bits takes 0 (automatic) or 1 .. 17"); return ARP_ERR_BAD_INPUT; }
+        g_debug.freq_frame_bits = (long)value;
+    }
     else if (k == "ens_chunk_atoms") {
         if (value < 0) { set_error("arp_debug_set: ens_chunk_atoms takes 0 (automatic) or a positive atom count"); return ARP_ERR_BAD_INPUT; }
         g_debug.ens_chunk_atoms = (long)value;
@@ -662,7 +666,7 @@ extern "C" arp_status arp_debug_set(const char *key, int64_t value) {
         if (value < 0 || value > 1024 || (value & (value - 1)) != 0) { set_error("arp_debug_set: strip_rows takes 0 or a power of two up to 1024"); return ARP_ERR_BAD_INPUT; }
         g_debug.strip_rows = (int)value;
     }
-    else { set_error("arp_debug_set: unknown key '%s' (timing, emit_kernel, defer_entries, strip_rows, table_host, freq_chunk_atoms, freq_cap_items, ens_chunk_atoms)", key); return ARP_ERR_BAD_INPUT; }
+    else { set_error("arp_debug_set: unknown key '%s' (timing, emit_kernel, defer_entries, strip_rows, table_host, freq_chunk_atoms, freq_cap_items, freq_frame_bits, ens_chunk_atoms)", key); return ARP_ERR_BAD_INPUT; }
     return ARP_OK;
 }
 extern "C" int32_t arp_api_version(void) { return ARP_API_VERSION; }

@@ -7,8 +7,15 @@
 // becomes (key, value) items -- key = i_top << 34 | j_top << 5 | code, value = {1 frame, distance, distance} -- which are appended to the
 // running aggregate (one item per distinct key so far), sorted by key and reduced run by run.  Memory stays bounded by the distinct rows and
 // one chunk's items, whatever F is, and only the aggregate comes back.
+//
+// Residue level (arp_residue_contact_frequencies): the same items under the key
+// res(from) << (rb + 5 + fb) | res(to) << (5 + fb) | code << fb | tag, rb = bits of a residue ordinal, tag = the item's frame inside the pass + 1
+// in fb bits (an entry of the aggregate has tag 0).  One sort by the whole key puts every (row, frame) sub-run together; the reduction by
+// (key, tag) gives each sub-run's closest approach, k_freq_collapse turns it into {1 frame, c_f, c_f} and strips the tag, and a second
+// reduction of the already sorted array by the row key merges the frames with the aggregate.
 
 constexpr uint32_t kFreqKeyShiftI = 34, kFreqKeyShiftJ = 5;
+constexpr uint32_t kFreqCodeBits = 5, kFreqFrameBitsMax = 17;  // residue level: the code's bits, and the most tag bits a key gets
 constexpr uint64_t kFreqAutoAtoms = 1u << 21;  // atoms per pass when the knob freq_chunk_atoms is 0: 1ubq x 3000 frames, 6bft x 230
 
 // {frames, min, max} of one key; min / max are order-preserving codes of the f32 distances, so that unsigned atomics order them like floats
@@ -55,10 +62,15 @@ __global__ __launch_bounds__(256) void k_freq_tile(uint32_t frames, uint32_t W, 
     }
 }
 
+// residue level: the residue of a topology atom and where the key's fields start (freq_rings.inl takes a ring's residue from its slot)
+struct FreqResKey { const uint32_t *res_of; uint32_t shift_a, shift_b, frame_bits; };
+
 // one item per set bit of a pair's kind word, appended at base + (a place reserved with one atomic per wave); nothing is written at or past
-// cap, but *counter still counts every item (the host then grows the buffers and runs this again on the same pair list)
+// cap, but *counter still counts every item (the host then grows the buffers and runs this again on the same pair list).
+// RES: the residue-level key; the pair's frame inside the pass is its packed index / n.
+template <bool RES>
 __global__ __launch_bounds__(256) void k_freq_expand(const arp_pair *pairs, uint32_t n_pairs, uint32_t n, unsigned long long *keys, FreqVal *vals, uint32_t base,
-                                                     uint32_t cap, uint32_t *counter) {
+                                                     uint32_t cap, uint32_t *counter, FreqResKey rk) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63u;
     arp_pair q = {0u, 0u, 0.0f, 0u};
     if (p < n_pairs) q = pairs[p];
@@ -75,12 +87,19 @@ __global__ __launch_bounds__(256) void k_freq_expand(const arp_pair *pairs, uint
     at = (uint32_t)__shfl((int)at, 63);
     if (!cnt) return;
     // i and j are atoms of the same frame: their topology indices are the packed indices modulo n
-    const unsigned long long ij = ((unsigned long long)(q.i % n) << kFreqKeyShiftI) | ((unsigned long long)(q.j % n) << kFreqKeyShiftJ);
+    unsigned long long ij;
+    uint32_t code_shift = 0;
+    if constexpr (RES) {
+        ij = ((unsigned long long)rk.res_of[q.i % n] << rk.shift_a) | ((unsigned long long)rk.res_of[q.j % n] << rk.shift_b) | (unsigned long long)(q.i / n + 1u);
+        code_shift = rk.frame_bits;
+    } else {
+        ij = ((unsigned long long)(q.i % n) << kFreqKeyShiftI) | ((unsigned long long)(q.j % n) << kFreqKeyShiftJ);
+    }
     const uint32_t d = freq_code(q.dist);
     unsigned long long o = (unsigned long long)base + at + (incl - cnt);
     for (uint32_t b = kind; b; b &= b - 1u, ++o) {
         if (o >= cap) break;
-        keys[o] = ij | (unsigned long long)(__ffs((int)b) - 1);
+        keys[o] = ij | ((unsigned long long)(__ffs((int)b) - 1) << code_shift);
         vals[o] = FreqVal{1u, d, d};
     }
 }
@@ -116,6 +135,18 @@ __global__ __launch_bounds__(256) void k_freq_reduce(uint32_t m, const unsigned 
     if (t == 0u || keys[t - 1u] != keys[t]) out_keys[r] = keys[t];
 }
 
+// residue level, between the two reductions: entry t is one (row, tag) sub-run.  A frame's sub-run (tag >= 1) becomes {1 frame, c_f, c_f}, c_f its
+// smallest distance, and loses its tag; an entry of the aggregate (tag 0) stays as it is.
+__global__ __launch_bounds__(256) void k_freq_collapse(uint32_t m, unsigned long long tag_mask, unsigned long long *keys, FreqVal *vals) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= m) return;
+    const unsigned long long k = keys[t];
+    if (!(k & tag_mask)) return;
+    keys[t] = k & ~tag_mask;
+    const uint32_t mn = vals[t].mn;
+    vals[t] = FreqVal{1u, mn, mn};
+}
+
 // the ring items of a pass (ARP_FREQ_RINGS): the kernels are in freq_rings.inl, behind this file.  The topology's rings on the device: one plane
 // per ring residue (slot), one RingEnt per entity (src_res = slot; every altloc of a residue is an entity of its own that shares the residue's
 // plane), and the atoms a CationPi row can name.
@@ -127,9 +158,10 @@ struct FreqRings {
 };
 constexpr uint32_t kFreqRingTile = 64;  // ring entities per workgroup of k_freq_ring_rows
 __global__ __launch_bounds__(128) void k_freq_ring_fit(uint32_t frames, uint32_t n, FreqRings r, const double *x, const double *y, const double *z, PlaneD *planes);
+template <bool RES>
 __global__ __launch_bounds__(256) void k_freq_ring_rows(uint32_t n_tiles, uint32_t n, FreqRings r, const uint32_t *attr, const uint32_t *res_ord, const uint32_t *chain_rank, const double *x,
                                  const double *y, const double *z, const PlaneD *planes, double cutoff, unsigned long long *keys, FreqVal *vals, uint32_t base, uint32_t cap,
-                                 uint32_t *counter);
+                                 uint32_t *counter, FreqResKey rk);
 
 namespace {
 uint32_t freq_blocks(unsigned long long items) { return (uint32_t)std::max<unsigned long long>(1ull, (items + 255u) / 256u); }  // (items < 2^32: one thread each)
@@ -191,6 +223,16 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
     const uint64_t budget = job.chunk_atoms ? job.chunk_atoms : kFreqAutoAtoms;
     uint64_t per = std::max<uint64_t>(1, budget / n);
     per = std::min<uint64_t>({per, F, 0x7FFFFFF0ull / std::max<uint64_t>({n, nr + 1, nh, 1}), 65535});
+    // residue level: rb bits per residue ordinal, the tag gets what is left of the key (at most kFreqFrameBitsMax, or the knob's fewer), and a
+    // pass has at most 2^fb - 1 frames (tag 0 is the aggregate's)
+    uint32_t rb = 1, fbits = 0;
+    if (job.residue) {
+        if (nr == 0) { set_error("residue contact frequencies: the topology has no residue table"); return ARP_ERR_BAD_INPUT; }
+        while (rb < 29u && (1ull << rb) < nr) rb++;
+        fbits = std::min<uint32_t>(kFreqFrameBitsMax, 64u - kFreqCodeBits - 2u * rb);
+        if (job.frame_bits) fbits = std::min<uint32_t>(fbits, job.frame_bits);
+        per = std::min<uint64_t>(per, (1ull << fbits) - 1u);
+    }
     if (n_rings) per = std::min<uint64_t>(per, std::max<uint64_t>(1, 0x7FFFFFF0ull / std::max<uint64_t>({n_slots, (n_rings + kFreqRingTile - 1) / kFreqRingTile, 1})));  // (one thread per (frame, slot), one workgroup per (frame, tile))
     if (per == 0) { set_error("contact frequencies: one frame exceeds 32-bit indices"); return ARP_ERR_BAD_INPUT; }
     // topology (once) and the packed arrays of one pass
@@ -235,7 +277,11 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
     // key bits: j in bits 5.., i in bits 34..; only the bits an index of n atoms + n_rings rings can set are sorted
     int ibits = 1;
     while (ibits < 29 && (1ull << ibits) < n + n_rings) ibits++;
-    const int end_bit = (int)kFreqKeyShiftI + ibits;
+    const int end_bit = job.residue ? (int)(2u * rb + kFreqCodeBits + fbits) : (int)kFreqKeyShiftI + ibits;
+    const FreqResKey rk{tp.res_id, rb + kFreqCodeBits + fbits, kFreqCodeBits + fbits, fbits};
+    const unsigned long long tag_mask = (1ull << fbits) - 1ull;
+    const auto expand_kernel = job.residue ? k_freq_expand<true> : k_freq_expand<false>;
+    const auto ring_rows_kernel = job.residue ? k_freq_ring_rows<true> : k_freq_ring_rows<false>;
     FreqBufs fb;
     struct FreeBufs { FreqBufs *b; ~FreeBufs() { if (b->block) (void)hipFree(b->block); } } fb_owner{&fb};
     uint64_t n_agg = 0;
@@ -270,14 +316,14 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
         uint32_t n_items = 0;
         for (int attempt = 0;; attempt++) {
             HIP_TRY(hipMemsetAsync(fb.counter, 0, 4, st));
-            if (n_pairs) hipLaunchKernelGGL(k_freq_expand, dim3(freq_blocks(n_pairs)), dim3(256), 0, st, pairs, (uint32_t)n_pairs, (uint32_t)n, fb.kin, fb.vin, (uint32_t)n_agg,
-                                            (uint32_t)fb.cap, fb.counter);
+            if (n_pairs) hipLaunchKernelGGL(expand_kernel, dim3(freq_blocks(n_pairs)), dim3(256), 0, st, pairs, (uint32_t)n_pairs,
+                                            (uint32_t)n, fb.kin, fb.vin, (uint32_t)n_agg, (uint32_t)fb.cap, fb.counter, rk);
             HIP_TRY(hipGetLastError());
             if (n_rings) {
                 lap("expand");
-                hipLaunchKernelGGL(k_freq_ring_rows, dim3((uint32_t)fc * ring_tiles), dim3(256), 0, st, ring_tiles, (uint32_t)n, fr, tp.attr, tp.res_ord, tp.chain_rank,
-                                   (const double *)pk.x, (const double *)pk.y, (const double *)pk.z, (const PlaneD *)planes, job.dist_cutoff, fb.kin, fb.vin, (uint32_t)n_agg,
-                                   (uint32_t)fb.cap, fb.counter);
+                hipLaunchKernelGGL(ring_rows_kernel, dim3((uint32_t)fc * ring_tiles), dim3(256), 0, st, ring_tiles, (uint32_t)n, fr,
+                                   tp.attr, tp.res_ord, tp.chain_rank, (const double *)pk.x, (const double *)pk.y, (const double *)pk.z, (const PlaneD *)planes, job.dist_cutoff,
+                                   fb.kin, fb.vin, (uint32_t)n_agg, (uint32_t)fb.cap, fb.counter, rk);
                 HIP_TRY(hipGetLastError());
             }
             HIP_TRY(hipMemcpyAsync(&n_items, fb.counter, 4, hipMemcpyDeviceToHost, st));
@@ -304,9 +350,27 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
         uint32_t runs = 0;
         HIP_TRY(hipMemcpyAsync(&runs, fb.scan + (m - 1u), 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        std::swap(fb.kin, fb.kout); std::swap(fb.vin, fb.vout);
-        n_agg = runs;
         lap("sort + reduce");
+        if (job.residue) {
+            // 5b. kout / vout hold one entry per (row, tag) sub-run, still sorted: collapse each frame's sub-run to {1, c_f, c_f}, strip the tags and
+            // reduce again by the row key -- no second sort; the next aggregate goes to kin / vin, whose items are spent
+            hipLaunchKernelGGL(k_freq_collapse, dim3(freq_blocks(runs)), dim3(256), 0, st, runs, tag_mask, fb.kout, fb.vout);
+            hipLaunchKernelGGL(k_freq_heads, dim3(freq_blocks(runs)), dim3(256), 0, st, runs, (const unsigned long long *)fb.kout, fb.head);
+            tb = fb.tmp_bytes;
+            HIP_TRY(hipcub::DeviceScan::InclusiveSum(fb.tmp, tb, (const uint32_t *)fb.head, fb.scan, (int)runs, st));
+            hipLaunchKernelGGL(k_freq_init, dim3(freq_blocks(runs)), dim3(256), 0, st, runs, fb.vin);
+            hipLaunchKernelGGL(k_freq_reduce, dim3(freq_blocks(runs)), dim3(256), 0, st, runs, (const unsigned long long *)fb.kout, (const uint32_t *)fb.iota, (const FreqVal *)fb.vout,
+                               (const uint32_t *)fb.scan, fb.kin, fb.vin);
+            HIP_TRY(hipGetLastError());
+            uint32_t rows = 0;
+            HIP_TRY(hipMemcpyAsync(&rows, fb.scan + (runs - 1u), 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            n_agg = rows;
+            lap("collapse + reduce");
+        } else {
+            std::swap(fb.kin, fb.kout); std::swap(fb.vin, fb.vout);
+            n_agg = runs;
+        }
     }
     // 6. only the aggregate comes back
     out->key.resize(n_agg); out->count.resize(n_agg); out->mn.resize(n_agg); out->mx.resize(n_agg);
@@ -317,7 +381,9 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
         HIP_TRY(hipStreamSynchronize(st));
         auto decode = [](uint32_t c) { const uint32_t b = (c & 0x80000000u) ? (c & 0x7FFFFFFFu) : ~c; float f; memcpy(&f, &b, 4); return f; };
         for (uint64_t r = 0; r < n_agg; r++) { out->count[r] = v[r].count; out->mn[r] = decode(v[r].mn); out->mx[r] = decode(v[r].mx); }
+        if (job.residue) for (uint64_t r = 0; r < n_agg; r++) out->key[r] >>= fbits;  // (the aggregate's tags are 0)
     }
+    out->res_bits = job.residue ? rb : 0u;
     lap("download");
     return ARP_OK;
 }

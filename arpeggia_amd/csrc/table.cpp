@@ -294,6 +294,8 @@ struct arp_table {
     StrCol<4> from_insertion, from_altloc, to_insertion, to_altloc;
     // contact-frequency table (arp_contact_frequencies): no model / distance / sc_* columns; these four instead, materialised when built
     bool freq = false;
+    bool freq_res = false;                     // residue level (arp_residue_contact_frequencies): no atom, altloc or atomn columns; from_residue / to_residue instead
+    std::vector<int32_t> from_residue, to_residue;
     std::vector<int32_t> from_ring, to_ring;   // ring entity index of the topology, -1 for an atom (arp_contact_frequencies_ex)
     std::vector<uint32_t> n_frames;
     std::vector<float> frequency, min_distance, max_distance;
@@ -692,6 +694,12 @@ extern "C" const void *arp_table_column(const arp_table *t_const, const char *na
         if (c == "from_ring") return num(t->from_ring.data(), 4);
         if (c == "to_ring") return num(t->to_ring.data(), 4);
         if (c == "model" || c == "distance" || c.compare(0, 3, "sc_") == 0) return nullptr;
+        if (t->freq_res) {
+            if (c == "from_residue") return num(t->from_residue.data(), 4);
+            if (c == "to_residue") return num(t->to_residue.data(), 4);
+            for (const char *none : {"from_atom", "to_atom", "from_atomi", "to_atomi", "from_atomn", "to_atomn", "from_altloc", "to_altloc", "from_ring", "to_ring"})
+                if (c == none) return nullptr;
+        }
     }
     if (c == "model") return num(t->model.data(), 4);
     if (c == "interaction") return num(t->interaction.data(), 4);
@@ -917,7 +925,8 @@ arp_status export_arrow_fast(const arp_table *t, ArrowArray *out_array, ArrowSch
 }  // namespace
 
 namespace {
-// Arrow export of a contact-frequency table: the 21 columns of FREQ_COLUMNS (api.py), from the fixed-width columns it was built with
+// Arrow export of a contact-frequency table: the 19 columns of FREQ_COLUMNS (api.py), or the 13 of RESIDUE_FREQ_COLUMNS for the residue level,
+// from the fixed-width columns it was built with
 arp_status export_arrow_freq(const arp_table *t, ArrowArray *out_array, ArrowSchema *out_schema) {
     const int64_t n = (int64_t)t->n;
     struct Field { const char *name, *format; ArrowCol *col; };
@@ -937,14 +946,13 @@ arp_status export_arrow_freq(const arp_table *t, ArrowArray *out_array, ArrowSch
     std::vector<Field> fields = {
         {"interaction", "u", names},
         {"from_chain", "u", utf8_col(t->from_chain)}, {"from_resn", "u", utf8_col(t->from_resn)}, {"from_resi", "i", numeric_col(t->from_resi)},
-        {"from_insertion", "u", utf8_col(t->from_insertion)}, {"from_altloc", "u", utf8_col(t->from_altloc)}, {"from_atomn", "u", utf8_col(t->from_atomn)},
-        {"from_atomi", "i", numeric_col(t->from_atomi)},
-        {"to_chain", "u", utf8_col(t->to_chain)}, {"to_resn", "u", utf8_col(t->to_resn)}, {"to_resi", "i", numeric_col(t->to_resi)},
-        {"to_insertion", "u", utf8_col(t->to_insertion)}, {"to_altloc", "u", utf8_col(t->to_altloc)}, {"to_atomn", "u", utf8_col(t->to_atomn)},
-        {"to_atomi", "i", numeric_col(t->to_atomi)},
-        {"n_frames", "I", numeric_col(t->n_frames)}, {"frequency", "f", numeric_col(t->frequency)},
-        {"min_distance", "f", numeric_col(t->min_distance)}, {"max_distance", "f", numeric_col(t->max_distance)},
-    };
+        {"from_insertion", "u", utf8_col(t->from_insertion)}};
+    if (!t->freq_res) fields.insert(fields.end(), {{"from_altloc", "u", utf8_col(t->from_altloc)}, {"from_atomn", "u", utf8_col(t->from_atomn)}, {"from_atomi", "i", numeric_col(t->from_atomi)}});
+    fields.insert(fields.end(), {{"to_chain", "u", utf8_col(t->to_chain)}, {"to_resn", "u", utf8_col(t->to_resn)}, {"to_resi", "i", numeric_col(t->to_resi)},
+                                 {"to_insertion", "u", utf8_col(t->to_insertion)}});
+    if (!t->freq_res) fields.insert(fields.end(), {{"to_altloc", "u", utf8_col(t->to_altloc)}, {"to_atomn", "u", utf8_col(t->to_atomn)}, {"to_atomi", "i", numeric_col(t->to_atomi)}});
+    fields.insert(fields.end(), {{"n_frames", "I", numeric_col(t->n_frames)}, {"frequency", "f", numeric_col(t->frequency)},
+                                 {"min_distance", "f", numeric_col(t->min_distance)}, {"max_distance", "f", numeric_col(t->max_distance)}});
     ArrowBatch *b = new ArrowBatch();
     ArrowFields *f = new ArrowFields();
     b->kids.resize(fields.size()); f->kids.resize(fields.size());
@@ -1126,20 +1134,29 @@ extern "C" arp_status arp_contact_frequencies(arp_context *ctx, arp_structure *s
     return arp_contact_frequencies_ex(ctx, s, n_frames, xyz, groups, vdw_comp, dist_cutoff, 0u, out);
 }
 
-extern "C" arp_status arp_contact_frequencies_ex(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
-                                                 double dist_cutoff, uint32_t flags, arp_table **out) try {
-    if (!s || !out || !groups) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
-    *out = nullptr;
+namespace {
+// What both frequency entry points do before the device runs: the checks of arp_contact_frequencies_ex (nothing here touches the device), the
+// chain groups on the topology's attribute words, the ring entities with ARP_FREQ_RINGS, and the device job.  checked_only: ctx was NULL.
+struct FreqPrep {
+    uint64_t n0 = 0, r0 = 0, F = 0;
+    std::vector<double> model_xyz;
+    std::vector<uint32_t> attr;
+    FreqRingTopo rt;
+    FreqJob job;
+    bool checked_only = false;
+};
+arp_status freq_prepare(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp, double dist_cutoff, uint32_t flags,
+                        FreqPrep *p) {
     if (flags & ~(uint32_t)ARP_FREQ_RINGS) { set_error("contact frequencies: unknown flag bits 0x%x", flags & ~(uint32_t)ARP_FREQ_RINGS); return ARP_ERR_BAD_INPUT; }
     // validation: nothing here touches the device
-    uint64_t n0 = 0, r0 = 0, nm = 1;
+    uint64_t &n0 = p->n0, &r0 = p->r0, nm = 1;
     arp_status st = freq_topology(s, xyz == nullptr, &n0, &r0, &nm);
     if (st != ARP_OK) return st;
-    const uint64_t F = xyz ? n_frames : nm;
+    const uint64_t F = p->F = xyz ? n_frames : nm;
     if (F == 0) { set_error("contact frequencies: at least one frame is needed"); return ARP_ERR_BAD_INPUT; }
     if (n0 >= (1ull << 29)) { set_error("contact frequencies: the topology has %llu atoms, at most 2^29 - 1 are supported", (unsigned long long)n0); return ARP_ERR_BAD_INPUT; }
     if (F > (1ull << 40) / std::max<uint64_t>(n0, 1)) { set_error("contact frequencies: too many frames"); return ARP_ERR_BAD_INPUT; }
-    std::vector<double> model_xyz;
+    std::vector<double> &model_xyz = p->model_xyz;
     if (!xyz) {  // the models' coordinates as F x n0 x 3
         model_xyz.resize(F * n0 * 3);
         for (uint64_t a = 0; a < F * n0; a++) { model_xyz[3 * a] = s->x[a]; model_xyz[3 * a + 1] = s->y[a]; model_xyz[3 * a + 2] = s->z[a]; }
@@ -1157,7 +1174,8 @@ extern "C" arp_status arp_contact_frequencies_ex(arp_context *ctx, arp_structure
     if (std::isnan(vdw_comp) || std::isnan(dist_cutoff)) { set_error("NaN parameter"); return ARP_ERR_BAD_INPUT; }
     // the ligand / receptor bits of this chain-group spec, with the errors of arp_get_contacts (utils.rs:71-115); the structure's own attribute
     // words are left alone (a table call on it may be using them)
-    std::vector<uint32_t> attr(n0);
+    std::vector<uint32_t> &attr = p->attr;
+    attr.resize(n0);
     std::vector<uint32_t> bits(s->chain_ids.size(), 0);
     {
         std::vector<std::string> L, R;
@@ -1169,7 +1187,7 @@ extern "C" arp_status arp_contact_frequencies_ex(arp_context *ctx, arp_structure
         for (uint64_t a = 0; a < n0; a++) attr[a] = s->base_attr[a] | bits[s->chain_rank[a]];
     }
     // ARP_FREQ_RINGS: the topology's ring entities, as entities n0 .. n0 + n_rings - 1 (a topology without rings is the table without rings)
-    FreqRingTopo rt;
+    FreqRingTopo &rt = p->rt;
     TableCache *cache = nullptr;
     uint64_t n_rings = 0;
     if (flags & ARP_FREQ_RINGS) {
@@ -1181,8 +1199,9 @@ extern "C" arp_status arp_contact_frequencies_ex(arp_context *ctx, arp_structure
             return ARP_ERR_BAD_INPUT;
         }
     }
+    p->checked_only = !ctx;
     if (!ctx) return ARP_OK;  // validation only
-    FreqJob job;
+    FreqJob &job = p->job;
     job.n = n0; job.n_res = r0; job.n_h = r0 ? s->res_h_ptr[r0] : 0; job.n_frames = F;
     job.attr = attr.data(); job.res_ord = s->res_ord.data(); job.chain_rank = s->chain_rank.data(); job.res_id = s->res_id.data();
     job.res_h_ptr = s->res_h_ptr.data(); job.res_h_idx = s->res_h_idx.data(); job.res_cb = s->res_cb.data(); job.res_sg = s->res_sg.data();
@@ -1203,8 +1222,21 @@ extern "C" arp_status arp_contact_frequencies_ex(arp_context *ctx, arp_structure
         job.rings = rt.rings.data(); job.slot_res = rt.slot_res.data(); job.cand = rt.cand.data();
         job.res_atom_ptr = cache->res_atom_ptr.data(); job.res_atom_idx = cache->res_atom_idx.data(); job.plane_bits = cache->plane_bits.data();
     }
+    return ARP_OK;
+}
+}  // namespace
+
+extern "C" arp_status arp_contact_frequencies_ex(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
+                                                 double dist_cutoff, uint32_t flags, arp_table **out) try {
+    if (!s || !out || !groups) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    *out = nullptr;
+    FreqPrep prep;
+    arp_status st = freq_prepare(ctx, s, n_frames, xyz, groups, vdw_comp, dist_cutoff, flags, &prep);
+    if (st != ARP_OK || prep.checked_only) return st;
+    const uint64_t n0 = prep.n0, F = prep.F;
+    const FreqRingTopo &rt = prep.rt;
     FreqRowsHost rows;
-    if ((st = device_frequencies(ctx, job, &rows)) != ARP_OK) return st;
+    if ((st = device_frequencies(ctx, prep.job, &rows)) != ARP_OK) return st;
     // the table: identity strings of the rows' atoms from the topology
     std::unique_ptr<arp_table> t(new arp_table());
     const size_t nrow = rows.key.size();
@@ -1242,6 +1274,45 @@ extern "C" arp_status arp_contact_frequencies_ex(arp_context *ctx, arp_structure
             memcpy(t->to_insertion.at(k), s->icode.at(j), 4); memcpy(t->to_altloc.at(k), s->altloc.at(j), 4);
             t->to_resi[k] = s->resi[j]; t->to_atomi[k] = s->serial[j]; t->to_atom[k] = (int32_t)j;
         }
+    }
+    *out = t.release();
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+// Residue level: the same checks, set-up and items; the device keys them by residue and counts a frame once per row.
+extern "C" arp_status arp_residue_contact_frequencies(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
+                                                      double dist_cutoff, uint32_t flags, arp_table **out) try {
+    if (!s || !out || !groups) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    *out = nullptr;
+    FreqPrep prep;
+    arp_status st = freq_prepare(ctx, s, n_frames, xyz, groups, vdw_comp, dist_cutoff, flags, &prep);
+    if (st != ARP_OK || prep.checked_only) return st;
+    prep.job.residue = true;
+    prep.job.frame_bits = g_debug.freq_frame_bits > 0 ? (uint32_t)g_debug.freq_frame_bits : 0u;
+    FreqRowsHost rows;
+    if ((st = device_frequencies(ctx, prep.job, &rows)) != ARP_OK) return st;
+    // a residue's identity: its first topology atom (what the residue-SASA rows take it from)
+    std::vector<uint32_t> first(prep.r0, ARP_NONE);
+    for (uint64_t a = prep.n0; a-- > 0;) first[s->res_id[a]] = (uint32_t)a;
+    std::unique_ptr<arp_table> t(new arp_table());
+    const size_t nrow = rows.key.size();
+    t->freq = true; t->freq_res = true; t->n = nrow;
+    t->interaction.resize(nrow); t->from_resi.resize(nrow); t->to_resi.resize(nrow); t->from_residue.resize(nrow); t->to_residue.resize(nrow);
+    t->from_chain.resize(nrow); t->from_resn.resize(nrow); t->to_chain.resize(nrow); t->to_resn.resize(nrow);
+    t->from_insertion.resize(nrow); t->to_insertion.resize(nrow);
+    t->n_frames = std::move(rows.count); t->min_distance = std::move(rows.mn); t->max_distance = std::move(rows.mx);
+    t->frequency.resize(nrow);
+    const uint32_t rb = rows.res_bits;
+    for (size_t k = 0; k < nrow; k++) {
+        const unsigned long long key = rows.key[k];
+        const uint32_t A = (uint32_t)(key >> (rb + 5u)), B = (uint32_t)((key >> 5) & ((1ull << rb) - 1u)), code = (uint32_t)(key & 31u);
+        t->interaction[k] = (int32_t)code;
+        t->frequency[k] = (float)((double)t->n_frames[k] / (double)prep.F);
+        const uint32_t i = first.at(A), j = first.at(B);
+        memcpy(t->from_chain.at(k), s->chain.at(i), 8); memcpy(t->from_resn.at(k), s->res_resn.at(i), 8); memcpy(t->from_insertion.at(k), s->icode.at(i), 4);
+        t->from_resi[k] = s->resi[i]; t->from_residue[k] = (int32_t)A;
+        memcpy(t->to_chain.at(k), s->chain.at(j), 8); memcpy(t->to_resn.at(k), s->res_resn.at(j), 8); memcpy(t->to_insertion.at(k), s->icode.at(j), 4);
+        t->to_resi[k] = s->resi[j]; t->to_residue[k] = (int32_t)B;
     }
     *out = t.release();
     return ARP_OK;

@@ -85,11 +85,16 @@ struct FreqJob {
     const RingEnt *rings = nullptr;
     const uint32_t *slot_res = nullptr, *res_atom_ptr = nullptr, *res_atom_idx = nullptr, *cand = nullptr;
     const uint8_t *plane_bits = nullptr;
+    // arp_residue_contact_frequencies: rows per (residue of from, residue of to, code), a frame counted once per row; the
+    // rows' keys are res(from) << (res_bits + 5) | res(to) << 5 | code.  frame_bits: the knob freq_frame_bits, 0 = automatic
+    bool residue = false;
+    uint32_t frame_bits = 0;
 };
 struct FreqRowsHost {
     std::vector<unsigned long long> key;
     std::vector<uint32_t> count;
     std::vector<float> mn, mx;
+    uint32_t res_bits = 0;  // residue level: bits of a residue ordinal in the keys
 };
 arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost *out);
 

@@ -155,6 +155,8 @@ typedef struct arp_table arp_table;         /* the 20-column contact table (mod.
  *                      force several passes; 0 (default): about 2 x 10^6 atoms per pass
  *   "freq_cap_items" N > 0: the first buffers of arp_contact_frequencies hold N items (aggregate + one pass's items) instead of max(65536, 2 x pairs),
  *                      so that tests can make the grow-and-repeat path run; 0 (default): automatic
+ *   "freq_frame_bits" k in 1 .. 17: the device keys of arp_residue_contact_frequencies carry k frame bits, so a pass holds at most 2^k - 1 frames and
+ *                      tiny inputs reach the frame cap; 0 (default): automatic (17, fewer only beyond 2^21 residues)
  *   "ens_chunk_atoms" N > 0: arp_sasa_ensemble runs its frames in passes of N packed atoms (frames x selected atoms; whole frames, at least one per
  *                      pass), so that tests can force several passes; 0 (default): about 2 x 10^6 atoms per pass
  * Unknown keys return ARP_ERR_BAD_INPUT. */
@@ -469,6 +471,33 @@ arp_status arp_contact_frequencies(arp_context *ctx, arp_structure *topology, ui
 #define ARP_FREQ_RINGS 0x1u
 arp_status arp_contact_frequencies_ex(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
                                       double dist_cutoff, uint32_t flags, arp_table **out);
+
+/* ---- residue-level contact frequencies over the frames of an ensemble -- DESIGN.md section 3.12 ----
+ * Topology, N, F frames, xyz, groups, vdw_comp and dist_cutoff exactly as arp_contact_frequencies_ex defines them.  For frame f let items(f) be
+ * the items that call defines for the same flags: (from entity, to entity, code, f32 distance) -- the atom-atom items, plus the ring items with
+ * ARP_FREQ_RINGS.  Every entity maps to a residue of the topology: atom a to the ingest's residue ordinal res_id[a] (a residue is one (chain,
+ * resi, insertion); all altlocs of a residue are the same residue; ordinals run 0 .. n_res - 1 in hierarchy order), ring entity e to the residue
+ * of its plane (the altloc entities of one ring residue are the same residue).
+ * The table has one row per distinct (A = res(from), B = res(to), code) over all frames, ordered by (A, B, code).  A residue pair is in contact
+ * in a frame when ANY of its items is, so this table cannot be derived from the atom-level one:
+ *   "n_frames" u32      the number of DISTINCT frames with at least one item of the row
+ *   "frequency" f32     f32((double)n_frames / F)
+ *   "min_distance" f32  the minimum over those frames of c_f, c_f = the smallest f32 distance among the row's items in frame f (the frame's
+ *                       closest approach under that interaction)
+ *   "max_distance" f32  the maximum over those frames of c_f -- NOT the maximum over all items
+ * Orientation is the items' own, nothing is symmetrised: (A, B, code) and (B, A, code) are different rows if both occur.
+ * Further columns: "interaction" i32 code; "from_chain" "from_resn" "from_insertion" fixed-width strings and "from_resi" i32, taken from the first
+ * topology atom of the residue (as the residue-level SASA rows take them), the same four "to_*" columns, and "from_residue" / "to_residue" i32
+ * (the ordinals A, B).  The table has no atom, altloc, atomn, atomi or ring columns: arp_table_column returns NULL for them.  The Arrow batch has
+ * the 13 columns interaction, from_chain, from_resn, from_resi, from_insertion, to_chain, to_resn, to_resi, to_insertion, n_frames, frequency,
+ * min_distance, max_distance, in that order.
+ * The bytes do not depend on the pass size (arp_debug_set "freq_chunk_atoms"), the frame bits of the device keys ("freq_frame_bits"), the first
+ * buffer capacity ("freq_cap_items") or the order in which the device produced pairs or ran atomics: two calls give identical bytes.
+ * flags accepts ARP_FREQ_RINGS only; any other bit is ARP_ERR_BAD_INPUT.  Errors and checks are arp_contact_frequencies_ex's, with the same
+ * statuses and messages, before the device is touched; ctx == NULL runs only them (ARP_OK, *out = NULL).  No new size limit: a huge topology
+ * only gets smaller passes. */
+arp_status arp_residue_contact_frequencies(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
+                                           double dist_cutoff, uint32_t flags, arp_table **out);
 
 /* ---- SASA and SAP statistics over the frames of an ensemble (MD snapshots, NMR models, conformers of one topology) -- DESIGN.md section 3.8 ----
  * Topology, N, frames and xyz exactly as arp_contact_frequencies defines them: model 0 of `topology` is the topology, frame f is xyz[f]
