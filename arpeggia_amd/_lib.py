@@ -161,6 +161,7 @@ def _load():
         "arp_sasa_sphere_points": (C.c_int32, [C.c_uint32, C.POINTER(C.c_float)]),
         "arp_atom_sasa": (C.c_int32, [vp, C.c_uint64, _dp, _dp, _dp, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.c_float, C.c_int32, C.POINTER(C.c_float), _i32p]),
         "arp_sasa_tests": (C.c_uint64, [vp]),
+        "arp_pair_rare_batches": (C.c_uint64, [vp]),
         "arp_structure_sasa_select": (C.c_int32, [vp, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), _u32p]),
         "arp_structure_atom_sasa": (C.c_int32, [vp, vp, C.c_char_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.POINTER(C.c_uint64), _u32p,
                                                 C.POINTER(C.c_float), _i32p]),

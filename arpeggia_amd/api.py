@@ -316,6 +316,10 @@ class Context:
         _check(st)
         return int(n.value)
 
+    def rare_batches(self) -> int:
+        """arp_pair_rare_batches: batches of the last collected pair pass that decided on the real residue keys (diagnostics)."""
+        return int(lib.arp_pair_rare_batches(self._h))
+
     def profile(self, on: bool):
         _check(lib.arp_profile_enable(self._h, int(on)))
 

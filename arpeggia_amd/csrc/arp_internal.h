@@ -66,6 +66,8 @@ struct GridParams {
     uint32_t rk_bad;      // k_place met a residue ordinal or chain rank that does not fit the 32-bit residue word (Sorted::rkey): the residue-rule
                           // kernels (k_emit<.., RES>) then reject nothing early -- the exact phase decides on the real keys, as always
     uint32_t sy_shift;    // cell rows run (layer, y) when 0; else in y strips of 2^sy_shift rows: (strip, layer, y inside the strip) -- grid_row
+    uint32_t key_unsorted;  // k_place<.., NARROW> met an atom whose key (model, chain rank, residue ordinal) is smaller than its predecessor's in the
+                            // input order: the narrow-record kernels then order the two atoms of every pair on the real keys (Xrec, below)
 };
 
 // Row of cells (y, layer) -> its place in the cell order; a row's nx cells are consecutive.  Layer-major order keeps a row's neighbours in the
@@ -104,6 +106,18 @@ struct __attribute__((aligned(16))) Fat {
     uint32_t res_ord, crm /* chain rank (all 32 bits; the model is not in the key: every model owns its own slab of the grid + an empty
                              separator layer, so the windows of an atom only ever hold atoms of its own model, complex.rs:96-98) */, cell /* cell id of the slot */, attr;
 };
+// The narrow exact record, 32 B = two 16-byte parts: what k_emit's 12-wave kernels gather per survivor and k_place<.., NARROW> scatters per atom
+// when the launcher chose it (emit_narrow_bits, pairs.inl); it lives in the memory of Sorted::fat.  `ot` = original index in the HIGH `ib` bits
+// (the call's index width, a kernel argument: two records compare like their indices) and below them the low T = 32 - ib bits of the atom's TAG
+// (chain rank << kRkOrdBits) + residue ordinal, computed modulo 2^32.  The cell, the attribute word and the chain key of the wide record are not here: a task recomputes its home
+// cells from the coordinates (cell_coords, grid.inl), and whoever needs the real chain rank / ordinal / attribute word reads the caller's
+// arrays by the original index (the batch's rare branch in exact_finish_e, fat_from_narrow in the probe passes).
+struct __attribute__((aligned(16))) Xrec {
+    double x, y;
+    double z; uint32_t pw, ot;
+};
+constexpr uint32_t kNarrowMaxBits = 20;  // index bits of Xrec::ot at most (2^20 atoms): the tag keeps 12 bits or more.  Fewer tag bits alias too often: a resident input of
+                                         // 1250 five-thousand-atom models (6.25 x 10^6 atoms, 23 + 9 bits) ran k_emit 48 us longer than on the wide record, k_place 35 us shorter
 constexpr uint32_t kPwLigand = 1u << 24, kPwReceptor = 1u << 25, kPwResHasH = 1u << 30;  // (bits 26-29 and 31 stay clear: the emit kernel ANDs the word with a table entry's probe bits)
 
 // Cell-sorted copy of the heavy atoms (slot order: x-major cells, atoms of a cell in ascending input index).
@@ -127,7 +141,8 @@ constexpr uint32_t kTaskCtrWords = 4 * 8 * kTaskCtrStride;    // [mode][group]
 // arp_context::h_result after every pass; the kernels write them, engine.cpp pass_collect reads them): total pairs; status bits (kStat*); emit
 // allocator head (64-record units; records in the hole-free sequence); chunks of the deferred-probe list; how many of the first 255 atoms
 // carry their predecessor's residue word (k_place: the launcher's hint for the next call).  kSasaTestsWord: the SASA kernel's f32 distance tests.
-enum : uint32_t { kResPairs = 0, kResFlags = 1, kResEmitHead = 2, kResDeferred = 3, kResResRuns = 4, kResultWords = 5, kSasaTestsWord = 8 };
+enum : uint32_t { kResPairs = 0, kResFlags = 1, kResEmitHead = 2, kResDeferred = 3, kResResRuns = 4, kResRare = 5, kResultWords = 6, kSasaTestsWord = 8 };
+// kResRare: batches of the narrow-record emit kernels that fetched the real chain keys (exact_finish_e's rare branch) -- arp_pair_rare_batches
 // Status bits: the list did not fit the capacity / CYS SG..SG covalent pair whose residue has no CB / non-finite coordinate / the deferred-probe
 // list overflowed / k_fixup's hole plan is inconsistent / model ids too sparse for the workspace / the probe pass was skipped on a stale memo
 constexpr unsigned long long kStatCapacity = 1, kStatCysNoCb = 2, kStatNonFinite = 4, kStatDeferOverflow = 8, kStatHolePlan = 16,
@@ -190,13 +205,17 @@ struct Profiler {
 };
 
 // Launch wrappers (kernels.hip / pairs.inl).  All asynchronous on `st`.
-void launch_grid(const DevAtoms &in, const Workspace &ws, hipStream_t st, Profiler *prof, double cutoff, bool ordered, bool want_rkey = false);
+// narrow_ib != 0: k_place writes the narrow exact record (Xrec) with that many index bits instead of the wide one (Fat) -- only for a grid whose
+// one reader is launch_emit with the same narrow_ib (emit_narrow_bits says whether there are kernels for it)
+void launch_grid(const DevAtoms &in, const Workspace &ws, hipStream_t st, Profiler *prof, double cutoff, bool ordered, bool want_rkey = false, uint32_t narrow_ib = 0);
 void launch_count(const DevAtoms &in, const Workspace &ws, hipStream_t st, Profiler *prof, unsigned long long capacity, bool have_out, bool contacts_only);
 void launch_fill_ordered(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsigned long long capacity, hipStream_t st, Profiler *prof,
                          bool contacts_only);
 bool launch_emit(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsigned long long capacity, hipStream_t st, Profiler *prof, bool contacts_only,
-                 bool skip_deferred, bool res_filter = false);  // true: the hole-free sequence of small inputs ran (the host derives kResPairs and the flags: engine.cpp finish_result)
+                 bool skip_deferred, bool res_filter = false, uint32_t narrow_ib = 0);  // true: the hole-free sequence of small inputs ran (the host derives kResPairs and the flags: engine.cpp finish_result)
 bool emit_takes_res_filter(const DevAtoms &in);  // the single-pass emitter has residue-rule kernels for an input of this size (the grid build then writes Sorted::rkey)
+// index bits of the narrow exact record the single-pass emitter would read for this input (skip_deferred: as launch_emit will be called); 0: it reads the wide record
+uint32_t emit_narrow_bits(const DevAtoms &in, const Workspace &ws, bool skip_deferred);
 unsigned long long emit_scratch_records();
 void launch_neighbor_sum(const DevAtoms &in, const Workspace &ws, double radius, double r2, const float *weight, float *out, hipStream_t st, Profiler *prof);
 // Atom SASA (sasa.inl): the grid over the atoms without ARP_ATTR_H, then one wave per grid atom.  buried == nullptr: k_sasa; sasa / count hold

@@ -379,25 +379,32 @@ static arp_status grow_defer_list(arp_context *ctx, uint64_t n) {
 
 // ---- the pair pass ---------------------------------------------------------------------------------------------
 // One protocol for every caller (PairPass, engine.h): the callers differ in what they put into the PairPass and in how they grow their pair buffer.
-void arp::mark_grid_owner(arp_context *ctx, const double *x, uint64_t n, bool rkey_valid) { ctx->grid_x = x; ctx->grid_n = n; ctx->rkey_valid = rkey_valid; }
+void arp::mark_grid_owner(arp_context *ctx, const double *x, uint64_t n, bool rkey_valid, uint32_t narrow_ib) {
+    ctx->grid_x = x; ctx->grid_n = n; ctx->rkey_valid = rkey_valid; ctx->narrow_ib = narrow_ib;
+}
 void arp::mark_grid_foreign(arp_context *ctx) {
     mark_grid_owner(ctx, nullptr, 0, false);  // the workspace's cell list holds another input (context_grid must not hand it out)
     ctx->nodefer_x = nullptr; ctx->nodefer_n = 0;
 }
 
 // Builds the cell list of a pass, records whose it is; decides whether the pass will run the residue-rule kernels (k_place then writes the residue words).
-static void grid_for_call(arp_context *ctx, const DevAtoms &d, const arp_params *params, Profiler *prof, bool ordered) {
+// narrow_ok: the single-pass emitter is the list's one reader (an Emit pass nobody walks the records after): it gets the narrow exact record when it has
+// kernels for this input (emit_narrow_bits) -- k_place then scatters three 16-byte parts per atom instead of four, k_emit gathers two per survivor instead of three.
+static void grid_for_call(arp_context *ctx, const DevAtoms &d, const arp_params *params, Profiler *prof, bool ordered, bool narrow_ok, bool skip_deferred) {
     bool res = !ordered && emit_takes_res_filter(d);
     if (res) res = (params->flags & ARP_FLAG_RESIDUE_RUNS) ? true : ((params->flags & ARP_FLAG_NO_RESIDUE_RUNS) ? false : ctx->res_hint);
-    launch_grid(d, ctx->ws, ctx->stream, prof, params->dist_cutoff, ordered, res);
-    mark_grid_owner(ctx, d.per_model ? nullptr : d.x, d.per_model ? 0 : d.n, res);  // (a pack's grid, per-model origins, is nobody's)
+    const uint32_t narrow_ib = (narrow_ok && !ordered) ? emit_narrow_bits(d, ctx->ws, skip_deferred) : 0u;
+    launch_grid(d, ctx->ws, ctx->stream, prof, params->dist_cutoff, ordered, res, narrow_ib);
+    mark_grid_owner(ctx, d.per_model ? nullptr : d.x, d.per_model ? 0 : d.n, res, narrow_ib);  // (a pack's grid, per-model origins, is nobody's)
 }
 
 arp_status arp::pass_issue(arp_context *ctx, PairPass &p) {
     const bool ordered = (p.params->flags & ARP_FLAG_DETERMINISTIC) != 0, only = (p.params->flags & ARP_FLAG_CONTACTS_ONLY) != 0;
     Profiler *prof = p.profile ? context_profiler(ctx) : nullptr;
     p.skip = p.direct = p.collected = false;
-    if (p.grid) grid_for_call(ctx, p.d, p.params, prof, ordered);
+    const bool emit = p.mode == PairPass::Emit;
+    if (emit) p.skip = p.speculate && p.d.x != nullptr && ctx->nodefer_x == p.d.x && ctx->nodefer_n == p.d.n;  // the memo names this input
+    if (p.grid) grid_for_call(ctx, p.d, p.params, prof, ordered, emit && !p.wide_record, p.skip);
     if (p.mode == PairPass::Count) {
         // (with ARP_FLAG_CONTACTS_ONLY the count that sizes the single-pass emitter's buffer is the cheap candidate count; the ordered fill needs the exact one)
         launch_count(p.d, ctx->ws, ctx->stream, prof, p.capacity, p.have_out, p.have_out ? only : only && ordered);
@@ -405,8 +412,7 @@ arp_status arp::pass_issue(arp_context *ctx, PairPass &p) {
         if (p.grid) launch_count(p.d, ctx->ws, ctx->stream, prof, p.capacity, true, only);
         launch_fill_ordered(p.d, ctx->ws, p.out, p.capacity, ctx->stream, prof, only);
     } else {
-        p.skip = p.speculate && p.d.x != nullptr && ctx->nodefer_x == p.d.x && ctx->nodefer_n == p.d.n;  // the memo names this input
-        p.direct = launch_emit(p.d, ctx->ws, p.out, p.capacity, ctx->stream, prof, only, p.skip, ctx->rkey_valid);
+        p.direct = launch_emit(p.d, ctx->ws, p.out, p.capacity, ctx->stream, prof, only, p.skip, ctx->rkey_valid, ctx->narrow_ib);
     }
     arp_status s;
     if (p.between && (s = p.between(ctx, p, p.between_arg)) != ARP_OK) return s;
@@ -506,7 +512,7 @@ extern "C" arp_status arp_contacts_atomic_result(arp_context *ctx, uint64_t *n_p
 // Single-pass emitter into the context's reusable device buffer: ONE pass -- no count pass, no hipMalloc/hipFree per call (together
 // ~half of the latency of a PDB-sized structure).  A buffer that turns out too small only makes the pass report the size (k_fixup);
 // it is then grown and the pass repeated.  Leaves the list in ctx->out_buf[0 .. *total).
-static arp_status single_pass_into_context_buffer(arp_context *ctx, const DevAtoms &d, const arp_params *params, unsigned long long *total_out) {
+static arp_status single_pass_into_context_buffer(arp_context *ctx, const DevAtoms &d, const arp_params *params, unsigned long long *total_out, bool wide_record = false) {
     arp_status s;
     // first guess: 64 records per atom (twice the all-pairs density of a protein), at most 2 GiB; a larger result costs one more pass
     uint64_t want = std::max<uint64_t>(ctx->out_cap, std::min<uint64_t>(std::max<uint64_t>(64 * (uint64_t)d.n, 1u << 16), 1u << 27));
@@ -514,6 +520,7 @@ static arp_status single_pass_into_context_buffer(arp_context *ctx, const DevAto
         if (ctx->out_cap < want && (s = regrow(ctx, (void **)&ctx->out_buf, &ctx->out_cap, want, want * sizeof(arp_pair), false)) != ARP_OK) return s;
         PairPass p{d, params, ctx->out_buf, ctx->out_cap, PairPass::Emit};
         p.memo = p.speculate = true;  // (the synchronous paths use the memo whatever ARP_FLAG_NO_SPECULATION says)
+        p.wide_record = wide_record;
         if ((s = pass_run(ctx, p)) != ARP_OK) return s;
         const unsigned long long total = *total_out = ctx->h_result[kResPairs];
         if (total <= ctx->out_cap) return ARP_OK;
@@ -536,7 +543,7 @@ arp_status arp::contacts_atomic_view(arp_context *ctx, const arp_atoms *atoms, c
     if ((s = upload_params(ctx, params)) != ARP_OK) return s;
     unsigned long long total = 0;
     const auto t0 = std::chrono::steady_clock::now();
-    s = single_pass_into_context_buffer(ctx, d, params, &total);
+    s = single_pass_into_context_buffer(ctx, d, params, &total, /* wide_record: the table path's ring walk reads Fat by slot (context_grid) */ true);
     if (g_debug.timing) fprintf(stderr, "    pair pass (launches + sync)      %8.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     if (s != ARP_OK) return s;
     *data = ctx->out_buf; *n = total;
@@ -590,7 +597,7 @@ namespace arp {
 void *context_stream(arp_context *ctx) { return (void *)ctx->stream; }
 int context_device(arp_context *ctx) { return ctx->device; }
 bool context_grid(arp_context *ctx, const double *x, uint64_t n, const GridParams **grid, const uint32_t **cell_start, const Fat **fat) {
-    if (!ctx || ctx->pending || !ctx->ws.grid || !x || ctx->grid_x != x || ctx->grid_n != n) return false;
+    if (!ctx || ctx->pending || !ctx->ws.grid || !x || ctx->grid_x != x || ctx->grid_n != n || ctx->narrow_ib != 0u) return false;
     *grid = ctx->ws.grid; *cell_start = ctx->ws.cell_start; *fat = ctx->ws.sorted.fat;
     return true;
 }
@@ -639,6 +646,8 @@ extern "C" int32_t arp_profile_read(arp_context *ctx, const char **names, float 
 
 // ---- library-level -----------------------------------------------------------------------------------------------
 namespace arp { DebugKnobs g_debug{0, 0, 0, 0, 0, 0, 0, 0, 0}; }
+extern "C" uint64_t arp_pair_rare_batches(const arp_context *ctx) { return (ctx && ctx->h_result) ? ctx->h_result[kResRare] : 0u; }
+
 extern "C" arp_status arp_debug_set(const char *key, int64_t value) {
     if (!key) { set_error("null key"); return ARP_ERR_BAD_INPUT; }
     const std::string k(key);
@@ -662,11 +671,15 @@ extern "C" arp_status arp_debug_set(const char *key, int64_t value) {
         if (value < 0) { set_error("arp_debug_set: ens_chunk_atoms takes 0 (automatic) or a positive atom count"); return ARP_ERR_BAD_INPUT; }
         g_debug.ens_chunk_atoms = (long)value;
     }
+    else if (k == "index_bits") {
+        if (value > (int64_t)kNarrowMaxBits) { set_error("arp_debug_set: index_bits takes 0 (automatic), 1 .. 20 (the index width of the narrow exact record) or a negative value (the wide record always)"); return ARP_ERR_BAD_INPUT; }
+        g_debug.index_bits = (int)value;
+    }
     else if (k == "strip_rows") {
         if (value < 0 || value > 1024 || (value & (value - 1)) != 0) { set_error("arp_debug_set: strip_rows takes 0 or a power of two up to 1024"); return ARP_ERR_BAD_INPUT; }
         g_debug.strip_rows = (int)value;
     }
-    else { set_error("arp_debug_set: unknown key '%s' (timing, emit_kernel, defer_entries, strip_rows, table_host, freq_chunk_atoms, freq_cap_items, freq_frame_bits, ens_chunk_atoms)", key); return ARP_ERR_BAD_INPUT; }
+    else { set_error("arp_debug_set: unknown key '%s' (timing, emit_kernel, defer_entries, strip_rows, index_bits, table_host, freq_chunk_atoms, freq_cap_items, freq_frame_bits, ens_chunk_atoms)", key); return ARP_ERR_BAD_INPUT; }
     return ARP_OK;
 }
 extern "C" int32_t arp_api_version(void) { return ARP_API_VERSION; }

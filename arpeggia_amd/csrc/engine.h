@@ -23,6 +23,7 @@ struct PairPass {
     arp_status (*between)(arp_context *ctx, const PairPass &p, void *arg) = nullptr; void *between_arg = nullptr;
     // set by pass_issue: the probe pass was skipped / the hole-free sequence ran; by pass_finish: its status is what the pass reported, not a runtime failure
     bool skip = false, direct = false, collected = false;
+    bool wide_record = false;  // Emit: the cell list must carry the wide exact record (Fat) -- somebody reads it after the pass (the ring walk of the table path)
 };
 constexpr arp_status kRetryDefer = -1;  // internal, never crosses the C ABI: the deferred-probe list overflowed (pass_finish with max_reissues)
 }  // namespace arp
@@ -55,6 +56,7 @@ struct arp_context {
     // its residue words (Sorted::rkey) were written with it
     const double *grid_x = nullptr; uint64_t grid_n = 0;
     bool rkey_valid = false;
+    uint32_t narrow_ib = 0;                // ... and, when != 0, that its exact records are the narrow ones (Xrec) with that many index bits
     // Deferred-pass memo: the arrays (address + length) of the last single-pass call that deferred NOTHING to the probe pass (no hydrogens,
     // no CYS SG pair in the covalent band -- every X-ray structure without hydrogens).  The next call on the same arrays does not launch
     // k_pairs_deferred; should it defer after all (the caller rewrote the arrays), k_fixup raises kStatStaleSkip and the call is repeated
@@ -88,7 +90,7 @@ arp_status regrow_staged(arp_context *ctx, uint64_t cap);
 inline Profiler *context_profiler(arp_context *ctx) { return ctx->prof.enabled ? &ctx->prof : nullptr; }
 // The workspace's cell list now belongs to the arrays (x, n) (x == nullptr: to an input nothing can name, a pack) / to a caller outside the
 // pair pass, which also drops the deferred-pass memo.  Every path that builds a grid in the context's workspace says which.
-void mark_grid_owner(arp_context *ctx, const double *x, uint64_t n, bool rkey_valid);
+void mark_grid_owner(arp_context *ctx, const double *x, uint64_t n, bool rkey_valid, uint32_t narrow_ib = 0);
 void mark_grid_foreign(arp_context *ctx);
 arp_status pass_issue(arp_context *ctx, PairPass &p);   // asynchronous on the context's stream
 // An issued pass: synchronise, collect; on a stale memo or after growing an overflowed deferred-probe list queue it again (reissue: the caller's way) and start over.

@@ -70,6 +70,7 @@ DEVFN float grid_setup(const double lo_in[3], const double hi_in[3], bool empty,
     g->n_heavy = 0; g->n_tasks = 0;
     g->bad = bad;
     g->rk_bad = 0u;
+    g->key_unsorted = 0u;
     // f32 prefilter: relative coordinates carry <= 2^-24 * extent of rounding each; a 10x-safe bound on the
     // induced error of dx^2+dy^2+dz^2 near the cutoff (derivation in DESIGN.md "Prefilter margin")
     const double M = fmax(ext[0], fmax(ext[1], ext[2])) + edge;
@@ -294,16 +295,22 @@ __global__ __launch_bounds__(256) void k_setup(const double *partials, uint32_t 
     setup_block(acc, l, true, g, prm, cutoff, ncells_cap, n_atoms, result, task_ctr, model_box, model_org);
 }
 
-DEVFN uint32_t cell_index(const GridParams &g, double x, double y, double z, uint32_t model) {
+// Cell column, row and z layer of a point.  One function for k_cellid (cell_index below) and for the narrow-record emit kernels, which
+// recompute the cell of a task's home atoms from the same f64 coordinates and the same GridParams instead of reading it from the record.
+DEVFN void cell_coords(const GridParams &g, double x, double y, double z, uint32_t model, uint32_t &cx, uint32_t &cy, uint32_t &layer) {
     double ox = g.ox, oy = g.oy, oz = g.oz;
     if (g.model_org) { const double *o = g.model_org + 6u * min(model, kPackModels - 1u); ox = o[0]; oy = o[1]; oz = o[2]; }  // packed batch: the member's own corner
     double fx = (x - ox) * g.inv_edge_x, fy = (y - oy) * g.inv_edge, fz = (z - oz) * g.inv_edge;
-    uint32_t cx = (fx >= 0.0) ? (uint32_t)fmin(fx, 4.0e9) : 0u;  // NaN -> 0
-    uint32_t cy = (fy >= 0.0) ? (uint32_t)fmin(fy, 4.0e9) : 0u;
+    cx = (fx >= 0.0) ? (uint32_t)fmin(fx, 4.0e9) : 0u;  // NaN -> 0
+    cy = (fy >= 0.0) ? (uint32_t)fmin(fy, 4.0e9) : 0u;
     uint32_t cz = (fz >= 0.0) ? (uint32_t)fmin(fz, 4.0e9) : 0u;
     cx = min(cx, g.nx - 1u); cy = min(cy, g.ny - 1u); cz = min(cz, g.nz - 1u);
-    uint32_t layer = model * (g.nz + 1u) + cz;  // every model owns a z slab followed by one empty layer
+    layer = model * (g.nz + 1u) + cz;  // every model owns a z slab followed by one empty layer
     layer = min(layer, g.nzt - 1u);
+}
+DEVFN uint32_t cell_index(const GridParams &g, double x, double y, double z, uint32_t model) {
+    uint32_t cx, cy, layer;
+    cell_coords(g, x, y, z, model, cx, cy, layer);
     return grid_row(cy, layer, g.ny, g.nzt, g.sy_shift) * g.nx + cx;
 }
 
@@ -653,13 +660,22 @@ DEVFN uint32_t residue_word(uint32_t res_ord, uint32_t chain_rank, bool *bad) {
     *bad = (res_ord > kRkOrdMax) | (chain_rank > kRkChainMax);
     return ((chain_rank & kRkChainMax) << kRkOrdBits) + (res_ord & ((1u << kRkOrdBits) - 1u));
 }
+// The tag of an atom in the narrow record (arp_internal.h Xrec::ot keeps its low 32 - ib bits): the same sum WITHOUT the range masks, modulo 2^32,
+// so that for ANY two atoms of one chain  tag b - tag a = ordinal b - ordinal a  (mod 2^32) -- what exact_finish_e's tag test rests on.
+DEVFN uint32_t narrow_tag(uint32_t res_ord, uint32_t chain_rank) { return (chain_rank << kRkOrdBits) + res_ord; }
 // RKEY: also write the residue words of the slots (the launcher is about to run the residue-rule kernels, k_emit<.., RES>).
 // Block 0 always leaves result[4] = how many of atoms 1..255 carry their predecessor's residue word: inputs whose residues are runs of atoms
 // (every protein; not a cloud of one-atom residues) are the ones the residue-rule kernels pay for, and the engine picks the kernels of the
 // NEXT call by it (engine.cpp grid_for_call) -- a choice between two kernels with identical results, never a correctness assumption.
-template <bool RKEY>
+// NARROW: the exact record is the 32-byte Xrec (arp_internal.h) with `ib` index bits -- three 16-byte scattered stores per atom instead of four.
+// The kernels that read it take the ligand of a pair to be the atom with the smaller ORIGINAL INDEX, which is the reference's choice (the
+// smaller (chain rank, ordinal) key, complex.rs:108-130) whenever the keys never decrease along the input order: every thread compares its atom's
+// key (model, chain rank, ordinal) with its predecessor's here, and the first that finds a decrease raises GridParams::key_unsorted -- those
+// kernels then order every pair on the real keys.  (Keys non-decreasing in the index and ka != kb  =>  ka < kb <=> index a < index b; a pair
+// with ka == kb is one residue's and never a candidate.)
+template <bool RKEY, bool NARROW = false>
 __global__ __launch_bounds__(256) void k_place(DevAtoms in, GridParams *gp, const uint32_t *cell_start, const uint32_t *cell_of_atom,
-                                               const uint32_t *rank_of_atom, Sorted so, unsigned long long *result) {
+                                               const uint32_t *rank_of_atom, Sorted so, unsigned long long *result, uint32_t ib) {
     const uint32_t i0 = blockIdx.x * (256u * kPlacePer) + threadIdx.x;
     if (i0 == 0) { const uint32_t n_heavy = cell_start[gp->ncells]; gp->n_heavy = n_heavy; gp->n_tasks = (n_heavy + 63u) / 64u; }
     if (in.n == 0u) return;
@@ -683,6 +699,11 @@ __global__ __launch_bounds__(256) void k_place(DevAtoms in, GridParams *gp, cons
         x[u] = in.x[i]; y[u] = in.y[i]; z[u] = in.z[i];
         at[u] = in.attr[i]; ro[u] = in.res_ord[i]; cr[u] = in.chain_rank[i]; md[u] = in.model[i];
         rid[u] = any_h ? in.res_id[i] : 0u;
+        if (NARROW && i != 0u && i0 + u * 256u <= last) {  // the predecessor's key (the same lines the neighbouring lanes read)
+            const uint32_t pm = in.model[i - 1u], pc = in.chain_rank[i - 1u], po = in.res_ord[i - 1u];
+            const bool down = pm > md[u] || (pm == md[u] && (pc > cr[u] || (pc == cr[u] && po > ro[u])));
+            if (down && __hip_atomic_load(&gp->key_unsorted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) atomicOr(&gp->key_unsorted, 1u);
+        }
     }
     uint32_t d[kPlacePer], h0[kPlacePer], h1[kPlacePer];
     double mx[kPlacePer], my[kPlacePer], mz[kPlacePer];
@@ -706,12 +727,19 @@ __global__ __launch_bounds__(256) void k_place(DevAtoms in, GridParams *gp, cons
         // pass resolves residue -> hydrogens itself (hbond.rs:38-42)
         const bool has_h = h0[u] < h1[u];
         const uint32_t attr = at[u] & ~kAttrResHasH;
-        Fat f;
-        f.x = x[u]; f.y = y[u]; f.z = z[u];
-        f.pw = make_pair_word(attr, has_h); f.res_ord = ro[u];
-        f.crm = cr[u]; f.orig = i; f.cell = c[u];
-        f.attr = attr | (has_h ? kAttrResHasH : 0u);
-        so.fat[slot] = f;
+        if (NARROW) {
+            Xrec r;
+            r.x = x[u]; r.y = y[u]; r.z = z[u];
+            r.pw = make_pair_word(attr, has_h); r.ot = (i << (32u - ib)) | (narrow_tag(ro[u], cr[u]) & (0xFFFFFFFFu >> ib));  // (i < 2^ib: the launcher's condition)
+            reinterpret_cast<Xrec *>(so.fat)[slot] = r;
+        } else {
+            Fat f;
+            f.x = x[u]; f.y = y[u]; f.z = z[u];
+            f.pw = make_pair_word(attr, has_h); f.res_ord = ro[u];
+            f.crm = cr[u]; f.orig = i; f.cell = c[u];
+            f.attr = attr | (has_h ? kAttrResHasH : 0u);
+            so.fat[slot] = f;
+        }
         if (RKEY) {
             bool bad;
             so.rkey[slot] = residue_word(ro[u], cr[u], &bad);

@@ -195,15 +195,30 @@ DEVFN void load_lds_params(LdsParams &prm, const DevParams *dprm, const GridPara
 // Phase 2 on up to 64 survivors.  Returns the number of valid candidate pairs of the batch.  PROBES == false keeps the
 // rare data-dependent rules (hydrogen-bond angle test over the donor residue's hydrogens, disulfide dihedral) out of the
 // hot kernel -- they cost it half its occupancy in registers: such pairs go to a list that k_pairs_deferred finishes.
+// The wide record of a slot rebuilt from the narrow one (arp_internal.h Xrec; ib: its index bits) and the caller's arrays -- the probe passes behind a
+// narrow-record emit kernel (a few list entries per call): everything orient() and classify() read; the cell is nobody's there.
+DEVFN Fat fat_from_narrow(const DevAtoms &in, const Sorted &so, uint32_t slot, uint32_t ib) {
+    const Xrec r = reinterpret_cast<const Xrec *>(so.fat)[slot];
+    Fat f;
+    f.x = r.x; f.y = r.y; f.z = r.z; f.pw = r.pw;
+    f.orig = r.ot >> (32u - ib);
+    f.res_ord = in.res_ord[f.orig]; f.crm = in.chain_rank[f.orig]; f.cell = 0u;
+    f.attr = (in.attr[f.orig] & ~kAttrResHasH) | ((r.pw & kPwResHasH) ? kAttrResHasH : 0u);  // (what k_place puts into Fat::attr)
+    return f;
+}
+
+// ib != 0 (k_pairs_deferred behind a narrow-record emit kernel): the slots hold narrow records with that many index bits
 template <int MODE, bool PROBES>
 DEVFN uint32_t process_batch(const DevAtoms &in, const LdsParams &prm, const Sorted &so, WaveLds<MODE> &w, BlockLds &bl, uint2 ent, bool active,
-                             unsigned long long base, uint32_t emitted, const EmitTarget &tg, unsigned long long *result, uint32_t lane, uint32_t wflags) {
+                             unsigned long long base, uint32_t emitted, const EmitTarget &tg, unsigned long long *result, uint32_t lane, uint32_t wflags,
+                             uint32_t ib = 0u) {
     bool valid = false, swap = false;
     double s = 0.0;
     Fat a, b;
     const bool all_both = !PROBES && (wflags & kWaveAllBoth);  // wave-uniform (held in a scalar register): a scalar branch, no divergence
     if (active) {
-        a = fat_at<PROBES>(so.fat, ent.x); b = fat_at<PROBES>(so.fat, ent.y);  // the probe variants keep 64-bit addressing (inputs of any size)
+        if (PROBES && ib) { a = fat_from_narrow(in, so, ent.x, ib); b = fat_from_narrow(in, so, ent.y, ib); }
+        else { a = fat_at<PROBES>(so.fat, ent.x); b = fat_at<PROBES>(so.fat, ent.y); }  // the probe variants keep 64-bit addressing (inputs of any size)
         s = sq_dist(a.x, a.y, a.z, b.x, b.y, b.z);
         const int o = all_both ? orient_all_both(a, b) : orient(a, b);
         valid = (s <= prm.r2) & (o != 0);  // rstar: inclusive
@@ -475,7 +490,8 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, ((MODE == kEmit || MODE == kFi
 // inline and emitted through the same allocator (its blocks add their own holes to the list k_fixup closes).
 constexpr uint32_t kDeferBlocks = 384;       // fills the chip at this kernel's 3 waves per SIMD when the list is long
 __global__ __launch_bounds__(kWavesPerBlock * 64) void k_pairs_deferred(DevAtoms in, const DevParams *dprm, Sorted so, EmitTarget tg,
-                                                                         ulonglong2 *hole_list, unsigned long long *result, uint32_t chunk_shift) {
+                                                                         ulonglong2 *hole_list, unsigned long long *result, uint32_t chunk_shift,
+                                                                         uint32_t ib /* != 0: narrow records with that many index bits (fat_from_narrow) */) {
     __shared__ LdsParams prm;
     __shared__ WaveLds<kEmit> wl[kWavesPerBlock];
     __shared__ BlockLds bl;
@@ -497,7 +513,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void k_pairs_deferred(DevAtoms
         uint2 ent = make_uint2(0xFFFFFFFFu, 0u);
         if (e0 + lane < n) ent = tg.defer_list[e0 + lane];
         const bool act = ent.x != 0xFFFFFFFFu;  // chunk tails hold sentinels
-        process_batch<kEmit, true>(in, prm, so, wl[wave], bl, ent, act, 0ull, 0u, tg, result, lane, wflags);
+        process_batch<kEmit, true>(in, prm, so, wl[wave], bl, ent, act, 0ull, 0u, tg, result, lane, wflags, ib);
     }
     emit_epilogue(bl, hole_list + blockIdx.x, tg);
 }
@@ -505,7 +521,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void k_pairs_deferred(DevAtoms
 // The deferred pass of the fast ordered fill and of the single-pass emitter's all-candidates mode: {entry, position} pairs; the probes
 // decide the kind, which is patched in place (positions beyond the caller's capacity live in the engine's scratch until k_fixup).
 __global__ __launch_bounds__(kWavesPerBlock * 64) void k_patch_deferred(DevAtoms in, const DevParams *dprm, Sorted so, EmitTarget tg,
-                                                                         unsigned long long *result) {
+                                                                         unsigned long long *result, uint32_t ib /* as k_pairs_deferred */) {
     __shared__ LdsParams prm;
     const unsigned long long n = min(result[kResDeferred] * kDeferChunk, tg.defer_cap) / 2ull;  // {entry, position} pairs
     if (n == 0ull) return;  // nothing was deferred (no hydrogens, no close CYS SG pair)
@@ -514,7 +530,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void k_patch_deferred(DevAtoms
     for (unsigned long long q = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (unsigned long long)gridDim.x * blockDim.x) {
         const uint4 e = list[q];
         if (e.x == 0xFFFFFFFFu) continue;  // chunk tail
-        const Fat a = so.fat[e.x], b = so.fat[e.y];
+        const Fat a = ib ? fat_from_narrow(in, so, e.x, ib) : so.fat[e.x], b = ib ? fat_from_narrow(in, so, e.y, ib) : so.fat[e.y];
         const double s = sq_dist(a.x, a.y, a.z, b.x, b.y, b.z);
         const bool swap = orient(a, b) == 2;
         const uint32_t kind = classify<true>(in, prm, s, a, b, swap, result);
@@ -660,7 +676,8 @@ static uint32_t blocks_for(uint32_t n, uint32_t cap) {
 
 unsigned long long emit_scratch_records() { return (unsigned long long)kMaxHoles * kChunkRecords; }
 
-void launch_grid(const DevAtoms &in, const Workspace &ws, hipStream_t st, Profiler *prof, double cutoff, bool ordered, bool want_rkey) {
+void launch_grid(const DevAtoms &in, const Workspace &ws, hipStream_t st, Profiler *prof, double cutoff, bool ordered, bool want_rkey, uint32_t narrow_ib) {
+    if (ordered) narrow_ib = 0u;  // (the ordered fill's kernels read the wide record)
     const uint32_t n = in.n;
     const uint32_t nb = (n + 255) / 256;
     auto P0 = [&](const char *nm) { if (prof) prof->begin(nm, st); };
@@ -702,8 +719,11 @@ void launch_grid(const DevAtoms &in, const Workspace &ws, hipStream_t st, Profil
                            (const uint32_t *)ws.slot_cell, ws.sorted);
     } else {
         const dim3 pb((n + 256u * kPlacePer - 1u) / (256u * kPlacePer) + (n ? 0u : 1u));
-        if (want_rkey) hipLaunchKernelGGL(k_place<true>, pb, dim3(256), 0, st, in, ws.grid, (const uint32_t *)ws.cell_start, (const uint32_t *)ws.cell_of_atom, (const uint32_t *)ws.rank_of_atom, ws.sorted, ws.result);
-        else hipLaunchKernelGGL(k_place<false>, pb, dim3(256), 0, st, in, ws.grid, (const uint32_t *)ws.cell_start, (const uint32_t *)ws.cell_of_atom, (const uint32_t *)ws.rank_of_atom, ws.sorted, ws.result);
+#define ARP_LAUNCH_PLACE(RK, NW) hipLaunchKernelGGL((k_place<RK, NW>), pb, dim3(256), 0, st, in, ws.grid, (const uint32_t *)ws.cell_start, (const uint32_t *)ws.cell_of_atom, \
+                                                    (const uint32_t *)ws.rank_of_atom, ws.sorted, ws.result, narrow_ib)
+        if (narrow_ib) { if (want_rkey) ARP_LAUNCH_PLACE(true, true); else ARP_LAUNCH_PLACE(false, true); }
+        else { if (want_rkey) ARP_LAUNCH_PLACE(true, false); else ARP_LAUNCH_PLACE(false, false); }
+#undef ARP_LAUNCH_PLACE
     }
     P1();
 }
@@ -740,7 +760,7 @@ void launch_fill_ordered(const DevAtoms &in, const Workspace &ws, arp_pair *out,
                        (const DevParams *)ws.params, (const uint32_t *)ws.cell_start, ws.sorted, ws.task_count,
                        (const unsigned long long *)ws.task_base, tg, ws.hole_list, ws.task_ctr, ws.result);
     if (prof) { prof->end(st); prof->begin("pairs_patch", st); }
-    hipLaunchKernelGGL(k_patch_deferred, dim3(kDeferBlocks), dim3(kWavesPerBlock * 64), 0, st, in, (const DevParams *)ws.params, ws.sorted, tg, ws.result);
+    hipLaunchKernelGGL(k_patch_deferred, dim3(kDeferBlocks), dim3(kWavesPerBlock * 64), 0, st, in, (const DevParams *)ws.params, ws.sorted, tg, ws.result, 0u);
     if (prof) prof->end(st);
 }
 
@@ -751,14 +771,14 @@ void launch_fill_ordered(const DevAtoms &in, const Workspace &ws, arp_pair *out,
 // result[2] counts them, the probes ran inline -- nothing follows the emit kernel, and the host derives the count and the status flags
 // k_fixup would have published (engine.cpp finish_result).
 static void launch_emit_tail(const DevAtoms &in, const Workspace &ws, const EmitTarget &tg, uint32_t nb, hipStream_t st, Profiler *prof, bool skip_deferred, bool patch,
-                             uint32_t chunk_records) {
+                             uint32_t chunk_records, uint32_t narrow_ib = 0u) {
     const uint32_t chunk_shift = chunk_shift_of(chunk_records);
     if (prof) prof->end(st);
     if (chunk_records == 1u) return;
     if (!skip_deferred) {
         if (prof) prof->begin("pairs_deferred", st);
-        if (patch) hipLaunchKernelGGL(k_patch_deferred, dim3(kDeferBlocks), dim3(kWavesPerBlock * 64), 0, st, in, (const DevParams *)ws.params, ws.sorted, tg, ws.result);
-        else hipLaunchKernelGGL(k_pairs_deferred, dim3(kDeferBlocks), dim3(kWavesPerBlock * 64), 0, st, in, (const DevParams *)ws.params, ws.sorted, tg, ws.hole_list + nb, ws.result, chunk_shift);
+        if (patch) hipLaunchKernelGGL(k_patch_deferred, dim3(kDeferBlocks), dim3(kWavesPerBlock * 64), 0, st, in, (const DevParams *)ws.params, ws.sorted, tg, ws.result, narrow_ib);
+        else hipLaunchKernelGGL(k_pairs_deferred, dim3(kDeferBlocks), dim3(kWavesPerBlock * 64), 0, st, in, (const DevParams *)ws.params, ws.sorted, tg, ws.hole_list + nb, ws.result, chunk_shift, narrow_ib);
         if (prof) prof->end(st);
     }
     if (prof) prof->begin("pairs_fixup", st);
@@ -767,7 +787,7 @@ static void launch_emit_tail(const DevAtoms &in, const Workspace &ws, const Emit
     if (prof) prof->end(st);
 }
 bool launch_emit_e(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsigned long long capacity, hipStream_t st, Profiler *prof, bool contacts_only,
-                   bool skip_deferred, bool res_filter);
+                   bool skip_deferred, bool res_filter, uint32_t narrow_ib);
 // the residue-rule kernels exist for the inputs launch_emit_e gives a 12-wave kernel: whoever builds the grid asks this before k_place runs
 bool emit_takes_res_filter(const DevAtoms &in) {
     const uint32_t tasks = (in.n + 63u) / 64u;
@@ -776,8 +796,24 @@ bool emit_takes_res_filter(const DevAtoms &in) {
 // single-pass emit + hole fix-up: leaves result[0] = number of pairs, out[0..P) contiguous
 // Returns true when the hole-free sequence of small inputs ran: result[0] and the flags k_fixup sets are then the host's to derive from
 // kResEmitHead (the records) and kResDeferred (the deferred list's chunks) -- engine.cpp finish_result.
+// The narrow exact record (arp_internal.h Xrec) is read by k_emit's chunked 12-wave kernels -- single inputs of 320 wave-tasks (20 417 atoms) or more.  The 4-wave kernels of
+// the smallest inputs keep the wide record: they have no residue-rule variant, so on a protein every batch would hold pairs of one residue, which
+// the tags cannot decide, and take the rare branch.  The scratch-staged hole-free kernels (k_emit<.., STAGE>: repeated calls on resident inputs of up to
+// 131 k atoms) keep it as well -- at 10^5 atoms the narrow record measured -1.1 us on S2 and +0.3 us on S1 per step (profiles/r20_narrow_record.md): not worth
+// four more kernels.  Packs keep it too: measured on 1250 five-thousand-atom members, k_place ran 40 us shorter
+// and k_emit 54 us longer, the step 7 us longer (profiles/r20_narrow_record.md).  Index bits: as few as hold the largest index, so the tag gets the rest -- 20 + 12 at 10^6
+// atoms, 17 + 15 at 10^5; inputs beyond 2^20 atoms (kNarrowMaxBits: fewer than 12 tag bits) keep the wide record.  arp_debug_set("index_bits", v): v in
+// 1 .. 20 fixes the width (an input whose last index does not fit it keeps the wide record), v < 0 keeps the wide record always.
+bool emit_takes_stage(const DevAtoms &in, const Workspace &ws, bool skip_deferred);  // (pairs_emit.inl) launch_emit_e would run the scratch-staged hole-free sequence
+uint32_t emit_narrow_bits(const DevAtoms &in, const Workspace &ws, bool skip_deferred) {
+    if (g_debug.index_bits < 0 || g_debug.emit_kernel == 1 || in.n == 0u || in.per_model || !emit_takes_res_filter(in) || emit_takes_stage(in, ws, skip_deferred)) return 0u;
+    uint32_t need = 1u;
+    while (need < 32u && ((in.n - 1u) >> need) != 0u) need++;
+    const uint32_t ib = g_debug.index_bits > 0 ? (uint32_t)g_debug.index_bits : need;
+    return (ib >= need && ib <= kNarrowMaxBits) ? ib : 0u;
+}
 bool launch_emit(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsigned long long capacity, hipStream_t st, Profiler *prof, bool contacts_only,
-                 bool skip_deferred, bool res_filter) {
+                 bool skip_deferred, bool res_filter, uint32_t narrow_ib) {
     if (in.n >= kBigSlots) {  // beyond the 32-bit record offsets of the single-pass kernels: count + ordered fill with inline probes
         launch_count(in, ws, st, prof, capacity, true, contacts_only);
         launch_fill_ordered(in, ws, out, capacity, st, prof, contacts_only);
@@ -786,7 +822,7 @@ bool launch_emit(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsigne
     // The default is k_emit (pairs_emit.inl).  This file's k_pairs<kEmit> -- both exact operands gathered, 8-byte queue entries -- is the
     // one alternative kept: it takes the inputs beyond k_emit's 2^24 slots, and arp_debug_set("emit_kernel", 1) selects it for the parity suite.
     const bool gather = g_debug.emit_kernel == 1;  // (arp_debug_set("emit_kernel", 1): the parity suite's run of the alternative kernel)
-    if (!gather && in.n < (1u << kESlotBits) - 64u) return launch_emit_e(in, ws, out, capacity, st, prof, contacts_only, skip_deferred, res_filter && emit_takes_res_filter(in));
+    if (!gather && in.n < (1u << kESlotBits) - 64u) return launch_emit_e(in, ws, out, capacity, st, prof, contacts_only, skip_deferred, res_filter && emit_takes_res_filter(in), narrow_ib);
     EmitTarget tg{out, capacity, ws.scratch, ws.scratch_cap, ws.defer_list, ws.defer_cap};
     const uint32_t nb = blocks_for(in.n, kEmitBlocks);
     if (prof) prof->begin("pairs_emit", st);

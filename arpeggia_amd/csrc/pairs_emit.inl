@@ -38,14 +38,17 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
+// NARROW (the 32-byte exact record, arp_internal.h Xrec): the home side is the record's two parts as they are -- hzp.w = index | tag -- and there
+// is no chain key; its 512 B per wave stay unused (the block's LDS is not what bounds the kernel's occupancy: DESIGN.md section 3.1)
+template <bool NARROW>
 struct WaveLdsE {
     float4 nrec[kEChunk + kEGroup];           // f32 prefilter records of the staged chunk (+ kEGroup: over-reads stay in bounds)
     u32x4 hxy[64]; u32x4 hzp[64];             // the task's home atoms: {x, y}, {z, pw, orig} as raw words ...
-    unsigned long long hkey[64];              // ... and the chain key crm << 32 | res_ord
+    unsigned long long hkey[NARROW ? 1 : 64]; // ... and the chain key crm << 32 | res_ord
     uint32_t queue[kEQueue];                  // phase-1 survivors: home lane << 26 | neighbour slot
 };
-struct WaveLdsR { WaveLdsE e; uint32_t nkey[kEChunk + kEGroup]; };  // RES: + the residue words of the staged chunk (Sorted::rkey)
-struct WaveLdsN { WaveLdsE e; };
+template <bool NARROW> struct WaveLdsR { WaveLdsE<NARROW> e; uint32_t nkey[kEChunk + kEGroup]; };  // RES: + the residue words of the staged chunk (Sorted::rkey)
+template <bool NARROW> struct WaveLdsN { WaveLdsE<NARROW> e; };
 struct alignas(16) TablesE {                  // block-shared decision tables (10 KB)
     double s_vdw[256];                        // van-der-Waals bound of the element pair (vdw.rs:41), index = class a << 4 | class b
     uint32_t lut[2048];                       // rows of a pair: index = W | Lg << 7 | Le << 9 (pair_lut2_entry)
@@ -326,20 +329,23 @@ DEVFN void stage_flush_e(StageRef &sg, const EmitTarget &tg, unsigned long long 
 // allocator's common case in ~10 scalar instructions (the asm block at the end of exact_finish_e), masks straight out of the compares.
 // The batch in two halves: exact_issue_e reads the batch's queue entries and sends the neighbour gathers on their way, exact_finish_e does
 // the rest (counters after the scalar diet: 54 % of wave-cycles at s_waitcnt).
+// NARROW: two 16-byte gathers per survivor -- the whole 32-byte record -- and nothing else (kb stays unset).
 struct ExactRegs { uint32_t e; u32x4 bxy, bzp; unsigned long long kb; };
-template <bool FULL>
-DEVFN ExactRegs exact_issue_e(const WaveLdsE &w, const Sorted &so, uint32_t qoff, uint32_t count, uint32_t lane) {
+template <bool FULL, bool NARROW>
+DEVFN ExactRegs exact_issue_e(const WaveLdsE<NARROW> &w, const Sorted &so, uint32_t qoff, uint32_t count, uint32_t lane) {
     qoff = __builtin_amdgcn_readfirstlane(qoff); count = __builtin_amdgcn_readfirstlane(count);  // (wave-uniform by construction: say so)
     wave_lds_fence();  // lanes read entries other lanes wrote
     ExactRegs g;
     g.e = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(w.queue) + qoff + 4u * lane);
     if (!FULL) g.e = lane < count ? g.e : 0u;
     wave_lds_fence();
-    uint32_t goff;  // 48 * (the entry's low 24 bits = the neighbour slot) in one instruction: the 24-bit multiply ignores the home-lane byte
-    asm("v_mul_u32_u24 %0, %1, 48" : "=v"(goff) : "v"(g.e));
+    uint32_t goff;  // 48 (32) * (the entry's low 24 bits = the neighbour slot) in one instruction: the 24-bit multiply ignores the home-lane byte
+    if (NARROW) asm("v_mul_u32_u24 %0, %1, 32" : "=v"(goff) : "v"(g.e));
+    else asm("v_mul_u32_u24 %0, %1, 48" : "=v"(goff) : "v"(g.e));
     const char *gp = reinterpret_cast<const char *>(so.fat) + (size_t)goff;
     g.bxy = *reinterpret_cast<const u32x4 *>(gp); g.bzp = *reinterpret_cast<const u32x4 *>(gp + 16);
-    g.kb = *reinterpret_cast<const unsigned long long *>(gp + 32);
+    g.kb = 0ull;
+    if (!NARROW) g.kb = *reinterpret_cast<const unsigned long long *>(gp + 32);
     return g;
 }
 // CHUNK == 1: the hole-free sequence of small inputs -- no block allocator, the batch's records go to the wave's staging buffer (sg) on the
@@ -347,45 +353,83 @@ DEVFN ExactRegs exact_issue_e(const WaveLdsE &w, const Sorted &so, uint32_t qoff
 // list entry): these kernels run at two waves per SIMD anyway, the probes' registers cost them nothing, and a call without a probe pass is
 // one launch shorter.  pe: the bounds the probes read (DIRECT only) + the clash / covalent bounds of the full level count (global memory).
 struct ProbeParamsE { const double *s_clash, *s_cov, *s_vdw, *s_hacc; double s_ion, s_polar, s_hphob; };
-template <bool FULL, bool ONLY, uint32_t CHUNK>
-DEVFN void exact_finish_e(const ExactRegs &g, const ConstsE &K, const TablesE &tb, WaveLdsE &w, BlockLds &bl, uint32_t count, uint32_t slot0,
+// NARROW: the wave-uniform words of the narrow record's pair filter (all scalar).  ib: index bits; thr = 2 << ib, the tag test's threshold -- or
+// 0xFFFFFFFF, which no tag difference exceeds, when every batch has to decide on the real keys (chain groups other than "/", or keys that decrease
+// somewhere along the input order: GridParams::key_unsorted); n_rare: batches that did so far.
+struct NarrowE { uint32_t ib, thr, n_rare; };
+template <bool FULL, bool ONLY, uint32_t CHUNK, bool NARROW>
+DEVFN void exact_finish_e(const ExactRegs &g, const ConstsE &K, const TablesE &tb, WaveLdsE<NARROW> &w, BlockLds &bl, uint32_t count, uint32_t slot0,
                           const EmitTarget &tg, uint32_t cap_chunks, unsigned long long *result, uint32_t lane, uint32_t wflags, uint32_t probe_bits, StageRef &sg,
-                          const DevAtoms &in, const Sorted &so, const ProbeParamsE &pe) {
+                          const DevAtoms &in, const Sorted &so, const ProbeParamsE &pe, NarrowE &nw) {
     constexpr bool DIRECT = CHUNK == 1u, STAGE = CHUNK == 2u;  // (CHUNK 1 / 2: the hole-free sequences -- records staged per wave in LDS / in the wave's scratch region)
     count = __builtin_amdgcn_readfirstlane(count);
     const uint32_t e = g.e, hl = e >> kESlotBits, nb = e & kESlotMask;
     const u32x4 bxy = g.bxy, bzp = g.bzp;
-    const unsigned long long kb = g.kb;
+    unsigned long long kb = g.kb;
     // (two addresses, hl * 16 and hl * 8 from the wave's base, the arrays as immediate offsets)
     const char *wb = reinterpret_cast<const char *>(&w);
-    const u32x4 axy = *reinterpret_cast<const u32x4 *>(wb + offsetof(WaveLdsE, hxy) + 16u * hl), azp = *reinterpret_cast<const u32x4 *>(wb + offsetof(WaveLdsE, hzp) + 16u * hl);
-    const unsigned long long ka = *reinterpret_cast<const unsigned long long *>(wb + offsetof(WaveLdsE, hkey) + 8u * hl);
+    const u32x4 axy = *reinterpret_cast<const u32x4 *>(wb + offsetof(WaveLdsE<NARROW>, hxy) + 16u * hl), azp = *reinterpret_cast<const u32x4 *>(wb + offsetof(WaveLdsE<NARROW>, hzp) + 16u * hl);
+    unsigned long long ka = 0ull;
+    if (!NARROW) ka = *reinterpret_cast<const unsigned long long *>(wb + offsetof(WaveLdsE<NARROW>, hkey) + 8u * hl);
     // pdbtbx Atom::distance before the sqrt, f64, the reference's operation order, no contraction
     const double s = sq_dist(words_f64(axy.x, axy.y), words_f64(axy.z, axy.w), words_f64(azp.x, azp.y), words_f64(bxy.x, bxy.y), words_f64(bxy.z, bxy.w),
                              words_f64(bzp.x, bzp.y));
     const uint32_t pa = azp.z, pb = bzp.z;
     // should_compare_entities for both orientations (complex.rs:76-131); at most one can hold
-    lmask m_ok, m_swap;
-    if (wflags & kWaveAllBoth) {  // (wave-uniform: a scalar branch)  every atom in both chain sets: the ligand is the atom with the smaller key
-        const uint32_t d1 = (uint32_t)kb - (uint32_t)ka + 1u;                   // residue ordinals of one chain: |difference| >= 2 (:113)
-        m_ok = lm_lt_u32_sv(2u, d1) | lm_ne_u32((uint32_t)(ka >> 32), (uint32_t)(kb >> 32));  // another chain: always (:124-129); models never meet in the grid
-        m_swap = lm_lt_u64(kb, ka);
-    } else {  // chain groups: orient() of kernels.hip on lane masks (every comparison lands in a scalar register pair)
-        const uint32_t ca = (uint32_t)(ka >> 32), cb = (uint32_t)(kb >> 32);
-        const lmask same_model = ~0ull;  // :96-98 is the grid's: a slot window never holds an atom of another model (arp_internal.h Fat::crm)
-        const lmask same_chain = ~lm_ne_u32(ca, cb);
-        const lmask ab_chain = lm_lt_u32_vv((uint32_t)ka + 1u, (uint32_t)kb), ba_chain = lm_lt_u32_vv((uint32_t)kb + 1u, (uint32_t)ka);  // :108,:113
-        const uint32_t lr = pa & pb;                                                                            // bit 24: both ligand, bit 25: both receptor
-        const lmask both = lm_lt_u32_sv(0u, lr & (lr >> 1) & kPwLigand);                                        // :124-129
-        const lmask ab_cross = ~(both & lm_lt_u32_vv(cb, ca)), ba_cross = ~(both & lm_lt_u32_vv(ca, cb));
-        const lmask aL = lm_lt_u32_sv(0u, pa & kPwLigand), aR = lm_lt_u32_sv(0u, pa & kPwReceptor);
-        const lmask bL = lm_lt_u32_sv(0u, pb & kPwLigand), bR = lm_lt_u32_sv(0u, pb & kPwReceptor);
-        const lmask o1 = same_model & aL & bR & ((same_chain & ab_chain) | (~same_chain & ab_cross));
-        const lmask o2 = same_model & bL & aR & ((same_chain & ba_chain) | (~same_chain & ba_cross));
-        m_ok = o1 | o2; m_swap = o2 & ~o1;
+    lmask m_ok, m_swap, m_valid;
+    uint32_t oa = azp.w, ob = bzp.w;  // the two original indices (rec.x / rec.y below)
+    auto decide_on_keys = [&]() {
+        if (wflags & kWaveAllBoth) {  // (wave-uniform: a scalar branch)  every atom in both chain sets: the ligand is the atom with the smaller key
+            const uint32_t d1 = (uint32_t)kb - (uint32_t)ka + 1u;                   // residue ordinals of one chain: |difference| >= 2 (:113)
+            m_ok = lm_lt_u32_sv(2u, d1) | lm_ne_u32((uint32_t)(ka >> 32), (uint32_t)(kb >> 32));  // another chain: always (:124-129); models never meet in the grid
+            m_swap = lm_lt_u64(kb, ka);
+        } else {  // chain groups: orient() of kernels.hip on lane masks (every comparison lands in a scalar register pair)
+            const uint32_t ca = (uint32_t)(ka >> 32), cb = (uint32_t)(kb >> 32);
+            const lmask same_model = ~0ull;  // :96-98 is the grid's: a slot window never holds an atom of another model (arp_internal.h Fat::crm)
+            const lmask same_chain = ~lm_ne_u32(ca, cb);
+            const lmask ab_chain = lm_lt_u32_vv((uint32_t)ka + 1u, (uint32_t)kb), ba_chain = lm_lt_u32_vv((uint32_t)kb + 1u, (uint32_t)ka);  // :108,:113
+            const uint32_t lr = pa & pb;                                                                            // bit 24: both ligand, bit 25: both receptor
+            const lmask both = lm_lt_u32_sv(0u, lr & (lr >> 1) & kPwLigand);                                        // :124-129
+            const lmask ab_cross = ~(both & lm_lt_u32_vv(cb, ca)), ba_cross = ~(both & lm_lt_u32_vv(ca, cb));
+            const lmask aL = lm_lt_u32_sv(0u, pa & kPwLigand), aR = lm_lt_u32_sv(0u, pa & kPwReceptor);
+            const lmask bL = lm_lt_u32_sv(0u, pb & kPwLigand), bR = lm_lt_u32_sv(0u, pb & kPwReceptor);
+            const lmask o1 = same_model & aL & bR & ((same_chain & ab_chain) | (~same_chain & ab_cross));
+            const lmask o2 = same_model & bL & aR & ((same_chain & ba_chain) | (~same_chain & ba_cross));
+            m_ok = o1 | o2; m_swap = o2 & ~o1;
+        }
+    };
+    if constexpr (NARROW) {
+        // The pair filter on the records' tags.  The words wa, wb = index << T | (tag mod 2^T), T = 32 - ib, tag = (chain rank << kRkOrdBits) + ordinal
+        // (mod 2^32: grid.inl narrow_tag).  The reference rejects a pair of one model iff its atoms are of ONE chain and their ordinals differ by at
+        // most 1 (complex.rs:108-113; decide_on_keys above: d1 = ordinal b - ordinal a + 1 (mod 2^32) <= 2).  For such a pair
+        //     tag b - tag a = ordinal b - ordinal a  in {-1, 0, 1}  (mod 2^32), hence (mod 2^T) as well:  (tag b - tag a + 1) mod 2^T  in {0, 1, 2}.
+        // dt = (wb - wa + 1) << ib is that residue, shifted up by ib (the index bits of the difference, and their borrow, fall off the top).
+        // Contrapositive: dt > 2 << ib PROVES the pair is none of those, i.e. that it may pair -- whatever the chains and ordinals are, in range of
+        // the residue word or not.  When it does not hold for some candidate within the cutoff (ordinals 0 / +-1 apart, or aliases of that: another
+        // chain's ordinals when T <= kRkOrdBits, ordinals a multiple of 2^T apart), the batch takes the rare branch below and decides every lane on
+        // the real keys: the tags only ever SEND work there, they reject nothing.
+        // The ligand: the atom with the smaller key; with keys that never decrease along the input order that is the atom with the smaller index
+        // (k_place checks the order; otherwise nw.thr sends every batch to the real keys), and so it is for a pair of equal keys, which is never a
+        // candidate.  The index sits in the high bits and the two indices differ: the words compare like them.
+        const uint32_t dt = (bzp.w - azp.w + 1u) << nw.ib;
+        m_ok = lm_lt_u32_sv(nw.thr, dt);
+        m_swap = lm_lt_u32_vv(bzp.w, azp.w);
+        oa = azp.w >> (32u - nw.ib); ob = bzp.w >> (32u - nw.ib);
+        lmask m_geo = lm_ge_f64_sv(K.r2, s);  // rstar: inclusive
+        if (!FULL) m_geo &= (1ull << (count & 63u)) - 1ull;  // (!FULL: count < 64)
+        if (__builtin_expect((m_geo & ~m_ok) != 0ull, 0)) {  // (wave-uniform)
+            asm volatile("" ::: "memory");  // keep this a branch
+            ka = ((unsigned long long)in.chain_rank[oa] << 32) | in.res_ord[oa];
+            kb = ((unsigned long long)in.chain_rank[ob] << 32) | in.res_ord[ob];
+            nw.n_rare++;
+            decide_on_keys();
+        }
+        m_valid = m_geo & m_ok;
+    } else {
+        decide_on_keys();
+        m_valid = lm_ge_f64_sv(K.r2, s) & m_ok;  // rstar: inclusive
+        if (!FULL) m_valid &= (1ull << (count & 63u)) - 1ull;  // (!FULL: count < 64)
     }
-    lmask m_valid = lm_ge_f64_sv(K.r2, s) & m_ok;  // rstar: inclusive
-    if (!FULL) m_valid &= (1ull << (count & 63u)) - 1ull;  // (!FULL: count < 64)
     uint32_t n_rec = ONLY ? 0u : lm_count(m_valid);
     u32x2 a_old = {0u, 0u};
     if (!ONLY) {
@@ -464,7 +508,7 @@ DEVFN void exact_finish_e(const ExactRegs &g, const ConstsE &K, const TablesE &t
         if (n_rec && !DIRECT && !STAGE) a_old = alloc_issue_e(bl.alloc_state, n_rec);
     }
     u32x4 rec;
-    rec.x = lm_select(m_swap, bzp.w, azp.w); rec.y = lm_select(m_swap, azp.w, bzp.w);
+    rec.x = lm_select(m_swap, ob, oa); rec.y = lm_select(m_swap, oa, ob);
     uint32_t general;  // (wave-uniform, and opaque to the optimiser in both arms: as a bool it comes back as a lane mask + three scalar instructions per use)
     if (!DIRECT && __builtin_expect((m_exact | m_defer | m_close) == 0ull, 1)) {
         rec.z = __float_as_uint((float)y);
@@ -587,9 +631,11 @@ struct ScratchStageLdsE { uint4 rec[1][1]; uint32_t wave_n[kEWaves]; unsigned lo
 // residues are runs of atoms; the result is the same list either way
 // STAGE: the hole-free sequence of the 12-wave kernels with the four-way task split (stage_copy_g above): launched only when the engine's memo says the input
 // defers nothing to the probe pass
-template <int WAVES, int SPLIT, bool ONLY, bool DIRECT = false, bool RES = false, bool STAGE = false>
+// NARROW: the slots hold the 32-byte exact record (arp_internal.h Xrec, written by k_place<.., true>; ib: its index bits) -- two gathers per survivor,
+// the pair filter on the records' tags with a rare branch to the real keys (exact_finish_e), the home cells recomputed from the coordinates
+template <int WAVES, int SPLIT, bool ONLY, bool DIRECT = false, bool RES = false, bool STAGE = false, bool NARROW = false>
 __global__ __launch_bounds__(WAVES * 64, WAVES == kEWaves ? kEWavesPerSimd : 2) void k_emit(DevAtoms in, const GridParams *gp, const DevParams *dprm, const uint32_t *cell_start, Sorted so,
-                                                                                           EmitTarget tg, ulonglong2 *hole_list, uint32_t *task_ctr, unsigned long long *result) {
+                                                                                           EmitTarget tg, ulonglong2 *hole_list, uint32_t *task_ctr, unsigned long long *result, uint32_t ib) {
     // Inputs that do not fill the chip emit a few thousand records per block, or a few hundred: a 4096-record chunk per block would leave
     // holes as large as the list itself for the fix-up to close.  (Not smaller than this: every chunk costs a returning atomic on the one
     // global counter, ~11 ns each when they queue up -- 256-record chunks made the kernel 2.4x slower on 10^5 atoms and 30 % slower on 2x10^4.)
@@ -600,14 +646,19 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == kEWaves ? kEWavesPerSimd : 2) 
     constexpr uint32_t kChunkE = DIRECT ? 1u : (STAGE ? 2u : (SPLIT == 4 ? kSmallChunkRecords : kChunkRecords));
     static_assert(DIRECT || WAVES == kEWaves, "the 4-wave kernels are DIRECT");
     static_assert(!(RES && DIRECT), "the residue-rule rounds are the 12-wave kernels'");
+    static_assert(!(NARROW && DIRECT), "the 4-wave kernels read the wide record");
     __shared__ TablesE tb;
-    __shared__ typename std::conditional<RES, WaveLdsR, WaveLdsN>::type wl[WAVES];
+    __shared__ typename std::conditional<RES, WaveLdsR<NARROW>, WaveLdsN<NARROW>>::type wl[WAVES];
+    __shared__ uint32_t rare_total;  // NARROW: the block's batches that fetched the real keys (one atomic per block at the end)
     __shared__ BlockLds bl;
     __shared__ typename std::conditional<DIRECT, StageLdsE, typename std::conditional<STAGE, ScratchStageLdsE, NoStageLdsE>::type>::type stg;
     // (the grid and parameter words first: their loads travel together with the table's instead of behind the barrier)
     const uint32_t nx = gp->nx, ny = gp->ny, nzt = gp->nzt, kx = gp->kx, n_heavy = gp->n_heavy, n_tasks = gp->n_tasks * (uint32_t)SPLIT;  // (wave-tasks)
     const uint32_t sy = gp->sy_shift;  // (wave-uniform) the cell rows' order: arp_internal.h grid_row
     const uint32_t wflags = gp->all_both ? kWaveAllBoth : 0u;
+    // NARROW: every batch on the real keys unless all atoms are in both chain sets and the keys never decrease along the input order (exact_finish_e)
+    NarrowE nw{ib, (NARROW && gp->all_both != 0u && gp->key_unsorted == 0u) ? 2u << (ib & 31u) : 0xFFFFFFFFu, 0u};
+    const bool multi_model = NARROW && gp->nzt != gp->nz + 1u;  // (wave-uniform) more than one z slab: a home atom's cell needs its model
     const uint32_t rk_off = RES ? gp->rk_bad : 0u;  // (wave-uniform) an ordinal or a chain rank did not fit the residue words: no early rejection
     const ConstsE K{dprm->r2, dprm->s_hphob, dprm->s_ion, dprm->s_polar, dprm->s_cov_max};
     const double r2m = gp->r2m;
@@ -628,13 +679,14 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == kEWaves ? kEWavesPerSimd : 2) 
         bl.alloc_state = kAllocEmpty | kChunkE;  // "exhausted": the first allocation fetches a chunk
         bl.defer_state = kAllocEmpty | kDeferChunk;
         bl.chunk_shift = chunk_shift_of(kChunkE);
+        if (NARROW) rare_total = 0u;
     }
     __syncthreads();
     const uint32_t probe_bits = in.n_res != 0u ? (1u << 29) : 0u;  // residue tables present: CYS SG pairs in the covalent band get their dihedral probe
     // chunks that lie wholly inside the caller's buffer: a batch placed in one of them needs no further capacity test (exact_finish_e's fast tail)
     // (and inside its first 2^32 bytes: the fast path addresses with a 32-bit byte offset; what lies beyond takes the general path)
     const uint32_t cap_chunks = (uint32_t)min(tg.capacity >> chunk_shift_of(kChunkE), (unsigned long long)((1u << 28) / kChunkE));
-    WaveLdsE &w = wl[wave].e;
+    WaveLdsE<NARROW> &w = wl[wave].e;
     uint32_t nkey_lds = 0;  // RES: LDS byte address of the staged chunk's residue words
     if constexpr (RES) nkey_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)wl[wave].nkey);
     // STAGE: the wave's region, made scalar here once (the record stores take it as their base: lm_store_records); the readfirstlane is of the wave's
@@ -664,7 +716,18 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == kEWaves ? kEWavesPerSimd : 2) 
         {
             u32x4 hxy = {0u, 0u, 0u, 0u}, hzp = {0u, 0u, 0u, 0u};
             unsigned long long hkey = 0ull;
-            if (have) {
+            if (have && NARROW) {
+                // the record's two parts as they are; the cell from the coordinates, as k_cellid computed it (cell_coords: the same function of the
+                // same f64 words and the same GridParams, so the same cell); the residue word from the slot's own (RES: k_place wrote it)
+                home = so.rec[a];
+                const char *hp = reinterpret_cast<const char *>(so.fat) + ((size_t)a << 5);
+                hxy = *reinterpret_cast<const u32x4 *>(hp); hzp = *reinterpret_cast<const u32x4 *>(hp + 16);
+                if (RES && !rk_off) kh1 = so.rkey[a] - 1u;
+                const uint32_t model = multi_model ? in.model[hzp.w >> (32u - ib)] : 0u;
+                const GridParams *gpt = gp;  // (opaque: the grid words are read here, once per task, not held in scalar registers across the batches)
+                asm volatile("" : "+s"(gpt));
+                cell_coords(*gpt, words_f64(hxy.x, hxy.y), words_f64(hxy.z, hxy.w), words_f64(hzp.x, hzp.y), model, cx, cy, cz);
+            } else if (have) {
                 home = DIRECT ? home_pre : so.rec[a];
                 const Fat &f = *(DIRECT ? &fat_pre : &fat_at<false>(so.fat, a));
                 const double fx = f.x, fy = f.y, fz = f.z;
@@ -676,7 +739,8 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == kEWaves ? kEWavesPerSimd : 2) 
                 const uint32_t row = c / nx;
                 cx = c - row * nx; grid_row_decode(row, ny, nzt, sy, cy, cz);
             }
-            w.hxy[lane] = hxy; w.hzp[lane] = hzp; w.hkey[lane] = hkey;
+            w.hxy[lane] = hxy; w.hzp[lane] = hzp;
+            if (!NARROW) w.hkey[lane] = hkey;
         }
         const uint32_t xlo = cx > kx ? cx - kx : 0u, xhi = min(cx + kx, nx - 1);
         // all five slot windows of this lane up front: ten independent loads in flight instead of five round trips
@@ -792,8 +856,8 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == kEWaves ? kEWavesPerSimd : 2) 
                             qb -= 256u;
                             // (Finishing the batch only after the next compaction rounds -- the gathers in flight meanwhile -- was measured: no
                             // gain, 162 us either way; the compiler then parks the next prefilter run on vmcnt(0) for a register it sees reused.)
-                            const ExactRegs g = exact_issue_e<true>(w, so, qb - queue_lds, 64u, lane);
-                            exact_finish_e<true, ONLY, kChunkE>(g, K, tb, w, bl, 64u, slot0, tg, cap_chunks, result, lane, wflags, probe_bits, sg, in, so, pe);
+                            const ExactRegs g = exact_issue_e<true, NARROW>(w, so, qb - queue_lds, 64u, lane);
+                            exact_finish_e<true, ONLY, kChunkE, NARROW>(g, K, tb, w, bl, 64u, slot0, tg, cap_chunks, result, lane, wflags, probe_bits, sg, in, so, pe, nw);
                             compact(qb);
                         }
                         qbyte = qb;
@@ -804,15 +868,17 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == kEWaves ? kEWavesPerSimd : 2) 
         }
         if (qbyte != queue_lds) {  // the home records go with the task: drain
             const uint32_t left = (qbyte - queue_lds) >> 2;
-            const ExactRegs g = exact_issue_e<false>(w, so, 0u, left, lane);
-            exact_finish_e<false, ONLY, kChunkE>(g, K, tb, w, bl, left, slot0, tg, cap_chunks, result, lane, wflags, probe_bits, sg, in, so, pe);
+            const ExactRegs g = exact_issue_e<false, NARROW>(w, so, 0u, left, lane);
+            exact_finish_e<false, ONLY, kChunkE, NARROW>(g, K, tb, w, bl, left, slot0, tg, cap_chunks, result, lane, wflags, probe_bits, sg, in, so, pe, nw);
         }
         if (DIRECT || g_lo + group_waves >= g_hi) break;  // every task was some wave's static first one (small inputs): no round trip to the counter for nothing
         uint32_t nxt_task = 0;
         if (lane == 0) nxt_task = atomicAdd(ctr, 1u);  // (drawn only now: a wave that reserved its next task early would hold it hostage at the end of the launch)
         t = g_lo + group_waves + __builtin_amdgcn_readfirstlane(nxt_task);
     }
-    emit_epilogue(bl, hole_list + blockIdx.x, tg);
+    if (NARROW && nw.n_rare != 0u && lane == 0u) atomicAdd(&rare_total, nw.n_rare);
+    emit_epilogue(bl, hole_list + blockIdx.x, tg);  // (starts with a barrier)
+    if (NARROW && threadIdx.x == 0u && rare_total != 0u) atomicAdd(&result[kResRare], (unsigned long long)rare_total);
     if (DIRECT || STAGE) {  // what the waves still hold goes out together: one returning atomic per block
         const uint32_t mine = __builtin_amdgcn_readfirstlane(sg.n);
         if (lane == 0u) stg.wave_n[wave] = mine;
@@ -830,9 +896,15 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == kEWaves ? kEWavesPerSimd : 2) 
     }
 }
 
+// whether launch_emit_e runs the scratch-staged hole-free sequence (its comment there); asked by emit_narrow_bits too, before the grid is built
+bool emit_takes_stage(const DevAtoms &in, const Workspace &ws, bool skip_deferred) {
+    constexpr uint32_t kStageTasks = 2048;
+    const uint32_t tasks = (in.n + 63u) / 64u, want = (4u * tasks + (uint32_t)kEWaves - 1u) / (uint32_t)kEWaves, nb = want > kEBlocks ? kEBlocks : want;
+    return tasks >= 320u && tasks <= kStageTasks && !in.per_model && skip_deferred && (unsigned long long)nb * kEWaves * kWaveStageRecords <= ws.scratch_cap;
+}
 // single-pass emit + hole fix-up: leaves result[0] = number of pairs, out[0..P) contiguous
 bool launch_emit_e(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsigned long long capacity, hipStream_t st, Profiler *prof, bool contacts_only,
-                   bool skip_deferred, bool res_filter) {
+                   bool skip_deferred, bool res_filter, uint32_t narrow_ib) {
     EmitTarget tg{out, capacity, ws.scratch, ws.scratch_cap, ws.defer_list, ws.defer_cap};
     const uint32_t tasks = (in.n + 63u) / 64u;
     // Fewer tasks than the chip has wave slots: every task is shared out over four waves by window kind (eight for the smallest inputs, two
@@ -841,14 +913,16 @@ bool launch_emit_e(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsig
     // and an input that does not fill the chip has nothing else to hide it behind.
     // The 4-wave kernels are the hole-free ones (DIRECT); a pack that small keeps the 12-wave sequence with its fix-up, which is what publishes
     // the count its members' lists are split by on the device.
-    const bool shared = tasks < 4608u, narrow = tasks < 320u && !in.per_model, eight = narrow && tasks < 160u;  // (eight: 6bft's 128 tasks run 3 us faster that way, an S2 cloud of the same size 1.3 us slower)
-    const bool direct = narrow;
+    const bool shared = tasks < 4608u, small = tasks < 320u && !in.per_model, eight = small && tasks < 160u;  // (eight: 6bft's 128 tasks run 3 us faster that way, an S2 cloud of the same size 1.3 us slower)
+    const bool direct = small;
     const uint32_t split = eight ? 8u : (shared ? 4u : 1u);
-    const uint32_t per = narrow ? 4u : (uint32_t)kEWaves, cap = narrow ? 1536u : kEBlocks, want = (split * tasks + per - 1u) / per;
+    const uint32_t per = small ? 4u : (uint32_t)kEWaves, cap = small ? 1536u : kEBlocks, want = (split * tasks + per - 1u) / per;
     const uint32_t nb = want < 1 ? 1 : (want > cap ? cap : want);
     if (prof) prof->begin("pairs_emit", st);
-#define ARP_LAUNCH_E(W, S, O, ...) hipLaunchKernelGGL((k_emit<W, S, O, ##__VA_ARGS__>), dim3(nb), dim3(W * 64), 0, st, in, (const GridParams *)ws.grid, (const DevParams *)ws.params, \
-                                                 (const uint32_t *)ws.cell_start, ws.sorted, tg, ws.hole_list, ws.task_ctr, ws.result)
+#define ARP_LAUNCH_E1(...) hipLaunchKernelGGL((k_emit<__VA_ARGS__>), dim3(nb), dim3(per * 64u), 0, st, in, (const GridParams *)ws.grid, (const DevParams *)ws.params, \
+                                              (const uint32_t *)ws.cell_start, ws.sorted, tg, ws.hole_list, ws.task_ctr, ws.result, narrow_ib)
+    // (W, S, O, DIRECT, RES, STAGE; the chunked 12-wave kernels in two forms: the grid build wrote the narrow exact record for this call, narrow_ib != 0, or the wide one)
+#define ARP_LAUNCH_E(W, S, O, D, R, G) do { if (narrow_ib && !(D) && !(G)) ARP_LAUNCH_E1(W, S, O, D, R, G, !(D) && !(G)); else ARP_LAUNCH_E1(W, S, O, D, R, G, false); } while (0)
     // res_filter: the residue-rule kernels (the engine asks for them when the input's residues are runs of atoms, and had k_place write the residue
     // words); the 4-wave kernels of the smallest inputs have no such variant (a call of that size is launches and round trips, not batches)
     // stage: the hole-free sequence of the task-split 12-wave kernels (k_emit<.., STAGE>: records staged per wave in the scratch block, no fix-up launch) -- for
@@ -856,24 +930,24 @@ bool launch_emit_e(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsig
     // chunked sequence), whose waves' regions fit the scratch block
     // (up to kStageTasks tasks = 131 k atoms: every record crosses the L2 twice more on this route, which costs the kernel ~1 us per 3 x 10^5 records -- S2 per step,
     // staged against chunks + fix-up: 3 x 10^4 atoms 53 against 64 us, 6 x 10^4 64 / 71, 10^5 76 / 82 (S1 65 / 80), 1.9 x 10^5 106 / 102, 2.9 x 10^5 146 / 129)
-    constexpr uint32_t kStageTasks = 2048;
-    const bool stage = shared && !narrow && tasks <= kStageTasks && !in.per_model && skip_deferred && (unsigned long long)nb * kEWaves * kWaveStageRecords <= ws.scratch_cap;
+    const bool stage = emit_takes_stage(in, ws, skip_deferred);
     if (stage) {
         if (contacts_only) { if (res_filter) ARP_LAUNCH_E(kEWaves, 4, true, false, true, true); else ARP_LAUNCH_E(kEWaves, 4, true, false, false, true); }
         else { if (res_filter) ARP_LAUNCH_E(kEWaves, 4, false, false, true, true); else ARP_LAUNCH_E(kEWaves, 4, false, false, false, true); }
     } else if (contacts_only) {
-        if (eight) ARP_LAUNCH_E(4, 8, true, true);
-        else if (narrow) ARP_LAUNCH_E(4, 4, true, true);
-        else if (shared) { if (res_filter) ARP_LAUNCH_E(kEWaves, 4, true, false, true); else ARP_LAUNCH_E(kEWaves, 4, true); }
-        else { if (res_filter) ARP_LAUNCH_E(kEWaves, 1, true, false, true); else ARP_LAUNCH_E(kEWaves, 1, true); }
+        if (eight) ARP_LAUNCH_E(4, 8, true, true, false, false);
+        else if (small) ARP_LAUNCH_E(4, 4, true, true, false, false);
+        else if (shared) { if (res_filter) ARP_LAUNCH_E(kEWaves, 4, true, false, true, false); else ARP_LAUNCH_E(kEWaves, 4, true, false, false, false); }
+        else { if (res_filter) ARP_LAUNCH_E(kEWaves, 1, true, false, true, false); else ARP_LAUNCH_E(kEWaves, 1, true, false, false, false); }
     } else {
-        if (eight) ARP_LAUNCH_E(4, 8, false, true);
-        else if (narrow) ARP_LAUNCH_E(4, 4, false, true);
-        else if (shared) { if (res_filter) ARP_LAUNCH_E(kEWaves, 4, false, false, true); else ARP_LAUNCH_E(kEWaves, 4, false); }
-        else { if (res_filter) ARP_LAUNCH_E(kEWaves, 1, false, false, true); else ARP_LAUNCH_E(kEWaves, 1, false); }
+        if (eight) ARP_LAUNCH_E(4, 8, false, true, false, false);
+        else if (small) ARP_LAUNCH_E(4, 4, false, true, false, false);
+        else if (shared) { if (res_filter) ARP_LAUNCH_E(kEWaves, 4, false, false, true, false); else ARP_LAUNCH_E(kEWaves, 4, false, false, false, false); }
+        else { if (res_filter) ARP_LAUNCH_E(kEWaves, 1, false, false, true, false); else ARP_LAUNCH_E(kEWaves, 1, false, false, false, false); }
     }
 #undef ARP_LAUNCH_E
-    launch_emit_tail(in, ws, tg, nb, st, prof, skip_deferred, !contacts_only, (direct || stage) ? 1u : (shared ? kSmallChunkRecords : kChunkRecords));
+#undef ARP_LAUNCH_E1
+    launch_emit_tail(in, ws, tg, nb, st, prof, skip_deferred, !contacts_only, (direct || stage) ? 1u : (shared ? kSmallChunkRecords : kChunkRecords), narrow_ib);
     return direct || stage;  // (the host derives the count and the capacity flag from kResEmitHead: engine.cpp finish_result)
 }
 static_assert(kEBlocks + 384u <= kMaxHoles && 1536u + 384u <= kMaxHoles, "hole list: one entry per block of either kernel");

@@ -150,6 +150,9 @@ typedef struct arp_table arp_table;         /* the 20-column contact table (mod.
  *   "defer_entries" N > 0: entries of the deferred-probe list of workspaces allocated from now on (a tiny list makes the grow-and-repeat path run)
  *   "strip_rows"    N = a power of two: the cell rows of single-model inputs are ordered in y strips of N rows (chosen by input size when 0, the default:
  *                      strips only from ~2.5 x 10^6 atoms of a compact structure on), for parameter blocks built from now on -- lets the parity suite run the strip order on small inputs
+ *   "index_bits"    the narrow (32-byte) exact record of the single-pass emitter: 0 (default): its index width follows the input size; N = 1 .. 20: N index bits
+ *                      (an input whose last index does not fit them keeps the wide record); N < 0: the wide record always.  Same list either way -- lets the
+ *                      suite run the wide-index fallback on small inputs
  *   "table_host"    1: only in the test library built with -DARP_WITH_HOST_TABLE (tests/hosttable): arp_get_contacts assembles the table on the host
  *   "freq_chunk_atoms" N > 0: arp_contact_frequencies runs its frames in passes of N atoms (whole frames, at least one per pass), so that tests can
  *                      force several passes; 0 (default): about 2 x 10^6 atoms per pass
@@ -241,6 +244,10 @@ arp_status arp_atom_sasa(arp_context *ctx, uint64_t n, const double *x, const do
                          const uint8_t *include, float probe, int32_t n_points, float *out_sasa, int32_t *out_count);
 /* Diagnostics: f32 distance tests (point x list entry) the kernel of the most recent SASA call on ctx made. */
 uint64_t arp_sasa_tests(const arp_context *ctx);
+/* Diagnostics: how many 64-pair batches of the most recent collected pair pass on ctx decided their pair filter on the residue ordinals and chain
+ * ranks read from the input arrays instead of on the tags of the narrow exact record (0 when the pass ran on the wide record).
+ * (A diagnostics entry point like arp_sasa_tests: ARP_API_VERSION names the layout of arp_atoms / arp_params / arp_pair and does not move.) */
+uint64_t arp_pair_rare_batches(const arp_context *ctx);
 
 /* Structure level.  The atom selection is the reference's prepare_pdb_for_sasa + filter_pdb_by_model (sasa.rs:27-135, 183-195), in order:
  *   1. chains: a comma-separated list, entries trimmed, empty entries dropped; empty = all chains;
