@@ -6,6 +6,7 @@
 
 #include "../../include/arpeggia_amd.h"
 #include "debug_knobs.h"
+#include "emit_plan.h"
 
 namespace arp {
 
@@ -107,7 +108,7 @@ struct __attribute__((aligned(16))) Fat {
                              separator layer, so the windows of an atom only ever hold atoms of its own model, complex.rs:96-98) */, cell /* cell id of the slot */, attr;
 };
 // The narrow exact record, 32 B = two 16-byte parts: what k_emit's 12-wave kernels gather per survivor and k_place<.., NARROW> scatters per atom
-// when the launcher chose it (emit_narrow_bits, pairs.inl); it lives in the memory of Sorted::fat.  `ot` = original index in the HIGH `ib` bits
+// when the emit plan chose it (emit_plan.h plan_emit); it lives in the memory of Sorted::fat.  `ot` = original index in the HIGH `ib` bits
 // (the call's index width, a kernel argument: two records compare like their indices) and below them the low T = 32 - ib bits of the atom's TAG
 // (chain rank << kRkOrdBits) + residue ordinal, computed modulo 2^32.  The cell, the attribute word and the chain key of the wide record are not here: a task recomputes its home
 // cells from the coordinates (cell_coords, grid.inl), and whoever needs the real chain rank / ordinal / attribute word reads the caller's
@@ -116,8 +117,6 @@ struct __attribute__((aligned(16))) Xrec {
     double x, y;
     double z; uint32_t pw, ot;
 };
-constexpr uint32_t kNarrowMaxBits = 20;  // index bits of Xrec::ot at most (2^20 atoms): the tag keeps 12 bits or more.  Fewer tag bits alias too often: a resident input of
-                                         // 1250 five-thousand-atom models (6.25 x 10^6 atoms, 23 + 9 bits) ran k_emit 48 us longer than on the wide record, k_place 35 us shorter
 constexpr uint32_t kPwLigand = 1u << 24, kPwReceptor = 1u << 25, kPwResHasH = 1u << 30;  // (bits 26-29 and 31 stay clear: the emit kernel ANDs the word with a table entry's probe bits)
 
 // Cell-sorted copy of the heavy atoms (slot order: x-major cells, atoms of a cell in ascending input index).
@@ -205,17 +204,14 @@ struct Profiler {
 };
 
 // Launch wrappers (kernels.hip / pairs.inl).  All asynchronous on `st`.
-// narrow_ib != 0: k_place writes the narrow exact record (Xrec) with that many index bits instead of the wide one (Fat) -- only for a grid whose
-// one reader is launch_emit with the same narrow_ib (emit_narrow_bits says whether there are kernels for it)
+// want_rkey, narrow_ib: EmitPlan::res and EmitPlan::narrow_ib of the pass the cell list is built for (k_place writes the residue words / the narrow exact
+// record, Xrec, with that many index bits instead of the wide one, Fat)
 void launch_grid(const DevAtoms &in, const Workspace &ws, hipStream_t st, Profiler *prof, double cutoff, bool ordered, bool want_rkey = false, uint32_t narrow_ib = 0);
 void launch_count(const DevAtoms &in, const Workspace &ws, hipStream_t st, Profiler *prof, unsigned long long capacity, bool have_out, bool contacts_only);
 void launch_fill_ordered(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsigned long long capacity, hipStream_t st, Profiler *prof,
                          bool contacts_only);
-bool launch_emit(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsigned long long capacity, hipStream_t st, Profiler *prof, bool contacts_only,
-                 bool skip_deferred, bool res_filter = false, uint32_t narrow_ib = 0);  // true: the hole-free sequence of small inputs ran (the host derives kResPairs and the flags: engine.cpp finish_result)
-bool emit_takes_res_filter(const DevAtoms &in);  // the single-pass emitter has residue-rule kernels for an input of this size (the grid build then writes Sorted::rkey)
-// index bits of the narrow exact record the single-pass emitter would read for this input (skip_deferred: as launch_emit will be called); 0: it reads the wide record
-uint32_t emit_narrow_bits(const DevAtoms &in, const Workspace &ws, bool skip_deferred);
+// the launch sequence of the plan, on a cell list built for it; ARP_ERR_HIP: the plan names a k_emit variant there is none of (an internal error)
+arp_status launch_emit(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsigned long long capacity, hipStream_t st, Profiler *prof, const EmitPlan &plan);
 unsigned long long emit_scratch_records();
 void launch_neighbor_sum(const DevAtoms &in, const Workspace &ws, double radius, double r2, const float *weight, float *out, hipStream_t st, Profiler *prof);
 // Atom SASA (sasa.inl): the grid over the atoms without ARP_ATTR_H, then one wave per grid atom.  buried == nullptr: k_sasa; sasa / count hold

@@ -187,7 +187,7 @@ arp_status ensure_pack_buffers(arp_context *ctx, uint64_t in_bytes, uint64_t out
 // between the pack's pair kernels and the copy of their result words: the split of the list by member
 arp_status pack_split_step(arp_context *ctx, const PairPass &p, void *slot) {
     const BatchSlot &sl = *static_cast<const BatchSlot *>(slot);
-    // (a pack never takes the hole-free sequence of small inputs -- DevAtoms::per_model rules it out in launch_emit_e --: that sequence leaves
+    // (a pack never takes the hole-free sequence of small inputs -- DevAtoms::per_model rules it out in the emit plan, emit_plan.h --: that sequence leaves
     // the pair count and the capacity flag for the HOST to derive (engine.cpp finish_result), and the split kernels read the count on the device)
     if (p.direct) { set_error("internal error: a pack ran the hole-free emit sequence, whose pair count only exists on the host"); return ARP_ERR_HIP; }
     launch_pack_split(sl.pa, ctx->ws.result, ctx->out_buf, std::min(ctx->out_cap, ctx->grp_cap), ctx->grp_buf, p.mode == PairPass::OrderedFill, ctx->stream);

@@ -7,7 +7,7 @@ struct DebugKnobs {
     int emit_kernel;     // 1: the single-pass emitter runs k_pairs<kEmit> (both operands gathered: the route of inputs beyond 2^24 slots) -- parity suite
     long defer_entries;  // > 0: entries of the deferred-probe list of workspaces allocated from now on (tests: a tiny list makes the grow-and-repeat path run)
     int strip_rows;      // > 0: rows per y strip of the cell order (a power of two) for parameter blocks built from now on; 0: chosen by input size (grid.inl grid_setup)
-    int index_bits;      // the narrow exact record of the single-pass emitter (pairs.inl emit_narrow_bits): 0: index width chosen by input size; 1 .. 20: that width
+    int index_bits;      // the narrow exact record of the single-pass emitter (emit_plan.h plan_emit): 0: index width chosen by input size; 1 .. 20: that width
                          // (an input whose last index does not fit keeps the wide record); < 0: the wide record always
     int table_host;      // test-only library (-DARP_WITH_HOST_TABLE): arp_get_contacts assembles the table on the host
     long freq_chunk_atoms;  // > 0: atoms per pass of arp_contact_frequencies (whole frames, at least one); 0: automatic (freq.inl kFreqAutoAtoms)

@@ -387,15 +387,24 @@ void arp::mark_grid_foreign(arp_context *ctx) {
     ctx->nodefer_x = nullptr; ctx->nodefer_n = 0;
 }
 
-// Builds the cell list of a pass, records whose it is; decides whether the pass will run the residue-rule kernels (k_place then writes the residue words).
-// narrow_ok: the single-pass emitter is the list's one reader (an Emit pass nobody walks the records after): it gets the narrow exact record when it has
-// kernels for this input (emit_narrow_bits) -- k_place then scatters three 16-byte parts per atom instead of four, k_emit gathers two per survivor instead of three.
-static void grid_for_call(arp_context *ctx, const DevAtoms &d, const arp_params *params, Profiler *prof, bool ordered, bool narrow_ok, bool skip_deferred) {
-    bool res = !ordered && emit_takes_res_filter(d);
-    if (res) res = (params->flags & ARP_FLAG_RESIDUE_RUNS) ? true : ((params->flags & ARP_FLAG_NO_RESIDUE_RUNS) ? false : ctx->res_hint);
-    const uint32_t narrow_ib = (narrow_ok && !ordered) ? emit_narrow_bits(d, ctx->ws, skip_deferred) : 0u;
-    launch_grid(d, ctx->ws, ctx->stream, prof, params->dist_cutoff, ordered, res, narrow_ib);
-    mark_grid_owner(ctx, d.per_model ? nullptr : d.x, d.per_model ? 0 : d.n, res, narrow_ib);  // (a pack's grid, per-model origins, is nobody's)
+// The emit plan of a pass (emit_plan.h), made here and nowhere else.  THE INVARIANT: the cell list holds what the plan's kernels read -- residue words
+// (Sorted::rkey) if plan.res, the narrow exact record (Xrec) with plan.narrow_ib index bits if that is not 0, else the wide one (Fat).
+// A pass that builds its list (p.grid) plans freely and pass_issue has k_place write exactly that: narrow_ok when the single-pass emitter is the list's
+// one reader (an Emit pass nobody walks the records after) -- k_place then scatters three 16-byte parts per atom instead of four, k_emit gathers two per
+// survivor instead of three.  A pass on a list that stands plans under the format the context recorded for it (mark_grid_owner): it may use the residue
+// words only if they are there (plan.res implies res_wanted), and a route that reads another exact record than the list's is refused.
+static arp_status plan_pass(arp_context *ctx, const PairPass &p, bool ordered, EmitPlan *plan) {
+    const uint32_t flags = p.params->flags;
+    EmitQuery q;
+    q.n = p.d.n; q.per_model = p.d.per_model != 0u; q.ordered = ordered; q.contacts_only = (flags & ARP_FLAG_CONTACTS_ONLY) != 0; q.skip_deferred = p.skip;
+    q.scratch_cap = ctx->ws.scratch_cap; q.knob_emit_kernel = g_debug.emit_kernel;
+    if (p.grid) {
+        q.res_wanted = (flags & ARP_FLAG_RESIDUE_RUNS) ? true : ((flags & ARP_FLAG_NO_RESIDUE_RUNS) ? false : ctx->res_hint);
+        q.narrow_ok = p.mode == PairPass::Emit && !p.wide_record; q.knob_index_bits = g_debug.index_bits;
+    } else { q.res_wanted = ctx->rkey_valid; q.narrow_ok = ctx->narrow_ib != 0u; q.knob_index_bits = (int)ctx->narrow_ib; }
+    *plan = plan_emit(q);
+    if (!p.grid && plan->narrow_ib != ctx->narrow_ib) { set_error("internal error: the emit plan reads another exact record than the cell list holds"); return ARP_ERR_HIP; }
+    return ARP_OK;
 }
 
 arp_status arp::pass_issue(arp_context *ctx, PairPass &p) {
@@ -404,7 +413,13 @@ arp_status arp::pass_issue(arp_context *ctx, PairPass &p) {
     p.skip = p.direct = p.collected = false;
     const bool emit = p.mode == PairPass::Emit;
     if (emit) p.skip = p.speculate && p.d.x != nullptr && ctx->nodefer_x == p.d.x && ctx->nodefer_n == p.d.n;  // the memo names this input
-    if (p.grid) grid_for_call(ctx, p.d, p.params, prof, ordered, emit && !p.wide_record, p.skip);
+    arp_status s;
+    EmitPlan plan{};
+    if ((p.grid || emit) && (s = plan_pass(ctx, p, ordered, &plan)) != ARP_OK) return s;
+    if (p.grid) {  // builds the cell list as the plan reads it and records whose it is (a pack's grid, per-model origins, is nobody's)
+        launch_grid(p.d, ctx->ws, ctx->stream, prof, p.params->dist_cutoff, ordered, plan.res, plan.narrow_ib);
+        mark_grid_owner(ctx, p.d.per_model ? nullptr : p.d.x, p.d.per_model ? 0 : p.d.n, plan.res, plan.narrow_ib);
+    }
     if (p.mode == PairPass::Count) {
         // (with ARP_FLAG_CONTACTS_ONLY the count that sizes the single-pass emitter's buffer is the cheap candidate count; the ordered fill needs the exact one)
         launch_count(p.d, ctx->ws, ctx->stream, prof, p.capacity, p.have_out, p.have_out ? only : only && ordered);
@@ -412,16 +427,16 @@ arp_status arp::pass_issue(arp_context *ctx, PairPass &p) {
         if (p.grid) launch_count(p.d, ctx->ws, ctx->stream, prof, p.capacity, true, only);
         launch_fill_ordered(p.d, ctx->ws, p.out, p.capacity, ctx->stream, prof, only);
     } else {
-        p.direct = launch_emit(p.d, ctx->ws, p.out, p.capacity, ctx->stream, prof, only, p.skip, ctx->rkey_valid, ctx->narrow_ib);
+        if ((s = launch_emit(p.d, ctx->ws, p.out, p.capacity, ctx->stream, prof, plan)) != ARP_OK) return s;
+        p.direct = plan.route == EmitRoute::Direct || plan.route == EmitRoute::Stage;  // hole-free: the host derives the count (finish_result)
     }
-    arp_status s;
     if (p.between && (s = p.between(ctx, p, p.between_arg)) != ARP_OK) return s;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(ctx->h_result, ctx->ws.result, kResultWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     return ARP_OK;
 }
 
-// After the result words of a pass have arrived.  The hole-free sequence of small inputs (launch_emit returned true) has no fix-up kernel to
+// After the result words of a pass have arrived.  The hole-free sequences (the plan's route was Direct or Stage) have no fix-up kernel to
 // publish the pair count and the flags that depend on it: the records lie back to back from position 0 and kResEmitHead counts them; its
 // probes run inline, so kResDeferred (the chunks of a deferred list) stays 0 (the input-error flags were set by the grid sizing).
 static void finish_result(arp_context *ctx, bool direct, bool skipped, unsigned long long capacity) {

@@ -666,7 +666,7 @@ DEVFN uint32_t narrow_tag(uint32_t res_ord, uint32_t chain_rank) { return (chain
 // RKEY: also write the residue words of the slots (the launcher is about to run the residue-rule kernels, k_emit<.., RES>).
 // Block 0 always leaves result[4] = how many of atoms 1..255 carry their predecessor's residue word: inputs whose residues are runs of atoms
 // (every protein; not a cloud of one-atom residues) are the ones the residue-rule kernels pay for, and the engine picks the kernels of the
-// NEXT call by it (engine.cpp grid_for_call) -- a choice between two kernels with identical results, never a correctness assumption.
+// NEXT call by it (engine.cpp plan_pass) -- a choice between two kernels with identical results, never a correctness assumption.
 // NARROW: the exact record is the 32-byte Xrec (arp_internal.h) with `ib` index bits -- three 16-byte scattered stores per atom instead of four.
 // The kernels that read it take the ligand of a pair to be the atom with the smaller ORIGINAL INDEX, which is the reference's choice (the
 // smaller (chain rank, ordinal) key, complex.rs:108-130) whenever the keys never decrease along the input order: every thread compares its atom's

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #include "arp_internal.h"
 

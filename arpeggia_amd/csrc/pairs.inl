@@ -23,20 +23,13 @@
 enum PairMode { kCountTasks = 0, kFillOrdered = 1, kEmit = 2, kCountContacts = 3 };
 //   kCountContacts  kCountTasks for ARP_FLAG_CONTACTS_ONLY: classifies, counts only the pairs with an interaction
 
-constexpr int kWavesPerBlock = 8;
 constexpr int kQueue = 128;
 constexpr uint32_t kChunk = 256;            // neighbour records per staged chunk (4 KB)
 constexpr uint32_t kBlock = 16;             // prefilter tests per lane between two compaction steps
 constexpr uint32_t kReadAhead = 4;         // LDS reads in flight per lane in the prefilter (more costs a wave of occupancy in registers)
 constexpr uint32_t kPairBlocks = 256 * 8;   // ordered modes: blocks, each owning a contiguous range of wave-tasks
-constexpr int kEmitWavesPerSimd = 6;       // register budget of the emit kernel: 80 VGPRs at 6, 64 at 8
-constexpr uint32_t kEmitBlocks = (1024u * kEmitWavesPerSimd) / kWavesPerBlock;  // emit mode: blocks of 8 waves, 6 waves per SIMD
 constexpr uint32_t kGrab = 1;              // wave-tasks drawn per atomic
-constexpr uint32_t kESlotBits = 24;        // k_emit (pairs_emit.inl): neighbour slot bits of a queue entry (v_mul_u32_u24 turns the entry into the record offset); launch_emit routes larger inputs to k_pairs
-// records per global allocation (one device atomic each).  The wave whose allocation crosses the end of the block's chunk fetches the
-// next one while the block's other waves sleep: 2048 -> 4096 halves those stalls (emit 221 -> 208 us); 8192 gains 2 us more and costs
-// the fix-up 8 us (holes grow with the chunk).
-constexpr uint32_t kChunkRecords = 4096, kSmallChunkRecords = 2048;  // records per allocation chunk (powers of two; the smaller one: k_emit's four-way task split; its 4-wave kernels stage and flush instead)
+// (the launch shapes, chunk sizes and size thresholds of the emit routes: emit_plan.h)
 
 template <int MODE>
 struct WaveLds {                                  // per-wave LDS working set
@@ -169,8 +162,7 @@ DEVFN Slots alloc_chunked_rt(unsigned long long &state, unsigned long long *g_he
 constexpr uint32_t kWaveAllBoth = 1u, kWaveContactsOnly = 2u;  // wave-uniform switches of process_batch, kept in a scalar register
 // Record p of the cell-sorted array through a 32-bit byte offset from the (scalar) base: 48 p = (p + 2 p) << 4 is two full-rate
 // instructions and the load takes the scalar-base form, where a 64-bit multiply-add is a quarter-rate one.  Valid below 2^32 / 48
-// slots; the launchers route larger inputs (kBigSlots) to the variants with inline probes, which address in 64 bits.
-constexpr uint32_t kBigSlots = 0x5000000u;
+// slots; the plan routes larger inputs (kBigSlots, emit_plan.h) to the variants with inline probes, which address in 64 bits.
 template <bool BIG = false>
 DEVFN const Fat &fat_at(const Fat *base, uint32_t p) {
     if (BIG) return base[p];
@@ -488,7 +480,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, ((MODE == kEmit || MODE == kFi
 
 // The deferred pass of the emit mode: candidates that need a hydrogen or disulfide probe, classified with the probes
 // inline and emitted through the same allocator (its blocks add their own holes to the list k_fixup closes).
-constexpr uint32_t kDeferBlocks = 384;       // fills the chip at this kernel's 3 waves per SIMD when the list is long
 __global__ __launch_bounds__(kWavesPerBlock * 64) void k_pairs_deferred(DevAtoms in, const DevParams *dprm, Sorted so, EmitTarget tg,
                                                                          ulonglong2 *hole_list, unsigned long long *result, uint32_t chunk_shift,
                                                                          uint32_t ib /* != 0: narrow records with that many index bits (fat_from_narrow) */) {
@@ -677,7 +668,6 @@ static uint32_t blocks_for(uint32_t n, uint32_t cap) {
 unsigned long long emit_scratch_records() { return (unsigned long long)kMaxHoles * kChunkRecords; }
 
 void launch_grid(const DevAtoms &in, const Workspace &ws, hipStream_t st, Profiler *prof, double cutoff, bool ordered, bool want_rkey, uint32_t narrow_ib) {
-    if (ordered) narrow_ib = 0u;  // (the ordered fill's kernels read the wide record)
     const uint32_t n = in.n;
     const uint32_t nb = (n + 255) / 256;
     auto P0 = [&](const char *nm) { if (prof) prof->begin(nm, st); };
@@ -762,73 +752,4 @@ void launch_fill_ordered(const DevAtoms &in, const Workspace &ws, arp_pair *out,
     if (prof) { prof->end(st); prof->begin("pairs_patch", st); }
     hipLaunchKernelGGL(k_patch_deferred, dim3(kDeferBlocks), dim3(kWavesPerBlock * 64), 0, st, in, (const DevParams *)ws.params, ws.sorted, tg, ws.result, 0u);
     if (prof) prof->end(st);
-}
-
-// what follows either emit kernel: the deferred probe pass (unless the engine's memo says this input defers nothing) and the hole fix-up
-// patch: the emit kernel wrote the deferred candidates as records with a placeholder kind (k_emit, all candidates): k_patch_deferred decides
-// the kinds in place; otherwise k_pairs_deferred classifies and emits them itself (its blocks add holes of their own)
-// chunk_records == 1: the hole-free sequence of small inputs (k_emit's DIRECT kernels): the records lie back to back from position 0,
-// result[2] counts them, the probes ran inline -- nothing follows the emit kernel, and the host derives the count and the status flags
-// k_fixup would have published (engine.cpp finish_result).
-static void launch_emit_tail(const DevAtoms &in, const Workspace &ws, const EmitTarget &tg, uint32_t nb, hipStream_t st, Profiler *prof, bool skip_deferred, bool patch,
-                             uint32_t chunk_records, uint32_t narrow_ib = 0u) {
-    const uint32_t chunk_shift = chunk_shift_of(chunk_records);
-    if (prof) prof->end(st);
-    if (chunk_records == 1u) return;
-    if (!skip_deferred) {
-        if (prof) prof->begin("pairs_deferred", st);
-        if (patch) hipLaunchKernelGGL(k_patch_deferred, dim3(kDeferBlocks), dim3(kWavesPerBlock * 64), 0, st, in, (const DevParams *)ws.params, ws.sorted, tg, ws.result, narrow_ib);
-        else hipLaunchKernelGGL(k_pairs_deferred, dim3(kDeferBlocks), dim3(kWavesPerBlock * 64), 0, st, in, (const DevParams *)ws.params, ws.sorted, tg, ws.hole_list + nb, ws.result, chunk_shift, narrow_ib);
-        if (prof) prof->end(st);
-    }
-    if (prof) prof->begin("pairs_fixup", st);
-    hipLaunchKernelGGL(k_fixup, dim3(256), dim3(kFixThreads), 0, st, (const ulonglong2 *)ws.hole_list, (skip_deferred || patch) ? nb : nb + kDeferBlocks,
-                       (const GridParams *)ws.grid, tg, ws.result, skip_deferred ? 1u : 0u, chunk_shift);
-    if (prof) prof->end(st);
-}
-bool launch_emit_e(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsigned long long capacity, hipStream_t st, Profiler *prof, bool contacts_only,
-                   bool skip_deferred, bool res_filter, uint32_t narrow_ib);
-// the residue-rule kernels exist for the inputs launch_emit_e gives a 12-wave kernel: whoever builds the grid asks this before k_place runs
-bool emit_takes_res_filter(const DevAtoms &in) {
-    const uint32_t tasks = (in.n + 63u) / 64u;
-    return in.n < (1u << kESlotBits) - 64u && !(tasks < 320u && !in.per_model);
-}
-// single-pass emit + hole fix-up: leaves result[0] = number of pairs, out[0..P) contiguous
-// Returns true when the hole-free sequence of small inputs ran: result[0] and the flags k_fixup sets are then the host's to derive from
-// kResEmitHead (the records) and kResDeferred (the deferred list's chunks) -- engine.cpp finish_result.
-// The narrow exact record (arp_internal.h Xrec) is read by k_emit's chunked 12-wave kernels -- single inputs of 320 wave-tasks (20 417 atoms) or more.  The 4-wave kernels of
-// the smallest inputs keep the wide record: they have no residue-rule variant, so on a protein every batch would hold pairs of one residue, which
-// the tags cannot decide, and take the rare branch.  The scratch-staged hole-free kernels (k_emit<.., STAGE>: repeated calls on resident inputs of up to
-// 131 k atoms) keep it as well -- at 10^5 atoms the narrow record measured -1.1 us on S2 and +0.3 us on S1 per step (profiles/r20_narrow_record.md): not worth
-// four more kernels.  Packs keep it too: measured on 1250 five-thousand-atom members, k_place ran 40 us shorter
-// and k_emit 54 us longer, the step 7 us longer (profiles/r20_narrow_record.md).  Index bits: as few as hold the largest index, so the tag gets the rest -- 20 + 12 at 10^6
-// atoms, 17 + 15 at 10^5; inputs beyond 2^20 atoms (kNarrowMaxBits: fewer than 12 tag bits) keep the wide record.  arp_debug_set("index_bits", v): v in
-// 1 .. 20 fixes the width (an input whose last index does not fit it keeps the wide record), v < 0 keeps the wide record always.
-bool emit_takes_stage(const DevAtoms &in, const Workspace &ws, bool skip_deferred);  // (pairs_emit.inl) launch_emit_e would run the scratch-staged hole-free sequence
-uint32_t emit_narrow_bits(const DevAtoms &in, const Workspace &ws, bool skip_deferred) {
-    if (g_debug.index_bits < 0 || g_debug.emit_kernel == 1 || in.n == 0u || in.per_model || !emit_takes_res_filter(in) || emit_takes_stage(in, ws, skip_deferred)) return 0u;
-    uint32_t need = 1u;
-    while (need < 32u && ((in.n - 1u) >> need) != 0u) need++;
-    const uint32_t ib = g_debug.index_bits > 0 ? (uint32_t)g_debug.index_bits : need;
-    return (ib >= need && ib <= kNarrowMaxBits) ? ib : 0u;
-}
-bool launch_emit(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsigned long long capacity, hipStream_t st, Profiler *prof, bool contacts_only,
-                 bool skip_deferred, bool res_filter, uint32_t narrow_ib) {
-    if (in.n >= kBigSlots) {  // beyond the 32-bit record offsets of the single-pass kernels: count + ordered fill with inline probes
-        launch_count(in, ws, st, prof, capacity, true, contacts_only);
-        launch_fill_ordered(in, ws, out, capacity, st, prof, contacts_only);
-        return false;
-    }
-    // The default is k_emit (pairs_emit.inl).  This file's k_pairs<kEmit> -- both exact operands gathered, 8-byte queue entries -- is the
-    // one alternative kept: it takes the inputs beyond k_emit's 2^24 slots, and arp_debug_set("emit_kernel", 1) selects it for the parity suite.
-    const bool gather = g_debug.emit_kernel == 1;  // (arp_debug_set("emit_kernel", 1): the parity suite's run of the alternative kernel)
-    if (!gather && in.n < (1u << kESlotBits) - 64u) return launch_emit_e(in, ws, out, capacity, st, prof, contacts_only, skip_deferred, res_filter && emit_takes_res_filter(in), narrow_ib);
-    EmitTarget tg{out, capacity, ws.scratch, ws.scratch_cap, ws.defer_list, ws.defer_cap};
-    const uint32_t nb = blocks_for(in.n, kEmitBlocks);
-    if (prof) prof->begin("pairs_emit", st);
-    hipLaunchKernelGGL((k_pairs<kEmit, false>), dim3(nb), dim3(kWavesPerBlock * 64), 0, st, in, (const GridParams *)ws.grid, (const DevParams *)ws.params,
-                       (const uint32_t *)ws.cell_start, ws.sorted, ws.task_count, (const unsigned long long *)ws.task_base, tg, ws.hole_list,
-                       ws.task_ctr, ws.result);
-    launch_emit_tail(in, ws, tg, nb, st, prof, skip_deferred, false, kChunkRecords);
-    return false;
 }

@@ -26,8 +26,6 @@
 // What the time is made of now was measured by DOUBLING each class of work: the scattered gathers (21 us per million wave-loads), the LDS
 // reads (5.2) and every vector (0.63) or scalar (0.77) instruction add up to the kernel's time -- no single pipe binds.
 constexpr uint32_t kEChunk = 128;             // staged neighbour records per chunk
-constexpr int kEWaves = 12;                   // waves per block: two blocks per CU share the CU's LDS, 6 waves per SIMD
-constexpr uint32_t kEBlocks = 256u * 2u;
 constexpr int kEWavesPerSimd = (kEWaves * 2) / 4;
 constexpr uint32_t kESlotMask = (1u << kESlotBits) - 1u;
 constexpr uint32_t kEGroup = 8;               // prefilter tests per lane between two "is any window still open" checks
@@ -280,7 +278,6 @@ DEVFN void stage_copy_e(const uint4 *buf, uint32_t n, unsigned long long pos, co
 // to another wave, and the copy waits for the wave's own stores (s_waitcnt vmcnt(0)) and reads the region past the vector L1 (device-scope loads:
 // a region that was flushed once and refilled may still have its old lines there).  A final place beyond the caller's capacity is dropped, not
 // spilled into the scratch block (which holds other waves' regions); the count goes on and tells the host how large a buffer the list needs.
-constexpr uint32_t kWaveStageRecords = 1024;
 DEVFN void stage_copy_g(const uint4 *buf, uint32_t n, unsigned long long pos, const EmitTarget &tg, uint32_t lane) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // four records per lane and trip, every load of a trip in flight before the first is waited for (the first version read one record per trip
@@ -348,7 +345,8 @@ DEVFN ExactRegs exact_issue_e(const WaveLdsE<NARROW> &w, const Sorted &so, uint3
     if (!NARROW) g.kb = *reinterpret_cast<const unsigned long long *>(gp + 32);
     return g;
 }
-// CHUNK == 1: the hole-free sequence of small inputs -- no block allocator, the batch's records go to the wave's staging buffer (sg) on the
+// SEQ: where a batch's records go -- Chunked: the block allocator's chunks of CHUNK records; Direct / Stage: the hole-free sequences, no allocator, records
+// staged per wave (sg) in LDS / in the wave's scratch region.  Direct, the sequence of small inputs: the records go to the staging buffer on the
 // general path, and a pair a probe has to decide is decided HERE, by the lane that holds it (classify<true>, as k_patch_deferred does per
 // list entry): these kernels run at two waves per SIMD anyway, the probes' registers cost them nothing, and a call without a probe pass is
 // one launch shorter.  pe: the bounds the probes read (DIRECT only) + the clash / covalent bounds of the full level count (global memory).
@@ -357,11 +355,12 @@ struct ProbeParamsE { const double *s_clash, *s_cov, *s_vdw, *s_hacc; double s_i
 // 0xFFFFFFFF, which no tag difference exceeds, when every batch has to decide on the real keys (chain groups other than "/", or keys that decrease
 // somewhere along the input order: GridParams::key_unsorted); n_rare: batches that did so far.
 struct NarrowE { uint32_t ib, thr, n_rare; };
-template <bool FULL, bool ONLY, uint32_t CHUNK, bool NARROW>
+enum class EmitSeq { Chunked, Direct, Stage };
+template <bool FULL, bool ONLY, EmitSeq SEQ, uint32_t CHUNK, bool NARROW>
 DEVFN void exact_finish_e(const ExactRegs &g, const ConstsE &K, const TablesE &tb, WaveLdsE<NARROW> &w, BlockLds &bl, uint32_t count, uint32_t slot0,
                           const EmitTarget &tg, uint32_t cap_chunks, unsigned long long *result, uint32_t lane, uint32_t wflags, uint32_t probe_bits, StageRef &sg,
                           const DevAtoms &in, const Sorted &so, const ProbeParamsE &pe, NarrowE &nw) {
-    constexpr bool DIRECT = CHUNK == 1u, STAGE = CHUNK == 2u;  // (CHUNK 1 / 2: the hole-free sequences -- records staged per wave in LDS / in the wave's scratch region)
+    constexpr bool DIRECT = SEQ == EmitSeq::Direct, STAGE = SEQ == EmitSeq::Stage;
     count = __builtin_amdgcn_readfirstlane(count);
     const uint32_t e = g.e, hl = e >> kESlotBits, nb = e & kESlotMask;
     const u32x4 bxy = g.bxy, bzp = g.bzp;
@@ -643,6 +642,8 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == kEWaves ? kEWavesPerSimd : 2) 
     // taken from the global record counter (stage_flush_e): no holes, no fix-up launch.
     static_assert(!DIRECT || WAVES == 4, "the hole-free sequence is the 4-wave kernels'");
     static_assert(!STAGE || (!DIRECT && SPLIT == 4), "the scratch-staged sequence is the 12-wave kernels' with the task split");
+    constexpr EmitSeq kSeq = DIRECT ? EmitSeq::Direct : (STAGE ? EmitSeq::Stage : EmitSeq::Chunked);
+    // (Direct / Stage: 1 / 2 -- nothing allocates; the block's allocator words are set up all the same and emit_epilogue finds no hole in them)
     constexpr uint32_t kChunkE = DIRECT ? 1u : (STAGE ? 2u : (SPLIT == 4 ? kSmallChunkRecords : kChunkRecords));
     static_assert(DIRECT || WAVES == kEWaves, "the 4-wave kernels are DIRECT");
     static_assert(!(RES && DIRECT), "the residue-rule rounds are the 12-wave kernels'");
@@ -857,7 +858,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == kEWaves ? kEWavesPerSimd : 2) 
                             // (Finishing the batch only after the next compaction rounds -- the gathers in flight meanwhile -- was measured: no
                             // gain, 162 us either way; the compiler then parks the next prefilter run on vmcnt(0) for a register it sees reused.)
                             const ExactRegs g = exact_issue_e<true, NARROW>(w, so, qb - queue_lds, 64u, lane);
-                            exact_finish_e<true, ONLY, kChunkE, NARROW>(g, K, tb, w, bl, 64u, slot0, tg, cap_chunks, result, lane, wflags, probe_bits, sg, in, so, pe, nw);
+                            exact_finish_e<true, ONLY, kSeq, kChunkE, NARROW>(g, K, tb, w, bl, 64u, slot0, tg, cap_chunks, result, lane, wflags, probe_bits, sg, in, so, pe, nw);
                             compact(qb);
                         }
                         qbyte = qb;
@@ -869,7 +870,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == kEWaves ? kEWavesPerSimd : 2) 
         if (qbyte != queue_lds) {  // the home records go with the task: drain
             const uint32_t left = (qbyte - queue_lds) >> 2;
             const ExactRegs g = exact_issue_e<false, NARROW>(w, so, 0u, left, lane);
-            exact_finish_e<false, ONLY, kChunkE, NARROW>(g, K, tb, w, bl, left, slot0, tg, cap_chunks, result, lane, wflags, probe_bits, sg, in, so, pe, nw);
+            exact_finish_e<false, ONLY, kSeq, kChunkE, NARROW>(g, K, tb, w, bl, left, slot0, tg, cap_chunks, result, lane, wflags, probe_bits, sg, in, so, pe, nw);
         }
         if (DIRECT || g_lo + group_waves >= g_hi) break;  // every task was some wave's static first one (small inputs): no round trip to the counter for nothing
         uint32_t nxt_task = 0;
@@ -896,58 +897,59 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == kEWaves ? kEWavesPerSimd : 2) 
     }
 }
 
-// whether launch_emit_e runs the scratch-staged hole-free sequence (its comment there); asked by emit_narrow_bits too, before the grid is built
-bool emit_takes_stage(const DevAtoms &in, const Workspace &ws, bool skip_deferred) {
-    constexpr uint32_t kStageTasks = 2048;
-    const uint32_t tasks = (in.n + 63u) / 64u, want = (4u * tasks + (uint32_t)kEWaves - 1u) / (uint32_t)kEWaves, nb = want > kEBlocks ? kEBlocks : want;
-    return tasks >= 320u && tasks <= kStageTasks && !in.per_model && skip_deferred && (unsigned long long)nb * kEWaves * kWaveStageRecords <= ws.scratch_cap;
+
+// The k_emit instantiations: exactly emit_plan.h's list of variants, one kernel per entry.
+typedef void (*EmitKernel)(DevAtoms, const GridParams *, const DevParams *, const uint32_t *, Sorted, EmitTarget, ulonglong2 *, uint32_t *, unsigned long long *, uint32_t);
+template <int K>
+constexpr EmitKernel emit_kernel_of() {
+    constexpr EmitVariant v = kEmitVariants.v[K];
+    return k_emit<v.waves, v.split, v.only, v.direct, v.res, v.stage, v.narrow>;
 }
-// single-pass emit + hole fix-up: leaves result[0] = number of pairs, out[0..P) contiguous
-bool launch_emit_e(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsigned long long capacity, hipStream_t st, Profiler *prof, bool contacts_only,
-                   bool skip_deferred, bool res_filter, uint32_t narrow_ib) {
-    EmitTarget tg{out, capacity, ws.scratch, ws.scratch_cap, ws.defer_list, ws.defer_cap};
-    const uint32_t tasks = (in.n + 63u) / 64u;
-    // Fewer tasks than the chip has wave slots: every task is shared out over four waves by window kind (eight for the smallest inputs, two
-    // per kind set), and below 320 tasks the blocks shrink to four waves so that the few tasks reach more CUs.  Thresholds from size sweeps
-    // of this kernel (tests/microbench/ab_r3ae.sh .. ab_r3ag.sh, profiles/r03_small_inputs.txt): a task is a chain of dependent round trips,
-    // and an input that does not fill the chip has nothing else to hide it behind.
-    // The 4-wave kernels are the hole-free ones (DIRECT); a pack that small keeps the 12-wave sequence with its fix-up, which is what publishes
-    // the count its members' lists are split by on the device.
-    const bool shared = tasks < 4608u, small = tasks < 320u && !in.per_model, eight = small && tasks < 160u;  // (eight: 6bft's 128 tasks run 3 us faster that way, an S2 cloud of the same size 1.3 us slower)
-    const bool direct = small;
-    const uint32_t split = eight ? 8u : (shared ? 4u : 1u);
-    const uint32_t per = small ? 4u : (uint32_t)kEWaves, cap = small ? 1536u : kEBlocks, want = (split * tasks + per - 1u) / per;
-    const uint32_t nb = want < 1 ? 1 : (want > cap ? cap : want);
-    if (prof) prof->begin("pairs_emit", st);
-#define ARP_LAUNCH_E1(...) hipLaunchKernelGGL((k_emit<__VA_ARGS__>), dim3(nb), dim3(per * 64u), 0, st, in, (const GridParams *)ws.grid, (const DevParams *)ws.params, \
-                                              (const uint32_t *)ws.cell_start, ws.sorted, tg, ws.hole_list, ws.task_ctr, ws.result, narrow_ib)
-    // (W, S, O, DIRECT, RES, STAGE; the chunked 12-wave kernels in two forms: the grid build wrote the narrow exact record for this call, narrow_ib != 0, or the wide one)
-#define ARP_LAUNCH_E(W, S, O, D, R, G) do { if (narrow_ib && !(D) && !(G)) ARP_LAUNCH_E1(W, S, O, D, R, G, !(D) && !(G)); else ARP_LAUNCH_E1(W, S, O, D, R, G, false); } while (0)
-    // res_filter: the residue-rule kernels (the engine asks for them when the input's residues are runs of atoms, and had k_place write the residue
-    // words); the 4-wave kernels of the smallest inputs have no such variant (a call of that size is launches and round trips, not batches)
-    // stage: the hole-free sequence of the task-split 12-wave kernels (k_emit<.., STAGE>: records staged per wave in the scratch block, no fix-up launch) -- for
-    // inputs the engine's memo says defer nothing (skip_deferred: the kernel raises status bit 128 if they do after all and the host repeats the call with the
-    // chunked sequence), whose waves' regions fit the scratch block
-    // (up to kStageTasks tasks = 131 k atoms: every record crosses the L2 twice more on this route, which costs the kernel ~1 us per 3 x 10^5 records -- S2 per step,
-    // staged against chunks + fix-up: 3 x 10^4 atoms 53 against 64 us, 6 x 10^4 64 / 71, 10^5 76 / 82 (S1 65 / 80), 1.9 x 10^5 106 / 102, 2.9 x 10^5 146 / 129)
-    const bool stage = emit_takes_stage(in, ws, skip_deferred);
-    if (stage) {
-        if (contacts_only) { if (res_filter) ARP_LAUNCH_E(kEWaves, 4, true, false, true, true); else ARP_LAUNCH_E(kEWaves, 4, true, false, false, true); }
-        else { if (res_filter) ARP_LAUNCH_E(kEWaves, 4, false, false, true, true); else ARP_LAUNCH_E(kEWaves, 4, false, false, false, true); }
-    } else if (contacts_only) {
-        if (eight) ARP_LAUNCH_E(4, 8, true, true, false, false);
-        else if (small) ARP_LAUNCH_E(4, 4, true, true, false, false);
-        else if (shared) { if (res_filter) ARP_LAUNCH_E(kEWaves, 4, true, false, true, false); else ARP_LAUNCH_E(kEWaves, 4, true, false, false, false); }
-        else { if (res_filter) ARP_LAUNCH_E(kEWaves, 1, true, false, true, false); else ARP_LAUNCH_E(kEWaves, 1, true, false, false, false); }
-    } else {
-        if (eight) ARP_LAUNCH_E(4, 8, false, true, false, false);
-        else if (small) ARP_LAUNCH_E(4, 4, false, true, false, false);
-        else if (shared) { if (res_filter) ARP_LAUNCH_E(kEWaves, 4, false, false, true, false); else ARP_LAUNCH_E(kEWaves, 4, false, false, false, false); }
-        else { if (res_filter) ARP_LAUNCH_E(kEWaves, 1, false, false, true, false); else ARP_LAUNCH_E(kEWaves, 1, false, false, false, false); }
+template <int... K>
+static EmitKernel emit_kernel_at(int k, std::integer_sequence<int, K...>) {
+    static const EmitKernel table[] = {emit_kernel_of<K>()...};
+    return table[k];
+}
+void set_error(const char *fmt, ...);  // (host_common.h)
+// The plan's launch sequence, on a cell list built for it: leaves out[0..P) contiguous and result[0] = P; a plan that names a k_emit variant the list
+// above does not hold is an internal error.  The default is k_emit.  k_pairs<kEmit> (Gather, pairs.inl) -- both exact operands gathered, 8-byte
+// queue entries -- is the one alternative kept: it takes the inputs beyond k_emit's 2^24 slots, and arp_debug_set("emit_kernel", 1) selects it for
+// the parity suite.  What follows either (plan.fixup_holes != 0): the deferred probe pass (plan.probes: unless the engine's memo says this input
+// defers nothing) and the hole fix-up.  plan.patch: the emit kernel wrote the deferred candidates as records with a placeholder kind (k_emit, all
+// candidates): k_patch_deferred decides the kinds in place; otherwise k_pairs_deferred classifies and emits them itself (its blocks add holes of
+// their own).  The hole-free sequences (Direct, Stage): the records lie back to back from position 0, result[2] counts them, the probes ran inline
+// or there are none -- nothing follows the emit kernel, and the host derives the count and the status flags k_fixup would have published
+// (engine.cpp finish_result).
+arp_status launch_emit(const DevAtoms &in, const Workspace &ws, arp_pair *out, unsigned long long capacity, hipStream_t st, Profiler *prof, const EmitPlan &plan) {
+    if (plan.route == EmitRoute::Ordered) {  // beyond the 32-bit record offsets of the single-pass kernels: count + ordered fill with inline probes
+        launch_count(in, ws, st, prof, capacity, true, plan.only);
+        launch_fill_ordered(in, ws, out, capacity, st, prof, plan.only);
+        return ARP_OK;
     }
-#undef ARP_LAUNCH_E
-#undef ARP_LAUNCH_E1
-    launch_emit_tail(in, ws, tg, nb, st, prof, skip_deferred, !contacts_only, (direct || stage) ? 1u : (shared ? kSmallChunkRecords : kChunkRecords), narrow_ib);
-    return direct || stage;  // (the host derives the count and the capacity flag from kResEmitHead: engine.cpp finish_result)
+    const bool gather = plan.route == EmitRoute::Gather;
+    const int k = gather ? 0 : emit_variant_index(plan);
+    if (k < 0) { set_error("internal error: the emit plan names a k_emit variant there is none of"); return ARP_ERR_HIP; }
+    EmitTarget tg{out, capacity, ws.scratch, ws.scratch_cap, ws.defer_list, ws.defer_cap};
+    if (prof) prof->begin("pairs_emit", st);
+    if (gather)
+        hipLaunchKernelGGL((k_pairs<kEmit, false>), dim3(plan.blocks), dim3(plan.waves * 64u), 0, st, in, (const GridParams *)ws.grid, (const DevParams *)ws.params,
+                           (const uint32_t *)ws.cell_start, ws.sorted, ws.task_count, (const unsigned long long *)ws.task_base, tg, ws.hole_list, ws.task_ctr, ws.result);
+    else
+        hipLaunchKernelGGL(emit_kernel_at(k, std::make_integer_sequence<int, kEmitVariantCount>{}), dim3(plan.blocks), dim3(plan.waves * 64u), 0, st, in, (const GridParams *)ws.grid,
+                           (const DevParams *)ws.params, (const uint32_t *)ws.cell_start, ws.sorted, tg, ws.hole_list, ws.task_ctr, ws.result, plan.narrow_ib);
+    if (prof) prof->end(st);
+    if (plan.fixup_holes == 0u) return ARP_OK;
+    const uint32_t chunk_shift = chunk_shift_of(plan.chunk_records);
+    if (plan.probes) {
+        if (prof) prof->begin("pairs_deferred", st);
+        if (plan.patch) hipLaunchKernelGGL(k_patch_deferred, dim3(kDeferBlocks), dim3(kWavesPerBlock * 64), 0, st, in, (const DevParams *)ws.params, ws.sorted, tg, ws.result, plan.narrow_ib);
+        else hipLaunchKernelGGL(k_pairs_deferred, dim3(kDeferBlocks), dim3(kWavesPerBlock * 64), 0, st, in, (const DevParams *)ws.params, ws.sorted, tg, ws.hole_list + plan.blocks, ws.result, chunk_shift, plan.narrow_ib);
+        if (prof) prof->end(st);
+    }
+    if (prof) prof->begin("pairs_fixup", st);
+    hipLaunchKernelGGL(k_fixup, dim3(256), dim3(kFixThreads), 0, st, (const ulonglong2 *)ws.hole_list, plan.fixup_holes, (const GridParams *)ws.grid, tg, ws.result,
+                       plan.probes ? 0u : 1u, chunk_shift);
+    if (prof) prof->end(st);
+    return ARP_OK;
 }
-static_assert(kEBlocks + 384u <= kMaxHoles && 1536u + 384u <= kMaxHoles, "hole list: one entry per block of either kernel");
+static_assert(kEBlocks + kDeferBlocks <= kMaxHoles && kDirectBlocks + kDeferBlocks <= kMaxHoles, "hole list: one entry per block of either kernel");

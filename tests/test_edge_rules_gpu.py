@@ -13,7 +13,7 @@ import synth
 
 pytestmark = pytest.mark.gpu
 
-SMALL_ROUTE, STAGE_ROUTE = 20480, 131072  # pairs.inl emit_takes_res_filter (320 tasks of 64), pairs_emit.inl kStageTasks (2048 tasks)
+SMALL_ROUTE, STAGE_ROUTE = 20480, 131072  # emit_plan.h: kDirectTasks (320 tasks of 64), kStageTasks (2048 tasks)
 
 
 @pytest.fixture(scope="module")

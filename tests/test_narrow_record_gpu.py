@@ -12,20 +12,9 @@ import pytest
 import arpeggia_amd as aa
 import oracle_binding as ob
 import synth
+from oracle_lists import assert_same_as_oracle, both, canon
 
 N_CLOUD = 1 << 15  # the last index is the largest a 15-bit index holds; 512 wave-tasks: a 12-wave kernel with the four-way task split
-
-
-def canon(p):
-    return p[np.lexsort((p["j"], p["i"]))]
-
-
-def assert_same_as_oracle(got, want, what):
-    assert len(got) == len(want), f"{what}: {len(got)} pairs vs oracle {len(want)}"
-    g, w = canon(got), canon(want)
-    assert np.array_equal(g["i"], w["i"].astype(np.uint32)) and np.array_equal(g["j"], w["j"].astype(np.uint32)), f"{what}: pair indices differ"
-    assert np.array_equal(g["kind"], w["kind"]), f"{what}: kinds differ"
-    assert np.array_equal(g["dist"], w["dist"].astype(np.float32)), f"{what}: f32 distances not bit-identical"
 
 
 def tagged_cloud(n: int, modulus: int, two_chains: bool) -> dict:
@@ -62,12 +51,6 @@ def ordinal_gaps_within_cutoff(rec: dict, cutoff: float = 6.5) -> set:
     same = rec["chain"][pairs[:, 0]] == rec["chain"][pairs[:, 1]]
     ro = rec["res_ord"].astype(np.int64)
     return set(np.unique(np.abs(ro[pairs[same, 0]] - ro[pairs[same, 1]])).tolist())
-
-
-def both(rec: dict, groups: str = "/"):
-    soa = aa.Structure.from_records(rec, hierarchy=True).soa(groups)
-    want = ob.Structure.from_atoms(synth.records_to_oracle(rec, flat=True), flat=True).atomic_contacts(groups, 0.1, 6.5)
-    return soa, want
 
 
 @pytest.fixture(scope="module")
