@@ -23,6 +23,7 @@ ARP_FLAG_RESIDUE_RUNS = 0x8
 ARP_FLAG_NO_RESIDUE_RUNS = 0x10
 ARP_SASA_MAX_POINTS = 4096
 ARP_FREQ_RINGS = 0x1
+ARP_TIMELINE_NO_BITMAP = 0x2
 ARP_RADII_VDW, ARP_RADII_PROTOR = 0, 1
 
 ATTR = dict(
@@ -201,6 +202,9 @@ def _load():
         "arp_contact_frequencies": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_double, C.c_double, C.POINTER(vp)]),
         "arp_contact_frequencies_ex": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_double, C.c_double, C.c_uint32, C.POINTER(vp)]),
         "arp_residue_contact_frequencies": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_double, C.c_double, C.c_uint32, C.POINTER(vp)]),
+        "arp_contact_timelines": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_double, C.c_double, C.c_uint32, C.c_int32, C.POINTER(vp)]),
+        "arp_table_timeline": (C.c_void_p, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "arp_timeline_stats": (C.c_int32, [C.c_uint64, C.c_uint64] + [_u32p] * 6),
         "arp_sasa_radius": (C.c_int32, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, _fp]),
         "arp_max_asa": (C.c_float, [C.c_char_p]),
         "arp_residue_is_polar": (C.c_int32, [C.c_char_p]),

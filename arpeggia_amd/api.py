@@ -43,6 +43,9 @@ RESIDUE_FREQ_COLUMNS = [  # arp_residue_contact_frequencies: one row per distinc
     ("to_chain", "str"), ("to_resn", "str"), ("to_resi", "i4"), ("to_insertion", "str"),
     ("n_frames", "u4"), ("frequency", "f4"), ("min_distance", "f4"), ("max_distance", "f4"),
 ]
+TIMELINE_COLUMNS = [  # arp_contact_timelines: behind the frequency columns of the level (FREQ_COLUMNS / RESIDUE_FREQ_COLUMNS)
+    ("first_frame", "u4"), ("last_frame", "u4"), ("n_events", "u4"), ("longest_run", "u4"), ("mean_run", "f4"),
+]
 
 
 class ArpeggiaError(RuntimeError):
@@ -83,7 +86,7 @@ def default_params(vdw_comp: float = 0.1, dist_cutoff: float = 6.5, deterministi
 
 
 def debug_set(key: str, value: int):
-    """arp_debug_set: the library's diagnostic switches ("timing", "emit_kernel", "defer_entries", "table_host", "freq_chunk_atoms", "freq_cap_items", "freq_frame_bits", ...; include/arpeggia_amd.h)."""
+    """arp_debug_set: the library's diagnostic switches ("timing", "emit_kernel", "defer_entries", "table_host", "freq_chunk_atoms", "freq_cap_items", "freq_frame_bits", "timeline_cap_bytes", ...; include/arpeggia_amd.h)."""
     _check(lib.arp_debug_set(key.encode(), int(value)))
 
 
@@ -368,35 +371,20 @@ class Context:
         RESIDUE_FREQ_COLUMNS + from_residue / to_residue (residue ordinals of the topology)."""
         t = _freq_table(self, structure, frames, groups, vdw_comp, dist_cutoff, rings, level)
         try:
-            n = int(lib.arp_table_rows(t))
-            cols = {}
+            return _freq_columns(t, rings, level)
+        finally:
+            lib.arp_table_free(t)
 
-            def col(name, dtype=None):
-                w = C.c_int32()
-                p = lib.arp_table_column(t, name.encode(), C.byref(w))
-                if not p and n:
-                    raise KeyError(name)
-                return _np_from(p, n, dtype or f"S{max(w.value, 1)}")
-
-            if level == "residue":
-                for name, kind in RESIDUE_FREQ_COLUMNS:
-                    cols[name] = col(name, "<i4") if name == "interaction" else col(name) if kind == "str" else col(name, "<" + kind)
-                cols["from_residue"] = col("from_residue", "<i4")
-                cols["to_residue"] = col("to_residue", "<i4")
-                return cols
-            for name, kind in FREQ_COLUMNS:
-                if name == "interaction":
-                    cols[name] = col(name, "<i4")
-                elif kind == "str":
-                    cols[name] = col(name)
-                else:
-                    cols[name] = col(name, "<" + kind)
-            cols["from_atom"] = col("from_atom", "<i4")
-            cols["to_atom"] = col("to_atom", "<i4")
-            if rings:
-                cols["from_ring"] = col("from_ring", "<i4")
-                cols["to_ring"] = col("to_ring", "<i4")
-            return cols
+    def contact_timelines(self, structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, rings: bool = False,
+                          level: str = "atom", bitmap: bool = True) -> dict:
+        """arp_contact_timelines as a dict of numpy columns: every column contact_frequencies returns for the same arguments (identical bytes), plus
+        first_frame / last_frame / n_events / longest_run (u4) and mean_run (f4) per row (TIMELINE_COLUMNS): the first and last frame in which the
+        row's contact exists, its number of uninterrupted stretches, the longest of them in frames, and n_frames / n_events.  bitmap=True adds
+        timeline_words [rows, ceil(F / 32)] <u4 -- frame f is bit f & 31 of word f >> 5 (unpack_timeline makes it a bool [rows, F]) -- and
+        n_total_frames = F; bitmap=False (ARP_TIMELINE_NO_BITMAP) leaves the bitmap on the device."""
+        t = _timeline_table(self, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, bitmap)
+        try:
+            return _timeline_columns(t, rings, level)
         finally:
             lib.arp_table_free(t)
 
@@ -451,6 +439,93 @@ def _freq_table(ctx: "Context | None", structure: Structure, frames, groups: str
     _check(call(ctx._h if ctx is not None else None, structure._h, int(n_frames), ptr, groups.encode(), float(vdw_comp),
                 float(dist_cutoff), _lib.ARP_FREQ_RINGS if rings else 0, C.byref(t)))
     return t if ctx is not None else None
+
+
+def _freq_columns(t, rings: bool, level: str) -> dict:
+    """The numpy columns of a frequency table handle (copies): FREQ_COLUMNS + from_atom / to_atom (+ from_ring / to_ring with rings), or
+    RESIDUE_FREQ_COLUMNS + from_residue / to_residue."""
+    n = int(lib.arp_table_rows(t))
+    cols = {}
+
+    def col(name, dtype=None):
+        w = C.c_int32()
+        p = lib.arp_table_column(t, name.encode(), C.byref(w))
+        if not p and n:
+            raise KeyError(name)
+        return _np_from(p, n, dtype or f"S{max(w.value, 1)}")
+
+    if level == "residue":
+        for name, kind in RESIDUE_FREQ_COLUMNS:
+            cols[name] = col(name, "<i4") if name == "interaction" else col(name) if kind == "str" else col(name, "<" + kind)
+        cols["from_residue"] = col("from_residue", "<i4")
+        cols["to_residue"] = col("to_residue", "<i4")
+        return cols
+    for name, kind in FREQ_COLUMNS:
+        if name == "interaction":
+            cols[name] = col(name, "<i4")
+        elif kind == "str":
+            cols[name] = col(name)
+        else:
+            cols[name] = col(name, "<" + kind)
+    cols["from_atom"] = col("from_atom", "<i4")
+    cols["to_atom"] = col("to_atom", "<i4")
+    if rings:
+        cols["from_ring"] = col("from_ring", "<i4")
+        cols["to_ring"] = col("to_ring", "<i4")
+    return cols
+
+
+def _timeline_table(ctx: "Context | None", structure: Structure, frames, groups: str, vdw_comp: float, dist_cutoff: float, rings: bool, level: str, bitmap: bool):
+    """arp_contact_timelines -> table handle (the caller frees it).  ctx None: the inputs are only checked (raises their error, else returns None)."""
+    if level not in ("atom", "residue"):
+        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
+    n_frames, ptr, keep = _frames_arg(structure, frames, "contact timelines")
+    t = C.c_void_p()
+    flags = (_lib.ARP_FREQ_RINGS if rings else 0) | (0 if bitmap else _lib.ARP_TIMELINE_NO_BITMAP)
+    _check(lib.arp_contact_timelines(ctx._h if ctx is not None else None, structure._h, int(n_frames), ptr, groups.encode(), float(vdw_comp), float(dist_cutoff),
+                                     flags, 1 if level == "residue" else 0, C.byref(t)))
+    return t if ctx is not None else None
+
+
+def _timeline_columns(t, rings: bool, level: str) -> dict:
+    """The frequency columns of a timeline table handle, TIMELINE_COLUMNS and, when the table holds its bitmap, timeline_words + n_total_frames (copies)."""
+    cols = _freq_columns(t, rings, level)
+    n = int(lib.arp_table_rows(t))
+    for name, kind in TIMELINE_COLUMNS:
+        p = lib.arp_table_column(t, name.encode(), None)
+        if not p and n:
+            raise KeyError(name)
+        cols[name] = _np_from(p, n, "<" + kind)
+    wpr, nf = C.c_uint64(), C.c_uint64()
+    p = lib.arp_table_timeline(t, C.byref(wpr), C.byref(nf))
+    if p:
+        cols["timeline_words"] = _np_from(p, n * wpr.value, "<u4").reshape(n, wpr.value)
+        cols["n_total_frames"] = int(nf.value)
+    return cols
+
+
+def unpack_timeline(words, n_frames: int) -> np.ndarray:
+    """timeline_words [rows, ceil(F / 32)] <u4 -> bool [rows, F]: present[r, f] = bit f & 31 of words[r, f >> 5]."""
+    words = np.ascontiguousarray(words, dtype="<u4")
+    if words.ndim != 2 or words.shape[1] != (int(n_frames) + 31) // 32:
+        raise ValueError(f"words must have shape [rows, {(int(n_frames) + 31) // 32}] for {n_frames} frames, got {list(words.shape)}")
+    return np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")[:, :int(n_frames)].astype(bool)
+
+
+def timeline_stats(words, n_frames: int) -> dict:
+    """arp_timeline_stats (host only, no device): the definition of the timeline statistics, bit by bit, on any bitmap of the timeline_words layout
+    -- e.g. a frame window or the AND of two rows.  Returns n_present, first_frame, last_frame (0xFFFFFFFF for a row without a set bit), n_events,
+    longest_run, each [rows] <u4."""
+    words = np.ascontiguousarray(words, dtype="<u4")
+    W = (int(n_frames) + 31) // 32
+    if words.ndim != 2 or words.shape[1] != W:
+        raise ValueError(f"words must have shape [rows, {W}] for {n_frames} frames, got {list(words.shape)}")
+    rows = words.shape[0]
+    out = {k: np.zeros(rows, "<u4") for k in ("n_present", "first_frame", "last_frame", "n_events", "longest_run")}
+    u32p = C.POINTER(C.c_uint32)
+    src = words if words.size else np.zeros(1, "<u4")
+    _check(lib.arp_timeline_stats(rows, int(n_frames), src.ctypes.data_as(u32p), *[(v if rows else np.zeros(1, "<u4")).ctypes.data_as(u32p) for v in out.values()]))
+    return out
 
 
 def _frames_arg(structure: Structure, frames, what: str):
@@ -727,6 +802,51 @@ def contact_frequencies(input_file: str, groups: str = "/", vdw_comp: float = 0.
     if level not in ("atom", "residue"):
         raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
     return get_contact_frequencies(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings, level=level)
+
+
+def get_contact_timelines(structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, device: int = 0,
+                          rings: bool = False, level: str = "atom", bitmap: bool = True) -> dict:
+    """When every contact of an ensemble exists (arp_contact_timelines): the rows of get_contact_frequencies for the same arguments, as a dict of
+    numpy columns -- the frequency columns of the level (FREQ_COLUMNS + from_atom / to_atom, with rings from_ring / to_ring; RESIDUE_FREQ_COLUMNS +
+    from_residue / to_residue), identical bytes -- plus TIMELINE_COLUMNS per row: first_frame, last_frame, n_events (maximal runs of consecutive
+    frames with the contact), longest_run (frames) and mean_run = n_frames / n_events.  bitmap=True adds timeline_words [rows, ceil(F / 32)] <u4
+    (frame f = bit f & 31 of word f >> 5; unpack_timeline) and n_total_frames.  frames, groups, rings and level as get_contact_frequencies."""
+    if level not in ("atom", "residue"):
+        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
+    try:
+        ctx = _context(device)
+    except ArpeggiaError:
+        _timeline_table(None, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, bitmap)  # an input error takes precedence over the missing device
+        raise
+    return ctx.contact_timelines(structure, frames, groups, vdw_comp, dist_cutoff, rings, level, bitmap)
+
+
+def contact_timelines(input_file: str, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, ignore_zero_occupancy: bool = False,
+                      rings: bool = False, level: str = "atom", bitmap: bool = True) -> dict:
+    """Contact timelines across the models of a multi-model file (the models are the frames): see get_contact_timelines."""
+    if level not in ("atom", "residue"):
+        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
+    return get_contact_timelines(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings, level=level, bitmap=bitmap)
+
+
+def _contact_timelines_arrow(input_file: str, groups: str, vdw_comp: float, dist_cutoff: float, ignore_zero_occupancy: bool, rings: bool, level: str, bitmap: bool):
+    """The command line's form of contact_timelines: (Arrow table of the frequency + timeline columns, timeline_words or None)."""
+    import pyarrow as pa
+
+    structure = Structure.load(input_file, ignore_zero_occupancy)
+    try:
+        ctx = _context(0)
+    except ArpeggiaError:
+        _timeline_table(None, structure, None, groups, vdw_comp, dist_cutoff, rings, level, bitmap)
+        raise
+    t = _timeline_table(ctx, structure, None, groups, vdw_comp, dist_cutoff, rings, level, bitmap)
+    try:
+        arr, sch = _lib.ArrowArray(), _lib.ArrowSchema()
+        _check(lib.arp_table_export_arrow(t, C.byref(arr), C.byref(sch)))
+        table = pa.Table.from_batches([pa.RecordBatch._import_from_c(C.addressof(arr), C.addressof(sch))])
+        return table, _timeline_columns(t, rings, level).get("timeline_words")
+    finally:
+        lib.arp_table_free(t)
 
 
 def contacts_batch(input_files, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, ignore_zero_occupancy: bool = False,

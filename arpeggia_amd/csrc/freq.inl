@@ -161,7 +161,26 @@ __global__ __launch_bounds__(128) void k_freq_ring_fit(uint32_t frames, uint32_t
 template <bool RES>
 __global__ __launch_bounds__(256) void k_freq_ring_rows(uint32_t n_tiles, uint32_t n, FreqRings r, const uint32_t *attr, const uint32_t *res_ord, const uint32_t *chain_rank, const double *x,
                                  const double *y, const double *z, const PlaneD *planes, double cutoff, unsigned long long *keys, FreqVal *vals, uint32_t base, uint32_t cap,
-                                 uint32_t *counter, FreqResKey rk);
+                                 uint32_t *counter, FreqResKey rk, uint32_t *item_frame);
+
+// the mark sweep of arp_contact_timelines (timeline.inl, behind freq_rings.inl): the same passes -- upload, k_freq_tile, pair pass, ring fit -- but
+// every item ORs its frame's bit into its row of a bitmap instead of joining the aggregate.  What a pass hands over:
+struct TimelineMarks;
+struct FreqPassView {
+    uint32_t n, f0, frames, n_pairs;  // topology atoms; the pass's first frame and frame count; its listed pairs
+    const arp_pair *pairs;
+    bool residue;
+    uint32_t res_bits;                // residue level: bits of a residue ordinal in a row key
+    const uint32_t *res_of;
+    FreqRings fr;                     // n_rings > 0: what k_freq_ring_rows takes
+    uint32_t ring_tiles;
+    const uint32_t *attr, *res_ord, *chain_rank;
+    const double *x, *y, *z;
+    const PlaneD *planes;
+    double cutoff;
+    FreqResKey rk;
+};
+arp_status timeline_mark_pass(hipStream_t st, TimelineMarks *marks, const FreqPassView &v);
 
 namespace {
 uint32_t freq_blocks(unsigned long long items) { return (uint32_t)std::max<unsigned long long>(1ull, (items + 255u) / 256u); }  // (items < 2^32: one thread each)
@@ -203,7 +222,8 @@ arp_status freq_alloc(FreqBufs *b, uint64_t cap, uint64_t keep, hipStream_t st) 
 }
 }  // namespace
 
-arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost *out) {
+// marks == nullptr: the frequency table of the job.  Otherwise the mark sweep of timeline.inl: every pass ends in timeline_mark_pass and *out stays empty.
+arp_status freq_sweep(arp_context *ctx, const FreqJob &job, FreqRowsHost *out, TimelineMarks *marks) {
     hipStream_t st = (hipStream_t)context_stream(ctx);
     HIP_TRY(hipSetDevice(context_device(ctx)));
     const bool timing = g_debug.timing != 0;
@@ -311,6 +331,13 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
             HIP_TRY(hipGetLastError());
             lap("ring fit");
         }
+        if (marks) {
+            const FreqPassView view{(uint32_t)n, (uint32_t)f0, (uint32_t)fc, (uint32_t)n_pairs, pairs, job.residue, rb, tp.res_id, fr, ring_tiles, tp.attr, tp.res_ord, tp.chain_rank,
+                                    pk.x, pk.y, pk.z, planes, job.dist_cutoff, rk};
+            if ((s = timeline_mark_pass(st, marks, view)) != ARP_OK) return s;
+            lap("marks");
+            continue;
+        }
         // 3. expand into (key, value) items behind the aggregate, the ring items behind the atom items; grown and repeated when they do not fit
         if (!fb.block && (s = freq_alloc(&fb, g_debug.freq_cap_items > 0 ? (uint64_t)g_debug.freq_cap_items : std::max<uint64_t>(1u << 16, 2 * n_pairs), 0, st)) != ARP_OK) return s;
         uint32_t n_items = 0;
@@ -323,7 +350,7 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
                 lap("expand");
                 hipLaunchKernelGGL(ring_rows_kernel, dim3((uint32_t)fc * ring_tiles), dim3(256), 0, st, ring_tiles, (uint32_t)n, fr,
                                    tp.attr, tp.res_ord, tp.chain_rank, (const double *)pk.x, (const double *)pk.y, (const double *)pk.z, (const PlaneD *)planes, job.dist_cutoff,
-                                   fb.kin, fb.vin, (uint32_t)n_agg, (uint32_t)fb.cap, fb.counter, rk);
+                                   fb.kin, fb.vin, (uint32_t)n_agg, (uint32_t)fb.cap, fb.counter, rk, (uint32_t *)nullptr);
                 HIP_TRY(hipGetLastError());
             }
             HIP_TRY(hipMemcpyAsync(&n_items, fb.counter, 4, hipMemcpyDeviceToHost, st));
@@ -372,6 +399,7 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
             n_agg = runs;
         }
     }
+    if (marks) return ARP_OK;
     // 6. only the aggregate comes back
     out->key.resize(n_agg); out->count.resize(n_agg); out->mn.resize(n_agg); out->mx.resize(n_agg);
     if (n_agg) {
@@ -387,3 +415,4 @@ arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost
     lap("download");
     return ARP_OK;
 }
+arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost *out) { return freq_sweep(ctx, job, out, nullptr); }

@@ -27,11 +27,11 @@ __global__ __launch_bounds__(128) void k_freq_ring_fit(uint32_t frames, uint32_t
 // lanes sweep first the frame's rings (k_ring_ring: e1 in the ligand set, e2 in the receptor set, centres within 6 A first), then the topology's
 // candidate atoms (k_ring_atom: d^2 <= cutoff^2 in f64, the residue rule, then the plane arithmetic).  A hit is rare; the waves stay converged
 // around it, and per (tile ring, sweep step) the hits of a wave take their places with ONE atomic on the pass's item counter (k_freq_expand's
-// counter).  Nothing is written at or past cap; the counter counts every item.
+// counter).  Nothing is written at or past cap; the counter counts every item.  item_frame (nullable): the item's frame inside the pass, at the key's place.
 template <bool RES>
 __global__ __launch_bounds__(256) void k_freq_ring_rows(uint32_t n_tiles, uint32_t n, FreqRings r, const uint32_t *attr, const uint32_t *res_ord, const uint32_t *chain_rank,
                                                         const double *x, const double *y, const double *z, const PlaneD *planes, double cutoff,
-                                                        unsigned long long *keys, FreqVal *vals, uint32_t base, uint32_t cap, uint32_t *counter, FreqResKey rk) {
+                                                        unsigned long long *keys, FreqVal *vals, uint32_t base, uint32_t cap, uint32_t *counter, FreqResKey rk, uint32_t *item_frame) {
     __shared__ double s_c[3][kFreqRingTile], s_n[3][kFreqRingTile];
     __shared__ uint32_t s_chain[kFreqRingTile], s_ord[kFreqRingTile], s_flags[kFreqRingTile], s_res[RES ? kFreqRingTile : 1];
     const uint32_t f = blockIdx.x / n_tiles, e0 = (blockIdx.x % n_tiles) * kFreqRingTile, lane = threadIdx.x & 63u;
@@ -57,6 +57,7 @@ __global__ __launch_bounds__(256) void k_freq_ring_rows(uint32_t n_tiles, uint32
             const uint32_t d = freq_code((float)dist);  // (narrowed to f32 where the table path narrows it: append_row)
             keys[o] = key;
             vals[o] = FreqVal{1u, d, d};
+            if (item_frame) item_frame[o] = f;  // (the mark sweep of timeline.inl: an atom-level key does not hold the frame)
         }
     };
     // the item's key: from tile ring t to ring entity e2 (to_ring) or to topology atom `to`

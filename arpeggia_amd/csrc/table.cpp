@@ -299,6 +299,12 @@ struct arp_table {
     std::vector<int32_t> from_ring, to_ring;   // ring entity index of the topology, -1 for an atom (arp_contact_frequencies_ex)
     std::vector<uint32_t> n_frames;
     std::vector<float> frequency, min_distance, max_distance;
+    // contact-timeline table (arp_contact_timelines): a frequency table of either level with five more columns and, unless
+    // ARP_TIMELINE_NO_BITMAP, the rows' frame bitmap (arp_table_timeline)
+    bool timeline = false;
+    uint64_t tl_words_per_row = 0, tl_frames = 0;
+    std::vector<uint32_t> tl_words, first_frame, last_frame, n_events, longest_run;
+    std::vector<float> mean_run;
 };
 
 namespace {
@@ -693,7 +699,14 @@ extern "C" const void *arp_table_column(const arp_table *t_const, const char *na
         if (c == "max_distance") return num(t->max_distance.data(), 4);
         if (c == "from_ring") return num(t->from_ring.data(), 4);
         if (c == "to_ring") return num(t->to_ring.data(), 4);
-        if (c == "model" || c == "distance" || c.compare(0, 3, "sc_") == 0) return nullptr;
+        if (t->timeline) {
+            if (c == "first_frame") return num(t->first_frame.data(), 4);
+            if (c == "last_frame") return num(t->last_frame.data(), 4);
+            if (c == "n_events") return num(t->n_events.data(), 4);
+            if (c == "longest_run") return num(t->longest_run.data(), 4);
+            if (c == "mean_run") return num(t->mean_run.data(), 4);
+        }
+        if (c == "model"|| c == "distance" || c.compare(0, 3, "sc_") == 0) return nullptr;
         if (t->freq_res) {
             if (c == "from_residue") return num(t->from_residue.data(), 4);
             if (c == "to_residue") return num(t->to_residue.data(), 4);
@@ -953,6 +966,9 @@ arp_status export_arrow_freq(const arp_table *t, ArrowArray *out_array, ArrowSch
     if (!t->freq_res) fields.insert(fields.end(), {{"to_altloc", "u", utf8_col(t->to_altloc)}, {"to_atomn", "u", utf8_col(t->to_atomn)}, {"to_atomi", "i", numeric_col(t->to_atomi)}});
     fields.insert(fields.end(), {{"n_frames", "I", numeric_col(t->n_frames)}, {"frequency", "f", numeric_col(t->frequency)},
                                  {"min_distance", "f", numeric_col(t->min_distance)}, {"max_distance", "f", numeric_col(t->max_distance)}});
+    if (t->timeline)  // arp_contact_timelines: its five columns behind the frequency columns (the bitmap is not part of the batch)
+        fields.insert(fields.end(), {{"first_frame", "I", numeric_col(t->first_frame)}, {"last_frame", "I", numeric_col(t->last_frame)}, {"n_events", "I", numeric_col(t->n_events)},
+                                     {"longest_run", "I", numeric_col(t->longest_run)}, {"mean_run", "f", numeric_col(t->mean_run)}});
     ArrowBatch *b = new ArrowBatch();
     ArrowFields *f = new ArrowFields();
     b->kids.resize(fields.size()); f->kids.resize(fields.size());
@@ -1226,18 +1242,11 @@ arp_status freq_prepare(arp_context *ctx, arp_structure *s, uint64_t n_frames, c
 }
 }  // namespace
 
-extern "C" arp_status arp_contact_frequencies_ex(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
-                                                 double dist_cutoff, uint32_t flags, arp_table **out) try {
-    if (!s || !out || !groups) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
-    *out = nullptr;
-    FreqPrep prep;
-    arp_status st = freq_prepare(ctx, s, n_frames, xyz, groups, vdw_comp, dist_cutoff, flags, &prep);
-    if (st != ARP_OK || prep.checked_only) return st;
+namespace {
+// the atom-level frequency table of the device's rows: identity strings of the rows' atoms from the topology
+std::unique_ptr<arp_table> freq_table_atoms(const arp_structure *s, const FreqPrep &prep, FreqRowsHost &rows) {
     const uint64_t n0 = prep.n0, F = prep.F;
     const FreqRingTopo &rt = prep.rt;
-    FreqRowsHost rows;
-    if ((st = device_frequencies(ctx, prep.job, &rows)) != ARP_OK) return st;
-    // the table: identity strings of the rows' atoms from the topology
     std::unique_ptr<arp_table> t(new arp_table());
     const size_t nrow = rows.key.size();
     t->freq = true; t->n = nrow;
@@ -1275,22 +1284,26 @@ extern "C" arp_status arp_contact_frequencies_ex(arp_context *ctx, arp_structure
             t->to_resi[k] = s->resi[j]; t->to_atomi[k] = s->serial[j]; t->to_atom[k] = (int32_t)j;
         }
     }
-    *out = t.release();
-    return ARP_OK;
-} ARP_ABI_CATCH
+    return t;
+}
+}  // namespace
 
-// Residue level (DESIGN.md section 3.12): the same checks, set-up and items; the device keys them by residue and counts a frame once per row.
-extern "C" arp_status arp_residue_contact_frequencies(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
-                                                      double dist_cutoff, uint32_t flags, arp_table **out) try {
+extern "C" arp_status arp_contact_frequencies_ex(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
+                                                 double dist_cutoff, uint32_t flags, arp_table **out) try {
     if (!s || !out || !groups) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
     *out = nullptr;
     FreqPrep prep;
     arp_status st = freq_prepare(ctx, s, n_frames, xyz, groups, vdw_comp, dist_cutoff, flags, &prep);
     if (st != ARP_OK || prep.checked_only) return st;
-    prep.job.residue = true;
-    prep.job.frame_bits = g_debug.freq_frame_bits > 0 ? (uint32_t)g_debug.freq_frame_bits : 0u;
     FreqRowsHost rows;
     if ((st = device_frequencies(ctx, prep.job, &rows)) != ARP_OK) return st;
+    *out = freq_table_atoms(s, prep, rows).release();
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+namespace {
+// the residue-level frequency table of the device's rows
+std::unique_ptr<arp_table> freq_table_residues(const arp_structure *s, const FreqPrep &prep, FreqRowsHost &rows) {
     // a residue's identity: its first topology atom (what the residue-SASA rows take it from)
     std::vector<uint32_t> first(prep.r0, ARP_NONE);
     for (uint64_t a = prep.n0; a-- > 0;) first[s->res_id[a]] = (uint32_t)a;
@@ -1314,6 +1327,89 @@ extern "C" arp_status arp_residue_contact_frequencies(arp_context *ctx, arp_stru
         memcpy(t->to_chain.at(k), s->chain.at(j), 8); memcpy(t->to_resn.at(k), s->res_resn.at(j), 8); memcpy(t->to_insertion.at(k), s->icode.at(j), 4);
         t->to_resi[k] = s->resi[j]; t->to_residue[k] = (int32_t)B;
     }
+    return t;
+}
+}  // namespace
+
+// Residue level (DESIGN.md section 3.12): the same checks, set-up and items; the device keys them by residue and counts a frame once per row.
+extern "C" arp_status arp_residue_contact_frequencies(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
+                                                      double dist_cutoff, uint32_t flags, arp_table **out) try {
+    if (!s || !out || !groups) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    *out = nullptr;
+    FreqPrep prep;
+    arp_status st = freq_prepare(ctx, s, n_frames, xyz, groups, vdw_comp, dist_cutoff, flags, &prep);
+    if (st != ARP_OK || prep.checked_only) return st;
+    prep.job.residue = true;
+    prep.job.frame_bits = g_debug.freq_frame_bits > 0 ? (uint32_t)g_debug.freq_frame_bits : 0u;
+    FreqRowsHost rows;
+    if ((st = device_frequencies(ctx, prep.job, &rows)) != ARP_OK) return st;
+    *out = freq_table_residues(s, prep, rows).release();
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+// ---- contact timelines over frames (device pipeline: timeline.inl) ----------------------------------------------------
+extern "C" arp_status arp_contact_timelines(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
+                                            double dist_cutoff, uint32_t flags, int32_t level, arp_table **out) try {
+    if (!s || !out || !groups) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    *out = nullptr;
+    if (flags & ~(uint32_t)(ARP_FREQ_RINGS | ARP_TIMELINE_NO_BITMAP)) {
+        set_error("contact timelines: unknown flag bits 0x%x", flags & ~(uint32_t)(ARP_FREQ_RINGS | ARP_TIMELINE_NO_BITMAP));
+        return ARP_ERR_BAD_INPUT;
+    }
+    if (level != 0 && level != 1) { set_error("contact timelines: level must be 0 (atoms) or 1 (residues), got %d", (int)level); return ARP_ERR_BAD_INPUT; }
+    FreqPrep prep;
+    arp_status st = freq_prepare(ctx, s, n_frames, xyz, groups, vdw_comp, dist_cutoff, flags & ARP_FREQ_RINGS, &prep);
+    if (st != ARP_OK || prep.checked_only) return st;
+    if (level == 1) {
+        prep.job.residue = true;
+        prep.job.frame_bits = g_debug.freq_frame_bits > 0 ? (uint32_t)g_debug.freq_frame_bits : 0u;
+    }
+    const bool want_bitmap = !(flags & ARP_TIMELINE_NO_BITMAP);
+    const uint64_t cap = g_debug.timeline_cap_bytes > 0 ? (uint64_t)g_debug.timeline_cap_bytes : (1ull << 31);
+    FreqRowsHost rows;
+    TimelineHost tl;
+    if ((st = device_timelines(ctx, prep.job, want_bitmap, cap, &rows, &tl)) != ARP_OK) return st;
+    // the frequency columns are the frequency call's own (the same rows through the same table builder), the timeline columns join them
+    std::unique_ptr<arp_table> t = level == 1 ? freq_table_residues(s, prep, rows) : freq_table_atoms(s, prep, rows);
+    t->timeline = true;
+    t->tl_frames = prep.F;
+    t->tl_words_per_row = tl.words_per_row;
+    if (tl.has_bitmap) t->tl_words = std::move(tl.words);
+    else t->tl_words_per_row = 0;
+    t->first_frame = std::move(tl.first); t->last_frame = std::move(tl.last); t->n_events = std::move(tl.n_events); t->longest_run = std::move(tl.longest);
+    t->mean_run.resize(t->n);
+    for (uint64_t k = 0; k < t->n; k++) t->mean_run[k] = (float)((double)t->n_frames[k] / (double)t->n_events[k]);
     *out = t.release();
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+extern "C" const uint32_t *arp_table_timeline(const arp_table *t, uint64_t *words_per_row, uint64_t *n_frames) {
+    if (!t || !t->timeline || t->tl_words_per_row == 0) return nullptr;
+    if (words_per_row) *words_per_row = t->tl_words_per_row;
+    if (n_frames) *n_frames = t->tl_frames;
+    static const uint32_t no_rows = 0;
+    return t->tl_words.empty() ? &no_rows : t->tl_words.data();  // (a table without rows still has a bitmap: never NULL)
+}
+
+// The definition of the timeline statistics, bit by bit (no device): the yardstick of k_timeline_stats.
+extern "C" arp_status arp_timeline_stats(uint64_t rows, uint64_t n_frames, const uint32_t *words, uint32_t *n_present, uint32_t *first, uint32_t *last, uint32_t *n_events,
+                                         uint32_t *longest_run) try {
+    if ((rows && n_frames && !words) || (rows && (!n_present || !first || !last || !n_events || !longest_run))) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    if (n_frames > 0xFFFFFFF0ull) { set_error("timeline statistics: more than 2^32 frames"); return ARP_ERR_BAD_INPUT; }
+    const uint64_t W = (n_frames + 31u) / 32u;
+    for (uint64_t r = 0; r < rows; r++) {
+        uint32_t present = 0, f_first = ARP_NONE, f_last = ARP_NONE, events = 0, best = 0, run = 0;
+        for (uint64_t f = 0; f < n_frames; f++) {
+            if (words[r * W + (f >> 5)] >> (f & 31u) & 1u) {
+                if (!run) events++;
+                run++;
+                present++;
+                if (f_first == ARP_NONE) f_first = (uint32_t)f;
+                f_last = (uint32_t)f;
+                if (run > best) best = run;
+            } else run = 0;
+        }
+        n_present[r] = present; first[r] = f_first; last[r] = f_last; n_events[r] = events; longest_run[r] = best;
+    }
     return ARP_OK;
 } ARP_ABI_CATCH

@@ -98,6 +98,16 @@ struct FreqRowsHost {
 };
 arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost *out);
 
+// Contact timelines (timeline.inl, arp_contact_timelines): the frequency rows of the job (device_frequencies' own result)
+// and, per row, the bitmap of the frames that feed it (bit f & 31 of words[r * words_per_row + (f >> 5)]) with its statistics.  want_bitmap false:
+// the bitmap stays on the device (words empty).  cap_bytes: the most device memory the bitmap may take (ARP_ERR_CAPACITY beyond).
+struct TimelineHost {
+    uint64_t words_per_row = 0;
+    bool has_bitmap = false;
+    std::vector<uint32_t> words, first, last, n_events, longest;
+};
+arp_status device_timelines(arp_context *ctx, const FreqJob &job, bool want_bitmap, uint64_t cap_bytes, FreqRowsHost *rows, TimelineHost *out);
+
 // engine.cpp: the context's stream / device and grow-only scratch (device and pinned host)
 void *context_stream(arp_context *ctx);
 int context_device(arp_context *ctx);

@@ -947,5 +947,6 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
 
 #include "freq.inl"
 #include "freq_rings.inl"
+#include "timeline.inl"
 
 }  // namespace arp

@@ -162,6 +162,8 @@ typedef struct arp_table arp_table;         /* the 20-column contact table (mod.
  *                      tiny inputs reach the frame cap; 0 (default): automatic (17, fewer only beyond 2^21 residues)
  *   "ens_chunk_atoms" N > 0: arp_sasa_ensemble runs its frames in passes of N packed atoms (frames x selected atoms; whole frames, at least one per
  *                      pass), so that tests can force several passes; 0 (default): about 2 x 10^6 atoms per pass
+ *   "timeline_cap_bytes" N > 0: arp_contact_timelines refuses a device bitmap of more than N bytes (ARP_ERR_CAPACITY), so that tests reach the limit on
+ *                      tiny inputs; 0 (default): 2^31 bytes
  * Unknown keys return ARP_ERR_BAD_INPUT. */
 arp_status arp_debug_set(const char *key, int64_t value);
 int32_t arp_api_version(void);
@@ -505,6 +507,39 @@ arp_status arp_contact_frequencies_ex(arp_context *ctx, arp_structure *topology,
  * only gets smaller passes. */
 arp_status arp_residue_contact_frequencies(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
                                            double dist_cutoff, uint32_t flags, arp_table **out);
+
+/* ---- contact timelines over the frames of an ensemble: which frames, how many events, how long -- DESIGN.md section 3.13 ----
+ * Topology, n_frames, xyz, groups, vdw_comp and dist_cutoff exactly as arp_contact_frequencies_ex (level 0) or arp_residue_contact_frequencies
+ * (level 1) define them.  The rows are exactly the rows that call returns for the same arguments (flags & ARP_FREQ_RINGS), in its order, and the
+ * table serves every column of that frequency table with identical bytes.  On top of them, with F the number of frames:
+ *   present[r][f] = 1 iff frame f contributes at least one item to row r.  At atom level the item is (from entity, to entity, code); at residue level
+ *   it is any item whose entities map to (A, B, code) -- several items of one frame set the same bit.
+ * Per row, over f = 0 .. F - 1 (arp_table_column, all 4 bytes wide):
+ *   "first_frame" "last_frame" u32   the smallest / largest f with the bit set
+ *   "n_events" u32                   the number of maximal runs of consecutive set bits
+ *   "longest_run" u32                the length of the longest such run, in frames
+ *   "mean_run" f32                   f32((double)n_frames / n_events)
+ * The bitmap itself (arp_table_timeline): words[r][w] u32, W = ceil(F / 32) words per row, row-major; frame f is bit f & 31 of word f >> 5; the unused
+ * high bits of a row's last word are zero.  The popcount of a row equals the row's "n_frames"; should it ever not, the call fails with ARP_ERR_HIP and
+ * an "internal error" message instead of returning a table.
+ * arp_table_export_arrow appends the five columns behind the frequency columns of the level; the bitmap is not part of the Arrow batch.
+ * flags: ARP_FREQ_RINGS (the ring rows, as in the frequency calls) and ARP_TIMELINE_NO_BITMAP (the statistics are computed, the bitmap is not copied to the
+ * host: arp_table_timeline returns NULL); any other bit, or a level outside {0, 1}, is ARP_ERR_BAD_INPUT.  Every check, status and message of the frequency
+ * calls runs before the device is touched; ctx == NULL runs only the checks (ARP_OK, *out = NULL).
+ * Device memory: the frequency call's, plus rows x W x 4 bytes for the bitmap.  A bitmap above 2^31 bytes (arp_debug_set "timeline_cap_bytes") is
+ * ARP_ERR_CAPACITY, with a message that names rows, frames and bytes.  The bytes do not depend on the pass size or on the order in which the device
+ * produced pairs or ran atomics: two calls give identical bytes.  Synchronous; the frames cross the device twice (rows, then marks). */
+#define ARP_TIMELINE_NO_BITMAP 0x2u
+arp_status arp_contact_timelines(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
+                                 double dist_cutoff, uint32_t flags, int32_t level, arp_table **out);
+/* The host bitmap of a timeline table (owned by the table): *words_per_row = W, *n_frames = F (both nullable).  NULL for every other table and for a
+ * table built with ARP_TIMELINE_NO_BITMAP. */
+const uint32_t *arp_table_timeline(const arp_table *t, uint64_t *words_per_row, uint64_t *n_frames);
+/* The definition above on its own (no device), a plain loop over the bits of `rows` rows of ceil(n_frames / 32) words: n_present = the popcount over
+ * frames 0 .. n_frames - 1 (bits past n_frames are ignored), first / last, n_events, longest_run as above; a row without any set bit gets first = last =
+ * ARP_NONE and zeros.  For anyone who post-processes a bitmap (a frame window, an AND of two rows), and the yardstick of the device kernel. */
+arp_status arp_timeline_stats(uint64_t rows, uint64_t n_frames, const uint32_t *words, uint32_t *n_present, uint32_t *first, uint32_t *last, uint32_t *n_events,
+                              uint32_t *longest_run);
 
 /* ---- SASA and SAP statistics over the frames of an ensemble (MD snapshots, NMR models, conformers of one topology) -- DESIGN.md section 3.8 ----
  * Topology, N, frames and xyz exactly as arp_contact_frequencies defines them: model 0 of `topology` is the topology, frame f is xyz[f]
