@@ -7,6 +7,8 @@
 residue pair and interaction (a model counts once however many of the residues' atoms are in contact).
 `contact-timeline` (no counterpart either) takes the flags of `contact-frequency` and writes its table with five more columns per row -- first_frame,
 last_frame, n_events, longest_run, mean_run: when the contact exists across the models -- and, with --bitmap FILE.npy, the rows' frame bitmap.
+`contact-similarity` (no counterpart either) takes the flags of `contact-timeline` without --bitmap, plus --axis frames|rows and --metric tanimoto|count:
+it writes `contact-frequency`'s table and, with --matrix FILE.npy, the matrix between the models (or between the rows).
 `sasa-ensemble` and `sap-ensemble` (no counterpart either) take the flags and defaults of `sasa` / `sap` without --model: statistics over the models.
 `dsasa --level atom|residue` writes the interface row by row (default `total`: the reference's scalar); `dsasa-ensemble` takes the flags of
 `sasa-ensemble` and -g: dSASA per model and the per-atom statistics of the buried surface.
@@ -67,6 +69,22 @@ def build_parser() -> argparse.ArgumentParser:
                     help="Rows per atom pair, or per residue pair (a model counts once however many of the residues' atoms are in contact)")
     tl.add_argument("--bitmap", default=None, type=Path, metavar="FILE.npy",
                     help="Also write the rows' frame bitmap: uint32 [rows, ceil(models / 32)], model f = bit f %% 32 of word f // 32")
+    sm = sub.add_parser("contact-similarity", help="which models have the same contacts (Tanimoto matrix), or which contacts exist in the same models")
+    sm.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file whose models are the frames")
+    sm.add_argument("-o", "--output", required=True, type=Path, help="Output directory")
+    sm.add_argument("-g", "--groups", default="/", help="Chain groups, e.g. A,B/C,D ('/' = all against all)")
+    sm.add_argument("-f", "--filename", default="contact_similarity", help="Name of the output file")
+    sm.add_argument("-t", "--output-format", default="csv", type=str.lower, choices=FORMATS, help="Output file type")
+    sm.add_argument("-c", "--vdw-comp", default=0.1, type=float, help="Compensation factor for VdW radii dependent interaction types")
+    sm.add_argument("-d", "--dist-cutoff", default=6.5, type=float, help="Distance cutoff when searching for neighboring atoms")
+    sm.add_argument("-j", "--num-threads", default=1, type=int, help="Number of threads (accepted; the computation runs on the GPU)")
+    sm.add_argument("--ignore-zero-occupancy", action="store_true", help="Ignore atoms with zero occupancy")
+    sm.add_argument("--rings", action="store_true", help="Add the ring rows (CationPi, Pi stackings) of every model; ring-ring rows do not depend on --dist-cutoff")
+    sm.add_argument("-l", "--level", default="atom", choices=("atom", "residue"),
+                    help="Rows per atom pair, or per residue pair (a model counts once however many of the residues' atoms are in contact)")
+    sm.add_argument("--axis", default="frames", choices=("frames", "rows"), help="Compare the models with each other (frames), or the table's rows (rows)")
+    sm.add_argument("--metric", default="tanimoto", choices=("tanimoto", "count"), help="Tanimoto coefficient (float32), or the size of the intersection (uint32)")
+    sm.add_argument("--matrix", default=None, type=Path, metavar="FILE.npy", help="Write the [M, M] matrix: M = models (--axis frames) or rows of the table (--axis rows)")
     common = dict(model=("-m", "--model", 0, int, "Model number to analyze (0: the first model)"),
                   probe=("-r", "--probe-radius", 1.4, float, "Probe radius in Angstroms"),
                   points=("-n", "--num-points", 100, int, "Number of points for surface calculation"),
@@ -346,6 +364,32 @@ def run_contact_timeline(args) -> int:
     return 0
 
 
+def run_contact_similarity(args) -> int:
+    import numpy as np
+
+    import arpeggia_amd as aa
+    from arpeggia_amd import api
+
+    if not args.input.exists():
+        log.error("Failed to retrieve input file: %s", args.input)
+        return 1
+    try:
+        table, matrix = api._contact_similarity_arrow(str(args.input.resolve()), args.groups, args.vdw_comp, args.dist_cutoff, args.ignore_zero_occupancy, args.rings,
+                                                      args.level, args.axis, args.metric)
+    except aa.ArpeggiaError as e:
+        log.error("Contact similarity failed: %s", e)
+        return 1
+    args.output.mkdir(parents=True, exist_ok=True)
+    out = (args.output / args.filename).with_suffix("." + args.output_format)
+    write_table(table, out, args.output_format)
+    if args.matrix is not None:
+        args.matrix.parent.mkdir(parents=True, exist_ok=True)
+        with open(args.matrix, "wb") as f:  # (np.save on a name would append .npy to any other suffix)
+            np.save(f, matrix)
+    log.info("Results for %d contacts saved to %s", len(table), out)
+    return 0
+
+
 def main(argv=None) -> int:
     logging.basicConfig(level=logging.INFO, format="%(levelname)s %(message)s", stream=sys.stderr)
     args = build_parser().parse_args(argv)
@@ -357,6 +401,8 @@ def main(argv=None) -> int:
         return run_contact_frequency(args)
     if args.command == "contact-timeline":
         return run_contact_timeline(args)
+    if args.command == "contact-similarity":
+        return run_contact_similarity(args)
     return run_contacts(args) if args.command == "contacts" else run_surface(args)
 
 

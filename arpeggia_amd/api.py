@@ -86,7 +86,7 @@ def default_params(vdw_comp: float = 0.1, dist_cutoff: float = 6.5, deterministi
 
 
 def debug_set(key: str, value: int):
-    """arp_debug_set: the library's diagnostic switches ("timing", "emit_kernel", "defer_entries", "table_host", "freq_chunk_atoms", "freq_cap_items", "freq_frame_bits", "timeline_cap_bytes", ...; include/arpeggia_amd.h)."""
+    """arp_debug_set: the library's diagnostic switches ("timing", "emit_kernel", "defer_entries", "table_host", "freq_chunk_atoms", "freq_cap_items", "freq_frame_bits", "timeline_cap_bytes", "similarity_cap_bytes", ...; include/arpeggia_amd.h)."""
     _check(lib.arp_debug_set(key.encode(), int(value)))
 
 
@@ -388,6 +388,15 @@ class Context:
         finally:
             lib.arp_table_free(t)
 
+    def contact_similarity(self, structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, rings: bool = False,
+                           level: str = "atom", axis: str = "frames", metric: str = "tanimoto") -> dict:
+        """arp_contact_similarity as a dict: every column contact_frequencies returns for the same arguments (identical bytes), plus the [M, M] matrix
+        between the frames (axis "frames", M = F: which frames have the same contacts) or between the rows (axis "rows", M = rows: which contacts exist
+        in the same frames) -- `similarity` <f4 (metric "tanimoto": |a AND b| / |a OR b|, 1.0 for two empty sets) or `intersection` <u4 (metric
+        "count": |a AND b|) -- and `sizes` [M] <u4 (contacts per frame, or frames per row), `axis` and `n_total_frames` = F."""
+        owner = _TableOwner(_similarity_table(self, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, axis, metric))
+        return _similarity_columns(owner, rings, level, structure, frames)  # (a large matrix is a view of the table's: the table lives as long as it)
+
     def sasa_ensemble(self, structure: Structure, frames=None, chains: str = "", probe_radius: float = 1.4, n_points: int = 100, sap_radius: float | None = None,
                       per_frame: bool = False, radii=None) -> dict:
         """arp_sasa_ensemble as a dict of numpy arrays: per-atom SASA statistics over the frames of an ensemble, and SAP statistics when
@@ -526,6 +535,96 @@ def timeline_stats(words, n_frames: int) -> dict:
     src = words if words.size else np.zeros(1, "<u4")
     _check(lib.arp_timeline_stats(rows, int(n_frames), src.ctypes.data_as(u32p), *[(v if rows else np.zeros(1, "<u4")).ctypes.data_as(u32p) for v in out.values()]))
     return out
+
+
+def _similarity_flags(axis: str, metric: str) -> int:
+    if axis not in ("frames", "rows"):
+        raise ValueError(f"axis must be 'frames' or 'rows', got {axis!r}")
+    if metric not in ("tanimoto", "count"):
+        raise ValueError(f"metric must be 'tanimoto' or 'count', got {metric!r}")
+    return (_lib.ARP_SIM_ROWS if axis == "rows" else 0) | (_lib.ARP_SIM_COUNTS if metric == "count" else 0)
+
+
+def _similarity_table(ctx: "Context | None", structure: Structure, frames, groups: str, vdw_comp: float, dist_cutoff: float, rings: bool, level: str, axis: str,
+                      metric: str):
+    """arp_contact_similarity -> table handle (the caller frees it).  ctx None: the inputs are only checked (raises their error, else returns None)."""
+    if level not in ("atom", "residue"):
+        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
+    flags = _similarity_flags(axis, metric) | (_lib.ARP_FREQ_RINGS if rings else 0)
+    n_frames, ptr, keep = _frames_arg(structure, frames, "contact similarity")
+    t = C.c_void_p()
+    _check(lib.arp_contact_similarity(ctx._h if ctx is not None else None, structure._h, int(n_frames), ptr, groups.encode(), float(vdw_comp), float(dist_cutoff),
+                                      flags, 1 if level == "residue" else 0, C.byref(t)))
+    return t if ctx is not None else None
+
+
+class _TableOwner:
+    """Keeps a table handle alive for a numpy view into it; frees it with the last reference."""
+
+    def __init__(self, handle):
+        self.t = handle
+
+    def __del__(self):
+        if self.t is not None and lib is not None:
+            lib.arp_table_free(self.t)
+            self.t = None
+
+
+def _similarity_matrix(owner: _TableOwner) -> dict:
+    """similarity / intersection, sizes and axis of a similarity table.  A matrix of 1 MiB and more is a zero-copy view that keeps the table alive (at
+    10^4 frames it is 400 MB: a copy would cost more than the kernels); everything else is copied."""
+    m, flags, sizes = C.c_uint64(), C.c_uint32(), C.POINTER(C.c_uint32)()
+    p = lib.arp_table_similarity(owner.t, C.byref(m), C.byref(flags), C.byref(sizes))
+    if not p:
+        raise KeyError("similarity")
+    M = int(m.value)
+    counts = bool(flags.value & _lib.ARP_SIM_COUNTS)
+    dtype = "<u4" if counts else "<f4"
+    if M * M * 4 >= 1 << 20:
+        buf = (C.c_char * (M * M * 4)).from_address(p)
+        buf._owner = owner  # the ctypes buffer is the array's base: the table lives exactly as long as the array (and its views)
+        matrix = np.frombuffer(buf, dtype=dtype, count=M * M).reshape(M, M)
+    else:
+        matrix = _np_from(p, M * M, dtype).reshape(M, M)
+    out = {"intersection" if counts else "similarity": matrix}
+    out["sizes"] = _np_from(C.cast(sizes, C.c_void_p).value, M, "<u4")
+    out["axis"] = "rows" if flags.value & _lib.ARP_SIM_ROWS else "frames"
+    return out
+
+
+def _similarity_columns(owner: _TableOwner, rings: bool, level: str, structure: Structure, frames) -> dict:
+    cols = _freq_columns(owner.t, rings, level)
+    cols.update(_similarity_matrix(owner))
+    if frames is not None:
+        cols["n_total_frames"] = int(np.asarray(frames).shape[0])
+    else:
+        cols["n_total_frames"] = len(structure.ints("model")) // max(_topology_atoms(structure), 1)
+    return cols
+
+
+def bit_gram(words, n_bits: int, axis: str = "frames", metric: str = "tanimoto", device: int | None = None) -> tuple:
+    """(matrix, sizes) of a bitmap of the timeline_words layout, [rows, ceil(n_bits / 32)] <u4: the Tanimoto values (<f4) or intersection counts (<u4,
+    metric "count") between its bit columns (axis "frames": M = n_bits) or its rows (axis "rows": M = rows), and the M set sizes (<u4) -- the
+    definitions of Context.contact_similarity.  Bits past n_bits are ignored.  device None: arp_bit_gram_host, a plain loop on the CPU (the yardstick);
+    a device number: arp_bit_gram, the same kernels contact_similarity runs.  For bitmaps that were post-processed on the host (a frame window, a
+    subset of rows)."""
+    flags = _similarity_flags(axis, metric)
+    words = np.ascontiguousarray(words, dtype="<u4")
+    W = (int(n_bits) + 31) // 32
+    if words.ndim != 2 or words.shape[1] != W:
+        raise ValueError(f"words must have shape [rows, {W}] for {n_bits} bits, got {list(words.shape)}")
+    rows = words.shape[0]
+    M = rows if axis == "rows" else int(n_bits)
+    out = np.zeros((M, M), "<u4" if metric == "count" else "<f4")
+    sizes = np.zeros(M, "<u4")
+    u32p = C.POINTER(C.c_uint32)
+    ptr = lambda a: (a if a.size else np.zeros(1, a.dtype)).ctypes
+    args = (rows, int(n_bits), ptr(words).data_as(u32p), flags, ptr(out).data_as(C.c_void_p), ptr(sizes).data_as(u32p))
+    if device is None:
+        _check(lib.arp_bit_gram_host(*args))
+    else:
+        _check(lib.arp_bit_gram(_context(int(device))._h, *args))
+    return out, sizes
 
 
 def _frames_arg(structure: Structure, frames, what: str):
@@ -827,6 +926,50 @@ def contact_timelines(input_file: str, groups: str = "/", vdw_comp: float = 0.1,
     if level not in ("atom", "residue"):
         raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
     return get_contact_timelines(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings, level=level, bitmap=bitmap)
+
+
+def get_contact_similarity(structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, device: int = 0,
+                           rings: bool = False, level: str = "atom", axis: str = "frames", metric: str = "tanimoto") -> dict:
+    """Which frames of an ensemble look alike, which contacts come and go together (arp_contact_similarity): the rows of get_contact_frequencies for
+    the same arguments as a dict of numpy columns, identical bytes, plus the [M, M] matrix of the per-frame contact fingerprints (axis "frames", M =
+    F) or of the rows' frame sets (axis "rows", M = rows): `similarity` <f4 (metric "tanimoto") or `intersection` <u4 (metric "count"), with `sizes`
+    [M] <u4, `axis` and `n_total_frames`.  frames, groups, rings and level as get_contact_frequencies."""
+    if level not in ("atom", "residue"):
+        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
+    _similarity_flags(axis, metric)
+    try:
+        ctx = _context(device)
+    except ArpeggiaError:
+        _similarity_table(None, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, axis, metric)  # an input error takes precedence over the missing device
+        raise
+    return ctx.contact_similarity(structure, frames, groups, vdw_comp, dist_cutoff, rings, level, axis, metric)
+
+
+def contact_similarity(input_file: str, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, ignore_zero_occupancy: bool = False,
+                       rings: bool = False, level: str = "atom", axis: str = "frames", metric: str = "tanimoto") -> dict:
+    """Contact similarity across the models of a multi-model file (the models are the frames): see get_contact_similarity."""
+    if level not in ("atom", "residue"):
+        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
+    _similarity_flags(axis, metric)
+    return get_contact_similarity(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings, level=level, axis=axis, metric=metric)
+
+
+def _contact_similarity_arrow(input_file: str, groups: str, vdw_comp: float, dist_cutoff: float, ignore_zero_occupancy: bool, rings: bool, level: str, axis: str,
+                              metric: str):
+    """The command line's form of contact_similarity: (Arrow table of the frequency columns, the matrix)."""
+    import pyarrow as pa
+
+    structure = Structure.load(input_file, ignore_zero_occupancy)
+    try:
+        ctx = _context(0)
+    except ArpeggiaError:
+        _similarity_table(None, structure, None, groups, vdw_comp, dist_cutoff, rings, level, axis, metric)
+        raise
+    owner = _TableOwner(_similarity_table(ctx, structure, None, groups, vdw_comp, dist_cutoff, rings, level, axis, metric))
+    arr, sch = _lib.ArrowArray(), _lib.ArrowSchema()
+    _check(lib.arp_table_export_arrow(owner.t, C.byref(arr), C.byref(sch)))
+    table = pa.Table.from_batches([pa.RecordBatch._import_from_c(C.addressof(arr), C.addressof(sch))])
+    return table, _similarity_matrix(owner)["intersection" if metric == "count" else "similarity"]
 
 
 def _contact_timelines_arrow(input_file: str, groups: str, vdw_comp: float, dist_cutoff: float, ignore_zero_occupancy: bool, rings: bool, level: str, bitmap: bool):

@@ -15,6 +15,7 @@ struct DebugKnobs {
     long freq_frame_bits;   // > 0: frame-tag bits of the keys of arp_residue_contact_frequencies (at most 2^k - 1 frames per pass; tests: tiny inputs reach the frame cap); 0: automatic (freq.inl)
     long ens_chunk_atoms;   // > 0: packed atoms per pass of arp_sasa_ensemble (whole frames, at least one); 0: automatic (sasa_dev.cpp kEnsAutoAtoms)
     long long timeline_cap_bytes;  // > 0: the most device memory the bitmap of arp_contact_timelines may take (tests: the capacity error on tiny inputs); 0: 2^31 bytes
+    long long similarity_cap_bytes;  // > 0: the most bytes the matrix of arp_contact_similarity / arp_bit_gram may take (tests: the capacity error on tiny inputs); 0: 2^31 bytes
 };
 extern DebugKnobs g_debug;
 

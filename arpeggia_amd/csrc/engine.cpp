@@ -660,7 +660,7 @@ extern "C" int32_t arp_profile_read(arp_context *ctx, const char **names, float 
 }
 
 // ---- library-level -----------------------------------------------------------------------------------------------
-namespace arp { DebugKnobs g_debug{0, 0, 0, 0, 0, 0, 0, 0, 0}; }
+namespace arp { DebugKnobs g_debug{}; }
 extern "C" uint64_t arp_pair_rare_batches(const arp_context *ctx) { return (ctx && ctx->h_result) ? ctx->h_result[kResRare] : 0u; }
 
 extern "C" arp_status arp_debug_set(const char *key, int64_t value) {
@@ -690,6 +690,10 @@ extern "C" arp_status arp_debug_set(const char *key, int64_t value) {
         if (value < 0) { set_error("arp_debug_set: timeline_cap_bytes takes 0 (2^31 bytes) or a positive byte count"); return ARP_ERR_BAD_INPUT; }
         g_debug.timeline_cap_bytes = (long long)value;
     }
+    else if (k == "similarity_cap_bytes") {
+        if (value < 0) { set_error("arp_debug_set: similarity_cap_bytes takes 0 (2^31 bytes) or a positive byte count"); return ARP_ERR_BAD_INPUT; }
+        g_debug.similarity_cap_bytes = (long long)value;
+    }
     else if (k == "index_bits") {
         if (value > (int64_t)kNarrowMaxBits) { set_error("arp_debug_set: index_bits takes 0 (automatic), 1 .. 20 (the index width of the narrow exact record) or a negative value (the wide record always)"); return ARP_ERR_BAD_INPUT; }
         g_debug.index_bits = (int)value;
@@ -698,7 +702,7 @@ extern "C" arp_status arp_debug_set(const char *key, int64_t value) {
         if (value < 0 || value > 1024 || (value & (value - 1)) != 0) { set_error("arp_debug_set: strip_rows takes 0 or a power of two up to 1024"); return ARP_ERR_BAD_INPUT; }
         g_debug.strip_rows = (int)value;
     }
-    else { set_error("arp_debug_set: unknown key '%s' (timing, emit_kernel, defer_entries, strip_rows, index_bits, table_host, freq_chunk_atoms, freq_cap_items, freq_frame_bits, ens_chunk_atoms, timeline_cap_bytes)", key); return ARP_ERR_BAD_INPUT; }
+    else { set_error("arp_debug_set: unknown key '%s' (timing, emit_kernel, defer_entries, strip_rows, index_bits, table_host, freq_chunk_atoms, freq_cap_items, freq_frame_bits, ens_chunk_atoms, timeline_cap_bytes, similarity_cap_bytes)", key); return ARP_ERR_BAD_INPUT; }
     return ARP_OK;
 }
 extern "C" int32_t arp_api_version(void) { return ARP_API_VERSION; }

@@ -305,6 +305,14 @@ struct arp_table {
     uint64_t tl_words_per_row = 0, tl_frames = 0;
     std::vector<uint32_t> tl_words, first_frame, last_frame, n_events, longest_run;
     std::vector<float> mean_run;
+    // contact-similarity table (arp_contact_similarity): a frequency table of either level that owns the m x m matrix between frames or rows
+    // (arp_table_similarity); the matrix is not a column
+    bool similarity = false;
+    uint64_t sim_m = 0;
+    uint32_t sim_flags = 0;
+    std::shared_ptr<char> sim_owner;           // (the matrix's block: SimilarityHost::owner)
+    const uint32_t *sim_matrix = nullptr;
+    std::vector<uint32_t> sim_sizes;
 };
 
 namespace {
@@ -1412,4 +1420,97 @@ extern "C" arp_status arp_timeline_stats(uint64_t rows, uint64_t n_frames, const
         n_present[r] = present; first[r] = f_first; last[r] = f_last; n_events[r] = events; longest_run[r] = best;
     }
     return ARP_OK;
+} ARP_ABI_CATCH
+
+// ---- contact similarity between frames, contact co-occurrence between rows (device pipeline: similarity.inl) ----------------
+extern "C" arp_status arp_contact_similarity(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
+                                             double dist_cutoff, uint32_t flags, int32_t level, arp_table **out) try {
+    if (!s || !out || !groups) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    *out = nullptr;
+    if (flags & ~(uint32_t)(ARP_FREQ_RINGS | ARP_SIM_COUNTS | ARP_SIM_ROWS)) {
+        set_error("contact similarity: unknown flag bits 0x%x", flags & ~(uint32_t)(ARP_FREQ_RINGS | ARP_SIM_COUNTS | ARP_SIM_ROWS));
+        return ARP_ERR_BAD_INPUT;
+    }
+    if (level != 0 && level != 1) { set_error("contact similarity: level must be 0 (atoms) or 1 (residues), got %d", (int)level); return ARP_ERR_BAD_INPUT; }
+    FreqPrep prep;
+    arp_status st = freq_prepare(ctx, s, n_frames, xyz, groups, vdw_comp, dist_cutoff, flags & ARP_FREQ_RINGS, &prep);
+    if (st != ARP_OK || prep.checked_only) return st;
+    if (level == 1) {
+        prep.job.residue = true;
+        prep.job.frame_bits = g_debug.freq_frame_bits > 0 ? (uint32_t)g_debug.freq_frame_bits : 0u;
+    }
+    const uint64_t tl_cap = g_debug.timeline_cap_bytes > 0 ? (uint64_t)g_debug.timeline_cap_bytes : (1ull << 31);
+    const uint64_t cap = g_debug.similarity_cap_bytes > 0 ? (uint64_t)g_debug.similarity_cap_bytes : (1ull << 31);
+    FreqRowsHost rows;
+    SimilarityHost sim;
+    if ((st = device_similarity(ctx, prep.job, (flags & ARP_SIM_ROWS) != 0, (flags & ARP_SIM_COUNTS) != 0, tl_cap, cap, &rows, &sim)) != ARP_OK) return st;
+    // the table is the frequency table of the level (the same rows through the same table builder); the matrix rides along
+    std::unique_ptr<arp_table> t = level == 1 ? freq_table_residues(s, prep, rows) : freq_table_atoms(s, prep, rows);
+    t->similarity = true;
+    t->sim_m = sim.m;
+    t->sim_flags = flags & (uint32_t)(ARP_SIM_COUNTS | ARP_SIM_ROWS);
+    t->sim_owner = std::move(sim.owner);
+    t->sim_matrix = sim.matrix;
+    t->sim_sizes = std::move(sim.sizes);
+    *out = t.release();
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+extern "C" const void *arp_table_similarity(const arp_table *t, uint64_t *m, uint32_t *flags, const uint32_t **sizes) {
+    if (!t || !t->similarity) return nullptr;
+    if (m) *m = t->sim_m;
+    if (flags) *flags = t->sim_flags;
+    static const uint32_t nothing = 0;
+    if (sizes) *sizes = t->sim_sizes.empty() ? &nothing : t->sim_sizes.data();
+    return t->sim_matrix ? (const void *)t->sim_matrix : (const void *)&nothing;  // (an empty matrix is still a matrix: never NULL)
+}
+
+namespace {
+arp_status bit_gram_args(uint64_t rows, uint64_t n_bits, const uint32_t *words, uint32_t flags, const void *out, const uint32_t *sizes) {
+    if (flags & ~(uint32_t)(ARP_SIM_COUNTS | ARP_SIM_ROWS)) { set_error("bit gram: unknown flag bits 0x%x", flags & ~(uint32_t)(ARP_SIM_COUNTS | ARP_SIM_ROWS)); return ARP_ERR_BAD_INPUT; }
+    if (n_bits >= (1ull << 32) || rows >= (1ull << 32)) { set_error("bit gram: 2^32 or more %s (the counts are u32)", n_bits >= (1ull << 32) ? "bits" : "rows"); return ARP_ERR_BAD_INPUT; }
+    const uint64_t M = (flags & ARP_SIM_ROWS) ? rows : n_bits;
+    if (rows && ((n_bits && !words) || (M && (!out || !sizes)))) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    return ARP_OK;
+}
+}  // namespace
+
+// The definition of the matrix on its own (no device): the yardstick of k_bit_transpose / k_bit_sizes / k_bit_gram.  Every bit is looked at one by one
+// and filed under its set (a frame's set of rows, or a row's set of frames); |a AND b| is then counted over the sets' words.
+extern "C" arp_status arp_bit_gram_host(uint64_t rows, uint64_t n_bits, const uint32_t *words, uint32_t flags, void *out, uint32_t *sizes) try {
+    arp_status st = bit_gram_args(rows, n_bits, words, flags, out, sizes);
+    if (st != ARP_OK) return st;
+    const bool by_rows = (flags & ARP_SIM_ROWS) != 0, counts = (flags & ARP_SIM_COUNTS) != 0;
+    const uint64_t W = (n_bits + 31u) / 32u, M = by_rows ? rows : n_bits, N = by_rows ? n_bits : rows, K = (N + 31u) / 32u;
+    if (!rows && (by_rows || !out || !sizes)) return ARP_OK;  // (the frames of a bitmap without rows are n_bits empty sets)
+    std::vector<uint32_t> sets(M * K, 0u);
+    for (uint64_t r = 0; r < rows; r++)
+        for (uint64_t f = 0; f < n_bits; f++)
+            if (words[r * W + (f >> 5)] >> (f & 31u) & 1u) {
+                const uint64_t a = by_rows ? r : f, e = by_rows ? f : r;
+                sets[a * K + (e >> 5)] |= 1u << (e & 31u);
+            }
+    for (uint64_t a = 0; a < M; a++) {
+        uint32_t c = 0;
+        for (uint64_t w = 0; w < K; w++) c += (uint32_t)__builtin_popcount(sets[a * K + w]);
+        sizes[a] = c;
+    }
+    for (uint64_t a = 0; a < M; a++)
+        for (uint64_t b = 0; b < M; b++) {
+            uint32_t inter = 0;
+            for (uint64_t w = 0; w < K; w++) inter += (uint32_t)__builtin_popcount(sets[a * K + w] & sets[b * K + w]);
+            if (counts) { ((uint32_t *)out)[a * M + b] = inter; continue; }
+            const uint64_t uni = (uint64_t)sizes[a] + sizes[b] - inter;
+            ((float *)out)[a * M + b] = uni ? (float)((double)inter / (double)uni) : 1.0f;
+        }
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+extern "C" arp_status arp_bit_gram(arp_context *ctx, uint64_t rows, uint64_t n_bits, const uint32_t *words, uint32_t flags, void *out, uint32_t *sizes) try {
+    if (!ctx) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    arp_status st = bit_gram_args(rows, n_bits, words, flags, out, sizes);
+    if (st != ARP_OK) return st;
+    if (!rows || !n_bits) return arp_bit_gram_host(rows, n_bits, words, flags, out, sizes);  // (no bit to look at: every set is empty)
+    const uint64_t cap = g_debug.similarity_cap_bytes > 0 ? (uint64_t)g_debug.similarity_cap_bytes : (1ull << 31);
+    return device_bit_gram(ctx, rows, n_bits, words, (flags & ARP_SIM_ROWS) != 0, (flags & ARP_SIM_COUNTS) != 0, cap, out, sizes);
 } ARP_ABI_CATCH

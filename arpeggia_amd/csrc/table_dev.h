@@ -108,6 +108,20 @@ struct TimelineHost {
 };
 arp_status device_timelines(arp_context *ctx, const FreqJob &job, bool want_bitmap, uint64_t cap_bytes, FreqRowsHost *rows, TimelineHost *out);
 
+// Contact similarity (similarity.inl, arp_contact_similarity / arp_bit_gram): the frequency rows of the job and the Gram matrix of
+// its timeline bitmap -- between frames (m = F) or, by_rows, between rows (m = R) -- as u32 counts or as the bits of f32 Tanimoto values, with the
+// set sizes.  The bitmap never leaves the device.  cap_bytes: the most the matrix may take (ARP_ERR_CAPACITY beyond); timeline_cap_bytes: the bitmap's.
+struct SimilarityHost {
+    uint64_t m = 0;
+    std::shared_ptr<char> owner;         // the block the matrix lives in: pooled pinned memory (batch.cpp pinned_block) from 1 MiB on, the heap below
+    uint32_t *matrix = nullptr;          // m x m, row-major
+    std::vector<uint32_t> sizes;
+};
+arp_status device_similarity(arp_context *ctx, const FreqJob &job, bool by_rows, bool counts, uint64_t timeline_cap_bytes, uint64_t cap_bytes, FreqRowsHost *rows,
+                             SimilarityHost *out);
+// the same kernels on a host bitmap of `rows` rows of ceil(n_bits / 32) words (rows > 0, n_bits > 0): out m x m, sizes m
+arp_status device_bit_gram(arp_context *ctx, uint64_t rows, uint64_t n_bits, const uint32_t *words, bool by_rows, bool counts, uint64_t cap_bytes, void *out, uint32_t *sizes);
+
 // engine.cpp: the context's stream / device and grow-only scratch (device and pinned host)
 void *context_stream(arp_context *ctx);
 int context_device(arp_context *ctx);

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 
 #include "arp_internal.h"
@@ -948,5 +949,6 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
 #include "freq.inl"
 #include "freq_rings.inl"
 #include "timeline.inl"
+#include "similarity.inl"
 
 }  // namespace arp

@@ -191,6 +191,58 @@ arp_status timeline_mark_pass(hipStream_t st, TimelineMarks *mk, const FreqPassV
     return ARP_OK;
 }
 
+// The device block of a timeline: the row keys, the bitmap, the five per-row results of k_timeline_stats and the error word of the marks.  It lives as
+// long as this object, so that a follower (similarity.inl) can go on from the bitmap.  block == nullptr: the job has no rows.
+struct TimelineDev {
+    std::unique_ptr<char, void (*)(char *)> block{nullptr, [](char *p) { (void)hipFree(p); }};
+    unsigned long long *row_keys = nullptr;
+    uint32_t *words = nullptr, *stat[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *err = nullptr;
+};
+
+// rows sweep, marks sweep, statistics: everything of a timeline up to its download.  lap is called after "rows", "marks" and "stats"; after_rows (nullable)
+// sees the number of rows before anything is allocated and may refuse the job.
+arp_status timeline_device(arp_context *ctx, const FreqJob &job, uint64_t cap_bytes, FreqRowsHost *rows, TimelineDev *dev, const std::function<void(const char *)> &lap,
+                           const std::function<arp_status(uint64_t)> &after_rows) {
+    hipStream_t st = (hipStream_t)context_stream(ctx);
+    // 1. rows: the frequency table as the frequency call computes it
+    arp_status s = device_frequencies(ctx, job, rows);
+    if (s != ARP_OK) return s;
+    lap("rows");
+    const uint64_t R = rows->key.size(), F = job.n_frames, W = (F + 31u) / 32u;
+    if (after_rows && (s = after_rows(R)) != ARP_OK) return s;
+    if (R == 0) return ARP_OK;
+    if (F > 0xFFFFFFF0ull) { set_error("contact timelines: more than 2^32 frames"); return ARP_ERR_BAD_INPUT; }
+    const uint64_t need = R * W * 4u;
+    if (need > cap_bytes) {
+        set_error("contact timelines: the bitmap of %llu rows x %llu frames needs %llu bytes of device memory, the limit is %llu (timeline_cap_bytes)", (unsigned long long)R,
+                  (unsigned long long)F, (unsigned long long)need, (unsigned long long)cap_bytes);
+        return ARP_ERR_CAPACITY;
+    }
+    // 2. marks: the row keys back on the device, the zeroed bitmap, the five per-row results, the error word
+    char *block = nullptr;
+    HIP_TRY(hipMalloc((void **)&block, seg_align(R * 8) + seg_align(need) + 5 * seg_align(R * 4) + seg_align(256)));
+    dev->block.reset(block);
+    Bump bp{block};
+    dev->row_keys = bp.take<unsigned long long>(R);
+    dev->words = bp.take<uint32_t>(R * W);
+    for (uint32_t *&p : dev->stat) p = bp.take<uint32_t>(R);
+    dev->err = bp.take<uint32_t>(64);
+    HIP_TRY(hipMemcpyAsync(dev->row_keys, rows->key.data(), R * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(dev->words, 0, need, st));
+    HIP_TRY(hipMemsetAsync(dev->err, 0, 4, st));
+    TimelineMarks mk{dev->row_keys, (uint32_t)R, (uint32_t)F, dev->words, W, dev->err};
+    struct FreeItems { TimelineMarks *m; ~FreeItems() { if (m->items) (void)hipFree(m->items); } } items_owner{&mk};
+    FreqRowsHost none;
+    if ((s = freq_sweep(ctx, job, &none, &mk)) != ARP_OK) return s;
+    lap("marks");
+    // 3. statistics: one wave per row
+    hipLaunchKernelGGL(k_timeline_stats, dim3((uint32_t)((R + 3u) / 4u)), dim3(256), 0, st, (uint32_t)R, W, (const uint32_t *)dev->words, dev->stat[0], dev->stat[1], dev->stat[2],
+                       dev->stat[3], dev->stat[4]);
+    HIP_TRY(hipGetLastError());
+    lap("stats");
+    return ARP_OK;
+}
+
 arp_status device_timelines(arp_context *ctx, const FreqJob &job, bool want_bitmap, uint64_t cap_bytes, FreqRowsHost *rows, TimelineHost *out) {
     hipStream_t st = (hipStream_t)context_stream(ctx);
     HIP_TRY(hipSetDevice(context_device(ctx)));
@@ -204,56 +256,26 @@ arp_status device_timelines(arp_context *ctx, const FreqJob &job, bool want_bitm
         t_prev = now;
     };
     *out = TimelineHost{};
-    // 1. rows: the frequency table as the frequency call computes it
-    arp_status s = device_frequencies(ctx, job, rows);
+    TimelineDev dev;
+    arp_status s = timeline_device(ctx, job, cap_bytes, rows, &dev, lap, nullptr);
     if (s != ARP_OK) return s;
-    lap("rows");
-    const uint64_t R = rows->key.size(), F = job.n_frames, W = (F + 31u) / 32u;
+    const uint64_t R = rows->key.size(), F = job.n_frames, W = (F + 31u) / 32u, need = R * W * 4u;
     out->words_per_row = W;
     out->has_bitmap = want_bitmap;
     out->first.resize(R); out->last.resize(R); out->n_events.resize(R); out->longest.resize(R);
     if (R == 0) return ARP_OK;
-    if (F > 0xFFFFFFF0ull) { set_error("contact timelines: more than 2^32 frames"); return ARP_ERR_BAD_INPUT; }
-    const uint64_t need = R * W * 4u;
-    if (need > cap_bytes) {
-        set_error("contact timelines: the bitmap of %llu rows x %llu frames needs %llu bytes of device memory, the limit is %llu (timeline_cap_bytes)", (unsigned long long)R,
-                  (unsigned long long)F, (unsigned long long)need, (unsigned long long)cap_bytes);
-        return ARP_ERR_CAPACITY;
-    }
-    // 2. marks: the row keys back on the device, the zeroed bitmap, the five per-row results, the error word
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, seg_align(R * 8) + seg_align(need) + 5 * seg_align(R * 4) + seg_align(256)));
-    std::unique_ptr<char, void (*)(char *)> block_owner(block, [](char *p) { (void)hipFree(p); });
-    Bump bp{block};
-    unsigned long long *row_keys = bp.take<unsigned long long>(R);
-    uint32_t *words = bp.take<uint32_t>(R * W);
-    uint32_t *stat[5];
-    for (uint32_t *&p : stat) p = bp.take<uint32_t>(R);
-    uint32_t *err = bp.take<uint32_t>(64);
-    HIP_TRY(hipMemcpyAsync(row_keys, rows->key.data(), R * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(words, 0, need, st));
-    HIP_TRY(hipMemsetAsync(err, 0, 4, st));
-    TimelineMarks mk{row_keys, (uint32_t)R, (uint32_t)F, words, W, err};
-    struct FreeItems { TimelineMarks *m; ~FreeItems() { if (m->items) (void)hipFree(m->items); } } items_owner{&mk};
-    FreqRowsHost none;
-    if ((s = freq_sweep(ctx, job, &none, &mk)) != ARP_OK) return s;
-    lap("marks");
-    // 3. statistics: one wave per row
-    hipLaunchKernelGGL(k_timeline_stats, dim3((uint32_t)((R + 3u) / 4u)), dim3(256), 0, st, (uint32_t)R, W, (const uint32_t *)words, stat[0], stat[1], stat[2], stat[3], stat[4]);
-    HIP_TRY(hipGetLastError());
-    lap("stats");
     // 4. download
     uint32_t h_err = 0;
     std::vector<uint32_t> count(R);
-    HIP_TRY(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out->first.data(), stat[0], R * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out->last.data(), stat[1], R * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out->n_events.data(), stat[2], R * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out->longest.data(), stat[3], R * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(count.data(), stat[4], R * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&h_err, dev.err, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out->first.data(), dev.stat[0], R * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out->last.data(), dev.stat[1], R * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out->n_events.data(), dev.stat[2], R * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out->longest.data(), dev.stat[3], R * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(count.data(), dev.stat[4], R * 4, hipMemcpyDeviceToHost, st));
     if (want_bitmap) {
         out->words.resize(R * W);
-        HIP_TRY(hipMemcpyAsync(out->words.data(), words, need, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out->words.data(), dev.words, need, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
     lap("download");

@@ -164,6 +164,8 @@ typedef struct arp_table arp_table;         /* the 20-column contact table (mod.
  *                      pass), so that tests can force several passes; 0 (default): about 2 x 10^6 atoms per pass
  *   "timeline_cap_bytes" N > 0: arp_contact_timelines refuses a device bitmap of more than N bytes (ARP_ERR_CAPACITY), so that tests reach the limit on
  *                      tiny inputs; 0 (default): 2^31 bytes
+ *   "similarity_cap_bytes" N > 0: arp_contact_similarity and arp_bit_gram refuse a matrix of more than N bytes (ARP_ERR_CAPACITY), so that tests reach
+ *                      the limit on tiny inputs; 0 (default): 2^31 bytes
  * Unknown keys return ARP_ERR_BAD_INPUT. */
 arp_status arp_debug_set(const char *key, int64_t value);
 int32_t arp_api_version(void);
@@ -540,6 +542,40 @@ const uint32_t *arp_table_timeline(const arp_table *t, uint64_t *words_per_row, 
  * ARP_NONE and zeros.  For anyone who post-processes a bitmap (a frame window, an AND of two rows), and the yardstick of the device kernel. */
 arp_status arp_timeline_stats(uint64_t rows, uint64_t n_frames, const uint32_t *words, uint32_t *n_present, uint32_t *first, uint32_t *last, uint32_t *n_events,
                               uint32_t *longest_run);
+
+/* ---- contact similarity between frames, contact co-occurrence between rows -- DESIGN.md section 3.14 ----
+ * Topology, n_frames, xyz, groups, vdw_comp, dist_cutoff and level exactly as arp_contact_timelines defines them, and present[r][f] is that call's:
+ * the same rows in the same order, either level, with or without ARP_FREQ_RINGS.  With F frames and R rows:
+ *   axis "frames" (default)  S_f = { r : present[r][f] };  inter[f][g] = |S_f AND S_g|;  sizes[f] = |S_f|;  M = F
+ *   axis "rows" (ARP_SIM_ROWS)  T_r = { f : present[r][f] };  inter[r][s] = |T_r AND T_s|;  sizes[r] = |T_r| = the row's "n_frames";  M = R
+ *   metric "tanimoto" (default)  f32((double)inter / (double)(sizes_a + sizes_b - inter)), 1.0f when the union is empty (two empty sets are
+ *                             identical), so the diagonal is 1.0 everywhere; one IEEE f64 divide and one rounding to f32
+ *   metric "count" (ARP_SIM_COUNTS)  inter as u32
+ * The matrix is full, symmetric, M x M, row-major.  No contact in any frame (R = 0): on axis "frames" the counts are 0, the Tanimoto values 1.0 and
+ * the sizes 0; on axis "rows" the matrix is empty.
+ * The returned table is the frequency table of the level: every column and the Arrow export have the bytes of arp_contact_frequencies_ex /
+ * arp_residue_contact_frequencies for the same arguments; the matrix is not part of the batch (arp_table_similarity).
+ * flags: ARP_FREQ_RINGS, ARP_SIM_COUNTS, ARP_SIM_ROWS; any other bit, or a level outside {0, 1}, is ARP_ERR_BAD_INPUT.  Every check, status and message
+ * of the frequency calls runs before the device is touched; ctx == NULL runs only the checks (ARP_OK, *out = NULL).
+ * Device memory: the timeline call's (its bitmap limit applies, and the bitmap is never copied to the host), plus M x M x 4 bytes for the matrix and,
+ * on axis "frames", the transposed bitmap.  A matrix above 2^31 bytes (arp_debug_set "similarity_cap_bytes") is ARP_ERR_CAPACITY, with a message that
+ * names M, the axis and the bytes; the check runs as soon as R is known, before anything is allocated for the matrix.  The bytes do not depend on the
+ * pass size, on the order in which the device produced pairs, or on tile scheduling: two calls give identical bytes.  Synchronous. */
+#define ARP_SIM_COUNTS 0x4u
+#define ARP_SIM_ROWS 0x8u
+arp_status arp_contact_similarity(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
+                                  double dist_cutoff, uint32_t flags, int32_t level, arp_table **out);
+/* The host matrix of a similarity table (owned by the table): *m = M, *flags = the call's ARP_SIM_* bits (f32 values unless ARP_SIM_COUNTS: u32),
+ * *sizes = the M set sizes (all three nullable).  Never NULL for a similarity table, M = 0 included; NULL for every other table. */
+const void *arp_table_similarity(const arp_table *t, uint64_t *m, uint32_t *flags, const uint32_t **sizes);
+/* The definition above on any bitmap of the timeline layout (`rows` rows of ceil(n_bits / 32) words), bit by bit, without a device: ARP_SIM_ROWS
+ * clear compares the bit columns (the frames of a timeline bitmap: M = n_bits), set compares the word rows (M = rows); ARP_SIM_COUNTS as above.  out:
+ * M x M f32 or u32, sizes: M u32.  Bits past n_bits in a row's last word are ignored.  n_bits or rows of 2^32 and more, an unknown flag, or a null
+ * pointer with rows > 0 are ARP_ERR_BAD_INPUT.  The CPU yardstick of the device kernels, and a tool for post-processed bitmaps. */
+arp_status arp_bit_gram_host(uint64_t rows, uint64_t n_bits, const uint32_t *words, uint32_t flags, void *out, uint32_t *sizes);
+/* The same on the device for a host bitmap: upload, the kernels of arp_contact_similarity, download.  Identical bytes.  The matrix limit of
+ * arp_contact_similarity applies (ARP_ERR_CAPACITY). */
+arp_status arp_bit_gram(arp_context *ctx, uint64_t rows, uint64_t n_bits, const uint32_t *words, uint32_t flags, void *out, uint32_t *sizes);
 
 /* ---- SASA and SAP statistics over the frames of an ensemble (MD snapshots, NMR models, conformers of one topology) -- DESIGN.md section 3.8 ----
  * Topology, N, frames and xyz exactly as arp_contact_frequencies defines them: model 0 of `topology` is the topology, frame f is xyz[f]
