@@ -337,26 +337,8 @@ class Context:
         t = C.c_void_p()
         _check(lib.arp_get_contacts(self._h, structure._h, groups.encode(), vdw_comp, dist_cutoff, C.byref(t)))
         try:
-            n = int(lib.arp_table_rows(t))
-            cols = {}
-
-            def col(name, dtype=None):
-                w = C.c_int32()
-                p = lib.arp_table_column(t, name.encode(), C.byref(w))
-                if not p and n:
-                    raise KeyError(name)
-                return _np_from(p, n, dtype or f"S{w.value}")
-
-            for name, kind in TABLE_COLUMNS:
-                if name == "interaction":
-                    cols[name] = col(name, "<i4")
-                elif kind == "str":
-                    cols[name] = col(name)
-                else:
-                    cols[name] = col(name, "<" + kind)
-            cols["sc_valid"] = col("sc_valid", "u1").astype(bool)
-            cols["from_atom"] = col("from_atom", "<i4")
-            cols["to_atom"] = col("to_atom", "<i4")
+            cols = _read_columns(t, TABLE_COLUMNS, (("sc_valid", "u1"), ("from_atom", "i4"), ("to_atom", "i4")))
+            cols["sc_valid"] = cols["sc_valid"].astype(bool)
             return cols
         finally:
             lib.arp_table_free(t)
@@ -428,6 +410,55 @@ class Context:
         return _dsasa_ensemble(self, structure, frames, groups, probe_radius, n_points, radii, per_frame)
 
 
+def _check_level(level: str):
+    if level not in ("atom", "residue"):
+        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
+
+
+def _read_columns(t, spec, extra=()) -> dict:
+    """The numpy columns of a table handle (copies), read through arp_table_column.  spec: (name, kind) pairs as the *_COLUMNS lists hold them --
+    "str": NUL-padded bytes of the column's width; interaction: the i4 codes (the names are the Arrow batch's); else the dtype.  extra: more such
+    pairs behind them.  A column the table does not have is a KeyError (a table without rows serves none)."""
+    n = int(lib.arp_table_rows(t))
+    cols = {}
+    for name, kind in list(spec) + list(extra):
+        w = C.c_int32()
+        p = lib.arp_table_column(t, name.encode(), C.byref(w))
+        if not p and n:
+            raise KeyError(name)
+        cols[name] = _np_from(p, n, "<i4" if name == "interaction" else f"S{max(w.value, 1)}" if kind == "str" else "<" + kind)
+    return cols
+
+
+def _arrow_of(t):
+    """arp_table_export_arrow of a table handle as a pyarrow.Table (the batch owns copies: the handle may be freed)."""
+    import pyarrow as pa
+
+    arr, sch = _lib.ArrowArray(), _lib.ArrowSchema()
+    _check(lib.arp_table_export_arrow(t, C.byref(arr), C.byref(sch)))
+    return pa.Table.from_batches([pa.RecordBatch._import_from_c(C.addressof(arr), C.addressof(sch))])
+
+
+def _frame_of(table):
+    """What the reference returns (python.rs:55): a polars.DataFrame over the same Arrow buffers when polars is importable, else the pyarrow.Table."""
+    try:
+        import polars as pl
+
+        return pl.from_arrow(table)
+    except ImportError:
+        return table
+
+
+def _with_context(device: int, validate) -> "Context":
+    """The default context of `device`.  Without a device, validate() -- the same call with ctx None, which only checks the inputs -- runs first: an
+    input error takes precedence over the missing device."""
+    try:
+        return _context(device)
+    except ArpeggiaError:
+        validate()
+        raise
+
+
 def _topology_atoms(structure: Structure) -> int:
     """Atoms of model 0 (the topology of arp_contact_frequencies): the leading run of the first MODEL serial."""
     m = structure.ints("model")
@@ -440,8 +471,7 @@ def _topology_atoms(structure: Structure) -> int:
 def _freq_table(ctx: "Context | None", structure: Structure, frames, groups: str, vdw_comp: float, dist_cutoff: float, rings: bool = False, level: str = "atom"):
     """arp_contact_frequencies_ex (level "atom") or arp_residue_contact_frequencies ("residue") -> table handle (the caller frees it).  ctx None:
     the inputs are only checked (raises their error, else returns None)."""
-    if level not in ("atom", "residue"):
-        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
+    _check_level(level)
     n_frames, ptr, keep = _frames_arg(structure, frames, "contact frequencies")
     t = C.c_void_p()
     call = lib.arp_residue_contact_frequencies if level == "residue" else lib.arp_contact_frequencies_ex
@@ -453,41 +483,14 @@ def _freq_table(ctx: "Context | None", structure: Structure, frames, groups: str
 def _freq_columns(t, rings: bool, level: str) -> dict:
     """The numpy columns of a frequency table handle (copies): FREQ_COLUMNS + from_atom / to_atom (+ from_ring / to_ring with rings), or
     RESIDUE_FREQ_COLUMNS + from_residue / to_residue."""
-    n = int(lib.arp_table_rows(t))
-    cols = {}
-
-    def col(name, dtype=None):
-        w = C.c_int32()
-        p = lib.arp_table_column(t, name.encode(), C.byref(w))
-        if not p and n:
-            raise KeyError(name)
-        return _np_from(p, n, dtype or f"S{max(w.value, 1)}")
-
     if level == "residue":
-        for name, kind in RESIDUE_FREQ_COLUMNS:
-            cols[name] = col(name, "<i4") if name == "interaction" else col(name) if kind == "str" else col(name, "<" + kind)
-        cols["from_residue"] = col("from_residue", "<i4")
-        cols["to_residue"] = col("to_residue", "<i4")
-        return cols
-    for name, kind in FREQ_COLUMNS:
-        if name == "interaction":
-            cols[name] = col(name, "<i4")
-        elif kind == "str":
-            cols[name] = col(name)
-        else:
-            cols[name] = col(name, "<" + kind)
-    cols["from_atom"] = col("from_atom", "<i4")
-    cols["to_atom"] = col("to_atom", "<i4")
-    if rings:
-        cols["from_ring"] = col("from_ring", "<i4")
-        cols["to_ring"] = col("to_ring", "<i4")
-    return cols
+        return _read_columns(t, RESIDUE_FREQ_COLUMNS, (("from_residue", "i4"), ("to_residue", "i4")))
+    return _read_columns(t, FREQ_COLUMNS, (("from_atom", "i4"), ("to_atom", "i4")) + ((("from_ring", "i4"), ("to_ring", "i4")) if rings else ()))
 
 
 def _timeline_table(ctx: "Context | None", structure: Structure, frames, groups: str, vdw_comp: float, dist_cutoff: float, rings: bool, level: str, bitmap: bool):
     """arp_contact_timelines -> table handle (the caller frees it).  ctx None: the inputs are only checked (raises their error, else returns None)."""
-    if level not in ("atom", "residue"):
-        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
+    _check_level(level)
     n_frames, ptr, keep = _frames_arg(structure, frames, "contact timelines")
     t = C.c_void_p()
     flags = (_lib.ARP_FREQ_RINGS if rings else 0) | (0 if bitmap else _lib.ARP_TIMELINE_NO_BITMAP)
@@ -499,12 +502,8 @@ def _timeline_table(ctx: "Context | None", structure: Structure, frames, groups:
 def _timeline_columns(t, rings: bool, level: str) -> dict:
     """The frequency columns of a timeline table handle, TIMELINE_COLUMNS and, when the table holds its bitmap, timeline_words + n_total_frames (copies)."""
     cols = _freq_columns(t, rings, level)
+    cols.update(_read_columns(t, TIMELINE_COLUMNS))
     n = int(lib.arp_table_rows(t))
-    for name, kind in TIMELINE_COLUMNS:
-        p = lib.arp_table_column(t, name.encode(), None)
-        if not p and n:
-            raise KeyError(name)
-        cols[name] = _np_from(p, n, "<" + kind)
     wpr, nf = C.c_uint64(), C.c_uint64()
     p = lib.arp_table_timeline(t, C.byref(wpr), C.byref(nf))
     if p:
@@ -548,8 +547,7 @@ def _similarity_flags(axis: str, metric: str) -> int:
 def _similarity_table(ctx: "Context | None", structure: Structure, frames, groups: str, vdw_comp: float, dist_cutoff: float, rings: bool, level: str, axis: str,
                       metric: str):
     """arp_contact_similarity -> table handle (the caller frees it).  ctx None: the inputs are only checked (raises their error, else returns None)."""
-    if level not in ("atom", "residue"):
-        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
+    _check_level(level)
     flags = _similarity_flags(axis, metric) | (_lib.ARP_FREQ_RINGS if rings else 0)
     n_frames, ptr, keep = _frames_arg(structure, frames, "contact similarity")
     t = C.c_void_p()
@@ -829,22 +827,13 @@ def get_contacts(structure: Structure, groups: str = "/", vdw_comp: float = 0.1,
 
 
 def _table(ctx: "Context", structure: Structure, groups: str, vdw_comp: float, dist_cutoff: float, num_threads: int = -1):
-    import pyarrow as pa
-
     t = C.c_void_p()
     _check(lib.arp_get_contacts_mt(ctx._h, structure._h, groups.encode(), vdw_comp, dist_cutoff, int(num_threads), C.byref(t)))
     try:
-        arr, sch = _lib.ArrowArray(), _lib.ArrowSchema()
-        _check(lib.arp_table_export_arrow(t, C.byref(arr), C.byref(sch)))
+        table = _arrow_of(t)
     finally:
         lib.arp_table_free(t)
-    table = pa.Table.from_batches([pa.RecordBatch._import_from_c(C.addressof(arr), C.addressof(sch))])
-    try:  # the reference returns a polars.DataFrame (python.rs:55); same Arrow buffers when polars is installed
-        import polars as pl
-
-        return pl.from_arrow(table)
-    except ImportError:
-        return table
+    return _frame_of(table)
 
 
 def contacts(input_file: str, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5,
@@ -869,28 +858,14 @@ def get_contact_frequencies(structure: Structure, frames=None, groups: str = "/"
     residue of to, interaction) instead -- n_frames counts the distinct frames in which ANY item of the residue pair has the interaction (what
     the atom-level table cannot give), min_distance / max_distance are the extremes over those frames of the frame's closest approach
     (RESIDUE_FREQ_COLUMNS).  Returns a polars.DataFrame when polars is importable, else a pyarrow.Table, like get_contacts."""
-    import pyarrow as pa
-
-    if level not in ("atom", "residue"):
-        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
-    try:
-        ctx = _context(device)
-    except ArpeggiaError:
-        _freq_table(None, structure, frames, groups, vdw_comp, dist_cutoff, rings, level)  # an input error takes precedence over the missing device
-        raise
+    _check_level(level)
+    ctx = _with_context(device, lambda: _freq_table(None, structure, frames, groups, vdw_comp, dist_cutoff, rings, level))
     t = _freq_table(ctx, structure, frames, groups, vdw_comp, dist_cutoff, rings, level)
     try:
-        arr, sch = _lib.ArrowArray(), _lib.ArrowSchema()
-        _check(lib.arp_table_export_arrow(t, C.byref(arr), C.byref(sch)))
+        table = _arrow_of(t)
     finally:
         lib.arp_table_free(t)
-    table = pa.Table.from_batches([pa.RecordBatch._import_from_c(C.addressof(arr), C.addressof(sch))])
-    try:
-        import polars as pl
-
-        return pl.from_arrow(table)
-    except ImportError:
-        return table
+    return _frame_of(table)
 
 
 def contact_frequencies(input_file: str, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, ignore_zero_occupancy: bool = False,
@@ -898,8 +873,7 @@ def contact_frequencies(input_file: str, groups: str = "/", vdw_comp: float = 0.
     """Contact frequencies across the models of a multi-model file (NMR models, MODEL-record snapshots): see get_contact_frequencies.  With
     rings=True the rings are those of model 0 regarded as a single-model structure, not what get_contacts files for the multi-model file.
     level="residue": the residue-level table."""
-    if level not in ("atom", "residue"):
-        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
+    _check_level(level)
     return get_contact_frequencies(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings, level=level)
 
 
@@ -910,21 +884,15 @@ def get_contact_timelines(structure: Structure, frames=None, groups: str = "/", 
     from_residue / to_residue), identical bytes -- plus TIMELINE_COLUMNS per row: first_frame, last_frame, n_events (maximal runs of consecutive
     frames with the contact), longest_run (frames) and mean_run = n_frames / n_events.  bitmap=True adds timeline_words [rows, ceil(F / 32)] <u4
     (frame f = bit f & 31 of word f >> 5; unpack_timeline) and n_total_frames.  frames, groups, rings and level as get_contact_frequencies."""
-    if level not in ("atom", "residue"):
-        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
-    try:
-        ctx = _context(device)
-    except ArpeggiaError:
-        _timeline_table(None, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, bitmap)  # an input error takes precedence over the missing device
-        raise
+    _check_level(level)
+    ctx = _with_context(device, lambda: _timeline_table(None, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, bitmap))
     return ctx.contact_timelines(structure, frames, groups, vdw_comp, dist_cutoff, rings, level, bitmap)
 
 
 def contact_timelines(input_file: str, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, ignore_zero_occupancy: bool = False,
                       rings: bool = False, level: str = "atom", bitmap: bool = True) -> dict:
     """Contact timelines across the models of a multi-model file (the models are the frames): see get_contact_timelines."""
-    if level not in ("atom", "residue"):
-        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
+    _check_level(level)
     return get_contact_timelines(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings, level=level, bitmap=bitmap)
 
 
@@ -934,22 +902,16 @@ def get_contact_similarity(structure: Structure, frames=None, groups: str = "/",
     the same arguments as a dict of numpy columns, identical bytes, plus the [M, M] matrix of the per-frame contact fingerprints (axis "frames", M =
     F) or of the rows' frame sets (axis "rows", M = rows): `similarity` <f4 (metric "tanimoto") or `intersection` <u4 (metric "count"), with `sizes`
     [M] <u4, `axis` and `n_total_frames`.  frames, groups, rings and level as get_contact_frequencies."""
-    if level not in ("atom", "residue"):
-        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
+    _check_level(level)
     _similarity_flags(axis, metric)
-    try:
-        ctx = _context(device)
-    except ArpeggiaError:
-        _similarity_table(None, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, axis, metric)  # an input error takes precedence over the missing device
-        raise
+    ctx = _with_context(device, lambda: _similarity_table(None, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, axis, metric))
     return ctx.contact_similarity(structure, frames, groups, vdw_comp, dist_cutoff, rings, level, axis, metric)
 
 
 def contact_similarity(input_file: str, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, ignore_zero_occupancy: bool = False,
                        rings: bool = False, level: str = "atom", axis: str = "frames", metric: str = "tanimoto") -> dict:
     """Contact similarity across the models of a multi-model file (the models are the frames): see get_contact_similarity."""
-    if level not in ("atom", "residue"):
-        raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
+    _check_level(level)
     _similarity_flags(axis, metric)
     return get_contact_similarity(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings, level=level, axis=axis, metric=metric)
 
@@ -957,37 +919,19 @@ def contact_similarity(input_file: str, groups: str = "/", vdw_comp: float = 0.1
 def _contact_similarity_arrow(input_file: str, groups: str, vdw_comp: float, dist_cutoff: float, ignore_zero_occupancy: bool, rings: bool, level: str, axis: str,
                               metric: str):
     """The command line's form of contact_similarity: (Arrow table of the frequency columns, the matrix)."""
-    import pyarrow as pa
-
     structure = Structure.load(input_file, ignore_zero_occupancy)
-    try:
-        ctx = _context(0)
-    except ArpeggiaError:
-        _similarity_table(None, structure, None, groups, vdw_comp, dist_cutoff, rings, level, axis, metric)
-        raise
+    ctx = _with_context(0, lambda: _similarity_table(None, structure, None, groups, vdw_comp, dist_cutoff, rings, level, axis, metric))
     owner = _TableOwner(_similarity_table(ctx, structure, None, groups, vdw_comp, dist_cutoff, rings, level, axis, metric))
-    arr, sch = _lib.ArrowArray(), _lib.ArrowSchema()
-    _check(lib.arp_table_export_arrow(owner.t, C.byref(arr), C.byref(sch)))
-    table = pa.Table.from_batches([pa.RecordBatch._import_from_c(C.addressof(arr), C.addressof(sch))])
-    return table, _similarity_matrix(owner)["intersection" if metric == "count" else "similarity"]
+    return _arrow_of(owner.t), _similarity_matrix(owner)["intersection" if metric == "count" else "similarity"]
 
 
 def _contact_timelines_arrow(input_file: str, groups: str, vdw_comp: float, dist_cutoff: float, ignore_zero_occupancy: bool, rings: bool, level: str, bitmap: bool):
     """The command line's form of contact_timelines: (Arrow table of the frequency + timeline columns, timeline_words or None)."""
-    import pyarrow as pa
-
     structure = Structure.load(input_file, ignore_zero_occupancy)
-    try:
-        ctx = _context(0)
-    except ArpeggiaError:
-        _timeline_table(None, structure, None, groups, vdw_comp, dist_cutoff, rings, level, bitmap)
-        raise
+    ctx = _with_context(0, lambda: _timeline_table(None, structure, None, groups, vdw_comp, dist_cutoff, rings, level, bitmap))
     t = _timeline_table(ctx, structure, None, groups, vdw_comp, dist_cutoff, rings, level, bitmap)
     try:
-        arr, sch = _lib.ArrowArray(), _lib.ArrowSchema()
-        _check(lib.arp_table_export_arrow(t, C.byref(arr), C.byref(sch)))
-        table = pa.Table.from_batches([pa.RecordBatch._import_from_c(C.addressof(arr), C.addressof(sch))])
-        return table, _timeline_columns(t, rings, level).get("timeline_words")
+        return _arrow_of(t), _timeline_columns(t, rings, level).get("timeline_words")
     finally:
         lib.arp_table_free(t)
 
@@ -1104,13 +1048,7 @@ def _frame(cols: dict):
     """A table of the contact table's type: polars.DataFrame when polars is importable, else pyarrow.Table."""
     import pyarrow as pa
 
-    table = pa.table(cols)
-    try:
-        import polars as pl
-
-        return pl.from_arrow(table)
-    except ImportError:
-        return table
+    return _frame_of(pa.table(cols))
 
 
 def _strings(structure: Structure, column: str, idx: np.ndarray) -> list:
@@ -1448,11 +1386,7 @@ def get_buried_sasa(structure: Structure, groups: str, level: str = "atom", prob
         raise ValueError(f"Invalid level '{level}'. Must be one of: 'atom', 'residue'")
     if radii is not None:
         _radii_table(radii)
-    try:
-        ctx = _context(device)
-    except ArpeggiaError:
-        _buried_sasa(None, structure, groups, probe_radius, n_points, model_num, radii)  # an input error takes precedence over the missing device
-        raise
+    ctx = _with_context(device, lambda: _buried_sasa(None, structure, groups, probe_radius, n_points, model_num, radii))
     r = ctx.buried_sasa(structure, groups, probe_radius, n_points, model_num, radii)
     if lv == "atom":
         ident = _identity(structure, r["atoms"])
@@ -1523,11 +1457,7 @@ def get_dsasa_ensemble(structure: Structure, frames=None, groups: str = "/", pro
     None: the structure's models are the frames.  per_frame=True adds a third value {"buried": [F, m] i32 points}."""
     import pyarrow as pa
 
-    try:
-        ctx = _context(device)
-    except ArpeggiaError:
-        _dsasa_ensemble(None, structure, frames, groups, probe_radius, n_points, radii, False)  # an input error takes precedence over the missing device
-        raise
+    ctx = _with_context(device, lambda: _dsasa_ensemble(None, structure, frames, groups, probe_radius, n_points, radii, False))
     r = ctx.dsasa_ensemble(structure, frames, groups, probe_radius, n_points, radii, per_frame)
     F = r["n_frames"]
     ft = _frame({"frame": pa.array(np.arange(F, dtype="<u4"), pa.uint32()), "total_complex": pa.array(r["total_complex"], pa.float32()),
@@ -1569,11 +1499,7 @@ def _ensemble_table(structure: Structure, r: dict, names: list):
 
 
 def _ensemble_run(structure: Structure, frames, chains: str, probe_radius: float, n_points: int, sap_radius, per_frame: bool, device: int, radii=None) -> dict:
-    try:
-        ctx = _context(device)
-    except ArpeggiaError:
-        _sasa_ensemble(None, structure, frames, chains, probe_radius, n_points, sap_radius, False, radii)  # an input error takes precedence over the missing device
-        raise
+    ctx = _with_context(device, lambda: _sasa_ensemble(None, structure, frames, chains, probe_radius, n_points, sap_radius, False, radii))
     return ctx.sasa_ensemble(structure, frames, chains, probe_radius, n_points, sap_radius, per_frame, radii)
 
 
@@ -1588,11 +1514,7 @@ def get_residue_sasa_ensemble(structure: Structure, frames=None, chains: str = "
     extras = {"chains": the chain ids in get_chain_sasa's order, "chain_sasa": [F, n_chains] f32}; per_frame=True adds "residue_sasa": [F, n_res] f32."""
     import pyarrow as pa
 
-    try:
-        ctx = _context(device)
-    except ArpeggiaError:
-        _residue_sasa_ensemble(None, structure, frames, chains, probe_radius, n_points, radii, False)  # an input error takes precedence over the missing device
-        raise
+    ctx = _with_context(device, lambda: _residue_sasa_ensemble(None, structure, frames, chains, probe_radius, n_points, radii, False))
     r = ctx.residue_sasa_ensemble(structure, frames, chains, probe_radius, n_points, radii, per_frame)
     cols = _residue_identity(structure, r["res_atoms"])
     cols["is_polar"] = pa.array(r["is_polar"], pa.bool_())

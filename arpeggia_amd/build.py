@@ -13,8 +13,8 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libarpeggia_amd.so"
-SOURCES = ["kernels.hip", "engine.cpp", "batch.cpp", "sasa_dev.cpp", "structure.cpp", "table.cpp", "table_dev.hip", "sasa.cpp", "sc.cpp"]
-HEADERS = ["arp_internal.h", "emit_plan.h", "host_common.h", "engine.h", "debug_knobs.h", "grid.inl", "pairs.inl", "pairs_emit.inl", "batch.inl", "sap.inl", "sasa.inl", "ens.inl", "seg.inl", "sc.inl", "freq.inl", "freq_rings.inl", "timeline.inl", "similarity.inl", "table_dev.h", "../../include/arpeggia_amd.h"]
+SOURCES = ["kernels.hip", "engine.cpp", "batch.cpp", "sasa_dev.cpp", "structure.cpp", "table.cpp", "table_cache.cpp", "table_ens.cpp", "table_dev.hip", "sasa.cpp", "sc.cpp"]
+HEADERS = ["arp_internal.h", "emit_plan.h", "host_common.h", "engine.h", "debug_knobs.h", "grid.inl", "pairs.inl", "pairs_emit.inl", "batch.inl", "sap.inl", "sasa.inl", "ens.inl", "seg.inl", "sc.inl", "freq.inl", "freq_rings.inl", "timeline.inl", "similarity.inl", "table.h", "table_dev.h", "../../include/arpeggia_amd.h"]
 TEST_HEADERS = ["../../tests/hosttable/table_host.inl"]  # only the test library (build_host_table_library) contains it: not part of the product's hash
 STAMP = PKG / "build" / "libarpeggia_amd.sha256"  # hash of every source + the flags the library was last built from
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-fvisibility=default", "-Wall", "-Wno-unused-result",
@@ -79,7 +79,7 @@ HOST_TABLE_LIB = PKG.parent / "tests" / "hosttable" / "build" / "libarpeggia_amd
 
 
 def build_host_table_library(force: bool = False) -> Path:
-    """TEST-ONLY library: the product's objects with table.cpp recompiled under -DARP_WITH_HOST_TABLE, i.e. plus the round-1 host assembly
+    """TEST-ONLY library: the product's objects with table_cache.cpp recompiled under -DARP_WITH_HOST_TABLE, i.e. plus the round-1 host assembly
     of the contact table (tests/hosttable/table_host.inl) that tests/test_gpu_parity.py cross-checks the device table with.  The product library
     does not contain that code."""
     build_library()  # the product's objects must be current
@@ -89,9 +89,9 @@ def build_host_table_library(force: bool = False) -> Path:
         return HOST_TABLE_LIB
     HOST_TABLE_LIB.parent.mkdir(parents=True, exist_ok=True)
     cc = hipcc()
-    obj = HOST_TABLE_LIB.parent / "table_cpp_host.o"
-    subprocess.run([cc, "-x", "hip", *FLAGS, "-DARP_WITH_HOST_TABLE", "-c", str(CSRC / "table.cpp"), "-o", str(obj)], check=True)
-    objs = [str(obj) if src == "table.cpp" else str(PKG / "build" / (src.replace(".", "_") + ".o")) for src in SOURCES]
+    obj = HOST_TABLE_LIB.parent / "table_cache_cpp_host.o"
+    subprocess.run([cc, "-x", "hip", *FLAGS, "-DARP_WITH_HOST_TABLE", "-c", str(CSRC / "table_cache.cpp"), "-o", str(obj)], check=True)
+    objs = [str(obj) if src == "table_cache.cpp" else str(PKG / "build" / (src.replace(".", "_") + ".o")) for src in SOURCES]
     subprocess.run([cc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", str(HOST_TABLE_LIB), "-lpthread"], check=True)
     stamp.write_text(want + "\n")
     return HOST_TABLE_LIB

@@ -153,14 +153,8 @@ void run_helpers(int helpers, size_t n, F &&fn) {  // fn(item) over [0, n) on up
     if (first_error) std::rethrow_exception(first_error);
 }
 
-struct BatchLap {  // arp_debug_set("timing", 1): where a pack's host time goes (stderr)
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    void operator()(const char *what) {
-        if (!g_debug.timing) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "    batch %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
-        t = now;
-    }
+struct BatchLap : LapTimer {  // arp_debug_set("timing", 1): where a pack's host time goes (stderr)
+    BatchLap() : LapTimer("    batch %-28s %8.3f ms\n") {}
 };
 
 struct BatchSlot {

@@ -544,7 +544,7 @@ static arp_status single_pass_into_context_buffer(arp_context *ctx, const DevAto
     }
 }
 
-// The table path's pair pass (table.cpp get_contacts_device): device-resident inputs, the list stays in the context's buffer --
+// The table path's pair pass (table_cache.cpp get_contacts_device): device-resident inputs, the list stays in the context's buffer --
 // *data is a VIEW, valid until the next call on this context.
 arp_status arp::contacts_atomic_view(arp_context *ctx, const arp_atoms *atoms, const arp_params *params, const arp_pair **data, uint64_t *n) {
     *data = nullptr; *n = 0;

@@ -226,15 +226,7 @@ arp_status freq_alloc(FreqBufs *b, uint64_t cap, uint64_t keep, hipStream_t st) 
 arp_status freq_sweep(arp_context *ctx, const FreqJob &job, FreqRowsHost *out, TimelineMarks *marks) {
     hipStream_t st = (hipStream_t)context_stream(ctx);
     HIP_TRY(hipSetDevice(context_device(ctx)));
-    const bool timing = g_debug.timing != 0;
-    auto t_prev = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!timing) return;
-        (void)hipStreamSynchronize(st);
-        auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "    frequencies %-24s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
-        t_prev = now;
-    };
+    StreamLapTimer lap("    frequencies %-24s %8.3f ms\n", st);
     *out = FreqRowsHost{};
     const uint64_t n = job.n, nr = job.n_res, nh = job.n_h, F = job.n_frames;
     const uint64_t n_rings = job.n_rings, n_slots = job.n_slots, n_cand = job.n_cand, n_ra = n_rings ? job.res_atom_ptr[nr] : 0;

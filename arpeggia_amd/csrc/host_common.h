@@ -1,8 +1,10 @@
-// Host-side declarations shared by the host sources (engine.cpp, batch.cpp, sasa_dev.cpp, structure.cpp, table.cpp, table_dev.hip).
+// Host-side declarations shared by the host sources (engine.cpp, batch.cpp, sasa_dev.cpp, structure.cpp, table*.cpp, table_dev.hip).
 #pragma once
 #include <array>
+#include <chrono>
 #include <cstdarg>
 #include <cstdint>
+#include <cstdio>
 #include <exception>
 #include <mutex>
 #include <new>
@@ -42,6 +44,21 @@ struct Carver {  // the offset of the next segment; offsets only: one layout ser
             return (e_ == hipErrorOutOfMemory) ? ARP_ERR_OOM : ARP_ERR_HIP;                        \
         }                                                                                          \
     } while (0)
+
+// The stage laps of the "timing" switch (arp_debug_set): lap(what) prints the time since the previous lap (or the construction) on stderr through
+// `line`, a format that takes the stage's name (%s) and the milliseconds (%f).  Inert unless the switch is set when it is constructed.
+struct LapTimer {
+    const char *line;
+    bool on;
+    std::chrono::steady_clock::time_point prev;
+    explicit LapTimer(const char *line_format) : line(line_format), on(g_debug.timing != 0), prev(std::chrono::steady_clock::now()) {}
+    void operator()(const char *what) {
+        if (!on) return;
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, line, what, std::chrono::duration<double, std::milli>(now - prev).count());
+        prev = now;
+    }
+};
 
 // Fixed-width, NUL-padded string column (n x W chars), the layout the C ABI hands to numpy / Rust.
 template <int W>
@@ -98,7 +115,7 @@ struct arp_structure {
     std::vector<uint32_t> res_h_ptr, res_h_idx, res_cb, res_sg;
     std::string groups_applied;
     bool groups_valid = false;
-    // table.cpp: derived per-structure tables of the table path + the device-resident copy (built on the first arp_get_contacts)
+    // table_cache.cpp: derived per-structure tables of the table path + the device-resident copy (built on the first arp_get_contacts)
     void *table_cache = nullptr;
     std::mutex table_cache_mu;   // guards the creation of table_cache
     void (*table_cache_free)(void *) = nullptr;
@@ -194,7 +211,7 @@ struct BsaEnsOut {
     int32_t *buried = nullptr;                        // n_frames x m, nullable
 };
 arp_status bsa_ens_run(arp_context *ctx, const BsaEnsJob &job, const BsaEnsOut &out);
-// table.cpp: model 0 of a structure as the topology of an ensemble (n0 atoms, r0 residues); with frames_from_models every further model must
+// table_ens.cpp: model 0 of a structure as the topology of an ensemble (n0 atoms, r0 residues); with frames_from_models every further model must
 // repeat model 0's atoms one for one (ARP_ERR_BAD_INPUT naming the first model and atom that differ)
 arp_status freq_topology(const arp_structure *s, bool frames_from_models, uint64_t *n0, uint64_t *r0, uint64_t *n_models);
 // golden-spiral unit vectors in f64, rounded to f32 (DESIGN.md "Atom SASA")

@@ -182,20 +182,12 @@ arp_status device_similarity(arp_context *ctx, const FreqJob &job, bool by_rows,
                              SimilarityHost *out) {
     hipStream_t st = (hipStream_t)context_stream(ctx);
     HIP_TRY(hipSetDevice(context_device(ctx)));
-    const bool timing = g_debug.timing != 0;
-    auto t_prev = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!timing) return;
-        (void)hipStreamSynchronize(st);
-        auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "  similarity %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
-        t_prev = now;
-    };
+    StreamLapTimer lap("  similarity %-10s %8.3f ms\n", st);
     *out = SimilarityHost{};
     // 1. + 2. rows and marks (timeline.inl); the matrix is refused as soon as its edge is known
     TimelineDev dev;
     const uint64_t F = job.n_frames;
-    arp_status s = timeline_device(ctx, job, timeline_cap_bytes, rows, &dev, [&](const char *what) { if (strcmp(what, "stats")) lap(what); },
+    arp_status s = timeline_device(ctx, job, timeline_cap_bytes, rows, &dev, lap,
                                    [&](uint64_t R) { return similarity_cap_check(by_rows ? R : F, by_rows, cap_bytes); });
     if (s != ARP_OK) return s;
     const uint64_t R = rows->key.size(), W = (F + 31u) / 32u, WR = (R + 31u) / 32u, M = by_rows ? R : F;

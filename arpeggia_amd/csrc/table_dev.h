@@ -1,5 +1,5 @@
 // Device side of the contact table (SURVEY.md 8f rows f1 + f2): plane fits, ring rows, row expansion, the 10-key sort and the
-// side-chain plane statistics run as HIP kernels (table_dev.hip); table.cpp keeps the bookkeeping (entity lists, strings).
+// side-chain plane statistics run as HIP kernels (table_dev.hip); table_cache.cpp keeps the bookkeeping (entity lists, strings).
 #pragma once
 #include <cstdint>
 #include <memory>

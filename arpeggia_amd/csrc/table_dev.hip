@@ -1,6 +1,6 @@
 // The contact table on the device: SURVEY.md 8f rows f1 (ring / side-chain plane fits, ring-atom and ring-ring rows,
 // complex.rs:301-405, residues.rs:270-298, aromatic.rs:14-64) and f2 (row expansion, the 10-key sort of mod.rs:120-134, the
-// side-chain plane statistics of complex.rs:137-174).  The host (table.cpp) only keeps the bookkeeping: which entities exist and
+// side-chain plane statistics of complex.rs:137-174).  The host (table_cache.cpp) only keeps the bookkeeping: which entities exist and
 // their strings.  Written for gfx950; sorting and scans go through hipCUB (library primitives, not the hot path).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -22,7 +22,7 @@ namespace arp {
 struct PlaneD { double c[3], n[3]; };
 
 // ---- plane fits (residues.rs:270-298): centroid + direction of least variance --------------------------------------
-// The same cyclic Jacobi iteration as the host's former fit (table.cpp fit_plane): nalgebra's svd.u.column(2) is that direction up
+// The same cyclic Jacobi iteration as the host's former fit (table_cache.cpp fit_plane, test-only now): nalgebra's svd.u.column(2) is that direction up
 // to sign, and every use folds the angle into [0, 90] degrees.
 __device__ bool fit_plane_dev(const double *x, const double *y, const double *z, const uint32_t *idx, uint32_t lo, uint32_t hi, const uint8_t *bits, uint8_t want,
                               PlaneD *out) {
@@ -623,6 +623,11 @@ struct Bump {  // typed pieces of one block
     char *base; Carver c{};
     template <class T> T *take(uint64_t count) { return reinterpret_cast<T *>(base + c.take(count * sizeof(T))); }
 };
+struct StreamLapTimer : LapTimer {  // a lap ends when the stream has drained
+    hipStream_t st;
+    StreamLapTimer(const char *line_format, hipStream_t stream) : LapTimer(line_format), st(stream) {}
+    void operator()(const char *what) { if (on) { (void)hipStreamSynchronize(st); LapTimer::operator()(what); } }
+};
 }  // namespace
 
 arp_status device_planes(arp_context *ctx, const DevStructure &ds, std::vector<double> *planes, std::vector<uint8_t> *valid) {
@@ -654,15 +659,7 @@ arp_status device_planes(arp_context *ctx, const DevStructure &ds, std::vector<d
 arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<RingEnt> &rings, const std::vector<EntKey> &ring_keys, const arp_pair *pairs_dev,
                         uint64_t n_pairs, double dist_cutoff, TableRowsHost *out) {
     hipStream_t st = (hipStream_t)context_stream(ctx);
-    const bool timing = g_debug.timing != 0;
-    auto t_prev = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!timing) return;
-        (void)hipStreamSynchronize(st);
-        auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "    device_table %-20s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
-        t_prev = now;
-    };
+    StreamLapTimer lap("    device_table %-20s %8.3f ms\n", st);
     const uint64_t n = ds.n, nr = ds.n_res, n_rings = rings.size(), n_ent = n + n_rings;
     if (n_pairs > 0x7FFFFFF0ull / 8 || n_ent > 0x7FFFFFF0ull) { set_error("table too large for 32-bit row indices"); return ARP_ERR_BAD_INPUT; }
     // rows: <= 5 per pair in principle, but a contacts-only pair carries 1.06 rows on average; sized after the bit count below.
@@ -810,13 +807,13 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
         hipLaunchKernelGGL(k_table_small, dim3(1), dim3(kSmallThreads), 0, st, pairs_dev, (uint32_t)n_pairs, (const uint4 *)ring_rows, n_rings ? (const uint32_t *)counters : (const uint32_t *)nullptr,
                            (uint32_t)ring_rows_cap, reinterpret_cast<uint4 *>(dev2), (uint32_t)n, (const EntKey *)ds.ent_key, (const EntKey *)d_ring_keys, (const uint32_t *)ent_rank,
                            (const uint32_t *)ds.chain_rank, (const uint32_t *)ds.model, (const uint32_t *)ds.model_rank, (const RingEnt *)d_rings, tb, (const uint32_t *)ds.atom_sc_src,
-                           (const PlaneD *)sc_pl, (const uint8_t *)valid, pin2, timing ? reinterpret_cast<unsigned long long *>(pin2 + land - 128) : (unsigned long long *)nullptr);
+                           (const PlaneD *)sc_pl, (const uint8_t *)valid, pin2, lap.on ? reinterpret_cast<unsigned long long *>(pin2 + land - 128) : (unsigned long long *)nullptr);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));
         SmallHeader head;
         memcpy(&head, pin2, sizeof head);
         lap("one-launch table");
-        if (timing) {
+        if (lap.on) {
             unsigned long long t[6];
             memcpy(t, pin2 + land - 128, sizeof t);
             fprintf(stderr, "      k_table_small (us): rows %.1f  keys %.1f  sort %.1f  ties %.1f  finish %.1f\n", (t[1] - t[0]) * 0.01, (t[2] - t[1]) * 0.01, (t[3] - t[2]) * 0.01,

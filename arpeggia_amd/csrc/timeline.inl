@@ -199,9 +199,9 @@ struct TimelineDev {
     uint32_t *words = nullptr, *stat[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *err = nullptr;
 };
 
-// rows sweep, marks sweep, statistics: everything of a timeline up to its download.  lap is called after "rows", "marks" and "stats"; after_rows (nullable)
-// sees the number of rows before anything is allocated and may refuse the job.
-arp_status timeline_device(arp_context *ctx, const FreqJob &job, uint64_t cap_bytes, FreqRowsHost *rows, TimelineDev *dev, const std::function<void(const char *)> &lap,
+// rows sweep, marks sweep, statistics: everything of a timeline up to its download.  lap is called after "rows" and "marks" (the statistics kernel is
+// the caller's to lap, alone or with what it launches next); after_rows (nullable) sees the number of rows before anything is allocated and may refuse the job.
+arp_status timeline_device(arp_context *ctx, const FreqJob &job, uint64_t cap_bytes, FreqRowsHost *rows, TimelineDev *dev, StreamLapTimer &lap,
                            const std::function<arp_status(uint64_t)> &after_rows) {
     hipStream_t st = (hipStream_t)context_stream(ctx);
     // 1. rows: the frequency table as the frequency call computes it
@@ -239,27 +239,19 @@ arp_status timeline_device(arp_context *ctx, const FreqJob &job, uint64_t cap_by
     hipLaunchKernelGGL(k_timeline_stats, dim3((uint32_t)((R + 3u) / 4u)), dim3(256), 0, st, (uint32_t)R, W, (const uint32_t *)dev->words, dev->stat[0], dev->stat[1], dev->stat[2],
                        dev->stat[3], dev->stat[4]);
     HIP_TRY(hipGetLastError());
-    lap("stats");
     return ARP_OK;
 }
 
 arp_status device_timelines(arp_context *ctx, const FreqJob &job, bool want_bitmap, uint64_t cap_bytes, FreqRowsHost *rows, TimelineHost *out) {
     hipStream_t st = (hipStream_t)context_stream(ctx);
     HIP_TRY(hipSetDevice(context_device(ctx)));
-    const bool timing = g_debug.timing != 0;
-    auto t_prev = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!timing) return;
-        (void)hipStreamSynchronize(st);
-        auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "  timeline %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
-        t_prev = now;
-    };
+    StreamLapTimer lap("  timeline %-10s %8.3f ms\n", st);
     *out = TimelineHost{};
     TimelineDev dev;
     arp_status s = timeline_device(ctx, job, cap_bytes, rows, &dev, lap, nullptr);
     if (s != ARP_OK) return s;
     const uint64_t R = rows->key.size(), F = job.n_frames, W = (F + 31u) / 32u, need = R * W * 4u;
+    if (R) lap("stats");
     out->words_per_row = W;
     out->has_bitmap = want_bitmap;
     out->first.resize(R); out->last.resize(R); out->n_events.resize(R); out->longest.resize(R);

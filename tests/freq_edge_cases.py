@@ -1,4 +1,4 @@
-"""Cases and references for the edges of contact frequencies across frames (arp_contact_frequencies: freq.inl + the host half in table.cpp).
+"""Cases and references for the edges of contact frequencies across frames (arp_contact_frequencies: freq.inl + the host half in table_ens.cpp).
 No product imports: tests/test_freq_edge_host.py checks the cases on the CPU (closed form == oracle loop, every case reaches the edge it is named
 for), tests/test_freq_edge_gpu.py runs them on the device.
 

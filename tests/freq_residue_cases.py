@@ -1,5 +1,5 @@
 """Built cases and references for residue-level contact frequencies across frames (arp_residue_contact_frequencies: the residue mode of freq.inl +
-the host half in table.cpp).  No product imports: tests/test_freq_residue_host.py checks the cases on the CPU (closed form
+the host half in table_ens.cpp).  No product imports: tests/test_freq_residue_host.py checks the cases on the CPU (closed form
 == oracle loop, every case reaches the edge it is named for), tests/test_freq_residue_gpu.py runs them on the device.
 
 Topology.  The two-atom motifs of tests/freq_edge_cases.py (same places, same 1/256 A grid, so every distance is exact in f32 and compared for

@@ -1,5 +1,5 @@
 """Built inputs for the ring rows of contact frequencies across frames (arp_contact_frequencies_ex with ARP_FREQ_RINGS: freq_rings.inl + the host
-half in table.cpp).  No product imports: tests/test_freq_rings_host.py checks the cases on the CPU (closed form == oracle loop, every case reaches
+half in table_ens.cpp).  No product imports: tests/test_freq_rings_host.py checks the cases on the CPU (closed form == oracle loop, every case reaches
 the edges it is named for), tests/test_freq_rings_gpu.py runs them on the device.
 
 Topology.  K isolated motifs 32 A apart on a plane.  Every motif has a PHE ring (CG CD1 CD2 CE1 CE2 CZ, a regular hexagon of radius 1.39 A in the

@@ -1,16 +1,21 @@
 // The round-1 HOST assembly of the contact table (plane fits, ring rows, row expansion, 10-key sort and sc statistics on the CPU, from
 // the GPU's pair list): a second, independent implementation of src/contacts/mod.rs:61-137 that one GPU test compares the device table
-// with.  NOT part of libarpeggia_amd.so: table.cpp includes this file only under -DARP_WITH_HOST_TABLE, which arpeggia_amd/build.py sets
+// with.  NOT part of libarpeggia_amd.so: table_cache.cpp includes this file only under -DARP_WITH_HOST_TABLE, which arpeggia_amd/build.py sets
 // for the test-only library tests/hosttable/build/libarpeggia_amd_hosttable.so (build_host_table_library()).
+namespace {
+struct Entity {  // what a row says about one side: the identity the table shows, and what the sort and the sc statistics need
+    EntityRec id;
+    uint32_t chain_rank = 0;
+    int64_t sc_plane = -1;
+};
+struct Row {
+    uint32_t model; int32_t interaction; double distance;
+    Entity from, to;
+};
+}  // namespace
+
 static arp_status get_contacts_host(arp_context *ctx, arp_structure *s, const char *groups, double vdw_comp, double dist_cutoff, arp_table **out) {
-    const bool timing = getenv("ARP_TIMING") != nullptr;
-    auto t_prev = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!timing) return;
-        auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "  get_contacts %-22s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
-        t_prev = now;
-    };
+    LapTimer lap("  get_contacts %-22s %8.3f ms\n");
     // InteractionComplex::new (complex.rs:36-68)
     arp_atoms view;
     arp_status st = arp_structure_atoms(s, groups, &view);
@@ -75,19 +80,9 @@ static arp_status get_contacts_host(arp_context *ctx, arp_structure *s, const ch
             }
         });
     }
-    auto entity_from_atom = [&](uint32_t a) {  // structs.rs:109-119
-        Entity e;
-        memcpy(e.chain, s->chain.at(a), 8); memcpy(e.resn, s->res_resn.at(a), 8); memcpy(e.atomn, s->name.at(a), 8);
-        memcpy(e.insertion, s->icode.at(a), 4); memcpy(e.altloc, s->altloc.at(a), 4);
-        e.resi = s->resi[a]; e.atomi = s->serial[a]; e.atom = (int32_t)a; e.chain_rank = s->chain_rank[a]; e.sc_plane = atom_sc[a];
-        return e;
-    };
-    auto entity_from_ring = [&](const PlaneEntry &r) {  // complex.rs:334-342
-        Entity e;
-        auto put = [](char *dst, size_t cap, const std::string &v) { memset(dst, 0, cap); memcpy(dst, v.data(), std::min(cap - 1, v.size())); };
-        put(e.chain, 8, r.chain); put(e.resn, 8, r.resn); put(e.atomn, 8, "Ring"); put(e.insertion, 4, r.icode); put(e.altloc, 4, r.altloc);
-        e.resi = r.resi; e.atomi = 0; e.atom = -1;
-        e.chain_rank = r.chain_rank;
+    auto entity_from_atom = [&](uint32_t a) { return Entity{atom_entity(*s, a), s->chain_rank[a], atom_sc[a]}; };
+    auto entity_from_ring = [&](const PlaneEntry &r) {
+        Entity e{ring_entity(r), r.chain_rank, -1};
         if (direct) e.sc_plane = sc_first[r.res] >= 0 ? sc_first[r.res] + (int64_t)r.alt_k : -1;  // same residue, same conformer altloc
         else {
             auto f = sc_idx.find(plane_key(r.model_serial, r.chain.c_str(), r.resi, r.icode.c_str(), r.altloc.c_str(), r.resn.c_str()));
@@ -213,8 +208,8 @@ static arp_status get_contacts_host(arp_context *ctx, arp_structure *s, const ch
     parallel_for(rows.size(), 1u << 14, [&](size_t k0, size_t k1, size_t) {
     for (size_t k = k0; k < k1; k++) {
         const Row &r = rows[k];
-        keys[k] = SortKey{r.model, r.from.chain_rank, r.to.chain_rank, r.from.resi, be32(r.from.altloc), r.from.atomi, r.to.resi, be32(r.to.altloc),
-                          r.to.atomi, name_rank[r.interaction], be32(r.from.insertion), be32(r.to.insertion), r.distance, (uint32_t)k};
+        keys[k] = SortKey{r.model, r.from.chain_rank, r.to.chain_rank, r.from.id.resi, be32(r.from.id.altloc), r.from.id.atomi, r.to.id.resi, be32(r.to.id.altloc),
+                          r.to.id.atomi, name_rank[r.interaction], be32(r.from.id.insertion), be32(r.to.id.insertion), r.distance, (uint32_t)k};
     }
     });
     auto key_less = [](const SortKey &a, const SortKey &b) {
@@ -258,22 +253,14 @@ static arp_status get_contacts_host(arp_context *ctx, arp_structure *s, const ch
     arp_table *t = new arp_table();
     const size_t n = rows.size();
     t->n = n;
-    t->model.resize(n); t->interaction.resize(n); t->from_resi.resize(n); t->from_atomi.resize(n); t->to_resi.resize(n); t->to_atomi.resize(n);
-    t->from_atom.resize(n); t->to_atom.resize(n); t->distance.resize(n); t->sc_dist.resize(n); t->sc_dihedral.resize(n); t->sc_angle.resize(n); t->sc_valid.resize(n);
-    t->from_chain.resize(n); t->from_resn.resize(n); t->from_atomn.resize(n); t->to_chain.resize(n); t->to_resn.resize(n); t->to_atomn.resize(n);
-    t->from_insertion.resize(n); t->from_altloc.resize(n); t->to_insertion.resize(n); t->to_altloc.resize(n);
+    contact_columns(t);
     parallel_for(n, 1u << 14, [&](size_t k_begin, size_t k_end, size_t) {
     uint64_t last_pair = ~0ull;
     float last_sc[3] = {0.f, 0.f, 0.f};
     for (size_t k = k_begin; k < k_end; k++) {
         const Row &r = rows[order[k]];
         t->model[k] = r.model; t->interaction[k] = r.interaction; t->distance[k] = (float)r.distance;  // mod.rs:148
-        t->from_chain.set(k, r.from.chain); t->from_resn.set(k, r.from.resn); t->from_atomn.set(k, r.from.atomn);
-        t->from_insertion.set(k, r.from.insertion); t->from_altloc.set(k, r.from.altloc);
-        t->from_resi[k] = r.from.resi; t->from_atomi[k] = r.from.atomi; t->from_atom[k] = r.from.atom;
-        t->to_chain.set(k, r.to.chain); t->to_resn.set(k, r.to.resn); t->to_atomn.set(k, r.to.atomn);
-        t->to_insertion.set(k, r.to.insertion); t->to_altloc.set(k, r.to.altloc);
-        t->to_resi[k] = r.to.resi; t->to_atomi[k] = r.to.atomi; t->to_atom[k] = r.to.atom;
+        t->from.put(k, r.from.id); t->to.put(k, r.to.id);
         // collect_sc_stats (complex.rs:137-174): res1 = ligand residue, res2 = receptor residue
         if (r.from.sc_plane >= 0 && r.to.sc_plane >= 0) {  // rows are sorted by residue pair: consecutive rows mostly share the planes
             const uint64_t pk = ((uint64_t)r.from.sc_plane << 32) | (uint64_t)r.to.sc_plane;

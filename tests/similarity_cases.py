@@ -1,5 +1,5 @@
 """Cases and references for contact similarity between frames and contact co-occurrence between rows (arp_contact_similarity, arp_bit_gram:
-similarity.inl + the host half in table.cpp).  No product imports: tests/test_similarity_host.py checks arp_bit_gram_host and every case's reach on
+similarity.inl + the host half in table_ens.cpp).  No product imports: tests/test_similarity_host.py checks arp_bit_gram_host and every case's reach on
 the CPU, tests/test_similarity_gpu.py runs the cases on the device.
 
 A bitmap is the timeline bitmap: bool masks [R, F], packed by timeline_cases.pack into <u4 [R, ceil(F / 32)], frame f = bit f & 31 of word f >> 5.

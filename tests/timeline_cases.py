@@ -1,4 +1,4 @@
-"""Cases and references for contact timelines across frames (arp_contact_timelines: timeline.inl + the host half in table.cpp).  No product
+"""Cases and references for contact timelines across frames (arp_contact_timelines: timeline.inl + the host half in table_ens.cpp).  No product
 imports: tests/test_timeline_host.py checks the cases on the CPU (brute-force statistics == arp_timeline_stats, closed form == oracle loop, every
 case reaches the boundary it is named for), tests/test_timeline_gpu.py runs them on the device.
 
