@@ -6,7 +6,7 @@ contact_frequencies(), contact_timelines(), contact_similarity(), sasa_ensemble(
 fails loudly if the HIP extension has not been built -- there is no CPU fallback.
 """
 from .api import (  # noqa: F401
-    ArpeggiaError, Context, Structure, PAIR_DTYPE, TABLE_COLUMNS, atomic_contacts_batch, atoms_from_arrays, contacts, contacts_batch, debug_set, default_params,
+    ArpeggiaError, Context, Structure, PAIR_DTYPE, TABLE_COLUMNS, atomic_contacts_batch, atoms_from_arrays, contacts, contacts_batch, debug_get, debug_set, default_params,
     device_count, get_contacts, load_model, parse_groups, sap_neighbor_sum, sap_weight,
 )
 from .api import (  # noqa: F401  atom SASA, SAP score, dSASA (reference src/sasa.rs, src/sap.rs)

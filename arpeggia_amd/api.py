@@ -86,8 +86,15 @@ def default_params(vdw_comp: float = 0.1, dist_cutoff: float = 6.5, deterministi
 
 
 def debug_set(key: str, value: int):
-    """arp_debug_set: the library's diagnostic switches ("timing", "emit_kernel", "defer_entries", "table_host", "freq_chunk_atoms", "freq_cap_items", "freq_frame_bits", "timeline_cap_bytes", "similarity_cap_bytes", ...; include/arpeggia_amd.h)."""
+    """arp_debug_set: the library's diagnostic switches ("timing", "emit_kernel", "defer_entries", "table_host", "freq_chunk_atoms", "freq_cap_items", "freq_frame_bits", "timeline_cap_bytes", "similarity_cap_bytes", "table_key_bits", ...; include/arpeggia_amd.h)."""
     _check(lib.arp_debug_set(key.encode(), int(value)))
+
+
+def debug_get(key: str) -> int:
+    """arp_debug_get: what the last contact-table call of the process did ("table_small", "table_pairs", "table_atom_rows", "table_ring_rows", "table_plan", "table_long_way", "table_ring_cap"; include/arpeggia_amd.h)."""
+    v = C.c_int64(0)
+    _check(lib.arp_debug_get(key.encode(), C.byref(v)))
+    return int(v.value)
 
 
 def parse_groups(all_chains, groups: str):

@@ -12,6 +12,7 @@
 
 #include "engine.h"
 #include "table_dev.h"
+#include "table_plan.h"
 
 namespace arp {
 
@@ -698,11 +699,29 @@ extern "C" arp_status arp_debug_set(const char *key, int64_t value) {
         if (value > (int64_t)kNarrowMaxBits) { set_error("arp_debug_set: index_bits takes 0 (automatic), 1 .. 20 (the index width of the narrow exact record) or a negative value (the wide record always)"); return ARP_ERR_BAD_INPUT; }
         g_debug.index_bits = (int)value;
     }
+    else if (k == "table_key_bits") {
+        if (!table_key_bits_valid(value)) { set_error("arp_debug_set: table_key_bits takes 0 (64) or %d .. %d (no pass of the table sort is narrower than %d bits)", kTableMinKeyBits, kTableMaxKeyBits, kTableMinKeyBits); return ARP_ERR_BAD_INPUT; }
+        g_debug.table_key_bits = (int)value;
+    }
     else if (k == "strip_rows") {
         if (value < 0 || value > 1024 || (value & (value - 1)) != 0) { set_error("arp_debug_set: strip_rows takes 0 or a power of two up to 1024"); return ARP_ERR_BAD_INPUT; }
         g_debug.strip_rows = (int)value;
     }
-    else { set_error("arp_debug_set: unknown key '%s' (timing, emit_kernel, defer_entries, strip_rows, index_bits, table_host, freq_chunk_atoms, freq_cap_items, freq_frame_bits, ens_chunk_atoms, timeline_cap_bytes, similarity_cap_bytes)", key); return ARP_ERR_BAD_INPUT; }
+    else { set_error("arp_debug_set: unknown key '%s' (timing, emit_kernel, defer_entries, strip_rows, index_bits, table_host, freq_chunk_atoms, freq_cap_items, freq_frame_bits, ens_chunk_atoms, timeline_cap_bytes, similarity_cap_bytes, table_key_bits)", key); return ARP_ERR_BAD_INPUT; }
+    return ARP_OK;
+}
+extern "C" arp_status arp_debug_get(const char *key, int64_t *value) {
+    if (!key || !value) { set_error("arp_debug_get: null argument"); return ARP_ERR_BAD_INPUT; }
+    const std::string k(key);
+    const TableRoute r = table_route_last();
+    if (k == "table_small") *value = r.small;
+    else if (k == "table_pairs") *value = r.pairs;
+    else if (k == "table_atom_rows") *value = r.atom_rows;
+    else if (k == "table_ring_rows") *value = r.ring_rows;
+    else if (k == "table_plan") *value = r.plan;
+    else if (k == "table_long_way") *value = r.long_way;
+    else if (k == "table_ring_cap") *value = r.ring_cap;
+    else { set_error("arp_debug_get: unknown key '%s' (table_small, table_pairs, table_atom_rows, table_ring_rows, table_plan, table_long_way, table_ring_cap)", key); return ARP_ERR_BAD_INPUT; }
     return ARP_OK;
 }
 extern "C" int32_t arp_api_version(void) { return ARP_API_VERSION; }

@@ -66,6 +66,8 @@ std::shared_ptr<char> pinned_block(size_t bytes);   // pooled pinned host memory
 // ARP_MEM_DEVICE).  Returns ARP_ERR_NO_RINGS etc. like arp_get_contacts.
 arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<RingEnt> &rings, const std::vector<EntKey> &ring_keys,
                         const arp_pair *pairs_dev, uint64_t n_pairs, double dist_cutoff, TableRowsHost *out);
+struct TableRoute;
+TableRoute table_route_last();  // the route of the process's last device_table call (table_plan.h; arp_debug_get)
 // the planes the device fitted, for tests (PHE4 of 1ubq: residues.rs:355-372): 12 doubles per residue {ring c, ring n, sc c, sc n} + validity bits
 arp_status device_planes(arp_context *ctx, const DevStructure &ds, std::vector<double> *planes, std::vector<uint8_t> *valid);
 

@@ -11,11 +11,14 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <mutex>
 #include <string>
 
 #include "arp_internal.h"
+#include "debug_knobs.h"
 #include "host_common.h"
 #include "table_dev.h"
+#include "table_plan.h"
 
 namespace arp {
 
@@ -403,7 +406,7 @@ __global__ __launch_bounds__(256) void k_finish_rows(uint32_t n_rows, const uint
 // words in LDS, the tie pass on neighbours (k_tie_fix), the side-chain plane statistics (k_finish_rows), and the finished table written STRAIGHT
 // INTO THE PINNED LANDING BUFFER the host reads after the stream has drained (no copy command).  What does not fit (more rows, keys wider than
 // 64 - kSmallIdxBits bits, a tie run longer than kTieRun) is reported in the header and the general path runs instead.
-constexpr uint32_t kSmallRows = 4096, kSmallThreads = 1024, kSmallIdxBits = 12, kSmallPairs = 2048;
+// (kSmallRows, kSmallThreads, kSmallIdxBits, kSmallPairs: table_plan.h)
 struct SmallHeader { uint32_t n_rows, status, n_atom_rows, n_ring_rows; };  // status: 0 = done; 1 = too many rows; 2 = a tie run too long; 3 = more ring rows than reserved
 
 // Bitonic sort (ascending) of n_pad = E x (active threads) 64-bit words, thread t holding the E consecutive words t E .. t E + E - 1 in registers.
@@ -499,6 +502,12 @@ __global__ __launch_bounds__(kSmallThreads) void k_table_small(const arp_pair *p
     const uint32_t n_rows = n_atom_rows + n_ring_rows;
     if (n_rows > kSmallRows || n_ring_rows > ring_rows_cap) {
         if (tid == 0u) *head = SmallHeader{n_rows, n_ring_rows > ring_rows_cap ? 3u : 1u, n_atom_rows, n_ring_rows};
+        return;
+    }
+    // An empty table ends here (n_rows is the same in every thread).  The gathers below read rows[0] for every slot past n_rows and follow its entity
+    // indices; with no row written by this launch, rows[0] is whatever an earlier call -- on another structure -- left in the scratch block.
+    if (n_rows == 0u) {
+        if (tid == 0u) *head = SmallHeader{0u, 0u, 0u, 0u};
         return;
     }
     // 2. the rows (global scratch: 128 KB would not fit LDS next to the sort words), atom rows first, ring rows behind them
@@ -656,11 +665,29 @@ arp_status device_planes(arp_context *ctx, const DevStructure &ds, std::vector<d
     return ARP_OK;
 }
 
+// The route of the last table call of the process (arp_debug_get): a call fills a record of its own and publishes it when it ends, however it ends.
+namespace {
+std::mutex g_route_mu;
+TableRoute g_route;
+struct RoutePublisher {
+    TableRoute r;
+    ~RoutePublisher() { std::lock_guard<std::mutex> lock(g_route_mu); g_route = r; }
+};
+struct DevBlock {  // a device allocation of one call
+    void *p = nullptr;
+    ~DevBlock() { if (p) (void)hipFree(p); }
+};
+}  // namespace
+TableRoute table_route_last() { std::lock_guard<std::mutex> lock(g_route_mu); return g_route; }
+
 arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<RingEnt> &rings, const std::vector<EntKey> &ring_keys, const arp_pair *pairs_dev,
                         uint64_t n_pairs, double dist_cutoff, TableRowsHost *out) {
     hipStream_t st = (hipStream_t)context_stream(ctx);
     StreamLapTimer lap("    device_table %-20s %8.3f ms\n", st);
     const uint64_t n = ds.n, nr = ds.n_res, n_rings = rings.size(), n_ent = n + n_rings;
+    RoutePublisher route;
+    TableRoute &rt = route.r;
+    rt.pairs = (long long)n_pairs;
     if (n_pairs > 0x7FFFFFF0ull / 8 || n_ent > 0x7FFFFFF0ull) { set_error("table too large for 32-bit row indices"); return ARP_ERR_BAD_INPUT; }
     // rows: <= 5 per pair in principle, but a contacts-only pair carries 1.06 rows on average; sized after the bit count below.
     // First stage: everything whose size is known up front.
@@ -668,7 +695,9 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, cub_scan, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)std::max<uint64_t>(n_pairs, n_ent) + 1);
     (void)hipcub::DeviceRadixSort::SortPairs(nullptr, cub_sort_ent, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (const uint32_t *)nullptr,
                                              (uint32_t *)nullptr, (int)n_ent, 0, 64);
-    const uint64_t ring_rows_cap = 64 * n_rings + 1024;  // each ring meets a handful of cations / rings; checked below
+    // each ring meets a handful of cations / rings; a call that finds more reserves what the counter reported and runs the ring kernels again, once
+    uint64_t ring_rows_cap = 64 * n_rings + 1024;
+    rt.ring_cap = (long long)ring_rows_cap;
     uint64_t need = 2 * seg_align(nr * sizeof(PlaneD)) + seg_align(nr) + seg_align(n_rings * sizeof(RingEnt)) + seg_align(n_rings * sizeof(EntKey)) + seg_align(n_rings * 32) + 4096 + seg_align((n_pairs + 1) * 4) * 2 +
                     seg_align(std::max(cub_scan, cub_sort_ent)) + seg_align(n_ent * 8) * 2 + seg_align(n_ent * 4) * 4 + seg_align(ring_rows_cap * 16);
     char *dev = nullptr, *pin = nullptr;
@@ -726,7 +755,7 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
     // (measured on 6bft, 7236 rows: the one workgroup sorts for 68 us -- n log^2 n compare-exchanges on ONE compute unit -- and gathers for 40 more, which is
     // no faster than the dozen chip-wide launches it replaces: 0.32 against 0.29 ms per warm call; on 1ubq, 532 rows, the whole kernel is 19 us and the
     // call 0.13 against 0.15 ms.  So the one-launch path takes tables of up to kSmallPairs pairs; the kernel itself holds kSmallRows rows.)
-    bool small_try = n_pairs <= kSmallPairs;
+    bool small_try = table_few_pairs(n_pairs);
     auto launch_bits = [&]() -> arp_status {
         hipLaunchKernelGGL(k_count_bits, grid(n_pairs + 1, 256), dim3(256), 0, st, pairs_dev, (uint32_t)n_pairs, bits, counters);  // (also clears the counters)
         if (n_pairs) {
@@ -774,7 +803,9 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
         ds.max_ent_rank = max_rank;
     }
     lap("planes+bits+ranks");
-    auto width = [](uint64_t v) { uint32_t b = 1; while (b < 32 && (1ull << b) < v) b++; return b; };  // bits that hold 0 .. v-1
+    TableQuery tq;
+    tq.n_pairs = n_pairs; tq.n_models = ds.n_models; tq.n_chains = ds.n_chains; tq.max_ent_rank = ds.max_ent_rank; tq.any_icode = ds.any_icode; tq.knob_key_bits = g_debug.table_key_bits;
+    const TablePlan plan = plan_table(tq);
     SortTables tb{};
     {
         int o[ARP_N_INTERACTIONS];
@@ -782,9 +813,9 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
         std::sort(o, o + ARP_N_INTERACTIONS, [](int a, int c) { return strcmp(arp_interaction_name(a), arp_interaction_name(c)) < 0; });
         for (int k = 0; k < ARP_N_INTERACTIONS; k++) tb.name_rank[o[k]] = (uint8_t)k;
     }
-    tb.rank_bits = width((uint64_t)ds.max_ent_rank + 1); tb.chain_bits = width(std::max<uint64_t>(ds.n_chains, 1));
-    if (small_try && width(std::max<uint64_t>(ds.n_models, 1)) + 2 * tb.chain_bits + 2 * tb.rank_bits + 5 + kSmallIdxBits > 64) {
-        small_try = false;  // (the ten keys + a row index do not fit one word: the general path, from its first kernel)
+    tb.rank_bits = plan.rank_bits; tb.chain_bits = plan.chain_bits;
+    if (small_try && !plan.small_try) {
+        small_try = false; rt.small = 4;  // (the ten keys + a row index do not fit one word: the general path, from its first kernel)
         if ((s = launch_bits()) != ARP_OK) return s;
     }
     auto launch_rings = [&]() {
@@ -798,20 +829,37 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
                            counters, (uint32_t)ring_rows_cap);
         return ARP_OK;
     };
+    // More ring rows than reserved (append_row wrote none past the reserve): a block of this call's own for as many as the counter reported, and
+    // the ring kernels once more.  A second overflow -- the same kernels on the same input counting differently -- is an error.
+    // The block is hipMalloc'ed and freed when the call ends, and hipFree waits for the whole device: fine for a path that one ring under a thousand
+    // cations takes; the first scratch slot cannot grow here (counters, bits and offsets in it are in use) and the second is resized further down.
+    DevBlock ring_rows_big;
+    auto grow_ring_rows = [&](uint32_t reported) -> arp_status {
+        if (ring_rows_big.p) { set_error("internal error: more ring rows than reserved (%u > %llu)", reported, (unsigned long long)ring_rows_cap); return ARP_ERR_HIP; }
+        HIP_TRY(hipMalloc(&ring_rows_big.p, (size_t)reported * sizeof(uint4)));
+        ring_rows = reinterpret_cast<uint4 *>(ring_rows_big.p); ring_rows_cap = reported; rt.ring_cap = (long long)reported;
+        HIP_TRY(hipMemsetAsync(counters, 0, sizeof(uint32_t), st));  // (the ring-row counter alone)
+        return ARP_OK;
+    };
     if (small_try) {
         // ONE launch behind the ring kernels, the table written straight into the pinned landing block, one wait for the stream
         const uint64_t land = 16 + (uint64_t)kSmallRows * 32 + 256;
         char *dev2 = nullptr, *pin2 = nullptr;
         if ((s = context_scratch(ctx, 1, seg_align((uint64_t)kSmallRows * 16) + 4096, land, &dev2, &pin2)) != ARP_OK) return s;
-        if (n_rings && (s = launch_rings()) != ARP_OK) return s;
-        hipLaunchKernelGGL(k_table_small, dim3(1), dim3(kSmallThreads), 0, st, pairs_dev, (uint32_t)n_pairs, (const uint4 *)ring_rows, n_rings ? (const uint32_t *)counters : (const uint32_t *)nullptr,
-                           (uint32_t)ring_rows_cap, reinterpret_cast<uint4 *>(dev2), (uint32_t)n, (const EntKey *)ds.ent_key, (const EntKey *)d_ring_keys, (const uint32_t *)ent_rank,
-                           (const uint32_t *)ds.chain_rank, (const uint32_t *)ds.model, (const uint32_t *)ds.model_rank, (const RingEnt *)d_rings, tb, (const uint32_t *)ds.atom_sc_src,
-                           (const PlaneD *)sc_pl, (const uint8_t *)valid, pin2, lap.on ? reinterpret_cast<unsigned long long *>(pin2 + land - 128) : (unsigned long long *)nullptr);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(st));
         SmallHeader head;
-        memcpy(&head, pin2, sizeof head);
+        for (;;) {  // (twice at the most: grow_ring_rows refuses a second time)
+            if (n_rings && (s = launch_rings()) != ARP_OK) return s;
+            hipLaunchKernelGGL(k_table_small, dim3(1), dim3(kSmallThreads), 0, st, pairs_dev, (uint32_t)n_pairs, (const uint4 *)ring_rows, n_rings ? (const uint32_t *)counters : (const uint32_t *)nullptr,
+                               (uint32_t)ring_rows_cap, reinterpret_cast<uint4 *>(dev2), (uint32_t)n, (const EntKey *)ds.ent_key, (const EntKey *)d_ring_keys, (const uint32_t *)ent_rank,
+                               (const uint32_t *)ds.chain_rank, (const uint32_t *)ds.model, (const uint32_t *)ds.model_rank, (const RingEnt *)d_rings, tb, (const uint32_t *)ds.atom_sc_src,
+                               (const PlaneD *)sc_pl, (const uint8_t *)valid, pin2, lap.on ? reinterpret_cast<unsigned long long *>(pin2 + land - 128) : (unsigned long long *)nullptr);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(st));
+            memcpy(&head, pin2, sizeof head);
+            if (head.status != 3u) break;
+            if ((s = grow_ring_rows(head.n_ring_rows)) != ARP_OK) return s;
+        }
+        rt.small = head.status; rt.atom_rows = head.n_atom_rows; rt.ring_rows = head.n_ring_rows;
         lap("one-launch table");
         if (lap.on) {
             unsigned long long t[6];
@@ -831,7 +879,6 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
             lap("unpack");
             return ARP_OK;
         }
-        if (head.status == 3u) { set_error("internal error: more ring rows than reserved (%u > %llu)", head.n_ring_rows, (unsigned long long)ring_rows_cap); return ARP_ERR_HIP; }
         small_try = false;  // more rows than one workgroup sorts, or a long tie run: the general path, from its first kernel
         if ((s = launch_bits()) != ARP_OK) return s;
     }
@@ -845,8 +892,14 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
     if (n_rings) HIP_TRY(hipMemcpyAsync((void *)counts_host, counters, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     else if (n_pairs) HIP_TRY(hipMemcpyAsync((void *)(counts_host + 3), first + n_pairs, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    if (counts_host[0] > ring_rows_cap) {
+        if ((s = grow_ring_rows(counts_host[0])) != ARP_OK || (s = launch_rings()) != ARP_OK) return s;
+        HIP_TRY(hipMemcpyAsync((void *)counts_host, counters, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (counts_host[0] > ring_rows_cap) { set_error("internal error: more ring rows than reserved (%u > %llu)", (uint32_t)counts_host[0], (unsigned long long)ring_rows_cap); return ARP_ERR_HIP; }
+    }
     const uint32_t n_ring_rows = counts_host[0], n_atom_rows = counts_host[3];
-    if (n_ring_rows > ring_rows_cap) { set_error("internal error: more ring rows than reserved (%u > %llu)", n_ring_rows, (unsigned long long)ring_rows_cap); return ARP_ERR_HIP; }
+    rt.atom_rows = n_atom_rows; rt.ring_rows = n_ring_rows;
     const uint32_t n_rows = n_atom_rows + n_ring_rows;
     const uint64_t rows_cap = std::max<uint64_t>(n_rows, 1);
     size_t cub_sort_rows = 0;
@@ -873,21 +926,12 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
     // into ONE key when their actual widths fit 64 bits (else two or three passes); rows whose ten keys tie are put in order afterwards
     // (k_tie_fix).  `long_way`: the tie-breaking keys -- insertion codes (skipped when no atom carries one), distance -- as passes of their own.
     auto sort_and_finish = [&](bool long_way) -> arp_status {
-        const uint32_t model_bits = width(std::max<uint64_t>(ds.n_models, 1)), top = model_bits + 2 * tb.chain_bits;
-        int plan[5], end_bit[5], n_pass = 0;
-        if (long_way) {
-            plan[n_pass] = 0; end_bit[n_pass++] = 32;
-            if (ds.any_icode) { plan[n_pass] = 1; end_bit[n_pass++] = 64; }
-        }
-        if (top + 2 * tb.rank_bits + 5 <= 64) { plan[n_pass] = 6; end_bit[n_pass++] = (int)(top + 2 * tb.rank_bits + 5); }
-        else {
-            plan[n_pass] = 2; end_bit[n_pass++] = (int)(tb.rank_bits + 5);
-            if (top + tb.rank_bits <= 64) { plan[n_pass] = 5; end_bit[n_pass++] = (int)(top + tb.rank_bits); }
-            else { plan[n_pass] = 3; end_bit[n_pass++] = (int)tb.rank_bits; plan[n_pass] = 4; end_bit[n_pass++] = (int)top; }
-        }
+        const int n_pass = long_way ? plan.n_long : plan.n_pass;
+        const int *pass_of = long_way ? plan.long_pass : plan.pass, *end_bit = long_way ? plan.long_end_bit : plan.end_bit;
+        rt.plan = plan.digits; rt.long_way = long_way ? 1 : 0;
         uint32_t *pin_ = perm0, *pout = perm1;
         for (int q = 0; q < n_pass; q++) {
-            const int pass = plan[q];
+            const int pass = pass_of[q];
             hipLaunchKernelGGL(k_row_key, grid(n_rows, 256), dim3(256), 0, st, n_rows, (const uint4 *)rows, q ? (const uint32_t *)pin_ : (const uint32_t *)nullptr, pass, (uint32_t)n,
                                (const EntKey *)ds.ent_key, (const EntKey *)d_ring_keys, (const uint32_t *)ent_rank, (const uint32_t *)ds.chain_rank, (const uint32_t *)ds.model,
                                (const uint32_t *)ds.model_rank, (const RingEnt *)d_rings, tb, rk0, q ? (uint32_t *)nullptr : pin_);
@@ -896,7 +940,7 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
             std::swap(pin_, pout);
         }
         if (!long_way) {
-            const bool one_key = plan[n_pass - 1] == 6 && n_pass == 1;  // rk1 then holds every row's ten keys, in sorted order
+            const bool one_key = pass_of[n_pass - 1] == 6 && n_pass == 1;  // rk1 then holds every row's ten keys, in sorted order
             hipLaunchKernelGGL(k_tie_fix, grid(n_rows, 256), dim3(256), 0, st, n_rows, (const uint4 *)rows, (const uint32_t *)pin_, one_key ? (const unsigned long long *)rk1 : nullptr,
                                (uint32_t)n, (const EntKey *)ds.ent_key, (const EntKey *)d_ring_keys, (const uint32_t *)ent_rank, (const uint32_t *)ds.chain_rank, (const uint32_t *)ds.model,
                                (const uint32_t *)ds.model_rank, (const RingEnt *)d_rings, pout, counters + 1);

@@ -166,8 +166,22 @@ typedef struct arp_table arp_table;         /* the 20-column contact table (mod.
  *                      tiny inputs; 0 (default): 2^31 bytes
  *   "similarity_cap_bytes" N > 0: arp_contact_similarity and arp_bit_gram refuse a matrix of more than N bytes (ARP_ERR_CAPACITY), so that tests reach
  *                      the limit on tiny inputs; 0 (default): 2^31 bytes
+ *   "table_key_bits" N in 6 .. 64: N stands for the 64 bits of the key word when the contact table chooses its sort passes (one merged key, two or three
+ *                      passes) and decides whether the one-launch path may run, so that small inputs reach the plans of wide keys; the passes themselves sort
+ *                      on their real widths, and the table's bytes do not change.  0 (default): 64.  Anything else is ARP_ERR_BAD_INPUT (6 is the narrowest pass any structure can
+ *                      have, not the widest pass of the structure at hand: the knob is set before a structure is known, and a value below a real pass is harmless)
  * Unknown keys return ARP_ERR_BAD_INPUT. */
 arp_status arp_debug_set(const char *key, int64_t value);
+/* The read-only twin: what the last contact-table call of the process (arp_get_contacts) did.
+ *   "table_small"     the one-launch path: -1 not tried (more than 2048 pairs), 0 it finished the table, 1 / 2 / 3 it gave up (more than 4096 rows / a run of
+ *                     64 or more rows with equal sort keys / more ring rows than reserved, after the one repeat) and the general path ran, 4 not tried
+ *                     because the keys and a row index do not fit one word
+ *   "table_pairs"     contact pairs the table was built from;  "table_atom_rows" / "table_ring_rows"  its rows
+ *   "table_plan"      the radix passes of the general path as decimal digits: 6, 25 or 234; 0 when it did not sort
+ *   "table_long_way"  1: the general path sorted a second time with the tie-breaking keys as passes of their own
+ *   "table_ring_cap"  ring rows reserved when the call ended (64 x rings + 1024, or what the counter reported when that was too few)
+ * Unknown keys return ARP_ERR_BAD_INPUT. */
+arp_status arp_debug_get(const char *key, int64_t *value);
 int32_t arp_api_version(void);
 /* A binder compiled against this header calls arp_check_api_version(ARP_API_VERSION) once: ARP_OK when the library lays out arp_atoms /
  * arp_params / arp_pair as that version of the header does, ARP_ERR_BAD_INPUT (+ arp_last_error) otherwise -- a v1 caller (16-bit chain
