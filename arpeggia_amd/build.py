@@ -14,7 +14,7 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libarpeggia_amd.so"
 SOURCES = ["kernels.hip", "engine.cpp", "batch.cpp", "sasa_dev.cpp", "structure.cpp", "table.cpp", "table_cache.cpp", "table_ens.cpp", "table_dev.hip", "sasa.cpp", "sc.cpp"]
-HEADERS = ["arp_internal.h", "emit_plan.h", "host_common.h", "engine.h", "debug_knobs.h", "grid.inl", "pairs.inl", "pairs_emit.inl", "batch.inl", "sap.inl", "sasa.inl", "ens.inl", "seg.inl", "sc.inl", "freq.inl", "freq_rings.inl", "timeline.inl", "similarity.inl", "table.h", "table_dev.h", "table_plan.h", "../../include/arpeggia_amd.h"]
+HEADERS = ["arp_internal.h", "emit_plan.h", "host_common.h", "engine.h", "debug_knobs.h", "scan.inl", "grid.inl", "pairs.inl", "pairs_emit.inl", "batch.inl", "sap.inl", "sasa.inl", "ens.inl", "seg.inl", "sc.inl", "freq.inl", "freq_rings.inl", "timeline.inl", "similarity.inl", "table.h", "table_dev.h", "table_plan.h", "../../include/arpeggia_amd.h"]
 TEST_HEADERS = ["../../tests/hosttable/table_host.inl"]  # only the test library (build_host_table_library) contains it: not part of the product's hash
 STAMP = PKG / "build" / "libarpeggia_amd.sha256"  # hash of every source + the flags the library was last built from
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-fvisibility=default", "-Wall", "-Wno-unused-result",
@@ -95,6 +95,20 @@ def build_host_table_library(force: bool = False) -> Path:
     subprocess.run([cc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", str(HOST_TABLE_LIB), "-lpthread"], check=True)
     stamp.write_text(want + "\n")
     return HOST_TABLE_LIB
+
+
+SCAN_UNIT_SRC = PKG.parent / "tests" / "scan_unit" / "scan_unit.hip"
+SCAN_UNIT_LIB = SCAN_UNIT_SRC.with_name("libscan_unit.so")
+
+
+def build_scan_unit_library(force: bool = False) -> Path:
+    """TEST-ONLY library: scan.inl alone, with the product's flags, behind two C entry points (tests/test_scan_unit_gpu.py).  Rebuilt when it is
+    missing or older than one of the files it is made of."""
+    made_of = [SCAN_UNIT_SRC, CSRC / "scan.inl", CSRC / "arp_internal.h", CSRC / "debug_knobs.h", CSRC / "emit_plan.h", PKG.parent / "include" / "arpeggia_amd.h"]
+    if not force and SCAN_UNIT_LIB.exists() and all(SCAN_UNIT_LIB.stat().st_mtime >= f.stat().st_mtime for f in made_of):
+        return SCAN_UNIT_LIB
+    subprocess.run([hipcc(), *FLAGS, "-I", str(CSRC), "-shared", str(SCAN_UNIT_SRC), "-o", str(SCAN_UNIT_LIB)], check=True)
+    return SCAN_UNIT_LIB
 
 
 if __name__ == "__main__":

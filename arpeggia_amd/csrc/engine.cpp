@@ -110,7 +110,7 @@ arp_status arp::ensure_workspace(arp_context *ctx, uint64_t n) {
     (void)hipStreamSynchronize(ctx->stream);
     free_workspace(ctx);
     uint64_t cap = std::max<uint64_t>(n + n / 8, 1024);
-    uint64_t ccap = std::min<uint64_t>(8 * cap + 65536, 0xFFFFFFF0ull);
+    uint64_t ccap = std::min<uint64_t>(8 * cap + 65536, 0xFFFFFFF0ull);  // (a multiple of four either way: k_scan_single reads cell_count in whole 16-byte words, scan.inl scan_tile_load)
     arp_status s = ARP_OK;
     auto A = [&](auto &ptr, size_t cnt) { if (s == ARP_OK) s = dev_alloc(ctx, &ptr, cnt); };  // (after a failure the rest is skipped)
     A(w.partials, 1024 * 8); A(w.tickets, 4); A(w.grid, 1); A(w.params, 1);
@@ -707,7 +707,11 @@ extern "C" arp_status arp_debug_set(const char *key, int64_t value) {
         if (value < 0 || value > 1024 || (value & (value - 1)) != 0) { set_error("arp_debug_set: strip_rows takes 0 or a power of two up to 1024"); return ARP_ERR_BAD_INPUT; }
         g_debug.strip_rows = (int)value;
     }
-    else { set_error("arp_debug_set: unknown key '%s' (timing, emit_kernel, defer_entries, strip_rows, index_bits, table_host, freq_chunk_atoms, freq_cap_items, freq_frame_bits, ens_chunk_atoms, timeline_cap_bytes, similarity_cap_bytes, table_key_bits)", key); return ARP_ERR_BAD_INPUT; }
+    else if (k == "scan_kernel") {
+        if (value < 0 || value > 2) { set_error("arp_debug_set: scan_kernel takes 0 (automatic), 1 (the look-back cell scan on 256 blocks) or 2 (on 1024 blocks)"); return ARP_ERR_BAD_INPUT; }
+        g_debug.scan_kernel = (int)value;
+    }
+    else { set_error("arp_debug_set: unknown key '%s' (timing, emit_kernel, defer_entries, strip_rows, index_bits, scan_kernel, table_host, freq_chunk_atoms, freq_cap_items, freq_frame_bits, ens_chunk_atoms, timeline_cap_bytes, similarity_cap_bytes, table_key_bits)", key); return ARP_ERR_BAD_INPUT; }
     return ARP_OK;
 }
 extern "C" arp_status arp_debug_get(const char *key, int64_t *value) {

@@ -4,7 +4,7 @@
 //   k_cellid   sizes the grid from those (every block for itself, block 0 publishes: no launch of its own for one block's work), then the cell
 //              of every atom + its arrival rank in the cell (one returning atomic per distinct cell of a block).  Inputs of a few thousand
 //              atoms skip k_bounds as well: every block of k_cellid reads all the atoms.  Packed batches size their grid per model in k_setup.
-//   scan       cell_count -> cell_start: one block while the cells fit its registers, two launches beyond; clears cell_count for the next call
+//   scan       cell_count -> cell_start (scan.inl): one block while the cells fit its registers, one look-back launch beyond; clears cell_count for the next call
 //   k_place    emit mode: each atom writes its records straight to slot cell_start + arrival rank (coalesced reads)
 //   k_scatter + k_gather   ordered mode: slots inside a cell follow the atom index, so the emitted order is reproducible
 
@@ -89,8 +89,6 @@ DEVFN float grid_setup(const double lo_in[3], const double hi_in[3], bool empty,
 // (A single launch with an arrival ticket was measured 2-3x slower: the per-block device-scope atomics / write-through
 // stores cost more than the extra launch.)  partials: [kBoundsBlocks][8] doubles = {min xyz, max xyz, models, bad}.
 constexpr uint32_t kBoundsBlocks = 256, kBoundsThreads = 1024;
-constexpr uint32_t kScanBlocks = 1024, kScanThreads = 256, kScanPartAt = 32;  // (the two-launch scan's block decomposition; k_scan_single's chunk totals live behind the 32 result words)
-constexpr uint32_t kScanSingleBlocks = kScanThreads;  // one published word per thread of a later block: a single round of device-scope loads
 struct BoxAcc {
     double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     uint32_t models = 0, bad = 0;
@@ -393,220 +391,6 @@ __global__ __launch_bounds__(kCidThreads, BOX == 0 ? 8 : 4) void k_cellid(DevAto
     for (uint32_t u = 0; u < kCidPer; u++) {
         const uint32_t i = i0 + u * kCidThreads;
         if (i < in.n) { cell_of_atom[i] = c[u]; rank_of_atom[i] = c[u] != ARP_NONE ? t_cnt[slot[u]] + r[u] : 0u; }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------- scan
-// Exclusive scan of in[0..n) (n read from device memory) into out[0..n], out[n] = total, over a fixed 1024-block
-// decomposition so that no host knowledge of n is needed.  Three launches: per-block sums, their scan, the per-block
-// scans (a fused arrival-ticket variant was measured slower).  ZERO_IN clears the input behind itself (cell_count is
-// ready for the next call); FINISH also publishes the pair total and the status flags.
-template <typename TOut>
-DEVFN TOut block_exclusive_scan(TOut v, TOut *total, TOut *lds /* [kScanThreads/64 + 1] */) {
-    TOut inc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        TOut t = __shfl_up(inc, off);
-        if ((threadIdx.x & 63) >= (uint32_t)off) inc += t;
-    }
-    uint32_t w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 63) lds[w] = inc;
-    __syncthreads();
-    TOut wave_off = 0, tot = 0;
-    for (uint32_t k = 0; k < kScanThreads / 64; k++) { TOut s = lds[k]; if (k < w) wave_off += s; tot += s; }
-    *total = tot;
-    return wave_off + inc - v;
-}
-
-template <typename TOut>
-__global__ __launch_bounds__(kScanThreads) void k_scan_reduce(const uint32_t *in, const uint32_t *n_ptr, TOut *tmp) {
-    __shared__ TOut lds[kScanThreads / 64 + 1];
-    const uint32_t n = *n_ptr;
-    const uint32_t chunk = (n + kScanBlocks - 1) / kScanBlocks;
-    const uint32_t lo = min(n, blockIdx.x * chunk), hi = min(n, lo + chunk);
-    TOut s = 0;
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += kScanThreads) s += in[i];
-    TOut tot;
-    block_exclusive_scan<TOut>(s, &tot, lds);
-    if (threadIdx.x == 0) tmp[blockIdx.x] = tot;
-}
-template <typename TOut>
-__global__ __launch_bounds__(kScanThreads) void k_scan_tmp(TOut *tmp) {  // tmp[kScanBlocks] receives the grand total
-    __shared__ TOut lds[kScanThreads / 64 + 1];
-    TOut carry = 0;
-    for (uint32_t base = 0; base < kScanBlocks; base += kScanThreads) {
-        TOut v = tmp[base + threadIdx.x], tot;
-        TOut ex = block_exclusive_scan<TOut>(v, &tot, lds);
-        tmp[base + threadIdx.x] = carry + ex;
-        carry += tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) tmp[kScanBlocks] = carry;
-}
-
-template <typename TOut, bool ZERO_IN, bool FINISH>
-__global__ __launch_bounds__(kScanThreads) void k_scan_apply(uint32_t *in, const uint32_t *n_ptr, const TOut *tmp, TOut *out, const GridParams *g,
-                                                             unsigned long long *result, unsigned long long capacity, int have_out) {
-    __shared__ TOut lds[kScanThreads / 64 + 1];
-    const uint32_t n = *n_ptr;
-    const uint32_t chunk = (n + kScanBlocks - 1) / kScanBlocks;
-    const uint32_t lo = min(n, blockIdx.x * chunk), hi = min(n, lo + chunk);
-    // carry = sum of the partial totals of the blocks before this one, recomputed here from the kScanBlocks raw totals
-    // (4-8 KB out of L2): one launch less than scanning them in a kernel of their own
-    TOut part = 0, all = 0;
-    for (uint32_t k = threadIdx.x; k < kScanBlocks; k += kScanThreads) { const TOut v = tmp[k]; all += v; if (k < blockIdx.x) part += v; }
-    TOut carry, grand = 0;
-    block_exclusive_scan<TOut>(part, &carry, lds);
-    __syncthreads();
-    if (blockIdx.x == 0) { block_exclusive_scan<TOut>(all, &grand, lds); __syncthreads(); }
-    for (uint32_t base = lo; base < hi; base += kScanThreads) {
-        const uint32_t i = base + threadIdx.x;
-        TOut v = (i < hi) ? (TOut)in[i] : (TOut)0, tot;
-        TOut ex = block_exclusive_scan<TOut>(v, &tot, lds);
-        if (i < hi) { out[i] = carry + ex; if (ZERO_IN) in[i] = 0; }
-        carry += tot;
-        __syncthreads();
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const TOut total = grand;
-        out[n] = total;
-        if (FINISH) {  // the pair-count scan also publishes the result word and the status flags
-            result[kResPairs] = (unsigned long long)total;
-            if (have_out && (unsigned long long)total > capacity) result[kResFlags] |= kStatCapacity;
-            if (g->bad & 1u) result[kResFlags] |= kStatNonFinite;
-            if (g->bad & 2u) result[kResFlags] |= kStatSparseModels;
-        }
-    }
-}
-
-// The cell scan of larger inputs in ONE launch (round 5; two before: per-block totals, then carry + apply): every block adds up its chunk and
-// publishes the total as one 64-bit word {1, total}; a block's carry is the sum of the words of the blocks before it, read with device-scope
-// loads as they appear (the words are zeroed by the grid sizing of the same call, a kernel earlier on the stream).  A block only ever waits
-// for blocks with a smaller index -- dispatched before it -- so the wait ends whatever else shares the device; value and flag travel in
-// one atomic word, so nothing else has to become visible with it.
-__global__ __launch_bounds__(kScanThreads) void k_scan_single(uint32_t *in, const uint32_t *n_ptr, unsigned long long *part, uint32_t *out) {
-    __shared__ uint32_t lds[kScanThreads / 64 + 1];
-    const uint32_t n = *n_ptr;
-    const uint32_t chunk = (n + gridDim.x - 1) / gridDim.x;  // (gridDim.x: kScanSingleBlocks, or kScanBlocks for the cell counts of packs and of inputs beyond 2^20 atoms)
-    const uint32_t lo = min(n, blockIdx.x * chunk), hi = min(n, lo + chunk);
-    uint32_t s = 0, own;
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += kScanThreads) s += in[i];
-    block_exclusive_scan<uint32_t>(s, &own, lds);
-    if (threadIdx.x == 0) __hip_atomic_store(&part[blockIdx.x], (1ull << 32) | own, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // thread t waits for the words of blocks t, t + 256, ... (blocks with a smaller index were dispatched earlier); the loads of a round are in
-    // flight together, and only the words that had not appeared yet are asked for again
-    constexpr uint32_t kWordsPer = kScanBlocks / kScanThreads;
-    unsigned long long w[kWordsPer];
-    bool pending = false;
-#pragma unroll
-    for (uint32_t j = 0; j < kWordsPer; j++) {
-        const uint32_t k = threadIdx.x + j * kScanThreads;
-        w[j] = k < blockIdx.x ? __hip_atomic_load(&part[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (1ull << 32);
-    }
-#pragma unroll
-    for (uint32_t j = 0; j < kWordsPer; j++) pending |= (w[j] >> 32) == 0ull;
-    while (pending) {
-        pending = false;
-#pragma unroll
-        for (uint32_t j = 0; j < kWordsPer; j++)
-            if ((w[j] >> 32) == 0ull) { w[j] = __hip_atomic_load(&part[threadIdx.x + j * kScanThreads], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); pending |= (w[j] >> 32) == 0ull; }
-    }
-    uint32_t before = 0, carry;
-#pragma unroll
-    for (uint32_t j = 0; j < kWordsPer; j++) before += (uint32_t)w[j];
-    __syncthreads();
-    block_exclusive_scan<uint32_t>(before, &carry, lds);
-    __syncthreads();
-    if (blockIdx.x == gridDim.x - 1u && threadIdx.x == 0) out[n] = carry + own;  // (the last block's chunk ends at n: the grand total)
-    for (uint32_t base = lo; base < hi; base += kScanThreads) {
-        const uint32_t i = base + threadIdx.x;
-        uint32_t v = (i < hi) ? in[i] : 0u, tot;
-        const uint32_t ex = block_exclusive_scan<uint32_t>(v, &tot, lds);
-        if (i < hi) { out[i] = carry + ex; in[i] = 0; }  // (clears cell_count behind itself: ready for the next call)
-        carry += tot;
-        __syncthreads();
-    }
-}
-
-// The cell scan in ONE launch for inputs whose cells fit one workgroup's registers (launch_grid: up to kScanOneAtoms atoms, i.e. <= 65536
-// cells at the 0.35 cells per atom the grid sizing allows): wave w owns 4096 consecutive cells per pass -- 16 coalesced 16-byte loads per
-// lane, all in flight together --, scans them with the DPP row shifts (no LDS round trips), and one barrier exchanges the 16 wave totals.
-// A sparse input with more cells than that takes further passes (correct, just slower than the two-launch scan the launcher would have
-// picked had it known: the cell count only exists on the device).
-constexpr uint32_t kScanOneThreads = 1024, kScanOnePer = 16, kScanOneCells = kScanOneThreads * kScanOnePer * 4u, kScanOneAtoms = 180000;
-DEVFN uint32_t wave_inclusive_add_u32(uint32_t v) {  // (the scan wave_reduce_u32 is the last lane of)
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);  // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);  // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);  // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);  // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);  // row_bcast:15 -> rows 1, 3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
-    return v;
-}
-// Round 5: launched with kScanOneBlocks blocks.  Block b takes the passes b, b + kScanOneBlocks, ...: the usual input is one pass,
-// which block 0 runs exactly as before while the other blocks read the cell count and leave; a sparse or many-model input of the same atom
-// count (up to 8 n + 64 K cells: ~23 passes at 180 000 atoms) no longer runs them one after the other on one CU.  A pass publishes its total
-// as one word {1, total} (the words k_scan_single uses, zeroed by the grid sizing) and adds up the words of the passes before it.
-constexpr uint32_t kScanOneBlocks = 32;  // >= ceil((8 * kScanOneAtoms + 65536 + 1) / kScanOneCells) = 23 passes
-template <bool ZERO_IN>
-__global__ __launch_bounds__(kScanOneThreads) void k_scan_one(uint32_t *in, const uint32_t *n_ptr, unsigned long long *part, uint32_t *out) {
-    __shared__ uint32_t wave_total[kScanOneThreads / 64];
-    __shared__ uint32_t s_carry;
-    const uint32_t n = *n_ptr, wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t n_pass = (n + kScanOneCells - 1u) / kScanOneCells;
-    if (blockIdx.x == 0u && n_pass == 0u && threadIdx.x == 0u) out[0] = 0u;  // (no cells: the total)
-    for (uint32_t ps = blockIdx.x; ps < n_pass; ps += gridDim.x) {
-        const uint32_t base = ps * kScanOneCells;
-        const uint32_t w0 = base + wave * (kScanOnePer * 256u) + lane * 4u;
-        uint4 v[kScanOnePer];
-#pragma unroll
-        for (uint32_t j = 0; j < kScanOnePer; j++) {
-            const uint32_t i = w0 + j * 256u;
-            v[j] = make_uint4(0u, 0u, 0u, 0u);
-            if (i + 4u <= n) v[j] = *reinterpret_cast<const uint4 *>(in + i);
-            else if (i < n) { v[j].x = in[i]; if (i + 1u < n) v[j].y = in[i + 1u]; if (i + 2u < n) v[j].z = in[i + 2u]; }
-        }
-        uint32_t ex[kScanOnePer], run = 0;  // ex[j]: cells before this lane's four of trip j, inside the wave's stretch
-#pragma unroll
-        for (uint32_t j = 0; j < kScanOnePer; j++) {
-            const uint32_t s = v[j].x + v[j].y + v[j].z + v[j].w, inc = wave_inclusive_add_u32(s);
-            ex[j] = run + inc - s;
-            run += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-        }
-        __syncthreads();  // (the previous pass of this block is done with wave_total / s_carry)
-        if (lane == 0u) wave_total[wave] = run;
-        __syncthreads();
-        uint32_t before = 0, pass = 0;
-        for (uint32_t k = 0; k < kScanOneThreads / 64u; k++) { const uint32_t t = wave_total[k]; if (k < wave) before += t; pass += t; }
-        // the passes before this one (none for the usual single pass): their published totals, read as they appear
-        if (n_pass > 1u) {
-            if (threadIdx.x == 0u) __hip_atomic_store(&part[ps], (1ull << 32) | pass, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (wave == 0u) {
-                uint32_t c = 0;
-                for (uint32_t k = lane; k < ps; k += 64u) {
-                    unsigned long long w;
-                    do { w = __hip_atomic_load(&part[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while ((w >> 32) == 0ull);
-                    c += (uint32_t)w;
-                }
-                c = wave_inclusive_add_u32(c);
-                if (lane == 63u) s_carry = c;
-            }
-            __syncthreads();
-            before += s_carry;
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < kScanOnePer; j++) {
-            const uint32_t i = w0 + j * 256u, o = before + ex[j];
-            const uint4 r = make_uint4(o, o + v[j].x, o + v[j].x + v[j].y, o + v[j].x + v[j].y + v[j].z);
-            if (i + 4u <= n) {
-                *reinterpret_cast<uint4 *>(out + i) = r;
-                if (ZERO_IN) *reinterpret_cast<uint4 *>(in + i) = make_uint4(0u, 0u, 0u, 0u);
-            } else if (i < n) {
-                out[i] = r.x; if (i + 1u < n) out[i + 1u] = r.y; if (i + 2u < n) out[i + 2u] = r.z;
-                if (ZERO_IN) { in[i] = 0u; if (i + 1u < n) in[i + 1u] = 0u; if (i + 2u < n) in[i + 2u] = 0u; }
-            }
-        }
-        if (ps + 1u == n_pass && threadIdx.x == 0u) out[n] = (n_pass > 1u ? s_carry : 0u) + pass;  // the last pass holds the grand total
     }
 }
 

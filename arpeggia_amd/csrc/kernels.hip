@@ -57,6 +57,7 @@ DEVFN uint32_t wave_max_u32(uint32_t v) { return wave_reduce_u32<true>(v); }
 DEVFN void wave_lds_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
 
 // ---------------------------------------------------------------------------------------------- grid build, scan, sort
+#include "scan.inl"
 #include "grid.inl"
 
 // ---------------------------------------------------------------------------------------------- per-pair rules

@@ -535,7 +535,8 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void k_patch_deferred(DevAtoms
 // is filled with a valid record from [P, R).  No sorting is needed: a hole is the tail of ONE 2048-record chunk, so the
 // valid records above P are described by a per-chunk table over the <= n_holes + 1 chunks that [P, R) spans, and the
 // hole slots below P by the holes themselves in any order.  Each block rebuilds that (tiny) plan in LDS -- two
-// 2048-wide scans, two entries per thread -- and then takes part in a grid-stride copy.
+// 2048-wide scans, two entries per thread -- and then copies its waves' share of the slots to fill (one flat index space
+// over the launch, below; measured in profiles/r26_small_kernels.md).
 constexpr uint32_t kFixThreads = 1024;
 constexpr uint32_t kMaxHoles = 2 * kFixThreads;  // the launches keep emit blocks + deferred blocks < kMaxHoles
 DEVFN unsigned long long scan1024_u64(unsigned long long v, unsigned long long *red, unsigned long long *total) {
@@ -602,38 +603,58 @@ __global__ __launch_bounds__(kFixThreads) void k_fixup(const ulonglong2 *hole_li
         if (no_deferred_pass && result[kResDeferred] != 0ull) result[kResFlags] |= kStatStaleSkip;
     }
     if (P > tg.capacity || F != T) return;  // the caller's buffer cannot hold the table: report the size only
-    // The copy.  List entry e with a part of f = fpre[e + 1] - fpre[e] slots below P takes the records fpre[e] .. fpre[e] + f of the tail's
-    // valid stretches.  A block owns the entries e = blockIdx.x + j * gridDim.x (j < kFixPer: two or three real holes of a 4096-record
-    // chunk at most); wave j finds the tail chunk of entry j's first record by ONE binary search (every lane the same LDS words: broadcast
-    // reads), then all threads run over the block's slots as ONE flat index space -- every iteration independent, so the loads of a
-    // thread's six or so records are in flight together (hole after hole, each copy waited for the previous hole's round trip to memory).
-    constexpr uint32_t kFixPer = kMaxHoles / 256u;
-    __shared__ unsigned long long b_m0[kFixPer], b_pre[kFixPer + 1], b_dst[kFixPer];
-    __shared__ uint32_t b_chunk[kFixPer];
-    if (gridDim.x * kFixPer < kMaxHoles) return;  // (launched with 256 blocks)
-    const uint32_t wv = i >> 6;
-    if (wv < kFixPer) {
-        const uint32_t e = blockIdx.x + wv * gridDim.x;
-        const unsigned long long m0 = fpre[e];
-        uint32_t lo = 0, hi = kMaxHoles;  // last k with tpre[k] <= m0 (zero-length stretches are skipped by taking the last one)
-        while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (tpre[mid] <= m0) lo = mid; else hi = mid; }
-        if ((i & 63u) == 0u) { b_m0[wv] = m0; b_dst[wv] = fstart[e]; b_chunk[wv] = lo; b_pre[wv + 1] = fpre[e + 1] - m0; }
+    // The copy.  The F slots to fill are ONE flat index space over the whole launch: slot q lies in the list entry e with fpre[e] <= q < fpre[e + 1]
+    // (destination fstart[e] + q - fpre[e]) and takes record q of the tail's valid stretches (chunk c with tpre[c] <= q < tpre[c + 1]).  Every wave
+    // of the launch takes the same run of `rounds` x 64 consecutive slots, whichever holes it meets (before: a block owned the entries b, b + 256,
+    // ..., so a thread ran two to eight copies depending on the holes its block drew).  A wave finds e and c of its first slot by two binary
+    // searches, run side by side on the same LDS words in every lane (broadcast reads); from there every lane walks forward, a step or two.
+    // A batch of kFixBatch slots per lane first computes all its addresses, then issues all its loads -- from clamped, always valid addresses, so
+    // that none is predicated (grid.inl box_accumulate) -- and only then stores, predicated.  (Written as `*d = *sp` per trip, the code object
+    // waited for each record's load before it issued the next: one round trip to memory per record of a thread.)
+    constexpr uint32_t kFixBatch = 4;
+    static_assert(kMaxHoles == 2048u, "the binary searches below take 11 steps");
+    if (F == 0ull) return;
+    const uint32_t lane = i & 63u, wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(i >> 6));
+    const unsigned long long n_waves = (unsigned long long)gridDim.x * (kFixThreads / 64u);
+    const unsigned long long rounds = (F + n_waves * 64ull - 1ull) / (n_waves * 64ull);
+    const unsigned long long q0 = ((unsigned long long)blockIdx.x * (kFixThreads / 64u) + wv) * rounds * 64ull;
+    if (q0 >= F) return;  // (no barrier below)
+    const unsigned long long q_end = q0 + rounds * 64ull < F ? q0 + rounds * 64ull : F;
+    uint32_t e = 0, e_hi = kMaxHoles, c = 0, c_hi = kMaxHoles;  // last k with fpre[k] <= q0 / tpre[k] <= q0 (both arrays start at 0 and end at F > q0)
+    for (int it = 0; it < 11; it++) {
+        const uint32_t em = (e + e_hi) >> 1, cm = (c + c_hi) >> 1;
+        const bool eb = fpre[em] <= q0, cb = tpre[cm] <= q0;
+        e = eb ? em : e; e_hi = eb ? e_hi : em;
+        c = cb ? cm : c; c_hi = cb ? c_hi : cm;
     }
-    __syncthreads();
-    if (i == 0) { unsigned long long run = 0; b_pre[0] = 0; for (uint32_t j = 0; j < kFixPer; j++) { run += b_pre[j + 1]; b_pre[j + 1] = run; } }
-    __syncthreads();
-    const unsigned long long total = b_pre[kFixPer];
-    for (unsigned long long q = i; q < total; q += kFixThreads) {
-        uint32_t j = 0;
+    rec_u32x4 *const out = reinterpret_cast<rec_u32x4 *>(tg.out), *const scratch = reinterpret_cast<rec_u32x4 *>(tg.scratch);  // (a native vector: the record array below stays in registers)
+    bool miss = false;
+    for (unsigned long long qb = q0; qb < q_end; qb += 64ull * kFixBatch) {
+        rec_u32x4 *d[kFixBatch];
+        const rec_u32x4 *sp[kFixBatch];
+        bool ok[kFixBatch];
 #pragma unroll
-        for (uint32_t k = 1; k < kFixPer; k++) j += (b_pre[k] <= q) ? 1u : 0u;  // (b_pre is non-decreasing: the count is the index)
-        const unsigned long long r = q - b_pre[j], m = b_m0[j] + r;
-        uint32_t c = b_chunk[j];
-        while (c + 1u < kMaxHoles && tpre[c + 1u] <= m) c++;
-        uint4 *d = emit_slot(tg, b_dst[j] + r, result);
-        const uint4 *sp = emit_slot(tg, tail_start(c) + (m - tpre[c]), result);
-        if (d && sp) *d = *sp;
+        for (uint32_t k = 0; k < kFixBatch; k++) {
+            const unsigned long long q = qb + 64ull * k + lane;
+            const bool live = q < q_end;
+            const unsigned long long qc = live ? q : q_end - 1ull;  // (non-decreasing in k: e and c only ever move forward)
+            while (fpre[e + 1u] <= qc) e++;  // (ends at e + 1 = kMaxHoles at the latest: fpre[kMaxHoles] = F > qc; zero-length entries are passed over)
+            while (tpre[c + 1u] <= qc) c++;
+            const unsigned long long dpos = fstart[e] + (qc - fpre[e]), spos = tail_start(c) + (qc - tpre[c]);  // dpos < P <= capacity
+            const bool in_out = spos < tg.capacity, in_scratch = !in_out && spos - tg.capacity < tg.scratch_cap;
+            d[k] = out + dpos;
+            sp[k] = in_out ? out + spos : (in_scratch ? scratch + (spos - tg.capacity) : out);  // (out[0] exists: F > 0 puts a hole below P)
+            ok[k] = live & (in_out | in_scratch);
+            miss |= live & !(in_out | in_scratch);  // the record never had a home (emit_slot raised the flag when it was dropped): raise it again
+        }
+        rec_u32x4 rec[kFixBatch];
+#pragma unroll
+        for (uint32_t k = 0; k < kFixBatch; k++) rec[k] = *sp[k];
+#pragma unroll
+        for (uint32_t k = 0; k < kFixBatch; k++)
+            if (ok[k]) *d[k] = rec[k];
     }
+    if (miss) atomicOr(&result[kResFlags], kStatCapacity);
 }
 
 // ---------------------------------------------------------------------------------------------- profiler + launch
@@ -697,8 +718,9 @@ void launch_grid(const DevAtoms &in, const Workspace &ws, hipStream_t st, Profil
     }
     P1();
     P0("grid_scan");
-    if (!in.per_model && n <= kScanOneAtoms) hipLaunchKernelGGL(k_scan_one<true>, dim3(kScanOneBlocks), dim3(kScanOneThreads), 0, st, ws.cell_count, (const uint32_t *)&ws.grid->ncells, ws.result + kScanPartAt, ws.cell_start);
-    else hipLaunchKernelGGL(k_scan_single, dim3(in.per_model || n > kCidFoldAtoms ? kScanBlocks : kScanSingleBlocks), dim3(kScanThreads), 0, st, ws.cell_count, (const uint32_t *)&ws.grid->ncells,
+    const int scan_knob = g_debug.scan_kernel;  // (arp_debug_set "scan_kernel": 1 / 2 send any input through the look-back scan on 256 / 1 024 blocks)
+    if (!scan_knob && !in.per_model && n <= kScanOneAtoms) hipLaunchKernelGGL(k_scan_one<true>, dim3(kScanOneBlocks), dim3(kScanOneThreads), 0, st, ws.cell_count, (const uint32_t *)&ws.grid->ncells, ws.result + kScanPartAt, ws.cell_start);
+    else hipLaunchKernelGGL(k_scan_single, dim3(scan_knob == 2 || (!scan_knob && (in.per_model || n > kCidFoldAtoms)) ? kScanBlocks : kScanSingleBlocks), dim3(kScanThreads), 0, st, ws.cell_count, (const uint32_t *)&ws.grid->ncells,
                             ws.result + kScanPartAt, ws.cell_start);  // (256 blocks: one round of one word per thread; packs and the largest inputs have tens of MB of cells: 1024)
     P1();
     P0("grid_sort");

@@ -153,6 +153,8 @@ typedef struct arp_table arp_table;         /* the 20-column contact table (mod.
  *   "index_bits"    the narrow (32-byte) exact record of the single-pass emitter: 0 (default): its index width follows the input size; N = 1 .. 20: N index bits
  *                      (an input whose last index does not fit them keeps the wide record); N < 0: the wide record always.  Same list either way -- lets the
  *                      suite run the wide-index fallback on small inputs
+ *   "scan_kernel"   the scan of the cell counts: 0 (default): chosen by input size; 1: the look-back scan of large inputs on 256 blocks; 2: the same on
+ *                      1024 blocks (the shape of packs and of inputs beyond 2^20 atoms).  Same grid either way -- lets the suite run it on small inputs
  *   "table_host"    1: only in the test library built with -DARP_WITH_HOST_TABLE (tests/hosttable): arp_get_contacts assembles the table on the host
  *   "freq_chunk_atoms" N > 0: arp_contact_frequencies runs its frames in passes of N atoms (whole frames, at least one per pass), so that tests can
  *                      force several passes; 0 (default): about 2 x 10^6 atoms per pass
