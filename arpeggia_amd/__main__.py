@@ -9,6 +9,8 @@ residue pair and interaction (a model counts once however many of the residues' 
 last_frame, n_events, longest_run, mean_run: when the contact exists across the models -- and, with --bitmap FILE.npy, the rows' frame bitmap.
 `contact-similarity` (no counterpart either) takes the flags of `contact-timeline` without --bitmap, plus --axis frames|rows and --metric tanimoto|count:
 it writes `contact-frequency`'s table and, with --matrix FILE.npy, the matrix between the models (or between the rows).
+`contact-autocorrelation` (no counterpart either) takes the flags of `contact-timeline` without --bitmap, plus --mode intermittent|continuous and --max-lag N:
+it writes `contact-frequency`'s table with one more column, half_life, and, with --matrix FILE.npy, the per-row counts, with --curves FILE.csv the curves.
 `sasa-ensemble` and `sap-ensemble` (no counterpart either) take the flags and defaults of `sasa` / `sap` without --model: statistics over the models.
 `dsasa --level atom|residue` writes the interface row by row (default `total`: the reference's scalar); `dsasa-ensemble` takes the flags of
 `sasa-ensemble` and -g: dSASA per model and the per-atom statistics of the buried surface.
@@ -85,6 +87,24 @@ def build_parser() -> argparse.ArgumentParser:
     sm.add_argument("--axis", default="frames", choices=("frames", "rows"), help="Compare the models with each other (frames), or the table's rows (rows)")
     sm.add_argument("--metric", default="tanimoto", choices=("tanimoto", "count"), help="Tanimoto coefficient (float32), or the size of the intersection (uint32)")
     sm.add_argument("--matrix", default=None, type=Path, metavar="FILE.npy", help="Write the [M, M] matrix: M = models (--axis frames) or rows of the table (--axis rows)")
+    ac = sub.add_parser("contact-autocorrelation", help="how long each contact lives across the models: autocorrelation / survival counts per lag, half-lives")
+    ac.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file whose models are the frames")
+    ac.add_argument("-o", "--output", required=True, type=Path, help="Output directory")
+    ac.add_argument("-g", "--groups", default="/", help="Chain groups, e.g. A,B/C,D ('/' = all against all)")
+    ac.add_argument("-f", "--filename", default="contact_autocorrelation", help="Name of the output file")
+    ac.add_argument("-t", "--output-format", default="csv", type=str.lower, choices=FORMATS, help="Output file type")
+    ac.add_argument("-c", "--vdw-comp", default=0.1, type=float, help="Compensation factor for VdW radii dependent interaction types")
+    ac.add_argument("-d", "--dist-cutoff", default=6.5, type=float, help="Distance cutoff when searching for neighboring atoms")
+    ac.add_argument("-j", "--num-threads", default=1, type=int, help="Number of threads (accepted; the computation runs on the GPU)")
+    ac.add_argument("--ignore-zero-occupancy", action="store_true", help="Ignore atoms with zero occupancy")
+    ac.add_argument("--rings", action="store_true", help="Add the ring rows (CationPi, Pi stackings) of every model; ring-ring rows do not depend on --dist-cutoff")
+    ac.add_argument("-l", "--level", default="atom", choices=("atom", "residue"),
+                    help="Rows per atom pair, or per residue pair (a model counts once however many of the residues' atoms are in contact)")
+    ac.add_argument("--mode", default="intermittent", choices=("intermittent", "continuous"),
+                    help="Count the models f where the contact exists in f and in f + lag (intermittent), or in every model from f to f + lag (continuous)")
+    ac.add_argument("--max-lag", default=None, type=int, metavar="N", help="Largest lag (default: models - 1)")
+    ac.add_argument("--matrix", default=None, type=Path, metavar="FILE.npy", help="Write the per-row counts: uint32 [rows, max lag + 1]")
+    ac.add_argument("--curves", default=None, type=Path, metavar="FILE.csv", help="Write the window-corrected curve per interaction: lag, one column per interaction present")
     common = dict(model=("-m", "--model", 0, int, "Model number to analyze (0: the first model)"),
                   probe=("-r", "--probe-radius", 1.4, float, "Probe radius in Angstroms"),
                   points=("-n", "--num-points", 100, int, "Number of points for surface calculation"),
@@ -390,6 +410,39 @@ def run_contact_similarity(args) -> int:
     return 0
 
 
+def run_contact_autocorrelation(args) -> int:
+    import numpy as np
+
+    import arpeggia_amd as aa
+    from arpeggia_amd import api
+
+    if not args.input.exists():
+        log.error("Failed to retrieve input file: %s", args.input)
+        return 1
+    try:
+        table, cols = api._contact_autocorrelation_arrow(str(args.input.resolve()), args.groups, args.vdw_comp, args.dist_cutoff, args.ignore_zero_occupancy, args.rings,
+                                                         args.level, args.mode, args.max_lag, args.matrix is not None)
+    except (aa.ArpeggiaError, ValueError) as e:
+        log.error("Contact autocorrelation failed: %s", e)
+        return 1
+    args.output.mkdir(parents=True, exist_ok=True)
+    out = (args.output / args.filename).with_suffix("." + args.output_format)
+    write_table(table, out, args.output_format)
+    if args.matrix is not None:
+        args.matrix.parent.mkdir(parents=True, exist_ok=True)
+        with open(args.matrix, "wb") as f:  # (np.save on a name would append .npy to any other suffix)
+            np.save(f, cols["autocorrelation"])
+    if args.curves is not None:
+        args.curves.parent.mkdir(parents=True, exist_ok=True)
+        names = list(cols["by_interaction"])
+        with open(args.curves, "w") as f:
+            f.write(",".join(["lag"] + names) + "\n")
+            for k, lag in enumerate(cols["lags"]):
+                f.write(",".join([str(int(lag))] + [repr(float(cols["by_interaction"][n]["curve"][k])) for n in names]) + "\n")
+    log.info("Results for %d contacts saved to %s", len(table), out)
+    return 0
+
+
 def main(argv=None) -> int:
     logging.basicConfig(level=logging.INFO, format="%(levelname)s %(message)s", stream=sys.stderr)
     args = build_parser().parse_args(argv)
@@ -403,6 +456,8 @@ def main(argv=None) -> int:
         return run_contact_timeline(args)
     if args.command == "contact-similarity":
         return run_contact_similarity(args)
+    if args.command == "contact-autocorrelation":
+        return run_contact_autocorrelation(args)
     return run_contacts(args) if args.command == "contacts" else run_surface(args)
 
 

@@ -86,7 +86,7 @@ def default_params(vdw_comp: float = 0.1, dist_cutoff: float = 6.5, deterministi
 
 
 def debug_set(key: str, value: int):
-    """arp_debug_set: the library's diagnostic switches ("timing", "emit_kernel", "defer_entries", "table_host", "freq_chunk_atoms", "freq_cap_items", "freq_frame_bits", "timeline_cap_bytes", "similarity_cap_bytes", "table_key_bits", ...; include/arpeggia_amd.h)."""
+    """arp_debug_set: the library's diagnostic switches ("timing", "emit_kernel", "defer_entries", "table_host", "freq_chunk_atoms", "freq_cap_items", "freq_frame_bits", "timeline_cap_bytes", "similarity_cap_bytes", "autocorr_cap_bytes", "table_key_bits", ...; include/arpeggia_amd.h)."""
     _check(lib.arp_debug_set(key.encode(), int(value)))
 
 
@@ -386,6 +386,16 @@ class Context:
         owner = _TableOwner(_similarity_table(self, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, axis, metric))
         return _similarity_columns(owner, rings, level, structure, frames)  # (a large matrix is a view of the table's: the table lives as long as it)
 
+    def contact_autocorrelation(self, structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, rings: bool = False,
+                                level: str = "atom", mode: str = "intermittent", max_lag: int | None = None, matrix: bool = True) -> dict:
+        """arp_contact_autocorrelation as a dict: every column contact_frequencies returns for the same arguments (identical bytes), plus `half_life` <f4
+        per row (the smallest lag at which the window-corrected survival has fallen to one half; NaN: none), `autocorrelation` <u4 [rows, L + 1] (a view
+        of the table's block, absent with matrix=False) -- in how many frames the row's contact exists now and `lag` frames on (mode "intermittent"), or
+        without a gap all the way there (mode "continuous") --, `lags` = 0 .. L, `by_interaction` {interaction name: {"counts": <u8 [L + 1], "curve":
+        <f8 [L + 1]}} for the interactions that have rows (curve = counts F / (counts[0] (F - lags))), `mode` and `n_total_frames` = F.  max_lag None: F - 1."""
+        owner = _TableOwner(_autocorr_table(self, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, mode, max_lag, matrix))
+        return _autocorr_columns(owner, rings, level, structure, frames)
+
     def sasa_ensemble(self, structure: Structure, frames=None, chains: str = "", probe_radius: float = 1.4, n_points: int = 100, sap_radius: float | None = None,
                       per_frame: bool = False, radii=None) -> dict:
         """arp_sasa_ensemble as a dict of numpy arrays: per-atom SASA statistics over the frames of an ensemble, and SAP statistics when
@@ -630,6 +640,113 @@ def bit_gram(words, n_bits: int, axis: str = "frames", metric: str = "tanimoto",
     else:
         _check(lib.arp_bit_gram(_context(int(device))._h, *args))
     return out, sizes
+
+
+def _autocorr_flags(mode: str, matrix: bool = True) -> int:
+    if mode not in ("intermittent", "continuous"):
+        raise ValueError(f"mode must be 'intermittent' or 'continuous', got {mode!r}")
+    return (_lib.ARP_ACF_CONTINUOUS if mode == "continuous" else 0) | (0 if matrix else _lib.ARP_ACF_NO_MATRIX)
+
+
+def _max_lag_arg(max_lag) -> int:
+    if max_lag is None:
+        return _lib.ARP_NONE
+    if int(max_lag) < 0 or int(max_lag) >= _lib.ARP_NONE:
+        raise ValueError(f"max_lag must be None or 0 .. 2^32 - 2, got {max_lag!r}")
+    return int(max_lag)
+
+
+def _autocorr_table(ctx: "Context | None", structure: Structure, frames, groups: str, vdw_comp: float, dist_cutoff: float, rings: bool, level: str, mode: str,
+                    max_lag, matrix: bool):
+    """arp_contact_autocorrelation -> table handle (the caller frees it).  ctx None: the inputs are only checked (raises their error, else returns None)."""
+    _check_level(level)
+    flags = _autocorr_flags(mode, matrix) | (_lib.ARP_FREQ_RINGS if rings else 0)
+    n_frames, ptr, keep = _frames_arg(structure, frames, "contact autocorrelation")
+    t = C.c_void_p()
+    _check(lib.arp_contact_autocorrelation(ctx._h if ctx is not None else None, structure._h, int(n_frames), ptr, groups.encode(), float(vdw_comp), float(dist_cutoff),
+                                           flags, 1 if level == "residue" else 0, _max_lag_arg(max_lag), C.byref(t)))
+    return t if ctx is not None else None
+
+
+def _interaction_curves(sums: np.ndarray, n_frames: int) -> dict:
+    """{interaction name: {"counts", "curve"}} of the u64 [n_groups, L + 1] sums, for the interactions with rows (counts[0] > 0): the window-corrected
+    estimator C(lag) = (counts[lag] / (F - lag)) / (counts[0] / F)."""
+    lags = np.arange(sums.shape[1], dtype=np.float64)
+    out = {}
+    for c in range(min(sums.shape[0], len(_lib.INTERACTIONS))):
+        counts = sums[c]
+        if counts[0]:
+            out[_lib.INTERACTIONS[c]] = {"counts": counts.copy(), "curve": counts.astype(np.float64) * n_frames / (counts[0].astype(np.float64) * (n_frames - lags))}
+    return out
+
+
+def _autocorr_arrays(owner: _TableOwner) -> dict:
+    """autocorrelation (a view that keeps the table alive; absent for a table built without its matrix), lags, the sums and the mode of an autocorrelation table."""
+    n_lags, flags, sums, n_groups = C.c_uint64(), C.c_uint32(), C.POINTER(C.c_uint64)(), C.c_uint32()
+    p = lib.arp_table_autocorrelation(owner.t, C.byref(n_lags), C.byref(flags), C.byref(sums), C.byref(n_groups))
+    if not n_lags.value:
+        raise KeyError("autocorrelation")
+    R, K = int(lib.arp_table_rows(owner.t)), int(n_lags.value)
+    out = {"lags": np.arange(K, dtype="<u4"), "mode": "continuous" if flags.value & _lib.ARP_ACF_CONTINUOUS else "intermittent",
+           "sums": _np_from(C.cast(sums, C.c_void_p).value, n_groups.value * K, "<u8").reshape(n_groups.value, K)}
+    if p:
+        if R:
+            buf = (C.c_char * (R * K * 4)).from_address(p)
+            buf._owner = owner  # the ctypes buffer is the array's base: the table lives exactly as long as the array (and its views)
+            out["autocorrelation"] = np.frombuffer(buf, dtype="<u4", count=R * K).reshape(R, K)
+        else:
+            out["autocorrelation"] = np.zeros((0, K), "<u4")
+    return out
+
+
+def _autocorr_columns(owner: _TableOwner, rings: bool, level: str, structure: Structure, frames) -> dict:
+    cols = _freq_columns(owner.t, rings, level)
+    hl = _read_columns(owner.t, (("half_life", "f4"), ("half_life_valid", "u1")))
+    cols["half_life"] = np.where(hl["half_life_valid"] != 0, hl["half_life"], np.float32(np.nan)).astype("<f4")
+    arrays = _autocorr_arrays(owner)
+    F = int(np.asarray(frames).shape[0]) if frames is not None else len(structure.ints("model")) // max(_topology_atoms(structure), 1)
+    cols["by_interaction"] = _interaction_curves(arrays.pop("sums"), F)
+    cols.update(arrays)
+    cols["n_total_frames"] = F
+    return cols
+
+
+def bit_autocorrelation(words, n_bits: int, max_lag: int | None = None, mode: str = "intermittent", group=None, n_groups: int = 0, device: int | None = None,
+                        matrix: bool = True) -> dict:
+    """The autocorrelation of a bitmap of the timeline_words layout, [rows, ceil(n_bits / 32)] <u4, by the definitions of Context.contact_autocorrelation:
+    {"autocorrelation": <u4 [rows, L + 1] (absent with matrix=False), "half_life": <u4 [rows] (0xFFFFFFFF: none), "lags", and with `group` (one group
+    number below n_groups per row) "sums": <u8 [n_groups, L + 1]}.  Bits past n_bits are ignored; max_lag None: n_bits - 1.  device None:
+    arp_bit_autocorr_host, a plain loop on the CPU (the yardstick); a device number: arp_bit_autocorr, the same kernels contact_autocorrelation runs.  For
+    bitmaps that were post-processed on the host (a frame window, the AND of two rows)."""
+    flags = _autocorr_flags(mode)
+    words = np.ascontiguousarray(words, dtype="<u4")
+    W = (int(n_bits) + 31) // 32
+    if words.ndim != 2 or words.shape[1] != W:
+        raise ValueError(f"words must have shape [rows, {W}] for {n_bits} bits, got {list(words.shape)}")
+    rows = words.shape[0]
+    lag_arg = _max_lag_arg(max_lag)
+    L = max(int(n_bits) - 1, 0) if max_lag is None else int(max_lag)
+    u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    ptr = lambda a: (a if a.size else np.zeros(1, a.dtype)).ctypes
+    acf = np.zeros((rows, L + 1), "<u4") if matrix else None
+    half = np.zeros(rows, "<u4")
+    if group is not None:
+        group = np.ascontiguousarray(group, dtype="<u4")
+        if group.shape != (rows,):
+            raise ValueError(f"group must have shape [{rows}], got {list(group.shape)}")
+        sums = np.zeros((int(n_groups), L + 1), "<u8")
+    args = (rows, int(n_bits), ptr(words).data_as(u32p), flags, lag_arg, ptr(group).data_as(u32p) if group is not None else None, int(n_groups),
+            ptr(acf).data_as(u32p) if matrix else None, ptr(sums).data_as(u64p) if group is not None else None, ptr(half).data_as(u32p))
+    if device is None:
+        _check(lib.arp_bit_autocorr_host(*args))
+    else:
+        _check(lib.arp_bit_autocorr(_context(int(device))._h, *args))
+    out = {"half_life": half, "lags": np.arange(L + 1, dtype="<u4")}
+    if matrix:
+        out["autocorrelation"] = acf
+    if group is not None:
+        out["sums"] = sums
+    return out
 
 
 def _frames_arg(structure: Structure, frames, what: str):
@@ -921,6 +1038,37 @@ def contact_similarity(input_file: str, groups: str = "/", vdw_comp: float = 0.1
     _check_level(level)
     _similarity_flags(axis, metric)
     return get_contact_similarity(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings, level=level, axis=axis, metric=metric)
+
+
+def get_contact_autocorrelation(structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, device: int = 0,
+                                rings: bool = False, level: str = "atom", mode: str = "intermittent", max_lag: int | None = None, matrix: bool = True) -> dict:
+    """How long every contact of an ensemble lives and how fast it decays (arp_contact_autocorrelation): the rows of get_contact_frequencies for the same
+    arguments as a dict of numpy columns, identical bytes, plus `half_life` <f4 per row (NaN: none), `autocorrelation` <u4 [rows, L + 1] (absent with
+    matrix=False), `lags`, `by_interaction` {interaction name: {"counts": <u8 [L + 1], "curve": <f8 [L + 1]}}, `mode` and `n_total_frames`.  mode
+    "intermittent": the contact exists now and `lag` frames on; "continuous": and in every frame between.  max_lag None: F - 1.  frames, groups, rings and
+    level as get_contact_frequencies."""
+    _check_level(level)
+    _autocorr_flags(mode, matrix)
+    ctx = _with_context(device, lambda: _autocorr_table(None, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, mode, max_lag, matrix))
+    return ctx.contact_autocorrelation(structure, frames, groups, vdw_comp, dist_cutoff, rings, level, mode, max_lag, matrix)
+
+
+def contact_autocorrelation(input_file: str, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, ignore_zero_occupancy: bool = False,
+                            rings: bool = False, level: str = "atom", mode: str = "intermittent", max_lag: int | None = None, matrix: bool = True) -> dict:
+    """Contact autocorrelation across the models of a multi-model file (the models are the frames): see get_contact_autocorrelation."""
+    _check_level(level)
+    _autocorr_flags(mode, matrix)
+    return get_contact_autocorrelation(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings, level=level, mode=mode,
+                                       max_lag=max_lag, matrix=matrix)
+
+
+def _contact_autocorrelation_arrow(input_file: str, groups: str, vdw_comp: float, dist_cutoff: float, ignore_zero_occupancy: bool, rings: bool, level: str, mode: str,
+                                   max_lag, matrix: bool):
+    """The command line's form of contact_autocorrelation: (Arrow table of the frequency columns + half_life, the dict of _autocorr_columns)."""
+    structure = Structure.load(input_file, ignore_zero_occupancy)
+    ctx = _with_context(0, lambda: _autocorr_table(None, structure, None, groups, vdw_comp, dist_cutoff, rings, level, mode, max_lag, matrix))
+    owner = _TableOwner(_autocorr_table(ctx, structure, None, groups, vdw_comp, dist_cutoff, rings, level, mode, max_lag, matrix))
+    return _arrow_of(owner.t), _autocorr_columns(owner, rings, level, structure, None)
 
 
 def _contact_similarity_arrow(input_file: str, groups: str, vdw_comp: float, dist_cutoff: float, ignore_zero_occupancy: bool, rings: bool, level: str, axis: str,

@@ -109,6 +109,19 @@ void arp::timeline_columns(arp_table *t) {
     add_number(t, "mean_run", "f", t->mean_run.data());
 }
 
+void arp::autocorrelation_columns(arp_table *t) {
+    const size_t n = t->n;
+    t->acf.half_life.resize(n, ARP_NONE);
+    t->half_life.resize(n); t->half_life_valid.resize(n);
+    for (size_t k = 0; k < n; k++) {  // (a lag is below 2^24: exact as f32)
+        const uint32_t h = t->acf.half_life[k];
+        t->half_life_valid[k] = h != ARP_NONE ? 1 : 0;
+        t->half_life[k] = h != ARP_NONE ? (float)h : 0.f;
+    }
+    t->columns.push_back(TableColumn{"half_life", 4, "f", TableColumn::kNullableF32, true, t->half_life.data(), t->half_life_valid.data()});
+    t->columns.push_back(TableColumn{"half_life_valid", 1, "C", TableColumn::kNumber, false, t->half_life_valid.data(), nullptr});
+}
+
 namespace {
 // the fixed-width columns of a device-path table, all at once, on first access
 void materialize_columns(arp_table *t) {
@@ -153,6 +166,17 @@ extern "C" const void *arp_table_similarity(const arp_table *t, uint64_t *m, uin
     static const uint32_t nothing = 0;
     if (sizes) *sizes = t->sim.sizes.empty() ? &nothing : t->sim.sizes.data();
     return t->sim.matrix ? (const void *)t->sim.matrix : (const void *)&nothing;  // (an empty matrix is still a matrix: never NULL)
+}
+
+extern "C" const uint32_t *arp_table_autocorrelation(const arp_table *t, uint64_t *n_lags, uint32_t *flags, const uint64_t **sums, uint32_t *n_groups) {
+    if (!t || !t->autocorr) return nullptr;
+    if (n_lags) *n_lags = t->acf.n_lags;
+    if (flags) *flags = t->acf_flags;
+    static const uint64_t nothing = 0;
+    if (sums) *sums = t->acf.sums.empty() ? &nothing : reinterpret_cast<const uint64_t *>(t->acf.sums.data());
+    if (n_groups) *n_groups = t->acf.n_groups;
+    if (!t->acf.has_matrix) return nullptr;
+    return t->acf.matrix ? t->acf.matrix : reinterpret_cast<const uint32_t *>(&nothing);  // (a matrix without rows is still a matrix)
 }
 
 // ---- Arrow C Data Interface export ----------------------------------------------------------------------------------------------------------

@@ -111,6 +111,13 @@ struct arp_table {
     bool similarity = false;
     uint32_t sim_flags = 0;
     arp::SimilarityHost sim;
+    // contact-autocorrelation table (arp_contact_autocorrelation): a frequency table of either level with one more column, half_life (null: none), that
+    // owns the rows x n_lags counts and the per-interaction sums (arp_table_autocorrelation); the counts are not columns
+    bool autocorr = false;
+    uint32_t acf_flags = 0;
+    arp::AutocorrHost acf;
+    std::vector<float> half_life;
+    std::vector<uint8_t> half_life_valid;
 };
 
 namespace arp {
@@ -120,6 +127,7 @@ namespace arp {
 void contact_columns(arp_table *t);                        // the 20 columns of arp_get_contacts + sc_valid, from_atom / to_atom
 void frequency_columns(arp_table *t, uint32_t side);       // kAtomFreqSide or kResidueFreqSide
 void timeline_columns(arp_table *t);                       // behind frequency_columns: t->tl's statistics + mean_run
+void autocorrelation_columns(arp_table *t);                // behind frequency_columns: half_life, from t->acf.half_life (ARP_NONE: null)
 
 // ---- table_cache.cpp: which entities a structure has, kept with the structure ---------------------------------------------------------------
 // (model serial, chain id, resi, icode, altloc, resn) with the names packed into integers (ids are <= 7 / 3 characters, the

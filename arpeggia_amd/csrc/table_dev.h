@@ -124,6 +124,25 @@ arp_status device_similarity(arp_context *ctx, const FreqJob &job, bool by_rows,
 // the same kernels on a host bitmap of `rows` rows of ceil(n_bits / 32) words (rows > 0, n_bits > 0): out m x m, sizes m
 arp_status device_bit_gram(arp_context *ctx, uint64_t rows, uint64_t n_bits, const uint32_t *words, bool by_rows, bool counts, uint64_t cap_bytes, void *out, uint32_t *sizes);
 
+// Contact autocorrelation (autocorr.inl, arp_contact_autocorrelation / arp_bit_autocorr): the frequency rows of the job and, per row
+// and lag 0 .. L, in how many frames the row's contact exists now and L frames on (intermittent), or all the way there (continuous), with the per-
+// interaction sums and the rows' half-lives (ARP_NONE: none).  want_matrix false: no rows x (L + 1) buffer exists on either side.  cap_bytes: the most the
+// device matrix may take (ARP_ERR_CAPACITY beyond); timeline_cap_bytes: the bitmap's, which never leaves the device.
+struct AutocorrHost {
+    uint64_t n_lags = 0;
+    uint32_t n_groups = 0;
+    bool has_matrix = false;
+    std::shared_ptr<char> owner;         // the block the matrix lives in: pooled pinned memory from 1 MiB on, the heap below
+    uint32_t *matrix = nullptr;          // rows x n_lags, row-major
+    std::vector<unsigned long long> sums;  // n_groups x n_lags
+    std::vector<uint32_t> half_life;     // per row
+};
+arp_status device_autocorrelation(arp_context *ctx, const FreqJob &job, bool continuous, bool want_matrix, uint64_t max_lag, uint64_t timeline_cap_bytes, uint64_t cap_bytes,
+                                  FreqRowsHost *rows, AutocorrHost *out);
+// the same kernels on a host bitmap (rows > 0, max_lag < n_bits): acf rows x (max_lag + 1) (nullable), sums n_groups x (max_lag + 1) (written when group is given), half_life rows
+arp_status device_bit_autocorr(arp_context *ctx, uint64_t rows, uint64_t n_bits, const uint32_t *words, bool continuous, uint64_t max_lag, const uint32_t *group, uint64_t n_groups,
+                               uint64_t cap_bytes, uint32_t *acf, unsigned long long *sums, uint32_t *half_life);
+
 // engine.cpp: the context's stream / device and grow-only scratch (device and pinned host)
 void *context_stream(arp_context *ctx);
 int context_device(arp_context *ctx);

@@ -991,5 +991,6 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
 #include "freq_rings.inl"
 #include "timeline.inl"
 #include "similarity.inl"
+#include "autocorr.inl"
 
 }  // namespace arp

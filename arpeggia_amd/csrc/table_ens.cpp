@@ -1,7 +1,7 @@
-// The ensemble entry points -- contact frequencies, their residue level (3.12), timelines (3.13) and similarity (3.14) --
-// and the host yardsticks of the last two (arp_timeline_stats, arp_bit_gram_host).  One preamble (freq_prepare) checks the call and fills the device
-// job; the device pipelines are freq.inl, timeline.inl and similarity.inl; the table they all return is the level's frequency table (table.cpp's
-// columns), with the timeline columns or the matrix attached.
+// The ensemble entry points -- contact frequencies, their residue level (3.12), timelines (3.13), similarity (3.14) and
+// autocorrelation (3.16) -- and the host yardsticks of the last three (arp_timeline_stats, arp_bit_gram_host, arp_bit_autocorr_host).  One preamble
+// (freq_prepare) checks the call and fills the device job; the device pipelines are freq.inl, timeline.inl, similarity.inl and autocorr.inl; the table
+// they all return is the level's frequency table (table.cpp's columns), with the timeline columns, the matrix or the curves attached.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -86,7 +86,7 @@ struct FreqPrep {
     std::vector<uint32_t> attr;
     FreqRingTopo rt;
     FreqJob job;
-    uint64_t timeline_cap = 0, similarity_cap = 0;   // bytes the bitmap / the matrix may take
+    uint64_t timeline_cap = 0, similarity_cap = 0, autocorr_cap = 0;   // bytes the bitmap / the similarity matrix / the autocorrelation matrix may take
     bool checked_only = false;
 };
 arp_status freq_prepare(const char *what, uint32_t own_flags, int32_t level, arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups,
@@ -162,6 +162,7 @@ arp_status freq_prepare(const char *what, uint32_t own_flags, int32_t level, arp
     }
     p->timeline_cap = g_debug.timeline_cap_bytes > 0 ? (uint64_t)g_debug.timeline_cap_bytes : (1ull << 31);
     p->similarity_cap = g_debug.similarity_cap_bytes > 0 ? (uint64_t)g_debug.similarity_cap_bytes : (1ull << 31);
+    p->autocorr_cap = g_debug.autocorr_cap_bytes > 0 ? (uint64_t)g_debug.autocorr_cap_bytes : (1ull << 31);
     if (n_rings) {
         std::unordered_map<std::string, uint32_t> rank;
         for (size_t k = 0; k < s->chain_ids.size(); k++) rank[s->chain_ids[k]] = (uint32_t)k;
@@ -349,4 +350,92 @@ extern "C" arp_status arp_bit_gram(arp_context *ctx, uint64_t rows, uint64_t n_b
     if (!rows || !n_bits) return arp_bit_gram_host(rows, n_bits, words, flags, out, sizes);  // (no bit to look at: every set is empty)
     const uint64_t cap = g_debug.similarity_cap_bytes > 0 ? (uint64_t)g_debug.similarity_cap_bytes : (1ull << 31);
     return device_bit_gram(ctx, rows, n_bits, words, (flags & ARP_SIM_ROWS) != 0, (flags & ARP_SIM_COUNTS) != 0, cap, out, sizes);
+} ARP_ABI_CATCH
+
+// ---- contact autocorrelation and survival curves across frames (device pipeline: autocorr.inl) ----------------------------------
+extern "C" arp_status arp_contact_autocorrelation(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
+                                                  double dist_cutoff, uint32_t flags, int32_t level, uint32_t max_lag, arp_table **out) try {
+    FreqPrep prep;
+    arp_status st = freq_prepare("contact autocorrelation", ARP_ACF_CONTINUOUS | ARP_ACF_NO_MATRIX, level, ctx, s, n_frames, xyz, groups, vdw_comp, dist_cutoff, flags, out, &prep);
+    if (st != ARP_OK) return st;
+    const uint64_t F = prep.F;
+    if (F > (1ull << 24)) { set_error("contact autocorrelation: F = %llu frames, at most 2^24 are supported (the half-lives are served as f32)", (unsigned long long)F); return ARP_ERR_BAD_INPUT; }
+    if (max_lag != ARP_NONE && max_lag >= F) { set_error("contact autocorrelation: max_lag %u is not below the %llu frames", max_lag, (unsigned long long)F); return ARP_ERR_BAD_INPUT; }
+    if (prep.checked_only) return ARP_OK;
+    const uint64_t L = max_lag == ARP_NONE ? F - 1u : max_lag;
+    FreqRowsHost rows;
+    AutocorrHost acf;
+    if ((st = device_autocorrelation(ctx, prep.job, (flags & ARP_ACF_CONTINUOUS) != 0, !(flags & ARP_ACF_NO_MATRIX), L, prep.timeline_cap, prep.autocorr_cap, &rows, &acf)) != ARP_OK)
+        return st;
+    // the table is the frequency table of the level (the same rows through the same table builder); half_life joins its columns, the counts ride along
+    std::unique_ptr<arp_table> t = freq_table(s, prep, rows);
+    t->autocorr = true;
+    t->acf_flags = flags & (uint32_t)(ARP_ACF_CONTINUOUS | ARP_ACF_NO_MATRIX);
+    t->acf = std::move(acf);
+    autocorrelation_columns(t.get());
+    *out = t.release();
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+namespace {
+arp_status bit_autocorr_args(uint64_t rows, uint64_t n_bits, const uint32_t *words, uint32_t flags, uint32_t max_lag, const uint32_t *group, uint32_t n_groups, const uint64_t *sums,
+                             const uint32_t *half_life, uint64_t *L) {
+    if (flags & ~(uint32_t)ARP_ACF_CONTINUOUS) { set_error("bit autocorrelation: unknown flag bits 0x%x", flags & ~(uint32_t)ARP_ACF_CONTINUOUS); return ARP_ERR_BAD_INPUT; }
+    if (n_bits >= (1ull << 32) || rows >= (1ull << 32)) { set_error("bit autocorrelation: 2^32 or more %s (the counts are u32)", n_bits >= (1ull << 32) ? "bits" : "rows"); return ARP_ERR_BAD_INPUT; }
+    if (n_bits == 0) { set_error("bit autocorrelation: at least one bit per row is needed"); return ARP_ERR_BAD_INPUT; }
+    if (max_lag != ARP_NONE && max_lag >= n_bits) { set_error("bit autocorrelation: max_lag %u is not below the %llu bits", max_lag, (unsigned long long)n_bits); return ARP_ERR_BAD_INPUT; }
+    if ((rows && (!words || !half_life)) || (group && n_groups && !sums)) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    if (group)
+        for (uint64_t r = 0; r < rows; r++)
+            if (group[r] >= n_groups) { set_error("bit autocorrelation: group[%llu] = %u, there are %u groups", (unsigned long long)r, group[r], n_groups); return ARP_ERR_BAD_INPUT; }
+    *L = max_lag == ARP_NONE ? n_bits - 1u : max_lag;
+    return ARP_OK;
+}
+}  // namespace
+
+// The definition on its own (no device): every bit is looked at one by one.  Intermittent: per lag, the frames f with bit f and bit f + lag.  Continuous:
+// every maximal run of length n adds n - lag to each lag below n.  The half-life is the integer predicate of the header, lag by lag.
+extern "C" arp_status arp_bit_autocorr_host(uint64_t rows, uint64_t n_bits, const uint32_t *words, uint32_t flags, uint32_t max_lag, const uint32_t *group, uint32_t n_groups,
+                                            uint32_t *acf, uint64_t *sums, uint32_t *half_life) try {
+    uint64_t L = 0;
+    arp_status st = bit_autocorr_args(rows, n_bits, words, flags, max_lag, group, n_groups, sums, half_life, &L);
+    if (st != ARP_OK) return st;
+    const uint64_t W = (n_bits + 31u) / 32u, n_lags = L + 1u;
+    if (group && sums) std::fill(sums, sums + (uint64_t)n_groups * n_lags, 0ull);
+    std::vector<uint32_t> curve(n_lags);
+    for (uint64_t r = 0; r < rows; r++) {
+        auto bit = [&](uint64_t f) { return (words[r * W + (f >> 5)] >> (f & 31u) & 1u) != 0; };
+        std::fill(curve.begin(), curve.end(), 0u);
+        if (flags & ARP_ACF_CONTINUOUS) {
+            uint64_t run = 0;
+            for (uint64_t f = 0; f <= n_bits; f++) {
+                if (f < n_bits && bit(f)) { run++; continue; }
+                for (uint64_t lag = 0; lag < run && lag <= L; lag++) curve[lag] += (uint32_t)(run - lag);
+                run = 0;
+            }
+        } else {
+            for (uint64_t lag = 0; lag <= L; lag++)
+                for (uint64_t f = 0; f + lag < n_bits; f++)
+                    if (bit(f) && bit(f + lag)) curve[lag]++;
+        }
+        uint32_t half = ARP_NONE;
+        for (uint64_t lag = 1; lag <= L && half == ARP_NONE; lag++)  // 2 acf F <= acf0 (F - lag): the left product halved instead, so that nothing overflows
+            if ((uint64_t)curve[lag] * n_bits <= (((uint64_t)curve[0] * (n_bits - lag)) >> 1)) half = (uint32_t)lag;
+        half_life[r] = half;
+        if (acf) std::copy(curve.begin(), curve.end(), acf + r * n_lags);
+        if (group && sums)
+            for (uint64_t lag = 0; lag <= L; lag++) sums[(uint64_t)group[r] * n_lags + lag] += curve[lag];
+    }
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+extern "C" arp_status arp_bit_autocorr(arp_context *ctx, uint64_t rows, uint64_t n_bits, const uint32_t *words, uint32_t flags, uint32_t max_lag, const uint32_t *group,
+                                       uint32_t n_groups, uint32_t *acf, uint64_t *sums, uint32_t *half_life) try {
+    if (!ctx) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    uint64_t L = 0;
+    arp_status st = bit_autocorr_args(rows, n_bits, words, flags, max_lag, group, n_groups, sums, half_life, &L);
+    if (st != ARP_OK) return st;
+    if (!rows) return arp_bit_autocorr_host(rows, n_bits, words, flags, max_lag, group, n_groups, acf, sums, half_life);  // (no row: only the sums are zeroed)
+    const uint64_t cap = g_debug.autocorr_cap_bytes > 0 ? (uint64_t)g_debug.autocorr_cap_bytes : (1ull << 31);
+    return device_bit_autocorr(ctx, rows, n_bits, words, (flags & ARP_ACF_CONTINUOUS) != 0, L, group, n_groups, cap, acf, reinterpret_cast<unsigned long long *>(sums), half_life);
 } ARP_ABI_CATCH

@@ -168,6 +168,8 @@ typedef struct arp_table arp_table;         /* the 20-column contact table (mod.
  *                      tiny inputs; 0 (default): 2^31 bytes
  *   "similarity_cap_bytes" N > 0: arp_contact_similarity and arp_bit_gram refuse a matrix of more than N bytes (ARP_ERR_CAPACITY), so that tests reach
  *                      the limit on tiny inputs; 0 (default): 2^31 bytes
+ *   "autocorr_cap_bytes" N > 0: arp_contact_autocorrelation and arp_bit_autocorr refuse a device matrix of more than N bytes (ARP_ERR_CAPACITY), so that
+ *                      tests reach the limit on tiny inputs; 0 (default): 2^31 bytes
  *   "table_key_bits" N in 6 .. 64: N stands for the 64 bits of the key word when the contact table chooses its sort passes (one merged key, two or three
  *                      passes) and decides whether the one-launch path may run, so that small inputs reach the plans of wide keys; the passes themselves sort
  *                      on their real widths, and the table's bytes do not change.  0 (default): 64.  Anything else is ARP_ERR_BAD_INPUT (6 is the narrowest pass any structure can
@@ -592,6 +594,52 @@ arp_status arp_bit_gram_host(uint64_t rows, uint64_t n_bits, const uint32_t *wor
 /* The same on the device for a host bitmap: upload, the kernels of arp_contact_similarity, download.  Identical bytes.  The matrix limit of
  * arp_contact_similarity applies (ARP_ERR_CAPACITY). */
 arp_status arp_bit_gram(arp_context *ctx, uint64_t rows, uint64_t n_bits, const uint32_t *words, uint32_t flags, void *out, uint32_t *sizes);
+
+/* ---- contact autocorrelation and survival curves across frames: how long a contact lives -- DESIGN.md section 3.16 ----
+ * Topology, n_frames, xyz, groups, vdw_comp, dist_cutoff and level exactly as arp_contact_timelines defines them, and present[r][f] is that call's:
+ * the same rows in the same order, either level, with or without ARP_FREQ_RINGS.  With F frames, R rows and lags t = 0 .. L, L = max_lag:
+ *   intermittent (default)           acf[r][t] = #{ f : 0 <= f < F - t, present[r][f] and present[r][f + t] }
+ *   continuous (ARP_ACF_CONTINUOUS)  acf[r][t] = #{ f : 0 <= f < F - t, present[r][f] and present[r][f + 1] and ... and present[r][f + t] }
+ *                                    = the sum over the row's maximal runs of max(0, run length - t)
+ * acf[r][0] is the row's "n_frames"; continuous <= intermittent; continuous is 0 from the row's longest run on.
+ *   sums[c][t] = the sum of acf[r][t] over the rows with interaction code c (u64; ARP_N_INTERACTIONS codes)
+ *   half-life of row r = the smallest t in 1 .. L with 2 acf[r][t] F <= acf[r][0] (F - t): where the window-corrected estimator
+ *   C(t) = (acf[t] / (F - t)) / (acf[0] / F) has fallen to one half; none when no lag passes (an always-present row has C = 1 throughout).
+ * max_lag: ARP_NONE means F - 1; a max_lag >= F is ARP_ERR_BAD_INPUT; 0 is legal (one column equal to "n_frames", no half-life).  F > 2^24 is
+ * ARP_ERR_BAD_INPUT with a message that names F (the half-lives are served as f32).
+ * The returned table is the frequency table of the level -- every column has the bytes of arp_contact_frequencies_ex / arp_residue_contact_frequencies for
+ * the same arguments -- plus one column "half_life" (f32, the integral lag; null where there is none), which arp_table_export_arrow appends behind the
+ * frequency columns.  The counts are not columns (arp_table_autocorrelation).
+ * flags: ARP_FREQ_RINGS, ARP_ACF_CONTINUOUS, ARP_ACF_NO_MATRIX (the rows' curves are neither stored on the device nor copied: the sums and the half-lives
+ * only); any other bit -- ARP_TIMELINE_NO_BITMAP too: the bitmap never leaves the device here --, or a level outside {0, 1}, is ARP_ERR_BAD_INPUT.  Every
+ * check, status and message of the frequency calls runs before the device is touched; ctx == NULL runs only the checks, those on max_lag and F included
+ * (ARP_OK, *out = NULL).
+ * Device memory: the timeline call's (its bitmap limit applies), plus R x (L + 1) x 4 bytes for the matrix unless ARP_ACF_NO_MATRIX, and with
+ * ARP_ACF_CONTINUOUS 4 bytes per run of the bitmap (a run list above 2^31 bytes is ARP_ERR_CAPACITY too, and so
+ * are more than 2^24 - 1 lag tiles, rows x ceil((L + 1) / 256): what one launch takes, with or without the matrix).  A matrix above 2^31
+ * bytes (arp_debug_set "autocorr_cap_bytes") is ARP_ERR_CAPACITY, with a message that names rows, lags and bytes; the check runs as soon as R is known,
+ * before anything is allocated for the matrix.  Should acf[r][0] ever differ from the row's "n_frames", the call fails with ARP_ERR_HIP and an "internal
+ * error" message instead of returning a table.  Integer sums and minima only: two calls give identical bytes, whatever the pass size.  Synchronous. */
+#define ARP_ACF_CONTINUOUS 0x10u
+#define ARP_ACF_NO_MATRIX 0x20u
+arp_status arp_contact_autocorrelation(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
+                                       double dist_cutoff, uint32_t flags, int32_t level, uint32_t max_lag, arp_table **out);
+/* The host counts of an autocorrelation table (owned by the table): u32, rows x *n_lags, row-major, *n_lags = L + 1; *flags = the call's ARP_ACF_* bits;
+ * *sums = the u64 sums, *n_groups x *n_lags (all four nullable, and filled for every autocorrelation table).  Returns NULL for a table built with
+ * ARP_ACF_NO_MATRIX and for every other table; never NULL otherwise, a table without rows included. */
+const uint32_t *arp_table_autocorrelation(const arp_table *t, uint64_t *n_lags, uint32_t *flags, const uint64_t **sums, uint32_t *n_groups);
+/* The definition above on any bitmap of the timeline layout (`rows` rows of ceil(n_bits / 32) words), a plain loop over the bits, without a device.
+ * flags: ARP_ACF_CONTINUOUS only.  max_lag as above (ARP_NONE: n_bits - 1).  group (nullable): group[r] < n_groups files row r's counts under sums[group[r]]
+ * (u64, n_groups x (L + 1), zeroed first; not written without group); acf (nullable): u32 rows x (L + 1); half_life: u32 per row, ARP_NONE for none.
+ * Bits past n_bits in a row's last word are ignored.  A null words / half_life with rows > 0, an unknown flag, a max_lag >= n_bits, a group[r] >= n_groups,
+ * and n_bits or rows of 2^32 and more are ARP_ERR_BAD_INPUT.  The CPU yardstick of the device kernels, and a tool for post-processed bitmaps (a frame
+ * window, the AND of two rows). */
+arp_status arp_bit_autocorr_host(uint64_t rows, uint64_t n_bits, const uint32_t *words, uint32_t flags, uint32_t max_lag, const uint32_t *group, uint32_t n_groups,
+                                 uint32_t *acf, uint64_t *sums, uint32_t *half_life);
+/* The same on the device for a host bitmap: upload, the kernels of arp_contact_autocorrelation, download.  Identical bytes.  The matrix limit of
+ * arp_contact_autocorrelation applies when acf is given (ARP_ERR_CAPACITY).  rows == 0 is answered by the host function. */
+arp_status arp_bit_autocorr(arp_context *ctx, uint64_t rows, uint64_t n_bits, const uint32_t *words, uint32_t flags, uint32_t max_lag, const uint32_t *group,
+                            uint32_t n_groups, uint32_t *acf, uint64_t *sums, uint32_t *half_life);
 
 /* ---- SASA and SAP statistics over the frames of an ensemble (MD snapshots, NMR models, conformers of one topology) -- DESIGN.md section 3.8 ----
  * Topology, N, frames and xyz exactly as arp_contact_frequencies defines them: model 0 of `topology` is the topology, frame f is xyz[f]
