@@ -117,21 +117,52 @@ __device__ inline bool compare_residues_d(const ResKeyD &a, const ResKeyD &b, bo
     return !(symmetric && a.in_r && b.in_r && a.in_l && b.in_l && a.chain_rank > b.chain_rank);
 }
 
+// The ring angle rules are decided on the cosine quotient q = dot / (|a| |b|), never on the device's acos, as kernels.hip does for the atom
+// rules: the reference compares rn(fold(rn(acos q)) * 180/pi) with 30 and 60 using the C library's acos, and the device's acos rounds
+// differently next to a threshold (measured: two parallel rings at q = 0.5 exactly are 60 + 1 ulp degrees and a PiParallelInPlaneStacking
+// for the reference; the device's acos made them a PiDisplacedStacking).  The folded angle falls with q on [0, 1] and rises with q on
+// [-1, 0], and rounding keeps both monotone, so "angle <= T" is "q >= P(T) or q <= N(T)" within [-1, 1], and ">= T" the band between two
+// such bounds.  The constants are the extreme doubles the host's acos and fold_deg still put on the stated side, found by bisection;
+// tests/test_ring_edge_host.py re-derives every one.  No double q gives exactly 30 or 60, so `<` and `<=` share their bounds.  `<= 90`
+// holds for every q of [-1, 1].  q NaN (a zero-length vector: 0/0) or outside [-1, 1] (acos NaN) makes every comparison false, here as there.
+constexpr double kCosLe30Pos = 0x1.bb67ae8584cabp-1;   // smallest q > 0 with angle <= 30
+constexpr double kCosLe30Neg = -0x1.bb67ae8584caap-1;  // largest q < 0 with angle <= 30
+constexpr double kCosGe30Pos = 0x1.bb67ae8584caap-1;   // largest q > 0 with angle >= 30
+constexpr double kCosGe30Neg = -0x1.bb67ae8584ca9p-1;  // smallest q < 0 with angle >= 30
+constexpr double kCosLe60Pos = 0x1.0000000000001p-1;   // smallest q > 0 with angle <= 60
+constexpr double kCosLe60Neg = -0x1p-1;                // largest q < 0 with angle <= 60
+constexpr double kCosLt60Pos = 0x1.0000000000001p-1;   // smallest q > 0 with angle < 60
+constexpr double kCosLt60Neg = -0x1p-1;                // largest q < 0 with angle < 60
+__device__ inline bool fold_le30(double q) { return (q >= kCosLe30Pos && q <= 1.0) || (q <= kCosLe30Neg && q >= -1.0); }
+__device__ inline bool fold_ge30(double q) { return q <= kCosGe30Pos && q >= kCosGe30Neg; }
+__device__ inline bool fold_le60(double q) { return (q >= kCosLe60Pos && q <= 1.0) || (q <= kCosLe60Neg && q >= -1.0); }
+__device__ inline bool fold_lt60(double q) { return (q >= kCosLt60Pos && q <= 1.0) || (q <= kCosLt60Neg && q >= -1.0); }
+__device__ inline bool fold_le90(double q) { return q >= -1.0 && q <= 1.0; }
+__device__ inline double point_cos_d(const PlaneD &p, const double q[3]) {  // the quotient point_angle_d hands to acos
+    const double v[3] = {q[0] - p.c[0], q[1] - p.c[1], q[2] - p.c[2]};
+    const double dot = p.n[0] * v[0] + p.n[1] * v[1] + p.n[2] * v[2];
+    return dot / (norm3d(p.n) * norm3d(v));
+}
+__device__ inline double plane_cos_d(const PlaneD &a, const PlaneD &b) {  // the quotient plane_dihedral_d hands to acos
+    const double dot = a.n[0] * b.n[0] + a.n[1] * b.n[1] + a.n[2] * b.n[2];
+    return dot / (norm3d(a.n) * norm3d(b.n));
+}
+
 // The two ring classifications, shared by the table kernels below and the per-frame kernels of freq_rings.inl: one body each, so that a
 // frame's ring items are the table's ring rows by construction.
 // find_cation_pi (aromatic.rs:14-29): q = a positively ionizable atom near the ring; *dist = its distance from the ring centre
 __device__ inline bool cation_pi_d(const PlaneD &pl, const double q[3], double *dist) {
-    const double d = point_dist_d(pl, q), theta = point_angle_d(pl, q);
+    const double d = point_dist_d(pl, q), qt = point_cos_d(pl, q);
     *dist = d;
-    return theta <= 30.0 && d <= 4.5;
+    return fold_le30(qt) && d <= 4.5;  // theta <= 30.0 && d <= 4.5
 }
 // find_pi_pi (aromatic.rs:33-64): the stacking ladder of two rings whose centres are `dist` apart; -1 = none
 __device__ inline int pi_stacking_d(const PlaneD &p1, const PlaneD &p2, double dist) {
-    const double theta = point_angle_d(p1, p2.c), dih = plane_dihedral_d(p1, p2);
+    const double qt = point_cos_d(p1, p2.c), qd = plane_cos_d(p1, p2);  // theta and the dihedral, before the acos
     int code = -1;
-    if (dih <= 30.0) { if (theta <= 30.0) code = ARP_PiSandwichStacking; else if (theta <= 60.0) code = ARP_PiDisplacedStacking; else if (theta <= 90.0) code = ARP_PiParallelInPlaneStacking; }
-    else if (dih <= 60.0) code = ARP_PiTiltedStacking;
-    else if (dih <= 90.0) { if (theta >= 30.0 && theta < 60.0) code = ARP_PiLStacking; else if (dist <= 5.0) code = ARP_PiTStacking; }
+    if (fold_le30(qd)) { if (fold_le30(qt)) code = ARP_PiSandwichStacking; else if (fold_le60(qt)) code = ARP_PiDisplacedStacking; else if (fold_le90(qt)) code = ARP_PiParallelInPlaneStacking; }
+    else if (fold_le60(qd)) code = ARP_PiTiltedStacking;
+    else if (fold_le90(qd)) { if (fold_ge30(qt) && fold_lt60(qt)) code = ARP_PiLStacking; else if (dist <= 5.0) code = ARP_PiTStacking; }
     return code;
 }
 

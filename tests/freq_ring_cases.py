@@ -23,8 +23,8 @@ Frames.  Motif p is in state (f + 3 p) % (number of its states) in frame f:
              80     10     5.5     none
              (40)   (20)   6.5     none (centres more than 6 A apart)
 
-Every state is at least 2 degrees and 0.05 A from every threshold of the ladder: the exact edges belong to the device functions the table path
-shares with these kernels, not to these cases.
+Every state is at least 2 degrees and 0.05 A from every threshold of the ladder.  The thresholds themselves -- on the table path and through these
+kernels, frame by frame -- are the cases of tests/ring_edge_rules.py (tests/test_ring_edge_host.py, tests/test_ring_edge_gpu.py).
 
 expected(case) is the closed form from the schedule: one row per (motif, code) that some frame has, with the count, f32(count / F) divided in f64,
 and the smallest and largest d (h) of those frames.  edges(case, per) says which edges of the two kernels a run with `per` frames per pass reaches.
