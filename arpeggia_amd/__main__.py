@@ -11,6 +11,8 @@ last_frame, n_events, longest_run, mean_run: when the contact exists across the 
 it writes `contact-frequency`'s table and, with --matrix FILE.npy, the matrix between the models (or between the rows).
 `contact-autocorrelation` (no counterpart either) takes the flags of `contact-timeline` without --bitmap, plus --mode intermittent|continuous and --max-lag N:
 it writes `contact-frequency`'s table with one more column, half_life, and, with --matrix FILE.npy, the per-row counts, with --curves FILE.csv the curves.
+`contact-clusters` (no counterpart either) takes the flags of `contact-timeline` without --bitmap, plus --min-similarity X (required) and --max-clusters N: it
+writes `contact-frequency`'s table and, with --assignments FILE.csv, one line per model, with --cluster-counts FILE.npy the per-row counts inside each cluster.
 `sasa-ensemble` and `sap-ensemble` (no counterpart either) take the flags and defaults of `sasa` / `sap` without --model: statistics over the models.
 `dsasa --level atom|residue` writes the interface row by row (default `total`: the reference's scalar); `dsasa-ensemble` takes the flags of
 `sasa-ensemble` and -g: dSASA per model and the per-atom statistics of the buried surface.
@@ -105,6 +107,24 @@ def build_parser() -> argparse.ArgumentParser:
     ac.add_argument("--max-lag", default=None, type=int, metavar="N", help="Largest lag (default: models - 1)")
     ac.add_argument("--matrix", default=None, type=Path, metavar="FILE.npy", help="Write the per-row counts: uint32 [rows, max lag + 1]")
     ac.add_argument("--curves", default=None, type=Path, metavar="FILE.csv", help="Write the window-corrected curve per interaction: lag, one column per interaction present")
+    cl = sub.add_parser("contact-clusters", help="which states the models fall into by their contacts (gromos clusters on the Tanimoto similarity), and each state's centre")
+    cl.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file whose models are the frames")
+    cl.add_argument("-o", "--output", required=True, type=Path, help="Output directory")
+    cl.add_argument("-g", "--groups", default="/", help="Chain groups, e.g. A,B/C,D ('/' = all against all)")
+    cl.add_argument("-f", "--filename", default="contact_clusters", help="Name of the output file")
+    cl.add_argument("-t", "--output-format", default="csv", type=str.lower, choices=FORMATS, help="Output file type")
+    cl.add_argument("-c", "--vdw-comp", default=0.1, type=float, help="Compensation factor for VdW radii dependent interaction types")
+    cl.add_argument("-d", "--dist-cutoff", default=6.5, type=float, help="Distance cutoff when searching for neighboring atoms")
+    cl.add_argument("-j", "--num-threads", default=1, type=int, help="Number of threads (accepted; the computation runs on the GPU)")
+    cl.add_argument("--ignore-zero-occupancy", action="store_true", help="Ignore atoms with zero occupancy")
+    cl.add_argument("--rings", action="store_true", help="Add the ring rows (CationPi, Pi stackings) of every model; ring-ring rows do not depend on --dist-cutoff")
+    cl.add_argument("-l", "--level", default="atom", choices=("atom", "residue"),
+                    help="Rows per atom pair, or per residue pair (a model counts once however many of the residues' atoms are in contact)")
+    cl.add_argument("--min-similarity", required=True, type=float, metavar="X", help="Two models are neighbours when their Tanimoto similarity is at least X (0 .. 1)")
+    cl.add_argument("--max-clusters", default=None, type=int, metavar="N", help="Stop after N clusters; the models left over stay unassigned (default: no limit)")
+    cl.add_argument("--assignments", default=None, type=Path, metavar="FILE.csv",
+                    help="Write one line per model: frame, cluster, is_centre, similarity_to_centre, n_neighbours, size")
+    cl.add_argument("--cluster-counts", default=None, type=Path, metavar="FILE.npy", help="Write in how many models of each cluster a row's contact exists: uint32 [rows, clusters]")
     common = dict(model=("-m", "--model", 0, int, "Model number to analyze (0: the first model)"),
                   probe=("-r", "--probe-radius", 1.4, float, "Probe radius in Angstroms"),
                   points=("-n", "--num-points", 100, int, "Number of points for surface calculation"),
@@ -443,6 +463,41 @@ def run_contact_autocorrelation(args) -> int:
     return 0
 
 
+def run_contact_clusters(args) -> int:
+    import numpy as np
+
+    import arpeggia_amd as aa
+    from arpeggia_amd import api
+
+    if not args.input.exists():
+        log.error("Failed to retrieve input file: %s", args.input)
+        return 1
+    try:
+        table, cols = api._contact_clusters_arrow(str(args.input.resolve()), args.groups, args.vdw_comp, args.dist_cutoff, args.ignore_zero_occupancy, args.rings,
+                                                  args.level, args.min_similarity, args.max_clusters, args.cluster_counts is not None)
+    except (aa.ArpeggiaError, ValueError) as e:
+        log.error("Contact clusters failed: %s", e)
+        return 1
+    args.output.mkdir(parents=True, exist_ok=True)
+    out = (args.output / args.filename).with_suffix("." + args.output_format)
+    write_table(table, out, args.output_format)
+    if args.assignments is not None:
+        args.assignments.parent.mkdir(parents=True, exist_ok=True)
+        centres = set(int(c) for c in cols["centre"])
+        with open(args.assignments, "w") as f:
+            f.write("frame,cluster,is_centre,similarity_to_centre,n_neighbours,size\n")
+            for k in range(cols["n_total_frames"]):
+                left = int(cols["cluster"][k]) == 0xFFFFFFFF
+                f.write(",".join([str(k), "" if left else str(int(cols["cluster"][k])), "1" if k in centres else "0",
+                                  "" if left else repr(float(cols["similarity_to_centre"][k])), str(int(cols["n_neighbours"][k])), str(int(cols["sizes"][k]))]) + "\n")
+    if args.cluster_counts is not None:
+        args.cluster_counts.parent.mkdir(parents=True, exist_ok=True)
+        with open(args.cluster_counts, "wb") as f:  # (np.save on a name would append .npy to any other suffix)
+            np.save(f, cols["cluster_counts"])
+    log.info("Results for %d contacts in %d clusters saved to %s", len(table), cols["n_clusters"], out)
+    return 0
+
+
 def main(argv=None) -> int:
     logging.basicConfig(level=logging.INFO, format="%(levelname)s %(message)s", stream=sys.stderr)
     args = build_parser().parse_args(argv)
@@ -458,6 +513,8 @@ def main(argv=None) -> int:
         return run_contact_similarity(args)
     if args.command == "contact-autocorrelation":
         return run_contact_autocorrelation(args)
+    if args.command == "contact-clusters":
+        return run_contact_clusters(args)
     return run_contacts(args) if args.command == "contacts" else run_surface(args)
 
 

@@ -28,6 +28,7 @@ ARP_SIM_COUNTS = 0x4
 ARP_SIM_ROWS = 0x8
 ARP_ACF_CONTINUOUS = 0x10
 ARP_ACF_NO_MATRIX = 0x20
+ARP_CLUSTER_NO_COUNTS = 0x40
 ARP_RADII_VDW, ARP_RADII_PROTOR = 0, 1
 
 ATTR = dict(
@@ -218,6 +219,10 @@ def _load():
         "arp_table_autocorrelation": (C.c_void_p, [vp, C.POINTER(C.c_uint64), _u32p, C.POINTER(C.POINTER(C.c_uint64)), _u32p]),
         "arp_bit_autocorr_host": (C.c_int32, [C.c_uint64, C.c_uint64, _u32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _u32p, C.POINTER(C.c_uint64), _u32p]),
         "arp_bit_autocorr": (C.c_int32, [vp, C.c_uint64, C.c_uint64, _u32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _u32p, C.POINTER(C.c_uint64), _u32p]),
+        "arp_contact_clusters": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_double, C.c_double, C.c_uint32, C.c_int32, C.c_float, C.c_uint32, C.POINTER(vp)]),
+        "arp_table_clusters": (C.c_void_p, [vp, C.POINTER(C.c_uint64), _u32p, _u32p, C.POINTER(_fp)] + [C.POINTER(_u32p)] * 5),
+        "arp_bit_cluster_host": (C.c_int32, [C.c_uint64, C.c_uint64, _u32p, C.c_uint32, C.c_float, C.c_uint32, _u32p, _fp] + [_u32p] * 6),
+        "arp_bit_cluster": (C.c_int32, [vp, C.c_uint64, C.c_uint64, _u32p, C.c_uint32, C.c_float, C.c_uint32, _u32p, _fp] + [_u32p] * 6),
         "arp_sasa_radius": (C.c_int32, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, _fp]),
         "arp_max_asa": (C.c_float, [C.c_char_p]),
         "arp_residue_is_polar": (C.c_int32, [C.c_char_p]),

@@ -86,7 +86,7 @@ def default_params(vdw_comp: float = 0.1, dist_cutoff: float = 6.5, deterministi
 
 
 def debug_set(key: str, value: int):
-    """arp_debug_set: the library's diagnostic switches ("timing", "emit_kernel", "defer_entries", "table_host", "freq_chunk_atoms", "freq_cap_items", "freq_frame_bits", "timeline_cap_bytes", "similarity_cap_bytes", "autocorr_cap_bytes", "table_key_bits", ...; include/arpeggia_amd.h)."""
+    """arp_debug_set: the library's diagnostic switches ("timing", "emit_kernel", "defer_entries", "table_host", "freq_chunk_atoms", "freq_cap_items", "freq_frame_bits", "timeline_cap_bytes", "similarity_cap_bytes", "autocorr_cap_bytes", "cluster_cap_bytes", "table_key_bits", ...; include/arpeggia_amd.h)."""
     _check(lib.arp_debug_set(key.encode(), int(value)))
 
 
@@ -396,6 +396,17 @@ class Context:
         owner = _TableOwner(_autocorr_table(self, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, mode, max_lag, matrix))
         return _autocorr_columns(owner, rings, level, structure, frames)
 
+    def contact_clusters(self, structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, rings: bool = False,
+                         level: str = "atom", *, min_similarity: float, max_clusters: int | None = None, counts: bool = True) -> dict:
+        """arp_contact_clusters as a dict: every column contact_frequencies returns for the same arguments (identical bytes), plus the gromos clusters of the
+        frames on the neighbour relation tanimoto >= min_similarity -- per frame `cluster` <u4 (0xFFFFFFFF: left over by max_clusters),
+        `similarity_to_centre` <f4 (NaN for a left-over frame), `n_neighbours` <u4 (the frame's neighbours in the full graph, itself included) and `sizes`
+        <u4 (contacts per frame); per cluster `centre` and `cluster_size` <u4; `cluster_counts` <u4 [rows, n_clusters] (in how many frames of each cluster a
+        row is present; absent with counts=False), `n_clusters` and `n_total_frames` = F.  The frame-by-frame matrix never exists: the call also takes the
+        ensembles contact_similarity refuses."""
+        owner = _TableOwner(_cluster_table(self, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, min_similarity, max_clusters, counts))
+        return _cluster_columns(owner, rings, level)
+
     def sasa_ensemble(self, structure: Structure, frames=None, chains: str = "", probe_radius: float = 1.4, n_points: int = 100, sap_radius: float | None = None,
                       per_frame: bool = False, radii=None) -> dict:
         """arp_sasa_ensemble as a dict of numpy arrays: per-atom SASA statistics over the frames of an ensemble, and SAP statistics when
@@ -640,6 +651,91 @@ def bit_gram(words, n_bits: int, axis: str = "frames", metric: str = "tanimoto",
     else:
         _check(lib.arp_bit_gram(_context(int(device))._h, *args))
     return out, sizes
+
+
+def _max_clusters_arg(max_clusters) -> int:
+    if max_clusters is None:
+        return _lib.ARP_NONE
+    if int(max_clusters) < 0 or int(max_clusters) >= _lib.ARP_NONE:
+        raise ValueError(f"max_clusters must be None or 1 .. 2^32 - 2, got {max_clusters!r}")
+    return int(max_clusters)  # (0 is the library's to refuse)
+
+
+def _cluster_table(ctx: "Context | None", structure: Structure, frames, groups: str, vdw_comp: float, dist_cutoff: float, rings: bool, level: str, min_similarity: float,
+                   max_clusters, counts: bool):
+    """arp_contact_clusters -> table handle (the caller frees it).  ctx None: the inputs are only checked (raises their error, else returns None)."""
+    _check_level(level)
+    flags = (_lib.ARP_FREQ_RINGS if rings else 0) | (0 if counts else _lib.ARP_CLUSTER_NO_COUNTS)
+    n_frames, ptr, keep = _frames_arg(structure, frames, "contact clusters")
+    t = C.c_void_p()
+    _check(lib.arp_contact_clusters(ctx._h if ctx is not None else None, structure._h, int(n_frames), ptr, groups.encode(), float(vdw_comp), float(dist_cutoff),
+                                    flags, 1 if level == "residue" else 0, float(min_similarity), _max_clusters_arg(max_clusters), C.byref(t)))
+    return t if ctx is not None else None
+
+
+def _cluster_arrays(owner: _TableOwner) -> dict:
+    """The per-frame and per-cluster arrays of a cluster table (copies) and its counts: a zero-copy view that keeps the table alive from 1 MiB on."""
+    u32p = C.POINTER(C.c_uint32)
+    m, n, flags, sim = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.POINTER(C.c_float)()
+    nn, sizes, centre, csize, counts = u32p(), u32p(), u32p(), u32p(), u32p()
+    p = lib.arp_table_clusters(owner.t, C.byref(m), C.byref(n), C.byref(flags), C.byref(sim), C.byref(nn), C.byref(sizes), C.byref(centre), C.byref(csize), C.byref(counts))
+    if not p:
+        raise KeyError("cluster")
+    F, K, R = int(m.value), int(n.value), int(lib.arp_table_rows(owner.t))
+    addr = lambda q: C.cast(q, C.c_void_p).value
+    out = {"cluster": _np_from(p, F, "<u4"), "similarity_to_centre": _np_from(addr(sim), F, "<f4"), "n_neighbours": _np_from(addr(nn), F, "<u4"),
+           "sizes": _np_from(addr(sizes), F, "<u4"), "centre": _np_from(addr(centre), K, "<u4"), "cluster_size": _np_from(addr(csize), K, "<u4")}
+    if addr(counts):
+        if R * K * 4 >= 1 << 20:
+            buf = (C.c_char * (R * K * 4)).from_address(addr(counts))
+            buf._owner = owner  # the ctypes buffer is the array's base: the table lives exactly as long as the array (and its views)
+            out["cluster_counts"] = np.frombuffer(buf, dtype="<u4", count=R * K).reshape(R, K)
+        else:
+            out["cluster_counts"] = _np_from(addr(counts), R * K, "<u4").reshape(R, K)
+    out["n_clusters"] = K
+    out["n_total_frames"] = F
+    return out
+
+
+def _cluster_columns(owner: _TableOwner, rings: bool, level: str) -> dict:
+    cols = _freq_columns(owner.t, rings, level)
+    cols.update(_cluster_arrays(owner))
+    return cols
+
+
+def bit_cluster(words, n_bits: int, min_similarity: float, axis: str = "frames", max_clusters: int | None = None, device: int | None = None) -> dict:
+    """The gromos clusters of a bitmap of the timeline_words layout, [rows, ceil(n_bits / 32)] <u4, by the definitions of Context.contact_clusters: its bit
+    columns (axis "frames": M = n_bits) or its rows (axis "rows": M = rows) are the sets.  Returns cluster, similarity_to_centre, n_neighbours, sizes [M],
+    centre, cluster_size [n_clusters], n_clusters and, on axis "frames", cluster_counts [rows, n_clusters].  Bits past n_bits are ignored.  device None:
+    arp_bit_cluster_host, plain loops on the CPU (the yardstick); a device number: arp_bit_cluster, the same kernels contact_clusters runs."""
+    flags = _similarity_flags(axis, "tanimoto")
+    words = np.ascontiguousarray(words, dtype="<u4")
+    W = (int(n_bits) + 31) // 32
+    if words.ndim != 2 or words.shape[1] != W:
+        raise ValueError(f"words must have shape [rows, {W}] for {n_bits} bits, got {list(words.shape)}")
+    rows = words.shape[0]
+    M = rows if axis == "rows" else int(n_bits)
+    cap = min(M, _max_clusters_arg(max_clusters))
+    out = {"cluster": np.zeros(M, "<u4"), "similarity_to_centre": np.zeros(M, "<f4"), "n_neighbours": np.zeros(M, "<u4"), "sizes": np.zeros(M, "<u4"),
+           "centre": np.zeros(cap, "<u4"), "cluster_size": np.zeros(cap, "<u4")}
+    n = np.zeros(1, "<u4")
+    counts = np.zeros(rows * cap, "<u4") if axis == "frames" else None
+    u32p = C.POINTER(C.c_uint32)
+    ptr = lambda a, t=u32p: (a if a.size else np.zeros(1, a.dtype)).ctypes.data_as(t)
+    args = (rows, int(n_bits), ptr(words), flags, float(min_similarity), _max_clusters_arg(max_clusters), ptr(out["cluster"]),
+            ptr(out["similarity_to_centre"], C.POINTER(C.c_float)), ptr(out["n_neighbours"]), ptr(out["sizes"]), ptr(out["centre"]), ptr(out["cluster_size"]), ptr(n),
+            ptr(counts) if counts is not None else None)
+    if device is None:
+        _check(lib.arp_bit_cluster_host(*args))
+    else:
+        _check(lib.arp_bit_cluster(_context(int(device))._h, *args))
+    K = int(n[0])
+    out["centre"] = out["centre"][:K].copy()
+    out["cluster_size"] = out["cluster_size"][:K].copy()
+    out["n_clusters"] = K
+    if counts is not None:
+        out["cluster_counts"] = counts[:rows * K].reshape(rows, K).copy()
+    return out
 
 
 def _autocorr_flags(mode: str, matrix: bool = True) -> int:
@@ -1060,6 +1156,35 @@ def contact_autocorrelation(input_file: str, groups: str = "/", vdw_comp: float 
     _autocorr_flags(mode, matrix)
     return get_contact_autocorrelation(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings, level=level, mode=mode,
                                        max_lag=max_lag, matrix=matrix)
+
+
+def get_contact_clusters(structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, device: int = 0, rings: bool = False,
+                         level: str = "atom", *, min_similarity: float, max_clusters: int | None = None, counts: bool = True) -> dict:
+    """Which conformational states an ensemble has, which frame stands for each and which contacts tell them apart (arp_contact_clusters): the rows of
+    get_contact_frequencies for the same arguments as a dict of numpy columns, identical bytes, plus the gromos clusters (Daura et al. 1999) of the frames'
+    contact fingerprints on the neighbour relation tanimoto >= min_similarity: `cluster`, `similarity_to_centre`, `n_neighbours`, `sizes` per frame, `centre`
+    and `cluster_size` per cluster, `cluster_counts` [rows, n_clusters] (absent with counts=False), `n_clusters` and `n_total_frames`.  min_similarity has no
+    default: there is no meaningful one.  max_clusters None: no limit.  frames, groups, rings and level as get_contact_frequencies."""
+    _check_level(level)
+    ctx = _with_context(device, lambda: _cluster_table(None, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, min_similarity, max_clusters, counts))
+    return ctx.contact_clusters(structure, frames, groups, vdw_comp, dist_cutoff, rings, level, min_similarity=min_similarity, max_clusters=max_clusters, counts=counts)
+
+
+def contact_clusters(input_file: str, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, ignore_zero_occupancy: bool = False, rings: bool = False,
+                     level: str = "atom", *, min_similarity: float, max_clusters: int | None = None, counts: bool = True) -> dict:
+    """Contact clusters across the models of a multi-model file (the models are the frames): see get_contact_clusters."""
+    _check_level(level)
+    return get_contact_clusters(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings, level=level,
+                                min_similarity=min_similarity, max_clusters=max_clusters, counts=counts)
+
+
+def _contact_clusters_arrow(input_file: str, groups: str, vdw_comp: float, dist_cutoff: float, ignore_zero_occupancy: bool, rings: bool, level: str, min_similarity: float,
+                            max_clusters, counts: bool):
+    """The command line's form of contact_clusters: (Arrow table of the frequency columns, the dict of _cluster_arrays)."""
+    structure = Structure.load(input_file, ignore_zero_occupancy)
+    ctx = _with_context(0, lambda: _cluster_table(None, structure, None, groups, vdw_comp, dist_cutoff, rings, level, min_similarity, max_clusters, counts))
+    owner = _TableOwner(_cluster_table(ctx, structure, None, groups, vdw_comp, dist_cutoff, rings, level, min_similarity, max_clusters, counts))
+    return _arrow_of(owner.t), _cluster_arrays(owner)
 
 
 def _contact_autocorrelation_arrow(input_file: str, groups: str, vdw_comp: float, dist_cutoff: float, ignore_zero_occupancy: bool, rings: bool, level: str, mode: str,

@@ -179,6 +179,25 @@ extern "C" const uint32_t *arp_table_autocorrelation(const arp_table *t, uint64_
     return t->acf.matrix ? t->acf.matrix : reinterpret_cast<const uint32_t *>(&nothing);  // (a matrix without rows is still a matrix)
 }
 
+extern "C" const uint32_t *arp_table_clusters(const arp_table *t, uint64_t *n_frames, uint32_t *n_clusters, uint32_t *flags, const float **similarity_to_centre,
+                                              const uint32_t **n_neighbours, const uint32_t **sizes, const uint32_t **centre, const uint32_t **cluster_size,
+                                              const uint32_t **cluster_counts) {
+    if (!t || !t->clustered) return nullptr;
+    const ClustersHost &c = t->clusters;
+    static const uint32_t nothing = 0;
+    auto data = [](const std::vector<uint32_t> &v) { return v.empty() ? &nothing : v.data(); };  // (an empty array is still an array: never NULL)
+    if (n_frames) *n_frames = c.m;
+    if (n_clusters) *n_clusters = (uint32_t)c.n_clusters;
+    if (flags) *flags = t->cluster_flags;
+    if (similarity_to_centre) *similarity_to_centre = reinterpret_cast<const float *>(data(c.sim));
+    if (n_neighbours) *n_neighbours = data(c.n_neighbours);
+    if (sizes) *sizes = data(c.sizes);
+    if (centre) *centre = data(c.centre);
+    if (cluster_size) *cluster_size = data(c.cluster_size);
+    if (cluster_counts) *cluster_counts = !c.has_counts ? nullptr : c.counts ? c.counts : &nothing;
+    return data(c.cluster);
+}
+
 // ---- Arrow C Data Interface export ----------------------------------------------------------------------------------------------------------
 namespace {
 constexpr uint64_t kMaxUtf8 = 0x7FFFFFF0ull;  // (rows, or bytes of one string column: the offsets are 32-bit)

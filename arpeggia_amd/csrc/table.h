@@ -118,6 +118,11 @@ struct arp_table {
     arp::AutocorrHost acf;
     std::vector<float> half_life;
     std::vector<uint8_t> half_life_valid;
+    // contact-cluster table (arp_contact_clusters): a frequency table of either level that owns the per-frame and per-cluster arrays and the rows x clusters
+    // counts (arp_table_clusters); none of them is a column
+    bool clustered = false;
+    uint32_t cluster_flags = 0;
+    arp::ClustersHost clusters;
 };
 
 namespace arp {

@@ -143,6 +143,25 @@ arp_status device_autocorrelation(arp_context *ctx, const FreqJob &job, bool con
 arp_status device_bit_autocorr(arp_context *ctx, uint64_t rows, uint64_t n_bits, const uint32_t *words, bool continuous, uint64_t max_lag, const uint32_t *group, uint64_t n_groups,
                                uint64_t cap_bytes, uint32_t *acf, unsigned long long *sums, uint32_t *half_life);
 
+// Contact clusters (cluster.inl, arp_contact_clusters / arp_bit_cluster): the frequency rows of the job and the gromos clusters of its
+// frames on the neighbour relation tanimoto >= min_similarity -- per frame its cluster (ARP_NONE: left over by max_clusters), the bits of its f32 Tanimoto
+// value to the cluster's centre, its neighbours in the full graph and its set size; per cluster its centre and size; and, with want_counts, in how many frames
+// of each cluster every row is present.  Neither the bitmap nor any frame-by-frame matrix leaves the device.  cap_bytes: the most the neighbour bits, and the
+// counts, may take (ARP_ERR_CAPACITY beyond); timeline_cap_bytes: the bitmap's.
+struct ClustersHost {
+    uint64_t m = 0, n_clusters = 0;
+    bool has_counts = false;
+    std::vector<uint32_t> cluster, sim, n_neighbours, sizes;   // per frame
+    std::vector<uint32_t> centre, cluster_size;                // per cluster
+    std::shared_ptr<char> owner;         // the block the counts live in: pooled pinned memory from 1 MiB on, the heap below
+    uint32_t *counts = nullptr;          // rows x n_clusters, row-major
+};
+arp_status device_clusters(arp_context *ctx, const FreqJob &job, float min_similarity, uint32_t max_clusters, bool want_counts, uint64_t timeline_cap_bytes, uint64_t cap_bytes,
+                           FreqRowsHost *rows, ClustersHost *out);
+// the same kernels on a host bitmap (rows > 0, n_bits > 0); by_rows: the word rows are clustered (m = rows, no counts), else the bit columns (m = n_bits)
+arp_status device_bit_cluster(arp_context *ctx, uint64_t rows, uint64_t n_bits, const uint32_t *words, bool by_rows, float min_similarity, uint32_t max_clusters, bool want_counts,
+                              uint64_t cap_bytes, ClustersHost *out);
+
 // engine.cpp: the context's stream / device and grow-only scratch (device and pinned host)
 void *context_stream(arp_context *ctx);
 int context_device(arp_context *ctx);

@@ -1023,5 +1023,6 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
 #include "timeline.inl"
 #include "similarity.inl"
 #include "autocorr.inl"
+#include "cluster.inl"
 
 }  // namespace arp

@@ -1,7 +1,8 @@
-// The ensemble entry points -- contact frequencies, their residue level (3.12), timelines (3.13), similarity (3.14) and
-// autocorrelation (3.16) -- and the host yardsticks of the last three (arp_timeline_stats, arp_bit_gram_host, arp_bit_autocorr_host).  One preamble
-// (freq_prepare) checks the call and fills the device job; the device pipelines are freq.inl, timeline.inl, similarity.inl and autocorr.inl; the table
-// they all return is the level's frequency table (table.cpp's columns), with the timeline columns, the matrix or the curves attached.
+// The ensemble entry points -- contact frequencies, their residue level (3.12), timelines (3.13), similarity (3.14),
+// autocorrelation (3.16) and clusters (3.17) -- and the host yardsticks of the last four (arp_timeline_stats, arp_bit_gram_host, arp_bit_autocorr_host,
+// arp_bit_cluster_host).  One preamble (freq_prepare) checks the call and fills the device job; the device pipelines are freq.inl, timeline.inl,
+// similarity.inl, autocorr.inl and cluster.inl; the table they all return is the level's frequency table (table.cpp's columns), with the timeline columns,
+// the matrix, the curves or the clusters attached.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -350,6 +351,148 @@ extern "C" arp_status arp_bit_gram(arp_context *ctx, uint64_t rows, uint64_t n_b
     if (!rows || !n_bits) return arp_bit_gram_host(rows, n_bits, words, flags, out, sizes);  // (no bit to look at: every set is empty)
     const uint64_t cap = g_debug.similarity_cap_bytes > 0 ? (uint64_t)g_debug.similarity_cap_bytes : (1ull << 31);
     return device_bit_gram(ctx, rows, n_bits, words, (flags & ARP_SIM_ROWS) != 0, (flags & ARP_SIM_COUNTS) != 0, cap, out, sizes);
+} ARP_ABI_CATCH
+
+// ---- clusters of the frames by their contacts (device pipeline: cluster.inl) ---------------------------------------------------
+namespace {
+arp_status cluster_args(const char *what, float min_similarity, uint32_t max_clusters) {
+    if (!(std::isfinite(min_similarity) && min_similarity >= 0.0f && min_similarity <= 1.0f)) {
+        set_error("%s: min_similarity must be a finite value in [0, 1], got %g", what, (double)min_similarity);
+        return ARP_ERR_BAD_INPUT;
+    }
+    if (max_clusters == 0) { set_error("%s: max_clusters must be at least 1 (ARP_NONE: no limit)", what); return ARP_ERR_BAD_INPUT; }
+    return ARP_OK;
+}
+uint64_t cluster_cap() { return g_debug.cluster_cap_bytes > 0 ? (uint64_t)g_debug.cluster_cap_bytes : (1ull << 31); }
+}  // namespace
+
+extern "C" arp_status arp_contact_clusters(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp, double dist_cutoff,
+                                           uint32_t flags, int32_t level, float min_similarity, uint32_t max_clusters, arp_table **out) try {
+    FreqPrep prep;
+    arp_status st = freq_prepare("contact clusters", ARP_CLUSTER_NO_COUNTS, level, ctx, s, n_frames, xyz, groups, vdw_comp, dist_cutoff, flags, out, &prep);
+    if (st != ARP_OK || (st = cluster_args("contact clusters", min_similarity, max_clusters)) != ARP_OK || prep.checked_only) return st;
+    FreqRowsHost rows;
+    ClustersHost clusters;
+    if ((st = device_clusters(ctx, prep.job, min_similarity, max_clusters, !(flags & ARP_CLUSTER_NO_COUNTS), prep.timeline_cap, cluster_cap(), &rows, &clusters)) != ARP_OK) return st;
+    // the table is the frequency table of the level (the same rows through the same table builder); the clusters ride along
+    std::unique_ptr<arp_table> t = freq_table(s, prep, rows);
+    t->clustered = true;
+    t->cluster_flags = flags & (uint32_t)ARP_CLUSTER_NO_COUNTS;
+    t->clusters = std::move(clusters);
+    *out = t.release();
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+namespace {
+struct BitClusterOut { uint32_t *cluster; float *sim; uint32_t *n_neighbours, *sizes, *centre, *cluster_size, *n_clusters, *counts; };
+arp_status bit_cluster_args(uint64_t rows, uint64_t n_bits, const uint32_t *words, uint32_t flags, float min_similarity, uint32_t max_clusters, const BitClusterOut &o) {
+    if (flags & ~(uint32_t)ARP_SIM_ROWS) { set_error("bit cluster: unknown flag bits 0x%x", flags & ~(uint32_t)ARP_SIM_ROWS); return ARP_ERR_BAD_INPUT; }
+    if (n_bits >= (1ull << 32) || rows >= (1ull << 32)) { set_error("bit cluster: 2^32 or more %s (the counts are u32)", n_bits >= (1ull << 32) ? "bits" : "rows"); return ARP_ERR_BAD_INPUT; }
+    arp_status st = cluster_args("bit cluster", min_similarity, max_clusters);
+    if (st != ARP_OK) return st;
+    if ((flags & ARP_SIM_ROWS) && o.counts) { set_error("bit cluster: cluster_counts exist for the bit columns only, not with ARP_SIM_ROWS"); return ARP_ERR_BAD_INPUT; }
+    const uint64_t M = (flags & ARP_SIM_ROWS) ? rows : n_bits;
+    if (!o.n_clusters || (rows && n_bits && !words) || (M && (!o.cluster || !o.sim || !o.n_neighbours || !o.sizes || !o.centre || !o.cluster_size))) {
+        set_error("null argument");
+        return ARP_ERR_BAD_INPUT;
+    }
+    return ARP_OK;
+}
+}  // namespace
+
+// The definition of the clusters on its own (no device): the yardstick of k_bit_adjacency / k_cluster_round / k_cluster_tail / k_cluster_counts.  Every bit is
+// filed under its set as in arp_bit_gram_host, every pair of sets gets its f32 Tanimoto value and its neighbour flag, and the rounds recount the alive
+// neighbours of every alive set from scratch.
+extern "C" arp_status arp_bit_cluster_host(uint64_t rows, uint64_t n_bits, const uint32_t *words, uint32_t flags, float min_similarity, uint32_t max_clusters, uint32_t *cluster,
+                                           float *similarity_to_centre, uint32_t *n_neighbours, uint32_t *sizes, uint32_t *centre, uint32_t *cluster_size, uint32_t *n_clusters,
+                                           uint32_t *cluster_counts) try {
+    const BitClusterOut o{cluster, similarity_to_centre, n_neighbours, sizes, centre, cluster_size, n_clusters, cluster_counts};
+    arp_status st = bit_cluster_args(rows, n_bits, words, flags, min_similarity, max_clusters, o);
+    if (st != ARP_OK) return st;
+    const bool by_rows = (flags & ARP_SIM_ROWS) != 0;
+    const uint64_t W = (n_bits + 31u) / 32u, M = by_rows ? rows : n_bits, N = by_rows ? n_bits : rows, K = (N + 31u) / 32u;
+    *n_clusters = 0;
+    if (!M) return ARP_OK;
+    if (M > 46340u) { set_error("bit cluster: the host definition keeps one byte per pair, %llu sets are too many for it", (unsigned long long)M); return ARP_ERR_CAPACITY; }
+    std::vector<uint32_t> sets(M * K, 0u);
+    for (uint64_t r = 0; r < rows; r++)
+        for (uint64_t f = 0; f < n_bits; f++)
+            if (words[r * W + (f >> 5)] >> (f & 31u) & 1u) {
+                const uint64_t a = by_rows ? r : f, e = by_rows ? f : r;
+                sets[a * K + (e >> 5)] |= 1u << (e & 31u);
+            }
+    for (uint64_t a = 0; a < M; a++) {
+        uint32_t c = 0;
+        for (uint64_t w = 0; w < K; w++) c += (uint32_t)__builtin_popcount(sets[a * K + w]);
+        sizes[a] = c;
+    }
+    auto tanimoto = [&](uint64_t a, uint64_t b) {
+        uint32_t inter = 0;
+        for (uint64_t w = 0; w < K; w++) inter += (uint32_t)__builtin_popcount(sets[a * K + w] & sets[b * K + w]);
+        const uint64_t uni = (uint64_t)sizes[a] + sizes[b] - inter;
+        return uni ? (float)((double)inter / (double)uni) : 1.0f;
+    };
+    std::vector<uint8_t> adj(M * M), alive(M, 1);
+    for (uint64_t a = 0; a < M; a++) {
+        uint32_t n = 0;
+        for (uint64_t b = 0; b < M; b++) n += (adj[a * M + b] = tanimoto(a, b) >= min_similarity);
+        n_neighbours[a] = n;
+    }
+    const uint32_t nan_bits = 0x7FC00000u;
+    for (uint64_t a = 0; a < M; a++) { cluster[a] = ARP_NONE; memcpy(similarity_to_centre + a, &nan_bits, 4); }
+    uint64_t n_alive = M;
+    uint32_t k = 0;
+    while (n_alive && k < max_clusters) {
+        uint64_t c = 0;
+        uint32_t best = 0;
+        for (uint64_t a = 0; a < M; a++) {
+            if (!alive[a]) continue;
+            uint32_t n = 0;
+            for (uint64_t b = 0; b < M; b++) n += alive[b] & adj[a * M + b];
+            if (n > best) { best = n; c = a; }  // (ties: the smallest index stays)
+        }
+        if (best == 1u) {  // nobody has a neighbour left: the rounds from here on take the alive sets one by one, in index order
+            for (uint64_t a = 0; a < M && k < max_clusters; a++)
+                if (alive[a]) { alive[a] = 0; cluster[a] = k; similarity_to_centre[a] = 1.0f; centre[k] = (uint32_t)a; cluster_size[k] = 1u; k++; }
+            break;
+        }
+        uint32_t size = 0;
+        for (uint64_t b = 0; b < M; b++)
+            if (alive[b] && adj[c * M + b]) { alive[b] = 0; cluster[b] = k; similarity_to_centre[b] = tanimoto(b, c); size++; }
+        centre[k] = (uint32_t)c; cluster_size[k] = size;
+        n_alive -= size;
+        k++;
+    }
+    *n_clusters = k;
+    if (cluster_counts) {
+        std::fill(cluster_counts, cluster_counts + rows * k, 0u);
+        for (uint64_t r = 0; r < rows; r++)
+            for (uint64_t f = 0; f < n_bits; f++)
+                if ((words[r * W + (f >> 5)] >> (f & 31u) & 1u) && cluster[f] != ARP_NONE) cluster_counts[r * k + cluster[f]]++;
+    }
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+extern "C" arp_status arp_bit_cluster(arp_context *ctx, uint64_t rows, uint64_t n_bits, const uint32_t *words, uint32_t flags, float min_similarity, uint32_t max_clusters,
+                                      uint32_t *cluster, float *similarity_to_centre, uint32_t *n_neighbours, uint32_t *sizes, uint32_t *centre, uint32_t *cluster_size,
+                                      uint32_t *n_clusters, uint32_t *cluster_counts) try {
+    if (!ctx) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
+    const BitClusterOut o{cluster, similarity_to_centre, n_neighbours, sizes, centre, cluster_size, n_clusters, cluster_counts};
+    arp_status st = bit_cluster_args(rows, n_bits, words, flags, min_similarity, max_clusters, o);
+    if (st != ARP_OK) return st;
+    if (!rows || !n_bits)  // (no bit to look at: every set is empty)
+        return arp_bit_cluster_host(rows, n_bits, words, flags, min_similarity, max_clusters, cluster, similarity_to_centre, n_neighbours, sizes, centre, cluster_size, n_clusters, cluster_counts);
+    ClustersHost c;
+    if ((st = device_bit_cluster(ctx, rows, n_bits, words, (flags & ARP_SIM_ROWS) != 0, min_similarity, max_clusters, cluster_counts != nullptr, cluster_cap(), &c)) != ARP_OK) return st;
+    std::copy(c.cluster.begin(), c.cluster.end(), cluster);
+    memcpy(similarity_to_centre, c.sim.data(), c.m * 4u);
+    std::copy(c.n_neighbours.begin(), c.n_neighbours.end(), n_neighbours);
+    std::copy(c.sizes.begin(), c.sizes.end(), sizes);
+    std::copy(c.centre.begin(), c.centre.end(), centre);
+    std::copy(c.cluster_size.begin(), c.cluster_size.end(), cluster_size);
+    *n_clusters = (uint32_t)c.n_clusters;
+    if (cluster_counts) memcpy(cluster_counts, c.counts, rows * c.n_clusters * 4u);
+    return ARP_OK;
 } ARP_ABI_CATCH
 
 // ---- contact autocorrelation and survival curves across frames (device pipeline: autocorr.inl) ----------------------------------

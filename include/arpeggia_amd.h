@@ -170,6 +170,8 @@ typedef struct arp_table arp_table;         /* the 20-column contact table (mod.
  *                      the limit on tiny inputs; 0 (default): 2^31 bytes
  *   "autocorr_cap_bytes" N > 0: arp_contact_autocorrelation and arp_bit_autocorr refuse a device matrix of more than N bytes (ARP_ERR_CAPACITY), so that
  *                      tests reach the limit on tiny inputs; 0 (default): 2^31 bytes
+ *   "cluster_cap_bytes" N > 0: arp_contact_clusters and arp_bit_cluster refuse neighbour bits, or cluster counts, of more than N bytes (ARP_ERR_CAPACITY), so
+ *                      that tests reach the limit on tiny inputs; 0 (default): 2^31 bytes
  *   "table_key_bits" N in 6 .. 64: N stands for the 64 bits of the key word when the contact table chooses its sort passes (one merged key, two or three
  *                      passes) and decides whether the one-launch path may run, so that small inputs reach the plans of wide keys; the passes themselves sort
  *                      on their real widths, and the table's bytes do not change.  0 (default): 64.  Anything else is ARP_ERR_BAD_INPUT (6 is the narrowest pass any structure can
@@ -640,6 +642,61 @@ arp_status arp_bit_autocorr_host(uint64_t rows, uint64_t n_bits, const uint32_t 
  * arp_contact_autocorrelation applies when acf is given (ARP_ERR_CAPACITY).  rows == 0 is answered by the host function. */
 arp_status arp_bit_autocorr(arp_context *ctx, uint64_t rows, uint64_t n_bits, const uint32_t *words, uint32_t flags, uint32_t max_lag, const uint32_t *group,
                             uint32_t n_groups, uint32_t *acf, uint64_t *sums, uint32_t *half_life);
+
+/* ---- clusters of the frames by their contacts: which states there are, which frame stands for each, which contacts tell them apart -- DESIGN.md section 3.17 ----
+ * Topology, n_frames, xyz, groups, vdw_comp, dist_cutoff and level exactly as arp_contact_similarity defines them on axis "frames", and present[r][f] is that
+ * call's: the same rows in the same order, either level, with or without ARP_FREQ_RINGS.  With F frames and R rows:
+ *   S_f = { r : present[r][f] };  sizes[f] = |S_f|;  tan(f, g) = the f32 Tanimoto value of arp_contact_similarity, bit for bit (1.0f for an empty union)
+ *   neighbours  adj[f][g] <=> tan(f, g) >= min_similarity, compared as f32 values: symmetric, adj[f][f] always -- what the matrix of arp_contact_similarity
+ *               gives when it is compared with min_similarity
+ *   clusters (the method MD users know as gromos: Daura et al. 1999)  all F frames alive, k = 0; while a frame is alive and k < max_clusters:
+ *               n[f] = #{ g alive : adj[f][g] } for every alive f (f itself included; over the frames alive NOW); c = the alive frame with the largest n[f], the
+ *               smallest index among equals; cluster k = { g alive : adj[c][g] } with centre c; its members leave the alive set; k += 1.  C = the final k; the
+ *               cluster sizes do not increase with k.
+ * min_similarity must be finite and in [0, 1]; max_clusters: ARP_NONE means no limit, 0 is ARP_ERR_BAD_INPUT.
+ * Results (arp_table_clusters; none of them is a column): cluster[f] u32 (ARP_NONE for the frames left over when max_clusters ended the loop),
+ * similarity_to_centre[f] f32 = tan(f, centre of its cluster) (1.0f for a centre, the bits 0x7FC00000 for a left-over frame), n_neighbours[f] u32 = n[f] of the
+ * first round (the degree in the full graph, f included), sizes[f] u32, centre[k] and cluster_size[k] u32 (C entries), and cluster_counts[r][k] u32, R x C,
+ * row-major = #{ f : cluster[f] = k and present[r][f] } -- the numerator of row r's frequency inside state k; not computed with ARP_CLUSTER_NO_COUNTS.
+ * No contact in any frame (R = 0): every frame is the empty set, all are mutual neighbours: one cluster with centre 0.
+ * The returned table is the frequency table of the level: every column and the Arrow export have the bytes of arp_contact_frequencies_ex /
+ * arp_residue_contact_frequencies for the same arguments.
+ * flags: ARP_FREQ_RINGS, ARP_CLUSTER_NO_COUNTS; any other bit -- ARP_SIM_ROWS, ARP_SIM_COUNTS and ARP_TIMELINE_NO_BITMAP too --, or a level outside {0, 1}, is
+ * ARP_ERR_BAD_INPUT.  Every check, status and message of the frequency calls runs before the device is touched; ctx == NULL runs only the checks, those on
+ * min_similarity and max_clusters included (ARP_OK, *out = NULL).
+ * Device memory: the timeline call's (its bitmap limit applies; the bitmap is never copied to the host), the transposed bitmap, F x ceil(F / 32) x 4 bytes of
+ * neighbour bits, a few vectors of F entries, and R x C x 4 bytes for the counts.  No F x F matrix of values exists on either side, and the limit of
+ * arp_contact_similarity ("similarity_cap_bytes") does not apply: 10^5 frames are 1.25 GB of neighbour bits.  Neighbour bits above 2^31 bytes
+ * (arp_debug_set "cluster_cap_bytes") are ARP_ERR_CAPACITY, with a message that names F and the bytes; the check runs as soon as R is known, before anything
+ * is allocated for them.  Counts above the same limit are ARP_ERR_CAPACITY too, once C is known and before they are allocated.  Should the cluster sizes not
+ * add up to the assigned frames, or -- with every frame assigned -- a row's counts not add up to its "n_frames", the call fails with ARP_ERR_HIP and an
+ * "internal error" message instead of returning a table.  Integer work and the one IEEE divide: two calls give identical bytes, whatever the pass size.
+ * Synchronous. */
+#define ARP_CLUSTER_NO_COUNTS 0x40u
+arp_status arp_contact_clusters(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
+                                double dist_cutoff, uint32_t flags, int32_t level, float min_similarity, uint32_t max_clusters, arp_table **out);
+/* The host arrays of a cluster table (owned by the table).  Returns cluster[F]; *n_frames = F, *n_clusters = C, *flags = the call's ARP_CLUSTER_* bits, and the
+ * arrays described above: F entries each for similarity_to_centre, n_neighbours and sizes, C for centre and cluster_size, R x C for cluster_counts (every out
+ * pointer nullable).  *cluster_counts is NULL for a table built with ARP_CLUSTER_NO_COUNTS; nothing else is ever NULL for a cluster table.  Returns NULL
+ * for every other table. */
+const uint32_t *arp_table_clusters(const arp_table *t, uint64_t *n_frames, uint32_t *n_clusters, uint32_t *flags, const float **similarity_to_centre,
+                                   const uint32_t **n_neighbours, const uint32_t **sizes, const uint32_t **centre, const uint32_t **cluster_size,
+                                   const uint32_t **cluster_counts);
+/* The definition above on any bitmap of the timeline layout (`rows` rows of ceil(n_bits / 32) words), bit by bit, without a device: ARP_SIM_ROWS clear
+ * clusters the bit columns (the frames of a timeline bitmap: M = n_bits), set clusters the word rows (M = rows).  cluster, similarity_to_centre, n_neighbours
+ * and sizes take M entries; centre and cluster_size take min(M, max_clusters); *n_clusters = C.  cluster_counts (nullable; the bit columns only) takes
+ * rows x min(M, max_clusters) entries and is written as rows x C, row-major.  Bits past n_bits in a row's last word are ignored.  n_bits or rows of 2^32 and
+ * more, any flag but ARP_SIM_ROWS, a min_similarity or max_clusters the call above refuses, cluster_counts with ARP_SIM_ROWS, a null n_clusters, or a null
+ * words or result pointer with M > 0 are ARP_ERR_BAD_INPUT.  The CPU yardstick of the device kernels (one byte per pair: more than 46340 sets are
+ * ARP_ERR_CAPACITY), and a tool for post-processed bitmaps. */
+arp_status arp_bit_cluster_host(uint64_t rows, uint64_t n_bits, const uint32_t *words, uint32_t flags, float min_similarity, uint32_t max_clusters, uint32_t *cluster,
+                                float *similarity_to_centre, uint32_t *n_neighbours, uint32_t *sizes, uint32_t *centre, uint32_t *cluster_size, uint32_t *n_clusters,
+                                uint32_t *cluster_counts);
+/* The same on the device for a host bitmap: upload, the kernels of arp_contact_clusters, download.  Identical bytes.  The limits of arp_contact_clusters
+ * apply (ARP_ERR_CAPACITY).  rows == 0 and n_bits == 0 are answered by the host function. */
+arp_status arp_bit_cluster(arp_context *ctx, uint64_t rows, uint64_t n_bits, const uint32_t *words, uint32_t flags, float min_similarity, uint32_t max_clusters,
+                           uint32_t *cluster, float *similarity_to_centre, uint32_t *n_neighbours, uint32_t *sizes, uint32_t *centre, uint32_t *cluster_size,
+                           uint32_t *n_clusters, uint32_t *cluster_counts);
 
 /* ---- SASA and SAP statistics over the frames of an ensemble (MD snapshots, NMR models, conformers of one topology) -- DESIGN.md section 3.8 ----
  * Topology, N, frames and xyz exactly as arp_contact_frequencies defines them: model 0 of `topology` is the topology, frame f is xyz[f]
