@@ -2,7 +2,7 @@
 
 Public surface mirrors the reference (src/lib.rs:20-34, src/python.rs:31-56) for this one path:
 contacts(), get_contacts(), load_model(), parse_groups(); and sasa(), relative_sasa(), sap_score(), dsasa(), buried_sasa(); and sc(); and
-contact_frequencies(), contact_timelines(), contact_similarity(), contact_autocorrelation(), contact_clusters(), sasa_ensemble(), sap_ensemble() and dsasa_ensemble() across the frames of an ensemble (no counterpart in the reference).  Importing this package loads libarpeggia_amd.so and
+contact_frequencies(), contact_timelines(), contact_similarity(), contact_autocorrelation(), contact_clusters(), sasa_ensemble(), sap_ensemble(), dsasa_ensemble() and sc_ensemble() across the frames of an ensemble (no counterpart in the reference).  Importing this package loads libarpeggia_amd.so and
 fails loudly if the HIP extension has not been built -- there is no CPU fallback.
 """
 from .api import (  # noqa: F401
@@ -18,6 +18,10 @@ from .api import (  # noqa: F401  residue- and chain-level SASA, relative SASA (
     get_residue_sasa_ensemble, max_asa, relative_sasa, sasa_radius, segment_sum,
 )
 from .api import get_sc, get_sc_results, sc, sc_arrays, sc_dots, sc_radius, sc_select  # noqa: F401  shape complementarity (src/sc/)
+from .api import (  # noqa: F401  shape complementarity across the frames of an ensemble
+    SC_ENSEMBLE_COLUMNS, SC_FRAME_COLUMNS, SC_FRAME_STATUS, SC_RESULTS_DTYPE, get_sc_ensemble, sc_arrays_ensemble, sc_dot_atoms, sc_dot_stats, sc_ensemble,
+    sc_frame_table,
+)
 from .api import FREQ_COLUMNS, RESIDUE_FREQ_COLUMNS, contact_frequencies, get_contact_frequencies  # noqa: F401  contact frequencies across the frames of an ensemble
 from .api import TIMELINE_COLUMNS, contact_timelines, get_contact_timelines, timeline_stats, unpack_timeline  # noqa: F401  which frames each contact exists in
 from .api import bit_gram, contact_similarity, get_contact_similarity  # noqa: F401  which frames look alike, which contacts come and go together

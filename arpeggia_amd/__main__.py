@@ -16,6 +16,8 @@ writes `contact-frequency`'s table and, with --assignments FILE.csv, one line pe
 `sasa-ensemble` and `sap-ensemble` (no counterpart either) take the flags and defaults of `sasa` / `sap` without --model: statistics over the models.
 `dsasa --level atom|residue` writes the interface row by row (default `total`: the reference's scalar); `dsasa-ensemble` takes the flags of
 `sasa-ensemble` and -g: dSASA per model and the per-atom statistics of the buried surface.
+`sc-ensemble` (no counterpart either) takes -i, -g, -o, -f, -t: shape complementarity of every model, and with --atoms how often each atom owns a
+trimmed dot of the interface.
 """
 from __future__ import annotations
 
@@ -203,7 +205,38 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("-g", "--groups", required=True, help="Chain groups, e.g. A,B/C,D: both surfaces must be given")
     g.add_argument("-m", "--model", default=0, type=int, dest="model_num", help="Model number to analyze (0: the first model)")
     g.add_argument("-j", "--num-threads", default=0, type=int, help="Number of threads (accepted; the computation runs on the GPU)")
+    ge = sub.add_parser("sc-ensemble", help="shape complementarity of every model of a multi-model file, all models in one pass on the device")
+    ge.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file whose models are the frames")
+    ge.add_argument("-g", "--groups", required=True, help="Chain groups, e.g. A,B/C,D: both surfaces must be given")
+    ge.add_argument("-o", "--output", required=True, type=Path, help="Output directory")
+    ge.add_argument("-f", "--filename", default="sc_ensemble", help="Name of the per-frame output file; with --atoms the per-atom table goes to <filename>_atoms")
+    ge.add_argument("-t", "--output-format", default="csv", type=str.lower, choices=FORMATS, help="Output file type")
+    ge.add_argument("--atoms", action="store_true", help="Also write the per-atom table: in how many frames each atom owns a trimmed dot")
     return ap
+
+
+def run_sc_ensemble(args) -> int:
+    """sc-ensemble: one row per model (SC_FRAME_COLUMNS); a model whose SC fails is a row with its status, not a failure of the command."""
+    import arpeggia_amd as aa
+
+    if not args.input.exists():
+        log.error("Failed to retrieve input file: %s", args.input)
+        return 1
+    if "/" not in args.groups:
+        log.error("Groups must be specified as 'A,B/C,D' with both surfaces defined")
+        return 2
+    try:
+        frames, atoms = aa.sc_ensemble(str(args.input.resolve()), args.groups)
+    except aa.ArpeggiaError as e:
+        log.error("SC calculation failed: %s", e)
+        return 1
+    args.output.mkdir(parents=True, exist_ok=True)
+    out = (args.output / args.filename).with_suffix("." + args.output_format)
+    write_table(frames, out, args.output_format)
+    if args.atoms:
+        write_table(atoms, (args.output / (args.filename + "_atoms")).with_suffix("." + args.output_format), args.output_format)
+    log.info("SC of %d frames saved to %s", len(frames), out)
+    return 0
 
 
 def run_sc(args) -> int:
@@ -503,6 +536,8 @@ def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     if args.command == "sc":
         return run_sc(args)
+    if args.command == "sc-ensemble":
+        return run_sc_ensemble(args)
     if args.command in ("sasa-ensemble", "sap-ensemble", "dsasa-ensemble"):
         return run_ensemble(args)
     if args.command == "contact-frequency":

@@ -182,6 +182,13 @@ def _load():
         "arp_structure_sc": (C.c_int32, [vp, vp, C.c_char_p, C.c_int32, C.POINTER(arp_sc_results)]),
         "arp_structure_sc_select": (C.c_int32, [vp, C.c_char_p, C.c_int32, C.POINTER(C.c_uint64), _u32p, C.POINTER(C.c_uint8)]),
         "arp_sc_dots": (C.c_int32, [vp, C.c_int32, C.c_uint64, C.POINTER(C.c_uint64), _dp, _dp, _dp, _u32p, _dp, _dp]),
+        "arp_sc_dot_atoms": (C.c_int32, [vp, C.c_int32, C.c_uint64, C.POINTER(C.c_uint64), _u32p]),
+        "arp_sc_ensemble": (C.c_int32, [vp, C.c_uint64, C.c_uint64, _dp, _dp, C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(arp_sc_settings),
+                                        C.POINTER(arp_sc_results), _u32p, _u32p, _u32p, C.POINTER(C.c_uint64)]),
+        "arp_structure_sc_ensemble": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _u32p,
+                                                  C.POINTER(C.c_uint8), C.POINTER(arp_sc_results), _u32p, _u32p, _u32p, C.POINTER(C.c_uint64)]),
+        "arp_sc_dot_stats_host": (C.c_int32, [C.c_uint64, C.POINTER(C.c_uint64), _u32p, _dp, _dp, _dp, _u32p, C.POINTER(arp_sc_surface)]),
+        "arp_sc_dot_stats": (C.c_int32, [vp, C.c_uint64, C.POINTER(C.c_uint64), _u32p, _dp, _dp, _dp, _u32p, C.POINTER(arp_sc_surface)]),
         "arp_profile_enable": (C.c_int32, [vp, C.c_int32]),
         "arp_profile_read": (C.c_int32, [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int32]),
         "arp_structure_load": (C.c_int32, [C.c_char_p, C.c_int32, C.POINTER(vp)]),

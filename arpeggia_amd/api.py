@@ -407,6 +407,13 @@ class Context:
         owner = _TableOwner(_cluster_table(self, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, min_similarity, max_clusters, counts))
         return _cluster_columns(owner, rings, level)
 
+    def sc_ensemble(self, structure: Structure, frames=None, groups: str = "/") -> dict:
+        """arp_structure_sc_ensemble as a dict: shape complementarity of every frame of an ensemble (the selection and radii of get_sc on model 0).
+        frames: [F, N, 3] f64 coordinates of the N atoms of model 0; None: the structure's models.  Keys: atoms (u32 structure indices of the m
+        selected atoms), molecule [m], n_frames, results (F arp_sc_results as a structured array, SC_RESULTS_DTYPE), status [F] (indices into
+        SC_FRAME_STATUS), err_atoms [F, 2] (rows of the coincident pair, ~0 elsewhere), frames_in_interface [m] u32, trimmed_dots [m] u64."""
+        return _sc_ensemble(self, structure, frames, groups)
+
     def sasa_ensemble(self, structure: Structure, frames=None, chains: str = "", probe_radius: float = 1.4, n_points: int = 100, sap_radius: float | None = None,
                       per_frame: bool = False, radii=None) -> dict:
         """arp_sasa_ensemble as a dict of numpy arrays: per-atom SASA statistics over the frames of an ensemble, and SAP statistics when
@@ -1950,3 +1957,151 @@ def sc(input_file: str, groups: str, model_num: int = 0, num_threads: int = 0) -
         return get_sc(Structure.load(input_file), groups, model_num)
     except ArpeggiaError as e:
         raise RuntimeError(f"SC calculation failed: {e}") from e
+
+
+# ---- shape complementarity across the frames of an ensemble (include/arpeggia_amd.h arp_sc_ensemble; no counterpart in the reference) ----
+SC_FRAME_STATUS = ["ok", "no_dots", "coincident", "sampling_limit"]  # ARP_SC_FRAME_*
+_SC_SURFACE_STATS = ["n_all_dots", "n_trimmed_dots", "trimmed_area", "d_median", "s_median", "d_mean", "s_mean"]
+SC_FRAME_COLUMNS = ["frame", "status", "sc", "distance", "area"] + [f"{k}_{m}" for k in _SC_SURFACE_STATS for m in (1, 2)] + \
+                   ["n_probes", "n_convex", "n_toroidal", "n_concave"]
+SC_ENSEMBLE_COLUMNS = ["chain", "resn", "resi", "insertion", "altloc", "atomn", "atomi", "molecule", "n_frames", "occupancy", "mean_trimmed_dots"]
+_SC_SURFACE_DT = np.dtype([(k, "<u8" if t is C.c_uint64 else "<f8") for k, t in _lib.arp_sc_surface._fields_])
+SC_RESULTS_DTYPE = np.dtype([("surface", _SC_SURFACE_DT, (2,)), ("combined", _SC_SURFACE_DT)] +
+                            [(k, "<u8") for k in ("n_convex", "n_toroidal", "n_concave", "n_probes")] + [(k, "<f8") for k in ("sc", "distance", "area")])
+assert SC_RESULTS_DTYPE.itemsize == C.sizeof(_lib.arp_sc_results)
+
+
+def _sc_ens_out(F: int, n: int):
+    res = np.zeros(max(F, 1), SC_RESULTS_DTYPE)
+    status, err = np.zeros(max(F, 1), "<u4"), np.zeros((max(F, 1), 2), "<u4")
+    fi, td = np.zeros(max(n, 1), "<u4"), np.zeros(max(n, 1), "<u8")
+    up = C.POINTER(C.c_uint32)
+    ptrs = (res.ctypes.data_as(C.POINTER(_lib.arp_sc_results)), status.ctypes.data_as(up), err.ctypes.data_as(up), fi.ctypes.data_as(up),
+            td.ctypes.data_as(C.POINTER(C.c_uint64)))
+    return res, status, err, fi, td, ptrs
+
+
+def sc_arrays_ensemble(ctx: "Context | None", xyz, radius, molecule, serial=None, settings: dict | None = None) -> dict:
+    """arp_sc_ensemble on raw arrays: xyz [F, n, 3], radius / molecule / serial [n] as sc_arrays takes them.  Returns results (a structured
+    array of F arp_sc_results, SC_RESULTS_DTYPE), status [F] (indices into SC_FRAME_STATUS), err_atoms [F, 2] (the coincident pair, ~0 elsewhere),
+    frames_in_interface [n] u32 and trimmed_dots [n] u64 (over the frames with status ok).  ctx None: the inputs are only checked."""
+    xyz = np.ascontiguousarray(xyz, dtype="<f8")
+    r = np.ascontiguousarray(radius, dtype=np.float64)
+    mol = np.ascontiguousarray(molecule, dtype=np.uint8)
+    if xyz.ndim != 3 or xyz.shape[1:] != (len(r), 3) or len(mol) != len(r):
+        raise ArpeggiaError(_lib.ARP_ERR_BAD_INPUT, f"sc ensemble: xyz must have shape [F, {len(r)}, 3] (one row per radius), got {list(xyz.shape)}")
+    ser = None if serial is None else np.ascontiguousarray(serial, dtype=np.int64)
+    st = _lib.arp_sc_settings()
+    lib.arp_sc_default_settings(C.byref(st))
+    for k, v in (settings or {}).items():
+        setattr(st, k, float(v))
+    F, n = xyz.shape[0], len(r)
+    res, status, err, fi, td, ptrs = _sc_ens_out(F, n)
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    src = xyz if xyz.size else np.zeros(1)
+    _check(lib.arp_sc_ensemble(None if ctx is None else ctx._h, n, F, dp(src), dp(r), mol.ctypes.data_as(C.POINTER(C.c_uint8)),
+                               None if ser is None else ser.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(st), *ptrs))
+    return {"n_frames": F, "results": res[:F], "status": status[:F], "err_atoms": err[:F], "frames_in_interface": fi[:n], "trimmed_dots": td[:n]}
+
+
+def _sc_ensemble(ctx: "Context | None", structure: Structure, frames, groups: str) -> dict:
+    """arp_structure_sc_ensemble.  ctx None: the inputs are only checked (raises their error); the result then holds atoms, molecule and n_frames."""
+    n_frames, ptr, keep = _frames_arg(structure, frames, "sc ensemble")
+    rows, used = C.c_uint64(), C.c_uint64()
+    n = max(structure.n_atoms, 1)
+    atoms, mol = np.zeros(n, "<u4"), np.zeros(n, np.uint8)
+    head = (structure._h, int(n_frames), ptr, groups.encode(), C.byref(rows), C.byref(used), atoms.ctypes.data_as(C.POINTER(C.c_uint32)),
+            mol.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if ctx is None:
+        _check(lib.arp_structure_sc_ensemble(None, *head, *([None] * 5)))
+        m = int(rows.value)
+        return {"atoms": atoms[:m].copy(), "molecule": mol[:m].copy(), "n_frames": int(used.value)}
+    n_top = _topology_atoms(structure)
+    f_cap = n_frames if frames is not None else (structure.n_atoms // n_top if n_top else 1)
+    res, status, err, fi, td, ptrs = _sc_ens_out(f_cap, n_top)
+    _check(lib.arp_structure_sc_ensemble(ctx._h, *head, *ptrs))
+    del keep
+    m, F = int(rows.value), int(used.value)
+    return {"atoms": atoms[:m].copy(), "molecule": mol[:m].copy(), "n_frames": F, "results": res[:F], "status": status[:F], "err_atoms": err[:F],
+            "frames_in_interface": fi[:m].copy(), "trimmed_dots": td[:m].copy()}
+
+
+def sc_frame_table(results, status):
+    """The per-frame table of get_sc_ensemble (SC_FRAME_COLUMNS) from the results and status arrays of an ensemble call."""
+    import pyarrow as pa
+
+    res, status = np.asarray(results), np.asarray(status)
+    bad = status != 0
+    f64 = lambda a: pa.array(np.ascontiguousarray(a, np.float64), pa.float64(), mask=bad)
+    cols = {"frame": pa.array(np.arange(len(res), dtype="<u4"), pa.uint32()), "status": pa.array([SC_FRAME_STATUS[int(k)] for k in status], pa.utf8())}
+    for k in ("sc", "distance", "area"):
+        cols[k] = f64(res[k])
+    for k in _SC_SURFACE_STATS:
+        for m in (0, 1):
+            v = res["surface"][k][:, m]
+            cols[f"{k}_{m + 1}"] = pa.array(np.ascontiguousarray(v), pa.uint64()) if k.startswith("n_") else f64(v)
+    for k in ("n_probes", "n_convex", "n_toroidal", "n_concave"):
+        cols[k] = pa.array(np.ascontiguousarray(res[k]), pa.uint64())
+    return _frame(cols)
+
+
+def get_sc_ensemble(structure: Structure, frames=None, groups: str = "/", device: int = 0):
+    """Shape complementarity across the frames of an ensemble, every frame of a pass in one set of launches: returns (frame_table, atom_table).
+    frame_table (SC_FRAME_COLUMNS): frame, status (SC_FRAME_STATUS), sc, distance, area, the statistics of the two surfaces (_1, _2) and the
+    probe and dot counts; a frame whose SC fails is a row with its status and nulls in the float columns.  atom_table (SC_ENSEMBLE_COLUMNS): one
+    row per selected atom with the identity columns, molecule (0 / 1), n_frames (the frames that succeeded), occupancy = the share of those in
+    which the atom owns a trimmed dot (f64) and mean_trimmed_dots; both null when no frame succeeded.  frames: [F, N, 3] f64 coordinates of the N
+    atoms of model 0; None: the structure's models are the frames."""
+    import pyarrow as pa
+
+    ctx = _with_context(device, lambda: _sc_ensemble(None, structure, frames, groups))
+    r = ctx.sc_ensemble(structure, frames, groups)
+    ft = sc_frame_table(r["results"], r["status"])
+    n_ok = int(np.count_nonzero(r["status"] == 0))
+    m = len(r["atoms"])
+    ident = _identity(structure, r["atoms"])
+    cols = {k: ident[k] for k in SC_ENSEMBLE_COLUMNS[:7]}
+    cols["molecule"] = pa.array(r["molecule"], pa.uint8())
+    cols["n_frames"] = pa.array(np.full(m, n_ok, "<u4"), pa.uint32())
+    none = np.full(m, n_ok == 0)
+    cols["occupancy"] = pa.array(r["frames_in_interface"].astype(np.float64) / float(max(n_ok, 1)), pa.float64(), mask=none)
+    cols["mean_trimmed_dots"] = pa.array(r["trimmed_dots"].astype(np.float64) / float(max(n_ok, 1)), pa.float64(), mask=none)
+    return ft, _frame(cols)
+
+
+def sc_ensemble(input_file: str, groups: str):
+    """Shape complementarity across the models of a multi-model file: see get_sc_ensemble."""
+    return get_sc_ensemble(Structure.load(input_file), None, groups)
+
+
+def sc_dot_atoms(ctx: Context, surface: int) -> np.ndarray:
+    """The owner atom (index into the call's atoms) of every dot of one surface of ctx's last SC call, in sc_dots' order (arp_sc_dot_atoms)."""
+    n = C.c_uint64()
+    _check(lib.arp_sc_dot_atoms(ctx._h, int(surface), 0, C.byref(n), None))
+    a = np.zeros(max(n.value, 1), "<u4")
+    _check(lib.arp_sc_dot_atoms(ctx._h, int(surface), n.value, C.byref(n), a.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return a[: n.value]
+
+
+def sc_dot_stats(seg_start, flags, area, nn_dist, score, other, device: int | None = None) -> np.ndarray:
+    """The statistics of dot segments as the ensemble call forms them: segment s = dots [seg_start[s], seg_start[s + 1]); a dot counts when its
+    flags have ARP_SC_DOT_TRIMMED (8); other[s] = the segment whose trimmed dots must exist for the means and medians of s.  Returns a structured
+    array, one arp_sc_surface per segment (n_all_dots, n_trimmed_dots, trimmed_area, d_mean, d_median, s_mean, s_median; the atom counts zero).
+    device None: arp_sc_dot_stats_host, the restatement on the CPU; a device number: arp_sc_dot_stats, the kernel.  The twins are bit-identical."""
+    start = np.ascontiguousarray(seg_start, dtype="<u8")
+    fl = np.ascontiguousarray(flags, dtype="<u4")
+    cols = [np.ascontiguousarray(a, dtype="<f8") for a in (area, nn_dist, score)]
+    oth = np.ascontiguousarray(other, dtype="<u4")
+    n_seg = len(oth)
+    if len(start) != n_seg + 1 or any(len(a) != len(fl) for a in cols) or (n_seg and int(start[-1]) != len(fl)):
+        raise ArpeggiaError(_lib.ARP_ERR_BAD_INPUT, "sc_dot_stats: seg_start needs one more entry than other, its last entry the length of the dot columns")
+    out = np.zeros(max(n_seg, 1), _SC_SURFACE_DT)
+    pad = lambda a: a if a.size else np.zeros(1, a.dtype)
+    dp = lambda a: pad(a).ctypes.data_as(C.POINTER(C.c_double))
+    args = (n_seg, start.ctypes.data_as(C.POINTER(C.c_uint64)), pad(fl).ctypes.data_as(C.POINTER(C.c_uint32)), *(dp(a) for a in cols),
+            pad(oth).ctypes.data_as(C.POINTER(C.c_uint32)), out.ctypes.data_as(C.POINTER(_lib.arp_sc_surface)))
+    if device is None:
+        _check(lib.arp_sc_dot_stats_host(*args))
+    else:
+        _check(lib.arp_sc_dot_stats(_context(int(device))._h, *args))
+    return out[:n_seg]

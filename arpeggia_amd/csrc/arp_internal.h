@@ -295,6 +295,37 @@ struct ScRunOut {
 };
 // Runs every device stage on `st` (synchronising for the sizes of the outputs).  ARP_ERR_HIP on a runtime failure; the SC errors in out->err.
 arp_status launch_sc(const ScJob &job, hipStream_t st, Profiler *prof, ScRunOut *out);
+// The same over the frames of an ensemble (sc_ens.inl).
+struct ScEnsFrame {       // one per frame, written on the device and copied back
+    uint32_t ok;          // no coincident pair, no subdivision failure, dots on both surfaces
+    uint32_t subdiv;      // the sampling limit was exceeded
+    uint32_t ci, cj;      // the coincident pair (atoms of the frame; both ~0 when there is none)
+    uint32_t att[2];      // Buried atoms per molecule
+    uint32_t nT[2], nC[2], nK[2];  // toroidal, contact and concave dots per surface
+    uint32_t n_probes;
+};
+struct ScEnsJob {
+    uint32_t n;                    // atoms per frame
+    uint64_t n_frames;
+    const double *xyz;             // host, [F][n][3]
+    const double *r;
+    const uint32_t *mol;
+    const long long *serial;
+    double rp, density, band, sep, w;
+    uint32_t frames_per_pass;      // > 0: the knob sc_ens_frames; 0: from the memory budget
+};
+struct ScEnsOut {                  // host arrays
+    arp_sc_surface *surf;          // [F][2]: the dot statistics of each surface (atom counts zero)
+    ScEnsFrame *frames;            // [F]
+    uint32_t *frames_in_interface; // [n]
+    unsigned long long *trimmed_dots;  // [n]
+};
+arp_status launch_sc_ens(const ScEnsJob &job, hipStream_t st, Profiler *prof, ScEnsOut *out);
+// statistics of dot segments (sc_ens.inl k_sc_dot_stats) on host columns, and the host restatement with the same summation order
+arp_status launch_sc_dot_stats(uint64_t n_seg, const uint64_t *start, const uint32_t *flags, const double *area, const double *nn, const double *score,
+                               const uint32_t *other, arp_sc_surface *out, hipStream_t st);
+void sc_dot_stats_host(uint64_t n_seg, const uint64_t *start, const uint32_t *flags, const double *area, const double *nn, const double *score,
+                       const uint32_t *other, arp_sc_surface *out);
 void launch_pack_split(const PackArrays &pa, const unsigned long long *result, const arp_pair *pairs, unsigned long long capacity, arp_pair *grouped, bool ordered, hipStream_t st);
 
 }  // namespace arp

@@ -286,5 +286,6 @@ DEVFN float dist_f32(double s) {
 #include "ens.inl"
 #include "seg.inl"
 #include "sc.inl"
+#include "sc_ens.inl"
 
 }  // namespace arp

@@ -20,6 +20,9 @@
 // reference's values bit for bit.  Neighbour searches use uniform cell lists (ScCells) whose edge is at least the search radius, so a
 // 27-cell visit is exhaustive; burial tests walk the atom's candidate list (other-molecule atoms within r_i + r_b + 2 rp + kScBurMargin),
 // which holds every atom that can bury a point at distance r_i + rp of atom i.
+//
+// Every kernel with relations between items is a template on ENS.  ENS = false is the single-frame path of launch_sc below, which passes an empty
+// ScEns and compiles to the code it had before the parameter existed; ENS = true takes many frames of one topology at once (sc_ens.inl).
 
 constexpr double kScBurMargin = 0.01;  // A: slack of the burial candidate lists over r_i + r_b + 2 rp (positions are within ~1e-12 A of their sphere)
 constexpr uint32_t kScDotConvex = ARP_SC_DOT_CONVEX, kScDotToroidal = ARP_SC_DOT_TOROIDAL, kScDotConcave = ARP_SC_DOT_CONCAVE, kScDotBuried = ARP_SC_DOT_BURIED,
@@ -29,6 +32,15 @@ struct ScCells {      // uniform cell list over a point set (sc.cpp sc_cells): s
     double ox, oy, oz, inv;
     int nx, ny, nz;
     const uint32_t *start, *item;
+    const double *org;  // ensemble (sc_ens.inl): one slab of nx ny nz cells per frame, frame f's origin at org[3 f]; the single-frame path leaves it unset
+};
+// What the frame-aware instantiations (ENS) of the kernels below need; the single-frame launches pass ScEns{} and never read it (sc_ens.inl)
+struct ScEns {
+    uint32_t n_per;              // atoms per frame: the frame of any item is (its owner atom) / n_per
+    unsigned long long *coinc;   // [B] the coincident-pair word of each frame (minimum over its pairs, atoms local to the frame)
+    uint32_t *subdiv;            // [B] the subdivision flag of each frame
+    const uint32_t *adj[2];      // [B] added to a fill offset: moves a frame's run of this kind into the frame's segment of the surface
+    const uint32_t *other;       // [B + 1] trim: the segment starts of the other surface (a frame without dots there is not trimmed)
 };
 struct ScAtoms {
     uint32_t n;
@@ -54,18 +66,22 @@ __device__ inline double vd2(DV a, DV b) { const DV d = vsub(a, b); return vdot(
 __device__ inline DV catom(const ScAtoms &A, uint32_t i) { const double4 c = A.c[i]; return v3(c.x, c.y, c.z); }
 __device__ inline DV dp3(const double *p) { return v3(p[0], p[1], p[2]); }
 
-__device__ inline void cell_of(const ScCells &g, DV p, int &cx, int &cy, int &cz) {
-    cx = (int)floor((p.x - g.ox) * g.inv); cy = (int)floor((p.y - g.oy) * g.inv); cz = (int)floor((p.z - g.oz) * g.inv);
+// the cell of p; returns the first cell of the slab it lies in (0 unless ENS: the slab of frame f, around that frame's own origin)
+template <bool ENS = false>
+__device__ inline uint32_t cell_of(const ScCells &g, DV p, int &cx, int &cy, int &cz, uint32_t f = 0) {
+    const double ox = ENS ? g.org[3u * f] : g.ox, oy = ENS ? g.org[3u * f + 1u] : g.oy, oz = ENS ? g.org[3u * f + 2u] : g.oz;
+    cx = (int)floor((p.x - ox) * g.inv); cy = (int)floor((p.y - oy) * g.inv); cz = (int)floor((p.z - oz) * g.inv);
     cx = min(max(cx, 0), g.nx - 1); cy = min(max(cy, 0), g.ny - 1); cz = min(max(cz, 0), g.nz - 1);
+    return ENS ? f * ((uint32_t)g.nx * (uint32_t)g.ny * (uint32_t)g.nz) : 0u;
 }
 // f(item) over the items of the cells within `reach` cells of p's cell; stops when f returns true
-template <class F>
-__device__ inline bool cells_visit(const ScCells &g, DV p, int reach, F &&f) {
+template <bool ENS = false, class F>
+__device__ inline bool cells_visit(const ScCells &g, DV p, int reach, F &&f, uint32_t frame = 0) {
     int cx, cy, cz;
-    cell_of(g, p, cx, cy, cz);
+    const uint32_t slab = cell_of<ENS>(g, p, cx, cy, cz, frame);
     for (int z = max(cz - reach, 0); z <= min(cz + reach, g.nz - 1); z++)
         for (int y = max(cy - reach, 0); y <= min(cy + reach, g.ny - 1); y++) {
-            const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
+            const uint32_t row = slab + ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
             const uint32_t lo = g.start[row + (uint32_t)max(cx - reach, 0)], hi = g.start[row + (uint32_t)min(cx + reach, g.nx - 1) + 1u];
             for (uint32_t s = lo; s < hi; s++) if (f(g.item[s])) return true;
         }
@@ -127,12 +143,14 @@ __global__ __launch_bounds__(256) void k_sc_scan_add(uint32_t *out, const uint32
 }
 
 // ---- (a) atoms: attention, neighbour lists (CSR, sorted by (d^2, index)), burial candidate lists, coincidence
-template <bool FILL>
+template <bool FILL, bool ENS = false>
 __global__ __launch_bounds__(256) void k_sc_atoms(ScAtoms A, ScCells g, uint32_t *nb_cnt, uint32_t *bur_cnt, uint32_t *att, uint32_t *acc, unsigned long long *err,
                                                   const uint32_t *nb_off, uint32_t *nb_idx, double *nb_d2, uint32_t *nb_own, const uint32_t *bur_off,
-                                                  uint32_t *bur_idx) {
+                                                  uint32_t *bur_idx, ScEns E) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= A.n) return;
+    const uint32_t fr = ENS ? i / E.n_per : 0u, a0 = fr * (ENS ? E.n_per : 0u);  // the frame and its first atom
+    if (ENS && FILL && E.coinc[fr] != ~0ull) return;  // a frame with a coincident pair has no lists (its counts were zeroed)
     const double4 ci4 = A.c[i];
     const DV ci = v3(ci4.x, ci4.y, ci4.z);
     const double ri = ci4.w, s2 = A.sep * A.sep;
@@ -140,7 +158,7 @@ __global__ __launch_bounds__(256) void k_sc_atoms(ScAtoms A, ScCells g, uint32_t
     double best = INFINITY;
     uint32_t m = 0, b = 0;
     const uint32_t nb0 = FILL ? nb_off[i] : 0u, bur0 = FILL ? bur_off[i] : 0u;
-    cells_visit(g, ci, 1, [&](uint32_t j) {
+    cells_visit<ENS>(g, ci, 1, [&](uint32_t j) {
         const double4 cj = A.c[j];
         const double d2 = vd2(ci, v3(cj.x, cj.y, cj.z));
         if (A.mol[j] != mi) {
@@ -150,7 +168,7 @@ __global__ __launch_bounds__(256) void k_sc_atoms(ScAtoms A, ScCells g, uint32_t
             return false;
         }
         if (!(d2 <= s2) || A.serial[j] == A.serial[i]) return false;
-        if (!FILL && d2 <= 0.0001) atomicMin(err, ((unsigned long long)i << 32) | j);
+        if (!FILL && d2 <= 0.0001) atomicMin(ENS ? E.coinc + fr : err, ((unsigned long long)(i - a0) << 32) | (j - a0));
         const double bridge = ri + cj.w + 2.0 * A.rp;
         if (d2 < bridge * bridge) {
             if (FILL) {  // insertion into this atom's segment by (d^2, index)
@@ -163,7 +181,7 @@ __global__ __launch_bounds__(256) void k_sc_atoms(ScAtoms A, ScCells g, uint32_t
             m++;
         }
         return false;
-    });
+    }, fr);
     if (!FILL) { nb_cnt[i] = m; bur_cnt[i] = b; att[i] = best < s2 ? 1u : 0u; acc[i] = m == 0u ? 1u : 0u; }
 }
 
@@ -216,9 +234,10 @@ __device__ inline void sc_put(ScDot *d, DV p, DV nml, double area, uint32_t atom
 
 // ---- (b) one item per neighbour-list entry (i, j): build_probes' body (:389-438), build_probe_triplets, emit_reentrant_surface
 struct ScPairOut { uint32_t *p_cnt, *t_cnt[2], *acc; unsigned long long *err; const uint32_t *p_off, *t_off[2]; ScProbe *probes; ScDot *tor[2]; };
-template <bool FILL>
+template <bool FILL, bool ENS = false>
 __global__ __launch_bounds__(256) void k_sc_pairs(ScAtoms A, uint32_t n_items, const uint32_t *nb_off, const uint32_t *nb_idx, const double *nb_d2,
-                                                  const uint32_t *nb_own, const uint32_t *att, const uint32_t *bur_off, const uint32_t *bur_idx, ScPairOut o) {
+                                                  const uint32_t *nb_own, const uint32_t *att, const uint32_t *bur_off, const uint32_t *bur_idx, ScPairOut o,
+                                                  ScEns E) {
     const uint32_t e = blockIdx.x * 256u + threadIdx.x;
     if (e >= n_items) return;
     const uint32_t i = nb_own[e], j = nb_idx[e], mi = A.mol[i];
@@ -372,7 +391,10 @@ __global__ __launch_bounds__(256) void k_sc_pairs(ScAtoms A, uint32_t n_items, c
     });
     // (a ring point with |dot| >= 1 ends the pair: its flag bit stops the remaining points, the dots before it stay)
     nt &= 0x7FFFFFFFu;
-    if (!(ok && ring_ok) && !FILL) atomicOr(o.err, (unsigned long long)kScErrSubdiv);
+    if (!(ok && ring_ok) && !FILL) {
+        if (ENS) atomicOr(&E.subdiv[i / E.n_per], 1u);
+        else atomicOr(o.err, (unsigned long long)kScErrSubdiv);
+    }
     finish();
 }
 
@@ -413,10 +435,10 @@ __device__ inline uint32_t sc_wave_lats(double rad, DV axis, double density, DV 
 
 // (c) contact dots (:217-373), one wave per atom; out[m] + off[m][i] receives atom i's dots (m = its molecule)
 constexpr uint32_t kScWaves = 4;
-template <bool FILL>
+template <bool FILL, bool ENS = false>
 __global__ __launch_bounds__(kScWaves * 64) void k_sc_contact(ScAtoms A, const uint32_t *nb_off, const uint32_t *nb_idx, const uint32_t *att,
                                                               const uint32_t *acc, const uint32_t *bur_off, const uint32_t *bur_idx, uint32_t *cnt0,
-                                                              uint32_t *cnt1, const uint32_t *off0, const uint32_t *off1, ScDot *out0, ScDot *out1) {
+                                                              uint32_t *cnt1, const uint32_t *off0, const uint32_t *off1, ScDot *out0, ScDot *out1, ScEns E) {
     const uint32_t i = blockIdx.x * kScWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (i >= A.n) return;  // (wave-uniform, as every return below)
     const uint32_t mi = A.mol[i];
@@ -453,6 +475,7 @@ __global__ __launch_bounds__(kScWaves * 64) void k_sc_contact(ScAtoms A, const u
         if (vdot(vcross(north, south), eq) <= 0.0) { finish(); return; }
     }
     ScDot *out = FILL ? (mi == 0u ? out0 + off0[i] : out1 + off1[i]) : nullptr;
+    if (FILL && ENS) out += E.adj[mi][i / E.n_per];
     uint32_t nl;
     double cs;
     // the latitudes first: their count and cs (a failure drops the atom, `.ok()?`)
@@ -485,10 +508,10 @@ __global__ __launch_bounds__(kScWaves * 64) void k_sc_contact(ScAtoms A, const u
 }
 
 // (d) concave dots (:713-880), one wave per probe; all three atoms of a probe are of one molecule (same-molecule neighbours)
-template <bool FILL>
+template <bool FILL, bool ENS = false>
 __global__ __launch_bounds__(kScWaves * 64) void k_sc_concave(ScAtoms A, const ScProbe *probes, uint32_t n_probes, ScCells low, const uint32_t *bur_off,
                                                               const uint32_t *bur_idx, uint32_t *cnt0, uint32_t *cnt1, const uint32_t *off0,
-                                                              const uint32_t *off1, ScDot *out0, ScDot *out1) {
+                                                              const uint32_t *off1, ScDot *out0, ScDot *out1, ScEns E) {
     const uint32_t pi = blockIdx.x * kScWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (pi >= n_probes) return;  // (wave-uniform)
     if (FILL && off0[pi + 1] + off1[pi + 1] == off0[pi] + off1[pi]) return;
@@ -511,6 +534,8 @@ __global__ __launch_bounds__(kScWaves * 64) void k_sc_concave(ScAtoms A, const S
     // burial is decided by the probe centre (pcen = pijk): one decision for all of this probe's dots
     const bool buried = FILL && sc_buried(A, bur_off, bur_idx, P.i, pijk);
     ScDot *out = FILL ? (mol == 0u ? out0 + off0[pi] : out1 + off1[pi]) : nullptr;
+    const uint32_t fr = ENS ? P.i / E.n_per : 0u;
+    if (FILL && ENS) out += E.adj[mol][fr];
     uint32_t nd = 0, nl;
     double cs;
     if (sc_arc(v3(0.0, 0.0, 0.0), rp, axis, density, vp[mm], south, nl, cs, [](uint32_t, DV) {}))  // (the latitudes' count and cs first)
@@ -528,11 +553,11 @@ __global__ __launch_bounds__(kScWaves * 64) void k_sc_concave(ScAtoms A, const S
                 if (vdot(p0, vec[0]) >= 0.0 || vdot(p0, vec[1]) >= 0.0 || vdot(p0, vec[2]) >= 0.0) return;
                 const DV p = vadd(p0, pijk);
                 if (hijk < rp) {  // the nears: other low probes within 2 rp of the centre; a point within rp of one is dropped
-                    const bool coll = cells_visit(low, p, 1, [&](uint32_t q) {
+                    const bool coll = cells_visit<ENS>(low, p, 1, [&](uint32_t q) {
                         if (q == pi) return false;
                         const DV c = dp3(probes[q].p);
                         return vd2(pijk, c) <= 4.0 * rp2 && vd2(p, c) < rp2;
-                    });
+                    }, fr);
                     if (coll) return;
                 }
                 int mc = 0;
@@ -551,26 +576,31 @@ __global__ __launch_bounds__(kScWaves * 64) void k_sc_concave(ScAtoms A, const S
 }
 
 // ---- (e) trim: a buried dot with no open (non-buried) dot of its surface within d^2 <= band^2 is trimmed (cells: the open dots, edge >= band)
-__global__ __launch_bounds__(256) void k_sc_trim(ScDot *dots, uint32_t n, ScCells open, double band2) {
+template <bool ENS = false>
+__global__ __launch_bounds__(256) void k_sc_trim(ScDot *dots, uint32_t n, ScCells open, double band2, ScEns E) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     if (k >= n) return;
     ScDot &d = dots[k];
     if (!(d.flags & kScDotBuried)) return;
+    const uint32_t fr = ENS ? d.atom / E.n_per : 0u;
+    if (ENS && E.other[fr + 1u] == E.other[fr]) return;  // "No molecular dots generated" for this frame
     const DV p = dp3(d.p);
-    const bool hit = cells_visit(open, p, 1, [&](uint32_t q) { return vd2(dp3(dots[q].p), p) <= band2; });
+    const bool hit = cells_visit<ENS>(open, p, 1, [&](uint32_t q) { return vd2(dp3(dots[q].p), p) <= band2; }, fr);
     if (!hit) d.flags |= kScDotTrimmed;
 }
 
 // ---- (f) nearest trimmed dot of the other surface: shells of cells around the dot's cell until the next shell's lower bound exceeds the
 // best d^2 (exact at any distance); the lower index wins a tie.  Writes nn_dist and score into the trimmed dots of `mine`.
-__global__ __launch_bounds__(256) void k_sc_nn(ScDot *mine, uint32_t n, const ScDot *theirs, ScCells g, double w) {
+template <bool ENS = false>
+__global__ __launch_bounds__(256) void k_sc_nn(ScDot *mine, uint32_t n, const ScDot *theirs, ScCells g, double w, ScEns E) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     if (k >= n) return;
     ScDot &d = mine[k];
     if (!(d.flags & kScDotTrimmed)) return;
     const DV p = dp3(d.p);
     int cx, cy, cz;
-    cell_of(g, p, cx, cy, cz);
+    const uint32_t slab = cell_of<ENS>(g, p, cx, cy, cz, ENS ? d.atom / E.n_per : 0u);
+    if (ENS && g.start[slab + (uint32_t)g.nx * (uint32_t)g.ny * (uint32_t)g.nz] == g.start[slab]) return;  // the frame's other surface has no trimmed dot
     const double edge = 1.0 / g.inv;
     const int smax = max(max(g.nx, g.ny), g.nz);
     double best = INFINITY;
@@ -587,7 +617,7 @@ __global__ __launch_bounds__(256) void k_sc_nn(ScDot *mine, uint32_t n, const Sc
                 const bool face = z == cz - s || z == cz + s || y == cy - s || y == cy + s;
                 for (int x = cx - s; x <= cx + s; x += (face || s == 0) ? 1 : 2 * s) {
                     if (x < 0 || x >= g.nx) continue;
-                    const uint32_t c = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx + (uint32_t)x;
+                    const uint32_t c = slab + ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx + (uint32_t)x;
                     for (uint32_t e = g.start[c]; e < g.start[c + 1]; e++) {
                         const uint32_t q = g.item[e];
                         const ScDot &o = theirs[q];
@@ -714,7 +744,7 @@ arp_status launch_sc(const ScJob &J, hipStream_t st, Profiler *prof, ScRunOut *o
     SC_TRY(hipMemsetAsync(err + 1, 0, 8, st));
     if (prof) prof->begin("sc_atoms_count", st);
     hipLaunchKernelGGL(k_sc_atoms<false>, dim3(sc_blocks(n)), dim3(256), 0, st, SA, ga, nb_cnt, bur_cnt, att, acc, err, nullptr, nullptr, nullptr,
-                       nullptr, nullptr, nullptr);
+                       nullptr, nullptr, nullptr, ScEns{});
     if (prof) prof->end(st);
     sc_scan(A, nb_cnt, nb_off, n + 1);
     sc_scan(A, bur_cnt, bur_off, n + 1);
@@ -728,7 +758,7 @@ arp_status launch_sc(const ScJob &J, hipStream_t st, Profiler *prof, ScRunOut *o
     if (A.failed) return sc_fail(ARP_ERR_OOM);
     if (prof) prof->begin("sc_atoms_fill", st);
     hipLaunchKernelGGL(k_sc_atoms<true>, dim3(sc_blocks(n)), dim3(256), 0, st, SA, ga, nullptr, nullptr, nullptr, nullptr, nullptr, (const uint32_t *)nb_off,
-                       nb_idx, nb_d2, nb_own, (const uint32_t *)bur_off, bur_idx);
+                       nb_idx, nb_d2, nb_own, (const uint32_t *)bur_off, bur_idx, ScEns{});
     if (prof) prof->end(st);
 
     // (b) pairs: probes, toroidal dots, accessible flags
@@ -739,7 +769,7 @@ arp_status launch_sc(const ScJob &J, hipStream_t st, Profiler *prof, ScRunOut *o
     if (A.failed) return sc_fail(ARP_ERR_OOM);
     if (prof) prof->begin("sc_pairs_count", st);
     if (n_nb) hipLaunchKernelGGL(k_sc_pairs<false>, dim3(sc_blocks(n_nb)), dim3(256), 0, st, SA, n_nb, (const uint32_t *)nb_off, (const uint32_t *)nb_idx,
-                                 (const double *)nb_d2, (const uint32_t *)nb_own, (const uint32_t *)att, (const uint32_t *)bur_off, (const uint32_t *)bur_idx, po);
+                                 (const double *)nb_d2, (const uint32_t *)nb_own, (const uint32_t *)att, (const uint32_t *)bur_off, (const uint32_t *)bur_idx, po, ScEns{});
     if (prof) prof->end(st);
     sc_scan(A, po.p_cnt, p_off, n_nb + 1);
     sc_scan(A, po.t_cnt[0], t_off0, n_nb + 1);
@@ -754,7 +784,7 @@ arp_status launch_sc(const ScJob &J, hipStream_t st, Profiler *prof, ScRunOut *o
     po.p_off = p_off; po.t_off[0] = t_off0; po.t_off[1] = t_off1; po.probes = probes; po.tor[0] = tor0; po.tor[1] = tor1;
     if (prof) prof->begin("sc_pairs_fill", st);
     if (n_nb) hipLaunchKernelGGL(k_sc_pairs<true>, dim3(sc_blocks(n_nb)), dim3(256), 0, st, SA, n_nb, (const uint32_t *)nb_off, (const uint32_t *)nb_idx,
-                                 (const double *)nb_d2, (const uint32_t *)nb_own, (const uint32_t *)att, (const uint32_t *)bur_off, (const uint32_t *)bur_idx, po);
+                                 (const double *)nb_d2, (const uint32_t *)nb_own, (const uint32_t *)att, (const uint32_t *)bur_off, (const uint32_t *)bur_idx, po, ScEns{});
     if (prof) prof->end(st);
 
     // (c) contact and (d) concave: counts first, so that each surface is laid out [toroidal | contact | concave]
@@ -764,13 +794,13 @@ arp_status launch_sc(const ScJob &J, hipStream_t st, Profiler *prof, ScRunOut *o
     if (A.failed) return sc_fail(ARP_ERR_OOM);
     if (prof) prof->begin("sc_contact_count", st);
     hipLaunchKernelGGL(k_sc_contact<false>, dim3((n + kScWaves - 1) / kScWaves), dim3(kScWaves * 64), 0, st, SA, (const uint32_t *)nb_off, (const uint32_t *)nb_idx, (const uint32_t *)att,
-                       (const uint32_t *)acc, (const uint32_t *)bur_off, (const uint32_t *)bur_idx, cc[0], cc[1], nullptr, nullptr, nullptr, nullptr);
+                       (const uint32_t *)acc, (const uint32_t *)bur_off, (const uint32_t *)bur_idx, cc[0], cc[1], nullptr, nullptr, nullptr, nullptr, ScEns{});
     if (prof) prof->end(st);
     const ScCells gl = sc_cells(A, box, (const double *)probes, sizeof(ScProbe) / 8, n_probe, kScPtLowProbe, J.rp, 2.0 * J.rp, prof, "sc_cells_low_probes");
     if (A.failed) return sc_fail(ARP_ERR_OOM);
     if (prof) prof->begin("sc_concave_count", st);
     if (n_probe) hipLaunchKernelGGL(k_sc_concave<false>, dim3((n_probe + kScWaves - 1) / kScWaves), dim3(kScWaves * 64), 0, st, SA, (const ScProbe *)probes, n_probe, gl,
-                                    (const uint32_t *)bur_off, (const uint32_t *)bur_idx, kc[0], kc[1], nullptr, nullptr, nullptr, nullptr);
+                                    (const uint32_t *)bur_off, (const uint32_t *)bur_idx, kc[0], kc[1], nullptr, nullptr, nullptr, nullptr, ScEns{});
     if (prof) prof->end(st);
     uint32_t nT[2] = {n_t0, n_t1}, nC[2], nK[2];
     for (int m = 0; m < 2; m++) { sc_scan(A, cc[m], co[m], n + 1); sc_scan(A, kc[m], ko[m], n_probe + 1); }
@@ -784,12 +814,12 @@ arp_status launch_sc(const ScJob &J, hipStream_t st, Profiler *prof, ScRunOut *o
     if (prof) prof->begin("sc_contact_fill", st);
     hipLaunchKernelGGL(k_sc_contact<true>, dim3((n + kScWaves - 1) / kScWaves), dim3(kScWaves * 64), 0, st, SA, (const uint32_t *)nb_off, (const uint32_t *)nb_idx, (const uint32_t *)att,
                        (const uint32_t *)acc, (const uint32_t *)bur_off, (const uint32_t *)bur_idx, nullptr, nullptr, (const uint32_t *)co[0],
-                       (const uint32_t *)co[1], surf[0] + nT[0], surf[1] + nT[1]);
+                       (const uint32_t *)co[1], surf[0] + nT[0], surf[1] + nT[1], ScEns{});
     if (prof) prof->end(st);
     if (prof) prof->begin("sc_concave_fill", st);
     if (n_probe) hipLaunchKernelGGL(k_sc_concave<true>, dim3((n_probe + kScWaves - 1) / kScWaves), dim3(kScWaves * 64), 0, st, SA, (const ScProbe *)probes, n_probe, gl,
                                     (const uint32_t *)bur_off, (const uint32_t *)bur_idx, nullptr, nullptr, (const uint32_t *)ko[0], (const uint32_t *)ko[1],
-                                    surf[0] + nT[0] + nC[0], surf[1] + nT[1] + nC[1]);
+                                    surf[0] + nT[0] + nC[0], surf[1] + nT[1] + nC[1], ScEns{});
     if (prof) prof->end(st);
     uint32_t nS[2];
     for (int m = 0; m < 2; m++) nS[m] = nT[m] + nC[m] + nK[m];
@@ -803,7 +833,7 @@ arp_status launch_sc(const ScJob &J, hipStream_t st, Profiler *prof, ScRunOut *o
                                         "sc_cells_open_dots");
             if (A.failed) return sc_fail(ARP_ERR_OOM);
             if (prof) prof->begin("sc_trim", st);
-            hipLaunchKernelGGL(k_sc_trim, dim3(sc_blocks(nS[m])), dim3(256), 0, st, surf[m], nS[m], go, J.band * J.band);
+            hipLaunchKernelGGL(k_sc_trim<false>, dim3(sc_blocks(nS[m])), dim3(256), 0, st, surf[m], nS[m], go, J.band * J.band, ScEns{});
             if (prof) prof->end(st);
             gt[m] = sc_cells(A, box, (const double *)surf[m], sizeof(ScDot) / 8, nS[m], kScPtDotTrimmed, J.rp, 1.5, prof, "sc_cells_trimmed_dots");
             if (A.failed) return sc_fail(ARP_ERR_OOM);
@@ -813,7 +843,7 @@ arp_status launch_sc(const ScJob &J, hipStream_t st, Profiler *prof, ScRunOut *o
         if (n_trim[0] && n_trim[1])
             for (int m = 0; m < 2; m++) {
                 if (prof) prof->begin("sc_nn", st);
-                hipLaunchKernelGGL(k_sc_nn, dim3(sc_blocks(nS[m])), dim3(256), 0, st, surf[m], nS[m], (const ScDot *)surf[1 - m], gt[1 - m], J.w);
+                hipLaunchKernelGGL(k_sc_nn<false>, dim3(sc_blocks(nS[m])), dim3(256), 0, st, surf[m], nS[m], (const ScDot *)surf[1 - m], gt[1 - m], J.w, ScEns{});
                 if (prof) prof->end(st);
             }
     }

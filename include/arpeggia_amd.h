@@ -164,6 +164,8 @@ typedef struct arp_table arp_table;         /* the 20-column contact table (mod.
  *                      tiny inputs reach the frame cap; 0 (default): automatic (17, fewer only beyond 2^21 residues)
  *   "ens_chunk_atoms" N > 0: arp_sasa_ensemble runs its frames in passes of N packed atoms (frames x selected atoms; whole frames, at least one per
  *                      pass), so that tests can force several passes; 0 (default): about 2 x 10^6 atoms per pass
+ *   "sc_ens_frames" N in 1 .. 2^20: arp_sc_ensemble runs N whole frames per pass, so that tests reach pass edges at tiny shapes; 0 (default): as many
+ *                      as the pass's memory budget allows.  The results do not depend on it
  *   "timeline_cap_bytes" N > 0: arp_contact_timelines refuses a device bitmap of more than N bytes (ARP_ERR_CAPACITY), so that tests reach the limit on
  *                      tiny inputs; 0 (default): 2^31 bytes
  *   "similarity_cap_bytes" N > 0: arp_contact_similarity and arp_bit_gram refuse a matrix of more than N bytes (ARP_ERR_CAPACITY), so that tests reach
@@ -399,6 +401,50 @@ arp_status arp_structure_sc_select(const arp_structure *s, const char *groups, i
 #define ARP_SC_DOT_TRIMMED 8
 arp_status arp_sc_dots(arp_context *ctx, int32_t surface, uint64_t cap, uint64_t *n, double *xyz, double *normal, double *area, uint32_t *flags,
                        double *nn_dist, double *score);
+/* The owner atom of each of those dots (an index into the atoms of the call), same order and cap convention. */
+arp_status arp_sc_dot_atoms(arp_context *ctx, int32_t surface, uint64_t cap, uint64_t *n, uint32_t *atom);
+
+/* ---- shape complementarity across the frames of an ensemble -- DESIGN.md section 3.18 ----
+ * F frames of one topology (n atoms; radius, molecule, serial and settings as arp_sc; xyz [F][n][3]) run through the device in passes of whole
+ * frames (as many as a memory budget allows; arp_debug_set "sc_ens_frames" fixes the number).  No relation crosses a frame: every frame's
+ * dots, flags, distances and scores are those of arp_sc on that frame, bit for bit.  Per frame, results[f] and status[f]:
+ *   ARP_SC_FRAME_OK          results[f] as arp_sc fills it.  Integer fields, medians, sc and distance equal arp_sc's; trimmed_area, d_mean,
+ *                            s_mean and area are sums of the same terms in another (fixed) order, see arp_sc_dot_stats
+ *   ARP_SC_FRAME_NO_DOTS     "No molecular dots generated": atom counts, kind and probe counts and n_all_dots filled, the rest zero
+ *   ARP_SC_FRAME_COINCIDENT  "Overlapping atoms detected": err_atoms[2 f], [2 f + 1] (nullable) name the pair arp_sc's message names (indices
+ *                            into the n atoms, ~0 for every other frame); atom counts filled, the rest zero
+ *   ARP_SC_FRAME_SUBDIV      "Sampling limit exceeded": atom counts filled, the rest zero
+ * A frame's status is not a call failure: the call returns ARP_OK when the inputs were valid, and a failed frame leaves the others unchanged.
+ * Per atom, over the frames with status OK: frames_in_interface[i] = the frames in which atom i owns a trimmed dot, trimmed_dots[i] = the sum of
+ * its trimmed dots.  Input errors (ARP_ERR_BAD_INPUT before any device work): null pointers, n_frames == 0, a non-finite coordinate (the message
+ * names the first such frame), and radii, molecule ids, serials and settings as arp_sc refuses them.  ctx == NULL runs only these checks.
+ * The dots arp_sc_dots returns are not touched.  Synchronous. */
+#define ARP_SC_FRAME_OK 0
+#define ARP_SC_FRAME_NO_DOTS 1
+#define ARP_SC_FRAME_COINCIDENT 2
+#define ARP_SC_FRAME_SUBDIV 3
+arp_status arp_sc_ensemble(arp_context *ctx, uint64_t n, uint64_t n_frames, const double *xyz, const double *radius, const uint8_t *molecule,
+                           const int64_t *serial, const arp_sc_settings *settings, arp_sc_results *results, uint32_t *status, uint32_t *err_atoms,
+                           uint32_t *frames_in_interface, uint64_t *trimmed_dots);
+/* The same on a structure: the selection, molecule ids and radii of arp_structure_sc on model 0 (the topology); the frames are xyz, n_frames x
+ * N x 3 coordinates of model 0's N atoms, or with xyz == NULL the structure's models (arp_dsasa_ensemble's convention and its topology
+ * errors).  *n_rows selected atoms: out_atoms (structure index) and out_molecule hold arp_structure_n_atoms entries at most, as do
+ * frames_in_interface and trimmed_dots; results, status and err_atoms (2 per frame, indices into the rows; nullable) hold *frames_used frames.
+ * ctx == NULL runs only the checks and writes *n_rows, *frames_used and (when given) out_atoms, out_molecule. */
+arp_status arp_structure_sc_ensemble(arp_context *ctx, const arp_structure *topology, uint64_t n_frames, const double *xyz, const char *groups,
+                                     uint64_t *n_rows, uint64_t *frames_used, uint32_t *out_atoms, uint8_t *out_molecule, arp_sc_results *results,
+                                     uint32_t *status, uint32_t *err_atoms, uint32_t *frames_in_interface, uint64_t *trimmed_dots);
+/* The statistics kernel of the ensemble call on the caller's dot columns (host arrays), and its host restatement: the twins are bit-identical.
+ * Segment s holds the dots [seg_start[s], seg_start[s + 1]) (seg_start[0] = 0); a dot counts when flags has ARP_SC_DOT_TRIMMED.  out[s]:
+ * n_all_dots = the segment's length, n_trimmed_dots = k, trimmed_area, and -- zero when k = 0 or segment other[s] has no trimmed dot --
+ * d_mean, s_mean (= -(sum of -score) / k), d_median and s_median = element k / 2 in ascending order of the trimmed dots' nn_dist / score (no
+ * averaging; -0 sorts before +0).  Each sum is taken in a fixed order that depends on the segment alone: lane t of 256 adds the trimmed dots at
+ * positions t, t + 256, ... of the segment in increasing position, starting from +0; the 256 partial sums are folded p[t] += p[t + h] for
+ * h = 128, 64, ..., 1.  The atom counts of out[s] are zero. */
+arp_status arp_sc_dot_stats_host(uint64_t n_seg, const uint64_t *seg_start, const uint32_t *flags, const double *area, const double *nn_dist,
+                                 const double *score, const uint32_t *other, arp_sc_surface *out);
+arp_status arp_sc_dot_stats(arp_context *ctx, uint64_t n_seg, const uint64_t *seg_start, const uint32_t *flags, const double *area,
+                            const double *nn_dist, const double *score, const uint32_t *other, arp_sc_surface *out);
 
 /* Per-kernel device timing of the most recent call (HIP events on the context's stream).  Enable, run, then read.
  * names[k] points to a static string.  Returns the number of kernels recorded (<= cap). */
