@@ -23,6 +23,7 @@ from .api import (  # noqa: F401  shape complementarity across the frames of an 
     sc_frame_table,
 )
 from .api import FREQ_COLUMNS, RESIDUE_FREQ_COLUMNS, contact_frequencies, get_contact_frequencies  # noqa: F401  contact frequencies across the frames of an ensemble
+from .api import WATER_BRIDGE_COLUMNS, get_water_bridges, water_bridges  # noqa: F401  water-mediated contacts, bridge by bridge
 from .api import TIMELINE_COLUMNS, contact_timelines, get_contact_timelines, timeline_stats, unpack_timeline  # noqa: F401  which frames each contact exists in
 from .api import bit_gram, contact_similarity, get_contact_similarity  # noqa: F401  which frames look alike, which contacts come and go together
 from .api import bit_cluster, contact_clusters, get_contact_clusters  # noqa: F401  which states there are, which frame stands for each, which contacts tell them apart

@@ -7,6 +7,7 @@
 residue pair and interaction (a model counts once however many of the residues' atoms are in contact).
 `contact-timeline` (no counterpart either) takes the flags of `contact-frequency` and writes its table with five more columns per row -- first_frame,
 last_frame, n_events, longest_run, mean_run: when the contact exists across the models -- and, with --bitmap FILE.npy, the rows' frame bitmap.
+Both take --waters (with --level residue): the WaterBridge rows.  `water-bridges` (no counterpart either) writes every water bridge of every model.
 `contact-similarity` (no counterpart either) takes the flags of `contact-timeline` without --bitmap, plus --axis frames|rows and --metric tanimoto|count:
 it writes `contact-frequency`'s table and, with --matrix FILE.npy, the matrix between the models (or between the rows).
 `contact-autocorrelation` (no counterpart either) takes the flags of `contact-timeline` without --bitmap, plus --mode intermittent|continuous and --max-lag N:
@@ -60,6 +61,7 @@ def build_parser() -> argparse.ArgumentParser:
     q.add_argument("--rings", action="store_true", help="Add the ring rows (CationPi, Pi stackings) of every model; ring-ring rows do not depend on --dist-cutoff")
     q.add_argument("-l", "--level", default="atom", choices=("atom", "residue"),
                    help="Rows per atom pair, or per residue pair (a model counts once however many of the residues' atoms are in contact)")
+    q.add_argument("--waters", action="store_true", help="Add the WaterBridge rows: residue pairs joined through a water within 3.5 A of a polar atom of each (needs -l residue)")
     tl = sub.add_parser("contact-timeline", help="in which models each contact exists: first / last model, events, longest run (contact-frequency's rows)")
     tl.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file whose models are the frames")
     tl.add_argument("-o", "--output", required=True, type=Path, help="Output directory")
@@ -73,8 +75,16 @@ def build_parser() -> argparse.ArgumentParser:
     tl.add_argument("--rings", action="store_true", help="Add the ring rows (CationPi, Pi stackings) of every model; ring-ring rows do not depend on --dist-cutoff")
     tl.add_argument("-l", "--level", default="atom", choices=("atom", "residue"),
                     help="Rows per atom pair, or per residue pair (a model counts once however many of the residues' atoms are in contact)")
+    tl.add_argument("--waters", action="store_true", help="Add the WaterBridge rows: residue pairs joined through a water within 3.5 A of a polar atom of each (needs -l residue)")
     tl.add_argument("--bitmap", default=None, type=Path, metavar="FILE.npy",
                     help="Also write the rows' frame bitmap: uint32 [rows, ceil(models / 32)], model f = bit f %% 32 of word f // 32")
+    wb = sub.add_parser("water-bridges", help="every water bridge of every model: the two bridged atoms, the water, both legs")
+    wb.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file whose models are the frames")
+    wb.add_argument("-o", "--output", required=True, type=Path, help="Output directory")
+    wb.add_argument("-g", "--groups", default="/", help="Chain groups, e.g. A,B/C,D ('/' = all against all)")
+    wb.add_argument("-f", "--filename", default="water_bridges", help="Name of the output file")
+    wb.add_argument("-t", "--output-format", default="csv", type=str.lower, choices=FORMATS, help="Output file type")
+    wb.add_argument("--ignore-zero-occupancy", action="store_true", help="Ignore atoms with zero occupancy")
     sm = sub.add_parser("contact-similarity", help="which models have the same contacts (Tanimoto matrix), or which contacts exist in the same models")
     sm.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file whose models are the frames")
     sm.add_argument("-o", "--output", required=True, type=Path, help="Output directory")
@@ -399,8 +409,12 @@ def run_contact_frequency(args) -> int:
     if not args.input.exists():
         log.error("Failed to retrieve input file: %s", args.input)
         return 1
+    if args.waters and args.level != "residue":
+        log.error("--waters needs --level residue (water-bridges lists the atoms of every bridge)")
+        return 1
     try:
-        table = aa.contact_frequencies(str(args.input.resolve()), args.groups, args.vdw_comp, args.dist_cutoff, args.ignore_zero_occupancy, rings=args.rings, level=args.level)
+        table = aa.contact_frequencies(str(args.input.resolve()), args.groups, args.vdw_comp, args.dist_cutoff, args.ignore_zero_occupancy, rings=args.rings, level=args.level,
+                                       waters=args.waters)
     except aa.ArpeggiaError as e:
         log.error("Contact frequencies failed: %s", e)
         return 1
@@ -420,9 +434,12 @@ def run_contact_timeline(args) -> int:
     if not args.input.exists():
         log.error("Failed to retrieve input file: %s", args.input)
         return 1
+    if args.waters and args.level != "residue":
+        log.error("--waters needs --level residue (water-bridges lists the atoms of every bridge)")
+        return 1
     try:
         table, words = api._contact_timelines_arrow(str(args.input.resolve()), args.groups, args.vdw_comp, args.dist_cutoff, args.ignore_zero_occupancy, args.rings,
-                                                    args.level, args.bitmap is not None)
+                                                    args.level, args.bitmap is not None, args.waters)
     except aa.ArpeggiaError as e:
         log.error("Contact timelines failed: %s", e)
         return 1
@@ -434,6 +451,24 @@ def run_contact_timeline(args) -> int:
         with open(args.bitmap, "wb") as f:  # (np.save on a name would append .npy to any other suffix)
             np.save(f, words)
     log.info("Results for %d contacts saved to %s", len(table), out)
+    return 0
+
+
+def run_water_bridges(args) -> int:
+    import arpeggia_amd as aa
+
+    if not args.input.exists():
+        log.error("Failed to retrieve input file: %s", args.input)
+        return 1
+    try:
+        table = aa.water_bridges(str(args.input.resolve()), args.groups, args.ignore_zero_occupancy)
+    except aa.ArpeggiaError as e:
+        log.error("Water bridges failed: %s", e)
+        return 1
+    args.output.mkdir(parents=True, exist_ok=True)
+    out = (args.output / args.filename).with_suffix("." + args.output_format)
+    write_table(table, out, args.output_format)
+    log.info("Results for %d water bridges saved to %s", len(table), out)
     return 0
 
 
@@ -544,6 +579,8 @@ def main(argv=None) -> int:
         return run_contact_frequency(args)
     if args.command == "contact-timeline":
         return run_contact_timeline(args)
+    if args.command == "water-bridges":
+        return run_water_bridges(args)
     if args.command == "contact-similarity":
         return run_contact_similarity(args)
     if args.command == "contact-autocorrelation":

@@ -29,6 +29,7 @@ ARP_SIM_ROWS = 0x8
 ARP_ACF_CONTINUOUS = 0x10
 ARP_ACF_NO_MATRIX = 0x20
 ARP_CLUSTER_NO_COUNTS = 0x40
+ARP_FREQ_WATERS = 0x100
 ARP_RADII_VDW, ARP_RADII_PROTOR = 0, 1
 
 ATTR = dict(
@@ -41,6 +42,9 @@ INTERACTIONS = [
     "PolarContact", "WeakPolarContact", "IonicRepulsion", "SaltBridge", "PiDisplacedStacking", "PiTStacking",
     "PiSandwichStacking", "PiParallelInPlaneStacking", "PiTiltedStacking", "PiLStacking", "CationPi", "HydrophobicContact",
 ]
+
+WATER_BRIDGE = 19  # ARP_WaterBridge: a row code of the ensemble tables, not a bit of arp_pair.kind (INTERACTIONS keeps the 19 variants)
+ROW_CODES = INTERACTIONS + ["WaterBridge"]  # what a table's "interaction" column can hold, by code
 
 _dp = C.POINTER(C.c_double)
 _u32p = C.POINTER(C.c_uint32)
@@ -215,6 +219,7 @@ def _load():
         "arp_contact_frequencies": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_double, C.c_double, C.POINTER(vp)]),
         "arp_contact_frequencies_ex": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_double, C.c_double, C.c_uint32, C.POINTER(vp)]),
         "arp_residue_contact_frequencies": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_double, C.c_double, C.c_uint32, C.POINTER(vp)]),
+        "arp_water_bridges": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.POINTER(vp)]),
         "arp_contact_timelines": (C.c_int32, [vp, vp, C.c_uint64, _dp, C.c_char_p, C.c_double, C.c_double, C.c_uint32, C.c_int32, C.POINTER(vp)]),
         "arp_table_timeline": (C.c_void_p, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "arp_timeline_stats": (C.c_int32, [C.c_uint64, C.c_uint64] + [_u32p] * 6),

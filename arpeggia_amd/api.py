@@ -43,6 +43,15 @@ RESIDUE_FREQ_COLUMNS = [  # arp_residue_contact_frequencies: one row per distinc
     ("to_chain", "str"), ("to_resn", "str"), ("to_resi", "i4"), ("to_insertion", "str"),
     ("n_frames", "u4"), ("frequency", "f4"), ("min_distance", "f4"), ("max_distance", "f4"),
 ]
+WATER_BRIDGE_COLUMNS = [  # arp_water_bridges: one row per bridge (from atom, water, to atom) of a frame, ordered by (frame, from_atom, to_atom, water_atom)
+    ("frame", "u4"),
+    ("from_chain", "str"), ("from_resn", "str"), ("from_resi", "i4"), ("from_insertion", "str"), ("from_altloc", "str"),
+    ("from_atomn", "str"), ("from_atomi", "i4"),
+    ("to_chain", "str"), ("to_resn", "str"), ("to_resi", "i4"), ("to_insertion", "str"), ("to_altloc", "str"),
+    ("to_atomn", "str"), ("to_atomi", "i4"),
+    ("water_chain", "str"), ("water_resi", "i4"), ("water_insertion", "str"), ("water_altloc", "str"), ("water_atomi", "i4"),
+    ("from_distance", "f4"), ("to_distance", "f4"), ("distance", "f4"),
+]
 TIMELINE_COLUMNS = [  # arp_contact_timelines: behind the frequency columns of the level (FREQ_COLUMNS / RESIDUE_FREQ_COLUMNS)
     ("first_frame", "u4"), ("last_frame", "u4"), ("n_events", "u4"), ("longest_run", "u4"), ("mean_run", "f4"),
 ]
@@ -351,29 +360,39 @@ class Context:
             lib.arp_table_free(t)
 
     def contact_frequencies(self, structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, rings: bool = False,
-                            level: str = "atom") -> dict:
+                            waters: bool = False, level: str = "atom") -> dict:
         """arp_contact_frequencies_ex as a dict of numpy columns (FREQ_COLUMNS + from_atom / to_atom).  frames: [F, N, 3] f64 coordinates of the
         topology's N atoms (model 0 of `structure`); None: the structure's models are the frames.  rings=True (ARP_FREQ_RINGS) adds the ring rows
         (CationPi, Pi* stackings) behind the atom rows, and the columns from_ring / to_ring (ring entity index, -1 for an atom; from_atom /
         to_atom are -1 for a ring).  level="residue": arp_residue_contact_frequencies -- one row per (residue, residue, interaction), a frame
         counted once per row however many of the residues' atom pairs (and, with rings, ring entities) are in contact; the columns are
-        RESIDUE_FREQ_COLUMNS + from_residue / to_residue (residue ordinals of the topology)."""
-        t = _freq_table(self, structure, frames, groups, vdw_comp, dist_cutoff, rings, level)
+        RESIDUE_FREQ_COLUMNS + from_residue / to_residue (residue ordinals of the topology).  waters=True (ARP_FREQ_WATERS, level="residue" only): the
+        water-bridge rows (interaction code _lib.WATER_BRIDGE) join the table; see get_contact_frequencies."""
+        t = _freq_table(self, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, waters)
         try:
             return _freq_columns(t, rings, level)
         finally:
             lib.arp_table_free(t)
 
     def contact_timelines(self, structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, rings: bool = False,
-                          level: str = "atom", bitmap: bool = True) -> dict:
+                          level: str = "atom", bitmap: bool = True, waters: bool = False) -> dict:
         """arp_contact_timelines as a dict of numpy columns: every column contact_frequencies returns for the same arguments (identical bytes), plus
         first_frame / last_frame / n_events / longest_run (u4) and mean_run (f4) per row (TIMELINE_COLUMNS): the first and last frame in which the
         row's contact exists, its number of uninterrupted stretches, the longest of them in frames, and n_frames / n_events.  bitmap=True adds
         timeline_words [rows, ceil(F / 32)] <u4 -- frame f is bit f & 31 of word f >> 5 (unpack_timeline makes it a bool [rows, F]) -- and
         n_total_frames = F; bitmap=False (ARP_TIMELINE_NO_BITMAP) leaves the bitmap on the device."""
-        t = _timeline_table(self, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, bitmap)
+        t = _timeline_table(self, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, bitmap, waters)
         try:
             return _timeline_columns(t, rings, level)
+        finally:
+            lib.arp_table_free(t)
+
+    def water_bridges(self, structure: Structure, frames=None, groups: str = "/") -> dict:
+        """arp_water_bridges as a dict of numpy columns: WATER_BRIDGE_COLUMNS + from_atom / water_atom / to_atom (topology atom indices).  See
+        get_water_bridges."""
+        t = _water_bridge_table(self, structure, frames, groups)
+        try:
+            return _read_columns(t, WATER_BRIDGE_COLUMNS, (("from_atom", "i4"), ("water_atom", "i4"), ("to_atom", "i4")))
         finally:
             lib.arp_table_free(t)
 
@@ -450,6 +469,13 @@ def _check_level(level: str):
         raise ValueError(f"level must be 'atom' or 'residue', got {level!r}")
 
 
+def _check_waters(waters: bool, level: str):
+    if not isinstance(waters, (bool, np.bool_)):  # (a level passed by position would land here: pass level by keyword)
+        raise TypeError(f"waters must be a bool, got {waters!r}")
+    if waters and level != "residue":
+        raise ValueError("waters=True needs level='residue' (a bridge joins two residues through a water); get_water_bridges lists the atoms of every bridge")
+
+
 def _read_columns(t, spec, extra=()) -> dict:
     """The numpy columns of a table handle (copies), read through arp_table_column.  spec: (name, kind) pairs as the *_COLUMNS lists hold them --
     "str": NUL-padded bytes of the column's width; interaction: the i4 codes (the names are the Arrow batch's); else the dtype.  extra: more such
@@ -503,15 +529,25 @@ def _topology_atoms(structure: Structure) -> int:
     return int(other[0]) if len(other) else len(m)
 
 
-def _freq_table(ctx: "Context | None", structure: Structure, frames, groups: str, vdw_comp: float, dist_cutoff: float, rings: bool = False, level: str = "atom"):
+def _freq_table(ctx: "Context | None", structure: Structure, frames, groups: str, vdw_comp: float, dist_cutoff: float, rings: bool = False, level: str = "atom",
+                waters: bool = False):
     """arp_contact_frequencies_ex (level "atom") or arp_residue_contact_frequencies ("residue") -> table handle (the caller frees it).  ctx None:
     the inputs are only checked (raises their error, else returns None)."""
     _check_level(level)
+    _check_waters(waters, level)
     n_frames, ptr, keep = _frames_arg(structure, frames, "contact frequencies")
     t = C.c_void_p()
     call = lib.arp_residue_contact_frequencies if level == "residue" else lib.arp_contact_frequencies_ex
     _check(call(ctx._h if ctx is not None else None, structure._h, int(n_frames), ptr, groups.encode(), float(vdw_comp),
-                float(dist_cutoff), _lib.ARP_FREQ_RINGS if rings else 0, C.byref(t)))
+                float(dist_cutoff), (_lib.ARP_FREQ_RINGS if rings else 0) | (_lib.ARP_FREQ_WATERS if waters else 0), C.byref(t)))
+    return t if ctx is not None else None
+
+
+def _water_bridge_table(ctx: "Context | None", structure: Structure, frames, groups: str):
+    """arp_water_bridges -> table handle (the caller frees it).  ctx None: the inputs are only checked (raises their error, else returns None)."""
+    n_frames, ptr, keep = _frames_arg(structure, frames, "water bridges")
+    t = C.c_void_p()
+    _check(lib.arp_water_bridges(ctx._h if ctx is not None else None, structure._h, int(n_frames), ptr, groups.encode(), C.byref(t)))
     return t if ctx is not None else None
 
 
@@ -523,12 +559,14 @@ def _freq_columns(t, rings: bool, level: str) -> dict:
     return _read_columns(t, FREQ_COLUMNS, (("from_atom", "i4"), ("to_atom", "i4")) + ((("from_ring", "i4"), ("to_ring", "i4")) if rings else ()))
 
 
-def _timeline_table(ctx: "Context | None", structure: Structure, frames, groups: str, vdw_comp: float, dist_cutoff: float, rings: bool, level: str, bitmap: bool):
+def _timeline_table(ctx: "Context | None", structure: Structure, frames, groups: str, vdw_comp: float, dist_cutoff: float, rings: bool, level: str, bitmap: bool,
+                    waters: bool = False):
     """arp_contact_timelines -> table handle (the caller frees it).  ctx None: the inputs are only checked (raises their error, else returns None)."""
     _check_level(level)
+    _check_waters(waters, level)
     n_frames, ptr, keep = _frames_arg(structure, frames, "contact timelines")
     t = C.c_void_p()
-    flags = (_lib.ARP_FREQ_RINGS if rings else 0) | (0 if bitmap else _lib.ARP_TIMELINE_NO_BITMAP)
+    flags = (_lib.ARP_FREQ_RINGS if rings else 0) | (0 if bitmap else _lib.ARP_TIMELINE_NO_BITMAP) | (_lib.ARP_FREQ_WATERS if waters else 0)
     _check(lib.arp_contact_timelines(ctx._h if ctx is not None else None, structure._h, int(n_frames), ptr, groups.encode(), float(vdw_comp), float(dist_cutoff),
                                      flags, 1 if level == "residue" else 0, C.byref(t)))
     return t if ctx is not None else None
@@ -1076,7 +1114,7 @@ def contacts(input_file: str, groups: str = "/", vdw_comp: float = 0.1, dist_cut
 
 
 def get_contact_frequencies(structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, device: int = 0,
-                            rings: bool = False, level: str = "atom"):
+                            rings: bool = False, waters: bool = False, level: str = "atom"):
     """How often every atom-atom contact occurs across the frames of an ensemble (arp_contact_frequencies_ex): one row per distinct
     (from atom, to atom, interaction) with n_frames, frequency, min_distance and max_distance (FREQ_COLUMNS).  frames: [F, N, 3] f64
     coordinates of the N atoms of the topology (model 0 of `structure`); None: the structure's models are the frames.  rings=True adds the
@@ -1084,10 +1122,16 @@ def get_contact_frequencies(structure: Structure, frames=None, groups: str = "/"
     ring-ring rows do not depend on dist_cutoff.  level="residue" (arp_residue_contact_frequencies): one row per distinct (residue of from,
     residue of to, interaction) instead -- n_frames counts the distinct frames in which ANY item of the residue pair has the interaction (what
     the atom-level table cannot give), min_distance / max_distance are the extremes over those frames of the frame's closest approach
-    (RESIDUE_FREQ_COLUMNS).  Returns a polars.DataFrame when polars is importable, else a pyarrow.Table, like get_contacts."""
+    (RESIDUE_FREQ_COLUMNS).  waters=True (level="residue" only; ValueError otherwise, before any device work) adds the water-bridge rows,
+    interaction "WaterBridge": residue pair (A, B) is bridged in a frame when a water atom (residue HOH, not hydrogen) lies within 3.5 A of a polar
+    heavy atom (donor or acceptor) of A and of one of B, A in the ligand and B in the receptor set, under the residue rule of the contact table
+    (one orientation per pair, residues at least two apart on one chain); the water's own chain plays no part, nor do vdw_comp and dist_cutoff.
+    The row's distance is the longer leg of the frame's tightest bridge.  Returns a polars.DataFrame when polars is importable, else a
+    pyarrow.Table, like get_contacts."""
     _check_level(level)
-    ctx = _with_context(device, lambda: _freq_table(None, structure, frames, groups, vdw_comp, dist_cutoff, rings, level))
-    t = _freq_table(ctx, structure, frames, groups, vdw_comp, dist_cutoff, rings, level)
+    _check_waters(waters, level)
+    ctx = _with_context(device, lambda: _freq_table(None, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, waters))
+    t = _freq_table(ctx, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, waters)
     try:
         table = _arrow_of(t)
     finally:
@@ -1096,31 +1140,54 @@ def get_contact_frequencies(structure: Structure, frames=None, groups: str = "/"
 
 
 def contact_frequencies(input_file: str, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, ignore_zero_occupancy: bool = False,
-                        rings: bool = False, level: str = "atom"):
+                        rings: bool = False, waters: bool = False, level: str = "atom"):
     """Contact frequencies across the models of a multi-model file (NMR models, MODEL-record snapshots): see get_contact_frequencies.  With
     rings=True the rings are those of model 0 regarded as a single-model structure, not what get_contacts files for the multi-model file.
-    level="residue": the residue-level table."""
+    level="residue": the residue-level table; waters=True: with the water-bridge rows."""
     _check_level(level)
-    return get_contact_frequencies(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings, level=level)
+    _check_waters(waters, level)
+    return get_contact_frequencies(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings, level=level, waters=waters)
 
 
 def get_contact_timelines(structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, device: int = 0,
-                          rings: bool = False, level: str = "atom", bitmap: bool = True) -> dict:
+                          rings: bool = False, level: str = "atom", bitmap: bool = True, waters: bool = False) -> dict:
     """When every contact of an ensemble exists (arp_contact_timelines): the rows of get_contact_frequencies for the same arguments, as a dict of
     numpy columns -- the frequency columns of the level (FREQ_COLUMNS + from_atom / to_atom, with rings from_ring / to_ring; RESIDUE_FREQ_COLUMNS +
     from_residue / to_residue), identical bytes -- plus TIMELINE_COLUMNS per row: first_frame, last_frame, n_events (maximal runs of consecutive
     frames with the contact), longest_run (frames) and mean_run = n_frames / n_events.  bitmap=True adds timeline_words [rows, ceil(F / 32)] <u4
-    (frame f = bit f & 31 of word f >> 5; unpack_timeline) and n_total_frames.  frames, groups, rings and level as get_contact_frequencies."""
+    (frame f = bit f & 31 of word f >> 5; unpack_timeline) and n_total_frames.  frames, groups, rings, level and waters as get_contact_frequencies
+    (bit_gram, bit_autocorrelation and bit_cluster on timeline_words give similarity, lifetimes and clusters of tables with water-bridge rows)."""
     _check_level(level)
-    ctx = _with_context(device, lambda: _timeline_table(None, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, bitmap))
-    return ctx.contact_timelines(structure, frames, groups, vdw_comp, dist_cutoff, rings, level, bitmap)
+    _check_waters(waters, level)
+    ctx = _with_context(device, lambda: _timeline_table(None, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, bitmap, waters))
+    return ctx.contact_timelines(structure, frames, groups, vdw_comp, dist_cutoff, rings, level, bitmap, waters)
 
 
 def contact_timelines(input_file: str, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, ignore_zero_occupancy: bool = False,
-                      rings: bool = False, level: str = "atom", bitmap: bool = True) -> dict:
+                      rings: bool = False, level: str = "atom", bitmap: bool = True, waters: bool = False) -> dict:
     """Contact timelines across the models of a multi-model file (the models are the frames): see get_contact_timelines."""
     _check_level(level)
-    return get_contact_timelines(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings, level=level, bitmap=bitmap)
+    _check_waters(waters, level)
+    return get_contact_timelines(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings, level=level, bitmap=bitmap, waters=waters)
+
+
+def get_water_bridges(structure: Structure, frames=None, groups: str = "/", device: int = 0):
+    """Every water bridge of every frame (arp_water_bridges): one row per (frame, from atom, to atom, water atom) with the identity of the three atoms,
+    the two legs (from_distance, to_distance) and the longer of them (distance) -- WATER_BRIDGE_COLUMNS.  The rule is get_contact_frequencies'
+    waters=True; grouping the rows by the residues of from and to gives that table's WaterBridge rows.  frames and groups as get_contact_frequencies.
+    Returns a polars.DataFrame when polars is importable, else a pyarrow.Table."""
+    ctx = _with_context(device, lambda: _water_bridge_table(None, structure, frames, groups))
+    t = _water_bridge_table(ctx, structure, frames, groups)
+    try:
+        table = _arrow_of(t)
+    finally:
+        lib.arp_table_free(t)
+    return _frame_of(table)
+
+
+def water_bridges(input_file: str, groups: str = "/", ignore_zero_occupancy: bool = False):
+    """Water bridges of every model of a file (the models are the frames): see get_water_bridges."""
+    return get_water_bridges(Structure.load(input_file, ignore_zero_occupancy), None, groups)
 
 
 def get_contact_similarity(structure: Structure, frames=None, groups: str = "/", vdw_comp: float = 0.1, dist_cutoff: float = 6.5, device: int = 0,
@@ -1212,11 +1279,12 @@ def _contact_similarity_arrow(input_file: str, groups: str, vdw_comp: float, dis
     return _arrow_of(owner.t), _similarity_matrix(owner)["intersection" if metric == "count" else "similarity"]
 
 
-def _contact_timelines_arrow(input_file: str, groups: str, vdw_comp: float, dist_cutoff: float, ignore_zero_occupancy: bool, rings: bool, level: str, bitmap: bool):
+def _contact_timelines_arrow(input_file: str, groups: str, vdw_comp: float, dist_cutoff: float, ignore_zero_occupancy: bool, rings: bool, level: str, bitmap: bool,
+                             waters: bool = False):
     """The command line's form of contact_timelines: (Arrow table of the frequency + timeline columns, timeline_words or None)."""
     structure = Structure.load(input_file, ignore_zero_occupancy)
-    ctx = _with_context(0, lambda: _timeline_table(None, structure, None, groups, vdw_comp, dist_cutoff, rings, level, bitmap))
-    t = _timeline_table(ctx, structure, None, groups, vdw_comp, dist_cutoff, rings, level, bitmap)
+    ctx = _with_context(0, lambda: _timeline_table(None, structure, None, groups, vdw_comp, dist_cutoff, rings, level, bitmap, waters))
+    t = _timeline_table(ctx, structure, None, groups, vdw_comp, dist_cutoff, rings, level, bitmap, waters)
     try:
         return _arrow_of(t), _timeline_columns(t, rings, level).get("timeline_words")
     finally:

@@ -779,4 +779,7 @@ static const char *k_interactions[ARP_N_INTERACTIONS] = {
     "StericClash", "CovalentBond", "Disulfide", "VanDerWaalsContact", "IonicBond", "HydrogenBond", "WeakHydrogenBond",
     "PolarContact", "WeakPolarContact", "IonicRepulsion", "SaltBridge", "PiDisplacedStacking", "PiTStacking",
     "PiSandwichStacking", "PiParallelInPlaneStacking", "PiTiltedStacking", "PiLStacking", "CationPi", "HydrophobicContact"};
-extern "C" const char *arp_interaction_name(int32_t code) { return (code >= 0 && code < ARP_N_INTERACTIONS) ? k_interactions[code] : "?"; }
+extern "C" const char *arp_interaction_name(int32_t code) {
+    if (code == ARP_WaterBridge) return "WaterBridge";  // (a row code of the ensemble tables, not a bit of arp_pair.kind: outside the enum)
+    return (code >= 0 && code < ARP_N_INTERACTIONS) ? k_interactions[code] : "?";
+}

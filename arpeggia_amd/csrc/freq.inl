@@ -163,6 +163,22 @@ __global__ __launch_bounds__(256) void k_freq_ring_rows(uint32_t n_tiles, uint32
                                  const double *y, const double *z, const PlaneD *planes, double cutoff, unsigned long long *keys, FreqVal *vals, uint32_t base, uint32_t cap,
                                  uint32_t *counter, FreqResKey rk, uint32_t *item_frame);
 
+// the water-bridge items of a pass (ARP_FREQ_WATERS): the kernel is in freq_water.inl, behind freq_rings.inl.  The topology's water atoms and polar
+// atoms on the device; a water keeps at most kFreqWaterPartners polar atoms within 3.5 A (more fail the call: water_capacity_error).
+struct FreqWaters {
+    uint32_t n_water, n_polar;
+    const uint32_t *water, *polar;
+};
+constexpr uint32_t kFreqWaterTile = 64, kFreqWaterPartners = 32;  // waters per workgroup of k_freq_water_rows; list entries per water
+template <bool TRIPLES>
+__global__ __launch_bounds__(256) void k_freq_water_rows(uint32_t n_tiles, uint32_t n, FreqWaters w, const uint32_t *attr, const uint32_t *res_ord, const uint32_t *chain_rank,
+                                                         const double *x, const double *y, const double *z, unsigned long long *keys, FreqVal *vals, WaterTriple *triples,
+                                                         uint32_t f0, uint32_t base, uint32_t cap, uint32_t *counter, uint32_t *err, FreqResKey rk);
+inline arp_status water_capacity_error() {
+    set_error("water bridges: a water has more than %u polar atoms within 3.5 A in some frame (the per-water partner list is full)", kFreqWaterPartners);
+    return ARP_ERR_CAPACITY;
+}
+
 // the mark sweep of arp_contact_timelines (timeline.inl, behind freq_rings.inl): the same passes -- upload, k_freq_tile, pair pass, ring fit -- but
 // every item ORs its frame's bit into its row of a bitmap instead of joining the aggregate.  What a pass hands over:
 struct TimelineMarks;
@@ -179,6 +195,8 @@ struct FreqPassView {
     const PlaneD *planes;
     double cutoff;
     FreqResKey rk;
+    FreqWaters fw;                    // n_water > 0: what k_freq_water_rows takes
+    uint32_t water_tiles;
 };
 arp_status timeline_mark_pass(hipStream_t st, TimelineMarks *marks, const FreqPassView &v);
 
@@ -230,6 +248,7 @@ arp_status freq_sweep(arp_context *ctx, const FreqJob &job, FreqRowsHost *out, T
     *out = FreqRowsHost{};
     const uint64_t n = job.n, nr = job.n_res, nh = job.n_h, F = job.n_frames;
     const uint64_t n_rings = job.n_rings, n_slots = job.n_slots, n_cand = job.n_cand, n_ra = n_rings ? job.res_atom_ptr[nr] : 0;
+    const uint64_t n_water = job.residue ? job.n_water : 0, n_polar = n_water ? job.n_polar : 0, water_tiles = (n_water + kFreqWaterTile - 1) / kFreqWaterTile;
     if (n == 0 || F == 0) return ARP_OK;
     // frames per pass: the knob's atom budget, else kFreqAutoAtoms; never more frames than fit 32-bit packed indices
     const uint64_t budget = job.chunk_atoms ? job.chunk_atoms : kFreqAutoAtoms;
@@ -246,15 +265,18 @@ arp_status freq_sweep(arp_context *ctx, const FreqJob &job, FreqRowsHost *out, T
         per = std::min<uint64_t>(per, (1ull << fbits) - 1u);
     }
     if (n_rings) per = std::min<uint64_t>(per, std::max<uint64_t>(1, 0x7FFFFFF0ull / std::max<uint64_t>({n_slots, (n_rings + kFreqRingTile - 1) / kFreqRingTile, 1})));  // (one thread per (frame, slot), one workgroup per (frame, tile))
+    if (n_water) per = std::min<uint64_t>(per, std::max<uint64_t>(1, 0x7FFFFFF0ull / water_tiles));  // (one workgroup per (frame, tile))
     if (per == 0) { set_error("contact frequencies: one frame exceeds 32-bit indices"); return ARP_ERR_BAD_INPUT; }
     // topology (once) and the packed arrays of one pass
     struct Seg { const void *src; uint64_t bytes; };
-    const Seg topo_seg[14] = {{job.attr, n * 4}, {job.res_ord, n * 4}, {job.chain_rank, n * 4}, {nr ? job.res_id : nullptr, nr ? n * 4 : 0},
+    const Seg topo_seg[16] = {{job.attr, n * 4}, {job.res_ord, n * 4}, {job.chain_rank, n * 4}, {nr ? job.res_id : nullptr, nr ? n * 4 : 0},
                              {nr ? job.res_h_ptr : nullptr, nr ? (nr + 1) * 4 : 0}, {nh ? job.res_h_idx : nullptr, nh * 4}, {nr ? job.res_cb : nullptr, nr * 4},
                              {nr ? job.res_sg : nullptr, nr * 4},
                              // the rings of the topology (ARP_FREQ_RINGS; nothing otherwise)
                              {job.rings, n_rings * sizeof(RingEnt)}, {job.slot_res, n_slots * 4}, {job.res_atom_ptr, n_rings ? (nr + 1) * 4 : 0}, {job.res_atom_idx, n_ra * 4},
-                             {job.cand, n_cand * 4}, {job.plane_bits, n_rings ? n : 0}};
+                             {job.cand, n_cand * 4}, {job.plane_bits, n_rings ? n : 0},
+                             // the water and polar atoms of the topology (ARP_FREQ_WATERS; nothing otherwise)
+                             {job.water, n_water * 4}, {job.polar, n_polar * 4}};
     uint64_t topo_bytes = 0;
     for (const Seg &g : topo_seg) topo_bytes += seg_align(g.bytes);
     const uint64_t pn = per * n, pr = per * nr, ph = per * nh;
@@ -263,8 +285,8 @@ arp_status freq_sweep(arp_context *ctx, const FreqJob &job, FreqRowsHost *out, T
     HIP_TRY(hipMalloc((void **)&block, topo_bytes + pack_bytes + seg_align(per * n_slots * sizeof(PlaneD)) + 256));
     std::unique_ptr<char, void (*)(char *)> block_owner(block, [](char *p) { (void)hipFree(p); });
     Bump bp{block};
-    const void *topo_dev[14];
-    for (int k = 0; k < 14; k++) {
+    const void *topo_dev[16];
+    for (int k = 0; k < 16; k++) {
         char *d = bp.take<char>(topo_seg[k].bytes);
         topo_dev[k] = d;
         if (topo_seg[k].bytes) HIP_TRY(hipMemcpyAsync(d, topo_seg[k].src, topo_seg[k].bytes, hipMemcpyHostToDevice, st));
@@ -281,6 +303,7 @@ arp_status freq_sweep(arp_context *ctx, const FreqJob &job, FreqRowsHost *out, T
                        (const uint32_t *)topo_dev[12], (const uint8_t *)topo_dev[13], (const RingEnt *)topo_dev[8]};
     PlaneD *planes = bp.take<PlaneD>(per * n_slots);  // one pass's ring planes, frames x slots
     const uint32_t ring_tiles = (uint32_t)((n_rings + kFreqRingTile - 1) / kFreqRingTile);
+    const FreqWaters fw{(uint32_t)n_water, (uint32_t)n_polar, (const uint32_t *)topo_dev[14], (const uint32_t *)topo_dev[15]};
     lap("topology upload");
     arp_params prm;
     arp_default_params(&prm);
@@ -316,7 +339,7 @@ arp_status freq_sweep(arp_context *ctx, const FreqJob &job, FreqRowsHost *out, T
         if (s != ARP_OK) return s;
         lap("pair pass");
         if (n_pairs > 0xFFFFFFF0ull) { set_error("contact frequencies: more than 2^32 pairs in one pass (lower freq_chunk_atoms)"); return ARP_ERR_CAPACITY; }
-        if (n_pairs == 0 && !n_rings) continue;  // (ring - ring items need no atom pair: with rings no pass is skipped here)
+        if (n_pairs == 0 && !n_rings && !n_water) continue;  // (ring - ring items and water bridges need no atom pair: with either no pass is skipped here)
         if (n_rings) {  // the frames' ring planes
             hipLaunchKernelGGL(k_freq_ring_fit, dim3((uint32_t)((fc * n_slots + 127u) / 128u)), dim3(128), 0, st, (uint32_t)fc, (uint32_t)n, fr, (const double *)pk.x, (const double *)pk.y,
                                (const double *)pk.z, planes);
@@ -325,16 +348,18 @@ arp_status freq_sweep(arp_context *ctx, const FreqJob &job, FreqRowsHost *out, T
         }
         if (marks) {
             const FreqPassView view{(uint32_t)n, (uint32_t)f0, (uint32_t)fc, (uint32_t)n_pairs, pairs, job.residue, rb, tp.res_id, fr, ring_tiles, tp.attr, tp.res_ord, tp.chain_rank,
-                                    pk.x, pk.y, pk.z, planes, job.dist_cutoff, rk};
+                                    pk.x, pk.y, pk.z, planes, job.dist_cutoff, rk, fw, (uint32_t)water_tiles};
             if ((s = timeline_mark_pass(st, marks, view)) != ARP_OK) return s;
             lap("marks");
             continue;
         }
-        // 3. expand into (key, value) items behind the aggregate, the ring items behind the atom items; grown and repeated when they do not fit
+        // 3. expand into (key, value) items behind the aggregate, the ring items behind the atom items, the water bridges behind both; grown and
+        // repeated when they do not fit
         if (!fb.block && (s = freq_alloc(&fb, g_debug.freq_cap_items > 0 ? (uint64_t)g_debug.freq_cap_items : std::max<uint64_t>(1u << 16, 2 * n_pairs), 0, st)) != ARP_OK) return s;
-        uint32_t n_items = 0;
+        uint32_t counted[2] = {0u, 0u};  // {items, the water kernel's error word}
+        const size_t counted_bytes = n_water ? 8 : 4;
         for (int attempt = 0;; attempt++) {
-            HIP_TRY(hipMemsetAsync(fb.counter, 0, 4, st));
+            HIP_TRY(hipMemsetAsync(fb.counter, 0, counted_bytes, st));
             if (n_pairs) hipLaunchKernelGGL(expand_kernel, dim3(freq_blocks(n_pairs)), dim3(256), 0, st, pairs, (uint32_t)n_pairs,
                                             (uint32_t)n, fb.kin, fb.vin, (uint32_t)n_agg, (uint32_t)fb.cap, fb.counter, rk);
             HIP_TRY(hipGetLastError());
@@ -345,14 +370,24 @@ arp_status freq_sweep(arp_context *ctx, const FreqJob &job, FreqRowsHost *out, T
                                    fb.kin, fb.vin, (uint32_t)n_agg, (uint32_t)fb.cap, fb.counter, rk, (uint32_t *)nullptr);
                 HIP_TRY(hipGetLastError());
             }
-            HIP_TRY(hipMemcpyAsync(&n_items, fb.counter, 4, hipMemcpyDeviceToHost, st));
+            if (n_water) {
+                lap(n_rings ? "ring rows" : "expand");
+                hipLaunchKernelGGL(k_freq_water_rows<false>, dim3((uint32_t)(fc * water_tiles)), dim3(256), 0, st, (uint32_t)water_tiles, (uint32_t)n, fw, tp.attr, tp.res_ord,
+                                   tp.chain_rank, (const double *)pk.x, (const double *)pk.y, (const double *)pk.z, fb.kin, fb.vin, (WaterTriple *)nullptr, 0u, (uint32_t)n_agg,
+                                   (uint32_t)fb.cap, fb.counter, fb.counter + 1, rk);
+                HIP_TRY(hipGetLastError());
+            }
+            HIP_TRY(hipMemcpyAsync(counted, fb.counter, counted_bytes, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
+            if (counted[1]) return water_capacity_error();
+            const uint32_t n_items = counted[0];
             if (n_agg + n_items <= fb.cap) break;
             if (attempt) { set_error("internal error: the item count changed between passes"); return ARP_ERR_HIP; }
             const uint64_t want = n_agg + n_items;
             if ((s = freq_alloc(&fb, want + want / 4, n_agg, st)) != ARP_OK) return s;
         }
-        lap(n_rings ? "ring rows" : "expand");
+        lap(n_water ? "water bridges" : n_rings ? "ring rows" : "expand");
+        const uint32_t n_items = counted[0];
         if (n_items == 0) continue;
         // 4. + 5. sort the aggregate and the new items together, reduce every run of equal keys to one
         const uint32_t m = (uint32_t)(n_agg + n_items);

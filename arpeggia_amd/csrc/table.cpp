@@ -32,10 +32,10 @@ const void *side_data(const SideCols &c, uint32_t bit) {
         default: return c.residue.data();
     }
 }
-const char *side_name(int side, size_t field) {  // "from_chain" ... "to_residue": built once, never freed (an exported schema may point at them for ever)
+const char *side_name(int side, size_t field) {  // "from_chain" ... "water_residue": built once, never freed (an exported schema may point at them for ever)
     static const std::vector<std::string> *names = [] {
         auto *v = new std::vector<std::string>();
-        for (const char *prefix : {"from_", "to_"})
+        for (const char *prefix : {"from_", "to_", "water_"})
             for (const SideFieldInfo &f : kSideFields) v->push_back(std::string(prefix) + f.suffix);
         return v;
     }();
@@ -44,17 +44,15 @@ const char *side_name(int side, size_t field) {  // "from_chain" ... "to_residue
 void add_number(arp_table *t, const char *name, const char *format, const void *data, bool in_batch = true) {
     t->columns.push_back(TableColumn{name, 4, format, TableColumn::kNumber, in_batch, data, nullptr});
 }
-void add_sides(arp_table *t) {
-    for (int side = 0; side < 2; side++) {
-        const SideCols &c = side ? t->to : t->from;
-        for (size_t f = 0; f < kNSideFields; f++) {
-            const SideFieldInfo &info = kSideFields[f];
-            if (!(c.fields & info.bit)) continue;
-            t->columns.push_back(TableColumn{side_name(side, f), info.width, info.format, info.format[0] == 'u' ? TableColumn::kString : TableColumn::kNumber, info.in_batch,
-                                             side_data(c, info.bit), nullptr});
-        }
+void add_side(arp_table *t, int side, const SideCols &c) {  // side: 0 from, 1 to, 2 water
+    for (size_t f = 0; f < kNSideFields; f++) {
+        const SideFieldInfo &info = kSideFields[f];
+        if (!(c.fields & info.bit)) continue;
+        t->columns.push_back(TableColumn{side_name(side, f), info.width, info.format, info.format[0] == 'u' ? TableColumn::kString : TableColumn::kNumber, info.in_batch,
+                                         side_data(c, info.bit), nullptr});
     }
 }
+void add_sides(arp_table *t) { add_side(t, 0, t->from); add_side(t, 1, t->to); }
 }  // namespace
 
 void arp::SideCols::resize(size_t n, uint32_t which) {
@@ -97,6 +95,18 @@ void arp::frequency_columns(arp_table *t, uint32_t side) {
     add_number(t, "frequency", "f", t->frequency.data());
     add_number(t, "min_distance", "f", t->min_distance.data());
     add_number(t, "max_distance", "f", t->max_distance.data());
+}
+
+void arp::water_bridge_columns(arp_table *t) {
+    const size_t n = t->n;
+    t->frame.resize(n); t->from_distance.resize(n); t->to_distance.resize(n); t->distance.resize(n);
+    t->from.resize(n, kContactSide); t->to.resize(n, kContactSide); t->water.resize(n, kWaterSide);
+    add_number(t, "frame", "I", t->frame.data());
+    add_sides(t);
+    add_side(t, 2, t->water);
+    add_number(t, "from_distance", "f", t->from_distance.data());
+    add_number(t, "to_distance", "f", t->to_distance.data());
+    add_number(t, "distance", "f", t->distance.data());
 }
 
 void arp::timeline_columns(arp_table *t) {

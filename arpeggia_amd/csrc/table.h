@@ -36,6 +36,7 @@ enum SideField : uint32_t { kChain = 1, kResn = 2, kResi = 4, kInsertion = 8, kA
 constexpr uint32_t kContactSide = kChain | kResn | kResi | kInsertion | kAltloc | kAtomn | kAtomi | kAtom;
 constexpr uint32_t kAtomFreqSide = kContactSide | kRing;
 constexpr uint32_t kResidueFreqSide = kChain | kResn | kResi | kInsertion | kResidue;
+constexpr uint32_t kWaterSide = kChain | kResi | kInsertion | kAltloc | kAtomi | kAtom;  // the mediating water of arp_water_bridges ("water_*")
 struct SideCols {
     uint32_t fields = 0;
     StrCol<8> chain, resn, atomn;
@@ -118,6 +119,10 @@ struct arp_table {
     arp::AutocorrHost acf;
     std::vector<float> half_life;
     std::vector<uint8_t> half_life_valid;
+    // water-bridge table (arp_water_bridges): one row per bridge (from atom, water, to atom) of a frame; `distance` is the longer leg
+    arp::SideCols water;
+    std::vector<uint32_t> frame;
+    std::vector<float> from_distance, to_distance;
     // contact-cluster table (arp_contact_clusters): a frequency table of either level that owns the per-frame and per-cluster arrays and the rows x clusters
     // counts (arp_table_clusters); none of them is a column
     bool clustered = false;
@@ -131,6 +136,7 @@ namespace arp {
 // size keeps its values -- and lists them in t->columns.
 void contact_columns(arp_table *t);                        // the 20 columns of arp_get_contacts + sc_valid, from_atom / to_atom
 void frequency_columns(arp_table *t, uint32_t side);       // kAtomFreqSide or kResidueFreqSide
+void water_bridge_columns(arp_table *t);                   // frame, the from / to / water identities, the two legs and the longer of them
 void timeline_columns(arp_table *t);                       // behind frequency_columns: t->tl's statistics + mean_run
 void autocorrelation_columns(arp_table *t);                // behind frequency_columns: half_life, from t->acf.half_life (ARP_NONE: null)
 

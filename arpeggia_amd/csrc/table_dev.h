@@ -91,6 +91,10 @@ struct FreqJob {
     // rows' keys are res(from) << (res_bits + 5) | res(to) << 5 | code.  frame_bits: the knob freq_frame_bits, 0 = automatic
     bool residue = false;
     uint32_t frame_bits = 0;
+    // ARP_FREQ_WATERS (freq_water.inl), n_water > 0: the topology's water atoms (residue HOH, not ARP_ATTR_H) and polar atoms
+    // (ARP_ATTR_DONOR or ARP_ATTR_ACCEPTOR, not ARP_ATTR_H), both ascending and disjoint; residue level only
+    uint64_t n_water = 0, n_polar = 0;
+    const uint32_t *water = nullptr, *polar = nullptr;
 };
 struct FreqRowsHost {
     std::vector<unsigned long long> key;
@@ -99,6 +103,12 @@ struct FreqRowsHost {
     uint32_t res_bits = 0;  // residue level: bits of a residue ordinal in the keys
 };
 arp_status device_frequencies(arp_context *ctx, const FreqJob &job, FreqRowsHost *out);
+
+// Water bridges (freq_water.inl, arp_water_bridges): one record per bridge (p, w, q) of every frame -- topology atom indices,
+// the two legs as f32 -- ordered by (frame, p, q, w).  Of the job only the topology's attr / res_ord / chain_rank, the frames and the water and polar
+// lists are read.
+struct WaterTriple { uint32_t frame, p, q, w; float dp, dq; };
+arp_status device_water_bridges(arp_context *ctx, const FreqJob &job, std::vector<WaterTriple> *out);
 
 // Contact timelines (timeline.inl, arp_contact_timelines): the frequency rows of the job (device_frequencies' own result)
 // and, per row, the bitmap of the frames that feed it (bit f & 31 of words[r * words_per_row + (f >> 5)]) with its statistics.  want_bitmap false:

@@ -1020,6 +1020,7 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
 
 #include "freq.inl"
 #include "freq_rings.inl"
+#include "freq_water.inl"
 #include "timeline.inl"
 #include "similarity.inl"
 #include "autocorr.inl"

@@ -1,5 +1,5 @@
 // The ensemble entry points -- contact frequencies, their residue level (3.12), timelines (3.13), similarity (3.14),
-// autocorrelation (3.16) and clusters (3.17) -- and the host yardsticks of the last four (arp_timeline_stats, arp_bit_gram_host, arp_bit_autocorr_host,
+// autocorrelation (3.16), clusters (3.17) and water bridges (3.19) -- and the host yardsticks of the last four (arp_timeline_stats, arp_bit_gram_host, arp_bit_autocorr_host,
 // arp_bit_cluster_host).  One preamble (freq_prepare) checks the call and fills the device job; the device pipelines are freq.inl, timeline.inl,
 // similarity.inl, autocorr.inl and cluster.inl; the table they all return is the level's frequency table (table.cpp's columns), with the timeline columns,
 // the matrix, the curves or the clusters attached.
@@ -86,6 +86,7 @@ struct FreqPrep {
     std::vector<double> model_xyz;
     std::vector<uint32_t> attr;
     FreqRingTopo rt;
+    std::vector<uint32_t> water, polar;   // ARP_FREQ_WATERS: the topology's water atoms and polar atoms, ascending
     FreqJob job;
     uint64_t timeline_cap = 0, similarity_cap = 0, autocorr_cap = 0;   // bytes the bitmap / the similarity matrix / the autocorrelation matrix may take
     bool checked_only = false;
@@ -98,6 +99,10 @@ arp_status freq_prepare(const char *what, uint32_t own_flags, int32_t level, arp
     if (unknown) { set_error("%s: unknown flag bits 0x%x", what, unknown); return ARP_ERR_BAD_INPUT; }
     if (level != 0 && level != 1) { set_error("%s: level must be 0 (atoms) or 1 (residues), got %d", what, (int)level); return ARP_ERR_BAD_INPUT; }
     p->level = level;
+    if ((flags & ARP_FREQ_WATERS) && level == 0) {
+        set_error("%s: ARP_FREQ_WATERS needs level 1 (residues): a bridge joins two residues through a water; arp_water_bridges lists the atoms of every bridge", what);
+        return ARP_ERR_BAD_INPUT;
+    }
     // validation: nothing here touches the device
     uint64_t &n0 = p->n0, &r0 = p->r0, nm = 1;
     arp_status st = freq_topology(s, xyz == nullptr, &n0, &r0, &nm);
@@ -149,6 +154,19 @@ arp_status freq_prepare(const char *what, uint32_t own_flags, int32_t level, arp
             return ARP_ERR_BAD_INPUT;
         }
     }
+    // ARP_FREQ_WATERS: water atoms (residue HOH, not hydrogen) and polar atoms (donor or acceptor, not hydrogen); the classes keep them apart
+    if (flags & ARP_FREQ_WATERS) {
+        for (uint64_t a = 0; a < n0; a++) {
+            if (attr[a] & ARP_ATTR_H) continue;
+            const bool water = strcmp(s->res_resn.at(a), "HOH") == 0, polar = (attr[a] & (ARP_ATTR_DONOR | ARP_ATTR_ACCEPTOR)) != 0u;
+            if (water && polar) {
+                set_error("water bridges: atom %llu (%s of HOH %d, chain %s) is a water atom with a donor or acceptor class", (unsigned long long)a, s->name.at(a), s->resi[a], s->chain.at(a));
+                return ARP_ERR_BAD_INPUT;
+            }
+            if (water) p->water.push_back((uint32_t)a);
+            else if (polar) p->polar.push_back((uint32_t)a);
+        }
+    }
     p->checked_only = !ctx;
     if (!ctx) return ARP_OK;  // validation only
     FreqJob &job = p->job;
@@ -164,6 +182,8 @@ arp_status freq_prepare(const char *what, uint32_t own_flags, int32_t level, arp
     p->timeline_cap = g_debug.timeline_cap_bytes > 0 ? (uint64_t)g_debug.timeline_cap_bytes : (1ull << 31);
     p->similarity_cap = g_debug.similarity_cap_bytes > 0 ? (uint64_t)g_debug.similarity_cap_bytes : (1ull << 31);
     p->autocorr_cap = g_debug.autocorr_cap_bytes > 0 ? (uint64_t)g_debug.autocorr_cap_bytes : (1ull << 31);
+    job.n_water = p->water.size(); job.n_polar = p->polar.size();
+    job.water = p->water.data(); job.polar = p->polar.data();
     if (n_rings) {
         std::unordered_map<std::string, uint32_t> rank;
         for (size_t k = 0; k < s->chain_ids.size(); k++) rank[s->chain_ids[k]] = (uint32_t)k;
@@ -224,7 +244,7 @@ namespace {
 arp_status contact_frequencies(int32_t level, arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp, double dist_cutoff,
                                uint32_t flags, arp_table **out) {
     FreqPrep prep;
-    arp_status st = freq_prepare("contact frequencies", 0u, level, ctx, s, n_frames, xyz, groups, vdw_comp, dist_cutoff, flags, out, &prep);
+    arp_status st = freq_prepare("contact frequencies", level == 1 ? ARP_FREQ_WATERS : 0u, level, ctx, s, n_frames, xyz, groups, vdw_comp, dist_cutoff, flags, out, &prep);
     if (st != ARP_OK || prep.checked_only) return st;
     FreqRowsHost rows;
     if ((st = device_frequencies(ctx, prep.job, &rows)) != ARP_OK) return st;
@@ -247,7 +267,7 @@ extern "C" arp_status arp_residue_contact_frequencies(arp_context *ctx, arp_stru
 extern "C" arp_status arp_contact_timelines(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
                                             double dist_cutoff, uint32_t flags, int32_t level, arp_table **out) try {
     FreqPrep prep;
-    arp_status st = freq_prepare("contact timelines", ARP_TIMELINE_NO_BITMAP, level, ctx, s, n_frames, xyz, groups, vdw_comp, dist_cutoff, flags, out, &prep);
+    arp_status st = freq_prepare("contact timelines", ARP_TIMELINE_NO_BITMAP | ARP_FREQ_WATERS, level, ctx, s, n_frames, xyz, groups, vdw_comp, dist_cutoff, flags, out, &prep);
     if (st != ARP_OK || prep.checked_only) return st;
     FreqRowsHost rows;
     TimelineHost tl;
@@ -258,6 +278,26 @@ extern "C" arp_status arp_contact_timelines(arp_context *ctx, arp_structure *s, 
     t->tl_frames = prep.F;
     timeline_columns(t.get());
     for (uint64_t k = 0; k < t->n; k++) t->mean_run[k] = (float)((double)t->n_frames[k] / (double)t->tl.n_events[k]);
+    *out = t.release();
+    return ARP_OK;
+} ARP_ABI_CATCH
+
+// ---- water bridges, frame by frame (device pipeline: freq_water.inl) ----------------------------------------------------------
+extern "C" arp_status arp_water_bridges(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const char *groups, arp_table **out) try {
+    FreqPrep prep;
+    arp_status st = freq_prepare("water bridges", ARP_FREQ_WATERS, 1, ctx, s, n_frames, xyz, groups, 0.1, 6.5, ARP_FREQ_WATERS, out, &prep);
+    if (st != ARP_OK || prep.checked_only) return st;
+    std::vector<WaterTriple> rows;
+    if ((st = device_water_bridges(ctx, prep.job, &rows)) != ARP_OK) return st;
+    std::unique_ptr<arp_table> t(new arp_table());
+    t->n = rows.size();
+    water_bridge_columns(t.get());
+    for (size_t k = 0; k < t->n; k++) {
+        const WaterTriple &r = rows[k];
+        t->frame[k] = r.frame;
+        t->from.put(k, atom_entity(*s, r.p)); t->to.put(k, atom_entity(*s, r.q)); t->water.put(k, atom_entity(*s, r.w));
+        t->from_distance[k] = r.dp; t->to_distance[k] = r.dq; t->distance[k] = std::max(r.dp, r.dq);
+    }
     *out = t.release();
     return ARP_OK;
 } ARP_ABI_CATCH

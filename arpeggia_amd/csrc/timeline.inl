@@ -5,7 +5,7 @@
 //   rows   device_frequencies as it is: its table is the call's frequency columns, its sorted row keys go back to the device;
 //   marks  freq_sweep runs the same passes again (upload, k_freq_tile, contacts-only pair pass, ring fit); timeline_mark_pass finds every item's
 //          row by binary search and ORs bit f & 31 into words[r][f >> 5].  Atom pairs are read straight from the pair list (no expand, no sort,
-//          no item buffer); ring items come from k_freq_ring_rows into a small buffer of their own.
+//          no item buffer); ring items come from k_freq_ring_rows, water bridges from k_freq_water_rows, into a small buffer of their own.
 // OR is idempotent and order-free: the bitmap does not depend on the pass size or on the order of pairs, and two passes may share a word.
 // k_timeline_stats then folds each row's words, one wave per row, into {first, last, events, longest run, popcount}.
 //
@@ -17,7 +17,7 @@ struct TimelineMarks {
     uint32_t *words;                     // n_rows x W, zeroed
     uint64_t W;
     uint32_t *err;                       // device error word: 1 = an item without a row, 2 = a frame outside the call
-    // the ring items of one pass (allocated by the first pass with rings, grown when a pass has more)
+    // the ring and water-bridge items of one pass (allocated by the first pass with either, grown when a pass has more)
     char *items = nullptr;
     uint64_t items_cap = 0;
 };
@@ -142,11 +142,11 @@ __global__ __launch_bounds__(256) void k_timeline_stats(uint32_t n_rows, uint64_
 }
 
 namespace {
-// the ring items' buffers inside marks->items
+// the ring and water items' buffers inside marks->items
 struct TimelineItems { unsigned long long *keys; FreqVal *vals; uint32_t *frame, *counter; };
 arp_status timeline_items(TimelineMarks *mk, uint64_t cap, TimelineItems *it) {
     if (cap > mk->items_cap) {
-        if (cap > 0x7FFFFFF0ull) { set_error("contact timelines: more than 2^31 ring items in one pass (lower freq_chunk_atoms)"); return ARP_ERR_CAPACITY; }
+        if (cap > 0x7FFFFFF0ull) { set_error("contact timelines: more than 2^31 ring and water items in one pass (lower freq_chunk_atoms)"); return ARP_ERR_CAPACITY; }
         if (mk->items) { (void)hipFree(mk->items); mk->items = nullptr; mk->items_cap = 0; }
         HIP_TRY(hipMalloc((void **)&mk->items, seg_align(cap * 8) + seg_align(cap * sizeof(FreqVal)) + seg_align(cap * 4) + seg_align(256)));
         mk->items_cap = cap;
@@ -165,20 +165,31 @@ arp_status timeline_mark_pass(hipStream_t st, TimelineMarks *mk, const FreqPassV
                            mk->words, mk->W, mk->err);
         HIP_TRY(hipGetLastError());
     }
-    if (!v.fr.n_rings) return ARP_OK;
+    if (!v.fr.n_rings && !v.fw.n_water) return ARP_OK;
     const auto ring_rows_kernel = v.residue ? k_freq_ring_rows<true> : k_freq_ring_rows<false>;
     TimelineItems it;
     // (the knob freq_cap_items sizes this first buffer too, so that tests make it grow)
     arp_status s = timeline_items(mk, std::max<uint64_t>(mk->items_cap, g_debug.freq_cap_items > 0 ? (uint64_t)g_debug.freq_cap_items : 1u << 14), &it);
     if (s != ARP_OK) return s;
+    uint32_t counted[2] = {0u, 0u};  // {items, the water kernel's error word}
+    const size_t counted_bytes = v.fw.n_water ? 8 : 4;
     uint32_t n_items = 0;
     for (int attempt = 0;; attempt++) {  // grown and repeated when the items do not fit, as in device_frequencies
-        HIP_TRY(hipMemsetAsync(it.counter, 0, 4, st));
-        hipLaunchKernelGGL(ring_rows_kernel, dim3(v.frames * v.ring_tiles), dim3(256), 0, st, v.ring_tiles, v.n, v.fr, v.attr, v.res_ord, v.chain_rank, v.x, v.y, v.z, v.planes,
-                           v.cutoff, it.keys, it.vals, 0u, (uint32_t)mk->items_cap, it.counter, v.rk, v.residue ? (uint32_t *)nullptr : it.frame);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&n_items, it.counter, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemsetAsync(it.counter, 0, counted_bytes, st));
+        if (v.fr.n_rings) {
+            hipLaunchKernelGGL(ring_rows_kernel, dim3(v.frames * v.ring_tiles), dim3(256), 0, st, v.ring_tiles, v.n, v.fr, v.attr, v.res_ord, v.chain_rank, v.x, v.y, v.z, v.planes,
+                               v.cutoff, it.keys, it.vals, 0u, (uint32_t)mk->items_cap, it.counter, v.rk, v.residue ? (uint32_t *)nullptr : it.frame);
+            HIP_TRY(hipGetLastError());
+        }
+        if (v.fw.n_water) {  // (residue level only: the water items carry their frame in the key's tag, like the ring items of that level)
+            hipLaunchKernelGGL(k_freq_water_rows<false>, dim3(v.frames * v.water_tiles), dim3(256), 0, st, v.water_tiles, v.n, v.fw, v.attr, v.res_ord, v.chain_rank, v.x, v.y, v.z,
+                               it.keys, it.vals, (WaterTriple *)nullptr, 0u, 0u, (uint32_t)mk->items_cap, it.counter, it.counter + 1, v.rk);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(counted, it.counter, counted_bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
+        if (counted[1]) return water_capacity_error();
+        n_items = counted[0];
         if (n_items <= mk->items_cap) break;
         if (attempt) { set_error("internal error: the item count changed between passes"); return ARP_ERR_HIP; }
         if ((s = timeline_items(mk, (uint64_t)n_items + n_items / 4u, &it)) != ARP_OK) return s;

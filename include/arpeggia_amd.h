@@ -44,6 +44,9 @@ enum {
     ARP_PiDisplacedStacking, ARP_PiTStacking, ARP_PiSandwichStacking, ARP_PiParallelInPlaneStacking,
     ARP_PiTiltedStacking, ARP_PiLStacking, ARP_CationPi, ARP_HydrophobicContact, ARP_N_INTERACTIONS
 };
+/* A row code of the ensemble tables only (ARP_FREQ_WATERS below), never a bit of arp_pair.kind and not a variant of the reference enum: it stays
+ * outside the enum, ARP_N_INTERACTIONS stays 19, and arp_interaction_name returns "WaterBridge" for it. */
+#define ARP_WaterBridge 19
 
 /* ---- per-atom attribute word (arp_atoms.attr) ---- */
 #define ARP_ATTR_ELEM_MASK   0x0000000Fu /* element class: index into arp_params.cov_radius / vdw_radius            */
@@ -570,11 +573,42 @@ arp_status arp_contact_frequencies_ex(arp_context *ctx, arp_structure *topology,
  * min_distance, max_distance, in that order.
  * The bytes do not depend on the pass size (arp_debug_set "freq_chunk_atoms"), the frame bits of the device keys ("freq_frame_bits"), the first
  * buffer capacity ("freq_cap_items") or the order in which the device produced pairs or ran atomics: two calls give identical bytes.
- * flags accepts ARP_FREQ_RINGS only; any other bit is ARP_ERR_BAD_INPUT.  Errors and checks are arp_contact_frequencies_ex's, with the same
- * statuses and messages, before the device is touched; ctx == NULL runs only them (ARP_OK, *out = NULL).  No new size limit: a huge topology
- * only gets smaller passes. */
+ * flags accepts ARP_FREQ_RINGS and ARP_FREQ_WATERS (below); any other bit is ARP_ERR_BAD_INPUT.  Errors and checks are arp_contact_frequencies_ex's,
+ * with the same statuses and messages, before the device is touched; ctx == NULL runs only them (ARP_OK, *out = NULL).  No new size limit: a huge
+ * topology only gets smaller passes. */
 arp_status arp_residue_contact_frequencies(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const char *groups, double vdw_comp,
                                            double dist_cutoff, uint32_t flags, arp_table **out);
+
+/* ---- water bridges: water-mediated contacts per frame and across frames -- DESIGN.md section 3.19 ----
+ * Topology, N, F frames, xyz and groups exactly as arp_contact_frequencies_ex defines them.  The topology is classified once per call:
+ *   water atom   residue name HOH and not ARP_ATTR_H
+ *   polar atom   attr & (ARP_ATTR_DONOR | ARP_ATTR_ACCEPTOR) non-zero and not ARP_ATTR_H.  No water atom is polar (the attribute tables give a water
+ *                oxygen neither class; an input that breaks this is ARP_ERR_BAD_INPUT).  Hydrogens play no part: the rule is geometric on heavy
+ *                atoms, like PolarContact.
+ * In frame f:
+ *   leg (w, p)        holds iff d2 = dx*dx + dy*dy + dz*dz <= 12.25, evaluated in f64 in that order, inclusive (12.25 = 3.5^2, the PolarContact
+ *                     distance, exactly representable)
+ *   bridge (p, w, q)  holds iff p != q are polar, both legs hold, attr[p] & ARP_ATTR_LIGAND, attr[q] & ARP_ATTR_RECEPTOR, and the residue rule of
+ *                     the contact table in its symmetric form accepts (residue of p, residue of q): on one chain ord(q) >= ord(p) + 2, and two
+ *                     chains that are both in the ligand and in the receptor set are listed once, by chain order.  One orientation per residue pair.
+ * The water's own chain and groups play no part (a water filed under a third chain still mediates), and a bridge depends on neither vdw_comp nor
+ * dist_cutoff: the bridged atoms may be up to 7 A apart.
+ * ARP_FREQ_WATERS on arp_residue_contact_frequencies, and on arp_contact_timelines at level 1, adds one item per bridge:
+ *   (A = res_id[p], B = res_id[q], code ARP_WaterBridge, frame f, dist = (float)sqrt(max(d2p, d2q)), the longer leg)
+ * so the closest approach of a frame is its tightest bridge, and a row's "min_distance" <= T says the pair is bridged at leg length T in some frame.
+ * The rows with any other code are byte for byte the table without the flag; without the flag nothing changes.  ARP_FREQ_RINGS may be combined.
+ * At level 0 (arp_contact_frequencies_ex never accepts the bit; arp_contact_timelines with level 0) the flag is ARP_ERR_BAD_INPUT.  The similarity,
+ * autocorrelation and cluster calls reject the bit as unknown: arp_bit_gram, arp_bit_autocorr and arp_bit_cluster on the timeline's bitmap serve meanwhile.
+ * Capacity: a water with more than 32 polar atoms within 3.5 A in any frame fails the whole call with ARP_ERR_CAPACITY and a message saying so,
+ * never a shorter table (real structures have 4 to 8).  The sweep is brute force, waters x polar atoms per frame. */
+#define ARP_FREQ_WATERS 0x100u
+/* The bridges themselves, one row per (frame, p, q, w), ordered by those four (topology atom indices).  Same frame convention and checks as the
+ * frequency calls; ctx == NULL runs only the checks (ARP_OK, *out = NULL).  No pair pass runs.  Columns (arp_table_column; the Arrow batch has them in
+ * this order): "frame" u32; "from_chain" "from_resn" "from_resi" "from_insertion" "from_altloc" "from_atomn" "from_atomi" (atom p) and the same seven
+ * "to_*" (atom q); "water_chain" "water_resi" "water_insertion" "water_altloc" "water_atomi"; "from_distance" "to_distance" f32 (the legs) and
+ * "distance" f32 (the longer leg).  "from_atom" / "water_atom" / "to_atom" i32 (topology indices) are served by arp_table_column only.  Grouping the
+ * rows by (res_id[p], res_id[q]) gives the ARP_WaterBridge rows of arp_residue_contact_frequencies exactly.  More than 2^31 rows: ARP_ERR_CAPACITY. */
+arp_status arp_water_bridges(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const char *groups, arp_table **out);
 
 /* ---- contact timelines over the frames of an ensemble: which frames, how many events, how long -- DESIGN.md section 3.13 ----
  * Topology, n_frames, xyz, groups, vdw_comp and dist_cutoff exactly as arp_contact_frequencies_ex (level 0) or arp_residue_contact_frequencies
@@ -591,8 +625,9 @@ arp_status arp_residue_contact_frequencies(arp_context *ctx, arp_structure *topo
  * high bits of a row's last word are zero.  The popcount of a row equals the row's "n_frames"; should it ever not, the call fails with ARP_ERR_HIP and
  * an "internal error" message instead of returning a table.
  * arp_table_export_arrow appends the five columns behind the frequency columns of the level; the bitmap is not part of the Arrow batch.
- * flags: ARP_FREQ_RINGS (the ring rows, as in the frequency calls) and ARP_TIMELINE_NO_BITMAP (the statistics are computed, the bitmap is not copied to the
- * host: arp_table_timeline returns NULL); any other bit, or a level outside {0, 1}, is ARP_ERR_BAD_INPUT.  Every check, status and message of the frequency
+ * flags: ARP_FREQ_RINGS (the ring rows, as in the frequency calls), ARP_FREQ_WATERS (level 1 only: the water-bridge rows; at level 0 it is
+ * ARP_ERR_BAD_INPUT with a message that names level 1 and arp_water_bridges) and ARP_TIMELINE_NO_BITMAP (the statistics are computed, the bitmap is not copied
+ * to the host: arp_table_timeline returns NULL); any other bit, or a level outside {0, 1}, is ARP_ERR_BAD_INPUT.  Every check, status and message of the frequency
  * calls runs before the device is touched; ctx == NULL runs only the checks (ARP_OK, *out = NULL).
  * Device memory: the frequency call's, plus rows x W x 4 bytes for the bitmap.  A bitmap above 2^31 bytes (arp_debug_set "timeline_cap_bytes") is
  * ARP_ERR_CAPACITY, with a message that names rows, frames and bytes.  The bytes do not depend on the pass size or on the order in which the device
