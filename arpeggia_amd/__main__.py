@@ -14,6 +14,9 @@ it writes `contact-frequency`'s table and, with --matrix FILE.npy, the matrix be
 it writes `contact-frequency`'s table with one more column, half_life, and, with --matrix FILE.npy, the per-row counts, with --curves FILE.csv the curves.
 `contact-clusters` (no counterpart either) takes the flags of `contact-timeline` without --bitmap, plus --min-similarity X (required) and --max-clusters N: it
 writes `contact-frequency`'s table and, with --assignments FILE.csv, one line per model, with --cluster-counts FILE.npy the per-row counts inside each cluster.
+`rmsd`, `rmsd-matrix` and `rmsd-clusters` (no counterpart either) superpose the models on --atoms ca|backbone|heavy|all of the chains -c: `rmsd` writes frame, rmsd
+against --reference K; `rmsd-matrix` the matrix to --matrix FILE.npy; `rmsd-clusters` the gromos clusters at --cutoff X (required) with the --max-clusters and
+--assignments of `contact-clusters`.
 `sasa-ensemble` and `sap-ensemble` (no counterpart either) take the flags and defaults of `sasa` / `sap` without --model: statistics over the models.
 `dsasa --level atom|residue` writes the interface row by row (default `total`: the reference's scalar); `dsasa-ensemble` takes the flags of
 `sasa-ensemble` and -g: dSASA per model and the per-atom statistics of the buried surface.
@@ -137,6 +140,25 @@ def build_parser() -> argparse.ArgumentParser:
     cl.add_argument("--assignments", default=None, type=Path, metavar="FILE.csv",
                     help="Write one line per model: frame, cluster, is_centre, similarity_to_centre, n_neighbours, size")
     cl.add_argument("--cluster-counts", default=None, type=Path, metavar="FILE.npy", help="Write in how many models of each cluster a row's contact exists: uint32 [rows, clusters]")
+    for name, hlp in (("rmsd", "how far each model is from a reference model after optimal superposition: frame, rmsd"),
+                      ("rmsd-matrix", "the rmsd between every two models after optimal superposition"),
+                      ("rmsd-clusters", "which models are the same conformation (gromos clusters on rmsd <= cutoff), and each cluster's centre")):
+        rm = sub.add_parser(name, help=hlp)
+        rm.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file whose models are the frames")
+        rm.add_argument("--atoms", default="ca", choices=("ca", "backbone", "heavy", "all"), help="Atoms to superpose on (residue HOH is never among them)")
+        rm.add_argument("-c", "--chains", default="", help="Comma-separated chain IDs to include (empty: all)")
+        rm.add_argument("--ignore-zero-occupancy", action="store_true", help="Ignore atoms with zero occupancy")
+        if name == "rmsd-matrix":
+            rm.add_argument("--matrix", required=True, type=Path, metavar="FILE.npy", help="Write the matrix: float32 [models, models]")
+            continue
+        rm.add_argument("-o", "--output", required=True, type=Path, help="Output directory")
+        rm.add_argument("-f", "--filename", default=name.replace("-", "_"), help="Name of the output file (.csv)")
+        if name == "rmsd":
+            rm.add_argument("--reference", default=0, type=int, metavar="K", help="The reference model (0: the first)")
+        else:
+            rm.add_argument("--cutoff", required=True, type=float, metavar="X", help="Two models are neighbours when their rmsd is at most X Angstroms")
+            rm.add_argument("--max-clusters", default=None, type=int, metavar="N", help="Stop after N clusters; the models left over stay unassigned (default: no limit)")
+            rm.add_argument("--assignments", default=None, type=Path, metavar="FILE.csv", help="Write one line per model: frame, cluster, is_centre, rmsd_to_centre, n_neighbours")
     common = dict(model=("-m", "--model", 0, int, "Model number to analyze (0: the first model)"),
                   probe=("-r", "--probe-radius", 1.4, float, "Probe radius in Angstroms"),
                   points=("-n", "--num-points", 100, int, "Number of points for surface calculation"),
@@ -566,9 +588,60 @@ def run_contact_clusters(args) -> int:
     return 0
 
 
+def run_rmsd(args) -> int:
+    import numpy as np
+
+    import arpeggia_amd as aa
+
+    if not args.input.exists():
+        log.error("Failed to retrieve input file: %s", args.input)
+        return 1
+    path = str(args.input.resolve())
+    try:
+        if args.command == "rmsd":
+            values = aa.rmsd(path, args.reference, args.atoms, args.chains, args.ignore_zero_occupancy)
+        elif args.command == "rmsd-matrix":
+            values = aa.rmsd_matrix(path, args.atoms, args.chains, args.ignore_zero_occupancy)
+        else:
+            cols = aa.rmsd_clusters(path, args.atoms, args.chains, args.ignore_zero_occupancy, cutoff=args.cutoff, max_clusters=args.max_clusters)
+    except (aa.ArpeggiaError, ValueError) as e:
+        log.error("RMSD failed: %s", e)
+        return 1
+    if args.command == "rmsd-matrix":
+        args.matrix.parent.mkdir(parents=True, exist_ok=True)
+        with open(args.matrix, "wb") as f:  # (np.save on a name would append .npy to any other suffix)
+            np.save(f, values)
+        log.info("RMSD matrix of %d models saved to %s", len(values), args.matrix)
+        return 0
+    args.output.mkdir(parents=True, exist_ok=True)
+    out = (args.output / args.filename).with_suffix(".csv")
+    with open(out, "w") as f:
+        if args.command == "rmsd":
+            f.write("frame,rmsd\n")
+            for k, v in enumerate(values):
+                f.write(f"{k},{float(v)!r}\n")
+        else:
+            f.write("cluster,centre,size\n")
+            for k in range(cols["n_clusters"]):
+                f.write(f"{k},{int(cols['centre'][k])},{int(cols['cluster_size'][k])}\n")
+    if args.command == "rmsd-clusters" and args.assignments is not None:
+        args.assignments.parent.mkdir(parents=True, exist_ok=True)
+        centres = set(int(c) for c in cols["centre"])
+        with open(args.assignments, "w") as f:
+            f.write("frame,cluster,is_centre,rmsd_to_centre,n_neighbours\n")
+            for k in range(len(cols["cluster"])):
+                left = int(cols["cluster"][k]) == 0xFFFFFFFF
+                f.write(",".join([str(k), "" if left else str(int(cols["cluster"][k])), "1" if k in centres else "0",
+                                  "" if left else repr(float(cols["rmsd_to_centre"][k])), str(int(cols["n_neighbours"][k]))]) + "\n")
+    log.info("Results saved to %s", out)
+    return 0
+
+
 def main(argv=None) -> int:
     logging.basicConfig(level=logging.INFO, format="%(levelname)s %(message)s", stream=sys.stderr)
     args = build_parser().parse_args(argv)
+    if args.command in ("rmsd", "rmsd-matrix", "rmsd-clusters"):
+        return run_rmsd(args)
     if args.command == "sc":
         return run_sc(args)
     if args.command == "sc-ensemble":

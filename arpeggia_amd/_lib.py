@@ -235,6 +235,10 @@ def _load():
         "arp_table_clusters": (C.c_void_p, [vp, C.POINTER(C.c_uint64), _u32p, _u32p, C.POINTER(_fp)] + [C.POINTER(_u32p)] * 5),
         "arp_bit_cluster_host": (C.c_int32, [C.c_uint64, C.c_uint64, _u32p, C.c_uint32, C.c_float, C.c_uint32, _u32p, _fp] + [_u32p] * 6),
         "arp_bit_cluster": (C.c_int32, [vp, C.c_uint64, C.c_uint64, _u32p, C.c_uint32, C.c_float, C.c_uint32, _u32p, _fp] + [_u32p] * 6),
+        "arp_rmsd_host": (C.c_int32, [C.c_uint64, C.c_uint64, _dp, _fp]),
+        "arp_rmsd_matrix": (C.c_int32, [vp, vp, C.c_uint64, _dp, _u32p, C.c_uint64, _fp]),
+        "arp_rmsd_reference": (C.c_int32, [vp, vp, C.c_uint64, _dp, _u32p, C.c_uint64, _dp, C.c_uint64, _fp]),
+        "arp_rmsd_clusters": (C.c_int32, [vp, vp, C.c_uint64, _dp, _u32p, C.c_uint64, C.c_float, C.c_uint32, _u32p, _fp] + [_u32p] * 4),
         "arp_sasa_radius": (C.c_int32, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, _fp]),
         "arp_max_asa": (C.c_float, [C.c_char_p]),
         "arp_residue_is_polar": (C.c_int32, [C.c_char_p]),

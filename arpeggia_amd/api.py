@@ -426,6 +426,22 @@ class Context:
         owner = _TableOwner(_cluster_table(self, structure, frames, groups, vdw_comp, dist_cutoff, rings, level, min_similarity, max_clusters, counts))
         return _cluster_columns(owner, rings, level)
 
+    def rmsd(self, structure: Structure, frames=None, reference=0, atoms="ca", chains: str = "") -> np.ndarray:
+        """arp_rmsd_reference: <f4 [F], the rmsd of every frame to `reference` after optimal superposition (proper rotations only) on the atoms of
+        rmsd_select(structure, atoms, chains).  reference: a frame index (that entry is 0.0, the others are the bytes of rmsd_matrix's row) or an [N, 3]
+        array of the topology's atoms.  frames: [F, N, 3] f64; None: the structure's models."""
+        return _rmsd_reference(self, structure, frames, reference, atoms, chains)
+
+    def rmsd_matrix(self, structure: Structure, frames=None, atoms="ca", chains: str = "") -> np.ndarray:
+        """arp_rmsd_matrix: <f4 [F, F], the rmsd between every two frames; exactly symmetric, the diagonal exactly 0."""
+        return _rmsd_matrix(self, structure, frames, atoms, chains)
+
+    def rmsd_clusters(self, structure: Structure, frames=None, atoms="ca", chains: str = "", *, cutoff: float, max_clusters: int | None = None) -> dict:
+        """arp_rmsd_clusters as a dict: the gromos clusters of the frames on the neighbour relation rmsd <= cutoff (f32, inclusive) -- per frame `cluster`
+        <u4 (0xFFFFFFFF: left over by max_clusters), `rmsd_to_centre` <f4 (the matrix entry's bytes; 0.0 for a centre, NaN for a left-over frame) and
+        `n_neighbours` <u4 (itself included); per cluster `centre` and `cluster_size` <u4; `n_clusters`.  The matrix never exists."""
+        return _rmsd_clusters(self, structure, frames, atoms, chains, cutoff, max_clusters)
+
     def sc_ensemble(self, structure: Structure, frames=None, groups: str = "/") -> dict:
         """arp_structure_sc_ensemble as a dict: shape complementarity of every frame of an ensemble (the selection and radii of get_sc on model 0).
         frames: [F, N, 3] f64 coordinates of the N atoms of model 0; None: the structure's models.  Keys: atoms (u32 structure indices of the m
@@ -1250,6 +1266,160 @@ def contact_clusters(input_file: str, groups: str = "/", vdw_comp: float = 0.1, 
     _check_level(level)
     return get_contact_clusters(Structure.load(input_file, ignore_zero_occupancy), None, groups, vdw_comp, dist_cutoff, rings=rings, level=level,
                                 min_similarity=min_similarity, max_clusters=max_clusters, counts=counts)
+
+
+# ---- RMSD between frames after optimal superposition (arp_rmsd_matrix / arp_rmsd_reference / arp_rmsd_clusters) ----
+RMSD_ATOMS = ("ca", "backbone", "heavy", "all")
+
+
+def rmsd_select(structure: Structure, atoms="ca", chains: str = "") -> np.ndarray:
+    """The <u4 topology atom indices (model 0, strictly increasing) an rmsd call superposes on.  atoms: "ca" (atom name CA), "backbone" (N, CA, C, O),
+    "heavy" (not hydrogen) or "all" -- residue HOH is left out of every keyword, every altloc that matches is kept -- or an explicit integer array, which
+    is passed through sorted (a duplicate is an error).  chains: a comma list of chain ids ("" = every chain) that the keywords are restricted to."""
+    n = _topology_atoms(structure)
+    if not isinstance(atoms, str):
+        a = np.asarray(atoms)
+        if a.ndim != 1 or a.dtype.kind not in "iu":
+            raise ValueError(f"atoms must be one of {RMSD_ATOMS} or a 1-D integer array, got {atoms!r}")
+        if len(a) and (int(a.min()) < 0 or int(a.max()) >= 1 << 32):
+            raise ValueError("atoms: an index is negative or does not fit 32 bits")
+        a = np.sort(a.astype("<u4"))
+        if len(a) > 1 and (np.diff(a.astype(np.int64)) == 0).any():
+            raise ValueError("atoms: duplicate indices")
+        return a
+    if atoms not in RMSD_ATOMS:
+        raise ValueError(f"atoms must be one of {RMSD_ATOMS} or an integer array, got {atoms!r}")
+    name, resn, elem, chain = (structure.strings(k)[:n] for k in ("atomn", "resn", "element", "chain"))
+    keep = resn != b"HOH"
+    if atoms == "ca":
+        keep &= name == b"CA"
+    elif atoms == "backbone":
+        keep &= np.isin(name, [b"N", b"CA", b"C", b"O"])
+    elif atoms == "heavy":
+        keep &= ~np.isin(elem, [b"H", b"D"])
+    wanted = [c.strip().encode() for c in chains.split(",") if c.strip()]
+    if wanted:
+        keep &= np.isin(chain, wanted)
+    return np.flatnonzero(keep).astype("<u4")
+
+
+def _rmsd_args(structure: Structure, frames, atoms, chains: str, what: str):
+    """(the leading arguments of the arp_rmsd_* calls behind ctx, F or None when the models are the frames, keep-alive arrays)."""
+    sel = rmsd_select(structure, atoms, chains)
+    n_frames, ptr, keep = _frames_arg(structure, frames, what)
+    sel_keep = sel if len(sel) else np.zeros(1, "<u4")
+    return (structure._h, int(n_frames), ptr, sel_keep.ctypes.data_as(C.POINTER(C.c_uint32)), len(sel)), (keep, sel_keep)
+
+
+def _rmsd_frames(structure: Structure, frames) -> int:
+    n = _topology_atoms(structure)
+    return int(np.asarray(frames).shape[0]) if frames is not None else (structure.n_atoms // n if n else 0)
+
+
+def _rmsd_matrix(ctx: "Context | None", structure: Structure, frames, atoms, chains: str):
+    """arp_rmsd_matrix.  ctx None: the inputs are only checked (raises their error, else returns None)."""
+    args, keep = _rmsd_args(structure, frames, atoms, chains, "rmsd matrix")
+    if ctx is None:
+        _check(lib.arp_rmsd_matrix(None, *args, None))
+        return None
+    F = _rmsd_frames(structure, frames)
+    out = np.zeros((F, F), "<f4")
+    _check(lib.arp_rmsd_matrix(ctx._h, *args, (out if out.size else np.zeros(1, "<f4")).ctypes.data_as(C.POINTER(C.c_float))))
+    return out
+
+
+def _rmsd_reference(ctx: "Context | None", structure: Structure, frames, reference, atoms, chains: str):
+    """arp_rmsd_reference.  ctx None: the inputs are only checked."""
+    args, keep = _rmsd_args(structure, frames, atoms, chains, "rmsd")
+    ref_keep, ref_ptr, ref_frame = None, None, 0
+    if isinstance(reference, (int, np.integer)):
+        if int(reference) < 0:
+            raise ValueError(f"reference must be a frame index or an [N, 3] array, got {reference!r}")
+        ref_frame = int(reference)
+    else:
+        n = _topology_atoms(structure)
+        ref_keep = np.ascontiguousarray(reference, dtype="<f8")
+        if ref_keep.shape != (n, 3):
+            raise ArpeggiaError(_lib.ARP_ERR_BAD_INPUT, f"rmsd: reference must be a frame index or have shape [{n}, 3] (the topology's atoms), got {list(ref_keep.shape)}")
+        ref_ptr = (ref_keep if ref_keep.size else np.zeros(1, "<f8")).ctypes.data_as(C.POINTER(C.c_double))
+    if ctx is None:
+        _check(lib.arp_rmsd_reference(None, *args, ref_ptr, ref_frame, None))
+        return None
+    out = np.zeros(_rmsd_frames(structure, frames), "<f4")
+    _check(lib.arp_rmsd_reference(ctx._h, *args, ref_ptr, ref_frame, (out if out.size else np.zeros(1, "<f4")).ctypes.data_as(C.POINTER(C.c_float))))
+    return out
+
+
+def _rmsd_clusters(ctx: "Context | None", structure: Structure, frames, atoms, chains: str, cutoff: float, max_clusters):
+    """arp_rmsd_clusters.  ctx None: the inputs are only checked."""
+    args, keep = _rmsd_args(structure, frames, atoms, chains, "rmsd clusters")
+    cap_arg = _max_clusters_arg(max_clusters)
+    if ctx is None:
+        _check(lib.arp_rmsd_clusters(None, *args, C.c_float(cutoff), cap_arg, *([None] * 6)))
+        return None
+    F = _rmsd_frames(structure, frames)
+    cap = min(F, cap_arg)
+    out = {"cluster": np.zeros(F, "<u4"), "rmsd_to_centre": np.zeros(F, "<f4"), "n_neighbours": np.zeros(F, "<u4"), "centre": np.zeros(cap, "<u4"),
+           "cluster_size": np.zeros(cap, "<u4")}
+    n = np.zeros(1, "<u4")
+    u32p = C.POINTER(C.c_uint32)
+    ptr = lambda a, t=u32p: (a if a.size else np.zeros(1, a.dtype)).ctypes.data_as(t)
+    _check(lib.arp_rmsd_clusters(ctx._h, *args, C.c_float(cutoff), cap_arg, ptr(out["cluster"]), ptr(out["rmsd_to_centre"], C.POINTER(C.c_float)), ptr(out["n_neighbours"]),
+                                 ptr(out["centre"]), ptr(out["cluster_size"]), ptr(n)))
+    K = int(n[0])
+    out["centre"] = out["centre"][:K].copy()
+    out["cluster_size"] = out["cluster_size"][:K].copy()
+    out["n_clusters"] = K
+    return out
+
+
+def rmsd_host(xyz_sel) -> np.ndarray:
+    """arp_rmsd_host: the <f4 [F, F] rmsd matrix of [F, n, 3] f64 coordinates (the selected atoms only) by the definition in plain sequential C++ on the
+    CPU -- the yardstick of the device calls."""
+    x = np.ascontiguousarray(xyz_sel, dtype="<f8")
+    if x.ndim != 3 or x.shape[2] != 3:
+        raise ValueError(f"xyz_sel must have shape [F, n, 3], got {list(x.shape)}")
+    F, n = x.shape[:2]
+    out = np.zeros((F, F), "<f4")
+    _check(lib.arp_rmsd_host(F, n, (x if x.size else np.zeros(1, "<f8")).ctypes.data_as(C.POINTER(C.c_double)), (out if out.size else np.zeros(1, "<f4")).ctypes.data_as(C.POINTER(C.c_float))))
+    return out
+
+
+def get_rmsd(structure: Structure, frames=None, reference=0, atoms="ca", chains: str = "", device: int = 0) -> np.ndarray:
+    """How far every frame of an ensemble is from a reference: <f4 [F], the rmsd after optimal superposition (proper rotations only: a mirror image does
+    not superpose) on the atoms of rmsd_select(structure, atoms, chains).  reference: a frame index (default: the first frame) or an [N, 3] array of the
+    topology's atoms.  frames: [F, N, 3] f64 coordinates of the atoms of model 0; None: the structure's models."""
+    ctx = _with_context(device, lambda: _rmsd_reference(None, structure, frames, reference, atoms, chains))
+    return ctx.rmsd(structure, frames, reference, atoms, chains)
+
+
+def get_rmsd_matrix(structure: Structure, frames=None, atoms="ca", chains: str = "", device: int = 0) -> np.ndarray:
+    """The rmsd between every two frames of an ensemble, <f4 [F, F]: exactly symmetric, the diagonal exactly 0.  Arguments as get_rmsd."""
+    ctx = _with_context(device, lambda: _rmsd_matrix(None, structure, frames, atoms, chains))
+    return ctx.rmsd_matrix(structure, frames, atoms, chains)
+
+
+def get_rmsd_clusters(structure: Structure, frames=None, atoms="ca", chains: str = "", device: int = 0, *, cutoff: float, max_clusters: int | None = None) -> dict:
+    """Which frames of an ensemble are the same conformation: the gromos clusters (Daura et al. 1999) on the neighbour relation rmsd <= cutoff, the loop
+    of get_contact_clusters on coordinates.  Keys: cluster, rmsd_to_centre, n_neighbours [F]; centre, cluster_size [n_clusters]; n_clusters.  The F x F
+    matrix never exists: the call also takes the ensembles get_rmsd_matrix refuses.  cutoff has no default.  max_clusters None: no limit."""
+    ctx = _with_context(device, lambda: _rmsd_clusters(None, structure, frames, atoms, chains, cutoff, max_clusters))
+    return ctx.rmsd_clusters(structure, frames, atoms, chains, cutoff=cutoff, max_clusters=max_clusters)
+
+
+def rmsd(input_file: str, reference=0, atoms="ca", chains: str = "", ignore_zero_occupancy: bool = False) -> np.ndarray:
+    """RMSD of every model of a multi-model file to a reference (the models are the frames): see get_rmsd."""
+    return get_rmsd(Structure.load(input_file, ignore_zero_occupancy), None, reference, atoms, chains)
+
+
+def rmsd_matrix(input_file: str, atoms="ca", chains: str = "", ignore_zero_occupancy: bool = False) -> np.ndarray:
+    """RMSD between the models of a multi-model file: see get_rmsd_matrix."""
+    return get_rmsd_matrix(Structure.load(input_file, ignore_zero_occupancy), None, atoms, chains)
+
+
+def rmsd_clusters(input_file: str, atoms="ca", chains: str = "", ignore_zero_occupancy: bool = False, *, cutoff: float, max_clusters: int | None = None) -> dict:
+    """RMSD clusters of the models of a multi-model file: see get_rmsd_clusters."""
+    return get_rmsd_clusters(Structure.load(input_file, ignore_zero_occupancy), None, atoms, chains, cutoff=cutoff, max_clusters=max_clusters)
 
 
 def _contact_clusters_arrow(input_file: str, groups: str, vdw_comp: float, dist_cutoff: float, ignore_zero_occupancy: bool, rings: bool, level: str, min_similarity: float,

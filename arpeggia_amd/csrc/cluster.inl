@@ -145,6 +145,9 @@ __device__ inline uint32_t wave_sum(uint32_t v) {
 //   a frame that stays alive gets n[f] = popcount(adj[f] AND alive) -- in round 0, with every frame alive, popcount(adj[f]) = n_neighbours[f]: a set bit past
 //   M would be a phantom neighbour there -- and offers (n << 32 | ~f) to best[round].
 // round == max_clusters: the last cluster is applied, nothing is counted, best[round] stays 0.
+// kTanimoto false (rmsd.inl: the neighbour bits come from coordinates, there are no bit-rows): a member gets its cluster only, A, K and sizes are not read and
+// sim is left to the caller's own kernel.
+template <bool kTanimoto>
 __global__ __launch_bounds__(256) void k_cluster_round(uint32_t round, uint32_t max_clusters, const uint32_t *adj, uint32_t M, uint64_t KA, const uint32_t *A, uint64_t K,
                                                        const uint32_t *sizes, unsigned long long *best, const uint32_t *alive_prev, uint32_t *alive_next, uint32_t *cluster,
                                                        uint32_t *sim, uint32_t *n_neighbours) {
@@ -170,7 +173,9 @@ __global__ __launch_bounds__(256) void k_cluster_round(uint32_t round, uint32_t 
         const uint32_t bit = 1u << (f & 31u);
         const bool was = (alive_prev[f >> 5] & bit) != 0u;
         const bool member = was && adj_c && (adj_c[f >> 5] & bit) != 0u;
-        if (member) {
+        if (member && !kTanimoto) {
+            if (lane == 0u) cluster[f] = round - 1u;
+        } else if (member) {
             const uint32_t *a = A + (size_t)f * K, *b = A + (size_t)c * K;
             uint32_t inter = 0;
             for (uint64_t w = lane; w < K; w += 64u) inter += (uint32_t)__popc(a[w] & b[w]);
@@ -270,33 +275,38 @@ struct ClusterDev {
     std::vector<unsigned long long> best;  // the host's copy, n_clusters entries
 };
 
-// sizes, adjacency, rounds and tail for the bit-rows A[M][K] on the device (M > 0, K > 0).  The host looks at best[] once per batch of launches; the
-// launches of a batch that lie behind the last round are no-ops.
-arp_status cluster_launch(hipStream_t st, const uint32_t *A, uint64_t M, uint64_t K, float min_similarity, uint32_t max_clusters, StreamLapTimer &lap, ClusterDev *dv) {
+// The buffers of the rounds inside dv->block: the neighbour bits, the two alive sets and best[] (zeroed), with every frame unassigned and alive[1] full
+struct ClusterBufs { uint32_t *adj = nullptr, *alive[2] = {nullptr, nullptr}; unsigned long long *best = nullptr; uint64_t KA = 0, last = 0; };
+arp_status cluster_alloc(hipStream_t st, uint64_t M, uint32_t max_clusters, ClusterDev *dv, ClusterBufs *b) {
     const uint64_t KA = (M + 31u) / 32u, last = std::min<uint64_t>(M, max_clusters);  // launch `last` applies the last cluster there can be
     char *block = nullptr;
     HIP_TRY(hipMalloc((void **)&block, seg_align(M * KA * 4u) + 4 * seg_align(M * 4u) + 2 * seg_align(KA * 4u) + seg_align((last + 2u) * 8u) + 256));
     dv->block.reset(block);
     Bump bp{block};
-    uint32_t *adj = bp.take<uint32_t>(M * KA);
+    b->KA = KA; b->last = last;
+    b->adj = bp.take<uint32_t>(M * KA);
     dv->sizes = bp.take<uint32_t>(M); dv->cluster = bp.take<uint32_t>(M); dv->sim = bp.take<uint32_t>(M); dv->n_neighbours = bp.take<uint32_t>(M);
-    uint32_t *alive[2] = {bp.take<uint32_t>(KA), bp.take<uint32_t>(KA)};
-    unsigned long long *best = bp.take<unsigned long long>(last + 2u);
-    HIP_TRY(hipMemsetAsync(best, 0, (last + 2u) * 8u, st));
-    hipLaunchKernelGGL(k_cluster_init, dim3((uint32_t)((M + 255u) / 256u)), dim3(256), 0, st, (uint32_t)M, KA, dv->cluster, dv->sim, alive[1]);
+    b->alive[0] = bp.take<uint32_t>(KA); b->alive[1] = bp.take<uint32_t>(KA);
+    b->best = bp.take<unsigned long long>(last + 2u);
+    HIP_TRY(hipMemsetAsync(b->best, 0, (last + 2u) * 8u, st));
+    hipLaunchKernelGGL(k_cluster_init, dim3((uint32_t)((M + 255u) / 256u)), dim3(256), 0, st, (uint32_t)M, KA, dv->cluster, dv->sim, b->alive[1]);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_bit_sizes, dim3((uint32_t)((M + 3u) / 4u)), dim3(256), 0, st, A, (uint32_t)M, K, K, dv->sizes);
-    HIP_TRY(hipGetLastError());
-    const uint32_t T = (uint32_t)((M + kSimTile - 1u) / kSimTile);
-    hipLaunchKernelGGL(k_bit_adjacency, dim3((uint32_t)((uint64_t)T * (T + 1u) / 2u)), dim3(256), 0, st, A, (uint32_t)M, K, K, (const uint32_t *)dv->sizes, T, min_similarity, adj, KA);
-    HIP_TRY(hipGetLastError());
-    lap("adjacency");
+    return ARP_OK;
+}
+
+// Rounds and tail on the neighbour bits b.adj (M > 0).  The host looks at best[] once per batch of launches; the launches of a batch that lie behind the last
+// round are no-ops.  kTanimoto: k_cluster_round's mode (false: A, K and dv->sizes are not read).
+template <bool kTanimoto>
+arp_status cluster_rounds(hipStream_t st, const ClusterBufs &b, uint64_t M, const uint32_t *A, uint64_t K, uint32_t max_clusters, StreamLapTimer &lap, ClusterDev *dv) {
+    const uint64_t KA = b.KA, last = b.last;
+    uint32_t *const adj = b.adj, *const alive[2] = {b.alive[0], b.alive[1]};
+    unsigned long long *const best = b.best;
     dv->best.assign(last + 1u, 0ull);
     uint64_t next = 0, stop = last + 1u;  // stop: the first launch index whose best[] has a count <= 1
     for (uint64_t batch = kClusterBatch0; next <= last; batch = std::min<uint64_t>(batch * 2u, kClusterBatchMax)) {
         const uint64_t r0 = next, r1 = std::min(last + 1u, next + batch);
         for (uint64_t r = r0; r < r1; r++) {
-            hipLaunchKernelGGL(k_cluster_round, dim3((uint32_t)((M + kClusterRows - 1u) / kClusterRows)), dim3(256), 0, st, (uint32_t)r, max_clusters, (const uint32_t *)adj,
+            hipLaunchKernelGGL(k_cluster_round<kTanimoto>, dim3((uint32_t)((M + kClusterRows - 1u) / kClusterRows)), dim3(256), 0, st, (uint32_t)r, max_clusters, (const uint32_t *)adj,
                                (uint32_t)M, KA, A, K, (const uint32_t *)dv->sizes, best, (const uint32_t *)alive[(r + 1u) & 1u], alive[r & 1u], dv->cluster, dv->sim,
                                dv->n_neighbours);
             HIP_TRY(hipGetLastError());
@@ -320,6 +330,20 @@ arp_status cluster_launch(hipStream_t st, const uint32_t *A, uint64_t M, uint64_
     dv->best.resize(C);
     lap("rounds");
     return ARP_OK;
+}
+
+// sizes, adjacency, rounds and tail for the bit-rows A[M][K] on the device (M > 0, K > 0)
+arp_status cluster_launch(hipStream_t st, const uint32_t *A, uint64_t M, uint64_t K, float min_similarity, uint32_t max_clusters, StreamLapTimer &lap, ClusterDev *dv) {
+    ClusterBufs b;
+    arp_status s = cluster_alloc(st, M, max_clusters, dv, &b);
+    if (s != ARP_OK) return s;
+    hipLaunchKernelGGL(k_bit_sizes, dim3((uint32_t)((M + 3u) / 4u)), dim3(256), 0, st, A, (uint32_t)M, K, K, dv->sizes);
+    HIP_TRY(hipGetLastError());
+    const uint32_t T = (uint32_t)((M + kSimTile - 1u) / kSimTile);
+    hipLaunchKernelGGL(k_bit_adjacency, dim3((uint32_t)((uint64_t)T * (T + 1u) / 2u)), dim3(256), 0, st, A, (uint32_t)M, K, K, (const uint32_t *)dv->sizes, T, min_similarity, b.adj, b.KA);
+    HIP_TRY(hipGetLastError());
+    lap("adjacency");
+    return cluster_rounds<true>(st, b, M, A, K, max_clusters, lap, dv);
 }
 
 // cluster_counts[R][C] on the device, from the bitmap words[R][W] and the finished assignment (R > 0, C > 0)

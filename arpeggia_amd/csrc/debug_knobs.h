@@ -18,7 +18,9 @@ struct DebugKnobs {
     long long similarity_cap_bytes;  // > 0: the most bytes the matrix of arp_contact_similarity / arp_bit_gram may take (tests: the capacity error on tiny inputs); 0: 2^31 bytes
     long long autocorr_cap_bytes;  // > 0: the most bytes the device matrix of arp_contact_autocorrelation / arp_bit_autocorr may take (tests: the capacity error on tiny inputs); 0: 2^31 bytes
     long long cluster_cap_bytes;  // > 0: the most bytes the neighbour bits, and the counts, of arp_contact_clusters / arp_bit_cluster may take (tests: the capacity error on tiny inputs); 0: 2^31 bytes
-    long sc_ens_frames;     // > 0: frames per pass of arp_sc_ensemble (tests: pass edges at tiny shapes); 0: from the memory budget (sc_ens.inl launch_sc_ens)
+    long rmsd_chunk_atoms;  // > 0: atoms per upload pass of the arp_rmsd_* calls (whole frames, at least one; tests: several passes on tiny inputs); 0: automatic (freq.inl kFreqAutoAtoms)
+    long long rmsd_cap_bytes;  // > 0: the most bytes the matrix of arp_rmsd_matrix, the neighbour bits of arp_rmsd_clusters and the packed frames of either may take (tests: the capacity error on tiny inputs); 0: 2^31 bytes
+    long sc_ens_frames;    // > 0: frames per pass of arp_sc_ensemble (tests: pass edges at tiny shapes); 0: from the memory budget (sc_ens.inl launch_sc_ens)
     int scan_kernel;    // the cell scan (pairs.inl launch_grid): 0: chosen by input size; 1: the look-back scan k_scan_single on 256 blocks; 2: on 1 024 blocks (tests: small inputs reach it)
     int table_key_bits;  // > 0: stands for the 64 of the table plan's three width tests (table_plan.h plan_table; tests: small inputs reach the plans of wide keys); 0: 64
 };

@@ -707,6 +707,14 @@ extern "C" arp_status arp_debug_set(const char *key, int64_t value) {
         if (value < 0) { set_error("arp_debug_set: cluster_cap_bytes takes 0 (2^31 bytes) or a positive byte count"); return ARP_ERR_BAD_INPUT; }
         g_debug.cluster_cap_bytes = (long long)value;
     }
+    else if (k == "rmsd_chunk_atoms") {
+        if (value < 0) { set_error("arp_debug_set: rmsd_chunk_atoms takes 0 (automatic) or a positive atom count"); return ARP_ERR_BAD_INPUT; }
+        g_debug.rmsd_chunk_atoms = (long)value;
+    }
+    else if (k == "rmsd_cap_bytes") {
+        if (value < 0) { set_error("arp_debug_set: rmsd_cap_bytes takes 0 (2^31 bytes) or a positive byte count"); return ARP_ERR_BAD_INPUT; }
+        g_debug.rmsd_cap_bytes = (long long)value;
+    }
     else if (k == "index_bits") {
         if (value > (int64_t)kNarrowMaxBits) { set_error("arp_debug_set: index_bits takes 0 (automatic), 1 .. 20 (the index width of the narrow exact record) or a negative value (the wide record always)"); return ARP_ERR_BAD_INPUT; }
         g_debug.index_bits = (int)value;
@@ -723,7 +731,7 @@ extern "C" arp_status arp_debug_set(const char *key, int64_t value) {
         if (value < 0 || value > 2) { set_error("arp_debug_set: scan_kernel takes 0 (automatic), 1 (the look-back cell scan on 256 blocks) or 2 (on 1024 blocks)"); return ARP_ERR_BAD_INPUT; }
         g_debug.scan_kernel = (int)value;
     }
-    else { set_error("arp_debug_set: unknown key '%s' (timing, emit_kernel, defer_entries, strip_rows, index_bits, scan_kernel, table_host, freq_chunk_atoms, freq_cap_items, freq_frame_bits, ens_chunk_atoms, sc_ens_frames, timeline_cap_bytes, similarity_cap_bytes, autocorr_cap_bytes, cluster_cap_bytes, table_key_bits)", key); return ARP_ERR_BAD_INPUT; }
+    else { set_error("arp_debug_set: unknown key '%s' (timing, emit_kernel, defer_entries, strip_rows, index_bits, scan_kernel, table_host, freq_chunk_atoms, freq_cap_items, freq_frame_bits, ens_chunk_atoms, sc_ens_frames, timeline_cap_bytes, similarity_cap_bytes, autocorr_cap_bytes, cluster_cap_bytes, rmsd_chunk_atoms, rmsd_cap_bytes, table_key_bits)", key); return ARP_ERR_BAD_INPUT; }
     return ARP_OK;
 }
 extern "C" arp_status arp_debug_get(const char *key, int64_t *value) {

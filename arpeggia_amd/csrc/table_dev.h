@@ -172,6 +172,24 @@ arp_status device_clusters(arp_context *ctx, const FreqJob &job, float min_simil
 arp_status device_bit_cluster(arp_context *ctx, uint64_t rows, uint64_t n_bits, const uint32_t *words, bool by_rows, float min_similarity, uint32_t max_clusters, bool want_counts,
                               uint64_t cap_bytes, ClustersHost *out);
 
+// RMSD between frames (rmsd.inl, arp_rmsd_matrix / arp_rmsd_reference / arp_rmsd_clusters): n_frames x n_atoms x 3 f64 coordinates and
+// the n_sel selected atoms, strictly increasing.  kMatrix: out[F x F]; kReference: out[F] against frame ref_frame, or against ref_xyz[n_atoms x 3] when it is
+// given; kClusters: the gromos clusters on rmsd <= cutoff into ClustersHost (sim: the bits of the f32 rmsd to the centre; sizes and counts stay empty).  The
+// caller has checked the sizes against the capacity knob.
+struct RmsdJob {
+    enum Kind { kMatrix, kReference, kClusters } kind = kMatrix;
+    uint64_t n_atoms = 0, n_frames = 0, n_sel = 0;
+    const double *xyz = nullptr;
+    const uint32_t *sel = nullptr;
+    uint64_t chunk_atoms = 0;  // atoms per upload pass, 0 = automatic (arp_debug_set "rmsd_chunk_atoms")
+    const double *ref_xyz = nullptr;
+    uint64_t ref_frame = 0;
+    float cutoff = 0.0f;
+    uint32_t max_clusters = ARP_NONE;
+};
+constexpr uint64_t rmsd_n_pad(uint64_t n) { return (n + 3u) & ~3ull; }  // atoms of a packed frame: n rounded up to the K step of the f64 MFMA (rmsd.inl kRmsdStep)
+arp_status device_rmsd(arp_context *ctx, const RmsdJob &job, float *out, ClustersHost *clusters);
+
 // engine.cpp: the context's stream / device and grow-only scratch (device and pinned host)
 void *context_stream(arp_context *ctx);
 int context_device(arp_context *ctx);

@@ -1025,5 +1025,6 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
 #include "similarity.inl"
 #include "autocorr.inl"
 #include "cluster.inl"
+#include "rmsd.inl"
 
 }  // namespace arp

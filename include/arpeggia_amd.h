@@ -177,6 +177,10 @@ typedef struct arp_table arp_table;         /* the 20-column contact table (mod.
  *                      tests reach the limit on tiny inputs; 0 (default): 2^31 bytes
  *   "cluster_cap_bytes" N > 0: arp_contact_clusters and arp_bit_cluster refuse neighbour bits, or cluster counts, of more than N bytes (ARP_ERR_CAPACITY), so
  *                      that tests reach the limit on tiny inputs; 0 (default): 2^31 bytes
+ *   "rmsd_chunk_atoms" N > 0: the arp_rmsd_* calls upload their frames in passes of N atoms (whole frames, at least one per pass), so that tests can force
+ *                      several passes; 0 (default): about 2 x 10^6 atoms per pass.  The results do not depend on it
+ *   "rmsd_cap_bytes" N > 0: arp_rmsd_matrix refuses a matrix, arp_rmsd_clusters neighbour bits, and every arp_rmsd_* call packed coordinates of more than N
+ *                      bytes (ARP_ERR_CAPACITY), so that tests reach the limit on tiny inputs; 0 (default): 2^31 bytes
  *   "table_key_bits" N in 6 .. 64: N stands for the 64 bits of the key word when the contact table chooses its sort passes (one merged key, two or three
  *                      passes) and decides whether the one-launch path may run, so that small inputs reach the plans of wide keys; the passes themselves sort
  *                      on their real widths, and the table's bytes do not change.  0 (default): 64.  Anything else is ARP_ERR_BAD_INPUT (6 is the narrowest pass any structure can
@@ -778,6 +782,52 @@ arp_status arp_bit_cluster_host(uint64_t rows, uint64_t n_bits, const uint32_t *
 arp_status arp_bit_cluster(arp_context *ctx, uint64_t rows, uint64_t n_bits, const uint32_t *words, uint32_t flags, float min_similarity, uint32_t max_clusters,
                            uint32_t *cluster, float *similarity_to_centre, uint32_t *n_neighbours, uint32_t *sizes, uint32_t *centre, uint32_t *cluster_size,
                            uint32_t *n_clusters, uint32_t *cluster_counts);
+
+/* ---- RMSD between the frames of an ensemble after optimal superposition: how far each frame is from a reference, which frames are the same conformation --
+ * DESIGN.md section 3.20 ----
+ * Frames exactly as arp_contact_frequencies defines them: model 0 of `topology` is the topology, N atoms; xyz is n_frames x N x 3 f64 on the host, C order;
+ * xyz == NULL: the structure's models are the frames, with that call's one-for-one model check and its messages.
+ * Selection: sel[n_sel], u32 topology atom indices, strictly increasing (which also rules out duplicates); all atoms have weight 1; n = n_sel.
+ * Per frame f:  c_f = the f64 centroid of the selected atoms;  x_f,i = coordinate - c_f (centring happens before any product is formed);  G_f = sum_i |x_f,i|^2.
+ * Per pair (f, g):  S = sum_i x_f,i x_g,i^T, 3 x 3 (Sab: component a of f with component b of g), and K(S) is Horn's symmetric 4 x 4 matrix
+ *     |  Sxx + Syy + Szz    Syz - Szy          Szx - Sxz          Sxy - Syx        |
+ *     |  Syz - Szy          Sxx - Syy - Szz    Sxy + Syx          Szx + Sxz        |
+ *     |  Szx - Sxz          Sxy + Syx         -Sxx + Syy - Szz    Syz + Szy        |
+ *     |  Sxy - Syx          Szx + Sxz          Syz + Szy         -Sxx - Syy + Szz  |
+ *   lambda = its largest eigenvalue: the optimum over proper rotations only -- a mirror image does not superpose.  Then
+ *   msd(f, g) = max(0, (G_f + G_g - 2 lambda) / n);  rmsd(f, g) = (float)sqrt(msd), one rounding to f32, as the tables' distances are f32.
+ *   rmsd(f, f) is 0.0f by definition: written, never computed.  rmsd(f, g) and rmsd(g, f) are the same bits.  Two identical but distinct frames give a value
+ *   near 0, not necessarily 0.
+ *   neighbours  adj[f][g] <=> rmsd(f, g) <= cutoff, compared as f32 and inclusive: exactly what comparing the matrix with cutoff gives
+ *   clusters    the loop written out under arp_contact_clusters (gromos: Daura et al. 1999, who define it on this rmsd) with this adj: the largest alive
+ *               neighbour count wins, the smallest index among equals, the counts are retaken every round; max_clusters as there.
+ * Checks, all before the device is touched, ARP_ERR_BAD_INPUT: the frame checks of the frequency call with its statuses and messages; n_sel == 0; an index
+ * >= N; sel not strictly increasing; ref_frame >= F (without ref_xyz); a non-finite ref_xyz; a cutoff that is not finite or < 0; max_clusters == 0 (ARP_NONE:
+ * no limit).  ctx == NULL runs only the checks (ARP_OK).
+ * Device memory: the packed centred coordinates, F x 3 x n_pad x 8 bytes (n_pad: n rounded up to 4), stay resident for the call; above 2^31 bytes
+ * (arp_debug_set "rmsd_cap_bytes") the call is ARP_ERR_CAPACITY with a message that names F, n and the bytes.  The eigenvalue is found by cyclic Jacobi
+ * rotations, which lose no accuracy when the top eigenvalue is double (planar, collinear, mirror-image and n <= 3 selections).  A pair's products are summed in
+ * the order of the atoms wherever the pair is computed: two calls give identical bytes, whatever the pass size ("rmsd_chunk_atoms").  Synchronous.
+ *
+ * arp_rmsd_matrix: out[F x F], row-major, caller-owned.  A matrix above 2^31 bytes ("rmsd_cap_bytes") is ARP_ERR_CAPACITY. */
+arp_status arp_rmsd_matrix(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const uint32_t *sel, uint64_t n_sel, float *out);
+/* out[F] = rmsd(reference, f).  ref_xyz == NULL: the reference is frame ref_frame; out[ref_frame] is 0.0f and every other entry equals the matrix row bit
+ * for bit.  Otherwise ref_xyz is N x 3 f64 (the topology's atoms; the selection applies to it), ref_frame is ignored and every entry is computed: a reference
+ * equal to frame k gives the matrix row's bits except out[k], which is near 0. */
+arp_status arp_rmsd_reference(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const uint32_t *sel, uint64_t n_sel, const double *ref_xyz,
+                              uint64_t ref_frame, float *out);
+/* The clusters.  cluster[f] u32 (ARP_NONE for the frames left over when max_clusters ended the loop), rmsd_to_centre[f] f32 = the matrix entry (f, centre of
+ * its cluster) bit for bit (0.0f for a centre, the bits 0x7FC00000 for a left-over frame), n_neighbours[f] u32 = the degree in the full graph, f included: F
+ * entries each; centre[k] and cluster_size[k] u32 take min(F, max_clusters) entries, *n_clusters = C of them are written.  The matrix is never formed: the
+ * limit is the neighbour bits, F x ceil(F / 32) x 4 bytes against "rmsd_cap_bytes" (ARP_ERR_CAPACITY) -- 10^5 frames are legal here, where the matrix is
+ * not.  Should the cluster sizes not add up to the assigned frames the call fails with ARP_ERR_HIP and an "internal error" message. */
+arp_status arp_rmsd_clusters(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const uint32_t *sel, uint64_t n_sel, float cutoff,
+                             uint32_t max_clusters, uint32_t *cluster, float *rmsd_to_centre, uint32_t *n_neighbours, uint32_t *centre, uint32_t *cluster_size,
+                             uint32_t *n_clusters);
+/* The definition above in plain sequential C++, without a device: f64 throughout, the sums in the order of the atoms, cyclic Jacobi on K(S).  xyz_sel is
+ * n_frames x n x 3 f64 -- the selected atoms only --, out n_frames x n_frames.  n == 0 or a non-finite coordinate is ARP_ERR_BAD_INPUT, more than 46340
+ * frames ARP_ERR_CAPACITY.  The CPU yardstick of the device kernels: they agree with it within the rounding of the sums, not bit for bit. */
+arp_status arp_rmsd_host(uint64_t n_frames, uint64_t n, const double *xyz_sel, float *out);
 
 /* ---- SASA and SAP statistics over the frames of an ensemble (MD snapshots, NMR models, conformers of one topology) -- DESIGN.md section 3.8 ----
  * Topology, N, frames and xyz exactly as arp_contact_frequencies defines them: model 0 of `topology` is the topology, frame f is xyz[f]
