@@ -17,6 +17,9 @@ writes `contact-frequency`'s table and, with --assignments FILE.csv, one line pe
 `rmsd`, `rmsd-matrix` and `rmsd-clusters` (no counterpart either) superpose the models on --atoms ca|backbone|heavy|all of the chains -c: `rmsd` writes frame, rmsd
 against --reference K; `rmsd-matrix` the matrix to --matrix FILE.npy; `rmsd-clusters` the gromos clusters at --cutoff X (required) with the --max-clusters and
 --assignments of `contact-clusters`.
+`rmsf` (no counterpart either) superposes the models on --fit ca|backbone|heavy|all onto --reference mean (the iterated mean structure, --max-rounds N, --tol X)
+or model K, and writes per --atoms atom (default: the --fit atoms) or, with -l residue, per residue the mean position, rmsf and B-factor; --frames FILE.csv: each
+model's rmsd to the mean; --aligned FILE.npy: the superposed coordinates.
 `sasa-ensemble` and `sap-ensemble` (no counterpart either) take the flags and defaults of `sasa` / `sap` without --model: statistics over the models.
 `dsasa --level atom|residue` writes the interface row by row (default `total`: the reference's scalar); `dsasa-ensemble` takes the flags of
 `sasa-ensemble` and -g: dSASA per model and the per-atom statistics of the buried surface.
@@ -159,6 +162,21 @@ def build_parser() -> argparse.ArgumentParser:
             rm.add_argument("--cutoff", required=True, type=float, metavar="X", help="Two models are neighbours when their rmsd is at most X Angstroms")
             rm.add_argument("--max-clusters", default=None, type=int, metavar="N", help="Stop after N clusters; the models left over stay unassigned (default: no limit)")
             rm.add_argument("--assignments", default=None, type=Path, metavar="FILE.csv", help="Write one line per model: frame, cluster, is_centre, rmsd_to_centre, n_neighbours")
+    rf = sub.add_parser("rmsf", help="how much each atom moves across the models: superpose them on their mean structure (or on one model), average, and report the "
+                                     "fluctuation of every atom or residue about the average")
+    rf.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file whose models are the frames")
+    rf.add_argument("-o", "--output", required=True, type=Path, help="Output directory")
+    rf.add_argument("-f", "--filename", default="rmsf", help="Name of the output file (.csv)")
+    rf.add_argument("--fit", default="ca", choices=("ca", "backbone", "heavy", "all"), help="Atoms to superpose on (residue HOH is never among them)")
+    rf.add_argument("--atoms", default=None, choices=("ca", "backbone", "heavy", "all"), help="Atoms to measure (default: the atoms of --fit)")
+    rf.add_argument("-c", "--chains", default="", help="Comma-separated chain IDs to include (empty: all)")
+    rf.add_argument("--reference", default="mean", type=_rmsf_reference_arg, metavar="mean|K", help="Superpose on the iterated mean structure, or on model K (0: the first)")
+    rf.add_argument("--max-rounds", default=50, type=int, metavar="N", help="With --reference mean: at most N rounds of superposing and averaging")
+    rf.add_argument("--tol", default=1e-4, type=float, metavar="X", help="With --reference mean: stop when the mean moves by at most X Angstroms (rms over the fit atoms)")
+    rf.add_argument("-l", "--level", default="atom", choices=("atom", "residue"), help="Rows per measured atom, or per residue of the measured atoms")
+    rf.add_argument("--frames", default=None, type=Path, metavar="FILE.csv", help="Write one line per model: frame, rmsd (to the mean, over the --fit atoms)")
+    rf.add_argument("--aligned", default=None, type=Path, metavar="FILE.npy", help="Write the superposed coordinates of the measured atoms: float64 [models, atoms, 3]")
+    rf.add_argument("--ignore-zero-occupancy", action="store_true", help="Ignore atoms with zero occupancy")
     common = dict(model=("-m", "--model", 0, int, "Model number to analyze (0: the first model)"),
                   probe=("-r", "--probe-radius", 1.4, float, "Probe radius in Angstroms"),
                   points=("-n", "--num-points", 100, int, "Number of points for surface calculation"),
@@ -588,6 +606,65 @@ def run_contact_clusters(args) -> int:
     return 0
 
 
+def _rmsf_reference_arg(text: str):
+    """--reference of rmsf: the word mean, or a model index."""
+    if text == "mean":
+        return text
+    try:
+        k = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected 'mean' or a model index, got {text!r}")
+    if k < 0:
+        raise argparse.ArgumentTypeError(f"expected 'mean' or a model index, got {text!r}")
+    return k
+
+
+def run_rmsf(args) -> int:
+    import numpy as np
+
+    import arpeggia_amd as aa
+
+    if not args.input.exists():
+        log.error("Failed to retrieve input file: %s", args.input)
+        return 1
+    try:
+        structure = aa.Structure.load(str(args.input.resolve()), args.ignore_zero_occupancy)
+        res = aa.get_rmsf(structure, None, args.fit, args.atoms, args.chains, args.reference, args.max_rounds, args.tol, args.level, aligned=args.aligned is not None)
+    except (aa.ArpeggiaError, ValueError) as e:
+        log.error("RMSF failed: %s", e)
+        return 1
+    names = aa.RMSF_COLUMNS if args.level == "atom" else aa.RMSF_RESIDUE_COLUMNS
+    rows = res if args.level == "atom" else res["residue"]
+    idx = rows["atom"]
+    ident = {k: [b.decode() for b in structure.strings(k)[idx]] for k in ("chain", "resn", "insertion", "altloc", "atomn")}
+    ident["resi"], ident["atomi"] = [str(int(v)) for v in structure.ints("resi")[idx]], [str(int(v)) for v in structure.ints("atomi")[idx]]
+    values = {"rmsf": [repr(float(v)) for v in rows["rmsf"]], "bfactor": [repr(float(v)) for v in rows["bfactor"]]}
+    if args.level == "atom":
+        values.update({name: [repr(float(v)) for v in res["mean"][:, k]] for k, name in enumerate(("mean_x", "mean_y", "mean_z"))})
+    else:
+        values["n_atoms"] = [str(int(v)) for v in rows["n_atoms"]]
+    args.output.mkdir(parents=True, exist_ok=True)
+    out = (args.output / args.filename).with_suffix(".csv")
+    with open(out, "w") as f:
+        f.write(",".join(names) + "\n")
+        for k in range(len(idx)):
+            f.write(",".join(ident[c][k] if c in ident else values[c][k] for c in names) + "\n")
+    if args.frames is not None:
+        args.frames.parent.mkdir(parents=True, exist_ok=True)
+        with open(args.frames, "w") as f:
+            f.write("frame,rmsd\n")
+            for k, v in enumerate(res["frame_rmsd"]):
+                f.write(f"{k},{float(v)!r}\n")
+    if args.aligned is not None:
+        args.aligned.parent.mkdir(parents=True, exist_ok=True)
+        with open(args.aligned, "wb") as f:  # (np.save on a name would append .npy to any other suffix)
+            np.save(f, res["aligned"])
+    if args.reference == "mean" and not res["converged"]:
+        log.warning("The mean structure still moved by %.3g A after %d rounds (--tol %g): --max-rounds ended the iteration", res["last_change"], res["n_rounds"], args.tol)
+    log.info("RMSF of %d %s over %d models (%d rounds) saved to %s", len(idx), "atoms" if args.level == "atom" else "residues", len(res["frame_rmsd"]), res["n_rounds"], out)
+    return 0
+
+
 def run_rmsd(args) -> int:
     import numpy as np
 
@@ -642,6 +719,8 @@ def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     if args.command in ("rmsd", "rmsd-matrix", "rmsd-clusters"):
         return run_rmsd(args)
+    if args.command == "rmsf":
+        return run_rmsf(args)
     if args.command == "sc":
         return run_sc(args)
     if args.command == "sc-ensemble":

@@ -239,6 +239,8 @@ def _load():
         "arp_rmsd_matrix": (C.c_int32, [vp, vp, C.c_uint64, _dp, _u32p, C.c_uint64, _fp]),
         "arp_rmsd_reference": (C.c_int32, [vp, vp, C.c_uint64, _dp, _u32p, C.c_uint64, _dp, C.c_uint64, _fp]),
         "arp_rmsd_clusters": (C.c_int32, [vp, vp, C.c_uint64, _dp, _u32p, C.c_uint64, C.c_float, C.c_uint32, _u32p, _fp] + [_u32p] * 4),
+        "arp_rmsf": (C.c_int32, [vp, vp, C.c_uint64, _dp, _u32p, C.c_uint64, _u32p, C.c_uint64, _dp, C.c_uint64, C.c_uint32, C.c_double, _dp, _fp, _fp, _dp, _dp, _u32p, _dp]),
+        "arp_rmsf_host": (C.c_int32, [C.c_uint64, C.c_uint64, C.c_uint64, _dp, _dp, _dp, C.c_uint64, C.c_uint32, C.c_double, _dp, _fp, _fp, _dp, _dp, _u32p, _dp]),
         "arp_sasa_radius": (C.c_int32, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, _fp]),
         "arp_max_asa": (C.c_float, [C.c_char_p]),
         "arp_residue_is_polar": (C.c_int32, [C.c_char_p]),

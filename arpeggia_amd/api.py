@@ -442,6 +442,13 @@ class Context:
         `n_neighbours` <u4 (itself included); per cluster `centre` and `cluster_size` <u4; `n_clusters`.  The matrix never exists."""
         return _rmsd_clusters(self, structure, frames, atoms, chains, cutoff, max_clusters)
 
+    def rmsf(self, structure: Structure, frames=None, fit="ca", atoms=None, chains: str = "", reference="mean", max_rounds: int = 50, tol: float = 1e-4, level: str = "atom",
+             aligned: bool = False, transforms: bool = False) -> dict:
+        """arp_rmsf as a dict: the frames superposed on the atoms `fit` onto `reference` ("mean": the iterated mean structure from frame 0; a frame index or
+        an [N, 3] array: one fit to it), their mean and each measured atom's fluctuation about it -- `atom`, `mean`, `rmsf`, `bfactor`, `frame_rmsd`,
+        `n_rounds`, `last_change`, `converged`, on request `aligned` and `transforms`, with level="residue" also `residue` (get_rmsf)."""
+        return _rmsf(self, structure, frames, fit, atoms, chains, reference, max_rounds, tol, level, aligned, transforms)
+
     def sc_ensemble(self, structure: Structure, frames=None, groups: str = "/") -> dict:
         """arp_structure_sc_ensemble as a dict: shape complementarity of every frame of an ensemble (the selection and radii of get_sc on model 0).
         frames: [F, N, 3] f64 coordinates of the N atoms of model 0; None: the structure's models.  Keys: atoms (u32 structure indices of the m
@@ -1420,6 +1427,167 @@ def rmsd_matrix(input_file: str, atoms="ca", chains: str = "", ignore_zero_occup
 def rmsd_clusters(input_file: str, atoms="ca", chains: str = "", ignore_zero_occupancy: bool = False, *, cutoff: float, max_clusters: int | None = None) -> dict:
     """RMSD clusters of the models of a multi-model file: see get_rmsd_clusters."""
     return get_rmsd_clusters(Structure.load(input_file, ignore_zero_occupancy), None, atoms, chains, cutoff=cutoff, max_clusters=max_clusters)
+
+
+# ---- RMSF and the mean structure: the frames superposed on a reference or on their iterated mean (arp_rmsf; DESIGN.md section 3.21) ----
+RMSF_COLUMNS = ["chain", "resn", "resi", "insertion", "altloc", "atomn", "atomi", "mean_x", "mean_y", "mean_z", "rmsf", "bfactor"]
+RMSF_RESIDUE_COLUMNS = ["chain", "resn", "resi", "insertion", "n_atoms", "rmsf", "bfactor"]
+_BFACTOR = 8.0 * np.pi ** 2 / 3.0
+
+
+def _bfactor(rmsf_values: np.ndarray) -> np.ndarray:
+    """B = 8 pi^2 / 3 rmsf^2, formed in f64 from the f32 rmsf and rounded to f32 once."""
+    r = np.asarray(rmsf_values, np.float64)
+    return (_BFACTOR * r * r).astype("<f4")
+
+
+def rmsf_residues(chain, resi, insertion, rmsf_values) -> dict:
+    """Residue rows from atom rows: the atoms sharing (chain, resi, insertion) -- the residue identity of the residue SASA table --, sorted stably by
+    (chain as a byte string, resi, insertion).  Per row `first` (the index of its first atom, whose names are the row's), `n_atoms`, `rmsf` = the square
+    root of the unweighted mean of rmsf^2 over its atoms, formed in f64 in the order of the atoms and rounded to f32 once, and `bfactor` of that."""
+    groups: dict = {}
+    for k, key in enumerate(zip(chain, (int(r) for r in resi), insertion)):
+        groups.setdefault(key, []).append(k)
+    as_bytes = lambda v: v.encode() if isinstance(v, str) else bytes(v)
+    keys = sorted(groups, key=lambda g: (as_bytes(g[0]), g[1], as_bytes(g[2])))
+    r = np.asarray(rmsf_values, np.float64)
+    out = np.zeros(len(keys), np.float64)
+    for row, g in enumerate(keys):
+        total = 0.0
+        for k in groups[g]:
+            total += float(r[k]) * float(r[k])
+        out[row] = np.sqrt(total / len(groups[g]))
+    value = out.astype("<f4")
+    return {"first": np.array([groups[g][0] for g in keys], "<u4"), "n_atoms": np.array([len(groups[g]) for g in keys], "<u4"), "rmsf": value, "bfactor": _bfactor(value)}
+
+
+def _rmsf_reference(structure: Structure, reference, max_rounds):
+    """(ref_ptr, ref_frame, max_rounds, keep-alive) of the `reference` argument: "mean" iterates from frame 0; a frame index or an [N, 3] array is one round
+    on that reference."""
+    if isinstance(reference, str):
+        if reference != "mean":
+            raise ValueError(f"reference must be 'mean', a frame index or an [N, 3] array, got {reference!r}")
+        if not isinstance(max_rounds, (int, np.integer)) or int(max_rounds) < 0 or int(max_rounds) >= 1 << 32:
+            raise ValueError(f"max_rounds must be a positive integer, got {max_rounds!r}")
+        return None, 0, int(max_rounds), None
+    if isinstance(reference, (int, np.integer)):
+        if int(reference) < 0:
+            raise ValueError(f"reference must be 'mean', a frame index or an [N, 3] array, got {reference!r}")
+        return None, int(reference), 1, None
+    n = _topology_atoms(structure)
+    keep = np.ascontiguousarray(reference, dtype="<f8")
+    if keep.shape != (n, 3):
+        raise ArpeggiaError(_lib.ARP_ERR_BAD_INPUT, f"rmsf: reference must be 'mean', a frame index or have shape [{n}, 3] (the topology's atoms), got {list(keep.shape)}")
+    return (keep if keep.size else np.zeros(1, "<f8")).ctypes.data_as(C.POINTER(C.c_double)), 0, 1, keep
+
+
+def _rmsf(ctx: "Context | None", structure: Structure, frames, fit, atoms, chains: str, reference, max_rounds, tol, level: str, aligned: bool, transforms: bool):
+    """arp_rmsf.  ctx None: the inputs are only checked (raises their error, else returns None)."""
+    _check_level(level)
+    args, keep = _rmsd_args(structure, frames, fit, chains, "rmsf")
+    msel = None if atoms is None else rmsd_select(structure, atoms, chains)
+    msel_keep = None if msel is None else (msel if len(msel) else np.zeros(1, "<u4"))
+    msel_ptr = None if msel is None else msel_keep.ctypes.data_as(C.POINTER(C.c_uint32))
+    ref_ptr, ref_frame, rounds, ref_keep = _rmsf_reference(structure, reference, max_rounds)
+    head = (*args, msel_ptr, 0 if msel is None else len(msel), ref_ptr, ref_frame, rounds, C.c_double(tol))
+    if ctx is None:
+        _check(lib.arp_rmsf(None, *head, *([None] * 7)))
+        return None
+    F = _rmsd_frames(structure, frames)
+    idx = rmsd_select(structure, fit, chains) if msel is None else msel
+    m = len(idx)
+    out = {"atom": idx.copy(), "mean": np.zeros((m, 3), "<f8"), "rmsf": np.zeros(m, "<f4"), "frame_rmsd": np.zeros(F, "<f4")}
+    if transforms:
+        out["transforms"] = np.zeros((F, 12), "<f8")
+    if aligned:
+        out["aligned"] = np.zeros((F, m, 3), "<f8")
+    n_rounds, last = C.c_uint32(), C.c_double()
+    dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
+    ptr = lambda key, t: (out[key] if out[key].size else np.zeros(1, out[key].dtype)).ctypes.data_as(t) if key in out else None
+    _check(lib.arp_rmsf(ctx._h, *head, ptr("mean", dp), ptr("rmsf", fp), ptr("frame_rmsd", fp), ptr("transforms", dp), ptr("aligned", dp), C.byref(n_rounds), C.byref(last)))
+    out["bfactor"] = _bfactor(out["rmsf"])
+    out["n_rounds"], out["last_change"] = int(n_rounds.value), float(last.value)
+    out["converged"] = bool(out["last_change"] <= tol)
+    if level == "residue":
+        n = _topology_atoms(structure)
+        chain, ins = structure.strings("chain")[:n][idx], structure.strings("insertion")[:n][idx]
+        out["residue"] = rmsf_residues(chain, structure.ints("resi")[:n][idx], ins, out["rmsf"])
+        out["residue"]["atom"] = idx[out["residue"].pop("first")]
+    return out
+
+
+def rmsf_host(xyz_sel, xyz_msel=None, reference=0, max_rounds: int = 1, tol: float = 0.0, aligned: bool = True, transforms: bool = True) -> dict:
+    """arp_rmsf_host: the definition of arp_rmsf in plain sequential C++ on the CPU, on already-selected coordinates -- xyz_sel [F, n, 3] the fit atoms,
+    xyz_msel [F, m, 3] the measured atoms (None: the fit atoms), reference a frame index or the reference's fit atoms [n, 3].  The yardstick of the device
+    call.  Keys: mean, rmsf, frame_rmsd, n_rounds, last_change and, on request, aligned and transforms."""
+    x = np.ascontiguousarray(xyz_sel, dtype="<f8")
+    if x.ndim != 3 or x.shape[2] != 3:
+        raise ValueError(f"xyz_sel must have shape [F, n, 3], got {list(x.shape)}")
+    F, n = x.shape[:2]
+    xm = None if xyz_msel is None else np.ascontiguousarray(xyz_msel, dtype="<f8")
+    if xm is not None and (xm.ndim != 3 or xm.shape[0] != F or xm.shape[2] != 3):
+        raise ValueError(f"xyz_msel must have shape [{F}, m, 3], got {list(xm.shape)}")
+    m = n if xm is None else xm.shape[1]
+    dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
+    arr = lambda a, t=dp: (a if a.size else np.zeros(1, a.dtype)).ctypes.data_as(t)
+    ref, ref_frame = None, 0
+    if isinstance(reference, (int, np.integer)):
+        if int(reference) < 0:
+            raise ValueError(f"reference must be a frame index or an [n, 3] array, got {reference!r}")
+        ref_frame = int(reference)
+    else:
+        ref = np.ascontiguousarray(reference, dtype="<f8")
+        if ref.shape != (n, 3):
+            raise ValueError(f"reference must be a frame index or have shape [{n}, 3], got {list(ref.shape)}")
+    out = {"mean": np.zeros((m, 3), "<f8"), "rmsf": np.zeros(m, "<f4"), "frame_rmsd": np.zeros(F, "<f4")}
+    if transforms:
+        out["transforms"] = np.zeros((F, 12), "<f8")
+    if aligned:
+        out["aligned"] = np.zeros((F, m, 3), "<f8")
+    n_rounds, last = C.c_uint32(), C.c_double()
+    _check(lib.arp_rmsf_host(F, n, m, arr(x), None if xm is None else arr(xm), None if ref is None else arr(ref), ref_frame, int(max_rounds), C.c_double(tol), arr(out["mean"]),
+                             arr(out["rmsf"], fp), arr(out["frame_rmsd"], fp), arr(out["transforms"]) if transforms else None, arr(out["aligned"]) if aligned else None,
+                             C.byref(n_rounds), C.byref(last)))
+    out["n_rounds"], out["last_change"] = int(n_rounds.value), float(last.value)
+    return out
+
+
+def get_rmsf(structure: Structure, frames=None, fit="ca", atoms=None, chains: str = "", reference="mean", max_rounds: int = 50, tol: float = 1e-4, level: str = "atom",
+             aligned: bool = False, transforms: bool = False, device: int = 0) -> dict:
+    """How much each atom moves across the frames of an ensemble.  Every frame is superposed (proper rotations only) on the atoms of rmsd_select(structure, fit,
+    chains) onto the reference -- "mean": the iterated mean structure, started from frame 0 and repeated until the mean moves by at most `tol` A (rms over the
+    fit atoms) or `max_rounds` rounds are done; a frame index or an [N, 3] array: one fit to that fixed reference -- and the superposed frames are averaged.
+    atoms: the measured atoms (as rmsd_select takes them; None: the fit atoms).  Returns a dict: `atom` <u4 [m] (topology indices), `mean` <f8 [m, 3] (in the
+    reference's frame), `rmsf` <f4 [m], `bfactor` <f4 [m] (8 pi^2 / 3 rmsf^2), `frame_rmsd` <f4 [F] (each superposed frame against the mean, over the fit
+    atoms), `n_rounds`, `last_change`, `converged` (last_change <= tol); with aligned / transforms also `aligned` <f8 [F, m, 3] and `transforms` <f8 [F, 12]
+    (R row-major, then t: y = R x + t).  level="residue" adds `residue`: per residue of the measured atoms `atom` (its first), `n_atoms`, `rmsf` (the square
+    root of the mean of rmsf^2 over its atoms) and `bfactor`.  frames: [F, N, 3] f64; None: the structure's models."""
+    ctx = _with_context(device, lambda: _rmsf(None, structure, frames, fit, atoms, chains, reference, max_rounds, tol, level, aligned, transforms))
+    return ctx.rmsf(structure, frames, fit, atoms, chains, reference, max_rounds, tol, level, aligned, transforms)
+
+
+def rmsf(input_file: str, fit="ca", atoms=None, chains: str = "", reference="mean", max_rounds: int = 50, tol: float = 1e-4, level: str = "atom", aligned: bool = False,
+         transforms: bool = False, ignore_zero_occupancy: bool = False) -> dict:
+    """RMSF and the mean structure of the models of a multi-model file (the models are the frames): see get_rmsf."""
+    return get_rmsf(Structure.load(input_file, ignore_zero_occupancy), None, fit, atoms, chains, reference, max_rounds, tol, level, aligned, transforms)
+
+
+def rmsf_table(structure: Structure, result: dict, level: str = "atom"):
+    """The result of an rmsf call as a table of the contact table's type: RMSF_COLUMNS per measured atom, RMSF_RESIDUE_COLUMNS per residue."""
+    import pyarrow as pa
+
+    _check_level(level)
+    if level == "atom":
+        cols = _identity(structure, result["atom"])
+        for k, name in enumerate(("mean_x", "mean_y", "mean_z")):
+            cols[name] = pa.array(result["mean"][:, k], pa.float64())
+        cols["rmsf"], cols["bfactor"] = pa.array(result["rmsf"], pa.float32()), pa.array(result["bfactor"], pa.float32())
+        return _frame({k: cols[k] for k in RMSF_COLUMNS})
+    res = result["residue"]
+    cols = _identity(structure, res["atom"])
+    cols["n_atoms"] = pa.array(res["n_atoms"], pa.uint32())
+    cols["rmsf"], cols["bfactor"] = pa.array(res["rmsf"], pa.float32()), pa.array(res["bfactor"], pa.float32())
+    return _frame({k: cols[k] for k in RMSF_RESIDUE_COLUMNS})
 
 
 def _contact_clusters_arrow(input_file: str, groups: str, vdw_comp: float, dist_cutoff: float, ignore_zero_occupancy: bool, rings: bool, level: str, min_similarity: float,

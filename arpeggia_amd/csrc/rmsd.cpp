@@ -36,6 +36,9 @@ double jacobi_top(double a[4][4]) {
     return std::max(std::max(a[0][0], a[1][1]), std::max(a[2][2], a[3][3]));
 }
 
+}  // namespace
+
+namespace arp {
 uint64_t rmsd_cap() { return g_debug.rmsd_cap_bytes > 0 ? (uint64_t)g_debug.rmsd_cap_bytes : (1ull << 31); }
 
 // What the three device calls check before the device is touched: the frame checks of the frequency call with its statuses and messages, then the
@@ -75,6 +78,9 @@ arp_status rmsd_check(const char *what, const arp_structure *s, uint64_t n_frame
     return ARP_OK;
 }
 
+}  // namespace arp
+
+namespace {
 // the packed frames X[F][3][n_pad] and G[F] stay on the device for the call
 arp_status rmsd_packed_cap(const char *what, uint64_t F, uint64_t n) {
     const uint64_t need = F * 3u * rmsd_n_pad(n) * 8u + F * 8u;

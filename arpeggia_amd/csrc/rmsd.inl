@@ -36,7 +36,11 @@ __device__ inline double rmsd_block_sum(double v, double *red) {
     __syncthreads();
     return s;
 }
-__global__ __launch_bounds__(256) void k_rmsd_pack(const double *xyz, uint32_t N, const uint32_t *__restrict__ sel, uint32_t n, uint32_t n_pad, double *X, double *G) {
+// kMeasured (rmsf.inl): the centring is refined (below), the frame's centroid goes to C[f][3] as well, and the m atoms of msel, centred on that same
+// centroid of the fit atoms, to XM[F][3][m_pad].  The arp_rmsd_* calls instantiate kMeasured = false: nothing of theirs changes.
+template <bool kMeasured>
+__global__ __launch_bounds__(256) void k_rmsd_pack(const double *xyz, uint32_t N, const uint32_t *__restrict__ sel, uint32_t n, uint32_t n_pad, double *X, double *G,
+                                                   const uint32_t *__restrict__ msel, uint32_t m, uint32_t m_pad, double *XM, double *C) {
     __shared__ double red[256];
     const double *frame = xyz + (size_t)blockIdx.x * N * 3u;
     double *out = X + (size_t)blockIdx.x * 3u * n_pad;
@@ -58,6 +62,36 @@ __global__ __launch_bounds__(256) void k_rmsd_pack(const double *xyz, uint32_t N
     }
     g = rmsd_block_sum(g, red);
     if (threadIdx.x == 0u) G[blockIdx.x] = g;
+    if (kMeasured) {
+        // A second centring: c carries the rounding of a sum of absolute coordinates (10^-11 A for a frame 10^5 A from the origin), which would move the
+        // whole frame against the others.  r = the centroid of the centred atoms is that error, known to the rounding of the small x; the frame's centroid
+        // is c + r and x - r is centred to eps |x|.  (Each lane rereads what it wrote itself.)
+        double r[3];
+        for (int k = 0; k < 3; k++) {
+            double s = 0.0;
+            for (uint32_t i = threadIdx.x; i < n; i += 256u) s += out[(size_t)k * n_pad + i];
+            r[k] = rmsd_block_sum(s, red) / (double)n;
+        }
+        g = 0.0;
+        for (uint32_t i = threadIdx.x; i < n; i += 256u) {
+            double d[3];
+            for (int k = 0; k < 3; k++) out[(size_t)k * n_pad + i] = d[k] = out[(size_t)k * n_pad + i] - r[k];
+            g += d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+        }
+        g = rmsd_block_sum(g, red);
+        if (threadIdx.x == 0u) G[blockIdx.x] = g;
+        if (threadIdx.x == 0u)
+            for (int k = 0; k < 3; k++) C[(size_t)blockIdx.x * 3u + k] = c[k] + r[k];
+        double *outm = XM + (size_t)blockIdx.x * 3u * m_pad;
+        for (uint32_t i = threadIdx.x; i < m_pad; i += 256u) {
+            double d[3] = {0.0, 0.0, 0.0};
+            if (i < m) {
+                const double *p = frame + (size_t)msel[i] * 3u;
+                for (int k = 0; k < 3; k++) d[k] = (p[k] - c[k]) - r[k];
+            }
+            for (int k = 0; k < 3; k++) outm[(size_t)k * m_pad + i] = d[k];
+        }
+    }
 }
 
 // The largest eigenvalue of the symmetric 4 x 4 matrix a (its upper triangle) by cyclic Jacobi rotations: every rotation is backward stable whatever the gaps
@@ -302,13 +336,14 @@ arp_status device_rmsd(arp_context *ctx, const RmsdJob &job, float *out, Cluster
     for (uint64_t f0 = 0; f0 < F; f0 += per) {
         const uint64_t fc = std::min<uint64_t>(per, F - f0);
         HIP_TRY(hipMemcpyAsync(stage, job.xyz + f0 * N * 3u, fc * N * 24u, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_rmsd_pack, dim3((uint32_t)fc), dim3(256), 0, st, (const double *)stage, (uint32_t)N, (const uint32_t *)sel, (uint32_t)n, (uint32_t)n_pad,
-                           X + f0 * 3u * n_pad, G + f0);
+        hipLaunchKernelGGL(k_rmsd_pack<false>, dim3((uint32_t)fc), dim3(256), 0, st, (const double *)stage, (uint32_t)N, (const uint32_t *)sel, (uint32_t)n, (uint32_t)n_pad,
+                           X + f0 * 3u * n_pad, G + f0, (const uint32_t *)nullptr, 0u, 0u, (double *)nullptr, (double *)nullptr);
         HIP_TRY(hipGetLastError());
     }
     if (ext_ref) {
         HIP_TRY(hipMemcpyAsync(stage, job.ref_xyz, N * 24u, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_rmsd_pack, dim3(1), dim3(256), 0, st, (const double *)stage, (uint32_t)N, (const uint32_t *)sel, (uint32_t)n, (uint32_t)n_pad, XR, GR);
+        hipLaunchKernelGGL(k_rmsd_pack<false>, dim3(1), dim3(256), 0, st, (const double *)stage, (uint32_t)N, (const uint32_t *)sel, (uint32_t)n, (uint32_t)n_pad, XR, GR,
+                           (const uint32_t *)nullptr, 0u, 0u, (double *)nullptr, (double *)nullptr);
         HIP_TRY(hipGetLastError());
     }
     lap("pack");

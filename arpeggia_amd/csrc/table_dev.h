@@ -189,6 +189,35 @@ struct RmsdJob {
 };
 constexpr uint64_t rmsd_n_pad(uint64_t n) { return (n + 3u) & ~3ull; }  // atoms of a packed frame: n rounded up to the K step of the f64 MFMA (rmsd.inl kRmsdStep)
 arp_status device_rmsd(arp_context *ctx, const RmsdJob &job, float *out, ClustersHost *clusters);
+// rmsd.cpp: what every arp_rmsd_* / arp_rmsf call checks before the device is touched (the frame checks of the frequency call, then the selection), and the
+// capacity knob "rmsd_cap_bytes"
+uint64_t rmsd_cap();
+arp_status rmsd_check(const char *what, const arp_structure *s, uint64_t n_frames, const double *xyz, const uint32_t *sel, uint64_t n_sel, std::vector<double> *model_xyz,
+                      const double **frames, uint64_t *n0_out, uint64_t *F_out);
+
+// RMSF and the mean structure (rmsf.inl, arp_rmsf): the frames superposed on frame ref_frame, on ref_xyz[n_atoms x 3] when it is given, or
+// -- max_rounds > 1 -- on their own iterated mean, fitted on the n_sel atoms of sel and measured on the n_msel atoms of msel (msel == nullptr: on sel, n_msel
+// is then n_sel).  The outputs are arp_rmsf's; transforms and aligned may be null.  The caller has checked the sizes against the capacity knob.
+struct RmsfJob {
+    uint64_t n_atoms = 0, n_frames = 0, n_sel = 0, n_msel = 0;
+    const double *xyz = nullptr;
+    const uint32_t *sel = nullptr, *msel = nullptr;
+    uint64_t chunk_atoms = 0;  // atoms per upload pass, 0 = automatic (arp_debug_set "rmsd_chunk_atoms")
+    const double *ref_xyz = nullptr;
+    uint64_t ref_frame = 0;
+    uint32_t max_rounds = 1;
+    double tol = 0.0;
+};
+struct RmsfOut {
+    double *mean = nullptr;        // [m][3]
+    float *rmsf = nullptr;         // [m]
+    float *frame_rmsd = nullptr;   // [F]
+    double *transforms = nullptr;  // [F][12], nullable
+    double *aligned = nullptr;     // [F][m][3], nullable
+    uint32_t n_rounds = 0;
+    double last_change = 0.0;
+};
+arp_status device_rmsf(arp_context *ctx, const RmsfJob &job, RmsfOut *out);
 
 // engine.cpp: the context's stream / device and grow-only scratch (device and pinned host)
 void *context_stream(arp_context *ctx);

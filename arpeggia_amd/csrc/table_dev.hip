@@ -1026,5 +1026,6 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
 #include "autocorr.inl"
 #include "cluster.inl"
 #include "rmsd.inl"
+#include "rmsf.inl"
 
 }  // namespace arp

@@ -829,6 +829,50 @@ arp_status arp_rmsd_clusters(arp_context *ctx, arp_structure *topology, uint64_t
  * frames ARP_ERR_CAPACITY.  The CPU yardstick of the device kernels: they agree with it within the rounding of the sums, not bit for bit. */
 arp_status arp_rmsd_host(uint64_t n_frames, uint64_t n, const double *xyz_sel, float *out);
 
+/* ---- RMSF and the mean structure: the frames superposed on a reference or on their own average, how much each atom moves about it -- DESIGN.md section
+ * 3.21 ----
+ * Frames, topology and sel[n] (the fit atoms) as for the arp_rmsd_* calls above, with their checks and messages.  msel[m]: the measured atoms, u32 topology
+ * indices, strictly increasing; msel == NULL: the fit atoms are measured (m = n, n_msel is not looked at).  Weights are 1.
+ * Centring.  Per frame c_f = the f64 centroid of the fit atoms; x_f,i = coordinate - c_f, for the fit atoms and the measured atoms alike.  The centroid is
+ *   taken in two steps -- the mean, then the mean of what is left after subtracting it, subtracted again -- so that a frame 10^5 A from the origin is
+ *   centred to the rounding of its centred coordinates, not of its absolute ones.
+ * Starting target.  T_1 = the centred fit atoms of frame ref_frame, or of ref_xyz[N][3] when that is given (ref_frame is then ignored); c_T = that reference's
+ * fit centroid, fixed for the call.
+ * Round j = 1, 2, ..:  per frame S_f = sum_i x_f,i T_j,i^T over the fit atoms, K(S_f) as written out above, q_f = (w, x, y, z) a unit eigenvector of its
+ *   largest eigenvalue, R_f the proper rotation of q_f,
+ *     |  w^2 + x^2 - y^2 - z^2    2 (x y - w z)            2 (x z + w y)          |
+ *     |  2 (y x + w z)            w^2 - x^2 + y^2 - z^2    2 (y z - w x)          |
+ *     |  2 (z x - w y)            2 (z y + w x)            w^2 - x^2 - y^2 + z^2  |
+ *   the rotation that minimises sum_i |R x_f,i - T_j,i|^2 over proper rotations (a mirror image stays unsuperposed);  Y_f,i = R_f x_f,i;
+ *   M_j = (1 / F) sum_f Y_f over the fit atoms;  change_j = sqrt((1 / n) sum_i |M_j,i - T_j,i|^2).
+ *   The call stops after round j when j == max_rounds or change_j <= tol; otherwise T_j+1 = M_j.  max_rounds = 1 is the classic fit to a fixed reference.
+ * Outputs, all under the last round's R_f; quantities over the fit atoms use M over the fit set, quantities over the measured atoms the mean over the
+ * measured set:
+ *   mean[m][3]         f64  the mean of Y over the frames, plus c_T
+ *   rmsf[m]            f32  sqrt((1 / F) sum_f |Y_f,i - mean_i|^2): summed as deviations from the finished mean, never as E[y^2] - E[y]^2; one rounding to f32
+ *   frame_rmsd[F]      f32  sqrt((1 / n) sum_{i in sel} |Y_f,i - M_i|^2), no re-fit
+ *   transforms[F][12]  f64, may be NULL: R_f row-major, then t_f = c_T - R_f c_f, so that y = R x + t maps absolute frame coordinates onto the reference's
+ *   aligned[F][m][3]   f64, may be NULL: R x + t of the measured atoms, formed as R_f x_f,i + c_T
+ *   *n_rounds u32, *last_change f64: the rounds done and the final change; last_change > tol says that the cap max_rounds ended the call.
+ * Eigenvector choice.  Where the top eigenvalue of K is double (collinear fit atoms in either structure, n <= 2) any top eigenvector is allowed; it is chosen
+ * deterministically: the Jacobi column of the largest diagonal entry, the lowest index on ties.
+ * Checks, all before the device is touched, ARP_ERR_BAD_INPUT: those of the arp_rmsd_* calls (prefix "rmsf"); msel given and empty, with an index >= N or
+ * not strictly increasing; max_rounds == 0; a tol that is not finite or < 0; ref_frame >= F (without ref_xyz); a non-finite ref_xyz.  ctx == NULL runs only
+ * the checks (ARP_OK).
+ * Device memory: both packed sets, F x 3 x (n_pad + m_pad) x 8 bytes (m_pad only with msel), stay resident and are checked against "rmsd_cap_bytes" before
+ * anything is allocated: ARP_ERR_CAPACITY with a message that names F, n, m and the bytes.  No floating-point atomic is used and the order of every sum is a
+ * function of (F, n, m) alone: two calls give identical bytes, whatever the pass size ("rmsd_chunk_atoms").  Synchronous; one 8-byte read-back per round. */
+arp_status arp_rmsf(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const uint32_t *sel, uint64_t n_sel, const uint32_t *msel,
+                    uint64_t n_msel, const double *ref_xyz, uint64_t ref_frame, uint32_t max_rounds, double tol, double *mean, float *rmsf, float *frame_rmsd,
+                    double *transforms, double *aligned, uint32_t *n_rounds, double *last_change);
+/* The definition above in plain sequential C++ on already-selected coordinates, without a device: xyz_sel n_frames x n x 3 (the fit atoms), xyz_msel
+ * n_frames x m x 3 (the measured atoms; NULL: the fit atoms, m must equal n), ref_sel n x 3 (the reference's fit atoms; NULL: frame ref_frame).  f64
+ * throughout, every sum in the order of its index.  The outputs are arp_rmsf's.  n_frames, n or m == 0, max_rounds == 0, a bad tol or ref_frame and a
+ * non-finite coordinate are ARP_ERR_BAD_INPUT.  The CPU yardstick of the device kernels: they agree within the rounding of the sums, not bit for bit. */
+arp_status arp_rmsf_host(uint64_t n_frames, uint64_t n, uint64_t m, const double *xyz_sel, const double *xyz_msel, const double *ref_sel, uint64_t ref_frame,
+                         uint32_t max_rounds, double tol, double *mean, float *rmsf, float *frame_rmsd, double *transforms, double *aligned, uint32_t *n_rounds,
+                         double *last_change);
+
 /* ---- SASA and SAP statistics over the frames of an ensemble (MD snapshots, NMR models, conformers of one topology) -- DESIGN.md section 3.8 ----
  * Topology, N, frames and xyz exactly as arp_contact_frequencies defines them: model 0 of `topology` is the topology, frame f is xyz[f]
  * (n_frames x N x 3 f64, host, C order); xyz == NULL: the structure's models are the frames, with the same one-for-one model check and its error.
