@@ -20,6 +20,9 @@ against --reference K; `rmsd-matrix` the matrix to --matrix FILE.npy; `rmsd-clus
 `rmsf` (no counterpart either) superposes the models on --fit ca|backbone|heavy|all onto --reference mean (the iterated mean structure, --max-rounds N, --tol X)
 or model K, and writes per --atoms atom (default: the --fit atoms) or, with -l residue, per residue the mean position, rmsf and B-factor; --frames FILE.csv: each
 model's rmsd to the mean; --aligned FILE.npy: the superposed coordinates.
+`dccm` and `pca` (no counterpart either) take `rmsf`'s --fit, --atoms, -c, --reference, --max-rounds and --tol: `dccm` writes the dynamic cross-correlation map of
+the measured atoms to --matrix FILE.npy and, with -o (and -f, -t), in long form; `pca` takes --modes K and writes --eigenvalues FILE.csv, --modes-file FILE.npy,
+--projections FILE.csv and --covariance FILE.npy (the eigen-solve runs on the host).
 `sasa-ensemble` and `sap-ensemble` (no counterpart either) take the flags and defaults of `sasa` / `sap` without --model: statistics over the models.
 `dsasa --level atom|residue` writes the interface row by row (default `total`: the reference's scalar); `dsasa-ensemble` takes the flags of
 `sasa-ensemble` and -g: dSASA per model and the per-atom statistics of the buried surface.
@@ -177,6 +180,28 @@ def build_parser() -> argparse.ArgumentParser:
     rf.add_argument("--frames", default=None, type=Path, metavar="FILE.csv", help="Write one line per model: frame, rmsd (to the mean, over the --fit atoms)")
     rf.add_argument("--aligned", default=None, type=Path, metavar="FILE.npy", help="Write the superposed coordinates of the measured atoms: float64 [models, atoms, 3]")
     rf.add_argument("--ignore-zero-occupancy", action="store_true", help="Ignore atoms with zero occupancy")
+    for name in ("dccm", "pca"):
+        cv = sub.add_parser(name, help="which atoms move together across the models: the dynamic cross-correlation map after rmsf's superposition" if name == "dccm" else
+                            "along which collective directions the models move: principal components of the covariance of the superposed coordinates")
+        cv.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file whose models are the frames")
+        cv.add_argument("--fit", default="ca", choices=("ca", "backbone", "heavy", "all"), help="Atoms to superpose on (residue HOH is never among them)")
+        cv.add_argument("--atoms", default=None, choices=("ca", "backbone", "heavy", "all"), help="Atoms to measure (default: the atoms of --fit)")
+        cv.add_argument("-c", "--chains", default="", help="Comma-separated chain IDs to include (empty: all)")
+        cv.add_argument("--reference", default="mean", type=_rmsf_reference_arg, metavar="mean|K", help="Superpose on the iterated mean structure, or on model K (0: the first)")
+        cv.add_argument("--max-rounds", default=50, type=int, metavar="N", help="With --reference mean: at most N rounds of superposing and averaging")
+        cv.add_argument("--tol", default=1e-4, type=float, metavar="X", help="With --reference mean: stop when the mean moves by at most X Angstroms (rms over the fit atoms)")
+        cv.add_argument("--ignore-zero-occupancy", action="store_true", help="Ignore atoms with zero occupancy")
+        if name == "dccm":
+            cv.add_argument("--matrix", default=None, type=Path, metavar="FILE.npy", help="Write the map: float32 [atoms, atoms]")
+            cv.add_argument("-o", "--output", default=None, type=Path, help="Output directory of the long-form table (one row per pair of atoms)")
+            cv.add_argument("-f", "--filename", default="dccm", help="Name of the long-form table")
+            cv.add_argument("-t", "--output-format", default="csv", type=str.lower, choices=FORMATS, help="Output file type of the long-form table")
+        else:
+            cv.add_argument("--modes", default=10, type=int, metavar="K", help="Principal components to keep")
+            cv.add_argument("--eigenvalues", default=None, type=Path, metavar="FILE.csv", help="Write one line per kept mode: mode, eigenvalue, explained, cumulative")
+            cv.add_argument("--modes-file", default=None, type=Path, metavar="FILE.npy", help="Write the modes: float64 [K, 3 atoms], atom-major rows")
+            cv.add_argument("--projections", default=None, type=Path, metavar="FILE.csv", help="Write one line per model: frame, pc1 .. pcK")
+            cv.add_argument("--covariance", default=None, type=Path, metavar="FILE.npy", help="Write the covariance matrix: float64 [3 atoms, 3 atoms]")
     common = dict(model=("-m", "--model", 0, int, "Model number to analyze (0: the first model)"),
                   probe=("-r", "--probe-radius", 1.4, float, "Probe radius in Angstroms"),
                   points=("-n", "--num-points", 100, int, "Number of points for surface calculation"),
@@ -665,6 +690,77 @@ def run_rmsf(args) -> int:
     return 0
 
 
+def _save_npy(path: Path, array):
+    import numpy as np
+
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:  # (np.save on a name would append .npy to any other suffix)
+        np.save(f, array)
+
+
+def run_dccm(args) -> int:
+    import arpeggia_amd as aa
+
+    if not args.input.exists():
+        log.error("Failed to retrieve input file: %s", args.input)
+        return 1
+    if args.matrix is None and args.output is None:
+        log.error("DCCM: nothing to write, give --matrix FILE.npy and / or -o DIR")
+        return 1
+    try:
+        structure = aa.Structure.load(str(args.input.resolve()), args.ignore_zero_occupancy)
+        res = aa.get_dccm(structure, None, args.fit, args.atoms, args.chains, args.reference, args.max_rounds, args.tol)
+    except (aa.ArpeggiaError, ValueError) as e:
+        log.error("DCCM failed: %s", e)
+        return 1
+    if args.matrix is not None:
+        _save_npy(args.matrix, res["dccm"])
+    if args.output is not None:
+        args.output.mkdir(parents=True, exist_ok=True)
+        out = (args.output / args.filename).with_suffix("." + args.output_format)
+        write_table(aa.dccm_table(structure, res), out, args.output_format)
+    if args.reference == "mean" and not res["converged"]:
+        log.warning("The mean structure still moved by %.3g A after %d rounds (--tol %g): --max-rounds ended the iteration", res["last_change"], res["n_rounds"], args.tol)
+    log.info("DCCM of %d atoms over %d models (%d rounds) saved", len(res["atom"]), len(res["frame_rmsd"]), res["n_rounds"])
+    return 0
+
+
+def run_pca(args) -> int:
+    import arpeggia_amd as aa
+
+    if not args.input.exists():
+        log.error("Failed to retrieve input file: %s", args.input)
+        return 1
+    try:
+        structure = aa.Structure.load(str(args.input.resolve()), args.ignore_zero_occupancy)
+        res = aa.get_pca(structure, None, args.fit, args.atoms, args.chains, args.reference, args.max_rounds, args.tol, args.modes)
+    except (aa.ArpeggiaError, ValueError) as e:
+        log.error("PCA failed: %s", e)
+        return 1
+    k = len(res["modes"])
+    if args.eigenvalues is not None:
+        args.eigenvalues.parent.mkdir(parents=True, exist_ok=True)
+        with open(args.eigenvalues, "w") as f:
+            f.write("mode,eigenvalue,explained,cumulative\n")
+            for j in range(k):
+                f.write(f"{j + 1},{float(res['eigenvalues'][j])!r},{float(res['explained'][j])!r},{float(res['cumulative'][j])!r}\n")
+    if args.modes_file is not None:
+        _save_npy(args.modes_file, res["modes"])
+    if args.covariance is not None:
+        _save_npy(args.covariance, res["covariance"])
+    if args.projections is not None:
+        args.projections.parent.mkdir(parents=True, exist_ok=True)
+        with open(args.projections, "w") as f:
+            f.write(",".join(["frame"] + [f"pc{j + 1}" for j in range(k)]) + "\n")
+            for frame, row in enumerate(res["projections"]):
+                f.write(",".join([str(frame)] + [repr(float(v)) for v in row]) + "\n")
+    if args.reference == "mean" and not res["converged"]:
+        log.warning("The mean structure still moved by %.3g A after %d rounds (--tol %g): --max-rounds ended the iteration", res["last_change"], res["n_rounds"], args.tol)
+    log.info("%d principal components of %d atoms over %d models: %.1f %% of the variance", k, len(res["atom"]), len(res["frame_rmsd"]),
+             100.0 * float(res["cumulative"][-1]))
+    return 0
+
+
 def run_rmsd(args) -> int:
     import numpy as np
 
@@ -721,6 +817,10 @@ def main(argv=None) -> int:
         return run_rmsd(args)
     if args.command == "rmsf":
         return run_rmsf(args)
+    if args.command == "dccm":
+        return run_dccm(args)
+    if args.command == "pca":
+        return run_pca(args)
     if args.command == "sc":
         return run_sc(args)
     if args.command == "sc-ensemble":

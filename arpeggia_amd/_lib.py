@@ -241,6 +241,10 @@ def _load():
         "arp_rmsd_clusters": (C.c_int32, [vp, vp, C.c_uint64, _dp, _u32p, C.c_uint64, C.c_float, C.c_uint32, _u32p, _fp] + [_u32p] * 4),
         "arp_rmsf": (C.c_int32, [vp, vp, C.c_uint64, _dp, _u32p, C.c_uint64, _u32p, C.c_uint64, _dp, C.c_uint64, C.c_uint32, C.c_double, _dp, _fp, _fp, _dp, _dp, _u32p, _dp]),
         "arp_rmsf_host": (C.c_int32, [C.c_uint64, C.c_uint64, C.c_uint64, _dp, _dp, _dp, C.c_uint64, C.c_uint32, C.c_double, _dp, _fp, _fp, _dp, _dp, _u32p, _dp]),
+        "arp_covariance": (C.c_int32, [vp, vp, C.c_uint64, _dp, _u32p, C.c_uint64, _u32p, C.c_uint64, _dp, C.c_uint64, C.c_uint32, C.c_double, _dp, _fp, _dp, _fp, _fp, _dp, _u32p, _dp]),
+        "arp_project": (C.c_int32, [vp, vp, C.c_uint64, _dp, _u32p, C.c_uint64, _dp, _dp, _dp, C.c_uint64, _dp]),
+        "arp_covariance_host": (C.c_int32, [C.c_uint64, C.c_uint64, _dp, _dp, _dp, _fp]),
+        "arp_project_host": (C.c_int32, [C.c_uint64, C.c_uint64, _dp, _dp, _dp, _dp, C.c_uint64, _dp]),
         "arp_sasa_radius": (C.c_int32, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, _fp]),
         "arp_max_asa": (C.c_float, [C.c_char_p]),
         "arp_residue_is_polar": (C.c_int32, [C.c_char_p]),

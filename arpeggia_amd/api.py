@@ -449,6 +449,27 @@ class Context:
         `n_rounds`, `last_change`, `converged`, on request `aligned` and `transforms`, with level="residue" also `residue` (get_rmsf)."""
         return _rmsf(self, structure, frames, fit, atoms, chains, reference, max_rounds, tol, level, aligned, transforms)
 
+    def covariance(self, structure: Structure, frames=None, fit="ca", atoms=None, chains: str = "", reference="mean", max_rounds: int = 50, tol: float = 1e-4, cov: bool = True,
+                   dccm: bool = False, transforms: bool = False) -> dict:
+        """arp_covariance as a dict: rmsf's keys (the same superposition, byte for byte) plus `covariance` <f8 [3m, 3m] (cov=True: the second moments of the
+        superposed coordinates about their mean, atom-major, divisor F) and / or `dccm` <f4 [m, m] (dccm=True: the dynamic cross-correlation map)."""
+        return _covariance(self, structure, frames, fit, atoms, chains, reference, max_rounds, tol, cov, dccm, transforms)
+
+    def dccm(self, structure: Structure, frames=None, fit="ca", atoms=None, chains: str = "", reference="mean", max_rounds: int = 50, tol: float = 1e-4,
+             transforms: bool = False) -> dict:
+        """covariance() with the `dccm` output only."""
+        return _covariance(self, structure, frames, fit, atoms, chains, reference, max_rounds, tol, False, True, transforms)
+
+    def project(self, structure: Structure, frames, atoms, mean, modes, transforms=None) -> np.ndarray:
+        """arp_project: <f8 [F, k], the deviations of the measured atoms from `mean` [m, 3] along `modes` [k, 3m] (atom-major rows).  transforms [F, 12]
+        (as rmsf returns them) are applied to the frames' absolute coordinates first; None: the frames are already superposed.  No fit is repeated."""
+        return _project(self, structure, frames, atoms, mean, modes, transforms)
+
+    def pca(self, structure: Structure, frames=None, fit="ca", atoms=None, chains: str = "", reference="mean", max_rounds: int = 50, tol: float = 1e-4, n_modes: int = 10) -> dict:
+        """Principal components of the superposed coordinates ("essential dynamics"): covariance() on the device, numpy.linalg.eigh on the HOST (the eigen-solve
+        is not on the device), project() on the device.  See get_pca for the keys."""
+        return _pca(self, structure, frames, fit, atoms, chains, reference, max_rounds, tol, n_modes)
+
     def sc_ensemble(self, structure: Structure, frames=None, groups: str = "/") -> dict:
         """arp_structure_sc_ensemble as a dict: shape complementarity of every frame of an ensemble (the selection and radii of get_sc on model 0).
         frames: [F, N, 3] f64 coordinates of the N atoms of model 0; None: the structure's models.  Keys: atoms (u32 structure indices of the m
@@ -1588,6 +1609,214 @@ def rmsf_table(structure: Structure, result: dict, level: str = "atom"):
     cols["n_atoms"] = pa.array(res["n_atoms"], pa.uint32())
     cols["rmsf"], cols["bfactor"] = pa.array(res["rmsf"], pa.float32()), pa.array(res["bfactor"], pa.float32())
     return _frame({k: cols[k] for k in RMSF_RESIDUE_COLUMNS})
+
+
+# ---- Covariance, DCCM and principal components of the superposed coordinates (arp_covariance, arp_project) ----
+_ID_COLUMNS = ["chain", "resn", "resi", "insertion", "altloc", "atomn", "atomi"]
+DCCM_COLUMNS = [f"from_{k}" for k in _ID_COLUMNS] + [f"to_{k}" for k in _ID_COLUMNS] + ["correlation"]
+
+
+def _covariance(ctx: "Context | None", structure: Structure, frames, fit, atoms, chains: str, reference, max_rounds, tol, cov: bool, dccm: bool, transforms: bool):
+    """arp_covariance.  ctx None: the inputs are only checked (raises their error, else returns None)."""
+    if not cov and not dccm:
+        raise ValueError("covariance: at least one of cov and dccm must be asked for")
+    args, keep = _rmsd_args(structure, frames, fit, chains, "covariance")
+    msel = None if atoms is None else rmsd_select(structure, atoms, chains)
+    msel_keep = None if msel is None else (msel if len(msel) else np.zeros(1, "<u4"))
+    msel_ptr = None if msel is None else msel_keep.ctypes.data_as(C.POINTER(C.c_uint32))
+    ref_ptr, ref_frame, rounds, ref_keep = _rmsf_reference(structure, reference, max_rounds)
+    head = (*args, msel_ptr, 0 if msel is None else len(msel), ref_ptr, ref_frame, rounds, C.c_double(tol))
+    if ctx is None:
+        _check(lib.arp_covariance(None, *head, *([None] * 8)))
+        return None
+    F = _rmsd_frames(structure, frames)
+    idx = rmsd_select(structure, fit, chains) if msel is None else msel
+    m = len(idx)
+    out = {"atom": idx.copy(), "mean": np.zeros((m, 3), "<f8"), "rmsf": np.zeros(m, "<f4"), "frame_rmsd": np.zeros(F, "<f4")}
+    if cov:
+        out["covariance"] = np.zeros((3 * m, 3 * m), "<f8")
+    if dccm:
+        out["dccm"] = np.zeros((m, m), "<f4")
+    if transforms:
+        out["transforms"] = np.zeros((F, 12), "<f8")
+    n_rounds, last = C.c_uint32(), C.c_double()
+    dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
+    ptr = lambda key, t: (out[key] if out[key].size else np.zeros(1, out[key].dtype)).ctypes.data_as(t) if key in out else None
+    _check(lib.arp_covariance(ctx._h, *head, ptr("covariance", dp), ptr("dccm", fp), ptr("mean", dp), ptr("rmsf", fp), ptr("frame_rmsd", fp), ptr("transforms", dp),
+                              C.byref(n_rounds), C.byref(last)))
+    out["bfactor"] = _bfactor(out["rmsf"])
+    out["n_rounds"], out["last_change"] = int(n_rounds.value), float(last.value)
+    out["converged"] = bool(out["last_change"] <= tol)
+    return out
+
+
+def _project_arrays(m: int, F, mean, modes, transforms):
+    """(mean [m, 3], modes [k, 3m], transforms [F, 12] or None) as contiguous <f8, their shapes checked (F None: any number of frames)."""
+    mean = np.ascontiguousarray(mean, dtype="<f8")
+    if mean.shape != (m, 3):
+        raise ValueError(f"mean must have shape [{m}, 3] (the measured atoms), got {list(mean.shape)}")
+    modes = np.ascontiguousarray(modes, dtype="<f8")
+    if modes.ndim != 2 or modes.shape[1] != 3 * m:
+        raise ValueError(f"modes must have shape [k, {3 * m}] (atom-major rows over the measured atoms), got {list(modes.shape)}")
+    if transforms is not None:
+        transforms = np.ascontiguousarray(transforms, dtype="<f8")
+        if transforms.ndim != 2 or transforms.shape[1] != 12 or (F is not None and transforms.shape[0] != F):
+            raise ValueError(f"transforms must have shape [{'F' if F is None else F}, 12] (R row-major, then t), got {list(transforms.shape)}")
+    return mean, modes, transforms
+
+
+def _project(ctx: "Context | None", structure: Structure, frames, atoms, mean, modes, transforms):
+    """arp_project.  ctx None: the inputs are only checked."""
+    msel = rmsd_select(structure, atoms)
+    F = _rmsd_frames(structure, frames)
+    mean, modes, transforms = _project_arrays(len(msel), F, mean, modes, transforms)
+    n_frames, fptr, keep = _frames_arg(structure, frames, "project")
+    dp = C.POINTER(C.c_double)
+    arr = lambda a, t=dp: None if a is None else (a if a.size else np.zeros(1, a.dtype)).ctypes.data_as(t)
+    k = modes.shape[0]
+    head = (structure._h, int(n_frames), fptr, arr(msel, C.POINTER(C.c_uint32)), len(msel), arr(transforms), arr(mean), arr(modes), k)
+    if ctx is None:
+        _check(lib.arp_project(None, *head, None))
+        return None
+    out = np.zeros((F, k), "<f8")
+    _check(lib.arp_project(ctx._h, *head, arr(out)))
+    return out
+
+
+def pca_modes(covariance, n_modes: int = 10) -> dict:
+    """The host half of pca(): numpy.linalg.eigh of a symmetric [3m, 3m] matrix.  `eigenvalues` <f8 [3m], descending, raw (rounding may leave a small negative
+    one); `modes` <f8 [k, 3m], k = min(n_modes, 3m), unit rows, each with the sign that makes its largest-magnitude component positive (the lowest index
+    on ties); `explained` [k] = eigenvalue / trace and `cumulative` [k] its running sum (zeros when the trace is 0)."""
+    c = np.asarray(covariance, np.float64)
+    if c.ndim != 2 or c.shape[0] != c.shape[1] or c.shape[0] == 0:
+        raise ValueError(f"covariance must be a square matrix, got {list(c.shape)}")
+    if not isinstance(n_modes, (int, np.integer)) or int(n_modes) < 1:
+        raise ValueError(f"n_modes must be a positive integer, got {n_modes!r}")
+    k = min(int(n_modes), c.shape[0])
+    w, v = np.linalg.eigh(c)
+    w, v = w[::-1].copy(), v[:, ::-1]
+    modes = np.ascontiguousarray(v[:, :k].T, dtype="<f8")
+    top = np.argmax(np.abs(modes), axis=1)  # (the first of equal magnitudes)
+    modes[modes[np.arange(k), top] < 0.0] *= -1.0
+    total = float(np.trace(c))
+    explained = w[:k] / total if total > 0.0 else np.zeros(k)
+    return {"eigenvalues": w.astype("<f8"), "modes": modes, "explained": explained, "cumulative": np.cumsum(explained)}
+
+
+def _pca(ctx: "Context | None", structure: Structure, frames, fit, atoms, chains: str, reference, max_rounds, tol, n_modes):
+    if not isinstance(n_modes, (int, np.integer)) or int(n_modes) < 1:
+        raise ValueError(f"n_modes must be a positive integer, got {n_modes!r}")
+    out = _covariance(ctx, structure, frames, fit, atoms, chains, reference, max_rounds, tol, True, False, True)
+    if ctx is None:
+        return None
+    out.update(pca_modes(out["covariance"], n_modes))
+    out["projections"] = _project(ctx, structure, frames, out["atom"], out["mean"], out["modes"], out["transforms"])
+    return out
+
+
+def covariance_host(aligned, mean, cov: bool = True, dccm: bool = False) -> dict:
+    """arp_covariance_host: the definition of arp_covariance's `covariance` and `dccm` in plain sequential C++ on the CPU, from superposed coordinates
+    aligned [F, m, 3] and their mean [m, 3] (rmsf's `aligned` and `mean`).  The yardstick of the device call."""
+    a = np.ascontiguousarray(aligned, dtype="<f8")
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"aligned must have shape [F, m, 3], got {list(a.shape)}")
+    F, m = a.shape[:2]
+    mu = np.ascontiguousarray(mean, dtype="<f8")
+    if mu.shape != (m, 3):
+        raise ValueError(f"mean must have shape [{m}, 3], got {list(mu.shape)}")
+    out = {}
+    if cov:
+        out["covariance"] = np.zeros((3 * m, 3 * m), "<f8")
+    if dccm:
+        out["dccm"] = np.zeros((m, m), "<f4")
+    dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
+    arr = lambda x, t=dp: (x if x.size else np.zeros(1, x.dtype)).ctypes.data_as(t)
+    _check(lib.arp_covariance_host(F, m, arr(a), arr(mu), arr(out["covariance"]) if cov else None, arr(out["dccm"], fp) if dccm else None))
+    return out
+
+
+def project_host(xyz_msel, mean, modes, transforms=None) -> np.ndarray:
+    """arp_project_host: the definition of arp_project in plain sequential C++ on the CPU, on the measured atoms' absolute coordinates xyz_msel [F, m, 3]."""
+    x = np.ascontiguousarray(xyz_msel, dtype="<f8")
+    if x.ndim != 3 or x.shape[2] != 3:
+        raise ValueError(f"xyz_msel must have shape [F, m, 3], got {list(x.shape)}")
+    F, m = x.shape[:2]
+    mean, modes, transforms = _project_arrays(m, F, mean, modes, transforms)
+    k = modes.shape[0]
+    out = np.zeros((F, k), "<f8")
+    dp = C.POINTER(C.c_double)
+    arr = lambda a: None if a is None else (a if a.size else np.zeros(1, a.dtype)).ctypes.data_as(dp)
+    _check(lib.arp_project_host(F, m, arr(x), arr(transforms), arr(mean), arr(modes), k, arr(out)))
+    return out
+
+
+def get_covariance(structure: Structure, frames=None, fit="ca", atoms=None, chains: str = "", reference="mean", max_rounds: int = 50, tol: float = 1e-4, cov: bool = True,
+                   dccm: bool = False, transforms: bool = False, device: int = 0) -> dict:
+    """Which coordinates of an ensemble move together.  The frames are superposed exactly as get_rmsf superposes them (same arguments, same bytes) and, under
+    the last rotations, d = the measured atoms' superposed coordinates minus their mean.  Returns get_rmsf's keys (`atom`, `mean`, `rmsf`, `bfactor`,
+    `frame_rmsd`, `n_rounds`, `last_change`, `converged`, on request `transforms`) plus `covariance` <f8 [3m, 3m] (cov=True): (1 / F) sum_f d_a d_b with
+    the coordinate index a = 3 i + k, exactly symmetric, the trace of atom i's block = rmsf_i^2; and / or `dccm` <f4 [m, m] (dccm=True): see get_dccm."""
+    ctx = _with_context(device, lambda: _covariance(None, structure, frames, fit, atoms, chains, reference, max_rounds, tol, cov, dccm, transforms))
+    return ctx.covariance(structure, frames, fit, atoms, chains, reference, max_rounds, tol, cov, dccm, transforms)
+
+
+def get_dccm(structure: Structure, frames=None, fit="ca", atoms=None, chains: str = "", reference="mean", max_rounds: int = 50, tol: float = 1e-4, transforms: bool = False,
+             device: int = 0) -> dict:
+    """Which atoms of an ensemble move together: the dynamic cross-correlation map `dccm` <f4 [m, m], <d_i . d_j> / sqrt(<d_i^2> <d_j^2>) of the measured
+    atoms' deviations from their mean after get_rmsf's superposition: +1 the same direction, -1 opposite, 0 unrelated (or an atom that does not move); the
+    diagonal is exactly 1, the matrix exactly symmetric.  Residue-level maps: measure atoms="ca".  The other keys are get_rmsf's."""
+    ctx = _with_context(device, lambda: _covariance(None, structure, frames, fit, atoms, chains, reference, max_rounds, tol, False, True, transforms))
+    return ctx.dccm(structure, frames, fit, atoms, chains, reference, max_rounds, tol, transforms)
+
+
+def get_projection(structure: Structure, frames, atoms, mean, modes, transforms=None, device: int = 0) -> np.ndarray:
+    """Frames along given collective directions: <f8 [F, k], sum_a d_a modes[j, a] with d = R p + t - mean of the measured atoms (rmsd_select(structure,
+    atoms)).  transforms [F, 12] as get_rmsf(transforms=True) returns them; None: the frames are already superposed.  New frames, fitted to an old mean
+    structure with get_rmsf(reference=...), project onto old modes: no fit is repeated here."""
+    ctx = _with_context(device, lambda: _project(None, structure, frames, atoms, mean, modes, transforms))
+    return ctx.project(structure, frames, atoms, mean, modes, transforms)
+
+
+def get_pca(structure: Structure, frames=None, fit="ca", atoms=None, chains: str = "", reference="mean", max_rounds: int = 50, tol: float = 1e-4, n_modes: int = 10,
+            device: int = 0) -> dict:
+    """Along which few collective directions an ensemble moves (principal components, "essential dynamics").  The covariance is formed on the device
+    (get_covariance), its eigen-decomposition is numpy.linalg.eigh on the HOST -- O((3m)^3) on the CPU; its measured share of the call: 12 % at 76 atoms
+    x 10^4 frames, 81 - 88 % at 602 atoms x 10^4, 93 % at 1055 atoms x 10^3 --, and the frames are projected on the device (get_projection).  Keys: get_covariance's (with `covariance` and
+    `transforms`), `eigenvalues` <f8 [3m] descending, raw; `modes` <f8 [k, 3m], k = min(n_modes, 3m), unit rows, the sign fixed so that each mode's
+    largest-magnitude component is positive (lowest index on ties); `explained` and `cumulative` [k] (shares of the trace); `projections` <f8 [F, k]."""
+    ctx = _with_context(device, lambda: _pca(None, structure, frames, fit, atoms, chains, reference, max_rounds, tol, n_modes))
+    return ctx.pca(structure, frames, fit, atoms, chains, reference, max_rounds, tol, n_modes)
+
+
+def covariance(input_file: str, fit="ca", atoms=None, chains: str = "", reference="mean", max_rounds: int = 50, tol: float = 1e-4, cov: bool = True, dccm: bool = False,
+               transforms: bool = False, ignore_zero_occupancy: bool = False) -> dict:
+    """Covariance of the models of a multi-model file (the models are the frames): see get_covariance."""
+    return get_covariance(Structure.load(input_file, ignore_zero_occupancy), None, fit, atoms, chains, reference, max_rounds, tol, cov, dccm, transforms)
+
+
+def dccm(input_file: str, fit="ca", atoms=None, chains: str = "", reference="mean", max_rounds: int = 50, tol: float = 1e-4, transforms: bool = False,
+         ignore_zero_occupancy: bool = False) -> dict:
+    """DCCM of the models of a multi-model file: see get_dccm."""
+    return get_dccm(Structure.load(input_file, ignore_zero_occupancy), None, fit, atoms, chains, reference, max_rounds, tol, transforms)
+
+
+def pca(input_file: str, fit="ca", atoms=None, chains: str = "", reference="mean", max_rounds: int = 50, tol: float = 1e-4, n_modes: int = 10,
+        ignore_zero_occupancy: bool = False) -> dict:
+    """Principal components of the models of a multi-model file: see get_pca."""
+    return get_pca(Structure.load(input_file, ignore_zero_occupancy), None, fit, atoms, chains, reference, max_rounds, tol, n_modes)
+
+
+def dccm_table(structure: Structure, result: dict):
+    """The `dccm` of a result in long form, as a table of the contact table's type: one row per pair i < j of measured atoms, DCCM_COLUMNS -- the identity
+    columns of both atoms, then `correlation`."""
+    import pyarrow as pa
+
+    idx = np.asarray(result["atom"])
+    i, j = np.triu_indices(len(idx), 1)
+    cols = {f"from_{k}": v for k, v in _identity(structure, idx[i]).items()}
+    cols.update({f"to_{k}": v for k, v in _identity(structure, idx[j]).items()})
+    cols["correlation"] = pa.array(np.asarray(result["dccm"])[i, j], pa.float32())
+    return _frame({k: cols[k] for k in DCCM_COLUMNS})
 
 
 def _contact_clusters_arrow(input_file: str, groups: str, vdw_comp: float, dist_cutoff: float, ignore_zero_occupancy: bool, rings: bool, level: str, min_similarity: float,

@@ -185,33 +185,46 @@ extern "C" arp_status arp_rmsf_host(uint64_t n_frames, uint64_t n, uint64_t m, c
     return ARP_OK;
 } ARP_ABI_CATCH
 
+uint64_t arp::rmsf_resident_bytes(uint64_t F, uint64_t n_sel, uint64_t m, bool own_msel) {
+    return F * 3u * rmsd_n_pad(n_sel) * 8u + F * 8u + (own_msel ? F * 3u * rmsd_n_pad(m) * 8u : 0u);  // X, G and XM stay resident
+}
+
+arp_status arp::rmsf_check(const char *what, const arp_structure *s, uint64_t n_frames, const double *xyz, const uint32_t *sel, uint64_t n_sel, const uint32_t *msel, uint64_t n_msel,
+                           const double *ref_xyz, uint64_t ref_frame, uint32_t max_rounds, double tol, std::vector<double> *model_xyz, const double **frames, uint64_t *n0_out,
+                           uint64_t *F_out) {
+    arp_status st = rmsd_check(what, s, n_frames, xyz, sel, n_sel, model_xyz, frames, n0_out, F_out);
+    if (st != ARP_OK) return st;
+    const uint64_t n0 = *n0_out, F = *F_out;
+    if (msel) {
+        if (n_msel == 0) { set_error("%s: the measured selection is empty (n_msel == 0)", what); return ARP_ERR_BAD_INPUT; }
+        for (uint64_t i = 0; i < n_msel; i++) {
+            if (msel[i] >= n0) { set_error("%s: msel[%llu] = %u is not an atom of the topology (%llu atoms)", what, (unsigned long long)i, msel[i], (unsigned long long)n0); return ARP_ERR_BAD_INPUT; }
+            if (i && msel[i] <= msel[i - 1]) {
+                set_error("%s: msel is not strictly increasing at index %llu (%u after %u)", what, (unsigned long long)i, msel[i], msel[i - 1]);
+                return ARP_ERR_BAD_INPUT;
+            }
+        }
+    }
+    if ((st = rounds_check(what, max_rounds, tol)) != ARP_OK) return st;
+    if (!ref_xyz && ref_frame >= F) { set_error("%s: ref_frame %llu is not one of the %llu frames", what, (unsigned long long)ref_frame, (unsigned long long)F); return ARP_ERR_BAD_INPUT; }
+    if (ref_xyz)
+        for (uint64_t v = 0; v < n0 * 3; v++)
+            if (!std::isfinite(ref_xyz[v])) { set_error("%s: non-finite coordinate in ref_xyz, atom %llu", what, (unsigned long long)(v / 3)); return ARP_ERR_BAD_INPUT; }
+    return ARP_OK;
+}
+
 extern "C" arp_status arp_rmsf(arp_context *ctx, arp_structure *s, uint64_t n_frames, const double *xyz, const uint32_t *sel, uint64_t n_sel, const uint32_t *msel, uint64_t n_msel,
                                const double *ref_xyz, uint64_t ref_frame, uint32_t max_rounds, double tol, double *mean, float *rmsf, float *frame_rmsd, double *transforms,
                                double *aligned, uint32_t *n_rounds, double *last_change) try {
     std::vector<double> model_xyz;
     const double *frames = nullptr;
     uint64_t n0 = 0, F = 0;
-    arp_status st = rmsd_check("rmsf", s, n_frames, xyz, sel, n_sel, &model_xyz, &frames, &n0, &F);
+    arp_status st = rmsf_check("rmsf", s, n_frames, xyz, sel, n_sel, msel, n_msel, ref_xyz, ref_frame, max_rounds, tol, &model_xyz, &frames, &n0, &F);
     if (st != ARP_OK) return st;
-    if (msel) {
-        if (n_msel == 0) { set_error("rmsf: the measured selection is empty (n_msel == 0)"); return ARP_ERR_BAD_INPUT; }
-        for (uint64_t i = 0; i < n_msel; i++) {
-            if (msel[i] >= n0) { set_error("rmsf: msel[%llu] = %u is not an atom of the topology (%llu atoms)", (unsigned long long)i, msel[i], (unsigned long long)n0); return ARP_ERR_BAD_INPUT; }
-            if (i && msel[i] <= msel[i - 1]) {
-                set_error("rmsf: msel is not strictly increasing at index %llu (%u after %u)", (unsigned long long)i, msel[i], msel[i - 1]);
-                return ARP_ERR_BAD_INPUT;
-            }
-        }
-    }
-    if ((st = rounds_check("rmsf", max_rounds, tol)) != ARP_OK) return st;
-    if (!ref_xyz && ref_frame >= F) { set_error("rmsf: ref_frame %llu is not one of the %llu frames", (unsigned long long)ref_frame, (unsigned long long)F); return ARP_ERR_BAD_INPUT; }
-    if (ref_xyz)
-        for (uint64_t v = 0; v < n0 * 3; v++)
-            if (!std::isfinite(ref_xyz[v])) { set_error("rmsf: non-finite coordinate in ref_xyz, atom %llu", (unsigned long long)(v / 3)); return ARP_ERR_BAD_INPUT; }
     if (!ctx) return ARP_OK;  // validation only
     if (!mean || !rmsf || !frame_rmsd || !n_rounds || !last_change) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
     const uint64_t m = msel ? n_msel : n_sel;
-    const uint64_t need = F * 3u * rmsd_n_pad(n_sel) * 8u + F * 8u + (msel ? F * 3u * rmsd_n_pad(m) * 8u : 0u);  // X, G and XM stay resident
+    const uint64_t need = rmsf_resident_bytes(F, n_sel, m, msel != nullptr);
     if (need > rmsd_cap()) {
         set_error("rmsf: the packed coordinates of %llu frames (F) x %llu fit atoms (n) and %llu measured atoms (m) need %llu bytes, the limit is %llu (rmsd_cap_bytes)",
                   (unsigned long long)F, (unsigned long long)n_sel, (unsigned long long)m, (unsigned long long)need, (unsigned long long)rmsd_cap());

@@ -235,6 +235,8 @@ __global__ __launch_bounds__(256) void k_rmsf_aligned(const double *__restrict__
     for (int k = 0; k < 3; k++) out[idx * 3u + k] = ((r[3 * k] * x0 + r[3 * k + 1] * x1) + r[3 * k + 2] * x2) + c_t[k];
 }
 
+arp_status device_cov(hipStream_t st, StreamLapTimer &lap, const double *XM, const double *R, const double *mean_m, uint64_t F, uint64_t m, uint64_t m_pad, RmsfOut *out);  // cov.inl
+
 // The call on the device.  Upload and pack as device_rmsd does; X, XM, C and the rotations stay resident.  Then the rounds -- fit, sweep, finish, change, one
 // 8-byte read-back -- the measured atoms' mean and deviations under the last rotations, and the downloads; aligned goes through the staging buffer in the
 // upload passes' sizes.  The capacity checks ran on the host (rmsf.cpp) before this is called.
@@ -316,6 +318,10 @@ arp_status device_rmsf(arp_context *ctx, const RmsfJob &job, RmsfOut *out) {
     hipLaunchKernelGGL(k_rmsf_frame, per_frame, dim3(256), 0, st, (const double *)X, (const double *)R, (const double *)M, (uint32_t)F, (uint32_t)n, (uint32_t)n_pad, d_frame);
     HIP_TRY(hipGetLastError());
     lap("deviation");
+    if (out->cov || out->dccm) {  // arp_covariance: the second moments of the same deviations (cov.inl)
+        const arp_status cs = device_cov(st, lap, XM, R, mean_m, F, m, m_pad, out);
+        if (cs != ARP_OK) return cs;
+    }
     std::vector<double> h_mean(3u * m_pad), h_c(F * 3u), h_r(out->transforms ? F * 9u : 0u);
     double h_ct[3];
     HIP_TRY(hipMemcpyAsync(h_mean.data(), mean_m, 3u * m_pad * 8u, hipMemcpyDeviceToHost, st));

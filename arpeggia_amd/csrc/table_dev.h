@@ -1,6 +1,7 @@
 // Device side of the contact table (SURVEY.md 8f rows f1 + f2): plane fits, ring rows, row expansion, the 10-key sort and the
 // side-chain plane statistics run as HIP kernels (table_dev.hip); table_cache.cpp keeps the bookkeeping (entity lists, strings).
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <memory>
 #include <string>
@@ -214,10 +215,56 @@ struct RmsfOut {
     float *frame_rmsd = nullptr;   // [F]
     double *transforms = nullptr;  // [F][12], nullable
     double *aligned = nullptr;     // [F][m][3], nullable
+    double *cov = nullptr;         // [3 m][3 m], nullable: arp_covariance (cov.inl, behind the deviations of the same pipeline)
+    float *dccm = nullptr;         // [m][m], nullable: arp_covariance
     uint32_t n_rounds = 0;
     double last_change = 0.0;
 };
 arp_status device_rmsf(arp_context *ctx, const RmsfJob &job, RmsfOut *out);
+// rmsf.cpp: what arp_rmsf and arp_covariance check before the device is touched, under the prefix `what`: the checks of the arp_rmsd_* calls, then the
+// measured selection, the rounds and the reference
+arp_status rmsf_check(const char *what, const arp_structure *s, uint64_t n_frames, const double *xyz, const uint32_t *sel, uint64_t n_sel, const uint32_t *msel, uint64_t n_msel,
+                      const double *ref_xyz, uint64_t ref_frame, uint32_t max_rounds, double tol, std::vector<double> *model_xyz, const double **frames, uint64_t *n0_out, uint64_t *F_out);
+// rmsf.cpp: the bytes of arp_rmsf's resident state (X, G and, with a measured set of its own, XM) that "rmsd_cap_bytes" limits
+uint64_t rmsf_resident_bytes(uint64_t F, uint64_t n_sel, uint64_t m, bool own_msel);
+
+// Covariance, DCCM and projection (cov.inl, arp_covariance / arp_project).  The Gram kernel walks 32 x 32 tiles of the upper triangle of
+// an L x L product (L = 3 m_pad coordinates, or m_pad atoms for the DCCM) and splits the frames into slabs so that a small triangle still fills the chip:
+// about kCovGridTarget workgroups, a slab never shorter than kCovSlabMin frames and always whole chunks.  The plan is a function of (F, L) alone.
+constexpr uint32_t kCovTile = 32;           // coordinates of a workgroup tile edge: 2 x 2 waves of 16 x 16
+constexpr uint32_t kCovChunk = 16;          // contraction rows staged through LDS per step of the tile loop
+constexpr uint32_t kCovSlabMin = 64;        // frames of the shortest slab
+constexpr uint32_t kCovGridTarget = 1024;   // workgroups wanted: four per CU of the 256
+struct CovPlan {
+    uint64_t L = 0, T = 0, tri = 0, slab_frames = 0, slabs = 0;
+    uint64_t part_items() const { return slabs * tri * kCovTile * kCovTile; }  // doubles of partial[slab][tile][32][32]
+};
+inline CovPlan cov_plan(uint64_t F, uint64_t L) {
+    CovPlan p;
+    p.L = L;
+    p.T = (L + kCovTile - 1u) / kCovTile;
+    p.tri = p.T * (p.T + 1u) / 2u;
+    const uint64_t want = (kCovGridTarget + p.tri - 1u) / p.tri, per = (F + want - 1u) / want;
+    p.slab_frames = std::max<uint64_t>(kCovSlabMin, (per + kCovChunk - 1u) / kCovChunk * kCovChunk);
+    p.slabs = (F + p.slab_frames - 1u) / p.slab_frames;
+    return p;
+}
+// what arp_covariance adds to arp_rmsf's resident bytes: the deviations, the requested outputs at their padded sizes and the slab partials
+inline uint64_t cov_extra_bytes(uint64_t F, uint64_t m, bool cov, bool dccm) {
+    const uint64_t m_pad = rmsd_n_pad(m);
+    return F * 3u * m_pad * 8u + (cov ? 9u * m_pad * m_pad * 8u : 0u) + (dccm ? m_pad * m_pad * 4u : 0u) +
+           std::max(cov ? cov_plan(F, 3u * m_pad).part_items() : 0u, dccm ? cov_plan(F, m_pad).part_items() : 0u) * 8u;
+}
+struct ProjectJob {
+    uint64_t n_atoms = 0, n_frames = 0, n_msel = 0, k = 0;
+    const double *xyz = nullptr;         // [F][N][3]
+    const uint32_t *msel = nullptr;      // [m]
+    uint64_t chunk_atoms = 0;            // atoms per upload pass, 0 = automatic (arp_debug_set "rmsd_chunk_atoms")
+    const double *transforms = nullptr;  // [F][12], nullable: identity
+    const double *mean = nullptr;        // [m][3]
+    const double *modes = nullptr;       // [k][3 m]
+};
+arp_status device_project(arp_context *ctx, const ProjectJob &job, double *proj);
 
 // engine.cpp: the context's stream / device and grow-only scratch (device and pinned host)
 void *context_stream(arp_context *ctx);

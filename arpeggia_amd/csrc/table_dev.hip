@@ -1027,5 +1027,6 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
 #include "cluster.inl"
 #include "rmsd.inl"
 #include "rmsf.inl"
+#include "cov.inl"
 
 }  // namespace arp

@@ -873,6 +873,45 @@ arp_status arp_rmsf_host(uint64_t n_frames, uint64_t n, uint64_t m, const double
                          uint32_t max_rounds, double tol, double *mean, float *rmsf, float *frame_rmsd, double *transforms, double *aligned, uint32_t *n_rounds,
                          double *last_change);
 
+/* ---- Covariance, DCCM and principal components of an ensemble's motions -- DESIGN.md section 3.22 ----
+ * Which atoms move together, and along which collective directions: the second moments of the superposed coordinates.  Frames, topology, sel[n] (the fit
+ * atoms), msel[m] (the measured atoms; NULL: the fit atoms), ref_xyz / ref_frame, max_rounds and tol mean exactly what they mean for arp_rmsf, and the
+ * superposition is that call's.  Under its last rotations, for the measured atoms: Y_f,i = R_f x_f,i, mean_i their mean over the frames, and
+ *   d_f,a = Y_f,i,k - mean_i,k      with the coordinate index a = 3 i + k (atom-major; k = x, y, z).
+ * Outputs:
+ *   cov[3 m][3 m]  f64 row-major, may be NULL: cov[a][b] = (1 / F) sum_f d_f,a d_f,b.  The divisor is F, as in rmsf, so the trace of atom i's 3 x 3 block is
+ *                  rmsf_i^2.  cov[a][b] and cov[b][a] are the same bits: the mirror is written from the same value.
+ *   dccm[m][m]     f32 row-major, may be NULL: t_ij = (1 / F) sum_f sum_k d_f,(i,k) d_f,(j,k), v_i = t_ii, dccm[i][j] = clamp(t_ij / sqrt(v_i v_j), -1, 1),
+ *                  formed in f64 and rounded once to f32.  The diagonal is written 1.0f, never computed; an off-diagonal entry with v_i == 0 or v_j == 0 is
+ *                  0.0f; the matrix is symmetric in its bits, and its bytes do not depend on whether cov is asked for.
+ *   mean, rmsf, frame_rmsd, transforms (may be NULL), *n_rounds, *last_change: arp_rmsf's, byte for byte.  (aligned is not offered here.)
+ * Checks, all before the device is touched, ARP_ERR_BAD_INPUT: those of arp_rmsf under the prefix "covariance".  ctx == NULL runs only those checks
+ * (ARP_OK); with a context, cov == NULL and dccm == NULL together are ARP_ERR_BAD_INPUT.
+ * Device memory, checked against "rmsd_cap_bytes" before anything is allocated: what arp_rmsf keeps resident, the deviations F x 3 x m_pad x 8 bytes, the
+ * requested outputs at their padded sizes (3 m_pad)^2 x 8 and m_pad^2 x 4, and the partial sums of the frame slabs: ARP_ERR_CAPACITY with a message that
+ * names F, m and the bytes.  No floating-point atomic is used; the frames are summed in slabs whose count is a function of (F, m) alone, in a fixed order: two
+ * calls give identical bytes, whatever the pass size ("rmsd_chunk_atoms").  Synchronous.
+ * The eigen-decomposition of cov (principal components, "essential dynamics") is left to the caller; the Python layer's pca uses LAPACK on the host. */
+arp_status arp_covariance(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const uint32_t *sel, uint64_t n_sel, const uint32_t *msel,
+                          uint64_t n_msel, const double *ref_xyz, uint64_t ref_frame, uint32_t max_rounds, double tol, double *cov, float *dccm, double *mean, float *rmsf,
+                          float *frame_rmsd, double *transforms, uint32_t *n_rounds, double *last_change);
+/* Projection of frames onto given directions: proj[F][k] f64, proj[f][j] = sum_a d_f,a V[j][a] in the order of a, for the caller's modes V[k][3 m] (f64,
+ * atom-major rows, not required to be orthonormal), with d_f,(i,.) = R_f p_f,i + t_f - mean_i formed from the ABSOLUTE coordinates p of the measured atoms
+ * msel[m] (strictly increasing, required), the caller's transforms[F][12] (R row-major, then t, as arp_rmsf returns them; NULL: the identity -- the frames are
+ * already superposed) and mean[m][3].  No fit is repeated: new frames, once arp_rmsf has fitted them to the mean structure, project onto old modes.
+ * Frames and topology as for arp_rmsf; they are uploaded in the same passes ("rmsd_chunk_atoms") and each pass is projected where it is staged.
+ * Checks, all before the device is touched, ARP_ERR_BAD_INPUT: the frame checks of the arp_rmsd_* calls and their selection checks on msel (prefix "project");
+ * k == 0; k > 3 m; a non-finite mean, modes or transforms.  ctx == NULL runs only the checks.  The transforms, the modes and the projections are checked
+ * against "rmsd_cap_bytes": ARP_ERR_CAPACITY (the staging buffer of one upload pass, which "rmsd_chunk_atoms" sizes, is not counted, as in the arp_rmsd_* calls).  Plain f64 multiply-adds, one sum per projection: identical bytes for any pass size. */
+arp_status arp_project(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const uint32_t *msel, uint64_t n_msel, const double *transforms,
+                       const double *mean, const double *modes, uint64_t k, double *proj);
+/* The two definitions above in plain sequential C++, without a device, every sum in the order of its index.  arp_covariance_host: aligned n_frames x m x 3
+ * (superposed coordinates, as arp_rmsf's aligned) and mean m x 3 give d = aligned - mean; cov and dccm as above, each may be NULL, not both.
+ * arp_project_host: xyz_msel n_frames x m x 3 are the absolute coordinates of the measured atoms; transforms may be NULL.  n_frames or m == 0, k == 0,
+ * k > 3 m and a non-finite value are ARP_ERR_BAD_INPUT.  The CPU yardsticks of the device kernels: they agree within the rounding of the sums. */
+arp_status arp_covariance_host(uint64_t n_frames, uint64_t m, const double *aligned, const double *mean, double *cov, float *dccm);
+arp_status arp_project_host(uint64_t n_frames, uint64_t m, const double *xyz_msel, const double *transforms, const double *mean, const double *modes, uint64_t k, double *proj);
+
 /* ---- SASA and SAP statistics over the frames of an ensemble (MD snapshots, NMR models, conformers of one topology) -- DESIGN.md section 3.8 ----
  * Topology, N, frames and xyz exactly as arp_contact_frequencies defines them: model 0 of `topology` is the topology, frame f is xyz[f]
  * (n_frames x N x 3 f64, host, C order); xyz == NULL: the structure's models are the frames, with the same one-for-one model check and its error.
