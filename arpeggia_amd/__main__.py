@@ -23,6 +23,9 @@ model's rmsd to the mean; --aligned FILE.npy: the superposed coordinates.
 `dccm` and `pca` (no counterpart either) take `rmsf`'s --fit, --atoms, -c, --reference, --max-rounds and --tol: `dccm` writes the dynamic cross-correlation map of
 the measured atoms to --matrix FILE.npy and, with -o (and -f, -t), in long form; `pca` takes --modes K and writes --eigenvalues FILE.csv, --modes-file FILE.npy,
 --projections FILE.csv and --covariance FILE.npy (the eigen-solve runs on the host).
+`secondary-structure` (no counterpart either) assigns DSSP states (Kabsch & Sander) to the residues of the chains -c in every model and writes, with -o (and -f,
+-t), per residue the share of the models in each state and the consensus state; --codes FILE.npy: the codes, uint8 [models, residues]; --strings FILE.txt: one line
+of "-HBEGITS" characters per model.
 `sasa-ensemble` and `sap-ensemble` (no counterpart either) take the flags and defaults of `sasa` / `sap` without --model: statistics over the models.
 `dsasa --level atom|residue` writes the interface row by row (default `total`: the reference's scalar); `dsasa-ensemble` takes the flags of
 `sasa-ensemble` and -g: dSASA per model and the per-atom statistics of the buried surface.
@@ -202,6 +205,16 @@ def build_parser() -> argparse.ArgumentParser:
             cv.add_argument("--modes-file", default=None, type=Path, metavar="FILE.npy", help="Write the modes: float64 [K, 3 atoms], atom-major rows")
             cv.add_argument("--projections", default=None, type=Path, metavar="FILE.csv", help="Write one line per model: frame, pc1 .. pcK")
             cv.add_argument("--covariance", default=None, type=Path, metavar="FILE.npy", help="Write the covariance matrix: float64 [3 atoms, 3 atoms]")
+    ss = sub.add_parser("secondary-structure", help="where the helices and strands are: DSSP states of every residue in every model, and each residue's share of the "
+                                                    "models in every state")
+    ss.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file whose models are the frames")
+    ss.add_argument("-c", "--chains", default="", help="Comma-separated chain IDs to include (empty: all)")
+    ss.add_argument("-o", "--output", default=None, type=Path, help="Output directory of the per-residue table")
+    ss.add_argument("-f", "--filename", default="secondary_structure", help="Name of the per-residue table")
+    ss.add_argument("-t", "--output-format", default="csv", type=str.lower, choices=FORMATS, help="Output file type of the per-residue table")
+    ss.add_argument("--codes", default=None, type=Path, metavar="FILE.npy", help="Write the codes (indices into '-HBEGITS'): uint8 [models, residues]")
+    ss.add_argument("--strings", default=None, type=Path, metavar="FILE.txt", help="Write one line per model: the states of its residues as '-HBEGITS' characters")
+    ss.add_argument("--ignore-zero-occupancy", action="store_true", help="Ignore atoms with zero occupancy")
     common = dict(model=("-m", "--model", 0, int, "Model number to analyze (0: the first model)"),
                   probe=("-r", "--probe-radius", 1.4, float, "Probe radius in Angstroms"),
                   points=("-n", "--num-points", 100, int, "Number of points for surface calculation"),
@@ -725,6 +738,36 @@ def run_dccm(args) -> int:
     return 0
 
 
+def run_secondary_structure(args) -> int:
+    import arpeggia_amd as aa
+
+    if not args.input.exists():
+        log.error("Failed to retrieve input file: %s", args.input)
+        return 1
+    if args.output is None and args.codes is None and args.strings is None:
+        log.error("Secondary structure: nothing to write, give -o DIR, --codes FILE.npy and / or --strings FILE.txt")
+        return 1
+    try:
+        structure = aa.Structure.load(str(args.input.resolve()), args.ignore_zero_occupancy)
+        res = aa.get_secondary_structure(structure, None, args.chains)
+    except (aa.ArpeggiaError, ValueError) as e:
+        log.error("Secondary structure failed: %s", e)
+        return 1
+    if args.output is not None:
+        args.output.mkdir(parents=True, exist_ok=True)
+        out = (args.output / args.filename).with_suffix("." + args.output_format)
+        write_table(aa.secondary_structure_table(structure, res), out, args.output_format)
+    if args.codes is not None:
+        _save_npy(args.codes, res["codes"])
+    if args.strings is not None:
+        args.strings.parent.mkdir(parents=True, exist_ok=True)
+        with open(args.strings, "w") as f:
+            for row in res["codes"]:
+                f.write(aa.ss_string(row) + "\n")
+    log.info("Secondary structure of %d residues over %d models saved", len(res["residue"]), len(res["frame_counts"]))
+    return 0
+
+
 def run_pca(args) -> int:
     import arpeggia_amd as aa
 
@@ -819,6 +862,8 @@ def main(argv=None) -> int:
         return run_rmsf(args)
     if args.command == "dccm":
         return run_dccm(args)
+    if args.command == "secondary-structure":
+        return run_secondary_structure(args)
     if args.command == "pca":
         return run_pca(args)
     if args.command == "sc":

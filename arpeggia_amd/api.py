@@ -470,6 +470,11 @@ class Context:
         is not on the device), project() on the device.  See get_pca for the keys."""
         return _pca(self, structure, frames, fit, atoms, chains, reference, max_rounds, tol, n_modes)
 
+    def secondary_structure(self, structure: Structure, frames=None, chains: str = "", codes: bool = True, hbonds: bool = False) -> dict:
+        """arp_dssp as a dict: the secondary structure (Kabsch & Sander) of every frame and each residue's share of the frames in every state -- `residue`,
+        `counts`, `fraction`, `frame_counts`, with codes=True `codes`, with hbonds=True `hb_acceptor` and `hb_energy` (get_secondary_structure)."""
+        return _secondary_structure(self, structure, frames, chains, codes, hbonds)
+
     def sc_ensemble(self, structure: Structure, frames=None, groups: str = "/") -> dict:
         """arp_structure_sc_ensemble as a dict: shape complementarity of every frame of an ensemble (the selection and radii of get_sc on model 0).
         frames: [F, N, 3] f64 coordinates of the N atoms of model 0; None: the structure's models.  Keys: atoms (u32 structure indices of the m
@@ -1817,6 +1822,132 @@ def dccm_table(structure: Structure, result: dict):
     cols.update({f"to_{k}": v for k, v in _identity(structure, idx[j]).items()})
     cols["correlation"] = pa.array(np.asarray(result["dccm"])[i, j], pa.float32())
     return _frame({k: cols[k] for k in DCCM_COLUMNS})
+
+
+# ---- Secondary structure (DSSP, Kabsch & Sander 1983) per frame and across the frames of an ensemble (arp_dssp) ----
+SS_CODES = "-HBEGITS"   # code k of every output is SS_CODES[k]: loop, alpha helix, isolated bridge, strand, 3-10 helix, pi helix, turn, bend
+DSSP_CHAIN_START, DSSP_NO_H = 1, 2
+SS_COLUMNS = ["chain", "resn", "resi", "insertion"] + [f"frac_{c}" for c in ("loop", "H", "B", "E", "G", "I", "T", "S")] + ["consensus"]
+
+
+def backbone_select(structure: Structure, chains: str = "") -> dict:
+    """The residues arp_dssp works on: the residues of model 0 in file order (a residue: a maximal run of atoms with the same chain, resi and insertion code),
+    HOH left out, restricted to the comma list `chains` ("" = every chain), and only those with all of N, CA, C, O -- the first atom of each name, so an
+    altloc after the first is ignored; a residue without one of the four is dropped (the gap it leaves is a chain break by geometry).  Returns `atom` <u4 [R]
+    (each residue's first atom), `bb` <u4 [R, 4] (the topology indices of N, CA, C, O) and `flags` u1 [R] (bit 0 DSSP_CHAIN_START: the first residue, or another
+    chain than the residue before; bit 1 DSSP_NO_H: residue name PRO)."""
+    n = _topology_atoms(structure)
+    name, resn, chain, ins = (structure.strings(k)[:n] for k in ("atomn", "resn", "chain", "insertion"))
+    resi = structure.ints("resi")[:n]
+    if n == 0:
+        return {"atom": np.zeros(0, "<u4"), "bb": np.zeros((0, 4), "<u4"), "flags": np.zeros(0, "u1")}
+    new = np.ones(n, bool)
+    new[1:] = (chain[1:] != chain[:-1]) | (resi[1:] != resi[:-1]) | (ins[1:] != ins[:-1])
+    run = np.cumsum(new) - 1
+    first = np.flatnonzero(new)
+    keep = resn[first] != b"HOH"
+    wanted = [c.strip().encode() for c in chains.split(",") if c.strip()]
+    if wanted:
+        keep &= np.isin(chain[first], wanted)
+    bb = np.zeros((len(first), 4), np.int64)
+    for k, atom_name in enumerate((b"N", b"CA", b"C", b"O")):
+        idx = np.flatnonzero(name == atom_name)
+        runs, at = np.unique(run[idx], return_index=True)   # the first atom of that name in every run that has one
+        has = np.zeros(len(first), bool)
+        has[runs] = True
+        bb[runs, k] = idx[at]
+        keep &= has
+    rows = np.flatnonzero(keep)
+    atom, ch = first[rows], chain[first[rows]]
+    flags = np.where(resn[atom] == b"PRO", DSSP_NO_H, 0).astype("u1")
+    if len(rows):
+        flags[0] |= DSSP_CHAIN_START
+        flags[1:][ch[1:] != ch[:-1]] |= DSSP_CHAIN_START
+    return {"atom": atom.astype("<u4"), "bb": np.ascontiguousarray(bb[rows], "<u4"), "flags": flags}
+
+
+def _secondary_structure(ctx: "Context | None", structure: Structure, frames, chains: str, codes: bool, hbonds: bool):
+    """arp_dssp.  ctx None: the inputs are only checked (raises their error, else returns None)."""
+    sel = backbone_select(structure, chains)
+    R = len(sel["atom"])
+    n_frames, ptr, keep = _frames_arg(structure, frames, "dssp")
+    u8p, u32p, fp = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_float)
+    arr = lambda a, t: (a if a.size else np.zeros(1, a.dtype)).ctypes.data_as(t)
+    head = (structure._h, int(n_frames), ptr, arr(sel["bb"], u32p), arr(sel["flags"], u8p), R)
+    if ctx is None:
+        _check(lib.arp_dssp(None, *head, *([None] * 5)))
+        return None
+    F = _rmsd_frames(structure, frames)
+    out = {"residue": sel["atom"], "counts": np.zeros((R, 8), "<u4"), "frame_counts": np.zeros((F, 8), "<u4")}
+    if codes:
+        out["codes"] = np.zeros((F, R), "u1")
+    if hbonds:
+        out["hb_acceptor"], out["hb_energy"] = np.zeros((F, R, 2), "<u4"), np.zeros((F, R, 2), "<f4")
+    ptr_of = lambda key, t: arr(out[key], t) if key in out else None
+    _check(lib.arp_dssp(ctx._h, *head, ptr_of("codes", u8p), ptr_of("counts", u32p), ptr_of("frame_counts", u32p), ptr_of("hb_acceptor", u32p), ptr_of("hb_energy", fp)))
+    out["fraction"] = (out["counts"].astype(np.float64) / F).astype("<f4")
+    return out
+
+
+def secondary_structure_host(bb_xyz, flags, codes: bool = True, hbonds: bool = True) -> dict:
+    """arp_dssp_host: the definition of arp_dssp in plain sequential C++ on the CPU, on already-gathered coordinates bb_xyz [F, R, 4, 3] (N, CA, C, O of every
+    residue) and flags [R].  The yardstick of the device call.  Keys: counts, frame_counts and, on request, codes, hb_acceptor and hb_energy."""
+    x = np.ascontiguousarray(bb_xyz, dtype="<f8")
+    if x.ndim != 4 or x.shape[2:] != (4, 3):
+        raise ValueError(f"bb_xyz must have shape [F, R, 4, 3], got {list(x.shape)}")
+    F, R = x.shape[:2]
+    fl = np.ascontiguousarray(flags, dtype="u1")
+    if fl.shape != (R,):
+        raise ValueError(f"flags must have shape [{R}], got {list(fl.shape)}")
+    u8p, u32p, fp, dp = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_double)
+    arr = lambda a, t: (a if a.size else np.zeros(1, a.dtype)).ctypes.data_as(t)
+    out = {"counts": np.zeros((R, 8), "<u4"), "frame_counts": np.zeros((F, 8), "<u4")}
+    if codes:
+        out["codes"] = np.zeros((F, R), "u1")
+    if hbonds:
+        out["hb_acceptor"], out["hb_energy"] = np.zeros((F, R, 2), "<u4"), np.zeros((F, R, 2), "<f4")
+    ptr_of = lambda key, t: arr(out[key], t) if key in out else None
+    _check(lib.arp_dssp_host(F, R, arr(x, dp), arr(fl, u8p), ptr_of("codes", u8p), arr(out["counts"], u32p), arr(out["frame_counts"], u32p), ptr_of("hb_acceptor", u32p),
+                             ptr_of("hb_energy", fp)))
+    return out
+
+
+def ss_string(codes_row) -> str:
+    """One row of `codes` as a string over SS_CODES ("-HBEGITS")."""
+    return "".join(SS_CODES[int(c)] for c in np.asarray(codes_row).ravel())
+
+
+def get_secondary_structure(structure: Structure, frames=None, chains: str = "", codes: bool = True, hbonds: bool = False, device: int = 0) -> dict:
+    """Where the helices and strands are, and in what share of the frames: DSSP (Kabsch & Sander 1983) on the residues of backbone_select(structure, chains),
+    for every frame of an ensemble.  Returns a dict: `residue` <u4 [R] (the first atom of every residue), `counts` <u4 [R, 8] (in how many frames the residue
+    has each code of SS_CODES), `fraction` <f4 [R, 8] = counts / F, `frame_counts` <u4 [F, 8]; codes=True: `codes` u1 [F, R]; hbonds=True: `hb_acceptor` <u4
+    [F, R, 2] (row indices of each donor's two best acceptors, 0xFFFFFFFF: none) and `hb_energy` <f4 [F, R, 2] (kcal/mol).  Departures from mkdssp: energies are
+    not rounded to three decimals, ladders are not linked across beta bulges, and G is assigned before I.  frames: [F, N, 3] f64; None: the structure's models."""
+    ctx = _with_context(device, lambda: _secondary_structure(None, structure, frames, chains, codes, hbonds))
+    return ctx.secondary_structure(structure, frames, chains, codes, hbonds)
+
+
+def secondary_structure(input_file: str, chains: str = "", codes: bool = True, hbonds: bool = False, ignore_zero_occupancy: bool = False) -> dict:
+    """Secondary structure of the models of a file (the models are the frames; one model: one frame): see get_secondary_structure."""
+    return get_secondary_structure(Structure.load(input_file, ignore_zero_occupancy), None, chains, codes, hbonds)
+
+
+def ss_consensus(counts) -> np.ndarray:
+    """u1 [R]: the most frequent code of every residue, the lower code on ties."""
+    return np.argmax(np.asarray(counts), axis=1).astype("u1")
+
+
+def secondary_structure_table(structure: Structure, result: dict):
+    """The result of a secondary-structure call as a table of the contact table's type, one row per residue: SS_COLUMNS -- chain, resn, resi, insertion, the
+    eight fractions and `consensus`, the most frequent code as a character (the lower code on ties)."""
+    import pyarrow as pa
+
+    ident = _identity(structure, np.asarray(result["residue"]))
+    cols = {k: ident[k] for k in ("chain", "resn", "resi", "insertion")}
+    for k, name in enumerate(SS_COLUMNS[4:12]):
+        cols[name] = pa.array(np.asarray(result["fraction"])[:, k], pa.float32())
+    cols["consensus"] = pa.array([SS_CODES[int(c)] for c in ss_consensus(result["counts"])], pa.string())
+    return _frame({k: cols[k] for k in SS_COLUMNS})
 
 
 def _contact_clusters_arrow(input_file: str, groups: str, vdw_comp: float, dist_cutoff: float, ignore_zero_occupancy: bool, rings: bool, level: str, min_similarity: float,

@@ -41,10 +41,9 @@ double jacobi_top(double a[4][4]) {
 namespace arp {
 uint64_t rmsd_cap() { return g_debug.rmsd_cap_bytes > 0 ? (uint64_t)g_debug.rmsd_cap_bytes : (1ull << 31); }
 
-// What the three device calls check before the device is touched: the frame checks of the frequency call with its statuses and messages, then the
-// selection.  *frames: the coordinates (xyz, or the models' in `model_xyz`), *n0: the topology's atoms, *F: the frames.
-arp_status rmsd_check(const char *what, const arp_structure *s, uint64_t n_frames, const double *xyz, const uint32_t *sel, uint64_t n_sel, std::vector<double> *model_xyz,
-                      const double **frames, uint64_t *n0_out, uint64_t *F_out) {
+// The frame checks of the frequency call with its statuses and messages.  *frames: the coordinates (xyz, or the models' in `model_xyz`), *n0: the topology's
+// atoms, *F: the frames.  (arp_dssp, which takes no selection, stops here.)
+arp_status rmsd_frames_check(const arp_structure *s, uint64_t n_frames, const double *xyz, std::vector<double> *model_xyz, const double **frames, uint64_t *n0_out, uint64_t *F_out) {
     if (!s) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
     uint64_t n0 = 0, r0 = 0, nm = 1;
     arp_status st = freq_topology(s, xyz == nullptr, &n0, &r0, &nm);
@@ -64,6 +63,16 @@ arp_status rmsd_check(const char *what, const arp_structure *s, uint64_t n_frame
             set_error("contact frequencies: non-finite coordinate in frame %llu, atom %llu", (unsigned long long)(v / (3 * n0)), (unsigned long long)(v / 3 % n0));
             return ARP_ERR_BAD_INPUT;
         }
+    *frames = xyz; *n0_out = n0; *F_out = F;
+    return ARP_OK;
+}
+
+// What the three device calls check before the device is touched: the frame checks, then the selection.
+arp_status rmsd_check(const char *what, const arp_structure *s, uint64_t n_frames, const double *xyz, const uint32_t *sel, uint64_t n_sel, std::vector<double> *model_xyz,
+                      const double **frames, uint64_t *n0_out, uint64_t *F_out) {
+    const arp_status st = rmsd_frames_check(s, n_frames, xyz, model_xyz, frames, n0_out, F_out);
+    if (st != ARP_OK) return st;
+    const uint64_t n0 = *n0_out, F = *F_out;
     if (n_sel == 0) { set_error("%s: the selection is empty (n_sel == 0)", what); return ARP_ERR_BAD_INPUT; }
     if (!sel) { set_error("null argument"); return ARP_ERR_BAD_INPUT; }
     for (uint64_t i = 0; i < n_sel; i++) {
@@ -74,7 +83,6 @@ arp_status rmsd_check(const char *what, const arp_structure *s, uint64_t n_frame
         }
     }
     if (F >= (1ull << 32)) { set_error("%s: 2^32 or more frames", what); return ARP_ERR_BAD_INPUT; }
-    *frames = xyz; *n0_out = n0; *F_out = F;
     return ARP_OK;
 }
 

@@ -266,6 +266,34 @@ struct ProjectJob {
 };
 arp_status device_project(arp_context *ctx, const ProjectJob &job, double *proj);
 
+// Secondary structure (dssp.inl, arp_dssp).  The constants of the definition, written once: the host twin (dssp.cpp) and the kernels
+// read these.
+constexpr double kDsspCos70 = 0.3420201433256687;  // cos 70 deg: a bend where cos kappa is below it
+constexpr double kDsspBreak = 2.5;                 // A: |C[r-1] - N[r]| above it breaks the chain
+constexpr double kDsspCaCut = 9.0;                 // A: pairs with |CA - CA| below it get an energy
+constexpr double kDsspMinDist = 0.5;               // A: a distance below it gives kDsspMinEnergy
+constexpr double kDsspMinEnergy = -9.9;
+constexpr double kDsspCoupling = 27.888;           // kcal A / mol: 332 x 0.42 x 0.20
+constexpr double kDsspHbond = -0.5;                // kcal / mol: a bond where E is below it
+constexpr uint64_t kDsspMaxRes = 1ull << 28;
+struct DsspJob {
+    uint64_t n_atoms = 0, n_frames = 0, n_res = 0;
+    const double *xyz = nullptr;     // [F][N][3]
+    const uint32_t *bb = nullptr;    // [R][4]: N, CA, C, O
+    const uint8_t *flags = nullptr;  // [R]
+    uint64_t chunk_atoms = 0;        // atoms per upload pass, 0 = automatic (arp_debug_set "rmsd_chunk_atoms")
+};
+struct DsspOut {
+    uint8_t *codes = nullptr;         // [F][R], nullable
+    uint32_t *counts = nullptr;       // [R][8]
+    uint32_t *frame_counts = nullptr; // [F][8], nullable
+    uint32_t *hb_acceptor = nullptr;  // [F][R][2], nullable
+    float *hb_energy = nullptr;       // [F][R][2], nullable
+};
+arp_status device_dssp(arp_context *ctx, const DsspJob &job, DsspOut *out);
+// rmsd.cpp: the frame half of rmsd_check (topology, frame count, finite coordinates), for the calls that take no selection
+arp_status rmsd_frames_check(const arp_structure *s, uint64_t n_frames, const double *xyz, std::vector<double> *model_xyz, const double **frames, uint64_t *n0_out, uint64_t *F_out);
+
 // engine.cpp: the context's stream / device and grow-only scratch (device and pinned host)
 void *context_stream(arp_context *ctx);
 int context_device(arp_context *ctx);

@@ -1028,5 +1028,6 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
 #include "rmsd.inl"
 #include "rmsf.inl"
 #include "cov.inl"
+#include "dssp.inl"
 
 }  // namespace arp

@@ -912,6 +912,45 @@ arp_status arp_project(arp_context *ctx, arp_structure *topology, uint64_t n_fra
 arp_status arp_covariance_host(uint64_t n_frames, uint64_t m, const double *aligned, const double *mean, double *cov, float *dccm);
 arp_status arp_project_host(uint64_t n_frames, uint64_t m, const double *xyz_msel, const double *transforms, const double *mean, const double *modes, uint64_t k, double *proj);
 
+/* ---- Secondary structure (DSSP, Kabsch & Sander 1983) per frame and across the frames of an ensemble -- DESIGN.md section 3.23 ----
+ * Where the helices and strands are, and in what share of the frames.  Frames and topology as for the arp_rmsd_* calls (xyz == NULL: the structure's models
+ * are the frames).  The caller names the residues: bb[n_res][4] u32 are the topology atom indices of N, CA, C, O of residue r = 0 .. R - 1 in chain order,
+ * flags[n_res] u8 carry ARP_DSSP_CHAIN_START (bit 0: r == 0, or r's chain differs from r - 1's) and ARP_DSSP_NO_H (bit 1: no amide hydrogen, proline).
+ * All arithmetic is f64 in the order written; every distance is sqrt((dx dx + dy dy) + dz dz).  Per frame:
+ *   brk[r]   = r == 0, or CHAIN_START, or |C[r-1] - N[r]| > 2.5.  cont(a, b), a <= b: 0 <= a, b < R and no brk in a + 1 .. b.
+ *   H[r]     = N[r] + (C[r-1] - O[r-1]) / |C[r-1] - O[r-1]| (per component) where !brk[r] and not NO_H; any other residue donates nothing.
+ *   E(i, j)  for acceptor i (its C=O) and donor j (its N-H), i != j, i != j - 1, |CA[i] - CA[j]| < 9.0:
+ *            27.888 * (((1 / d(O_i, N_j) + 1 / d(C_i, H_j)) - 1 / d(O_i, H_j)) - 1 / d(C_i, N_j)); -9.9 where one of the four distances is < 0.5.
+ *            E is NOT rounded to three decimals (mkdssp rounds; a pair within 5e-4 of the threshold can differ from it).
+ *   best[j]  the two acceptors of donor j with the lowest E, the lower i on equal E;  hb(i, j) = i is one of them and E(i, j) < -0.5.
+ *   turn_n(i), n = 3, 4, 5 = cont(i, i + n) and hb(i, i + n).
+ *   A bridge is considered for |i - j| >= 3, cont(i - 1, i + 1) and cont(j - 1, j + 1):
+ *     par(i, j)  = [hb(i-1, j) and hb(j, i+1)] or [hb(j-1, i) and hb(i, j+1)];   anti(i, j) = [hb(i, j) and hb(j, i)] or [hb(i-1, j+1) and hb(j-1, i+1)].
+ *   States, codes 0 .. 7 of the string "-HBEGITS", assigned in this order:
+ *     B  i has a bridge.   E  par(i, j) and (par(i-1, j-1) or par(i+1, j+1)), or anti(i, j) and (anti(i-1, j+1) or anti(i+1, j-1)), for some j.  Ladders are
+ *        NOT linked across beta bulges (mkdssp links them: a bulge residue it calls E stays B or loop here).
+ *     H  turn_4(i-1) and turn_4(i) set i .. i+3, over B and E.
+ *     G  for i ascending, turn_3(i-1) and turn_3(i) set i .. i+2 when all three are '-' or G at that moment: all three or none.   I  the same with turn_5, i .. i+4.
+ *     T  k still '-' and some turn_n(i) with i < k < i + n.
+ *     S  k still '-', cont(k-2, k+2) and cos of the angle between CA[k] - CA[k-2] and CA[k+2] - CA[k] < cos 70 deg = 0.3420201433256687 (the dot product
+ *        (x x' + y y') + z z' over the product of the two lengths).
+ * Outputs: codes[F][R] u8 (may be NULL); counts[R][8] u32, in how many frames residue r has each code; frame_counts[F][8] u32 (may be NULL); hb_acceptor[F][R][2]
+ * u32 (may be NULL): best[j], ARP_NONE where there is none; hb_energy[F][R][2] f32 (may be NULL): their E rounded once, 0 where there is none.
+ * Checks, all before the device is touched, ARP_ERR_BAD_INPUT: the frame checks of the arp_rmsd_* calls; n_res == 0; n_res >= 2^28; a bb index >= N; a flag
+ * bit other than the two (all under the prefix "dssp").  ctx == NULL runs only the checks (ARP_OK).
+ * The frames go through the device in the upload passes of the arp_rmsd_* calls ("rmsd_chunk_atoms"); no frame depends on another, so device memory is one
+ * pass plus counts, whatever F is.  The only atomics are u32 additions: two calls give identical bytes, for any pass size.  Synchronous. */
+#define ARP_DSSP_CHAIN_START 1u
+#define ARP_DSSP_NO_H 2u
+arp_status arp_dssp(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const uint32_t *bb, const uint8_t *flags, uint64_t n_res,
+                    uint8_t *codes, uint32_t *counts, uint32_t *frame_counts, uint32_t *hb_acceptor, float *hb_energy);
+/* The definition above in plain sequential C++ without a device, on already-gathered coordinates bb_xyz n_frames x n_res x 4 (N, CA, C, O) x 3 f64; bridges are
+ * found by trying every j.  The outputs are arp_dssp's (counts required, the others may be NULL).  n_frames or n_res == 0, a flag bit other than the two and a
+ * non-finite coordinate are ARP_ERR_BAD_INPUT.  The CPU yardstick of the device kernels: codes, counts and acceptors agree exactly wherever no comparison of the
+ * definition is within rounding of its threshold. */
+arp_status arp_dssp_host(uint64_t n_frames, uint64_t n_res, const double *bb_xyz, const uint8_t *flags, uint8_t *codes, uint32_t *counts, uint32_t *frame_counts,
+                         uint32_t *hb_acceptor, float *hb_energy);
+
 /* ---- SASA and SAP statistics over the frames of an ensemble (MD snapshots, NMR models, conformers of one topology) -- DESIGN.md section 3.8 ----
  * Topology, N, frames and xyz exactly as arp_contact_frequencies defines them: model 0 of `topology` is the topology, frame f is xyz[f]
  * (n_frames x N x 3 f64, host, C order); xyz == NULL: the structure's models are the frames, with the same one-for-one model check and its error.
