@@ -2,7 +2,7 @@
 
 Public surface mirrors the reference (src/lib.rs:20-34, src/python.rs:31-56) for this one path:
 contacts(), get_contacts(), load_model(), parse_groups(); and sasa(), relative_sasa(), sap_score(), dsasa(), buried_sasa(); and sc(); and
-contact_frequencies(), contact_timelines(), contact_similarity(), contact_autocorrelation(), contact_clusters(), rmsd(), rmsd_matrix(), rmsd_clusters(), rmsf(), covariance(), dccm(), pca(), secondary_structure(), sasa_ensemble(), sap_ensemble(), dsasa_ensemble() and sc_ensemble() across the frames of an ensemble (no counterpart in the reference).  Importing this package loads libarpeggia_amd.so and
+contact_frequencies(), contact_timelines(), contact_similarity(), contact_autocorrelation(), contact_clusters(), rmsd(), rmsd_matrix(), rmsd_clusters(), rmsf(), covariance(), dccm(), pca(), secondary_structure(), torsions(), sasa_ensemble(), sap_ensemble(), dsasa_ensemble() and sc_ensemble() across the frames of an ensemble (no counterpart in the reference).  Importing this package loads libarpeggia_amd.so and
 fails loudly if the HIP extension has not been built -- there is no CPU fallback.
 """
 from .api import (  # noqa: F401
@@ -32,6 +32,9 @@ from .api import RMSF_COLUMNS, RMSF_RESIDUE_COLUMNS, get_rmsf, rmsf, rmsf_host, 
 from .api import DCCM_COLUMNS, covariance, covariance_host, dccm, dccm_table, get_covariance, get_dccm, get_pca, get_projection, pca, pca_modes, project_host  # noqa: F401  which atoms move together, and along which collective directions
 from .api import (  # noqa: F401  where the helices and strands are, and in what share of the frames
     SS_CODES, SS_COLUMNS, backbone_select, get_secondary_structure, secondary_structure, secondary_structure_host, secondary_structure_table, ss_consensus, ss_string,
+)
+from .api import (  # noqa: F401  what phi, psi, omega and chi are, which rotamer each side chain sits in, the Ramachandran map of the ensemble
+    CHI_ATOMS, RAMA_CLASSES, TORSION_COLUMNS, TORSION_KINDS, get_torsions, torsion_select, torsion_table, torsions, torsions_host,
 )
 from .api import bit_autocorrelation, contact_autocorrelation, get_contact_autocorrelation  # noqa: F401  how long a contact lives, how fast it decays
 from .api import (  # noqa: F401  SASA / SAP statistics across the frames of an ensemble

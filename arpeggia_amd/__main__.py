@@ -26,6 +26,9 @@ the measured atoms to --matrix FILE.npy and, with -o (and -f, -t), in long form;
 `secondary-structure` (no counterpart either) assigns DSSP states (Kabsch & Sander) to the residues of the chains -c in every model and writes, with -o (and -f,
 -t), per residue the share of the models in each state and the consensus state; --codes FILE.npy: the codes, uint8 [models, residues]; --strings FILE.txt: one line
 of "-HBEGITS" characters per model.
+`torsions` (no counterpart either) measures phi, psi, omega and chi1 .. chi5 (--kinds) of the residues of the chains -c in every model and writes, with -o (and
+-f, -t), per torsion the circular mean, resultant and standard deviation, the shares of the models in g+, t and g- and the number of transitions; --angles
+FILE.npy: the angles, float32 [models, torsions]; --rama-file FILE.npy: the Ramachandran maps, uint32 [groups, --bins, --bins], --rama class|residue.
 `sasa-ensemble` and `sap-ensemble` (no counterpart either) take the flags and defaults of `sasa` / `sap` without --model: statistics over the models.
 `dsasa --level atom|residue` writes the interface row by row (default `total`: the reference's scalar); `dsasa-ensemble` takes the flags of
 `sasa-ensemble` and -g: dSASA per model and the per-atom statistics of the buried surface.
@@ -215,6 +218,20 @@ def build_parser() -> argparse.ArgumentParser:
     ss.add_argument("--codes", default=None, type=Path, metavar="FILE.npy", help="Write the codes (indices into '-HBEGITS'): uint8 [models, residues]")
     ss.add_argument("--strings", default=None, type=Path, metavar="FILE.txt", help="Write one line per model: the states of its residues as '-HBEGITS' characters")
     ss.add_argument("--ignore-zero-occupancy", action="store_true", help="Ignore atoms with zero occupancy")
+    tr = sub.add_parser("torsions", help="what phi, psi, omega and the chi angles are in every model: means, rotamer states and transitions per torsion, and the "
+                                         "Ramachandran map of the models")
+    tr.add_argument("-i", "--input", required=True, type=Path, help="Path to the PDB or mmCIF file whose models are the frames")
+    tr.add_argument("-c", "--chains", default="", help="Comma-separated chain IDs to include (empty: all)")
+    tr.add_argument("--kinds", default="phi,psi,omega,chi", help="Comma-separated torsions to include: phi, psi, omega, chi (all five) or chi1 .. chi5")
+    tr.add_argument("--bins", default=36, type=int, metavar="N", help="Bins of the histograms over (-180, 180] (at most 360)")
+    tr.add_argument("--rama", default="class", choices=("class", "residue"), help="Groups of the Ramachandran maps: the four residue classes (general, GLY, PRO, "
+                                                                                   "pre-PRO) or one map per residue")
+    tr.add_argument("-o", "--output", default=None, type=Path, help="Output directory of the per-torsion table")
+    tr.add_argument("-f", "--filename", default="torsions", help="Name of the per-torsion table")
+    tr.add_argument("-t", "--output-format", default="csv", type=str.lower, choices=FORMATS, help="Output file type of the per-torsion table")
+    tr.add_argument("--angles", default=None, type=Path, metavar="FILE.npy", help="Write the angles in degrees: float32 [models, torsions], NaN where undefined")
+    tr.add_argument("--rama-file", default=None, type=Path, metavar="FILE.npy", help="Write the Ramachandran maps: uint32 [groups, N, N], rows phi, columns psi")
+    tr.add_argument("--ignore-zero-occupancy", action="store_true", help="Ignore atoms with zero occupancy")
     common = dict(model=("-m", "--model", 0, int, "Model number to analyze (0: the first model)"),
                   probe=("-r", "--probe-radius", 1.4, float, "Probe radius in Angstroms"),
                   points=("-n", "--num-points", 100, int, "Number of points for surface calculation"),
@@ -768,6 +785,36 @@ def run_secondary_structure(args) -> int:
     return 0
 
 
+def run_torsions(args) -> int:
+    import arpeggia_amd as aa
+
+    if not args.input.exists():
+        log.error("Failed to retrieve input file: %s", args.input)
+        return 1
+    if args.output is None and args.angles is None and args.rama_file is None:
+        log.error("Torsions: nothing to write, give -o DIR, --angles FILE.npy and / or --rama-file FILE.npy")
+        return 1
+    try:
+        structure = aa.Structure.load(str(args.input.resolve()), args.ignore_zero_occupancy)
+        res = aa.get_torsions(structure, None, args.chains, args.kinds, args.bins, args.rama, angles=args.angles is not None)
+    except (aa.ArpeggiaError, ValueError) as e:
+        log.error("Torsions failed: %s", e)
+        return 1
+    if args.rama_file is not None and "hist2" not in res:
+        log.error("Torsions: no Ramachandran map to write (--kinds leaves no residue with both phi and psi, or --bins is 0)")
+        return 1
+    if args.output is not None:
+        args.output.mkdir(parents=True, exist_ok=True)
+        out = (args.output / args.filename).with_suffix("." + args.output_format)
+        write_table(aa.torsion_table(structure, res), out, args.output_format)
+    if args.angles is not None:
+        _save_npy(args.angles, res["angles"])
+    if args.rama_file is not None:
+        _save_npy(args.rama_file, res["hist2"])
+    log.info("%d torsions of %d residues saved", len(res["kind"]), res["n_rows"])
+    return 0
+
+
 def run_pca(args) -> int:
     import arpeggia_amd as aa
 
@@ -864,6 +911,8 @@ def main(argv=None) -> int:
         return run_dccm(args)
     if args.command == "secondary-structure":
         return run_secondary_structure(args)
+    if args.command == "torsions":
+        return run_torsions(args)
     if args.command == "pca":
         return run_pca(args)
     if args.command == "sc":

@@ -247,6 +247,8 @@ def _load():
         "arp_project_host": (C.c_int32, [C.c_uint64, C.c_uint64, _dp, _dp, _dp, _dp, C.c_uint64, _dp]),
         "arp_dssp": (C.c_int32, [vp, vp, C.c_uint64, _dp, _u32p, _u8p, C.c_uint64, _u8p, _u32p, _u32p, _u32p, _fp]),
         "arp_dssp_host": (C.c_int32, [C.c_uint64, C.c_uint64, _dp, _u8p, _u8p, _u32p, _u32p, _u32p, _fp]),
+        "arp_torsions": (C.c_int32, [vp, vp, C.c_uint64, _dp, _u32p, C.c_uint64, C.c_uint32, _u32p, C.c_uint64, C.c_uint32, _fp, _dp, _u8p, _dp, _u32p, _u32p, _u32p, _u32p, _u32p]),
+        "arp_torsions_host": (C.c_int32, [C.c_uint64, C.c_uint64, _dp, C.c_uint32, _u32p, C.c_uint64, C.c_uint32, _fp, _dp, _u8p, _dp, _u32p, _u32p, _u32p, _u32p, _u32p]),
         "arp_sasa_radius": (C.c_int32, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, _fp]),
         "arp_max_asa": (C.c_float, [C.c_char_p]),
         "arp_residue_is_polar": (C.c_int32, [C.c_char_p]),

@@ -475,6 +475,12 @@ class Context:
         `counts`, `fraction`, `frame_counts`, with codes=True `codes`, with hbonds=True `hb_acceptor` and `hb_energy` (get_secondary_structure)."""
         return _secondary_structure(self, structure, frames, chains, codes, hbonds)
 
+    def torsions(self, structure: Structure, frames=None, chains: str = "", kinds=("phi", "psi", "omega", "chi"), bins: int = 36, rama="class", angles: bool = True,
+                 cossin: bool = False, states: bool = False) -> dict:
+        """arp_torsions as a dict: phi, psi, omega and chi of every frame, their rotamer states, transitions, circular statistics, histograms and the
+        Ramachandran maps of the ensemble (get_torsions)."""
+        return _torsions(self, structure, frames, chains, kinds, bins, rama, angles, cossin, states)
+
     def sc_ensemble(self, structure: Structure, frames=None, groups: str = "/") -> dict:
         """arp_structure_sc_ensemble as a dict: shape complementarity of every frame of an ensemble (the selection and radii of get_sc on model 0).
         frames: [F, N, 3] f64 coordinates of the N atoms of model 0; None: the structure's models.  Keys: atoms (u32 structure indices of the m
@@ -1948,6 +1954,230 @@ def secondary_structure_table(structure: Structure, result: dict):
         cols[name] = pa.array(np.asarray(result["fraction"])[:, k], pa.float32())
     cols["consensus"] = pa.array([SS_CODES[int(c)] for c in ss_consensus(result["counts"])], pa.string())
     return _frame({k: cols[k] for k in SS_COLUMNS})
+
+
+# ---- Torsion angles, rotamer states and Ramachandran maps across the frames of an ensemble (arp_torsions) ----
+TORSION_KINDS = ["phi", "psi", "omega", "chi1", "chi2", "chi3", "chi4", "chi5"]   # `kind` of every torsion indexes this
+TORSION_STATES = "-+t-"   # state k of every output: 0 undefined, 1 g+, 2 t, 3 g-
+RAMA_CLASSES = ["general", "GLY", "PRO", "pre-PRO"]   # `rama_class` of every (phi, psi) pair, tested GLY, PRO, pre-PRO, general
+TORSION_COLUMNS = ["chain", "resn", "resi", "insertion", "torsion", "n_defined", "mean", "resultant", "circ_std", "frac_gplus", "frac_trans", "frac_gminus", "n_transitions"]
+LINK_MAX = 2.5   # A: |C[r-1] - N[r]| of model 0 above it, and r-1 and r are not linked (the chain break of arp_dssp)
+
+
+def _chi_atoms() -> dict:
+    """resn -> [(p0, p1, p2, p3)] of chi1 .. (IUPAC; the first of two equivalent branches: CG1, OD1, ND1, CD1, OE1, NH1)."""
+    chi = {}
+    fourth = {1: {"CG": "ARG ASN ASP GLN GLU HIS LEU LYS MET PHE PRO TRP TYR", "CG1": "ILE VAL", "OG": "SER", "OG1": "THR", "SG": "CYS"},
+              2: {"CD": "ARG GLN GLU LYS PRO", "OD1": "ASN ASP", "ND1": "HIS", "CD1": "LEU PHE TRP TYR", "SD": "MET"},
+              3: {"NE": "ARG", "OE1": "GLN GLU", "CE": "LYS"}}
+    head = {1: ("N", "CA", "CB"), 2: ("CA", "CB", "CG"), 3: ("CB", "CG", "CD")}
+    for n in (1, 2, 3):
+        for atom, names in fourth[n].items():
+            for resn in names.split():
+                chi.setdefault(resn, []).append(head[n] + (atom,))
+    chi["ILE"].append(("CA", "CB", "CG1", "CD1"))
+    chi["MET"].append(("CB", "CG", "SD", "CE"))
+    chi["ARG"] += [("CG", "CD", "NE", "CZ"), ("CD", "NE", "CZ", "NH1")]
+    chi["LYS"].append(("CG", "CD", "CE", "NZ"))
+    return chi
+
+
+CHI_ATOMS = _chi_atoms()
+
+
+def _torsion_kinds(kinds) -> set:
+    """The indices into TORSION_KINDS a `kinds` argument names: a comma list or a sequence of phi, psi, omega, chi (all five) and chi1 .. chi5."""
+    names = [k.strip() for k in kinds.split(",")] if isinstance(kinds, str) else list(kinds)
+    want = set()
+    for k in names:
+        if k == "chi":
+            want |= {3, 4, 5, 6, 7}
+        elif k in TORSION_KINDS:
+            want.add(TORSION_KINDS.index(k))
+        elif k:
+            raise ValueError(f"Invalid torsion kind '{k}'. Must be one of: {', '.join(TORSION_KINDS[:3] + ['chi'] + TORSION_KINDS[3:])}")
+    return want
+
+
+def torsion_select(structure: Structure, chains: str = "", kinds=("phi", "psi", "omega", "chi")) -> dict:
+    """The torsions arp_torsions works on.  Residues are those of model 0 as in backbone_select -- file order, HOH out, `chains`, the first atom of each name --
+    but a residue is NOT dropped for a missing atom: only the torsions that lack an atom are.  Rows r-1 and r are linked iff they have the same chain, follow each
+    other in the selection and |C[r-1] - N[r]| <= 2.5 A in model 0.  phi(r) = C[r-1]-N-CA-C where r-1 is linked; psi(r) = N-CA-C-N[r+1] and omega(r) =
+    CA-C-N[r+1]-CA[r+1] where r+1 is linked; chi1 .. chi5 by CHI_ATOMS.  Order: residues in selection order, within one phi, psi, omega, chi1 ..
+    Returns `quads` <u4 [D, 4] (topology atom indices), `kind` u1 [D] (index into TORSION_KINDS), `residue` <u4 [D] (the first atom of the owning residue), `row`
+    <u4 [D] (the residue's index in the selection), `n_rows`, `pairs` <u4 [P, 3] (phi, psi of one residue, and its rama_class as the group) and `rama_class` u1 [P]
+    (1 GLY, 2 PRO, 3 the residue before a PRO, 0 general -- tested in this order)."""
+    want = _torsion_kinds(kinds)
+    n = _topology_atoms(structure)
+    empty = {"quads": np.zeros((0, 4), "<u4"), "kind": np.zeros(0, "u1"), "residue": np.zeros(0, "<u4"), "row": np.zeros(0, "<u4"), "n_rows": 0,
+             "pairs": np.zeros((0, 3), "<u4"), "rama_class": np.zeros(0, "u1")}
+    if n == 0:
+        return empty
+    name, resn, chain, ins = (structure.strings(k)[:n] for k in ("atomn", "resn", "chain", "insertion"))
+    resi = structure.ints("resi")[:n]
+    new = np.ones(n, bool)
+    new[1:] = (chain[1:] != chain[:-1]) | (resi[1:] != resi[:-1]) | (ins[1:] != ins[:-1])
+    run = np.cumsum(new) - 1
+    first = np.flatnonzero(new)
+    keep = resn[first] != b"HOH"
+    wanted = [c.strip().encode() for c in chains.split(",") if c.strip()]
+    if wanted:
+        keep &= np.isin(chain[first], wanted)
+    rows = np.flatnonzero(keep)
+    R = len(rows)
+    if R == 0:
+        return empty
+    atom_names = sorted({"N", "CA", "C"} | {a for quads in CHI_ATOMS.values() for q in quads for a in q})
+    at = {}   # atom name -> [R] topology index of the first atom of that name in every selected residue, -1: none
+    for a in atom_names:
+        idx = np.flatnonzero(name == a.encode())
+        runs, pos = np.unique(run[idx], return_index=True)
+        col = np.full(len(first), -1, np.int64)
+        col[runs] = idx[pos]
+        at[a] = col[rows]
+    soa = structure.soa()
+    xyz = np.stack([np.asarray(soa[k][:n], np.float64) for k in ("x", "y", "z")], 1)
+    names_r = [b.decode() for b in resn[first[rows]]]
+    ch = chain[first[rows]]
+    link = np.zeros(R + 1, bool)   # link[r]: rows r - 1 and r are linked (link[0] and link[R]: no neighbour)
+    ok = (ch[1:] == ch[:-1]) & (at["C"][:-1] >= 0) & (at["N"][1:] >= 0)
+    dist = np.sqrt(((xyz[at["C"][:-1]] - xyz[at["N"][1:]]) ** 2).sum(1))
+    link[1:R] = ok & (dist <= LINK_MAX)
+    link = link.tolist()
+    at = {a: col.tolist() for a, col in at.items()}   # (plain lists: the loop below indexes them a few times per residue)
+    quads, kind, row, pairs, rama = [], [], [], [], []
+    for r in range(R):
+        here = {}
+        cand = []
+        if link[r]:
+            cand.append((0, (at["C"][r - 1], at["N"][r], at["CA"][r], at["C"][r])))
+        if link[r + 1]:
+            cand.append((1, (at["N"][r], at["CA"][r], at["C"][r], at["N"][r + 1])))
+            cand.append((2, (at["CA"][r], at["C"][r], at["N"][r + 1], at["CA"][r + 1])))
+        for k, q in enumerate(CHI_ATOMS.get(names_r[r], ())):
+            cand.append((3 + k, tuple(at[a][r] for a in q)))
+        for k, q in cand:
+            if k in want and min(q) >= 0:
+                here[k] = len(quads)
+                quads.append(q); kind.append(k); row.append(r)
+        if 0 in here and 1 in here:
+            cls = 1 if names_r[r] == "GLY" else 2 if names_r[r] == "PRO" else 3 if names_r[r + 1] == "PRO" else 0   # (psi exists: r + 1 is linked)
+            pairs.append((here[0], here[1], cls)); rama.append(cls)
+    row = np.asarray(row, "<u4")
+    return {"quads": np.asarray(quads, "<u4").reshape(-1, 4), "kind": np.asarray(kind, "u1"), "residue": first[rows][row].astype("<u4"), "row": row, "n_rows": R,
+            "pairs": np.asarray(pairs, "<u4").reshape(-1, 3), "rama_class": np.asarray(rama, "u1")}
+
+
+def _torsion_outputs(F: int, D: int, bins: int, G: int, angles: bool, cossin: bool, states: bool) -> dict:
+    out = {"sums": np.zeros((D, 2), "<f8"), "n_defined": np.zeros(D, "<u4"), "state_counts": np.zeros((D, 4), "<u4"), "n_transitions": np.zeros(D, "<u4")}
+    if angles:
+        out["angles"] = np.zeros((F, D), "<f4")
+    if cossin:
+        out["cossin"] = np.zeros((F, D, 2), "<f8")
+    if states:
+        out["states"] = np.zeros((F, D), "u1")
+    if bins:
+        out["hist"] = np.zeros((D, bins), "<u4")
+        if G:
+            out["hist2"] = np.zeros((G, bins, bins), "<u4")
+    return out
+
+
+def _torsion_pointers(out: dict) -> tuple:
+    u8p, u32p, fp, dp = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_double)
+    arr = lambda a, t: (a if a.size else np.zeros(1, a.dtype)).ctypes.data_as(t)
+    ptr_of = lambda key, t: arr(out[key], t) if key in out else None
+    return (ptr_of("angles", fp), ptr_of("cossin", dp), ptr_of("states", u8p), arr(out["sums"], dp), arr(out["n_defined"], u32p), arr(out["state_counts"], u32p),
+            arr(out["n_transitions"], u32p), ptr_of("hist", u32p), ptr_of("hist2", u32p))
+
+
+def _torsion_statistics(out: dict) -> dict:
+    """The circular statistics of a result, on the host in f64: mean = degrees(atan2(sum s, sum c)), resultant = hypot(sum c, sum s) / n_defined, circ_std =
+    degrees(sqrt(-2 ln resultant)) (a resultant that rounding lifts above 1 counts as 1), NaN where the torsion is never defined; state_fraction f4 [D, 3]."""
+    nd = out["n_defined"].astype(np.float64)
+    sc, ss = out["sums"][:, 0], out["sums"][:, 1]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["mean"] = np.where(nd > 0, np.degrees(np.arctan2(ss, sc)), np.nan)
+        out["resultant"] = np.where(nd > 0, np.hypot(sc, ss) / nd, np.nan)
+        out["circ_std"] = np.degrees(np.sqrt(np.abs(2.0 * np.log(np.minimum(out["resultant"], 1.0)))))
+        out["state_fraction"] = (out["state_counts"][:, 1:].astype(np.float64) / nd[:, None]).astype("<f4")
+    return out
+
+
+def _torsions(ctx: "Context | None", structure: Structure, frames, chains: str, kinds, bins: int, rama, angles: bool, cossin: bool, states: bool):
+    """arp_torsions.  ctx None: the inputs are only checked (raises their error, else returns None)."""
+    if rama not in ("class", "residue", None):
+        raise ValueError(f"Invalid rama '{rama}'. Must be one of: 'class', 'residue', None")
+    sel = torsion_select(structure, chains, kinds)
+    D, P = len(sel["quads"]), len(sel["pairs"])
+    n_frames, ptr, keep = _frames_arg(structure, frames, "torsions")
+    pairs = sel["pairs"].copy()
+    if rama == "residue":
+        pairs[:, 2] = sel["row"][pairs[:, 0]]
+    G = 0 if rama is None or P == 0 or int(bins) <= 0 else len(RAMA_CLASSES) if rama == "class" else int(sel["n_rows"])
+    u32p = C.POINTER(C.c_uint32)
+    arr = lambda a, t: (a if a.size else np.zeros(4, a.dtype)).ctypes.data_as(t)
+    head = (structure._h, int(n_frames), ptr, arr(sel["quads"], u32p), D, max(int(bins), 0), arr(pairs, u32p), P if G else 0, G)
+    if ctx is None:
+        _check(lib.arp_torsions(None, *head, *([None] * 9)))
+        return None
+    F = _rmsd_frames(structure, frames)
+    out = _torsion_outputs(F, D, max(int(bins), 0), G, angles, cossin, states)
+    _check(lib.arp_torsions(ctx._h, *head, *_torsion_pointers(out)))
+    out.update({k: v for k, v in sel.items() if k != "pairs"})
+    out["pairs"], out["n_groups"] = pairs, G
+    return _torsion_statistics(out)
+
+
+def torsions_host(quad_xyz, pairs=None, n_groups: int = 0, bins: int = 36, angles: bool = True, cossin: bool = True, states: bool = True) -> dict:
+    """arp_torsions_host: the definition of arp_torsions in plain sequential C++ on the CPU, on already-gathered coordinates quad_xyz [F, D, 4, 3].  pairs [P, 3]
+    with n_groups > 0 ask for `hist2`.  The yardstick of the device call.  Keys: sums, n_defined, state_counts, n_transitions, the statistics derived from them
+    and, on request, angles, cossin, states, hist (bins > 0), hist2."""
+    x = np.ascontiguousarray(quad_xyz, dtype="<f8")
+    if x.ndim != 4 or x.shape[2:] != (4, 3):
+        raise ValueError(f"quad_xyz must have shape [F, D, 4, 3], got {list(x.shape)}")
+    F, D = x.shape[:2]
+    pr = np.zeros((0, 3), "<u4") if pairs is None else np.ascontiguousarray(pairs, dtype="<u4").reshape(-1, 3)
+    G = int(n_groups) if len(pr) else 0
+    out = _torsion_outputs(F, D, max(int(bins), 0), G, angles, cossin, states)
+    arr = lambda a, t: (a if a.size else np.zeros(4, a.dtype)).ctypes.data_as(t)
+    _check(lib.arp_torsions_host(F, D, arr(x, C.POINTER(C.c_double)), max(int(bins), 0), arr(pr, C.POINTER(C.c_uint32)), len(pr) if G else 0, G, *_torsion_pointers(out)))
+    return _torsion_statistics(out)
+
+
+def get_torsions(structure: Structure, frames=None, chains: str = "", kinds=("phi", "psi", "omega", "chi"), bins: int = 36, rama="class", angles: bool = True,
+                 cossin: bool = False, states: bool = False, device: int = 0) -> dict:
+    """What phi, psi, omega and the side-chain chi angles are in every frame, which well each sits in, how often it jumps, and the Ramachandran map of the
+    ensemble.  The torsions are those of torsion_select(structure, chains, kinds).  Returns the selection's arrays and, per torsion: `n_defined`, `state_counts`
+    [D, 4] (undefined, g+, t, g-), `state_fraction` f4 [D, 3], `n_transitions`, `sums` [D, 2] (sum cos, sum sin), `mean` (degrees), `resultant`, `circ_std`
+    (degrees); with bins > 0 `hist` [D, bins]; with rama="class" `hist2` [4, bins, bins] (RAMA_CLASSES; rows phi, columns psi, bin k = [-180 + k w, -180 + (k + 1)
+    w)), with rama="residue" `hist2` [n_rows, bins, bins], one map per residue of the selection; angles=True: `angles` f4 [F, D] in degrees, NaN where undefined;
+    cossin=True: `cossin` f8 [F, D, 2] (what a dihedral PCA takes); states=True: `states` u1 [F, D].  frames: [F, N, 3] f64; None: the structure's models."""
+    ctx = _with_context(device, lambda: _torsions(None, structure, frames, chains, kinds, bins, rama, angles, cossin, states))
+    return ctx.torsions(structure, frames, chains, kinds, bins, rama, angles, cossin, states)
+
+
+def torsions(input_file: str, chains: str = "", kinds=("phi", "psi", "omega", "chi"), bins: int = 36, rama="class", angles: bool = True, cossin: bool = False,
+             states: bool = False, ignore_zero_occupancy: bool = False) -> dict:
+    """Torsions of the models of a file (the models are the frames; one model: one frame): see get_torsions."""
+    return get_torsions(Structure.load(input_file, ignore_zero_occupancy), None, chains, kinds, bins, rama, angles, cossin, states)
+
+
+def torsion_table(structure: Structure, result: dict):
+    """The result of a torsion call as a table of the contact table's type, one row per torsion: TORSION_COLUMNS -- chain, resn, resi, insertion, `torsion` (a
+    name of TORSION_KINDS), n_defined, mean, resultant, circ_std, the three state fractions and n_transitions."""
+    import pyarrow as pa
+
+    ident = _identity(structure, np.asarray(result["residue"]))
+    cols = {k: ident[k] for k in ("chain", "resn", "resi", "insertion")}
+    cols["torsion"] = pa.array([TORSION_KINDS[int(k)] for k in result["kind"]], pa.string())
+    cols["n_defined"] = pa.array(np.asarray(result["n_defined"], "<u4"), pa.uint32())
+    for k in ("mean", "resultant", "circ_std"):
+        cols[k] = pa.array(np.asarray(result[k], np.float64), pa.float64())
+    for k, name in enumerate(("frac_gplus", "frac_trans", "frac_gminus")):
+        cols[name] = pa.array(np.asarray(result["state_fraction"])[:, k], pa.float32())
+    cols["n_transitions"] = pa.array(np.asarray(result["n_transitions"], "<u4"), pa.uint32())
+    return _frame({k: cols[k] for k in TORSION_COLUMNS})
 
 
 def _contact_clusters_arrow(input_file: str, groups: str, vdw_comp: float, dist_cutoff: float, ignore_zero_occupancy: bool, rings: bool, level: str, min_similarity: float,

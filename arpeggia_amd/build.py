@@ -13,8 +13,8 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libarpeggia_amd.so"
-SOURCES = ["kernels.hip", "engine.cpp", "batch.cpp", "sasa_dev.cpp", "structure.cpp", "table.cpp", "table_cache.cpp", "table_ens.cpp", "table_dev.hip", "sasa.cpp", "sc.cpp", "rmsd.cpp", "rmsf.cpp", "cov.cpp", "dssp.cpp"]
-HEADERS = ["arp_internal.h", "emit_plan.h", "host_common.h", "engine.h", "debug_knobs.h", "scan.inl", "grid.inl", "pairs.inl", "pairs_emit.inl", "batch.inl", "sap.inl", "sasa.inl", "ens.inl", "seg.inl", "sc.inl", "sc_ens.inl", "freq.inl", "freq_rings.inl", "freq_water.inl", "timeline.inl", "similarity.inl", "autocorr.inl", "cluster.inl", "rmsd.inl", "rmsf.inl", "cov.inl", "dssp.inl", "table.h", "table_dev.h", "table_plan.h", "../../include/arpeggia_amd.h"]
+SOURCES = ["kernels.hip", "engine.cpp", "batch.cpp", "sasa_dev.cpp", "structure.cpp", "table.cpp", "table_cache.cpp", "table_ens.cpp", "table_dev.hip", "sasa.cpp", "sc.cpp", "rmsd.cpp", "rmsf.cpp", "cov.cpp", "dssp.cpp", "torsion.cpp"]
+HEADERS = ["arp_internal.h", "emit_plan.h", "host_common.h", "engine.h", "debug_knobs.h", "scan.inl", "grid.inl", "pairs.inl", "pairs_emit.inl", "batch.inl", "sap.inl", "sasa.inl", "ens.inl", "seg.inl", "sc.inl", "sc_ens.inl", "freq.inl", "freq_rings.inl", "freq_water.inl", "timeline.inl", "similarity.inl", "autocorr.inl", "cluster.inl", "rmsd.inl", "rmsf.inl", "cov.inl", "dssp.inl", "torsion.inl", "table.h", "table_dev.h", "table_plan.h", "../../include/arpeggia_amd.h"]
 TEST_HEADERS = ["../../tests/hosttable/table_host.inl"]  # only the test library (build_host_table_library) contains it: not part of the product's hash
 STAMP = PKG / "build" / "libarpeggia_amd.sha256"  # hash of every source + the flags the library was last built from
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-fvisibility=default", "-Wall", "-Wno-unused-result",

@@ -23,6 +23,7 @@ struct DebugKnobs {
     long sc_ens_frames;    // > 0: frames per pass of arp_sc_ensemble (tests: pass edges at tiny shapes); 0: from the memory budget (sc_ens.inl launch_sc_ens)
     int scan_kernel;    // the cell scan (pairs.inl launch_grid): 0: chosen by input size; 1: the look-back scan k_scan_single on 256 blocks; 2: on 1 024 blocks (tests: small inputs reach it)
     int table_key_bits;  // > 0: stands for the 64 of the table plan's three width tests (table_plan.h plan_table; tests: small inputs reach the plans of wide keys); 0: 64
+    int torsion_hist2_route;  // the Ramachandran maps of arp_torsions (torsion.inl): 0: chosen by G B^2; 1: per-workgroup LDS tables (falls back to 2 where they do not fit); 2: wave-matched global adds; 3: one global add per sample (measurements)
 };
 extern DebugKnobs g_debug;
 

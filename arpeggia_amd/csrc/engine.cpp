@@ -731,7 +731,11 @@ extern "C" arp_status arp_debug_set(const char *key, int64_t value) {
         if (value < 0 || value > 2) { set_error("arp_debug_set: scan_kernel takes 0 (automatic), 1 (the look-back cell scan on 256 blocks) or 2 (on 1024 blocks)"); return ARP_ERR_BAD_INPUT; }
         g_debug.scan_kernel = (int)value;
     }
-    else { set_error("arp_debug_set: unknown key '%s' (timing, emit_kernel, defer_entries, strip_rows, index_bits, scan_kernel, table_host, freq_chunk_atoms, freq_cap_items, freq_frame_bits, ens_chunk_atoms, sc_ens_frames, timeline_cap_bytes, similarity_cap_bytes, autocorr_cap_bytes, cluster_cap_bytes, rmsd_chunk_atoms, rmsd_cap_bytes, table_key_bits)", key); return ARP_ERR_BAD_INPUT; }
+    else if (k == "torsion_hist2_route") {
+        if (value < 0 || value > 3) { set_error("arp_debug_set: torsion_hist2_route takes 0 (automatic), 1 (LDS tables), 2 (wave-matched global adds) or 3 (one global add per sample)"); return ARP_ERR_BAD_INPUT; }
+        g_debug.torsion_hist2_route = (int)value;
+    }
+    else { set_error("arp_debug_set: unknown key '%s' (timing, emit_kernel, defer_entries, strip_rows, index_bits, scan_kernel, table_host, freq_chunk_atoms, freq_cap_items, freq_frame_bits, ens_chunk_atoms, sc_ens_frames, timeline_cap_bytes, similarity_cap_bytes, autocorr_cap_bytes, cluster_cap_bytes, rmsd_chunk_atoms, rmsd_cap_bytes, table_key_bits, torsion_hist2_route)", key); return ARP_ERR_BAD_INPUT; }
     return ARP_OK;
 }
 extern "C" arp_status arp_debug_get(const char *key, int64_t *value) {

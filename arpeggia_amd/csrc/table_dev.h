@@ -2,6 +2,7 @@
 // side-chain plane statistics run as HIP kernels (table_dev.hip); table_cache.cpp keeps the bookkeeping (entity lists, strings).
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <memory>
 #include <string>
@@ -293,6 +294,71 @@ struct DsspOut {
 arp_status device_dssp(arp_context *ctx, const DsspJob &job, DsspOut *out);
 // rmsd.cpp: the frame half of rmsd_check (topology, frame count, finite coordinates), for the calls that take no selection
 arp_status rmsd_frames_check(const arp_structure *s, uint64_t n_frames, const double *xyz, std::vector<double> *model_xyz, const double **frames, uint64_t *n0_out, uint64_t *F_out);
+
+// Torsion angles and Ramachandran maps (torsion.inl, arp_torsions).  The definition, written once: the host twin (torsion.cpp) and the
+// kernels call these two functions.  Every expression is f64 in the order of include/arpeggia_amd.h (the library is built with -ffp-contract=off).
+#if defined(__HIPCC__)
+#define ARP_HOST_DEVICE __host__ __device__
+#else
+#define ARP_HOST_DEVICE   // (a stand-alone host build of the twin under the sanitizers compiles this header as plain C++)
+#endif
+constexpr double kTorsionDeg = 57.29577951308232;   // 180 / pi
+constexpr uint32_t kTorsionMaxBins = 360;
+constexpr uint32_t kTorsionNanBits = 0x7FC00000u;   // angles of an undefined torsion
+constexpr uint16_t kTorsionNoBin = 0xFFFFu;
+struct Torsion {
+    double c, s, a;   // cos, sin, degrees in (-180, 180]; 0, 0, 0 where undefined
+    uint8_t state;    // 0 undefined, 1 g+, 2 t, 3 g-
+};
+ARP_HOST_DEVICE inline Torsion torsion_eval(const double *p0, const double *p1, const double *p2, const double *p3) {
+    const double b1x = p1[0] - p0[0], b1y = p1[1] - p0[1], b1z = p1[2] - p0[2];
+    const double b2x = p2[0] - p1[0], b2y = p2[1] - p1[1], b2z = p2[2] - p1[2];
+    const double b3x = p3[0] - p2[0], b3y = p3[1] - p2[1], b3z = p3[2] - p2[2];
+    const double n1x = b1y * b2z - b1z * b2y, n1y = b1z * b2x - b1x * b2z, n1z = b1x * b2y - b1y * b2x;
+    const double n2x = b2y * b3z - b2z * b3y, n2y = b2z * b3x - b2x * b3z, n2z = b2x * b3y - b2y * b3x;
+    const double x = (n1x * n2x + n1y * n2y) + n1z * n2z;
+    const double y = sqrt((b2x * b2x + b2y * b2y) + b2z * b2z) * ((b1x * n2x + b1y * n2y) + b1z * n2z);
+    const double h = sqrt(x * x + y * y);
+    Torsion t{0.0, 0.0, 0.0, 0u};
+    if (!(h > 0.0) || !(h < INFINITY)) return t;
+    t.c = x / h; t.s = y / h;
+    t.a = atan2(y, x) * kTorsionDeg;
+    t.state = t.c <= -0.5 ? 2u : t.s >= 0.0 ? 1u : 3u;
+    return t;
+}
+// the bin of a defined angle, B = n_bins > 0: floor((a + 180) / (360 / B)), B wraps to 0 (+180 falls into bin 0).  atan2 gives -pi for y = -0, x < 0: should
+// the product with 180 / pi round below -180, the negative quotient counts as bin 0, where -180 itself falls; the result is below B whatever a is.
+ARP_HOST_DEVICE inline uint32_t torsion_bin(double a, uint32_t B) {
+    const double w = 360.0 / (double)B, q = floor((a + 180.0) / w);
+    uint32_t k = q > 0.0 ? (uint32_t)q : 0u;
+    if (k >= B) k -= B;
+    return k < B ? k : B - 1u;
+}
+struct TorsionJob {
+    uint64_t n_atoms = 0, n_frames = 0, n_tors = 0, n_pairs = 0;
+    uint32_t n_bins = 0, n_groups = 0;
+    const double *xyz = nullptr;      // [F][N][3]
+    const uint32_t *quads = nullptr;  // [D][4]
+    const uint32_t *pairs = nullptr;  // [P][3]: torsion a, torsion b, group
+    uint64_t chunk_atoms = 0;         // atoms per upload pass, 0 = automatic (arp_debug_set "rmsd_chunk_atoms")
+    int hist2_route = 0;              // arp_debug_set "torsion_hist2_route"
+};
+struct TorsionOut {
+    float *angles = nullptr;           // [F][D], nullable
+    double *cossin = nullptr;          // [F][D][2], nullable
+    uint8_t *states = nullptr;         // [F][D], nullable
+    double *sums = nullptr;            // [D][2]
+    uint32_t *n_defined = nullptr;     // [D]
+    uint32_t *state_counts = nullptr;  // [D][4]
+    uint32_t *n_transitions = nullptr; // [D]
+    uint32_t *hist = nullptr;          // [D][B], nullable
+    uint32_t *hist2 = nullptr;         // [G][B][B], nullable
+};
+// The resident device bytes of arp_torsions that "rmsd_cap_bytes" limits: the state bytes, the slab sums and the two histograms (torsion.inl kTorsionSlab = 32).
+inline uint64_t torsion_resident_bytes(uint64_t F, uint64_t D, uint64_t B, uint64_t G, bool hist, bool hist2) {
+    return F * D + (F + 31u) / 32u * D * 16u + (hist ? D * B * 4u : 0u) + (hist2 ? G * B * B * 4u : 0u);
+}
+arp_status device_torsions(arp_context *ctx, const TorsionJob &job, TorsionOut *out);
 
 // engine.cpp: the context's stream / device and grow-only scratch (device and pinned host)
 void *context_stream(arp_context *ctx);

@@ -1029,5 +1029,6 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
 #include "rmsf.inl"
 #include "cov.inl"
 #include "dssp.inl"
+#include "torsion.inl"
 
 }  // namespace arp

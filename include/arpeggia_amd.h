@@ -185,6 +185,9 @@ typedef struct arp_table arp_table;         /* the 20-column contact table (mod.
  *                      passes) and decides whether the one-launch path may run, so that small inputs reach the plans of wide keys; the passes themselves sort
  *                      on their real widths, and the table's bytes do not change.  0 (default): 64.  Anything else is ARP_ERR_BAD_INPUT (6 is the narrowest pass any structure can
  *                      have, not the widest pass of the structure at hand: the knob is set before a structure is known, and a value below a real pass is harmless)
+ *   "torsion_hist2_route" how arp_torsions adds up its Ramachandran maps: 0 (default) per-workgroup LDS tables where n_groups x n_bins^2 x 4 bytes fit 64 KiB,
+ *                      wave-matched global adds otherwise; 1 the LDS tables where they fit; 2 the wave-matched adds always; 3 one global add per sample
+ *                      (measurements).  The results do not depend on it
  * Unknown keys return ARP_ERR_BAD_INPUT. */
 arp_status arp_debug_set(const char *key, int64_t value);
 /* The read-only twin: what the last contact-table call of the process (arp_get_contacts) did.
@@ -950,6 +953,44 @@ arp_status arp_dssp(arp_context *ctx, arp_structure *topology, uint64_t n_frames
  * definition is within rounding of its threshold. */
 arp_status arp_dssp_host(uint64_t n_frames, uint64_t n_res, const double *bb_xyz, const uint8_t *flags, uint8_t *codes, uint32_t *counts, uint32_t *frame_counts,
                          uint32_t *hb_acceptor, float *hb_energy);
+
+/* ---- Torsion angles, rotamer states and Ramachandran maps across the frames of an ensemble -- DESIGN.md section 3.24 ----
+ * What phi, psi, omega and the chi angles are in every frame, in which well each sits and how often it jumps, and the two-dimensional histogram of (phi, psi).
+ * Frames and topology as for arp_dssp (xyz == NULL: the structure's models are the frames).  The caller names the torsions: quads[n_tors][4] u32 are topology
+ * atom indices p0 .. p3 of torsion d = 0 .. D - 1 (the Python layer's torsion_select builds them); quads may repeat and overlap.
+ * One torsion, all f64 in the order written (the library is built with -ffp-contract=off):
+ *   b1 = p1 - p0, b2 = p2 - p1, b3 = p3 - p2;  n1 = b1 x b2, n2 = b2 x b3, cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x)
+ *   x = (n1.x n2.x + n1.y n2.y) + n1.z n2.z
+ *   y = sqrt((b2.x b2.x + b2.y b2.y) + b2.z b2.z) * ((b1.x n2.x + b1.y n2.y) + b1.z n2.z)
+ *   h = sqrt(x x + y y).  The torsion is defined in this frame iff h > 0 and h is finite (a repeated atom or a collinear triple leaves it undefined).
+ *   c = x / h, s = y / h;  a = atan2(y, x) * (180 / pi) in (-180, 180], IUPAC sign: p0 = (1,0,0), p1 = 0, p2 = (0,0,1), p3 = (cos t, sin t, 1) has a = t.
+ *   state u8: 0 undefined; 2 (t) where c <= -0.5; 1 (g+) where not t and s >= 0; 3 (g-) otherwise -- the wells |a| >= 120, [0, 120), (-120, 0), decided from c
+ *     and s alone, which are correctly rounded on the device and on the host: both agree bit for bit on c, s and the state.
+ *   bin, n_bins = B > 0, w = 360 / B: k = floor((a + 180) / w), k -= B if k >= B (+180 falls into bin 0; a quotient below 0, which only the rounding of
+ *     atan2(-0, x < 0) * (180 / pi) = -180 could give, counts as 0).  The one place where atan2 decides an integer.
+ * Over the frames, per torsion d: n_defined[d]; state_counts[d][4], the frames in each state; n_transitions[d], the f in 1 .. F - 1 whose states at f - 1 and f
+ * are both non-zero and differ; sums[d][2] = (sum c, sum s) over the defined frames -- slabs of 32 frames, each summed in frame order, wave j of four sums the
+ * slabs j, j + 4, .., the four meet in a fixed tree: a function of F alone, no floating-point atomic; hist[d][B] u32, the frames per bin.
+ * Ramachandran maps: pairs[n_pairs][3] u32 = (torsion a, torsion b, group), group < n_groups; hist2[G][B][B] u32 gets + 1 at [group][bin(a)][bin(b)] for every
+ * frame in which both are defined.  The caller chooses the groups (the Python layer: four residue classes, or one group per residue).
+ * Outputs: angles[F][D] f32 (may be NULL; undefined: the bits 0x7FC00000), cossin[F][D][2] f64 (may be NULL; undefined: 0, 0), states[F][D] u8 (may be NULL),
+ * sums, n_defined, state_counts, n_transitions (required with a context), hist (may be NULL), hist2 (may be NULL; pairs are read only with it).
+ * Checks, all before the device is touched: the frame checks of the arp_rmsd_* calls with their messages; then ARP_ERR_BAD_INPUT under the prefix "torsions:" for
+ * n_tors == 0, an atom index >= N, n_bins > 360, hist or hist2 with n_bins == 0, hist2 with n_groups == 0 or n_pairs == 0, a pair's torsion >= D or group >= G.
+ * The device keeps one state byte per (frame, torsion), the slab sums (D x 16 bytes per 32 frames) and the two histograms resident: their bytes against
+ * "rmsd_cap_bytes" are ARP_ERR_CAPACITY.  ctx == NULL runs only the checks (ARP_OK).
+ * The frames go through the device in the upload passes of the arp_rmsd_* calls ("rmsd_chunk_atoms").  Transitions are counted from the state bytes after the last
+ * pass; the only atomics are u32 additions: two calls give identical bytes for every output, for any pass size.  Synchronous. */
+arp_status arp_torsions(arp_context *ctx, arp_structure *topology, uint64_t n_frames, const double *xyz, const uint32_t *quads, uint64_t n_tors, uint32_t n_bins,
+                        const uint32_t *pairs, uint64_t n_pairs, uint32_t n_groups, float *angles, double *cossin, uint8_t *states, double *sums, uint32_t *n_defined,
+                        uint32_t *state_counts, uint32_t *n_transitions, uint32_t *hist, uint32_t *hist2);
+/* The definition above in plain sequential C++ without a device, on already-gathered coordinates quad_xyz n_frames x n_tors x 4 x 3 f64.  The outputs are
+ * arp_torsions' (sums, n_defined, state_counts and n_transitions required).  sums run in frame order: they agree with the device within the reordering of at most F
+ * terms of magnitude <= 1; everything else agrees exactly, except that angles may differ in the last bits of atan2 (and a bin where an angle is within that of an
+ * edge).  n_frames == 0, a non-finite coordinate and the shape checks above are ARP_ERR_BAD_INPUT. */
+arp_status arp_torsions_host(uint64_t n_frames, uint64_t n_tors, const double *quad_xyz, uint32_t n_bins, const uint32_t *pairs, uint64_t n_pairs, uint32_t n_groups,
+                             float *angles, double *cossin, uint8_t *states, double *sums, uint32_t *n_defined, uint32_t *state_counts, uint32_t *n_transitions,
+                             uint32_t *hist, uint32_t *hist2);
 
 /* ---- SASA and SAP statistics over the frames of an ensemble (MD snapshots, NMR models, conformers of one topology) -- DESIGN.md section 3.8 ----
  * Topology, N, frames and xyz exactly as arp_contact_frequencies defines them: model 0 of `topology` is the topology, frame f is xyz[f]
