@@ -162,7 +162,7 @@ arp_status autocorr_cap_check(uint64_t R, uint64_t L, uint64_t cap_bytes) {
 
 // The device buffers of one autocorrelation and the kernels on a device bitmap with its k_timeline_stats results (n_events, longest, count).
 struct AcfDev {
-    std::unique_ptr<char, void (*)(char *)> block{nullptr, [](char *p) { (void)hipFree(p); }}, runs{nullptr, [](char *p) { (void)hipFree(p); }};
+    DevBlock block, runs;
     uint32_t *matrix = nullptr, *lag0 = nullptr, *half = nullptr, *group = nullptr;
     unsigned long long *sums = nullptr;
 };
@@ -178,13 +178,12 @@ arp_status acf_launch(hipStream_t st, const uint32_t *words, uint64_t R, uint64_
     }
     const bool with_sums = (row_keys || group_host) && n_groups;
     if (with_sums && n_groups * n_lags * 8u > (1ull << 31)) { set_error("contact autocorrelation: the sums of %llu groups x %llu lags are more than 2^31 bytes", (unsigned long long)n_groups, (unsigned long long)n_lags); return ARP_ERR_CAPACITY; }
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, seg_align(want_matrix ? R * n_lags * 4u : 0u) + 3 * seg_align(R * 4u) + seg_align(with_sums ? n_groups * n_lags * 8u : 0u) + 256));
-    dv->block.reset(block);
-    Bump bp{block};
-    dv->matrix = want_matrix ? bp.take<uint32_t>(R * n_lags) : nullptr;
-    dv->lag0 = bp.take<uint32_t>(R); dv->half = bp.take<uint32_t>(R); dv->group = bp.take<uint32_t>(R);
-    dv->sums = with_sums ? bp.take<unsigned long long>(n_groups * n_lags) : nullptr;
+    arp_status s;
+    if ((s = dv->block.carve([&](Bump &bp) {
+            dv->matrix = want_matrix ? bp.take<uint32_t>(R * n_lags) : nullptr;
+            dv->lag0 = bp.take<uint32_t>(R); dv->half = bp.take<uint32_t>(R); dv->group = bp.take<uint32_t>(R);
+            dv->sums = with_sums ? bp.take<unsigned long long>(n_groups * n_lags) : nullptr; bp.take<char>(256);  // (slack)
+        })) != ARP_OK) return s;
     HIP_TRY(hipMemsetAsync(dv->half, 0xFF, R * 4u, st));
     if (with_sums) HIP_TRY(hipMemsetAsync(dv->sums, 0, n_groups * n_lags * 8u, st));
     if (group_host) HIP_TRY(hipMemcpyAsync(dv->group, group_host, R * 4u, hipMemcpyHostToDevice, st));
@@ -196,7 +195,6 @@ arp_status acf_launch(hipStream_t st, const uint32_t *words, uint64_t R, uint64_
     } events_owner;
     hipEvent_t(&ev)[2] = events_owner.ev;
     auto stamp = [&](int k) -> arp_status { if (g_debug.timing) { if (!ev[k]) HIP_TRY(hipEventCreate(&ev[k])); HIP_TRY(hipEventRecord(ev[k], st)); } return ARP_OK; };
-    arp_status s;
     if (!continuous) {
         if ((s = stamp(0)) != ARP_OK) return s;
         hipLaunchKernelGGL(k_acf_intermittent, dim3((uint32_t)(R * n_tiles)), dim3(kAcfLagsPerBlock), 0, st, words, W, (uint32_t)n_tiles, o);
@@ -210,12 +208,10 @@ arp_status acf_launch(hipStream_t st, const uint32_t *words, uint64_t R, uint64_
         for (uint64_t r = 0; r < R; r++) off[r + 1u] = off[r] + events[r];
         const uint64_t total = off[R];
         if (total * 4u > (1ull << 31)) { set_error("contact autocorrelation: the run list of %llu runs is more than 2^31 bytes", (unsigned long long)total); return ARP_ERR_CAPACITY; }
-        char *rb = nullptr;
-        HIP_TRY(hipMalloc((void **)&rb, seg_align((R + 1u) * 8u) + seg_align(total * 4u) + 256));
-        dv->runs.reset(rb);
-        Bump rp{rb};
-        unsigned long long *d_off = rp.take<unsigned long long>(R + 1u);
-        uint32_t *d_runs = rp.take<uint32_t>(total);
+        unsigned long long *d_off = nullptr; uint32_t *d_runs = nullptr;
+        if ((s = dv->runs.carve([&](Bump &rp) {
+                d_off = rp.take<unsigned long long>(R + 1u); d_runs = rp.take<uint32_t>(total); rp.take<char>(256);  // (slack)
+            })) != ARP_OK) return s;
         HIP_TRY(hipMemcpyAsync(d_off, off.data(), (R + 1u) * 8u, hipMemcpyHostToDevice, st));
         if ((s = stamp(0)) != ARP_OK) return s;
         hipLaunchKernelGGL(k_acf_runs, dim3((uint32_t)((R + kAcfRowsPerBlock - 1u) / kAcfRowsPerBlock)), dim3(64 * kAcfRowsPerBlock), 0, st, words, (uint32_t)R, W,
@@ -300,12 +296,12 @@ arp_status device_bit_autocorr(arp_context *ctx, uint64_t rows, uint64_t n_bits,
     arp_status s;
     if (acf && (s = autocorr_cap_check(rows, L, cap_bytes)) != ARP_OK) return s;
     if (rows * W * 4u > (1ull << 31)) { set_error("bit autocorrelation: a bitmap of %llu rows x %llu bits is more than 2^31 bytes", (unsigned long long)rows, (unsigned long long)n_bits); return ARP_ERR_CAPACITY; }
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, seg_align(rows * W * 4u) + 5 * seg_align(rows * 4u) + 256));
-    std::unique_ptr<char, void (*)(char *)> block_owner(block, [](char *p) { (void)hipFree(p); });
-    Bump bp{block};
-    uint32_t *d_words = bp.take<uint32_t>(rows * W), *stat[5];
-    for (uint32_t *&p : stat) p = bp.take<uint32_t>(rows);
+    uint32_t *d_words = nullptr, *stat[5];
+    DevBlock block;
+    if ((s = block.carve([&](Bump &bp) {
+            d_words = bp.take<uint32_t>(rows * W);
+            for (uint32_t *&p : stat) p = bp.take<uint32_t>(rows); bp.take<char>(256);  // (slack)
+        })) != ARP_OK) return s;
     HIP_TRY(hipMemcpyAsync(d_words, words, rows * W * 4u, hipMemcpyHostToDevice, st));
     if (n_bits & 31u) {
         hipLaunchKernelGGL(k_bit_mask_tail, dim3((uint32_t)((rows + 255u) / 256u)), dim3(256), 0, st, d_words, rows, W, (1u << (n_bits & 31u)) - 1u);

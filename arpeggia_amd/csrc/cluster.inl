@@ -270,7 +270,7 @@ arp_status cluster_cap_check(uint64_t M, bool by_rows, uint64_t cap_bytes) {
 
 // The device buffers of one clustering.  best[k], k < n_clusters, holds cluster k's (size << 32 | ~centre).
 struct ClusterDev {
-    std::unique_ptr<char, void (*)(char *)> block{nullptr, [](char *p) { (void)hipFree(p); }}, counts_block{nullptr, [](char *p) { (void)hipFree(p); }};
+    DevBlock block, counts_block;
     uint32_t *sizes = nullptr, *cluster = nullptr, *sim = nullptr, *n_neighbours = nullptr, *counts = nullptr;
     std::vector<unsigned long long> best;  // the host's copy, n_clusters entries
 };
@@ -279,15 +279,13 @@ struct ClusterDev {
 struct ClusterBufs { uint32_t *adj = nullptr, *alive[2] = {nullptr, nullptr}; unsigned long long *best = nullptr; uint64_t KA = 0, last = 0; };
 arp_status cluster_alloc(hipStream_t st, uint64_t M, uint32_t max_clusters, ClusterDev *dv, ClusterBufs *b) {
     const uint64_t KA = (M + 31u) / 32u, last = std::min<uint64_t>(M, max_clusters);  // launch `last` applies the last cluster there can be
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, seg_align(M * KA * 4u) + 4 * seg_align(M * 4u) + 2 * seg_align(KA * 4u) + seg_align((last + 2u) * 8u) + 256));
-    dv->block.reset(block);
-    Bump bp{block};
     b->KA = KA; b->last = last;
-    b->adj = bp.take<uint32_t>(M * KA);
-    dv->sizes = bp.take<uint32_t>(M); dv->cluster = bp.take<uint32_t>(M); dv->sim = bp.take<uint32_t>(M); dv->n_neighbours = bp.take<uint32_t>(M);
-    b->alive[0] = bp.take<uint32_t>(KA); b->alive[1] = bp.take<uint32_t>(KA);
-    b->best = bp.take<unsigned long long>(last + 2u);
+    if (arp_status s = dv->block.carve([&](Bump &bp) {
+            b->adj = bp.take<uint32_t>(M * KA);
+            dv->sizes = bp.take<uint32_t>(M); dv->cluster = bp.take<uint32_t>(M); dv->sim = bp.take<uint32_t>(M); dv->n_neighbours = bp.take<uint32_t>(M);
+            b->alive[0] = bp.take<uint32_t>(KA); b->alive[1] = bp.take<uint32_t>(KA);
+            b->best = bp.take<unsigned long long>(last + 2u); bp.take<char>(256);  // (slack)
+        }); s != ARP_OK) return s;
     HIP_TRY(hipMemsetAsync(b->best, 0, (last + 2u) * 8u, st));
     hipLaunchKernelGGL(k_cluster_init, dim3((uint32_t)((M + 255u) / 256u)), dim3(256), 0, st, (uint32_t)M, KA, dv->cluster, dv->sim, b->alive[1]);
     HIP_TRY(hipGetLastError());
@@ -353,10 +351,7 @@ arp_status cluster_counts_launch(hipStream_t st, const uint32_t *words, uint64_t
                   (unsigned long long)(R * C * 4u), (unsigned long long)cap_bytes);
         return ARP_ERR_CAPACITY;
     }
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, seg_align(R * C * 4u)));
-    dv->counts_block.reset(block);
-    dv->counts = reinterpret_cast<uint32_t *>(block);
+    if (arp_status s = dv->counts_block.carve([&](Bump &bp) { dv->counts = bp.take<uint32_t>(R * C); }); s != ARP_OK) return s;
     hipLaunchKernelGGL(k_cluster_counts, dim3((uint32_t)R), dim3(256), 0, st, words, W, (const uint32_t *)dv->cluster, (uint32_t)C, dv->counts);
     HIP_TRY(hipGetLastError());
     return ARP_OK;
@@ -432,10 +427,9 @@ arp_status device_clusters(arp_context *ctx, const FreqJob &job, float min_simil
         return want_counts ? cluster_counts_host(0, 1, out) : ARP_OK;
     }
     // 3. the bit transpose: frames become the bit-rows
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, seg_align(F * WR * 4u)));
-    std::unique_ptr<char, void (*)(char *)> block_owner(block, [](char *p) { (void)hipFree(p); });
-    uint32_t *wordsT = reinterpret_cast<uint32_t *>(block);
+    uint32_t *wordsT = nullptr;
+    DevBlock block;
+    if ((s = block.carve([&](Bump &bp) { wordsT = bp.take<uint32_t>(F * WR); })) != ARP_OK) return s;
     if ((s = bit_transpose_launch(st, dev.words, R, W, F, wordsT, WR)) != ARP_OK) return s;
     lap("transpose");
     // 4. neighbour bits, rounds, counts
@@ -474,11 +468,12 @@ arp_status device_bit_cluster(arp_context *ctx, uint64_t rows, uint64_t n_bits, 
     arp_status s = cluster_cap_check(M, by_rows, cap_bytes);
     if (s != ARP_OK) return s;
     if (rows * W * 4u > (1ull << 31)) { set_error("bit cluster: a bitmap of %llu rows x %llu bits is more than 2^31 bytes", (unsigned long long)rows, (unsigned long long)n_bits); return ARP_ERR_CAPACITY; }
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, seg_align(rows * W * 4u) + seg_align(by_rows ? 0u : n_bits * WR * 4u)));
-    std::unique_ptr<char, void (*)(char *)> block_owner(block, [](char *p) { (void)hipFree(p); });
-    Bump bp{block};
-    uint32_t *d_words = bp.take<uint32_t>(rows * W);
+    uint32_t *d_words = nullptr, *wordsT = nullptr;
+    DevBlock block;
+    if ((s = block.carve([&](Bump &bp) {
+            d_words = bp.take<uint32_t>(rows * W);
+            if (!by_rows) wordsT = bp.take<uint32_t>(n_bits * WR);
+        })) != ARP_OK) return s;
     HIP_TRY(hipMemcpyAsync(d_words, words, rows * W * 4u, hipMemcpyHostToDevice, st));
     if (n_bits & 31u) {
         hipLaunchKernelGGL(k_bit_mask_tail, dim3((uint32_t)((rows + 255u) / 256u)), dim3(256), 0, st, d_words, rows, W, (1u << (n_bits & 31u)) - 1u);
@@ -487,7 +482,6 @@ arp_status device_bit_cluster(arp_context *ctx, uint64_t rows, uint64_t n_bits, 
     const uint32_t *A = d_words;
     uint64_t K = W;
     if (!by_rows) {
-        uint32_t *wordsT = bp.take<uint32_t>(n_bits * WR);
         if ((s = bit_transpose_launch(st, d_words, rows, W, n_bits, wordsT, WR)) != ARP_OK) return s;
         A = wordsT;
         K = WR;

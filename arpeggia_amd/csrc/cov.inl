@@ -161,13 +161,12 @@ arp_status device_cov(hipStream_t st, StreamLapTimer &lap, const double *XM, con
     }
     const uint64_t part_items = std::max(out->cov ? full.part_items() : 0u, out->dccm ? atoms.part_items() : 0u);
     const uint64_t cov_bytes = out->cov ? 9u * m_pad * m_pad * 8u : 0u, dccm_bytes = out->dccm ? m_pad * m_pad * 4u : 0u;
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, seg_align(F * 3u * m_pad * 8u) + seg_align(part_items * 8u) + seg_align(cov_bytes) + seg_align(dccm_bytes) + seg_align(m_pad * 8u) + 256));
-    std::unique_ptr<char, void (*)(char *)> block_owner(block, [](char *p) { (void)hipFree(p); });
-    Bump bp{block};
-    double *D = bp.take<double>(F * 3u * m_pad), *part = bp.take<double>(part_items), *d_cov = reinterpret_cast<double *>(bp.take<char>(cov_bytes));
-    float *d_dccm = reinterpret_cast<float *>(bp.take<char>(dccm_bytes));
-    double *var = bp.take<double>(m_pad);
+    double *D = nullptr, *part = nullptr, *d_cov = nullptr, *var = nullptr; float *d_dccm = nullptr;
+    DevBlock block;
+    if (arp_status s = block.carve([&](Bump &bp) {
+            D = bp.take<double>(F * 3u * m_pad); part = bp.take<double>(part_items); d_cov = reinterpret_cast<double *>(bp.take<char>(cov_bytes));
+            d_dccm = reinterpret_cast<float *>(bp.take<char>(dccm_bytes)); var = bp.take<double>(m_pad); bp.take<char>(256);  // (slack)
+        }); s != ARP_OK) return s;
     hipLaunchKernelGGL(k_cov_dev, dim3((uint32_t)((F * m_pad + 255u) / 256u)), dim3(256), 0, st, XM, R, mean_m, F, (uint32_t)m, (uint32_t)m_pad, D);
     HIP_TRY(hipGetLastError());
     lap("cov_dev");
@@ -248,14 +247,13 @@ arp_status device_project(arp_context *ctx, const ProjectJob &job, double *proj)
     StreamLapTimer lap("  project %-10s %8.3f ms\n", st);
     const uint64_t N = job.n_atoms, F = job.n_frames, m = job.n_msel, k = job.k;
     if ((k + kProjTile - 1u) / kProjTile > 65535u) { set_error("project: %llu modes are more than one launch covers", (unsigned long long)k); return ARP_ERR_CAPACITY; }
-    const uint64_t per = std::min<uint64_t>(F, std::max<uint64_t>(1, (job.chunk_atoms ? job.chunk_atoms : kFreqAutoAtoms) / std::max<uint64_t>(N, 1)));
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, seg_align(per * N * 24u) + seg_align(F * 96u) + seg_align(m * 4u) + seg_align(m * 24u) + seg_align(k * 3u * m * 8u) + seg_align(F * k * 8u) + 256));
-    std::unique_ptr<char, void (*)(char *)> block_owner(block, [](char *p) { (void)hipFree(p); });
-    Bump bp{block};
-    double *stage = bp.take<double>(per * N * 3u), *tr = bp.take<double>(F * 12u);
-    uint32_t *msel = bp.take<uint32_t>(m);
-    double *mean = bp.take<double>(m * 3u), *modes = bp.take<double>(k * 3u * m), *d_proj = bp.take<double>(F * k);
+    const uint64_t per = frames_per_pass(job.chunk_atoms, N, F);
+    double *stage = nullptr, *tr = nullptr, *mean = nullptr, *modes = nullptr, *d_proj = nullptr; uint32_t *msel = nullptr;
+    DevBlock block;
+    if (arp_status s = block.carve([&](Bump &bp) {
+            stage = bp.take<double>(per * N * 3u); tr = bp.take<double>(F * 12u); msel = bp.take<uint32_t>(m);
+            mean = bp.take<double>(m * 3u); modes = bp.take<double>(k * 3u * m); d_proj = bp.take<double>(F * k); bp.take<char>(256);  // (slack)
+        }); s != ARP_OK) return s;
     std::vector<double> identity;
     if (!job.transforms) {
         identity.assign(F * 12u, 0.0);

@@ -213,22 +213,18 @@ arp_status device_dssp(arp_context *ctx, const DsspJob &job, DsspOut *out) {
     StreamLapTimer lap("  dssp %-10s %8.3f ms\n", st);
     const uint64_t N = job.n_atoms, F = job.n_frames, R = job.n_res;
     const uint64_t tiles = (R + kDsspTile - 1u) / kDsspTile;
-    uint64_t per = std::min<uint64_t>(F, std::max<uint64_t>(1, (job.chunk_atoms ? job.chunk_atoms : kFreqAutoAtoms) / std::max<uint64_t>(N, 1)));
+    uint64_t per = frames_per_pass(job.chunk_atoms, N, F);
     per = std::min<uint64_t>(per, std::max<uint64_t>(1, ((1ull << 31) - 1u) / std::max(tiles, (R + kDsspPack - 1u) / kDsspPack)));  // one launch covers a pass
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, seg_align(per * N * 24u) + seg_align(R * 16u) + seg_align(R) + seg_align(per * R * 72u) + seg_align(per * R * 48u) + 3u * seg_align(per * R) +
-                                           2u * seg_align(per * R * 8u) + seg_align(per * R) + seg_align(R * 32u) + seg_align(per * 32u) + 256));
-    std::unique_ptr<char, void (*)(char *)> block_owner(block, [](char *p) { (void)hipFree(p); });
-    Bump bp{block};
-    double *stage = bp.take<double>(per * N * 3u);
-    uint32_t *bb = bp.take<uint32_t>(R * 4u);
-    uint8_t *flags = bp.take<uint8_t>(R);
-    double *A = bp.take<double>(per * R * 9u), *D = bp.take<double>(per * R * 6u);
-    uint8_t *bits = bp.take<uint8_t>(per * R), *ok = bp.take<uint8_t>(per * R), *code = bp.take<uint8_t>(per * R);
-    uint32_t *acc = bp.take<uint32_t>(per * R * 2u);
-    float *en = bp.take<float>(per * R * 2u);
-    uint8_t *mark = bp.take<uint8_t>(per * R);
-    uint32_t *counts = bp.take<uint32_t>(R * 8u), *fcounts = bp.take<uint32_t>(per * 8u);
+    double *stage = nullptr, *A = nullptr, *D = nullptr; uint32_t *bb = nullptr, *acc = nullptr, *counts = nullptr, *fcounts = nullptr; float *en = nullptr;
+    uint8_t *flags = nullptr, *bits = nullptr, *ok = nullptr, *code = nullptr, *mark = nullptr;
+    DevBlock block;
+    if (arp_status s = block.carve([&](Bump &bp) {
+            stage = bp.take<double>(per * N * 3u); bb = bp.take<uint32_t>(R * 4u); flags = bp.take<uint8_t>(R);
+            A = bp.take<double>(per * R * 9u); D = bp.take<double>(per * R * 6u);
+            bits = bp.take<uint8_t>(per * R); ok = bp.take<uint8_t>(per * R); code = bp.take<uint8_t>(per * R);
+            acc = bp.take<uint32_t>(per * R * 2u); en = bp.take<float>(per * R * 2u); mark = bp.take<uint8_t>(per * R);
+            counts = bp.take<uint32_t>(R * 8u); fcounts = bp.take<uint32_t>(per * 8u); bp.take<char>(256);  // (slack)
+        }); s != ARP_OK) return s;
     HIP_TRY(hipMemcpyAsync(bb, job.bb, R * 16u, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(flags, job.flags, R, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(counts, 0, R * 32u, st));

@@ -17,6 +17,10 @@
 constexpr uint32_t kFreqKeyShiftI = 34, kFreqKeyShiftJ = 5;
 constexpr uint32_t kFreqCodeBits = 5, kFreqFrameBitsMax = 17;  // residue level: the code's bits, and the most tag bits a key gets
 constexpr uint64_t kFreqAutoAtoms = 1u << 21;  // atoms per pass when the knob freq_chunk_atoms is 0: 1ubq x 3000 frames, 6bft x 230
+// the frames of an upload pass of the calls that stage whole frames of N atoms (rmsd.inl and behind): the knob's atom budget, else kFreqAutoAtoms; 1 <= it <= F
+inline uint64_t frames_per_pass(uint64_t chunk_atoms, uint64_t N, uint64_t F) {
+    return std::min<uint64_t>(F, std::max<uint64_t>(1, (chunk_atoms ? chunk_atoms : kFreqAutoAtoms) / std::max<uint64_t>(N, 1)));
+}
 
 // {frames, min, max} of one key; min / max are order-preserving codes of the f32 distances, so that unsigned atomics order them like floats
 struct FreqVal { uint32_t count, mn, mx; };
@@ -205,12 +209,18 @@ uint32_t freq_blocks(unsigned long long items) { return (uint32_t)std::max<unsig
 
 // the aggregate and one chunk's items: kin / vin hold the aggregate (first n_agg) + the new items; the sort and the reduction write the other set
 struct FreqBufs {
-    char *block = nullptr;
+    DevBlock block;
     uint64_t cap = 0;  // items
     unsigned long long *kin = nullptr, *ks = nullptr, *kout = nullptr;
     FreqVal *vin = nullptr, *vout = nullptr;
     uint32_t *iota = nullptr, *is = nullptr, *head = nullptr, *scan = nullptr, *counter = nullptr;
     void *tmp = nullptr; size_t tmp_bytes = 0;
+    void layout(Bump &bp) {  // cap and tmp_bytes are set
+        kin = bp.take<unsigned long long>(cap); ks = bp.take<unsigned long long>(cap); kout = bp.take<unsigned long long>(cap);
+        vin = bp.take<FreqVal>(cap); vout = bp.take<FreqVal>(cap);
+        iota = bp.take<uint32_t>(cap); is = bp.take<uint32_t>(cap); head = bp.take<uint32_t>(cap); scan = bp.take<uint32_t>(cap);
+        counter = bp.take<uint32_t>(64); tmp = bp.take<char>(tmp_bytes);
+    }
 };
 arp_status freq_alloc(FreqBufs *b, uint64_t cap, uint64_t keep, hipStream_t st) {
     if (cap > 0x7FFFFFF0ull) { set_error("contact frequencies: more than 2^31 items in one pass (lower freq_chunk_atoms)"); return ARP_ERR_CAPACITY; }
@@ -219,23 +229,15 @@ arp_status freq_alloc(FreqBufs *b, uint64_t cap, uint64_t keep, hipStream_t st) 
                                                (uint32_t *)nullptr, (int)cap, 0, 64, st));
     HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)cap, st));
     const size_t tmp = std::max(sort_bytes, scan_bytes);
-    const uint64_t bytes = 3 * seg_align(cap * 8) + 2 * seg_align(cap * sizeof(FreqVal)) + 4 * seg_align(cap * 4) + seg_align(256) + seg_align(tmp);
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, bytes));
-    Bump bp{block};
     FreqBufs nb;
-    nb.block = block; nb.cap = cap;
-    nb.kin = bp.take<unsigned long long>(cap); nb.ks = bp.take<unsigned long long>(cap); nb.kout = bp.take<unsigned long long>(cap);
-    nb.vin = bp.take<FreqVal>(cap); nb.vout = bp.take<FreqVal>(cap);
-    nb.iota = bp.take<uint32_t>(cap); nb.is = bp.take<uint32_t>(cap); nb.head = bp.take<uint32_t>(cap); nb.scan = bp.take<uint32_t>(cap);
-    nb.counter = bp.take<uint32_t>(64); nb.tmp = bp.take<char>(tmp); nb.tmp_bytes = tmp;
-    if (keep && b->block) {  // the aggregate moves into the new block
+    nb.cap = cap; nb.tmp_bytes = tmp;
+    if (arp_status s = nb.block.carve([&](Bump &bp) { nb.layout(bp); }); s != ARP_OK) return s;
+    if (keep && b->block.p) {  // the aggregate moves into the new block
         HIP_TRY(hipMemcpyAsync(nb.kin, b->kin, keep * 8, hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemcpyAsync(nb.vin, b->vin, keep * sizeof(FreqVal), hipMemcpyDeviceToDevice, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
-    if (b->block) (void)hipFree(b->block);
-    *b = nb;
+    *b = std::move(nb);  // (frees the old block)
     return ARP_OK;
 }
 }  // namespace
@@ -277,31 +279,24 @@ arp_status freq_sweep(arp_context *ctx, const FreqJob &job, FreqRowsHost *out, T
                              {job.cand, n_cand * 4}, {job.plane_bits, n_rings ? n : 0},
                              // the water and polar atoms of the topology (ARP_FREQ_WATERS; nothing otherwise)
                              {job.water, n_water * 4}, {job.polar, n_polar * 4}};
-    uint64_t topo_bytes = 0;
-    for (const Seg &g : topo_seg) topo_bytes += seg_align(g.bytes);
     const uint64_t pn = per * n, pr = per * nr, ph = per * nh;
-    const uint64_t pack_bytes = seg_align(pn * 24) + 3 * seg_align(pn * 8) + 5 * seg_align(pn * 4) + seg_align((pr + 1) * 4) + 2 * seg_align(pr * 4) + seg_align(ph * 4);
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, topo_bytes + pack_bytes + seg_align(per * n_slots * sizeof(PlaneD)) + 256));
-    std::unique_ptr<char, void (*)(char *)> block_owner(block, [](char *p) { (void)hipFree(p); });
-    Bump bp{block};
-    const void *topo_dev[16];
-    for (int k = 0; k < 16; k++) {
-        char *d = bp.take<char>(topo_seg[k].bytes);
-        topo_dev[k] = d;
-        if (topo_seg[k].bytes) HIP_TRY(hipMemcpyAsync(d, topo_seg[k].src, topo_seg[k].bytes, hipMemcpyHostToDevice, st));
-    }
+    char *topo_dev[16];
+    double *xyz = nullptr; FreqPack pk; PlaneD *planes = nullptr;  // planes: one pass's ring planes, frames x slots
+    DevBlock block;
+    if (arp_status s = block.carve([&](Bump &bp) {
+            for (int k = 0; k < 16; k++) topo_dev[k] = bp.take<char>(topo_seg[k].bytes);
+            xyz = bp.take<double>(pn * 3);
+            pk.x = bp.take<double>(pn); pk.y = bp.take<double>(pn); pk.z = bp.take<double>(pn);
+            pk.attr = bp.take<uint32_t>(pn); pk.res_ord = bp.take<uint32_t>(pn); pk.chain_rank = bp.take<uint32_t>(pn); pk.model = bp.take<uint32_t>(pn);
+            pk.res_id = bp.take<uint32_t>(pn); pk.res_h_ptr = bp.take<uint32_t>(pr + 1); pk.res_cb = bp.take<uint32_t>(pr); pk.res_sg = bp.take<uint32_t>(pr);
+            pk.res_h_idx = bp.take<uint32_t>(ph); planes = bp.take<PlaneD>(per * n_slots); bp.take<char>(256);  // (slack)
+        }); s != ARP_OK) return s;
+    for (int k = 0; k < 16; k++)
+        if (topo_seg[k].bytes) HIP_TRY(hipMemcpyAsync(topo_dev[k], topo_seg[k].src, topo_seg[k].bytes, hipMemcpyHostToDevice, st));
     FreqTopo tp{(uint32_t)n, (uint32_t)nr, (uint32_t)nh, (const uint32_t *)topo_dev[0], (const uint32_t *)topo_dev[1], (const uint32_t *)topo_dev[2],
                 (const uint32_t *)topo_dev[3], (const uint32_t *)topo_dev[4], (const uint32_t *)topo_dev[5], (const uint32_t *)topo_dev[6], (const uint32_t *)topo_dev[7]};
-    double *xyz = bp.take<double>(pn * 3);
-    FreqPack pk;
-    pk.x = bp.take<double>(pn); pk.y = bp.take<double>(pn); pk.z = bp.take<double>(pn);
-    pk.attr = bp.take<uint32_t>(pn); pk.res_ord = bp.take<uint32_t>(pn); pk.chain_rank = bp.take<uint32_t>(pn); pk.model = bp.take<uint32_t>(pn);
-    pk.res_id = bp.take<uint32_t>(pn); pk.res_h_ptr = bp.take<uint32_t>(pr + 1); pk.res_cb = bp.take<uint32_t>(pr); pk.res_sg = bp.take<uint32_t>(pr);
-    pk.res_h_idx = bp.take<uint32_t>(ph);
     const FreqRings fr{(uint32_t)n_rings, (uint32_t)n_slots, (uint32_t)n_cand, (const uint32_t *)topo_dev[10], (const uint32_t *)topo_dev[11], (const uint32_t *)topo_dev[9],
                        (const uint32_t *)topo_dev[12], (const uint8_t *)topo_dev[13], (const RingEnt *)topo_dev[8]};
-    PlaneD *planes = bp.take<PlaneD>(per * n_slots);  // one pass's ring planes, frames x slots
     const uint32_t ring_tiles = (uint32_t)((n_rings + kFreqRingTile - 1) / kFreqRingTile);
     const FreqWaters fw{(uint32_t)n_water, (uint32_t)n_polar, (const uint32_t *)topo_dev[14], (const uint32_t *)topo_dev[15]};
     lap("topology upload");
@@ -318,7 +313,6 @@ arp_status freq_sweep(arp_context *ctx, const FreqJob &job, FreqRowsHost *out, T
     const auto expand_kernel = job.residue ? k_freq_expand<true> : k_freq_expand<false>;
     const auto ring_rows_kernel = job.residue ? k_freq_ring_rows<true> : k_freq_ring_rows<false>;
     FreqBufs fb;
-    struct FreeBufs { FreqBufs *b; ~FreeBufs() { if (b->block) (void)hipFree(b->block); } } fb_owner{&fb};
     uint64_t n_agg = 0;
     for (uint64_t f0 = 0; f0 < F; f0 += per) {
         const uint64_t fc = std::min<uint64_t>(per, F - f0);
@@ -355,7 +349,7 @@ arp_status freq_sweep(arp_context *ctx, const FreqJob &job, FreqRowsHost *out, T
         }
         // 3. expand into (key, value) items behind the aggregate, the ring items behind the atom items, the water bridges behind both; grown and
         // repeated when they do not fit
-        if (!fb.block && (s = freq_alloc(&fb, g_debug.freq_cap_items > 0 ? (uint64_t)g_debug.freq_cap_items : std::max<uint64_t>(1u << 16, 2 * n_pairs), 0, st)) != ARP_OK) return s;
+        if (!fb.block.p && (s = freq_alloc(&fb, g_debug.freq_cap_items > 0 ? (uint64_t)g_debug.freq_cap_items : std::max<uint64_t>(1u << 16, 2 * n_pairs), 0, st)) != ARP_OK) return s;
         uint32_t counted[2] = {0u, 0u};  // {items, the water kernel's error word}
         const size_t counted_bytes = n_water ? 8 : 4;
         for (int attempt = 0;; attempt++) {

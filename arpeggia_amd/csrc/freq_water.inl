@@ -112,13 +112,13 @@ arp_status device_water_bridges(arp_context *ctx, const FreqJob &job, std::vecto
     const uint64_t budget = job.chunk_atoms ? job.chunk_atoms : kFreqAutoAtoms;
     const uint64_t per = std::min<uint64_t>({std::max<uint64_t>(1, budget / n), F, 0x7FFFFFF0ull / std::max<uint64_t>(n, tiles)});
     if (per == 0) { set_error("water bridges: one frame exceeds 32-bit indices"); return ARP_ERR_BAD_INPUT; }
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, 3 * seg_align(n * 4) + seg_align(nw * 4) + seg_align(np * 4) + seg_align(per * n * 24) + seg_align(256)));
-    std::unique_ptr<char, void (*)(char *)> block_owner(block, [](char *p) { (void)hipFree(p); });
-    Bump bp{block};
-    uint32_t *attr = bp.take<uint32_t>(n), *res_ord = bp.take<uint32_t>(n), *chain_rank = bp.take<uint32_t>(n), *water = bp.take<uint32_t>(nw), *polar = bp.take<uint32_t>(np);
-    double *xyz = bp.take<double>(per * n * 3);
-    uint32_t *counter = bp.take<uint32_t>(64);
+    uint32_t *attr = nullptr, *res_ord = nullptr, *chain_rank = nullptr, *water = nullptr, *polar = nullptr, *counter = nullptr; double *xyz = nullptr;
+    DevBlock block;
+    arp_status s;
+    if ((s = block.carve([&](Bump &bp) {
+            attr = bp.take<uint32_t>(n); res_ord = bp.take<uint32_t>(n); chain_rank = bp.take<uint32_t>(n); water = bp.take<uint32_t>(nw); polar = bp.take<uint32_t>(np);
+            xyz = bp.take<double>(per * n * 3); counter = bp.take<uint32_t>(64);
+        })) != ARP_OK) return s;
     HIP_TRY(hipMemcpyAsync(attr, job.attr, n * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(res_ord, job.res_ord, n * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(chain_rank, job.chain_rank, n * 4, hipMemcpyHostToDevice, st));
@@ -136,7 +136,7 @@ arp_status device_water_bridges(arp_context *ctx, const FreqJob &job, std::vecto
         rec_cap = cap;
         return ARP_OK;
     };
-    arp_status s = rec_alloc(g_debug.freq_cap_items > 0 ? (uint64_t)g_debug.freq_cap_items : std::max<uint64_t>(1u << 14, 4 * nw));
+    s = rec_alloc(g_debug.freq_cap_items > 0 ? (uint64_t)g_debug.freq_cap_items : std::max<uint64_t>(1u << 14, 4 * nw));
     if (s != ARP_OK) return s;
     for (uint64_t f0 = 0; f0 < F; f0 += per) {
         const uint64_t fc = std::min<uint64_t>(per, F - f0);

@@ -1,4 +1,5 @@
-// Host-side declarations shared by the host sources (engine.cpp, batch.cpp, sasa_dev.cpp, structure.cpp, table*.cpp, table_dev.hip).
+// Host-side declarations shared by the host sources (engine.cpp, batch.cpp, sasa_dev.cpp, structure.cpp, table*.cpp, table_dev.hip), and the rule
+// by which a block of several arrays is planned and carved (seg_align, Carver, Bump, planned_bytes, carve_block).  It includes no HIP header: the rule is checked in a host program of its own (tests/hostcheck/carve_check.cpp).
 #pragma once
 #include <array>
 #include <chrono>
@@ -21,12 +22,29 @@ namespace arp {
 
 void set_error(const char *fmt, ...);
 
-// A block that holds several arrays is carved into 256-byte aligned segments.  The rule lives here and nowhere else.
+// A block that holds several arrays is carved into 256-byte aligned segments.  The rule lives here and nowhere else: a block's size is never
+// written down, it is what its layout -- the sequence of take() calls that hands out its arrays -- adds up to.  The layout is walked twice: once
+// without a block, to plan the bytes to allocate, and once on the block, to carve it (planned_bytes, carve_block).
 constexpr uint64_t seg_align(uint64_t bytes) { return (bytes + 255u) & ~255ull; }
 struct Carver {  // the offset of the next segment; offsets only: one layout serves a device block and its pinned twin
     uint64_t off = 0;
     uint64_t take(uint64_t bytes) { const uint64_t at = off; off += seg_align(bytes); return at; }
 };
+struct Bump {  // typed pieces of one block; without a block (base == nullptr) it plans: take() moves the offset on and returns nullptr
+    char *base = nullptr; Carver c{};
+    template <class T> T *take(uint64_t count) { const uint64_t at = c.take(count * sizeof(T)); return base ? reinterpret_cast<T *>(base + at) : nullptr; }
+};
+// A layout is a callable void(Bump &) that assigns the pointers of a call.  The bytes a block needs to hold it:
+template <class Layout> uint64_t planned_bytes(Layout &&layout) { Bump plan; layout(plan); return plan.c.off; }
+// The pointers into `block`, which holds `planned` bytes.  A layout that asks for other sizes on its second walk (one that changes a value it
+// reads, say) is an error of the program: a status, and the caller launches nothing.
+template <class Layout> arp_status carve_block(char *block, uint64_t planned, Layout &&layout) {
+    Bump b{block};
+    layout(b);
+    if (b.c.off == planned) return ARP_OK;
+    set_error("internal error: a block planned at %llu bytes was carved into %llu", (unsigned long long)planned, (unsigned long long)b.c.off);
+    return ARP_ERR_HIP;
+}
 
 // No exception may cross the C ABI (SURVEY.md 8b "Errors": the reference panics, a C boundary returns a status).  Every status-returning entry
 // point that allocates or starts threads is a function-try-block that ends in this: `extern "C" arp_status f(...) try { ... } ARP_ABI_CATCH`.

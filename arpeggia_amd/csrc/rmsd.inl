@@ -320,18 +320,16 @@ arp_status device_rmsd(arp_context *ctx, const RmsdJob &job, float *out, Cluster
     HIP_TRY(hipSetDevice(context_device(ctx)));
     StreamLapTimer lap("  rmsd %-10s %8.3f ms\n", st);
     const uint64_t N = job.n_atoms, F = job.n_frames, n = job.n_sel, n_pad = rmsd_n_pad(n);
-    const uint64_t per = std::min<uint64_t>(F, std::max<uint64_t>(1, (job.chunk_atoms ? job.chunk_atoms : kFreqAutoAtoms) / std::max<uint64_t>(N, 1)));
+    const uint64_t per = frames_per_pass(job.chunk_atoms, N, F);
     const bool ext_ref = job.kind == RmsdJob::kReference && job.ref_xyz;
     const uint64_t out_bytes = job.kind == RmsdJob::kMatrix ? F * F * 4u : job.kind == RmsdJob::kReference ? F * 4u : 0u;
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, seg_align(F * 3u * n_pad * 8u) + seg_align(F * 8u) + seg_align(n * 4u) + seg_align(per * N * 24u) + seg_align(3u * n_pad * 8u) + seg_align(8u) +
-                                           seg_align(out_bytes) + 256));
-    std::unique_ptr<char, void (*)(char *)> block_owner(block, [](char *p) { (void)hipFree(p); });
-    Bump bp{block};
-    double *X = bp.take<double>(F * 3u * n_pad), *G = bp.take<double>(F);
-    uint32_t *sel = bp.take<uint32_t>(n);
-    double *stage = bp.take<double>(per * N * 3u), *XR = bp.take<double>(3u * n_pad), *GR = bp.take<double>(1);
-    float *d_out = reinterpret_cast<float *>(bp.take<char>(out_bytes));
+    double *X = nullptr, *G = nullptr, *stage = nullptr, *XR = nullptr, *GR = nullptr; uint32_t *sel = nullptr; float *d_out = nullptr;
+    DevBlock block;
+    if (arp_status s = block.carve([&](Bump &bp) {
+            X = bp.take<double>(F * 3u * n_pad); G = bp.take<double>(F); sel = bp.take<uint32_t>(n);
+            stage = bp.take<double>(per * N * 3u); XR = bp.take<double>(3u * n_pad); GR = bp.take<double>(1);
+            d_out = reinterpret_cast<float *>(bp.take<char>(out_bytes)); bp.take<char>(256);  // (slack)
+        }); s != ARP_OK) return s;
     HIP_TRY(hipMemcpyAsync(sel, job.sel, n * 4u, hipMemcpyHostToDevice, st));
     for (uint64_t f0 = 0; f0 < F; f0 += per) {
         const uint64_t fc = std::min<uint64_t>(per, F - f0);

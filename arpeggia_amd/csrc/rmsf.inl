@@ -247,25 +247,22 @@ arp_status device_rmsf(arp_context *ctx, const RmsfJob &job, RmsfOut *out) {
     const uint64_t N = job.n_atoms, F = job.n_frames, n = job.n_sel, n_pad = rmsd_n_pad(n);
     const bool own = job.msel != nullptr;  // a measured set of its own
     const uint64_t m = own ? job.n_msel : n, m_pad = rmsd_n_pad(m), w_pad = std::max(n_pad, m_pad);
-    const uint64_t per = std::min<uint64_t>(F, std::max<uint64_t>(1, (job.chunk_atoms ? job.chunk_atoms : kFreqAutoAtoms) / std::max<uint64_t>(N, 1)));
+    const uint64_t per = frames_per_pass(job.chunk_atoms, N, F);
     const uint64_t slabs = (F + kRmsfSlab - 1u) / kRmsfSlab, fin_n = (3u * n_pad + kRmsfFinish - 1u) / kRmsfFinish, fin_m = (3u * m_pad + kRmsfFinish - 1u) / kRmsfFinish,
                    fin_dev = (m_pad + kRmsfFinish - 1u) / kRmsfFinish;
     const uint64_t tiles_n = (n_pad + kRmsfTile - 1u) / kRmsfTile, tiles_m = (m_pad + kRmsfTile - 1u) / kRmsfTile;
     if (slabs * std::max(tiles_n, tiles_m) >= (1ull << 31)) { set_error("rmsf: %llu frames x %llu atoms are more than one launch covers", (unsigned long long)F, (unsigned long long)std::max(n, m)); return ARP_ERR_CAPACITY; }
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, seg_align(F * 3u * n_pad * 8u) + seg_align(F * 8u) + seg_align(n * 4u) + seg_align(m * 4u) + seg_align(own ? F * 3u * m_pad * 8u : 0u) +
-                                           seg_align(F * 24u) + seg_align(per * N * 24u) + seg_align(3u * n_pad * 8u) + seg_align(8u) + seg_align(24u) + seg_align(F * 72u) +
-                                           2u * seg_align(3u * n_pad * 8u) + seg_align(3u * m_pad * 8u) + seg_align(slabs * 3u * w_pad * 8u) + seg_align(fin_n * 8u) + seg_align(8u) +
-                                           seg_align(m * 4u) + seg_align(F * 4u) + 256));
-    std::unique_ptr<char, void (*)(char *)> block_owner(block, [](char *p) { (void)hipFree(p); });
-    Bump bp{block};
-    double *X = bp.take<double>(F * 3u * n_pad), *G = bp.take<double>(F);
-    uint32_t *sel = bp.take<uint32_t>(n), *msel = bp.take<uint32_t>(m);
-    double *XM = own ? bp.take<double>(F * 3u * m_pad) : X, *C = bp.take<double>(F * 3u);
-    double *stage = bp.take<double>(per * N * 3u), *XR = bp.take<double>(3u * n_pad), *GR = bp.take<double>(1), *CR = bp.take<double>(3), *R = bp.take<double>(F * 9u);
-    double *M2[2] = {bp.take<double>(3u * n_pad), bp.take<double>(3u * n_pad)};
-    double *MM = bp.take<double>(3u * m_pad), *part = bp.take<double>(slabs * 3u * w_pad), *block_d2 = bp.take<double>(fin_n), *d_change = bp.take<double>(1);
-    float *d_rmsf = bp.take<float>(m), *d_frame = bp.take<float>(F);
+    double *X = nullptr, *G = nullptr, *XM = nullptr, *C = nullptr, *stage = nullptr, *XR = nullptr, *GR = nullptr, *CR = nullptr, *R = nullptr, *M2[2] = {nullptr, nullptr};
+    double *MM = nullptr, *part = nullptr, *block_d2 = nullptr, *d_change = nullptr; uint32_t *sel = nullptr, *msel = nullptr; float *d_rmsf = nullptr, *d_frame = nullptr;
+    DevBlock block;
+    if (arp_status s = block.carve([&](Bump &bp) {
+            X = bp.take<double>(F * 3u * n_pad); G = bp.take<double>(F); sel = bp.take<uint32_t>(n); msel = bp.take<uint32_t>(m);
+            XM = own ? bp.take<double>(F * 3u * m_pad) : X; C = bp.take<double>(F * 3u);
+            stage = bp.take<double>(per * N * 3u); XR = bp.take<double>(3u * n_pad); GR = bp.take<double>(1); CR = bp.take<double>(3); R = bp.take<double>(F * 9u);
+            for (double *&p : M2) p = bp.take<double>(3u * n_pad);
+            MM = bp.take<double>(3u * m_pad); part = bp.take<double>(slabs * 3u * w_pad); block_d2 = bp.take<double>(fin_n); d_change = bp.take<double>(1);
+            d_rmsf = bp.take<float>(m); d_frame = bp.take<float>(F); bp.take<char>(256);  // (slack)
+        }); s != ARP_OK) return s;
     HIP_TRY(hipMemcpyAsync(sel, job.sel, n * 4u, hipMemcpyHostToDevice, st));
     if (own) HIP_TRY(hipMemcpyAsync(msel, job.msel, m * 4u, hipMemcpyHostToDevice, st));
     for (uint64_t f0 = 0; f0 < F; f0 += per) {

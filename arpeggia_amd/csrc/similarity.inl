@@ -208,15 +208,15 @@ arp_status device_similarity(arp_context *ctx, const FreqJob &job, bool by_rows,
         for (uint64_t k = 0; k < M * M; k++) out->matrix[k] = counts ? 0u : 0x3F800000u;
         return ARP_OK;
     }
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, seg_align(M * M * 4u) + seg_align(M * 4u) + seg_align(by_rows ? 0u : F * WR * 4u)));
-    std::unique_ptr<char, void (*)(char *)> block_owner(block, [](char *p) { (void)hipFree(p); });
-    Bump bp{block};
-    uint32_t *d_out = bp.take<uint32_t>(M * M), *d_sizes = bp.take<uint32_t>(M);
+    uint32_t *d_out = nullptr, *d_sizes = nullptr, *wordsT = nullptr;
+    DevBlock block;
+    if ((s = block.carve([&](Bump &bp) {
+            d_out = bp.take<uint32_t>(M * M); d_sizes = bp.take<uint32_t>(M);
+            if (!by_rows) wordsT = bp.take<uint32_t>(F * WR);
+        })) != ARP_OK) return s;
     const uint32_t *A = dev.words;
     uint64_t K = W;
     if (!by_rows) {  // 3. the bit transpose: frames become the bit-rows
-        uint32_t *wordsT = bp.take<uint32_t>(F * WR);
         if ((s = bit_transpose_launch(st, dev.words, R, W, F, wordsT, WR)) != ARP_OK) return s;
         A = wordsT;
         K = WR;
@@ -252,11 +252,12 @@ arp_status device_bit_gram(arp_context *ctx, uint64_t rows, uint64_t n_bits, con
     arp_status s = similarity_cap_check(M, by_rows, cap_bytes);
     if (s != ARP_OK) return s;
     if (rows * W * 4u > (1ull << 31)) { set_error("bit gram: a bitmap of %llu rows x %llu bits is more than 2^31 bytes", (unsigned long long)rows, (unsigned long long)n_bits); return ARP_ERR_CAPACITY; }
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, seg_align(rows * W * 4u) + seg_align(M * M * 4u) + seg_align(M * 4u) + seg_align(by_rows ? 0u : n_bits * WR * 4u)));
-    std::unique_ptr<char, void (*)(char *)> block_owner(block, [](char *p) { (void)hipFree(p); });
-    Bump bp{block};
-    uint32_t *d_words = bp.take<uint32_t>(rows * W), *d_out = bp.take<uint32_t>(M * M), *d_sizes = bp.take<uint32_t>(M);
+    uint32_t *d_words = nullptr, *d_out = nullptr, *d_sizes = nullptr, *wordsT = nullptr;
+    DevBlock block;
+    if ((s = block.carve([&](Bump &bp) {
+            d_words = bp.take<uint32_t>(rows * W); d_out = bp.take<uint32_t>(M * M); d_sizes = bp.take<uint32_t>(M);
+            if (!by_rows) wordsT = bp.take<uint32_t>(n_bits * WR);
+        })) != ARP_OK) return s;
     HIP_TRY(hipMemcpyAsync(d_words, words, rows * W * 4u, hipMemcpyHostToDevice, st));
     if (n_bits & 31u) {
         hipLaunchKernelGGL(k_bit_mask_tail, dim3((uint32_t)((rows + 255u) / 256u)), dim3(256), 0, st, d_words, rows, W, (1u << (n_bits & 31u)) - 1u);
@@ -265,7 +266,6 @@ arp_status device_bit_gram(arp_context *ctx, uint64_t rows, uint64_t n_bits, con
     const uint32_t *A = d_words;
     uint64_t K = W;
     if (!by_rows) {
-        uint32_t *wordsT = bp.take<uint32_t>(n_bits * WR);
         if ((s = bit_transpose_launch(st, d_words, rows, W, n_bits, wordsT, WR)) != ARP_OK) return s;
         A = wordsT;
         K = WR;

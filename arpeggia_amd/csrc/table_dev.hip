@@ -659,10 +659,27 @@ __global__ __launch_bounds__(kSmallThreads) void k_table_small(const arp_pair *p
 
 // ---- host orchestration ----------------------------------------------------------------------------------------------
 namespace {
-struct Bump {  // typed pieces of one block
-    char *base; Carver c{};
-    template <class T> T *take(uint64_t count) { return reinterpret_cast<T *>(base + c.take(count * sizeof(T))); }
+struct DevBlock {  // a device allocation and its owner.  carve(layout): as many bytes as the layout plans, carved by it (host_common.h)
+    char *p = nullptr;
+    DevBlock() = default;
+    DevBlock(DevBlock &&o) noexcept : p(o.p) { o.p = nullptr; }  // (movable, hence not copyable)
+    DevBlock &operator=(DevBlock &&o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
+    ~DevBlock() { reset(); }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; }
+    arp_status alloc(uint64_t bytes) { reset(); HIP_TRY(hipMalloc((void **)&p, bytes)); return ARP_OK; }
+    template <class Layout> arp_status carve(Layout &&layout) {
+        const uint64_t bytes = planned_bytes(layout);
+        const arp_status s = alloc(bytes);
+        return s != ARP_OK ? s : carve_block(p, bytes, layout);
+    }
 };
+// The same for a slot of the context's scratch, which the context owns: plan, context_scratch, carve.
+template <class Layout> arp_status scratch_carve(arp_context *ctx, int slot, uint64_t pin_bytes, char **pin, Layout &&layout) {
+    const uint64_t bytes = planned_bytes(layout);
+    char *dev = nullptr;
+    const arp_status s = context_scratch(ctx, slot, bytes, pin_bytes, &dev, pin);
+    return s != ARP_OK ? s : carve_block(dev, bytes, layout);
+}
 struct StreamLapTimer : LapTimer {  // a lap ends when the stream has drained
     hipStream_t st;
     StreamLapTimer(const char *line_format, hipStream_t stream) : LapTimer(line_format), st(stream) {}
@@ -673,12 +690,11 @@ struct StreamLapTimer : LapTimer {  // a lap ends when the stream has drained
 arp_status device_planes(arp_context *ctx, const DevStructure &ds, std::vector<double> *planes, std::vector<uint8_t> *valid) {
     hipStream_t st = (hipStream_t)context_stream(ctx);
     const uint64_t nr = ds.n_res;
-    char *dev = nullptr, *pin = nullptr;
-    arp_status s = context_scratch(ctx, 0, 2 * seg_align(nr * sizeof(PlaneD)) + seg_align(nr) + 4096, 0, &dev, &pin);
-    if (s != ARP_OK) return s;
-    Bump b{dev};
-    PlaneD *ring = b.take<PlaneD>(nr), *sc = b.take<PlaneD>(nr);
-    uint8_t *v = b.take<uint8_t>(nr);
+    char *pin = nullptr;
+    PlaneD *ring = nullptr, *sc = nullptr; uint8_t *v = nullptr;
+    if (arp_status s = scratch_carve(ctx, 0, 0, &pin, [&](Bump &b) {
+            ring = b.take<PlaneD>(nr); sc = b.take<PlaneD>(nr); v = b.take<uint8_t>(nr); b.take<char>(4096);  // (slack)
+        }); s != ARP_OK) return s;
     if (nr) hipLaunchKernelGGL(k_fit_planes, dim3((uint32_t)((nr + 127) / 128)), dim3(128), 0, st, (uint32_t)nr, (const uint32_t *)ds.res_atom_ptr, (const uint32_t *)ds.res_atom_idx,
                                (const uint8_t *)ds.plane_bits, (const double *)ds.x, (const double *)ds.y, (const double *)ds.z, ring, sc, v);
     HIP_TRY(hipGetLastError());
@@ -704,10 +720,6 @@ struct RoutePublisher {
     TableRoute r;
     ~RoutePublisher() { std::lock_guard<std::mutex> lock(g_route_mu); g_route = r; }
 };
-struct DevBlock {  // a device allocation of one call
-    void *p = nullptr;
-    ~DevBlock() { if (p) (void)hipFree(p); }
-};
 }  // namespace
 TableRoute table_route_last() { std::lock_guard<std::mutex> lock(g_route_mu); return g_route; }
 
@@ -729,21 +741,30 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
     // each ring meets a handful of cations / rings; a call that finds more reserves what the counter reported and runs the ring kernels again, once
     uint64_t ring_rows_cap = 64 * n_rings + 1024;
     rt.ring_cap = (long long)ring_rows_cap;
-    uint64_t need = 2 * seg_align(nr * sizeof(PlaneD)) + seg_align(nr) + seg_align(n_rings * sizeof(RingEnt)) + seg_align(n_rings * sizeof(EntKey)) + seg_align(n_rings * 32) + 4096 + seg_align((n_pairs + 1) * 4) * 2 +
-                    seg_align(std::max(cub_scan, cub_sort_ent)) + seg_align(n_ent * 8) * 2 + seg_align(n_ent * 4) * 4 + seg_align(ring_rows_cap * 16);
-    char *dev = nullptr, *pin = nullptr;
+    char *pin = nullptr;
     const uint64_t pin_bytes = seg_align(n_rings * sizeof(RingEnt)) + seg_align(n_rings * sizeof(EntKey)) + 4096;
-    arp_status s = context_scratch(ctx, 0, need, pin_bytes, &dev, &pin);
-    if (s != ARP_OK) return s;
-    Bump b{dev};
+    RingPoint *ring_pts = nullptr; char *cub_tmp = nullptr; unsigned long long *ek0 = nullptr, *ek1 = nullptr; uint4 *ring_rows = nullptr;
+    uint32_t *counters = nullptr, *bits = nullptr, *first = nullptr, *eid0 = nullptr, *eid1 = nullptr, *eflag = nullptr;
+    arp_status s;
+    if ((s = scratch_carve(ctx, 0, pin_bytes, &pin, [&](Bump &b) {
+            ring_pts = b.take<RingPoint>(n_rings);
+            counters = b.take<uint32_t>(64);  // [0] rows, [1] tie runs too long for k_tie_fix, [2] largest entity rank
+            bits = b.take<uint32_t>(n_pairs + 1); first = b.take<uint32_t>(n_pairs + 1); cub_tmp = b.take<char>(std::max(cub_scan, cub_sort_ent));
+            ek0 = b.take<unsigned long long>(n_ent); ek1 = b.take<unsigned long long>(n_ent);
+            eid0 = b.take<uint32_t>(n_ent); eid1 = b.take<uint32_t>(n_ent); eflag = b.take<uint32_t>(n_ent);
+            ring_rows = b.take<uint4>(ring_rows_cap);  // the ring kernels' rows, until the row buffers exist (they are sized by BOTH row counts: one read-back)
+            b.take<char>(4096);  // slack
+        })) != ARP_OK) return s;
     // planes and entity ranks depend on the structure alone: computed by the first call, kept with the resident copy
     const bool derive = !ds.derived || ds.derived_n_ent != n_ent;
     if (derive) {
         if (ds.derived) { (void)hipFree(ds.derived); ds.derived = nullptr; }
-        const uint64_t bytes = 2 * seg_align(nr * sizeof(PlaneD)) + seg_align(nr) + seg_align(n_ent * 4) + 1024;
+        auto derived = [&](Bump &db) {
+            ds.ring_pl = db.take<PlaneD>(nr); ds.sc_pl = db.take<PlaneD>(nr); ds.pl_valid = db.take<uint8_t>(nr); ds.ent_rank = db.take<uint32_t>(n_ent); db.take<char>(1024);  // (slack)
+        };
+        const uint64_t bytes = planned_bytes(derived);
         HIP_TRY(hipMalloc((void **)&ds.derived, bytes));
-        Bump db{ds.derived};
-        ds.ring_pl = db.take<PlaneD>(nr); ds.sc_pl = db.take<PlaneD>(nr); ds.pl_valid = db.take<uint8_t>(nr); ds.ent_rank = db.take<uint32_t>(n_ent);
+        if ((s = carve_block(ds.derived, bytes, derived)) != ARP_OK) return s;
         ds.derived_n_ent = n_ent;
     }
     PlaneD *ring_pl = (PlaneD *)ds.ring_pl, *sc_pl = (PlaneD *)ds.sc_pl;
@@ -767,13 +788,7 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
             HIP_TRY(hipMemcpyAsync(ds.rings_block, pin, tot, hipMemcpyHostToDevice, st));
         }
     }
-    RingPoint *ring_pts = b.take<RingPoint>(n_rings);
-    uint32_t *counters = b.take<uint32_t>(64);  // [0] rows, [1] tie runs too long for k_tie_fix, [2] largest entity rank
-    uint32_t *bits = b.take<uint32_t>(n_pairs + 1), *first = b.take<uint32_t>(n_pairs + 1);
-    char *cub_tmp = b.take<char>(std::max(cub_scan, cub_sort_ent));
-    unsigned long long *ek0 = b.take<unsigned long long>(n_ent), *ek1 = b.take<unsigned long long>(n_ent);
-    uint32_t *eid0 = b.take<uint32_t>(n_ent), *eid1 = b.take<uint32_t>(n_ent), *eflag = b.take<uint32_t>(n_ent), *ent_rank = ds.ent_rank;
-    uint4 *ring_rows = b.take<uint4>(ring_rows_cap);  // the ring kernels' rows, until the row buffers exist (they are sized by BOTH row counts: one read-back)
+    uint32_t *ent_rank = ds.ent_rank;
     volatile uint32_t *counts_host = reinterpret_cast<volatile uint32_t *>(pin + pin_bytes - 64);  // pinned landing of that read-back
 
     auto grid = [](uint64_t items, uint32_t block) { return dim3((uint32_t)std::max<uint64_t>(1, (items + block - 1) / block)); };
@@ -867,7 +882,7 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
     DevBlock ring_rows_big;
     auto grow_ring_rows = [&](uint32_t reported) -> arp_status {
         if (ring_rows_big.p) { set_error("internal error: more ring rows than reserved (%u > %llu)", reported, (unsigned long long)ring_rows_cap); return ARP_ERR_HIP; }
-        HIP_TRY(hipMalloc(&ring_rows_big.p, (size_t)reported * sizeof(uint4)));
+        if (arp_status sg = ring_rows_big.alloc((uint64_t)reported * sizeof(uint4)); sg != ARP_OK) return sg;
         ring_rows = reinterpret_cast<uint4 *>(ring_rows_big.p); ring_rows_cap = reported; rt.ring_cap = (long long)reported;
         HIP_TRY(hipMemsetAsync(counters, 0, sizeof(uint32_t), st));  // (the ring-row counter alone)
         return ARP_OK;
@@ -875,13 +890,14 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
     if (small_try) {
         // ONE launch behind the ring kernels, the table written straight into the pinned landing block, one wait for the stream
         const uint64_t land = 16 + (uint64_t)kSmallRows * 32 + 256;
-        char *dev2 = nullptr, *pin2 = nullptr;
-        if ((s = context_scratch(ctx, 1, seg_align((uint64_t)kSmallRows * 16) + 4096, land, &dev2, &pin2)) != ARP_OK) return s;
+        char *pin2 = nullptr;
+        uint4 *small_rows = nullptr;
+        if ((s = scratch_carve(ctx, 1, land, &pin2, [&](Bump &b2) { small_rows = b2.take<uint4>(kSmallRows); b2.take<char>(4096); /* slack */ })) != ARP_OK) return s;
         SmallHeader head;
         for (;;) {  // (twice at the most: grow_ring_rows refuses a second time)
             if (n_rings && (s = launch_rings()) != ARP_OK) return s;
             hipLaunchKernelGGL(k_table_small, dim3(1), dim3(kSmallThreads), 0, st, pairs_dev, (uint32_t)n_pairs, (const uint4 *)ring_rows, n_rings ? (const uint32_t *)counters : (const uint32_t *)nullptr,
-                               (uint32_t)ring_rows_cap, reinterpret_cast<uint4 *>(dev2), (uint32_t)n, (const EntKey *)ds.ent_key, (const EntKey *)d_ring_keys, (const uint32_t *)ent_rank,
+                               (uint32_t)ring_rows_cap, small_rows, (uint32_t)n, (const EntKey *)ds.ent_key, (const EntKey *)d_ring_keys, (const uint32_t *)ent_rank,
                                (const uint32_t *)ds.chain_rank, (const uint32_t *)ds.model, (const uint32_t *)ds.model_rank, (const RingEnt *)d_rings, tb, (const uint32_t *)ds.atom_sc_src,
                                (const PlaneD *)sc_pl, (const uint8_t *)valid, pin2, lap.on ? reinterpret_cast<unsigned long long *>(pin2 + land - 128) : (unsigned long long *)nullptr);
             HIP_TRY(hipGetLastError());
@@ -936,21 +952,18 @@ arp_status device_table(arp_context *ctx, DevStructure &ds, const std::vector<Ri
     size_t cub_sort_rows = 0;
     (void)hipcub::DeviceRadixSort::SortPairs(nullptr, cub_sort_rows, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (const uint32_t *)nullptr,
                                              (uint32_t *)nullptr, (int)rows_cap, 0, 64);
-    const uint64_t need2 = seg_align(rows_cap * 16) + seg_align(rows_cap * 32 + 256) + seg_align(rows_cap * 8) * 2 + seg_align(rows_cap * 4) * 2 + seg_align(cub_sort_rows) + 4096;
-    char *dev2 = nullptr, *pin2 = nullptr;  // the row-sized buffers live in a scratch slot of their own: the first one must not move
-    if ((s = context_scratch(ctx, 1, need2, 2 * seg_align(rows_cap * 16) + 4096, &dev2, &pin2)) != ARP_OK) return s;
-    b = Bump{dev2};
-    pin = pin2;
+    // The row-sized buffers live in a scratch slot of their own: the first one must not move.  out_all is the finished table in ONE piece
+    // {rows, sc values, the tie-overflow word}: one copy fetches it
+    uint4 *rows = nullptr; char *out_all = nullptr, *cub_tmp2 = nullptr; unsigned long long *rk0 = nullptr, *rk1 = nullptr; uint32_t *perm0 = nullptr, *perm1 = nullptr;
+    if ((s = scratch_carve(ctx, 1, 2 * seg_align(rows_cap * 16) + 4096, &pin, [&](Bump &b2) {
+            rows = b2.take<uint4>(rows_cap); out_all = b2.take<char>(rows_cap * 32 + 256);
+            rk0 = b2.take<unsigned long long>(rows_cap); rk1 = b2.take<unsigned long long>(rows_cap);
+            perm0 = b2.take<uint32_t>(rows_cap); perm1 = b2.take<uint32_t>(rows_cap); cub_tmp2 = b2.take<char>(cub_sort_rows); b2.take<char>(4096);  // (slack)
+        })) != ARP_OK) return s;
     lap("ring rows + scratch");
-    // the finished table in ONE device block {rows, sc values, the tie-overflow word}: one copy fetches it
-    uint4 *rows = b.take<uint4>(rows_cap);
-    char *out_all = b.take<char>(rows_cap * 32 + 256);
     uint4 *out_rows = reinterpret_cast<uint4 *>(out_all);
     float4 *out_sc = reinterpret_cast<float4 *>(out_all + (size_t)n_rows * 16);
     uint32_t *out_flag = reinterpret_cast<uint32_t *>(out_all + (size_t)n_rows * 32);
-    unsigned long long *rk0 = b.take<unsigned long long>(rows_cap), *rk1 = b.take<unsigned long long>(rows_cap);
-    uint32_t *perm0 = b.take<uint32_t>(rows_cap), *perm1 = b.take<uint32_t>(rows_cap);
-    char *cub_tmp2 = b.take<char>(cub_sort_rows);
     if (n_pairs + n_ring_rows) hipLaunchKernelGGL(k_expand_rows, grid(n_pairs + n_ring_rows, 256), dim3(256), 0, st, pairs_dev, (uint32_t)n_pairs, (const uint32_t *)first, rows,
                                                   (uint32_t)rows_cap, (const uint4 *)ring_rows, n_ring_rows, n_atom_rows);  // (the ring rows behind the atom rows)
     // The sort: stable radix passes over row indices, least significant key first.  The entity ranks, interaction, chains and model go

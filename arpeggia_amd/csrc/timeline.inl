@@ -18,7 +18,7 @@ struct TimelineMarks {
     uint64_t W;
     uint32_t *err;                       // device error word: 1 = an item without a row, 2 = a frame outside the call
     // the ring and water-bridge items of one pass (allocated by the first pass with either, grown when a pass has more)
-    char *items = nullptr;
+    DevBlock items;
     uint64_t items_cap = 0;
 };
 
@@ -145,16 +145,16 @@ namespace {
 // the ring and water items' buffers inside marks->items
 struct TimelineItems { unsigned long long *keys; FreqVal *vals; uint32_t *frame, *counter; };
 arp_status timeline_items(TimelineMarks *mk, uint64_t cap, TimelineItems *it) {
-    if (cap > mk->items_cap) {
-        if (cap > 0x7FFFFFF0ull) { set_error("contact timelines: more than 2^31 ring and water items in one pass (lower freq_chunk_atoms)"); return ARP_ERR_CAPACITY; }
-        if (mk->items) { (void)hipFree(mk->items); mk->items = nullptr; mk->items_cap = 0; }
-        HIP_TRY(hipMalloc((void **)&mk->items, seg_align(cap * 8) + seg_align(cap * sizeof(FreqVal)) + seg_align(cap * 4) + seg_align(256)));
-        mk->items_cap = cap;
-    }
-    Bump bp{mk->items};
-    it->keys = bp.take<unsigned long long>(mk->items_cap); it->vals = bp.take<FreqVal>(mk->items_cap); it->frame = bp.take<uint32_t>(mk->items_cap);
-    it->counter = bp.take<uint32_t>(64);
-    return ARP_OK;
+    auto layout = [&](Bump &bp) {
+        it->keys = bp.take<unsigned long long>(mk->items_cap); it->vals = bp.take<FreqVal>(mk->items_cap); it->frame = bp.take<uint32_t>(mk->items_cap);
+        it->counter = bp.take<uint32_t>(64);
+    };
+    if (cap <= mk->items_cap) return carve_block(mk->items.p, planned_bytes(layout), layout);  // the block as it is
+    if (cap > 0x7FFFFFF0ull) { set_error("contact timelines: more than 2^31 ring and water items in one pass (lower freq_chunk_atoms)"); return ARP_ERR_CAPACITY; }
+    mk->items_cap = cap;
+    const arp_status s = mk->items.carve(layout);
+    if (s != ARP_OK) mk->items_cap = 0;
+    return s;
 }
 }  // namespace
 
@@ -205,7 +205,7 @@ arp_status timeline_mark_pass(hipStream_t st, TimelineMarks *mk, const FreqPassV
 // The device block of a timeline: the row keys, the bitmap, the five per-row results of k_timeline_stats and the error word of the marks.  It lives as
 // long as this object, so that a follower (similarity.inl) can go on from the bitmap.  block == nullptr: the job has no rows.
 struct TimelineDev {
-    std::unique_ptr<char, void (*)(char *)> block{nullptr, [](char *p) { (void)hipFree(p); }};
+    DevBlock block;
     unsigned long long *row_keys = nullptr;
     uint32_t *words = nullptr, *stat[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *err = nullptr;
 };
@@ -230,19 +230,16 @@ arp_status timeline_device(arp_context *ctx, const FreqJob &job, uint64_t cap_by
         return ARP_ERR_CAPACITY;
     }
     // 2. marks: the row keys back on the device, the zeroed bitmap, the five per-row results, the error word
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, seg_align(R * 8) + seg_align(need) + 5 * seg_align(R * 4) + seg_align(256)));
-    dev->block.reset(block);
-    Bump bp{block};
-    dev->row_keys = bp.take<unsigned long long>(R);
-    dev->words = bp.take<uint32_t>(R * W);
-    for (uint32_t *&p : dev->stat) p = bp.take<uint32_t>(R);
-    dev->err = bp.take<uint32_t>(64);
+    if ((s = dev->block.carve([&](Bump &bp) {
+            dev->row_keys = bp.take<unsigned long long>(R);
+            dev->words = bp.take<uint32_t>(R * W);
+            for (uint32_t *&p : dev->stat) p = bp.take<uint32_t>(R);
+            dev->err = bp.take<uint32_t>(64);
+        })) != ARP_OK) return s;
     HIP_TRY(hipMemcpyAsync(dev->row_keys, rows->key.data(), R * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(dev->words, 0, need, st));
     HIP_TRY(hipMemsetAsync(dev->err, 0, 4, st));
     TimelineMarks mk{dev->row_keys, (uint32_t)R, (uint32_t)F, dev->words, W, dev->err};
-    struct FreeItems { TimelineMarks *m; ~FreeItems() { if (m->items) (void)hipFree(m->items); } } items_owner{&mk};
     FreqRowsHost none;
     if ((s = freq_sweep(ctx, job, &none, &mk)) != ARP_OK) return s;
     lap("marks");

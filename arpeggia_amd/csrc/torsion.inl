@@ -156,26 +156,19 @@ arp_status device_torsions(arp_context *ctx, const TorsionJob &job, TorsionOut *
     // the route of the maps: LDS tables where they fit, matched global adds where not
     int route = job.hist2_route == 0 ? 1 : job.hist2_route;
     if (route == 1 && cells * 4u > kTorsionLdsBytes) route = 2;
-    uint64_t per = std::min<uint64_t>(F, std::max<uint64_t>(1, (job.chunk_atoms ? job.chunk_atoms : kFreqAutoAtoms) / std::max<uint64_t>(N, 1)));
+    uint64_t per = frames_per_pass(job.chunk_atoms, N, F);
     per = std::min<uint64_t>(per, std::max<uint64_t>(1, kTorsionPassSamples / std::max(D, std::max<uint64_t>(P, 1))));
     const uint64_t slabs = (F + kTorsionSlab - 1u) / kTorsionSlab;
     const uint64_t chunk = std::max<uint64_t>(kTorsionStatsFrames, (F + 65534u) / 65535u), chunks = (F + chunk - 1u) / chunk;
-    char *block = nullptr;
-    HIP_TRY(hipMalloc((void **)&block, seg_align(per * N * 24u) + seg_align(D * 16u) + seg_align(std::max<uint64_t>(P, 1) * 12u) + seg_align(per * D * 16u) + seg_align(per * D * 2u) +
-                                           seg_align(per * D * 4u) + seg_align(F * D) + seg_align(slabs * D * 16u) + seg_align(D * 16u) + seg_align(D * 24u) +
-                                           seg_align(std::max<uint64_t>(D * B, 1) * 4u) + seg_align(std::max<uint64_t>(cells, 1) * 4u) + 256));
-    std::unique_ptr<char, void (*)(char *)> block_owner(block, [](char *p) { (void)hipFree(p); });
-    Bump bp{block};
-    double *stage = bp.take<double>(per * N * 3u);
-    uint4 *quads = bp.take<uint4>(D);
-    uint32_t *pairs = bp.take<uint32_t>(std::max<uint64_t>(P, 1) * 3u);
-    double2 *cs = bp.take<double2>(per * D);
-    uint16_t *bins = bp.take<uint16_t>(per * D);
-    float *ang = bp.take<float>(per * D);
-    uint8_t *states = bp.take<uint8_t>(F * D);
-    double2 *part = bp.take<double2>(slabs * D);
-    double *sums = bp.take<double>(D * 2u);
-    uint32_t *stats = bp.take<uint32_t>(D * 6u), *hist = bp.take<uint32_t>(std::max<uint64_t>(D * B, 1)), *hist2 = bp.take<uint32_t>(std::max<uint64_t>(cells, 1));
+    double *stage = nullptr, *sums = nullptr; uint4 *quads = nullptr; uint32_t *pairs = nullptr, *stats = nullptr, *hist = nullptr, *hist2 = nullptr;
+    double2 *cs = nullptr, *part = nullptr; uint16_t *bins = nullptr; float *ang = nullptr; uint8_t *states = nullptr;
+    DevBlock block;
+    if (arp_status s = block.carve([&](Bump &bp) {
+            stage = bp.take<double>(per * N * 3u); quads = bp.take<uint4>(D); pairs = bp.take<uint32_t>(std::max<uint64_t>(P, 1) * 3u);
+            cs = bp.take<double2>(per * D); bins = bp.take<uint16_t>(per * D); ang = bp.take<float>(per * D);
+            states = bp.take<uint8_t>(F * D); part = bp.take<double2>(slabs * D); sums = bp.take<double>(D * 2u);
+            stats = bp.take<uint32_t>(D * 6u); hist = bp.take<uint32_t>(std::max<uint64_t>(D * B, 1)); hist2 = bp.take<uint32_t>(std::max<uint64_t>(cells, 1)); bp.take<char>(256);  // (slack)
+        }); s != ARP_OK) return s;
     HIP_TRY(hipMemcpyAsync(quads, job.quads, D * 16u, hipMemcpyHostToDevice, st));
     if (want_hist2) HIP_TRY(hipMemcpyAsync(pairs, job.pairs, P * 12u, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(stats, 0, D * 24u, st));
