@@ -4,6 +4,9 @@ k_dssp_pack / k_dssp_sweep / k_dssp_assign against the host twin arp_dssp_host o
 the definition, so the two must agree exactly): the two files, jittered frames, the built helices, R = 1 .. 5 and R around the sweep's tile; identical bytes
 from call to call and from pass size to pass size; rigid motion; the identities between the outputs; the models of a structure as frames; errors; the command
 line.  Expected values never come from the call under test, except where bit-equality between two calls is the property.
+
+Inputs ON the thresholds (one ulp either side of E = -0.5, |CA - CA| = 9, |C - N| = 2.5, a distance of 0.5, kappa = 70 degrees) and features placed on the sweep's
+tiles of 64 and the assignment's stride of 256 are in tests/test_dssp_edge_gpu.py (cases: tests/dssp_edge_cases.py).
 """
 from __future__ import annotations
 

@@ -6,6 +6,9 @@ f32 angles and the order of the sums): the two files, jittered frames, D around 
 identical bytes from call to call and from pass size to pass size, with the only transition on a pass or slab boundary; both routes of the Ramachandran
 maps and the contention case; the identities between the outputs; rigid motion; the models of a structure as frames; errors; the command line.  Expected
 values never come from the call under test, except where bit-equality between two calls is the property.
+
+The decision edges (exact angles on bin edges, subnormal sines, c = -0.5 one ulp at a time), more than one chunk of k_torsion_stats and the partial waves of
+k_torsion_hist2_match are in tests/test_torsion_edge_gpu.py (cases: tests/torsion_edge_cases.py).
 """
 from __future__ import annotations
 
